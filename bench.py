@@ -179,6 +179,35 @@ def stream_read_ceiling(torch, gib: float = 4.0):
     return best
 
 
+DUMP_QUERIES = 1 << 19    # --dump-outputs: queries per run, all ranks together (12 float64 arrays: 50 MB)
+DUMP_SEED = 0xB10D5       # the fixed sample of queries a dump holds when the table has more than that
+
+
+def dump_outputs(directory, engine, torch, np, out, n_queries, q_offset, rank, world):
+    """The records of the last timed step (what a caller of blu_consensus_run receives) as DIR/<field>.npy, float64: every
+    field of blu_result as its exact value, level_mask as its two 32-bit halves, and query_index (global query number).
+    A table with more than DUMP_QUERIES queries gives a seeded sample of them, the same one for the same arguments.  Ranks
+    of an N > 1 run write <field>_rank<r>.npy, each with its share of DUMP_QUERIES."""
+    fields = [f for f in engine.RESULT_DTYPE.names if f != "level_mask"] + ["level_mask_lo", "level_mask_hi", "query_index"]
+    cap = DUMP_QUERIES // world
+    if n_queries <= cap:
+        idx = np.arange(n_queries, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED + rank).choice(n_queries, size=cap, replace=False)).astype(np.int64)
+    torch.cuda.synchronize()
+    rec = engine.records_from_tensor(out.view(-1, 32)[torch.from_numpy(idx).to(out.device)].reshape(-1))
+    arrays = {f: rec[f].astype(np.float64) for f in engine.RESULT_DTYPE.names if f != "level_mask"}
+    arrays["level_mask_lo"] = (rec["level_mask"] & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    arrays["level_mask_hi"] = (rec["level_mask"] >> np.uint64(32)).astype(np.float64)
+    arrays["query_index"] = (idx + q_offset).astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for f in fields:
+        np.save(os.path.join(directory, f + suffix + ".npy"), arrays[f])
+    log(f"[bench] dumped {len(idx)} of {n_queries} queries' records ({len(fields)} arrays, "
+        f"{len(fields) * 8 * len(idx) / 1e6:.1f} MB) to {directory}")
+
+
 def time_pack(engine, torch, np, eng_tax, cols, wide: bool, n_hits: int, reps: int = 5):
     """blu_hits_pack / blu_hits_pack64 on the timed table's columns, HIP events on the launch stream: what a caller that
     holds SoA columns pays once per table before the packed layout's runs.  Bytes: the four 4-byte columns (f64 layout:
@@ -364,9 +393,14 @@ def main():
     ap.add_argument("--no-parity-gate", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary measurements (N = 1: the other workloads of SECONDARY; N > 1: the weak-scaling figure)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records of the last one as DIR/<field>.npy (float64; a fixed seeded "
+                         "sample of 2^19 queries when the table has more, about 50 MB in all)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # Launched without a launcher: start the N rank processes here.  This parent makes no GPU call of any kind before
         # (or after) it spawns them — fresh children, no re-exec of a process that has touched the card.
@@ -504,6 +538,8 @@ def main():
 
     # ---- timed region (the headline)
     elapsed, kernel_ms = timed(run_step)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, engine, torch, np, out, Q, query_range(scaling)[0], rank, world)
 
     # ---- parity gate (rank 0): the records the LAST TIMED STEP wrote, for a sample of the queries, == the columnar oracle.
     # No line is printed unless it passes.  It runs after the timed region, not before it: the oracle legs keep the GPU
