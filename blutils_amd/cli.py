@@ -19,14 +19,20 @@ writes the binary cache of a taxonomies file (not in the reference CLI; pass CAC
         --strategy S [...]
 
 = `blu blastn run-with-consensus` (commands.rs:24-103): `blastn` itself stays an external process (blutils_amd/blast.py).
-The DB builders are not part of this engine."""
+
+    python -m blutils_amd.cli build-db blu BLAST_DATABASE_PATH TAXDUMP_DIRECTORY_PATH OUTPUT_FILE_PATH
+        [-d] [-s TAXID]... [-r RANK=NEW]... [--accessions-file FILE] [--blastdbcmd EXE] [--device N]
+
+= `blu build-db blu` (ports/cli/src/cmds/db_builder/commands.rs:22-77): the taxonomies database built on the GPU
+(blutils_amd/taxdb.py, csrc/taxdb_gpu.hip); `blastdbcmd` stays an external process.  The qiime2 and kraken2 converters
+are not part of this engine."""
 from __future__ import annotations
 
 import argparse
 import os
 import sys
 
-from . import blast, pipeline, tabular
+from . import blast, pipeline, tabular, taxdb
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -68,11 +74,43 @@ def build_parser() -> argparse.ArgumentParser:
     bt.add_argument("blu_result", nargs="?", default="-")
     bt.add_argument("-o", "--output-file")
     bt.add_argument("-i", "--input-format", default="json", choices=["json", "jsonl", "yaml"])
+    bd = sub.add_parser("build-db").add_subparsers(dest="sub", required=True)
+    db = bd.add_parser("blu", help="the taxonomies database (*.blutils.json) from an NCBI taxdump and a BLAST database")
+    db.add_argument("blast_database_path")
+    db.add_argument("taxdump_directory_path")
+    db.add_argument("output_file_path")
+    db.add_argument("-d", "--drop-non-linnaean-taxonomies", action="store_true")
+    db.add_argument("-s", "--skip-taxid", type=_u64, action="append")
+    db.add_argument("-r", "--replace-rank", action="append")
+    db.add_argument("--accessions-file", help="the text `blastdbcmd -entry all -db DB -outfmt \"%%a  %%T  %%o\"` prints; "
+                                              "no blastdbcmd run and no database check (not in the reference CLI)")
+    db.add_argument("--blastdbcmd", default="blastdbcmd", help="blastdbcmd executable (not in the reference CLI)")
+    db.add_argument("--device", type=int, default=0, help="HIP device ordinal (not in the reference CLI)")
     cd = sub.add_parser("cache-db", help="binary cache of a *.blutils.json (pass it as --tax-file afterwards)")
     cd.add_argument("tax_file")
     cd.add_argument("cache_file")
     cd.add_argument("-u", "--use-taxid", action="store_true")
     return ap
+
+
+def _u64(text: str) -> int:
+    """clap's u64 value parser"""
+    v = int(text)
+    if not 0 <= v < (1 << 64):
+        raise argparse.ArgumentTypeError(f"invalid u64: {text!r}")
+    return v
+
+
+def _build_db(args) -> int:
+    """ports/cli/src/cmds/db_builder/mod.rs:12-44"""
+    try:
+        replace = taxdb.parse_replace_rank(args.replace_rank)
+        taxdb.build_ref_db_from_ncbi_files(args.blast_database_path, args.taxdump_directory_path, args.output_file_path,
+                                           args.skip_taxid, replace, args.drop_non_linnaean_taxonomies,
+                                           args.accessions_file, args.blastdbcmd, args.device)
+    except (taxdb.TaxdbError, blast.BlastError) as e:
+        raise SystemExit(str(e))
+    return 0
 
 
 def _run_with_consensus(args) -> int:
@@ -107,6 +145,8 @@ def _run_with_consensus(args) -> int:
 
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
+    if args.cmd == "build-db":
+        return _build_db(args)
     if args.cmd == "cache-db":
         pipeline.build_db_cache(args.tax_file, args.cache_file, args.use_taxid)
         return 0

@@ -46,6 +46,7 @@
 #include "blu_consensus.h"
 #include "blu_internal.h"
 #include "ingest.h"
+#include "ingest_prims.h"
 
 namespace blu {
 namespace {
@@ -744,6 +745,31 @@ struct DeviceArena {
     ~DeviceArena() { free_all(); }
 };
 
+// ---- the ingest's pieces for the taxonomies-database builder (ingest_prims.h): host wrappers, the kernels stay here
+uint64_t line_tiles(uint64_t size) { return (size + TILE_BYTES - 1) / TILE_BYTES; }
+hipError_t line_count_tiles(const unsigned char* d_text, uint64_t size, uint32_t* d_tile) {
+    const uint64_t n_tiles = line_tiles(size);
+    if (n_tiles) hipLaunchKernelGGL(count_newlines, dim3((unsigned)n_tiles), dim3(TILE_THREADS), 0, 0, (const uint4*)d_text, size, d_tile);
+    return hipGetLastError();
+}
+hipError_t line_write_starts(const unsigned char* d_text, uint64_t size, const uint32_t* d_tile_base, uint64_t* d_line) {
+    const uint64_t n_tiles = line_tiles(size);
+    if (n_tiles) hipLaunchKernelGGL(write_line_starts, dim3((unsigned)n_tiles), dim3(TILE_THREADS), 0, 0, (const uint4*)d_text, size, d_tile_base, d_line);
+    return hipGetLastError();
+}
+size_t scan_tmp_bytes_u32(size_t n) { return scan_tmp_bytes<uint32_t>(n); }
+size_t scan_tmp_bytes_u64(size_t n) { return scan_tmp_bytes<unsigned long long>(n); }
+hipError_t exclusive_scan_u32(const uint32_t* in, uint32_t* out, size_t n, void* tmp) { return exclusive_scan_dev<uint32_t>(in, out, n, tmp); }
+hipError_t exclusive_scan_u64(const unsigned long long* in, unsigned long long* out, size_t n, void* tmp) {
+    return exclusive_scan_dev<unsigned long long>(in, out, n, tmp);
+}
+size_t radix_table_words(uint32_t n) { return (size_t)2 * 256 * (((size_t)n + RS_BLOCK - 1) / RS_BLOCK); }
+size_t radix_scan_tmp_bytes(uint32_t n) { return scan_tmp_bytes<uint32_t>((size_t)256 * (((size_t)n + RS_BLOCK - 1) / RS_BLOCK)); }
+hipError_t radix_sort_pairs(uint32_t** keys, uint32_t** keys_alt, uint32_t** vals, uint32_t** vals_alt, uint32_t n, int bits,
+                            uint32_t* table, void* scan_tmp) {
+    return radix_sort_pairs_dev(keys, keys_alt, vals, vals_alt, n, bits, table, scan_tmp);
+}
+
 // The text goes page cache -> pinned staging -> HBM without ever being mapped into the process: three reader threads,
 // each with two pinned slots, pread() a piece while the previous one is on the wire.  What the parts cost on a box
 // (scripts/probe/upload_probe.hip, 6.7 GB): the copies alone 0.12 s (56 GB/s, the PCIe rate; one stream carries 50 of it),
@@ -753,7 +779,7 @@ struct DeviceArena {
 // null stream, which the kernels that follow need anyway (in order on one queue: a slot's event still says when it is free).
 // Mapping the file and handing it to hipMemcpy moves the bytes as fast (the runtime pins the page-cache pages) but
 // costs 0.06 s to populate and 0.07-0.10 s to unmap 6.7 GB of page table.
-static int upload_file(int fd, size_t size, unsigned char* d_text, int device, std::string* err) {
+int upload_file(int fd, size_t size, unsigned char* d_text, int device, std::string* err) {
     unsigned nt = 3;
     if (const char* env = getenv("BLU_UPLOAD_THREADS")) nt = (unsigned)atoi(env);
     const size_t piece = 8u << 20, n_pieces = (size + piece - 1) / piece;
@@ -1233,11 +1259,10 @@ done:
 
 // Device -> pageable host memory in 8 MiB pieces by a pool of host threads: the first touch of the fresh destination pages
 // (and the runtime's pinning of them) costs more than the transfer, and it parallelises.
-struct D2HPiece { char* dst; const char* src; size_t bytes; };
-static void d2h_add(std::vector<D2HPiece>& v, void* dst, const void* src, size_t bytes, size_t piece = 8u << 20) {
+void d2h_add(std::vector<D2HPiece>& v, void* dst, const void* src, size_t bytes, size_t piece) {
     for (size_t o = 0; o < bytes; o += piece) v.push_back({(char*)dst + o, (const char*)src + o, std::min(piece, bytes - o)});
 }
-static hipError_t d2h_parallel(const std::vector<D2HPiece>& pieces, int device, unsigned max_threads = 16) {
+hipError_t d2h_parallel(const std::vector<D2HPiece>& pieces, int device, unsigned max_threads) {
     if (pieces.empty()) return hipSuccess;
     unsigned nt = std::thread::hardware_concurrency();
     if (const char* env = getenv("BLU_INGEST_THREADS")) nt = (unsigned)atoi(env);

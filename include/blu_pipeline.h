@@ -120,6 +120,51 @@ int blu_last_ingest_path(void);
  * truncated or altered one fails its checksum (BLU_ERR_PARSE). */
 int blu_db_cache_build(const char* taxonomies_file, int use_taxid, const char* cache_file);
 
+/* `blu build-db blu` (core/src/use_cases/build_blutils_db_from_ncbi_files/, build_taxonomy_database.rs:49-498) on the GPU:
+ * the NCBI taxdump files and the text `blastdbcmd -entry all -db DB -outfmt "%a  %T  %o"` prints -> <output_stem>.blutils.json
+ * (serde_json::to_string_pretty of TaxonomiesMap, taxonomies in ascending taxid) and <output_stem>.non-mapped.tsv (taxid, tab,
+ * deleted | merged | unknown; ascending taxid; removed and created again on every call).  DESIGN.md "Taxonomies database
+ * builder" has the rules.  Errors name the file and the 1-based line (blu_last_error); there is no CPU path. */
+#define BLU_TAXDB_DEFAULT_VERSION "8.3.1"   /* blutilsVersion when blutils_version is NULL (blutils_amd/blast.py BLUTILS_VERSION) */
+typedef struct blu_taxdb_desc {
+    const char* nodes_path;        /* nodes.dmp */
+    const char* names_path;        /* names.dmp */
+    const char* lineage_path;      /* taxidlineage.dmp */
+    const char* merged_path;       /* merged.dmp */
+    const char* delnodes_path;     /* delnodes.dmp */
+    const char* accessions_path;   /* the blastdbcmd listing */
+    const uint64_t* skip_taxids;   /* -s, in command-line order (written to ignoreTaxids as given) */
+    uint64_t n_skip;
+    int32_t has_skip;              /* 0: ignoreTaxids is null */
+    int32_t has_replace;           /* 0: replaceRank is null */
+    const char* const* replace_from;   /* -r FROM=TO pairs, in command-line order (a repeated FROM keeps its last TO) */
+    const char* const* replace_to;
+    uint64_t n_replace;
+    int32_t drop_non_linnaean;     /* -d */
+    int32_t device;                /* HIP device ordinal */
+    const char* source_database;   /* sourceDatabase, as given */
+    const char* blutils_version;   /* NULL = BLU_TAXDB_DEFAULT_VERSION */
+    const char* output_stem;       /* <parent>/<stem> after PathBuf::set_extension("json") (rs:240-270) */
+} blu_taxdb_desc;
+
+typedef struct blu_taxdb_stats {
+    uint64_t n_nodes;              /* nodes.dmp lines read (UTF-8) */
+    uint64_t n_names;              /* scientific-name lines of names.dmp */
+    uint64_t n_lineage_tokens;     /* ancestor ids in taxidlineage.dmp */
+    uint64_t n_accession_lines;
+    uint64_t n_distinct_taxids;
+    uint64_t n_mapped;             /* entries of a node */
+    uint64_t n_mapped_merged;      /* entries through merged.dmp */
+    uint64_t n_deleted, n_merged_missing, n_unknown;   /* TSV lines */
+    uint64_t n_dropped;            /* leaves dropped by -d */
+    uint64_t n_unmapped_ancestors; /* ancestors without a node (the reference's warnings) */
+    uint64_t n_nonascii_names;     /* scientific names with bytes >= 0x80 (slug parity unpinned there) */
+    uint64_t input_bytes, doc_bytes, tsv_bytes;
+    double t_upload_ms, t_parse_ms, t_tables_ms, t_group_ms, t_assemble_ms, t_render_ms, t_write_ms;
+} blu_taxdb_stats;
+
+int blu_taxdb_build(const blu_taxdb_desc* desc, blu_taxdb_stats* stats);
+
 /* CustomTaxon::from_file (domain/dtos/taxon.rs:28-66): .yaml or .json with the eight cutoff fields. */
 int blu_custom_taxon_from_file(const char* path, blu_cutoff_config* cfg);
 
