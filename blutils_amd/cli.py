@@ -24,15 +24,23 @@ writes the binary cache of a taxonomies file (not in the reference CLI; pass CAC
         [-d] [-s TAXID]... [-r RANK=NEW]... [--accessions-file FILE] [--blastdbcmd EXE] [--device N]
 
 = `blu build-db blu` (ports/cli/src/cmds/db_builder/commands.rs:22-77): the taxonomies database built on the GPU
-(blutils_amd/taxdb.py, csrc/taxdb_gpu.hip); `blastdbcmd` stays an external process.  The qiime2 and kraken2 converters
-are not part of this engine."""
+(blutils_amd/taxdb.py, csrc/taxdb_gpu.hip); `blastdbcmd` stays an external process.
+
+    python -m blutils_amd.cli build-db kraken2 BLAST_DATABASE_PATH -o OUTPUT_DIRECTORY
+        [--listing-file FILE] [--blastdbcmd EXE] [--device N]
+    python -m blutils_amd.cli build-db qiime2 TAXONOMIES_DATABASE_PATH OUTPUT_TAXONOMIES_FILE BLAST_DATABASE_PATH
+        OUTPUT_SEQUENCES_FILE [-u] [--listing-file FILE] [--blastdbcmd EXE] [--device N]
+
+= `blu build-db kraken2` / `blu build-db qiime2` (commands.rs:11-20): the sequences of `blastdbcmd -entry all` rewritten on
+the GPU as they stream from the pipe (blutils_amd/seqdb.py, csrc/seqdb_gpu.hip); the QIIME taxonomy TSV is rendered on the
+host from a `*.blutils.json` that `build-db blu` wrote."""
 from __future__ import annotations
 
 import argparse
 import os
 import sys
 
-from . import blast, pipeline, tabular, taxdb
+from . import blast, pipeline, seqdb, tabular, taxdb
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -86,6 +94,24 @@ def build_parser() -> argparse.ArgumentParser:
                                               "no blastdbcmd run and no database check (not in the reference CLI)")
     db.add_argument("--blastdbcmd", default="blastdbcmd", help="blastdbcmd executable (not in the reference CLI)")
     db.add_argument("--device", type=int, default=0, help="HIP device ordinal (not in the reference CLI)")
+    kr = bd.add_parser("kraken2", help="library.fna and prelim_map.txt for Kraken 2 from a BLAST database",
+                       description="OUTPUT_DIRECTORY is removed first, whether it is a directory or a file, and created "
+                                   "again, before the database is checked (as the reference does).")
+    kr.add_argument("blast_database_path")
+    kr.add_argument("-o", "--output-directory", required=True,
+                    help="removed if it exists (directory or file), then created; gets library.fna and prelim_map.txt")
+    qi = bd.add_parser("qiime2", help="QIIME 2 taxonomy TSV and sequences from a *.blutils.json and a BLAST database")
+    qi.add_argument("taxonomies_database_path")
+    qi.add_argument("output_taxonomies_file")
+    qi.add_argument("blast_database_path")
+    qi.add_argument("output_sequences_file")
+    qi.add_argument("-u", "--use-taxid", action="store_true")
+    for sp, fmt in ((kr, seqdb.KRAKEN2_OUTFMT), (qi, seqdb.QIIME2_OUTFMT)):
+        sp.add_argument("--listing-file", help=f"the text `blastdbcmd -entry all -db DB -outfmt \"{fmt}\"` prints; "
+                                               "no blastdbcmd run and no database check (not in the reference CLI)"
+                                               .replace("%", "%%"))
+        sp.add_argument("--blastdbcmd", default="blastdbcmd", help="blastdbcmd executable (not in the reference CLI)")
+        sp.add_argument("--device", type=int, default=0, help="HIP device ordinal (not in the reference CLI)")
     cd = sub.add_parser("cache-db", help="binary cache of a *.blutils.json (pass it as --tax-file afterwards)")
     cd.add_argument("tax_file")
     cd.add_argument("cache_file")
@@ -104,11 +130,20 @@ def _u64(text: str) -> int:
 def _build_db(args) -> int:
     """ports/cli/src/cmds/db_builder/mod.rs:12-44"""
     try:
+        if args.sub == "kraken2":
+            seqdb.build_kraken_db_from_ncbi_files(args.blast_database_path, args.output_directory, args.listing_file,
+                                                  args.blastdbcmd, device=args.device)
+            return 0
+        if args.sub == "qiime2":
+            seqdb.build_qiime_db_from_blutils_db(args.taxonomies_database_path, args.output_taxonomies_file,
+                                                 args.blast_database_path, args.output_sequences_file, args.use_taxid,
+                                                 args.listing_file, args.blastdbcmd, device=args.device)
+            return 0
         replace = taxdb.parse_replace_rank(args.replace_rank)
         taxdb.build_ref_db_from_ncbi_files(args.blast_database_path, args.taxdump_directory_path, args.output_file_path,
                                            args.skip_taxid, replace, args.drop_non_linnaean_taxonomies,
                                            args.accessions_file, args.blastdbcmd, args.device)
-    except (taxdb.TaxdbError, blast.BlastError) as e:
+    except (taxdb.TaxdbError, blast.BlastError, seqdb.SeqdbError) as e:
         raise SystemExit(str(e))
     return 0
 

@@ -36,6 +36,7 @@
 #include "blu_pipeline.h"
 #include "ingest.h"
 #include "ingest_prims.h"
+#include "text_dev.h"
 
 namespace blu {
 namespace {
@@ -58,52 +59,6 @@ enum : uint32_t { E_FIELDS = 1, E_NUMBER = 2, E_RANGE = 3, E_PIECES = 4, E_TAXID
 enum : uint8_t { S_MAPPED = 0, S_MERGED_MAPPED = 1, S_DELETED = 2, S_MERGED_MISSING = 3, S_UNKNOWN = 4, S_DROPPED = 5, S_BEYOND = 6 };
 
 constexpr uint32_t NULL4 = 'n' | ('u' << 8) | ('l' << 16) | ('l' << 24);   // "null" as a little-endian word
-
-__device__ __forceinline__ bool is_ws(uint32_t c) { return c == ' ' || (c >= 9 && c <= 13); }   // str::trim, ASCII range
-
-// visit bytes of text[a, b) through aligned 16-byte loads (the text is padded past its end); f returns false to stop
-template <class F>
-__device__ __forceinline__ void for_bytes(const unsigned char* __restrict__ text, uint64_t a, uint64_t b, F&& f) {
-    for (uint64_t w = a & ~15ull; w < b; w += 16) {
-        const uint4 v = *reinterpret_cast<const uint4*>(text + w);
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const uint64_t p = w + k;
-            if (p < a || p >= b) continue;
-            const uint32_t x = (k & 8) ? ((k & 4) ? v.w : v.z) : ((k & 4) ? v.y : v.x);   // (no array: stays in registers unrolled or not)
-            if (!f((x >> (8 * (k & 3))) & 0xFFu, p)) return;
-        }
-    }
-}
-
-// str::from_utf8 on a line (Rust rejects overlong forms, surrogates and code points above U+10FFFF, as this does)
-__device__ __forceinline__ bool utf8_valid(const unsigned char* __restrict__ text, uint64_t a, uint64_t b) {
-    uint32_t need = 0, lo = 0x80, hi = 0xBF;
-    bool ok = true;
-    for_bytes(text, a, b, [&](uint32_t c, uint64_t) {
-        if (need == 0) {
-            if (c < 0x80) return true;
-            if (c >= 0xC2 && c <= 0xDF) { need = 1; lo = 0x80; hi = 0xBF; }
-            else if (c == 0xE0) { need = 2; lo = 0xA0; hi = 0xBF; }
-            else if ((c >= 0xE1 && c <= 0xEC) || c == 0xEE || c == 0xEF) { need = 2; lo = 0x80; hi = 0xBF; }
-            else if (c == 0xED) { need = 2; lo = 0x80; hi = 0x9F; }
-            else if (c == 0xF0) { need = 3; lo = 0x90; hi = 0xBF; }
-            else if (c >= 0xF1 && c <= 0xF3) { need = 3; lo = 0x80; hi = 0xBF; }
-            else if (c == 0xF4) { need = 3; lo = 0x80; hi = 0x8F; }
-            else { ok = false; return false; }
-            return true;
-        }
-        if (c < lo || c > hi) { ok = false; return false; }
-        lo = 0x80; hi = 0xBF; --need;
-        return true;
-    });
-    return ok && need == 0;
-}
-
-__device__ __forceinline__ void trim(const unsigned char* __restrict__ text, uint64_t& a, uint64_t& b) {
-    while (a < b && is_ws(text[a])) ++a;
-    while (b > a && is_ws(text[b - 1])) --b;
-}
 
 // signed decimal of a field (tabs inside removed first, load_dump_file.rs:52); false if not a number or beyond i64
 __device__ __forceinline__ bool parse_i64(const unsigned char* __restrict__ text, uint64_t a, uint64_t b, bool skip_tabs, long long* out) {

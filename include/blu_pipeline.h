@@ -165,6 +165,49 @@ typedef struct blu_taxdb_stats {
 
 int blu_taxdb_build(const blu_taxdb_desc* desc, blu_taxdb_stats* stats);
 
+/* `blu build-db kraken2` and the sequence half of `blu build-db qiime2` on the GPU
+ * (core/src/use_cases/build_kraken_db_from_ncbi_files/, build_qiime_db_from_blutils_db/mod.rs:90-150): the text
+ * `blastdbcmd -entry all -db DB -outfmt "%a  %T  %s"` (kraken2) or `"%a  %T  %o  %s"` (qiime2) prints, streamed in chunks
+ * from a file descriptor (the pipe from blastdbcmd) or a path, rewritten on the device and written as it goes.
+ *   kraken2: fna_path gets `>kraken:taxid|TAXID|ACC\n` + the sequence upper-cased in 80-column lines + `\n` per line;
+ *            map_path gets `TAXID\tkraken:taxid|N|ACC\tN\n` per line (N: the taxid as usize), written only on success.
+ *   qiime2:  fna_path gets `>TAXID-OID-ACC\nSEQUENCE\n` per line.
+ * Output stops quietly before the first line that is not UTF-8 (the reference's read_line loop ends there); stats
+ * `invalid_utf8_line` names it.  A line with too few pieces, a kraken2 taxid that is not a usize or a kraken2 sequence
+ * with a byte >= 0x80 is an error (blu_last_error names the input and the 1-based line).  DESIGN.md "Sequence export". */
+#define BLU_SEQDB_KRAKEN2 0
+#define BLU_SEQDB_QIIME2 1
+#define BLU_SEQDB_DEFAULT_CHUNK (1ull << 30)   /* chunk_bytes = 0 */
+typedef struct blu_seqdb_desc {
+    int32_t format;                /* BLU_SEQDB_KRAKEN2 | BLU_SEQDB_QIIME2 */
+    int32_t input_fd;              /* >= 0: read this descriptor (not closed); -1: open input_path */
+    const char* input_path;        /* the listing, or a label for input_fd in messages (may be NULL then) */
+    const char* fna_path;          /* library.fna (kraken2) / the .fna of qiime2: created or truncated */
+    const char* map_path;          /* prelim_map.txt (kraken2; NULL for qiime2) */
+    uint64_t chunk_bytes;          /* bytes read per chunk; 0 = BLU_SEQDB_DEFAULT_CHUNK; a longer line grows the chunk */
+    int32_t device;                /* HIP device ordinal */
+    int32_t reserved;
+} blu_seqdb_desc;
+
+typedef struct blu_seqdb_stats {
+    uint64_t n_lines;              /* records written */
+    uint64_t input_bytes;          /* listing bytes consumed (up to the stop or error line) */
+    uint64_t fna_bytes, map_bytes;
+    uint64_t n_chunks;
+    uint64_t max_line_bytes;       /* longest line seen, newline excluded */
+    uint64_t invalid_utf8_line;    /* 1-based line of a quiet stop, 0 = none */
+    double t_read_ms, t_gpu_ms, t_write_ms, t_wall_ms;   /* read: time inside read(); gpu: upload + kernels + download;
+                                                             write: time inside write(); the three overlap */
+} blu_seqdb_stats;
+
+int blu_seqdb_export(const blu_seqdb_desc* desc, blu_seqdb_stats* stats);
+
+/* The taxonomies half of `blu build-db qiime2` (build_qiime_db_from_blutils_db/mod.rs:24-84), on the host: the
+ * `*.blutils.json` read as serde reads TaxonomiesMap, then `Feature ID\tTaxon\n` and one `TAXID-OID-ACC\tLINEAGE\n` per
+ * accession in document order (numericLineage if use_taxid, else textLineage) to out_path.  A document serde_json would
+ * reject is BLU_ERR_PARSE and out_path is then left absent; a binary cache (blu_db_cache_build) is refused. */
+int blu_qiime_taxonomy_tsv(const char* json_path, int use_taxid, const char* out_path);
+
 /* CustomTaxon::from_file (domain/dtos/taxon.rs:28-66): .yaml or .json with the eight cutoff fields. */
 int blu_custom_taxon_from_file(const char* path, blu_cutoff_config* cfg);
 
