@@ -255,21 +255,29 @@ def shard_ranges(seg_off, n_shards: int) -> np.ndarray:
 
 
 def run_consensus_multi(taxes: Sequence[Taxonomy], seg_off, bitscore, tax_row, pident, align_len, acc_rank,
-                        strategy: str = "relaxed", pident_milli=None) -> np.ndarray:
+                        strategy: str = "relaxed", pident_milli=None, packed=False) -> np.ndarray:
     """blu_consensus_run_multi: one host table over several handles of the same taxonomy (one per GPU); `tax_row` holds
-    engine row ids (identical for every handle of one taxonomy)."""
+    engine row ids (identical for every handle of one taxonomy).  pident_milli and packed as in run_consensus_host (the
+    side records are built with the first handle: shape hints are the same for every handle of one taxonomy)."""
     seg = np.ascontiguousarray(seg_off, dtype=np.uint64)
     bs = np.ascontiguousarray(bitscore, dtype=np.int32)
-    tx = np.ascontiguousarray(tax_row)
-    tx = tx.view(np.uint32) if tx.dtype == np.int32 else np.ascontiguousarray(tx, dtype=np.uint32)
-    pid = np.ascontiguousarray(pident, dtype=np.float64) if pident_milli is None else None
-    pm = np.ascontiguousarray(pident_milli, dtype=np.uint32) if pident_milli is not None else None
-    aln = np.ascontiguousarray(align_len, dtype=np.int32)
-    ac = np.ascontiguousarray(acc_rank)
-    ac = ac.view(np.uint32) if ac.dtype == np.int32 else np.ascontiguousarray(ac, dtype=np.uint32)
     nq, nh = len(seg) - 1, int(seg[-1])
-    hits = N.Hits(bs.ctypes.data, tx.ctypes.data, pid.ctypes.data if pm is None else None, aln.ctypes.data, ac.ctypes.data,
-                  seg.ctypes.data, nh, nq, 0, 0, pm.ctypes.data if pm is not None else None, None, None)
+    if packed:
+        wide = packed == "wide"
+        rec = pack_records(taxes[0], tax_row, pident_milli, align_len, acc_rank, pident=pident if pident_milli is None else None, wide=wide)
+        assert rec.shape == (nh, 6 if wide else 4) and rec.ctypes.data % 16 == 0
+        hits = N.Hits(bs.ctypes.data, None, None, None, None, seg.ctypes.data, nh, nq, 0, 0, None, None if wide else rec.ctypes.data,
+                      rec.ctypes.data if wide else None)
+    else:
+        tx = np.ascontiguousarray(tax_row)
+        tx = tx.view(np.uint32) if tx.dtype == np.int32 else np.ascontiguousarray(tx, dtype=np.uint32)
+        pid = np.ascontiguousarray(pident, dtype=np.float64) if pident_milli is None else None
+        pm = np.ascontiguousarray(pident_milli, dtype=np.uint32) if pident_milli is not None else None
+        aln = np.ascontiguousarray(align_len, dtype=np.int32)
+        ac = np.ascontiguousarray(acc_rank)
+        ac = ac.view(np.uint32) if ac.dtype == np.int32 else np.ascontiguousarray(ac, dtype=np.uint32)
+        hits = N.Hits(bs.ctypes.data, tx.ctypes.data, pid.ctypes.data if pm is None else None, aln.ctypes.data, ac.ctypes.data,
+                      seg.ctypes.data, nh, nq, 0, 0, pm.ctypes.data if pm is not None else None, None, None)
     params = N.RunParams(N.STRATEGY[strategy], 0, None)
     out = np.zeros(nq, dtype=RESULT_DTYPE)
     handles = (C.c_void_p * len(taxes))(*[t.handle for t in taxes])

@@ -34,6 +34,17 @@ def columnar(tax: synth.SynthTaxonomy, hits: dict, taxon, strategy, custom=None,
                             taxon=taxon, strategy=strategy, custom=custom, bad=bad, threads=threads)
 
 
+def assert_records_equal(got, exp):
+    """Every field of every 32-byte record equal (ident_used bit for bit); names the first five queries that differ."""
+    assert len(got) == len(exp)
+    for name in orc.RESULT_DTYPE.names:
+        a, b = got[name], exp[name]
+        if name == "ident_used":
+            a, b = a.view(np.uint64), b.view(np.uint64)
+        bad = np.nonzero(a != b)[0]
+        assert len(bad) == 0, (name, bad[:5], got[bad[:5]], exp[bad[:5]])
+
+
 class Renderer:
     """Record -> the reference's TaxonomyBean fields, using only the taxonomy arrays and rank tables.
     rank_display/rank_serde: canonical rank code -> string; is_default(tax_row, level) -> bool."""

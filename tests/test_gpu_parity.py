@@ -30,14 +30,7 @@ def _run_host(t, hits, strategy):
                                      hits["align_len"], hits["acc_rank"], strategy=strategy)
 
 
-def _assert_records_equal(got, exp):
-    assert len(got) == len(exp)
-    for name in engine.RESULT_DTYPE.names:
-        a, b = got[name], exp[name]
-        if name == "ident_used":
-            a, b = a.view(np.uint64), b.view(np.uint64)
-        bad = np.nonzero(a != b)[0]
-        assert len(bad) == 0, (name, bad[:5], got[bad[:5]], exp[bad[:5]])
+_assert_records_equal = H.assert_records_equal
 
 
 def _engine_renderer(t, tax, hits):
