@@ -12,6 +12,16 @@ the format's (write_blutils_output.rs:39-52) and JSON is pretty-printed.
 
 = `blu blastn build-tabular` (commands.rs:145-161, parse_consensus_as_tabular/mod.rs:15).
 
+    python -m blutils_amd.cli blastn build-consensus ... --report FILE [--report-weight one|size]
+    python -m blutils_amd.cli blastn run-with-consensus ... --report FILE [--report-weight one|size]
+    python -m blutils_amd.cli blastn build-report [BLU_RESULT|-] [-o OUT] [-i json|jsonl|yaml] [--weight one|size]
+
+not in the reference: the taxon abundance report — how many queries, or with `size` weighting how many
+dereplicated reads (`;size=N` / `_size_N` in the query name), each taxon holds, summed up the lineage.  With --report it is
+counted on the GPU from the run's own records and written after the document, which stays what it is without the flag;
+build-report makes it on the host from an existing document, including one written by reference blutils
+(blutils_amd/report.py, csrc/report_kernel.hip).
+
     python -m blutils_amd.cli cache-db TAX.json CACHE [-u]
 
 writes the binary cache of a taxonomies file (not in the reference CLI; pass CACHE as -t afterwards).  
@@ -37,10 +47,11 @@ host from a `*.blutils.json` that `build-db blu` wrote."""
 from __future__ import annotations
 
 import argparse
+import functools
 import os
 import sys
 
-from . import blast, pipeline, seqdb, tabular, taxdb
+from . import blast, pipeline, report, seqdb, tabular, taxdb
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -78,6 +89,16 @@ def build_parser() -> argparse.ArgumentParser:
     rw.add_argument("--threads", type=int, default=1, help="the reference's global `--threads` option (default 1)")
     rw.add_argument("--blastn", default="blastn", help="blastn executable (not in the reference CLI)")
     rw.add_argument("--device", type=int, default=0, help="HIP device ordinal (not in the reference CLI)")
+    for sp in (bc, rw):
+        sp.add_argument("--report", help="also write the taxon abundance report of the results to this file, counted on the "
+                                         "GPU (not in the reference CLI)")
+        sp.add_argument("--report-weight", default="one", choices=["one", "size"],
+                        help="count results (one) or the dereplicated reads in the query names (size)")
+    br = blastn.add_parser("build-report", help="blutils result document -> taxon abundance report (not in the reference)")
+    br.add_argument("blu_result", nargs="?", default="-")
+    br.add_argument("-o", "--output-file")
+    br.add_argument("-i", "--input-format", default="json", choices=["json", "jsonl", "yaml"])
+    br.add_argument("--weight", default="one", choices=["one", "size"])
     bt = blastn.add_parser("build-tabular", help="blutils result document -> TSV")
     bt.add_argument("blu_result", nargs="?", default="-")
     bt.add_argument("-o", "--output-file")
@@ -172,7 +193,7 @@ def _run_with_consensus(args) -> int:
         blast.run_blast_and_build_consensus(args.query, args.tax_file, args.blast_out_file, args.blutils_out_file, config,
                                             blast.ExecuteBlastnProcRepository(args.blastn), args.force_overwrite,
                                             args.threads, args.strategy, args.use_taxid, args.out_format, custom,
-                                            device=args.device)
+                                            device=args.device, report_path=args.report, report_weight=args.report_weight)
     except blast.BlastError as e:
         raise SystemExit(str(e))
     return 0
@@ -191,6 +212,12 @@ def main(argv=None) -> int:
         except tabular.TabularError as e:
             raise SystemExit(str(e))
         return 0
+    if args.sub == "build-report":
+        try:
+            report.build_report(args.blu_result, args.output_file, args.input_format, args.weight)
+        except (tabular.TabularError, report.ReportError) as e:
+            raise SystemExit(str(e))
+        return 0
     if args.sub == "run-with-consensus":
         return _run_with_consensus(args)
     custom = None
@@ -201,17 +228,21 @@ def main(argv=None) -> int:
         raise SystemExit("Custom taxon values are required when the custom taxon option is selected.")
     to_file = args.blutils_out_file is not None
     fmt = args.out_format if (to_file or args.out_format != "json") else "json-compact"
+    # (with --report: the same document, plus the report file)
+    build = pipeline.build_consensus_identities
+    if args.report is not None:
+        build = functools.partial(pipeline.build_consensus_identities_with_report, report_path=args.report,
+                                  report_weight=args.report_weight)
     if to_file:
         path = os.path.splitext(args.blutils_out_file)[0] + "." + args.out_format      # PathBuf::set_extension
         parent = os.path.dirname(path)
         if parent and not os.path.exists(parent):
             os.makedirs(parent)
-        pipeline.build_consensus_identities(args.blast_out, args.tax_file, args.taxon, args.strategy, args.use_taxid, custom,
-                                            headers=None, out_format=fmt, device=args.device, parse=False, out_path=path)
+        build(args.blast_out, args.tax_file, args.taxon, args.strategy, args.use_taxid, custom, headers=None, out_format=fmt,
+              device=args.device, parse=False, out_path=path)
     else:
-        text, _ = pipeline.build_consensus_identities(args.blast_out, args.tax_file, args.taxon, args.strategy,
-                                                      args.use_taxid, custom, headers=None, out_format=fmt,
-                                                      device=args.device, parse=False)
+        text, _ = build(args.blast_out, args.tax_file, args.taxon, args.strategy, args.use_taxid, custom, headers=None,
+                        out_format=fmt, device=args.device, parse=False)
         sys.stdout.write(text)
     return 0
 

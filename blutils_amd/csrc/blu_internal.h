@@ -117,6 +117,19 @@ int launch_consensus(const TaxDev& tax, const HitsDev& hits, int strategy, blu_r
 const char* consensus_kernel_name();
 void consensus_last_geometry(uint32_t* grid, uint32_t* block);
 
+// report_kernel.hip: the taxon abundance report of one run's records (device pointers; blu_consensus_report stages host ones).
+// The engine row of record q is row_src[idx * row_stride], idx = its ref_row (< n_rows), or q itself when by_query.
+struct ReportInput {
+    const blu_result* recs;
+    uint64_t n_queries;
+    const uint32_t* row_src;
+    uint64_t n_rows;
+    uint32_t row_stride;
+    bool by_query;
+    const uint32_t* weight;   // [n_queries] or null
+};
+int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* out);
+
 void set_error(const char* fmt, ...);
 // LinnaeanRank::from_str (linnaean_ranks.rs:52-72): enum kind 0..8, or K_FIRST_OTHER with the slug in *other
 uint16_t parse_rank(const char* name, std::string* other);

@@ -145,8 +145,11 @@ void warm_up_device(int device);
 // forward table), perc_identity as milli-percent when every value is exactly k/1000 (checked on the device), one
 // blu_consensus_run with device pointers, records copied to `out` (host) and the top-score rows of the rendered
 // queries compacted into `top`.  The device columns are left as they were.
+// kept: where the run's device records and engine row ids stay (with the columns, until they are freed) for a second pass
+// over them — the taxon report; row of record q = rows[ref_row * row_stride].
+struct DeviceRecords { const blu_result* recs = nullptr; const uint32_t* rows = nullptr; uint32_t row_stride = 1; };
 int device_run_consensus(const blu_taxonomy* tax, DeviceHits& dev, const uint32_t* fwd, uint64_t n_tax, int strategy, blu_result* out,
-                         TopTable* top);
+                         TopTable* top, DeviceRecords* kept = nullptr);
 
 }  // namespace blu
 #endif

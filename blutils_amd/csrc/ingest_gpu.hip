@@ -1398,7 +1398,7 @@ DeviceHits::~DeviceHits() {
 }
 
 int device_run_consensus(const blu_taxonomy* tax, DeviceHits& dev, const uint32_t* fwd, uint64_t n_tax, int strategy, blu_result* out,
-                         TopTable* top) {
+                         TopTable* top, DeviceRecords* kept) {
     int rc = BLU_OK;
     const bool oom_fallback = false;
     std::string* const oom_why = nullptr;
@@ -1448,6 +1448,7 @@ int device_run_consensus(const blu_taxonomy* tax, DeviceHits& dev, const uint32_
         blu_run_params rp{strategy, 0, nullptr};
         rc = blu_consensus_run(tax, &h, &rp, d_out);
         if (rc != BLU_OK) goto done;
+        if (kept) { kept->recs = d_out; kept->rows = packed ? (const uint32_t*)d_rec : d_rows; kept->row_stride = packed ? 4u : 1u; }
     }
     HIPCHK(hipStreamSynchronize(nullptr));
     {

@@ -185,6 +185,7 @@ struct Db {
     std::vector<std::string> rank_raw;       // rank strings as they appear in lineages
     std::vector<std::string> rank_display;   // canonical Display of rank_raw[i]
     std::vector<std::string> node_ident;     // node id -> identifier string
+    std::vector<uint16_t> node_rank;         // node id -> index into rank_display (a node is interned on (Display(rank), identifier))
     std::unordered_map<std::string, uint16_t> rank_ids;
     std::unordered_map<std::string, uint32_t> node_ids;   // key: Display(rank) + '\x1f' + identifier
     TaxidMap row_of;                         // taxid -> its (first) row
@@ -231,6 +232,7 @@ void add_lineage(Db& db, int64_t taxid, const std::string& lineage) {
             if (nit == db.node_ids.end()) {
                 nit = db.node_ids.emplace(std::move(key), (uint32_t)db.node_ident.size()).first;
                 db.node_ident.push_back(ident);
+                db.node_rank.push_back(rit->second);
             }
             db.lin_node.push_back(nit->second);
             db.lin_rank.push_back(rit->second);
@@ -315,6 +317,8 @@ int load_db_cache(const MappedFile& f, bool use_taxid, Db& db) {
     }
     db.node_ident.resize(h.n_nodes);
     for (uint64_t i = 0; i < h.n_nodes; ++i) db.node_ident[i].assign(nbytes + noff[i], noff[i + 1] - noff[i]);
+    db.node_rank.assign(h.n_nodes, 0);
+    for (uint64_t i = 0; i < h.n_lin; ++i) db.node_rank[db.lin_node[i]] = db.lin_rank[i];
     db.row_of.reserve(h.n_tax);
     for (uint64_t i = 0; i < h.n_tax; ++i) db.note_row(db.taxid[i], (uint32_t)i);
     return BLU_OK;
@@ -1105,11 +1109,99 @@ const char* status_site(uint8_t st) {
     }
 }
 
+bool write_all(int fd, const char* p, size_t left);
+
+// ---- taxon abundance report ---------------------------------------------------------------------------
+// Weight of a query under `size` weighting: the first ';'-separated field that is exactly `size=` + decimal digits, else a
+// name ending in `_size_` + digits, else 1.  false: the value does not fit 32 bits.
+bool size_weight(std::string_view name, uint32_t* w) {
+    auto digits = [](std::string_view v) { if (v.empty()) return false; for (char c : v) if (c < '0' || c > '9') return false; return true; };
+    auto value = [&](std::string_view v) {
+        uint64_t x = 0;
+        for (char c : v) { x = x * 10 + (uint64_t)(c - '0'); if (x > 0xFFFFFFFFull) return false; }
+        *w = (uint32_t)x;
+        return true;
+    };
+    for (size_t pos = 0;;) {
+        const size_t semi = name.find(';', pos);
+        const std::string_view f = name.substr(pos, semi == std::string_view::npos ? std::string_view::npos : semi - pos);
+        if (f.size() > 5 && f.compare(0, 5, "size=") == 0 && digits(f.substr(5))) return value(f.substr(5));
+        if (semi == std::string_view::npos) break;
+        pos = semi + 1;
+    }
+    const size_t at = name.rfind("_size_");
+    if (at != std::string_view::npos && digits(name.substr(at + 6))) return value(name.substr(at + 6));
+    *w = 1;
+    return true;
+}
+
+// The report's text: header, unclassified, unplaced (when any), then the paths depth first, siblings by clade descending
+// and element text ascending (bytewise).  rep.paths has parents before children (blu_consensus_report).
+std::string render_report(const Db& db, const blu_report& rep) {
+    std::string o = "#percent\tclade\tdirect\trank\tidentifier\ttaxonomy\n";
+    const double total = (double)rep.total;
+    auto num = [&](uint64_t v) { char b[24]; auto r = std::to_chars(b, b + sizeof b, v); o.append(b, (size_t)(r.ptr - b)); };
+    auto pct = [&](uint64_t c) { char b[64]; const int n = snprintf(b, sizeof b, "%.2f", rep.total ? 100.0 * (double)c / total : 0.0); o.append(b, (size_t)n); };
+    auto fixed_row = [&](uint64_t c, const char* what) { pct(c); o.push_back('\t'); num(c); o.push_back('\t'); num(c); o += "\t-\t"; o += what; o += "\t\n"; };
+    fixed_row(rep.unclassified, "unclassified");
+    if (rep.unplaced) fixed_row(rep.unplaced, "unplaced");
+    const uint64_t n = rep.n_paths;
+    const blu_report_path* P = rep.paths;
+    // children of path i at kids[off[i + 1] .. off[i + 2]); the first-level paths at kids[off[0] .. off[1])
+    std::vector<uint64_t> off(n + 2, 0);
+    for (uint64_t i = 0; i < n; ++i) ++off[(P[i].parent == BLU_REPORT_NO_PARENT ? 0 : (uint64_t)P[i].parent + 1) + 1];
+    for (uint64_t i = 0; i + 1 < off.size(); ++i) off[i + 1] += off[i];
+    std::vector<uint32_t> kids(n);
+    {
+        std::vector<uint64_t> at(off.begin(), off.end() - 1);
+        for (uint64_t i = 0; i < n; ++i) kids[at[P[i].parent == BLU_REPORT_NO_PARENT ? 0 : (uint64_t)P[i].parent + 1]++] = (uint32_t)i;
+    }
+    auto rank_of = [&](uint32_t node) -> const std::string& { return db.rank_display[db.node_rank[node]]; };
+    std::string ea, eb;   // (element texts of a comparison: buffers reused)
+    auto less = [&](uint32_t a, uint32_t b) {
+        if (P[a].clade != P[b].clade) return P[a].clade > P[b].clade;
+        ea.assign(rank_of(P[a].node)); ea += "__"; ea += db.node_ident[P[a].node];
+        eb.assign(rank_of(P[b].node)); eb += "__"; eb += db.node_ident[P[b].node];
+        return ea < eb;
+    };
+    for (uint64_t g = 0; g + 1 < off.size(); ++g)
+        if (off[g + 1] - off[g] > 1) std::sort(kids.begin() + off[g], kids.begin() + off[g + 1], less);
+    std::string path;
+    std::vector<size_t> len_at;                       // path text length after the element at each depth
+    std::vector<std::pair<uint32_t, uint32_t>> stack;  // (path, depth)
+    for (uint64_t k = off[1]; k-- > off[0];) stack.emplace_back(kids[k], 0u);
+    while (!stack.empty()) {
+        const auto [i, d] = stack.back();
+        stack.pop_back();
+        path.resize(d ? len_at[d - 1] : 0);
+        if (d) path.push_back(';');
+        const std::string& rk = rank_of(P[i].node);
+        const std::string& id = db.node_ident[P[i].node];
+        path += rk; path += "__"; path += id;
+        if (len_at.size() <= d) len_at.resize(d + 1);
+        len_at[d] = path.size();
+        pct(P[i].clade); o.push_back('\t'); num(P[i].clade); o.push_back('\t'); num(P[i].direct); o.push_back('\t');
+        o += rk; o.push_back('\t'); o += id; o.push_back('\t'); o += path; o.push_back('\n');
+        for (uint64_t k = off[(uint64_t)i + 2]; k-- > off[(uint64_t)i + 1];) stack.emplace_back(kids[k], d + 1);
+    }
+    return o;
+}
+
+bool write_text_file(const char* path, const std::string& text) {
+    const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) return false;
+    const bool ok = write_all(fd, text.data(), text.size());
+    if (close(fd) != 0 || !ok) { unlink(path); return false; }
+    return true;
+}
+
 // The serialized document as the pieces the workers rendered, in order: they are copied (or written) in parallel
 // straight from the worker buffers, never concatenated.
 struct Document {
     std::vector<Out> pieces;
     bool written = false;      // the pieces went to the output file while they were rendered (and were freed)
+    bool has_report = false;   // report: the taxon report's text, written by the caller once the document is out
+    std::string report;
     size_t size() const { size_t n = 0; for (auto& p : pieces) n += p.size(); return n; }
 };
 
@@ -1147,12 +1239,68 @@ bool parallel_dynamic(size_t n, unsigned nthreads, F&& f) {
     return !oom;
 }
 
+// The report of one pipeline run (blu_build_consensus_identities_report): weights from the query names, the device pass over
+// the records (in place on the device path; uploaded on the host path), the header-only queries as unclassified, the text.
+int build_report(const Db& db, const HitTable& ht, const blu_taxonomy* tax, const Column<blu_result>& recs, const DeviceRecords& kept,
+                 bool on_device, const std::vector<uint32_t>& eng_rows, const std::vector<std::string>& extra, int32_t weight,
+                 std::string& text) {
+    const uint64_t nq = recs.size();
+    std::vector<uint32_t> w;
+    uint64_t extra_w = 0;
+    if (weight == BLU_REPORT_WEIGHT_SIZE) {
+        w.resize(nq);
+        for (uint64_t q = 0; q < nq; ++q)
+            if (!size_weight(ht.query_names[q], &w[q])) { set_error("query `%s`: its size is 2^32 or more", ht.query_names[q].c_str()); return BLU_ERR_INVALID_ARG; }
+        for (const std::string& name : extra) {
+            uint32_t x;
+            if (!size_weight(name, &x)) { set_error("query `%s`: its size is 2^32 or more", name.c_str()); return BLU_ERR_INVALID_ARG; }
+            extra_w += x;
+        }
+    } else extra_w = extra.size();
+    blu_report rep{};
+    struct Free { blu_report& r; ~Free() { blu_report_free(&r); } } free_rep{rep};
+    int rc;
+    if (on_device && nq) {
+        uint32_t* d_w = nullptr;
+        if (!w.empty()) {
+            hipError_t e = hipMalloc((void**)&d_w, nq * 4);
+            if (e == hipSuccess) e = hipMemcpy(d_w, w.data(), nq * 4, hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                if (d_w) (void)hipFree(d_w);
+                set_error("report: weights upload failed: %s", hipGetErrorString(e));
+                return e == hipErrorOutOfMemory ? BLU_ERR_ALLOC : BLU_ERR_HIP;
+            }
+        }
+        ReportInput in{kept.recs, nq, kept.rows, ht.n_hits, kept.row_stride, false, d_w};
+        rc = report_device(tax, in, &rep);
+        if (d_w) (void)hipFree(d_w);
+    } else {
+        blu_hits h{};
+        h.tax_row = eng_rows.data();
+        h.n_hits = eng_rows.size();
+        h.n_queries = nq;
+        h.on_device = 0;
+        rc = blu_consensus_report(tax, &h, recs.data(), w.empty() ? nullptr : w.data(), nullptr, &rep);
+    }
+    if (rc != BLU_OK) return rc;
+    rep.unclassified += extra_w;
+    rep.total += extra_w;
+    text = render_report(db, rep);
+    return BLU_OK;
+}
+
 // out_path != nullptr: the document is written there (an existing file is replaced, write_blutils_output.rs:57-63) by a
 // writer thread that follows the renderers piece by piece; otherwise the pieces are left in `document`.
 int build_document(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
                    const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                   const char* config_text, const char* out_path, Document* document, blu_pipeline_stats* stats) {
+                   const char* config_text, const char* out_path, Document* document, blu_pipeline_stats* stats,
+                   const blu_report_params* report = nullptr) {
     if (!blast_output_file || !taxonomies_file || !params || !document) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    if (report && (!report->report_path || (report->weight != BLU_REPORT_WEIGHT_ONE && report->weight != BLU_REPORT_WEIGHT_SIZE))) {
+        set_error("report: a path and weight BLU_REPORT_WEIGHT_ONE or BLU_REPORT_WEIGHT_SIZE are needed");
+        return BLU_ERR_INVALID_ARG;
+    }
     blu_pipeline_stats st{};
     Trace tr;
     const unsigned nthreads = worker_threads();
@@ -1220,6 +1368,8 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     recs.resize(ht.n_queries);                    //  the threads that copy the records back)
     TopTable top;
     bool done_on_device = false;
+    DeviceRecords kept;                       // (the device records, for the report)
+    std::vector<uint32_t> eng_rows;           // (the host path's engine row ids, for the report)
     // (BLU_PIPELINE_HOST_COLUMNS=1, tests: take the fallback below although the device path would work)
     const bool force_host = getenv("BLU_PIPELINE_HOST_COLUMNS") != nullptr;
     if (force_host && ht.dev) { rc = download_columns(ht); if (rc != BLU_OK) return rc; }
@@ -1227,13 +1377,13 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
         // the GPU ingest left the grouped columns on the device: the engine reads them in place and only the records and
         // the top-score rows come back (if that fails — e.g. no room for the work buffers — the columns are downloaded and
         // go through the staging path below)
-        done_on_device = device_run_consensus(tax, *ht.dev, fwd.data(), db.taxid.size(), params->strategy, recs.data(), &top) == BLU_OK;   // mod.rs:104-128
+        done_on_device = device_run_consensus(tax, *ht.dev, fwd.data(), db.taxid.size(), params->strategy, recs.data(), &top, &kept) == BLU_OK;   // mod.rs:104-128
         if (!done_on_device) { rc = download_columns(ht); if (rc != BLU_OK) return rc; }
     }
     // (the device columns and the engine's work buffers stay with the hit table: they are freed off the caller's path at the end)
     if (!done_on_device) ht.dev.reset();
     if (!done_on_device) {
-        std::vector<uint32_t> eng_rows(ht.tax_desc_row.size());
+        eng_rows.resize(ht.tax_desc_row.size());
         for (size_t i = 0; i < eng_rows.size(); ++i)
             eng_rows[i] = ht.tax_desc_row[i] == BLU_UNMATCHED_TAXID ? BLU_UNMATCHED_TAXID : fwd[ht.tax_desc_row[i]];
         if (!recs.empty()) {
@@ -1314,6 +1464,13 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
             set_error("query `%s`: %s", it.name->c_str(), status_site(s));
             return BLU_ERR_REFERENCE_PANIC;
         }
+    }
+    if (report) {
+        // the taxon report, from the records while they (on the device path: and the engine rows) are still on the device
+        rc = build_report(db, ht, tax, recs, kept, done_on_device, eng_rows, extra, report->weight, document->report);
+        if (rc != BLU_OK) return rc;
+        document->has_report = true;
+        tr.lap("report");
     }
     const bool pretty = params->out_format == BLU_OUT_JSON;
     const bool doc = pretty || params->out_format == BLU_OUT_JSON_COMPACT;   // one {results, config} document
@@ -1471,29 +1628,18 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     return BLU_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int blu_build_consensus_identities(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                   const char* taxonomies_file, const blu_pipeline_params* params, char** out_text,
-                                   size_t* out_len, blu_pipeline_stats* stats) {
-    return blu_build_consensus_identities_cfg(blast_output_file, headers, n_headers, taxonomies_file, params, nullptr, nullptr,
-                                              out_text, out_len, stats);
-}
-
-int blu_build_consensus_identities_cfg(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                       const char* taxonomies_file, const blu_pipeline_params* params,
-                                       const char* run_id_text, const char* config_text, char** out_text, size_t* out_len,
-                                       blu_pipeline_stats* stats) {
+int consensus_to_text(const char* blast_output_file, const char* const* headers, uint64_t n_headers, const char* taxonomies_file,
+                      const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const blu_report_params* report,
+                      char** out_text, size_t* out_len, blu_pipeline_stats* stats) {
     if (!out_text) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     *out_text = nullptr;
     if (out_len) *out_len = 0;
     Document d;
     int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats); }
+    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats, report); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }   // (no exception crosses the C ABI)
     if (rc != BLU_OK) return rc;
+    if (d.has_report && !write_text_file(report->report_path, d.report)) { set_error("cannot write %s", report->report_path); return BLU_ERR_IO; }
     const size_t total = d.size();
     char* buf = (char*)malloc(total + 1);
     if (!buf) { set_error("out of memory"); return BLU_ERR_ALLOC; }
@@ -1507,18 +1653,22 @@ int blu_build_consensus_identities_cfg(const char* blast_output_file, const char
     return BLU_OK;
 }
 
-int blu_build_consensus_identities_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                           const char* taxonomies_file, const blu_pipeline_params* params,
-                                           const char* run_id_text, const char* config_text, const char* out_path,
-                                           blu_pipeline_stats* stats) {
+// (the report file, when asked for, is written once the document is out)
+int consensus_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers, const char* taxonomies_file,
+                      const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const char* out_path,
+                      const blu_report_params* report, blu_pipeline_stats* stats) {
     if (!out_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     Document d;
     int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats); }
+    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats, report); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
     if (rc != BLU_OK) return rc;
     if (getenv("BLU_INGEST_TRACE")) fprintf(stderr, "[pipeline] %-26s %.3f s\n", "tear-down (tables, strings)", now_s() - g_t_body_end);
-    if (d.written) return BLU_OK;
+    auto put_report = [&]() -> int {
+        if (d.has_report && !write_text_file(report->report_path, d.report)) { set_error("cannot write %s", report->report_path); return BLU_ERR_IO; }
+        return BLU_OK;
+    };
+    if (d.written) return put_report();
     // (YAML: one piece, written here) write_blutils_output.rs:57-63: an existing file is replaced
     Trace tr;
     const int fd = open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
@@ -1537,7 +1687,47 @@ int blu_build_consensus_identities_to_file(const char* blast_output_file, const 
     });
     if (close(fd) != 0 || !ok) { set_error("cannot write %s", out_path); return BLU_ERR_IO; }
     tr.lap("write file");
-    return BLU_OK;
+    return put_report();
+}
+
+
+}  // namespace
+
+extern "C" {
+
+int blu_build_consensus_identities(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                   const char* taxonomies_file, const blu_pipeline_params* params, char** out_text,
+                                   size_t* out_len, blu_pipeline_stats* stats) {
+    return blu_build_consensus_identities_cfg(blast_output_file, headers, n_headers, taxonomies_file, params, nullptr, nullptr,
+                                              out_text, out_len, stats);
+}
+
+int blu_build_consensus_identities_cfg(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                       const char* taxonomies_file, const blu_pipeline_params* params,
+                                       const char* run_id_text, const char* config_text, char** out_text, size_t* out_len,
+                                       blu_pipeline_stats* stats) {
+    return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, out_text,
+                             out_len, stats);
+}
+
+int blu_build_consensus_identities_report(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                          const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
+                                          const char* config_text, const char* out_path, const blu_report_params* report,
+                                          char** out_text, size_t* out_len, blu_pipeline_stats* stats) {
+    if (!report || !report->report_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    if (out_path)
+        return consensus_to_file(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, report,
+                                 stats);
+    return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, report, out_text,
+                             out_len, stats);
+}
+
+int blu_build_consensus_identities_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                           const char* taxonomies_file, const blu_pipeline_params* params,
+                                           const char* run_id_text, const char* config_text, const char* out_path,
+                                           blu_pipeline_stats* stats) {
+    return consensus_to_file(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, nullptr,
+                             stats);
 }
 
 void blu_free_text(char* text) { free(text); }

@@ -109,6 +109,13 @@ def custom_taxon_from_file(path: str) -> dict:
     return {k: int(cfg.custom[i]) for i, k in enumerate(N.CUSTOM_FIELDS) if cfg.custom_has[i]}
 
 
+class ReportParams(C.Structure):
+    _fields_ = [("report_path", C.c_char_p), ("weight", C.c_int32), ("reserved", C.c_int32)]
+
+
+REPORT_WEIGHT = {"one": 0, "size": 1}
+
+
 def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
                                strategy: str = "relaxed", use_taxid: Optional[bool] = None,
                                custom_taxon_values: Optional[dict] = None, headers: Optional[Sequence[str]] = None,
@@ -118,6 +125,26 @@ def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: s
     (None, stats) is returned.  results: the parsed `results` list (json) / list of records (jsonl), sorted by
     query, or the raw text when parse=False.  config: Some(BlastBuilder) of the run-with-consensus path
     (blutils_amd.blast.BlastBuilder): its run id goes on every result and it is written as the document's config."""
+    return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
+                  lenient, parse, config, out_path, None, "one")
+
+
+def build_consensus_identities_with_report(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
+                                           strategy: str = "relaxed", use_taxid: Optional[bool] = None,
+                                           custom_taxon_values: Optional[dict] = None,
+                                           headers: Optional[Sequence[str]] = None, out_format: str = "json",
+                                           device: int = 0, lenient: bool = False, parse: bool = True, config=None,
+                                           out_path: Optional[str] = None, report_path: str = "report.tsv",
+                                           report_weight: str = "one"):
+    """build_consensus_identities plus the taxon abundance report of its results, counted on the GPU and written to
+    report_path after the document (include/blu_pipeline.h: blu_build_consensus_identities_report).
+    report_weight: "one" (results) or "size" (dereplicated reads named in the query)."""
+    return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
+                  lenient, parse, config, out_path, report_path, report_weight)
+
+
+def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device, lenient,
+           parse, config, out_path, report_path, report_weight):
     L = _bind()
     p = PipelineParams()
     p.cutoffs.taxon = N.TAXON[taxon]
@@ -145,7 +172,21 @@ def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: s
                                                      C.POINTER(PipelineStats)]
     run_id = str(config.run_id).encode() if config is not None else None
     cfg_text = config.render(out_format).encode() if config is not None else None
-    if out_path is not None:
+    if report_path is not None:
+        rp = ReportParams(str(report_path).encode(), REPORT_WEIGHT[report_weight], 0)
+        L.blu_build_consensus_identities_report.restype = C.c_int
+        L.blu_build_consensus_identities_report.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
+                                                            C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(ReportParams),
+                                                            C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(PipelineStats)]
+        rc = L.blu_build_consensus_identities_report(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
+                                                     taxonomies_file.encode(), C.byref(p), run_id, cfg_text,
+                                                     out_path.encode() if out_path is not None else None, C.byref(rp),
+                                                     C.byref(text), C.byref(n), C.byref(st))
+        if rc != N.BLU_OK:
+            raise N.BluError(rc, "blu_build_consensus_identities_report")
+        if out_path is not None:
+            return None, {f: getattr(st, f) for f, _ in PipelineStats._fields_}
+    elif out_path is not None:
         L.blu_build_consensus_identities_to_file.restype = C.c_int
         L.blu_build_consensus_identities_to_file.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
                                                              C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PipelineStats)]
@@ -155,11 +196,12 @@ def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: s
         if rc != N.BLU_OK:
             raise N.BluError(rc, "blu_build_consensus_identities_to_file")
         return None, {f: getattr(st, f) for f, _ in PipelineStats._fields_}
-    rc = L.blu_build_consensus_identities_cfg(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
-                                              taxonomies_file.encode(), C.byref(p), run_id, cfg_text, C.byref(text),
-                                              C.byref(n), C.byref(st))
-    if rc != N.BLU_OK:
-        raise N.BluError(rc, "blu_build_consensus_identities")
+    else:
+        rc = L.blu_build_consensus_identities_cfg(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
+                                                  taxonomies_file.encode(), C.byref(p), run_id, cfg_text, C.byref(text),
+                                                  C.byref(n), C.byref(st))
+        if rc != N.BLU_OK:
+            raise N.BluError(rc, "blu_build_consensus_identities")
     try:
         raw = C.string_at(text, n.value).decode("utf-8")
     finally:

@@ -1,0 +1,187 @@
+"""Taxon abundance report of a blutils result document.
+
+    python -m blutils_amd.cli blastn build-report [BLU_RESULT|-] [-o OUT] [-i json|jsonl|yaml] [--weight one|size]
+
+How many queries (or, with `size` weighting, dereplicated reads) each taxon holds, summed up the lineage.  Not in the
+reference.  Two ways in:
+
+* `report_from_results` / `build_report`: host only, from a document already written (by this project or by reference
+  blutils), read with `tabular.load_content`;
+* `build-consensus --report` (pipeline.build_consensus_identities_with_report): counted on the GPU from the run's own
+  records while they are on the device (csrc/report_kernel.hip, include/blu_consensus.h: blu_consensus_report), the
+  text written by the library.  Both give the same bytes for the same results.
+
+`consensus_report` binds the engine-level call for callers that hold the records themselves.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import sys
+from typing import Optional
+
+from . import _native as N
+from . import tabular
+
+HEADER = "#percent\tclade\tdirect\trank\tidentifier\ttaxonomy\n"
+WEIGHT = {"one": 0, "size": 1}
+NO_PARENT = 0xFFFFFFFF
+
+
+class ReportError(Exception):
+    pass
+
+
+def _digits(s: str) -> bool:
+    return bool(s) and all("0" <= c <= "9" for c in s)
+
+
+def weight_of(query: str, weight: str = "one") -> int:
+    """1 with `one`.  With `size`: the first ';'-separated field that is exactly `size=` + decimal digits, else a name
+    ending in `_size_` + digits, else 1.  A value of 2^32 or more is an error naming the query."""
+    if weight == "one":
+        return 1
+    if weight != "size":
+        raise ReportError(f"unknown weight `{weight}`")
+    value = None
+    for field in query.split(";"):
+        if field.startswith("size=") and _digits(field[5:]):
+            value = field[5:]
+            break
+    if value is None:
+        at = query.rfind("_size_")
+        if at >= 0 and _digits(query[at + 6:]):
+            value = query[at + 6:]
+    if value is None:
+        return 1
+    v = int(value)
+    if v >= 1 << 32:
+        raise ReportError(f"query `{query}`: its size is 2^32 or more")
+    return v
+
+
+def _pct(clade: int, total: int) -> str:
+    return "%.2f" % (100.0 * clade / total if total else 0.0)
+
+
+def render(unclassified: int, unplaced: int, paths) -> str:
+    """paths: {tuple of elements: [direct, clade]} holding every prefix of every path."""
+    total = unclassified + unplaced + sum(v[0] for v in paths.values())
+    out = [HEADER, f"{_pct(unclassified, total)}\t{unclassified}\t{unclassified}\t-\tunclassified\t\n"]
+    if unplaced:
+        out.append(f"{_pct(unplaced, total)}\t{unplaced}\t{unplaced}\t-\tunplaced\t\n")
+    kids = {}
+    for p in paths:
+        kids.setdefault(p[:-1], []).append(p)
+    for v in kids.values():
+        v.sort(key=lambda p: (-paths[p][1], p[-1].encode("utf-8", "surrogatepass")))
+    stack = list(reversed(kids.get((), [])))
+    while stack:
+        p = stack.pop()
+        direct, clade = paths[p]
+        rank, _, ident = p[-1].partition("__")
+        out.append(f"{_pct(clade, total)}\t{clade}\t{direct}\t{rank}\t{ident}\t{';'.join(p)}\n")
+        stack.extend(reversed(kids.get(p, [])))
+    return "".join(out)
+
+
+def report_from_results(results, weight: str = "one") -> str:
+    """The report of a document's `results` list (parsed QueryWithConsensus objects)."""
+    unclassified = unplaced = 0
+    paths = {}
+    for r in results:
+        w = weight_of(str(r["query"]), weight)
+        taxon = r.get("taxon")
+        if taxon is None:
+            unclassified += w
+            continue
+        tax = taxon.get("taxonomy")
+        if not tax:
+            unplaced += w
+            continue
+        els = tuple(tax.split(";"))
+        for i in range(1, len(els) + 1):
+            v = paths.setdefault(els[:i], [0, 0])
+            v[1] += w
+        paths[els][0] += w
+    return render(unclassified, unplaced, paths)
+
+
+def build_report(blu_result: str = "-", output_file: Optional[str] = None, input_format: str = "json",
+                 weight: str = "one", stdout=None) -> str:
+    """`blastn build-report`: the report of an existing document, to output_file or stdout."""
+    try:
+        content = tabular.load_content(blu_result, input_format)
+    except FileNotFoundError:
+        raise ReportError(f"The file `{blu_result}` does not exist.") from None
+    text = report_from_results(content["results"], weight)
+    if output_file is None:
+        (stdout if stdout is not None else sys.stdout).write(text)
+    else:
+        with open(output_file, "w", encoding="utf-8", newline="") as f:
+            f.write(text)
+    return text
+
+
+# ---- engine-level binding (include/blu_consensus.h: blu_consensus_report) -------------------------------------------
+
+class ReportPath(C.Structure):
+    _fields_ = [("node", C.c_uint32), ("parent", C.c_uint32), ("direct", C.c_uint64), ("clade", C.c_uint64)]
+
+
+class Report(C.Structure):
+    _fields_ = [("n_paths", C.c_uint64), ("paths", C.POINTER(ReportPath)), ("unclassified", C.c_uint64),
+                ("unplaced", C.c_uint64), ("total", C.c_uint64), ("table_slots", C.c_uint64), ("attempts", C.c_uint32),
+                ("reserved", C.c_uint32), ("t_device_ms", C.c_double)]
+
+
+def _bind():
+    L = N.lib()
+    L.blu_consensus_report.restype = C.c_int
+    L.blu_consensus_report.argtypes = [C.c_void_p, C.POINTER(N.Hits), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Report)]
+    L.blu_report_free.argtypes = [C.POINTER(Report)]
+    return L
+
+
+def consensus_report(tax, tax_row, records, n_hits: int, weights=None, on_device: Optional[bool] = None, stream=None,
+                     packed: Optional[str] = None) -> dict:
+    """blu_consensus_report on one run's records.  tax: engine.Taxonomy; tax_row: the engine row ids (numpy uint32 or a
+    CUDA tensor), or the packed / packed64 side records with packed="packed" / "packed64"; records: the blu_result
+    records (numpy structured array / uint8 buffer, or a CUDA uint8 tensor); weights: uint32 per query or None.
+    Returns {"paths": structured numpy array (node, parent, direct, clade), "unclassified", "unplaced", "total",
+    "table_slots", "attempts", "t_device_ms"}."""
+    import numpy as np
+
+    def ptr(a):
+        if a is None:
+            return None
+        return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+    if on_device is None:
+        on_device = bool(getattr(records, "is_cuda", False))
+    nbytes = records.numel() * records.element_size() if hasattr(records, "numel") else records.nbytes
+    nq = nbytes // 32
+    keep = []
+    if not on_device:
+        tax_row = np.ascontiguousarray(tax_row).view(np.uint32)
+        records = np.ascontiguousarray(records)
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.uint32)
+        keep += [tax_row, records, weights]
+    col = {"packed": (None, ptr(tax_row), None), "packed64": (None, None, ptr(tax_row))}.get(packed, (ptr(tax_row), None, None))
+    h = N.Hits(None, col[0], None, None, None, None, int(n_hits), int(nq), 1 if on_device else 0, 0, None, col[1], col[2])
+    if stream is None and on_device:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    L = _bind()
+    rep = Report()
+    rc = L.blu_consensus_report(tax.handle, C.byref(h), ptr(records), ptr(weights), stream, C.byref(rep))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_consensus_report")
+    try:
+        dt = np.dtype([("node", np.uint32), ("parent", np.uint32), ("direct", np.uint64), ("clade", np.uint64)])
+        n = int(rep.n_paths)
+        paths = (np.frombuffer(C.string_at(rep.paths, n * dt.itemsize), dtype=dt).copy() if n else np.zeros(0, dtype=dt))
+        return {"paths": paths, "unclassified": int(rep.unclassified), "unplaced": int(rep.unplaced), "total": int(rep.total),
+                "table_slots": int(rep.table_slots), "attempts": int(rep.attempts), "t_device_ms": float(rep.t_device_ms)}
+    finally:
+        L.blu_report_free(C.byref(rep))

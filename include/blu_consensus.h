@@ -248,6 +248,43 @@ int blu_shard_ranges(const uint64_t* seg_off, uint64_t n_queries, uint32_t n_sha
  * thread (for profiles/ bookkeeping). */
 int blu_consensus_last_launch(char* kernel_name, size_t len, uint32_t* grid, uint32_t* block);
 
+/* -------------------------------------------------------------------------- */
+/* Taxon abundance report (additive, ABI v5).  A query's path is the `taxonomy` the document writes for it: the
+ * levels of the lineage of tax_row[ref_row] that level_mask selects.  A path is a node sequence; its prefixes are
+ * paths too.  direct = summed weight of the queries whose path is exactly this one, clade = of those that have it as
+ * a prefix.  Counted on the device (csrc/report_kernel.hip); DESIGN.md §12. */
+#define BLU_REPORT_NO_PARENT 0xFFFFFFFFu
+
+typedef struct blu_report_path {
+    uint32_t node;     /* interned node id of the last element (blu_taxonomy_desc.lin_node) */
+    uint32_t parent;   /* index of the path one element shorter in blu_report.paths, BLU_REPORT_NO_PARENT for a first element */
+    uint64_t direct;
+    uint64_t clade;
+} blu_report_path;     /* 24 bytes */
+
+typedef struct blu_report {
+    uint64_t n_paths;
+    blu_report_path* paths;   /* [n_paths], parents before their children (paths[i].parent < i); otherwise in no promised
+                                 order.  malloc'd by the library: blu_report_free */
+    uint64_t unclassified;    /* weight of the records with status >= 2 (NoConsensusFound, and the panic statuses) */
+    uint64_t unplaced;        /* weight of the records with a taxon whose level_mask selects no level (taxonomy "") */
+    uint64_t total;           /* unclassified + unplaced + the clades of the first-level paths */
+    uint64_t table_slots;     /* size of the device path table of the last attempt */
+    uint32_t attempts;        /* 1, or 2 when the first table (sized from 2 n_tax) was too small and was rebuilt from the bound */
+    uint32_t reserved;
+    double t_device_ms;       /* table clear + count + compaction on the device, by events */
+} blu_report;
+
+/* The report of one run's records: `hits` gives the engine row ids (tax_row, or word 0 of the packed / packed64 records),
+ * n_hits, n_queries and on_device as for blu_consensus_run (the other columns are not read); results[n_queries] are its
+ * records (16-byte aligned); weights[n_queries] per-query weights or NULL (= 1 each), on the same side as the records.
+ * Device pointers: waits for `stream` (a hipStream_t, NULL = default) before reading them.  Host pointers: the records, the
+ * row of each record and the weights are uploaded.  Synchronous; the paths are on the host on return.  A record with a
+ * taxon whose reference row names no taxonomy row is BLU_ERR_INVALID_ARG; there is no CPU fallback. */
+int blu_consensus_report(const blu_taxonomy* tax, const blu_hits* hits, const blu_result* results, const uint32_t* weights,
+                         void* stream, blu_report* out);
+void blu_report_free(blu_report* report);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,6 +78,29 @@ int blu_build_consensus_identities_to_file(const char* blast_output_file, const 
                                            blu_pipeline_stats* stats);
 void blu_free_text(char* text);
 
+/* The use-case plus a taxon abundance report of its results in one run.  The document is what
+ * blu_build_consensus_identities_to_file (out_path != NULL) or blu_build_consensus_identities_cfg (out_path == NULL: into
+ * *out_text / *out_len) produces, byte for byte.  The report is counted on the device from the run's records
+ * (blu_consensus_report) and written to report->report_path after the document, tab-separated:
+ *   #percent  clade  direct  rank  identifier  taxonomy                 (header)
+ *   pct  U  U  -  unclassified  (empty)      always; U = weight of the results with "taxon": null (headers without hits too)
+ *   pct  N  N  -  unplaced  (empty)          when N > 0: results whose taxonomy is ""
+ *   one line per path, depth first; siblings by clade descending, then element text `rank__identifier` ascending (bytewise)
+ * percent = "%.2f" of 100.0 * clade / total (0.00 when total is 0).  Weights: BLU_REPORT_WEIGHT_ONE counts results;
+ * BLU_REPORT_WEIGHT_SIZE counts the dereplicated reads in the query name: the first ';'-field `size=<digits>`, else a
+ * `_size_<digits>` suffix, else 1 — a size of 2^32 or more is BLU_ERR_INVALID_ARG naming the query.  In strict mode a
+ * reference panic fails the call before either file is written. */
+enum blu_report_weight { BLU_REPORT_WEIGHT_ONE = 0, BLU_REPORT_WEIGHT_SIZE = 1 };
+typedef struct blu_report_params {
+    const char* report_path;   /* created or truncated */
+    int32_t weight;            /* enum blu_report_weight */
+    int32_t reserved;
+} blu_report_params;
+int blu_build_consensus_identities_report(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                          const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
+                                          const char* config_text, const char* out_path, const blu_report_params* report,
+                                          char** out_text, size_t* out_len, blu_pipeline_stats* stats);
+
 /* The text-ingest half alone (no GPU): DB JSON + outfmt-6 TSV -> SoA columns, as blu_build_consensus_identities does it.
  * Fills stats (rows, queries, taxids, unmatched rows, load times) and *checksum with an FNV-1a hash over every SoA
  * column, the segment offsets and the query names — identical for any BLU_INGEST_THREADS value.  For tests and for
