@@ -35,6 +35,13 @@
 //
 // Integer/compare work only: no MFMA.  HBM-bound: every bit-score is read (4 B/hit), the other 16 B/hit for top rows
 // only, one reference-row line and one 32-byte record per query.
+
+// gfx950 only: besides its cache-policy bits and LDS-DMA, the worklist handoff before the block ticket (end of the stream
+// kernel) waits for the wave's stores with s_waitcnt vmcnt, which counts stores on this architecture.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "consensus_kernel.hip is written for gfx950"
+#endif
+
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -45,84 +52,46 @@
 
 namespace blu {
 
-// Timing-only switches for attributing time / instruction counts to the phases of the stream kernel (make exp
-// FLAGS="-DBLU_EXPERIMENTS -DBLU_X_...=true"): they produce WRONG records.  The product build leaves them all false and
-// the compiler drops the tests.
-#ifndef BLU_EXPERIMENTS
-#define BLU_X_SKIP_PUSH false
-#define BLU_X_SKIP_STORES false
-#define BLU_X_SKIP_P1 false
-#define BLU_X_SKIP_2A false
-#define BLU_X_SKIP_2C false
-#define BLU_X_SKIP_RUNLEN false
-#define BLU_X_SKIP_LEVELS false
-#define BLU_X_SKIP_GATHER false
-#define BLU_X_SCAN_MIN false
-#else
-#ifndef BLU_X_SCAN_MIN
-#define BLU_X_SCAN_MIN false
-#endif
-#ifndef BLU_X_SKIP_P1
-#define BLU_X_SKIP_P1 false
-#endif
-#ifndef BLU_X_SKIP_PUSH
-#define BLU_X_SKIP_PUSH false
-#endif
-#ifndef BLU_X_SKIP_STORES
-#define BLU_X_SKIP_STORES false
-#endif
-#ifndef BLU_X_SKIP_2A
-#define BLU_X_SKIP_2A false
-#endif
-#ifndef BLU_X_SKIP_2C
-#define BLU_X_SKIP_2C false
-#endif
-#ifndef BLU_X_SKIP_RUNLEN
-#define BLU_X_SKIP_RUNLEN false
-#endif
-#ifndef BLU_X_SKIP_LEVELS
-#define BLU_X_SKIP_LEVELS false
-#endif
-#ifndef BLU_X_SKIP_GATHER
-#define BLU_X_SKIP_GATHER false
-#endif
-#endif
-
-
-// In-kernel stamps (experiment builds only: -DBLU_EXPERIMENTS -DBLU_X_STAMPS): s_memtime at the phase boundaries of the
-// stream kernel, summed per wave and written over the first records of `out` when the wave is done (scripts/stamps.py).
-#if defined(BLU_EXPERIMENTS) && defined(BLU_X_STAMPS)
-__device__ uint32_t g_stamps[8192 * 16];   // [wave][16]: cycles per phase, summed over the wave's tasks (read by blu_debug_stamps)
-#define STAMP_DECL uint64_t st_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; uint64_t st_prev = __builtin_amdgcn_s_memtime();
-#define STAMP(i) { const uint64_t st_now = __builtin_amdgcn_s_memtime(); st_sum[i] += st_now - st_prev; st_prev = st_now; }
-#define STAMP_DRAIN asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#else
-#define STAMP_DECL
-#define STAMP(i)
-#define STAMP_DRAIN
-#endif
-
 #define WAVE 64
-#ifndef BLOCK_A
-#define BLOCK_A 768   // 12 waves per CU (three per SIMD): what the per-wave LDS (ring 8 KiB + list) leaves room for
-#endif
-#define WAVES_A (BLOCK_A / WAVE)
-#ifndef BLOCK_N
-#define BLOCK_N 1024  // the kernel without the ring: 16 waves per CU (four per SIMD, 128 VGPRs)
-#endif
-#ifndef BLU_N_WAVES_PER_SIMD
-#define BLU_N_WAVES_PER_SIMD 4
-#endif
-#ifndef LIST_CAP
-#define LIST_CAP 208       // top-group entries per wave task (64 queries; mean ~183, sigma ~18 at geometric(0.35) groups)
-#endif
-#ifndef LIST_CAP_F64
-#define LIST_CAP_F64 232   // the same in the f64 layouts (4 more bytes per entry) with the ring: 11 waves per CU (BLOCK_F) so that a C3 task's top
-                           // rows (mean 183) fit one round — at 12 waves the list held 160 entries and most tasks took two
-#endif
-#ifndef BLOCK_F
-#define BLOCK_F 704        // f64 layouts, kernel with the ring
-#endif
+
+// ---- design constants -------------------------------------------------------
+// Stream kernel (kernel A): block size and occupancy per layout and kind (kernel with / without the bit-score ring)
+constexpr int BLOCK_A = 768;             // 12 waves per CU (three per SIMD): what the per-wave LDS (ring 8 KiB + list) leaves room for
+constexpr int BLU_WAVES_PER_SIMD = 3;    // one 768-thread block per CU: 168 VGPRs
+constexpr int BLOCK_N = 1024;            // the kernel without the ring: 16 waves per CU (four per SIMD, 128 VGPRs)
+constexpr int BLU_N_WAVES_PER_SIMD = 4;
+constexpr int BLOCK_F = 704;             // f64 layouts, kernel with the ring (11 waves per CU: see LIST_CAP_F64)
+constexpr int LIST_CAP = 208;            // top-group entries per wave task (64 queries; mean ~183, sigma ~18 at geometric(0.35) groups)
+constexpr int LIST_CAP_F64 = 232;        // the same in the f64 layouts (4 more bytes per entry) with the ring: 11 waves per CU (BLOCK_F) so that a C3 task's top
+                                         // rows (mean 183) fit one round — at 12 waves the list held 160 entries and most tasks took two
+// Phase 1
+constexpr uint32_t SHORT_SEG = 128u;     // segments up to here are streamed (4 .. 32 lanes per query); longer ones take the sparse long pass
+constexpr uint32_t MAX_TASK_SEG = 512u;  // longest segment the stream kernel takes (64 lanes x 4 rows, twice); longer ones go to the worklist
+constexpr uint32_t BLU_LONG_COST = 96u;  // lane-steps one query costs in the long pass (half a 64-lane step, not pipelined; 64 / 96 / 128 / 192 measured)
+constexpr uint32_t BLU_DENSE_Q = 3u;     // a dense step reads every record of its rows (four lanes per scanning lane) when at least 1 / BLU_DENSE_Q of them are top rows
+constexpr int BLU_STEP_SETS = 2;         // steps of the direct-load phase 1 issued together per iteration
+constexpr uint32_t FLAT_ROWS = 8u;       // rows per lane of a flat step (two 16-byte loads)
+constexpr uint32_t FLAT_SEG = 64u * FLAT_ROWS;   // longest segment the flat pass takes (64 lane units)
+constexpr uint32_t FLAT_STEPS = 8u;      // steps (of 64 units) a flat round takes at most: two registers per step and lane
+constexpr uint32_t FLAT_DEPTH = 4u;      // steps whose bit-scores are in flight together
+// The bit-score ring (see WaveLds)
+constexpr uint32_t RING_ROWS = 2048u;    // power of two, multiple of 256: the chunks of one step (up to 1792 rows + alignment slack) / what is requested ahead
+constexpr uint32_t RING_PAD = 32u;       // >= rows one lane scans in a step
+constexpr uint32_t RING_CHUNKS = RING_ROWS / 256u;
+constexpr uint32_t RING_MASK = RING_ROWS - 1u;
+// Cache-policy bits.  Plain (not nt) loads for the five columns: a 128-byte line is shared by consecutive queries (50 hits =
+// 200 B per 4-byte column), and with nt the line is dropped before the wave's next step needs its other half — measured
+// +12 % HBM read requests (TCC_EA0_RDREQ) and +10 % time.
+constexpr int STREAM_AUX = 0;
+#define RING_DMA_MOD " sc1 nt"           // the ring's DMA requests (spliced into the asm): every bit-score is read exactly once, so the stream
+                                         // should not displace the lineage rows (re-read ~4 times per run) from L2 / Infinity Cache: -6 % on C3
+constexpr int GATHER_AUX = 2;            // the gathered side records (2 = nt: read once as well)
+constexpr int RECORD_AUX = 18;           // the records (sc1 | nt, see the record stores)
+// Worklist kernel (kernel B)
+constexpr int BLOCK_B = 256;
+constexpr int BLU_B_WAVES_PER_SIMD = 7;  // 72 VGPRs, 28 waves per CU (it hides memory round trips with waves, not with registers).
+                                         // At 8 (64 VGPRs) every column-layout and cautious build parked 8-20 B per lane in scratch: the same time on
+                                         // C5 relaxed, 12 % slower on C5 cautious (0.471 -> 0.413 ms, scripts/calls/r4_call30.sh)
 
 // ---- cross-lane helpers -----------------------------------------------------
 __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
@@ -150,44 +119,6 @@ __device__ __forceinline__ int wave_min_i32(int x) {
     ROW_REDUCE(x, imin)
     return imin(imin(rl(x, 0), rl(x, 16)), imin(rl(x, 32), rl(x, 48)));
 }
-// Layouts (bit = LAYOUT) whose phase 2c reads the node id of the reported level back from the reference row's line — an L2
-// hit behind the eight loads that brought it — instead of keeping the row's 20 node ids in registers through the level
-// tests.  Measured, one box per pair: f64 side records 1.129 -> 1.031 ms (their build had 20 B/lane of scratch, none with
-// this), milli-percent columns 1.608 -> 1.437 (24 -> 8 B), f64 columns 1.410 -> 1.425 and the packed layout 0.953 -> 0.968
-// (no scratch either way: the extra round trip shows) — hence layout by layout: 1 and 3.
-// ... and every build of the kernel without the ring (128 VGPRs: its packed build goes from 60 to 40 B/lane of scratch;
-// uniform 1..200-row segments 0.947 -> 0.888 ms, C5 0.450 -> 0.441)
-// Where the row is not read back: levels whose node ids are kept in registers through phase 2c (the pick of the reported
-// level's id is a compare/select pair per kept level); a deeper reported level is read back.  12 instead of all 20 a
-// 128-byte row holds: C3 (8 levels) -1.0 %, zymo-like -2.1 %, C4 slice -1.3 % on one box (9: -0.4 / -2.1 / -1.3).
-#ifndef BLU_NID_REGS
-#define BLU_NID_REGS 12
-#endif
-#ifndef BLU_NODE_RELOAD_CAUTIOUS
-#define BLU_NODE_RELOAD_CAUTIOUS 1   // ... and every cautious build (12 B/lane of scratch in its packed ring build: C3 cautious 0.988 -> 0.921 ms, what relaxed takes)
-#endif
-#ifndef BLU_NODE_RELOAD_NORING
-#define BLU_NODE_RELOAD_NORING 1
-#endif
-#ifndef BLU_NODE_RELOAD_LAYOUTS
-#define BLU_NODE_RELOAD_LAYOUTS 0xAu
-#endif
-#ifndef BLU_FLAT_ALWAYS
-#define BLU_FLAT_ALWAYS 0   // experiment: every round of the kernel without the ring takes the flat pass
-#endif
-#ifndef BLU_FLAT_PASS
-#define BLU_FLAT_PASS 1
-#endif
-#ifndef FLAT_ROWS
-#define FLAT_ROWS 8u             // rows per lane of a flat step (two 16-byte loads)
-#endif
-#define FLAT_SEG (64u * FLAT_ROWS)   // longest segment the flat pass takes (64 lane units)
-#ifndef FLAT_STEPS
-#define FLAT_STEPS 8u            // steps (of 64 units) a flat round takes at most: two registers per step and lane
-#endif
-#ifndef FLAT_DEPTH
-#define FLAT_DEPTH 4u            // steps whose bit-scores are in flight together
-#endif
 __device__ __forceinline__ int iadd(int a, int b) { return a + b; }
 __device__ __forceinline__ int wave_sum_u32(uint32_t v) {
     int x = (int)v;
@@ -401,13 +332,9 @@ __device__ __forceinline__ uint32_t chain_count4(const uint4 c, const uint32_t h
 // Two vector instructions per row; as C++ ((mask << 1) | (b == M)) hipcc emits compare, select, or, shift — 3.5 per row — and the
 // scan is a third of the stream kernel's vector instructions.  (gfx950: a VALU read of a scalar pair needs two wait states
 // after the VALU write: the three instructions between a compare and its add cover them.)
-#ifndef BLU_ADDC_MASK
-#define BLU_ADDC_MASK 1
-#endif
 template <uint32_t N>
 __device__ __forceinline__ uint32_t tie_mask(const int (&b)[N], const int M) {
     static_assert(N % 8u == 0u, "two half masks, four rows per group each");
-#if BLU_ADDC_MASK
     // two accumulators (rows 0 .. N/2 - 1 and N/2 .. N - 1) so that consecutive adds do not depend on each other
     constexpr uint32_t H = N / 2u;
     uint32_t ma = 0, mb = 0;
@@ -436,12 +363,6 @@ __device__ __forceinline__ uint32_t tie_mask(const int (&b)[N], const int M) {
               [b2] "v"(b[H + i + 2]), [b3] "v"(b[H + i + 3]), [M] "v"(M));
     }
     return (ma << H) | mb;
-#else
-    uint32_t mask = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < N; ++i) mask = (mask << 1) | (uint32_t)(b[i] == M);
-    return mask;
-#endif
 }
 
 // ===============================================================================
@@ -468,90 +389,18 @@ __device__ __forceinline__ double pid_f64(typename PidKey<PID32>::type k) {
 #define KEYED_LEN_SHIFT 25u
 #define KEYED_PID_SHIFT 8u
 #define PM_MASK ((1u << KEY_PID_BITS) - 1u)
-#ifndef SHORT_SEG
-#define SHORT_SEG 128u           // segments up to here are streamed (4 .. 32 lanes per query); longer ones take the sparse long pass
-#endif
-#ifndef BLU_LONG_COST
-#define BLU_LONG_COST 96u   // lane-steps one query costs in the long pass (half a 64-lane step, not pipelined; 64 / 96 / 128 / 192 measured)
-#endif
-#ifndef BLU_DENSE_Q
-#define BLU_DENSE_Q 3u      // a dense step reads every record of its rows (four lanes per scanning lane) when at least 1 / BLU_DENSE_Q of them are top rows
-#endif
-#ifndef MAX_TASK_SEG
-#define MAX_TASK_SEG 512u        // longest segment the stream kernel takes (64 lanes x 4 rows, twice); longer ones go to the worklist
-#endif
-#ifndef BLOCK_B
-#define BLOCK_B 256
-#endif
 #define LONG_SPAN (1u << 28)    // rows one bit-score descriptor of the worklist kernel covers
-#ifndef BLU_B_WAVES_PER_SIMD
-#define BLU_B_WAVES_PER_SIMD 7   // worklist kernel: 72 VGPRs, 28 waves per CU (it hides memory round trips with waves, not with registers).
-                                 // At 8 (64 VGPRs) every column-layout and cautious build parked 8-20 B per lane in scratch: the same time on
-                                 // C5 relaxed, 12 % slower on C5 cautious (0.471 -> 0.413 ms, scripts/calls/r4_call30.sh)
-#endif
 #define KEEP_ROWS 1024u         // worklist kernel: a segment of up to this many rows is held in registers (4 x 16 bytes per lane)
 #define SLOT_CAP 256u           // worklist kernel: rows of a top group collected before their side records are gathered
 #define TASK_SPAN (1ull << 27)   // rows one task's buffer descriptors cover
 #define CUT_LDS 512        // distinct cutoff values kept in LDS (4 KiB); larger tables are read from global memory
 #define ROW_MASK ((1u << BLU_ROW_BITS) - 1u)
-// the five hit columns are read exactly once per run: non-temporal loads keep them from displacing the
-// lineage rows and cutoff tables (re-read by every query) in L2 / Infinity Cache
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// Plain (not nt) loads for the five columns: a 128-byte line is shared by consecutive queries (50 hits = 200 B per
-// 4-byte column), and with nt the line is dropped before the wave's next step needs its other half — measured
-// +12 % HBM read requests (TCC_EA0_RDREQ) and +10 % time.
-#define STREAM_AUX 0
-#ifndef RING_DMA_MOD
-#define RING_DMA_MOD " sc1 nt"   // cache-policy bits of the ring's DMA requests: every bit-score is read exactly once, so the stream
-                                 // should not displace the lineage rows (re-read ~4 times per run) from L2 / Infinity Cache: -6 % on C3
-#endif
-#ifndef GATHER_AUX
-#define GATHER_AUX 2         // cache-policy bits of the gathered side records (2 = nt: read once as well)
-#endif
-#ifndef RECORD_AUX
-#define RECORD_AUX 18  // sc1 | nt
-#endif
-#ifndef BLU_REF_NT
-#define BLU_REF_NT 0   // reference-row loads non-temporal (experiment)
-#endif
-#ifndef BLU_LANE_LAUNDER_LONG
-#define BLU_LANE_LAUNDER_LONG 0   // (the worklist kernel at 64 registers: laundering its lane id moved scratch from 8 to 28 B/lane in the packed build — off)
-#endif
-#ifndef BLU_PRIO_DENSE
-#define BLU_PRIO_DENSE 1   // dense steps of phase 1 (side records fetched and reduced by the scanning lanes) at raised wave priority: zymo-like
-                           // 1.217 -> 1.199 ms, all 50 hits tied 0.548 -> 0.528, C3 0.9554 -> 0.9527 (one box)
-#endif
-#ifndef BLU_PRIO_LONG
-#define BLU_PRIO_LONG 1   // the worklist kernel's finalisation (side-record gather, reference row, record) at raised wave priority: C5 0.4149 -> 0.4110 ms
-#endif
-#ifndef BLU_PRIO
-#define BLU_PRIO 4   // wave priority by phase (s_setprio): 0 = none; 4 = level 3 from the request of a task's side records to the request of
-                     // its reference rows — the stretch in which the wave is about to start its next memory round trip, and must not queue
-                     // behind other waves' scan arithmetic, whose data is prefetched anyway — then level 1 for the finalisation, 0 for the
-                     // scan.  One box, medians of seven: C3 0.9074 -> 0.8836 ms, zymo-like 1.179 -> 1.146, 10 hits per query 1.390 -> 1.335,
-                     // f64 side records 1.043 -> 1.021; modes 1 (level 2, back to 0), 2 (level 3), 3 (level 2 to the end of the task) and
-                     // 5 (3 / 2 / 0) within 0.5 % of it
-#endif
-#ifndef BLU_WIDE_RMQ
-#define BLU_WIDE_RMQ 0   // 1: wide groups ask the range-minimum tables as before round 4 (A/B and a test of the fallback)
-#endif
 
 // The bit-score stream of a task whose segments are all streamed goes through a per-wave LDS ring, filled by LDS-DMA
 // (buffer_load_dwordx4 ... lds: 1 KiB = 256 rows per wave instruction, no VGPR destination) well ahead of the steps that
 // read it, across task boundaries: a wave no longer pays a memory round trip per step.
-#ifndef BLU_MIXED_RING
-#define BLU_MIXED_RING 0
-#endif
-#ifndef BLU_MIXED_MAX_LPQ
-#define BLU_MIXED_MAX_LPQ 16u    // most lanes per query a task of mixed lengths may take to make its steps fit the ring
-#endif
-#ifndef RING_ROWS
-#define RING_ROWS 2048u          // power of two, multiple of 256: the chunks of one step (up to 1792 rows + alignment slack) / what is requested ahead
-#endif
-#define RING_PAD 32u              // >= rows one lane scans in a step
-#define RING_CHUNKS (RING_ROWS / 256u)
-#define RING_MASK (RING_ROWS - 1u)
 static_assert((RING_ROWS & RING_MASK) == 0 && RING_ROWS >= 1024u, "ring size");
 // A lane of a ring step scans RPL = 16 or 32 consecutive rows (16 for tasks of short segments, 32 otherwise: half as many
 // steps per task).  Lane descriptor in the list: top-row mask | first row (13 bits) | position / RPL (3 bits) — one word with
@@ -577,7 +426,7 @@ struct WaveLds : std::conditional_t<RING, NoFlatLds, FlatLds> {
     uint16_t pq[CAP];                       // position of the row in its segment
     uint32_t meta[WAVE + 4];    // first entry | k << 16, or META_SLOW
     uint2 seg[WAVE + 4];        // {first row relative to the task's first row, row count (0 if > MAX_TASK_SEG or outside the span)}
-    uint32_t vx[WAVE + 4];      // first row in the task's ring numbering (whole chunks inside longer segments are left out), [nq] = its end
+    uint32_t vx[WAVE + 4];      // first row in the task's ring numbering
 };
 
 // waits until at most k of the wave's vector-memory operations are outstanding (k is wave-uniform; s_waitcnt takes an immediate)
@@ -603,12 +452,6 @@ __device__ __forceinline__ void wait_vmcnt(uint32_t k) {
 }
 static_assert(RING_CHUNKS <= 16, "wait_vmcnt covers 0..15 younger chunks");
 
-#ifndef BLU_STEP_SETS
-#define BLU_STEP_SETS 2
-#endif
-#ifndef BLU_WAVES_PER_SIMD
-#define BLU_WAVES_PER_SIMD 3   // one 768-thread block per CU: 168 VGPRs
-#endif
 // LAYOUT: 0 = perc_identity f64 column, 1 = milli-percent u32 column, 2 = packed 16-byte side records
 // {tax_row, pident_milli | shape hint << 17, align_len, acc_rank} next to the bit-score column, 3 = 24-byte side records
 // {tax_row, shape hint << 17, align_len, acc_rank, perc_identity f64}
@@ -642,7 +485,7 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
         for (uint32_t i = threadIdx.x; i < t.n_cutvals; i += BLOCK_T) s_cut[i] = t.cutvals[i];
         __syncthreads();
     }
-    int lane = lane_id();   // (not const: see BLU_LANE_LAUNDER at the head of the task loop)
+    int lane = lane_id();   // (not const: see the head of the task loop)
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
     WaveLds<!PID32, RING>& L = s_lds[wib];
     const uint32_t wl_cap = wl_capacity(h.n_queries);
@@ -657,9 +500,6 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
     // the slowest wave does, and a piece costs less than a task.  (C4 slice, 1.25 M queries: 6 whole rounds + 1099 tasks
     // became 6 rounds + 3072 pieces of 24 queries; C2, 100 k queries, less than one round: 1563 tasks on 131 CUs became 2500
     // pieces of 40 on all CUs.)
-#ifndef BLU_TAIL_SPLIT
-#define BLU_TAIL_SPLIT 1
-#endif
     // (kept to three kernel-lifetime scalars — the whole rounds' task count and this wave's own piece: every further one costs
     // a register the ring build does not have)
     uint32_t t_full, tail_q0, tail_nq;
@@ -667,11 +507,8 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
         const uint32_t n_tasks64 = n_q32 / WAVE + ((n_q32 % WAVE) != 0u ? 1u : 0u);
         t_full = n_tasks64 / n_waves * n_waves;                         // tasks of the whole rounds
         const uint32_t q_full = t_full == n_tasks64 ? n_q32 : t_full * WAVE;
-        uint32_t tail_q = WAVE;                                         // (BLU_TAIL_SPLIT = 0: the tail as 64-query tasks, as before)
-        if (BLU_TAIL_SPLIT) {
-            tail_q = (((n_q32 - q_full) + n_waves - 1u) / n_waves + 7u) / 8u * 8u;   // (at most 64: the tail is less than a round)
-            tail_q = tail_q < 16u ? 16u : (tail_q > WAVE ? WAVE : tail_q);
-        }
+        uint32_t tail_q = (((n_q32 - q_full) + n_waves - 1u) / n_waves + 7u) / 8u * 8u;   // (at most 64: the tail is less than a round)
+        tail_q = tail_q < 16u ? 16u : (tail_q > WAVE ? WAVE : tail_q);
         const uint64_t p0 = (uint64_t)q_full + (uint64_t)wave * tail_q;   // this wave's piece of the tail
         tail_q0 = p0 < n_q32 ? (uint32_t)p0 : n_q32;
         tail_nq = n_q32 - tail_q0 < tail_q ? n_q32 - tail_q0 : tail_q;
@@ -700,23 +537,12 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(left < 0x80000000ull ? (uint32_t)left : 0x80000000u)), 0x00020000u};
     };
     const uint32_t ring_lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)L.ring);
-    auto ring_dma = [&](const u32x4 rs, const uint32_t c0, const uint32_t c, const uint32_t vc) {   // chunk c of the column into the slot of ring chunk vc: 64 lanes x 16 bytes, no VGPR destination
-        const uint32_t dst = ring_lds + (vc & (RING_CHUNKS - 1u)) * 1024u;
-        const uint32_t voff = (c - c0) * 1024u + (uint32_t)lane * 16u;
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen" RING_DMA_MOD " lds\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(dst), "s"(rs) : "memory");
-    };
     // chunks head .. lim - 1 (lim > head; ring numbering = column numbering) in one go: the loop is inside the asm statement —
-    // seven scalar instructions and one vector add per chunk where the C++ loop around ring_dma cost nineteen (m0 saved and
+    // seven scalar instructions and one vector add per chunk where a C++ loop of one-chunk requests cost nineteen (m0 saved and
     // restored per chunk, the slot address from scratch, the loop's own compares): the requests are a quarter of the stream
     // kernel's scalar instructions.  (The slot-address add into m0 is followed by the counter increment: the wait state an
     // LDS-DMA needs after a write of m0.)
-#ifndef BLU_DMA_RUN
-#define BLU_DMA_RUN 1
-#endif
     auto ring_dma_run = [&](const u32x4 rs, const uint32_t c0, uint32_t head, const uint32_t lim) {
-#if BLU_DMA_RUN
         uint32_t voff = (head - c0) * 1024u + (uint32_t)lane * 16u, keep, t;
         asm volatile("s_mov_b32 %[keep], m0\n"
                      "1:\n\t"
@@ -731,9 +557,6 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                      "s_mov_b32 m0, %[keep]"
                      : [keep] "=&s"(keep), [t] "=&s"(t), [head] "+s"(head), [voff] "+v"(voff)
                      : [cm] "n"(RING_CHUNKS - 1u), [base] "s"(ring_lds), [rs] "s"(rs), [lim] "s"(lim) : "memory", "scc");
-#else
-        for (; head < lim; ++head) ring_dma(rs, c0, head, head);
-#endif
     };
 
     // The offsets of a task are requested one task ahead (lane i: the row range of query q0 + i), so that their round
@@ -754,19 +577,19 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
     uint32_t task = wave;
     bool in_tail = task >= t_full, tail_done = false;
     load_seg(in_tail ? tail_q0 : task * WAVE, in_tail ? tail_nq : (uint32_t)WAVE, nx_off, nx_end);
-    STAMP_DECL
 
     for (; !in_tail || (tail_nq != 0u && !tail_done); tail_done = in_tail, task += n_waves, in_tail = task >= t_full) {
-#ifndef BLU_LANE_LAUNDER
-#define BLU_LANE_LAUNDER 1
-#endif
-        if (BLU_PRIO) __builtin_amdgcn_s_setprio(0);
-#if BLU_LANE_LAUNDER
+        // Wave priority by phase (s_setprio): 0 for the scan; 3 from the request of a task's side records to the request of its
+        // reference rows — the stretch in which the wave is about to start its next memory round trip, and must not queue
+        // behind other waves' scan arithmetic, whose data is prefetched anyway — then 1 for the finalisation.  One box, medians
+        // of seven, against no priorities: C3 0.9074 -> 0.8836 ms, zymo-like 1.179 -> 1.146, 10 hits per query 1.390 -> 1.335,
+        // f64 side records 1.043 -> 1.021; the other schedules tried (level 2 then back to 0, level 3 alone, level 2 to the end
+        // of the task, 3 / 2 / 0) within 0.5 % of it.
+        __builtin_amdgcn_s_setprio(0);
         // The lane id goes through an opaque statement once per task, so that nothing derived from it is loop-invariant to the
         // compiler: it had hoisted fifty-odd lane-derived addresses and masks (one instruction each to recompute) out of this loop
         // into registers of their own for the whole kernel — a third of the register file of a kernel that spills for lack of them.
         asm volatile("" : "+v"(lane));
-#endif
         const uint32_t q0_32 = in_tail ? tail_q0 : task * WAVE;
         const uint64_t q0 = q0_32;
         const uint32_t nq = in_tail ? tail_nq : (uint32_t)WAVE;
@@ -844,36 +667,8 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
         }
         const uint32_t task_nrows = (uint32_t)rl((int)task_rows, (int)nq - 1);   // rows of the whole task (contiguous tasks)
         const uint64_t vbase = (uint64_t)task_start + mis;                       // v of the task's first row
-        // Segments over SHORT_SEG rows are not read through the ring (long pass / worklist kernel): the whole chunks inside
-        // them are left out of the ring's numbering, so that a task of mixed lengths streams only what its steps read.
-        // Lane i (= query i): chunks left out before it (sk_before), where its own left-out chunks begin in the ring's
-        // numbering and how many are gone after it (ev_*), and its first row in that numbering (seg_x).
-        uint32_t sk_before = 0, ev_v = 0, ev_cum = 0, sk_total = 0;
-        bool ev_on = false;
-        if (BLU_MIXED_RING && contiguous && !all_short) {
-            const uint64_t v0 = vbase + (my_off - task_start), v1 = vbase + (my_end - task_start);
-            const uint32_t c_first = (uint32_t)((v0 + 255u) >> 8), c_past = (uint32_t)(v1 >> 8);
-            const uint32_t kq = ((uint32_t)lane < nq && (my_end - my_off) > SHORT_SEG && c_past > c_first) ? c_past - c_first : 0u;
-            uint32_t incl = kq;
-            incl += (uint32_t)dpp<0x111>((int)incl);
-            incl += (uint32_t)dpp<0x112>((int)incl);
-            incl += (uint32_t)dpp<0x114>((int)incl);
-            incl += (uint32_t)dpp<0x118>((int)incl);
-            const uint32_t t0 = (uint32_t)rl((int)incl, 15), t1 = (uint32_t)rl((int)incl, 31), t2 = (uint32_t)rl((int)incl, 47), t3 = (uint32_t)rl((int)incl, 63);
-            const uint32_t r16 = (uint32_t)lane >> 4;
-            incl += r16 == 0 ? 0u : (r16 == 1 ? t0 : (r16 == 2 ? t0 + t1 : t0 + t1 + t2));
-            sk_before = incl - kq;
-            sk_total = t0 + t1 + t2 + t3;
-            ev_on = kq != 0u;
-            ev_v = c_first - sk_before;
-            ev_cum = incl;
-        }
-        const uint32_t seg_x = (my_off - task_start) - 256u * sk_before;   // lane i: first row of query i in the ring's numbering, relative to the task
+        const uint32_t seg_x = my_off - task_start;   // lane i: first row of query i in the ring's numbering, relative to the task
         L.vx[lane] = seg_x;
-        auto ring_phys = [&](const uint32_t vc) {                               // chunk vc of the ring's numbering -> chunk of the column
-            const uint64_t m = __ballot(ev_on && ev_v <= vc);
-            return m ? vc + (uint32_t)rl((int)ev_cum, 63 - __builtin_clzll(m)) : vc;
-        };
         // ---------------- phase 1: LPQ lanes per query, 4 consecutive rows per lane, 64 / LPQ queries per step ----------------
         // LPQ is chosen per task from its longest segment: 4 lanes (<= 16 rows: blutils' own default is
         // max_target_seqs = 10), 8 (<= 32), 16 (<= 64), 32 (<= 128) or all 64 lanes (<= 256 rows: BLAST's own default
@@ -1329,12 +1124,8 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
         };
         auto ring_refill = [&]() {                              // request what the ring has room for, in chunk order
             if (ring_head < ring_tail) { ring_head = ring_tail; if (ring_landed < ring_tail) ring_landed = ring_tail; }
-            if (BLU_MIXED_RING && sk_total) {
-                while (ring_head < ring_end && ring_head - ring_tail < RING_CHUNKS) { ring_dma(rs_ring, ring_c0, ring_phys(ring_head), ring_head); ++ring_head; }
-            } else {
-                const uint32_t lim = ring_end < ring_tail + RING_CHUNKS ? ring_end : ring_tail + RING_CHUNKS;
-                if (ring_head < lim) { ring_dma_run(rs_ring, ring_c0, ring_head, lim); ring_head = lim; }   // (raised priority around these requests: no effect)
-            }
+            const uint32_t lim = ring_end < ring_tail + RING_CHUNKS ? ring_end : ring_tail + RING_CHUNKS;
+            if (ring_head < lim) { ring_dma_run(rs_ring, ring_c0, ring_head, lim); ring_head = lim; }   // (raised priority around these requests: no effect)
         };
         // FULL (every streamed segment of the round has at least RPL rows): the lane that would run past the end of its segment
         // takes the segment's LAST RPL rows instead — rows it shares with the lane before it are cleared from its top-row mask —
@@ -1356,15 +1147,13 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                 // the rows of this step lie back to back: [first row of query qb, first row of query qb + QPS)
                 const uint32_t r_lo = (uint32_t)rl((int)seg_x, (int)(qb < first_q ? first_q : qb));   // (queries before first_q are done)
                 const uint32_t qn = qb + QPS;
-                const uint32_t r_hi = qn < nq ? (uint32_t)rl((int)seg_x, (int)qn) : task_nrows - 256u * sk_total;
-                STAMP(1)
+                const uint32_t r_hi = qn < nq ? (uint32_t)rl((int)seg_x, (int)qn) : task_nrows;
                 ring_tail = (uint32_t)((vbase + r_lo) >> 8);
                 ring_refill();
                 if (r_hi > r_lo) {
                     const uint32_t need = (uint32_t)((vbase + r_hi - 1u) >> 8);
                     if (need >= ring_landed) { wait_vmcnt(ring_head - 1u - need); ring_mark_landed(need + 1u); }   // all but the chunks requested after `need`
                 }
-                STAMP(10)   // (waiting for ring data)
                 const uint32_t qi = qb + grp;
                 const uint2 sg = L.seg[qi];
                 const int left0 = (sg.y > short_seg ? 0 : (int)sg.y) - (int)sub;     // rows of the segment from this lane's nominal first row on
@@ -1396,7 +1185,6 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                 if (LPQ >= 4) M = imax(M, dpp<0x4E>(M));
                 if (LPQ >= 8) M = imax(M, dpp<0x141>(M));             // row_half_mirror
                 if (LPQ >= 16) M = imax(M, dpp<0x140>(M));            // row_mirror
-                if (BLU_X_SCAN_MIN) { if (sub == 0) L.meta[qi] = (uint32_t)M & 0xFFu; continue; }
                 uint32_t mask = tie_mask<RPL>(b, M);                  // bit RPL - 1 - i = row i ties on the query's top score
                 mask = left > 0 ? mask : 0u;
                 if constexpr (FULL) mask &= 0xFFFFFFFFu >> (32u - RPL + over);   // rows 0 .. over - 1 are the previous lane's
@@ -1416,11 +1204,10 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                 if (LPQ >= 4) gk += (uint32_t)dpp<0x4E>((int)gk);
                 if (LPQ >= 8) gk += (uint32_t)dpp<0x141>((int)gk);
                 if (LPQ >= 16) gk += (uint32_t)dpp<0x140>((int)gk);
-#ifndef BLU_DENSE_WHEN_FULL
-#define BLU_DENSE_WHEN_FULL 1
-#endif
-                if (PID32 && (BLU_DENSE_WHEN_FULL ? !fits : k0 + k1 + k2 + k3 > CAP)) {
-                    if (BLU_PRIO_DENSE) __builtin_amdgcn_s_setprio(2);   // (its record loads are round trips of the task's own chain)
+                if (PID32 && !fits) {
+                    // (raised wave priority: its record loads are round trips of the task's own chain — zymo-like 1.217 -> 1.199 ms,
+                    // all 50 hits tied 0.548 -> 0.528, C3 0.9554 -> 0.9527, one box)
+                    __builtin_amdgcn_s_setprio(2);
                     // ---- a DENSE step: the top rows of this step do not fit what is left of the list (many hits tie on the top
                     // score — identical database sequences; round 3: also when the steps before it have filled the list — that used
                     // to end the round and send the rest of the task through phase 1 again: tables with the reference's real
@@ -1571,7 +1358,7 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                         dn_k = (mine && dn_flag == 1u) ? f_gk : dn_k;   // (a query is reduced in one step only: dn_flag is this step's)
                     }
                     if (sub == 0 && gk != 0u) L.meta[qi] = META_DENSE;
-                    if (BLU_PRIO_DENSE) __builtin_amdgcn_s_setprio(0);
+                    __builtin_amdgcn_s_setprio(0);
                     continue;
                 }
                 uint32_t idx = rbase + incl - c;                      // list slot of this lane's first top row (file order)
@@ -1721,11 +1508,10 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
         if (RING && contiguous) {                                    // this task's chunks; what the task before requested ahead stays
             ring_c0 = (uint32_t)(vbase >> 8);
             rs_ring = ring_desc(ring_c0);
-            ring_end = task_nrows ? (uint32_t)((vbase + task_nrows - 1u) >> 8) + 1u - sk_total : ring_c0;
+            ring_end = task_nrows ? (uint32_t)((vbase + task_nrows - 1u) >> 8) + 1u : ring_c0;
             if (pref_q0 != q0_32) ring_head = ring_landed = ring_c0;
             ring_tail = ring_c0;
         }
-        STAMP(0)   // task set-up: offsets, descriptors, contiguity
         for (;;) {
         fill = 0;
         stop_q = WAVE;
@@ -1736,7 +1522,6 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
             const uint32_t rows = L.seg[lane].y;                    // this lane's query (0: empty, done, too long, or outside the span)
             const uint64_t live = __ballot(rows != 0u);
             first_q = live ? (uint32_t)__builtin_ctzll(live) : 0u;
-#ifndef BLU_FIXED_WIDTH
             // Width of the streamed pass.  Every streamed query pays the lanes of the widest one, so a few long segments
             // among short ones (Zipf-like hit counts) are cheaper in the long pass: estimated cost in lane-steps =
             // streamed queries x lanes per query + BLU_LONG_COST per query left to the long pass; smallest wins, ties to
@@ -1754,9 +1539,9 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                 if (c32 < best) { best = c32; short_seg = 32u; }
                 if (c16 < best) { best = c16; short_seg = 16u; }
             }
-#endif
             // Kernel without the ring: the round takes the flat pass when its units (at ~80 % of the lanes, + the gather) are fewer
-            // lane-steps than the cheapest width of the passes above plus their long pass
+            // lane-steps than the cheapest width of the passes above plus their long pass (the same cost model again, written
+            // as a minimum: sharing the block above changes the generated code)
             bool flat_round = false;
             if constexpr (!RING) {
                 const uint32_t n128 = (uint32_t)__builtin_popcountll(__ballot(rows != 0u && rows <= SHORT_SEG));
@@ -1772,33 +1557,16 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                     best = umin(best, 4u * n16 + BLU_LONG_COST * (n128 - n16));
                 }
                 const uint32_t units = (uint32_t)wave_sum_u32((rows + FLAT_ROWS - 1u) / FLAT_ROWS);
-                flat_round = BLU_FLAT_PASS && units != 0u && (BLU_FLAT_ALWAYS || units + units / 4u + 64u < best + BLU_LONG_COST * n_over);
+                flat_round = units != 0u && units + units / 4u + 64u < best + BLU_LONG_COST * n_over;
                 if (flat_round) { short_seg = FLAT_SEG; scan_rpl = 16u; }   // (scan_rpl: the descriptor format gather_list reads)
             }
             const uint32_t longest = flat_round ? 0u : wave_max_u32(rows > short_seg ? 0u : rows);   // longest streamed segment of the task
-            // (BLU_MIXED_RING: tasks that also hold longer segments through the ring, their whole chunks left out — correct
-            // (full GPU suite green with it) but no gain on C5, whose steps shrink to a few queries each: off)
-            ring_round = RING && contiguous && longest != 0u && (all_short ? __ballot(rows > short_seg) == 0ull : (bool)BLU_MIXED_RING);
+            ring_round = RING && contiguous && longest != 0u && all_short && __ballot(rows > short_seg) == 0ull;
             uint32_t lpq = 1;
             if (ring_round) {
                 scan_rpl = longest > 32u ? 32u : 16u;                     // rows per lane (measured on C3: 32 -3 %; on 10-hit tables: 16 -2.5 %)
                 while (lpq * scan_rpl < longest) lpq *= 2;                // lanes per query
                 while ((WAVE / lpq) * longest + 256u > RING_ROWS) lpq *= 2;   // and a step's rows (+ alignment slack) inside the ring
-                if (!all_short) {
-                    // a task of mixed lengths: the partial chunks of the longer segments between a step's queries count too —
-                    // fewer queries per step (more lanes per query) until every step's rows fit the ring, or no ring
-                    if ((uint32_t)lane == 0) L.vx[nq] = task_nrows - 256u * sk_total;
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                    for (;;) {
-                        const uint32_t qps = WAVE / lpq, qe = (uint32_t)lane + qps < nq ? (uint32_t)lane + qps : nq;
-                        const uint32_t span = L.vx[qe] - seg_x;
-                        if (__ballot((uint32_t)lane < nq && ((uint32_t)lane & (qps - 1u)) == 0u && span + 256u > RING_ROWS) == 0ull) break;
-                        if (lpq >= BLU_MIXED_MAX_LPQ) { ring_round = false; break; }
-                        lpq *= 2;
-                    }
-                }
             }
             list_round = ring_round || flat_round;
             if (list_round) {
@@ -1813,7 +1581,6 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                     else phase1_scan(std::integral_constant<uint32_t, 32>(), std::false_type(), lpq);
                 } else phase1_scan(std::integral_constant<uint32_t, 16>(), std::false_type(), lpq);
             }
-            else if (BLU_X_SKIP_P1) {}
             else if (flat_round) phase1_flat();
             else if (longest > 32u && longest <= 64u) phase1(std::integral_constant<uint32_t, 16>(), false);   // the C3 shape, specialised
             else if (longest) phase1(longest <= 16u ? 4u : (longest <= 32u ? 8u : 32u), longest >= (PACKED ? 9u : 25u));   // two-stage steps: measured break-even (packed records: 10 hits -2.5 %, 20 hits -17 %; columns: 20 hits +3 %, 30 hits -6 %)
@@ -1826,7 +1593,6 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        STAMP(1)   // phase 1
         // Last round of the task (nothing left pending): the ring is free, so the first chunks of the NEXT task are
         // requested now and travel while this task finishes (its offsets were requested when this task began).
         const bool last_round = __ballot(pend && (my_end - my_off) != 0u && (my_end - my_off) <= MAX_TASK_SEG && in_span && (L.meta[lane] & META_SLOW)) == 0ull;
@@ -1860,22 +1626,13 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                 pref_q0 = nx_q0;
             }
         };
-        if (BLU_PRIO) __builtin_amdgcn_s_setprio(BLU_PRIO == 2 || BLU_PRIO >= 4 ? 3 : 2);
-        if (list_round && !BLU_X_SKIP_GATHER) gather_list(prefetch_next);
+        __builtin_amdgcn_s_setprio(3);   // (see the head of the task loop)
+        if (list_round) gather_list(prefetch_next);
         else prefetch_next();
-        STAMP(2)   // next-task decision, gather issue + wait + list write
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 
-#if defined(BLU_EXPERIMENTS) && defined(BLU_X_PAD_VALU)
-        {   // (timing only: BLU_X_PAD_VALU independent vector instructions per round — is the kernel bound by instruction issue?)
-            uint32_t pad0 = (uint32_t)lane, pad1 = fill;
-#pragma unroll
-            for (int i = 0; i < BLU_X_PAD_VALU / 2; ++i) { asm volatile("v_add_u32 %0, %0, %0" : "+v"(pad0)); asm volatile("v_xor_b32 %0, %0, %0" : "+v"(pad1)); }
-            asm volatile("" ::"v"(pad0), "v"(pad1));
-        }
-#endif
         // ---------------- phase 2a: lane = query, LDS only ----------------
         // One pass over the list entries of every query at once: the trip count is the task's largest top group, a lane
         // whose group is shorter re-reads its last entry (every update below is idempotent), so there is no divergent
@@ -1883,7 +1640,7 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
         {
             const uint32_t nrows = my_end - my_off;
             const uint32_t m = L.meta[lane];
-            const bool listed = pend && nrows != 0 && nrows <= MAX_TASK_SEG && in_span && !(m & (META_SLOW | META_DENSE)) && !BLU_X_SKIP_2A;
+            const bool listed = pend && nrows != 0 && nrows <= MAX_TASK_SEG && in_span && !(m & (META_SLOW | META_DENSE));
             const uint32_t first = listed ? (m & 0xFFFFu) : 0u, k = listed ? ((m >> 16) & 0x3FFu) : 0u;
             const uint32_t kmax = wave_max_u32(k);
             // parse errors in file order (find_single_query_consensus.rs:51-64), then NaN perc_identity; reference row,
@@ -1983,12 +1740,11 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
             if (pend) {
                 bool done = true;
                 if (nrows == 0) { st_code = BLU_ST_NO_HITS; st_ref = 0xFFFFFFFFu; rec_kind = 2; }   // mod.rs:107-113
-                else if (nrows > MAX_TASK_SEG || !in_span) { if (!BLU_X_SKIP_PUSH) wl_push(wl_q, wl_cnt, (uint32_t)q); }
+                else if (nrows > MAX_TASK_SEG || !in_span) wl_push(wl_q, wl_cnt, (uint32_t)q);
                 else if (m & META_SLOW) done = false;   // its step did not fit the list this round: again in the next one
                 else if (dn_flag == 1) mode = dn_k == 1 ? 2u : 0u;                                    // reduced by a dense step
                 else if (dn_flag == 2) { st_code = dn_err; st_ref = row0 + dn_pos; rec_kind = 2; }
                 else if (dn_flag == 3) wl_push(wl_q, wl_cnt, (uint32_t)q);
-                else if (BLU_X_SKIP_2A) { mode = 2; r_row = L.rec[m & 0xFF].x & ROW_MASK; r_len = 5; minlen = 5; }
                 else if (err) { st_code = err; st_ref = row0 + err_pos; rec_kind = 2; }
                 else if (!PID32 && nan_pos != 0xFFFFFFFFu) { st_code = BLU_ST_ERR_BAD_PIDENT; st_ref = row0 + nan_pos; rec_kind = 2; }
                 else {
@@ -1999,7 +1755,6 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                 if (done) { pend = false; L.seg[lane].y = 0u; }   // later rounds skip it
             }
         }
-        STAMP(3)   // phase 2a
         const uint32_t pend_now = (uint32_t)__builtin_popcountll(__ballot(pend));
         if (pend_now == 0 || pend_now >= pend_before) break;      // all reduced, or a round without progress
         pend_before = pend_now;
@@ -2010,8 +1765,7 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
         if (pend) wl_push(wl_q, wl_cnt, (uint32_t)q);   // a single step larger than the whole list
 
         // ---------------- phase 2c: lane = query, cutoff tests and the record ----------------
-        if (BLU_X_SKIP_2C) { if (mode != 3) { st_code = mode; st_ref = r_row + minlen + r_pos + r_len + g_lo + g_hi; rec_kind = 2; } }
-        else if (mode != 3) {
+        if (mode != 3) {
             const bool single = mode == 2;
             rec_kind = 1;
             const uint32_t r_hint = (r_len >> 8) & ((1u << BLU_HINT_BITS) - 1u);
@@ -2028,42 +1782,33 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
             // side.  A wider group takes the wide-node tables (two L2 lookups, the first requested here, IN FRONT of the
             // reference row: vmcnt retires in issue order, so a lookup requested behind the row could not be used before the row
             // has arrived) — or, where those do not reach, the range-minimum tables, requested together with the row.
-            const bool spread = !single && g_lo < g_hi && !BLU_X_SKIP_RUNLEN;
+            const bool spread = !single && g_lo < g_hi;
             const uint32_t dl = r_row - g_lo, dh = g_hi - r_row;     // lo <= reference row <= hi
-#ifdef BLU_X_NO_WIDE
-            const bool wide = false;   // (timing only: wrong records for wide groups)
-#else
             const bool wide = spread && (dl > BLU_ROW_RUN_MAX || dh > BLU_ROW_RUN_MAX);   // saturated run lengths: not decidable from the row
-#endif
-            const bool wide_tab = wide && t.wblk != nullptr && !BLU_WIDE_RMQ;
+            const bool wide_tab = wide && t.wblk != nullptr;
             // (requesting the entry at the end of phase 2a instead, a hundred instructions earlier, changed nothing: 0.9866 vs 0.9863 ms)
             uint2 wentry = make_uint2(0u, 0u);
             if (wide_tab) wentry = t.wblk[g_lo >> BLU_WBLK_SHIFT];
             const uint32_t* ref = t.lin + (uint64_t)r_row * t.stride;   // sorted order: row index = pos
             const uint4* ref4 = reinterpret_cast<const uint4*>(ref);
-            constexpr bool NODE_RELOAD = ((BLU_NODE_RELOAD_LAYOUTS >> LAYOUT) & 1u) != 0u || (!RING && BLU_NODE_RELOAD_NORING) ||
-                                         (STRAT == BLU_CAUTIOUS && BLU_NODE_RELOAD_CAUTIOUS);
-            // node ids of the first NID_REGS levels stay in registers (words of the row that are loaded anyway); when a deeper level
-            // is the reported one its node id is read back from the row's line
-            constexpr uint32_t NID_REGS = NODE_RELOAD ? 0u : (uint32_t)BLU_NID_REGS;
+            // NODE_RELOAD: phase 2c reads the node id of the reported level back from the reference row's line — an L2 hit behind
+            // the eight loads that brought it — instead of keeping the row's node ids in registers through the level tests.
+            // Measured, one box per pair: f64 side records 1.129 -> 1.031 ms (their build had 20 B/lane of scratch, none with
+            // this), milli-percent columns 1.608 -> 1.437 (24 -> 8 B), f64 columns 1.410 -> 1.425 and the packed layout 0.953 ->
+            // 0.968 (no scratch either way: the extra round trip shows) — hence layout by layout: 1 and 3.  Also every build of the
+            // kernel without the ring (128 VGPRs: its packed build goes from 60 to 40 B/lane of scratch; uniform 1..200-row
+            // segments 0.947 -> 0.888 ms, C5 0.450 -> 0.441) and every cautious build (12 B/lane of scratch in its packed ring
+            // build: C3 cautious 0.988 -> 0.921 ms, what relaxed takes).
+            constexpr bool NODE_RELOAD = LAYOUT == 1 || LAYOUT == 3 || !RING || STRAT == BLU_CAUTIOUS;
+            // Otherwise the node ids of the first NID_REGS levels stay in registers (words of the row that are loaded anyway; the
+            // pick of the reported level's id is a compare/select pair per kept level) and a deeper reported level is read back.
+            // 12 instead of all 20 a 128-byte row holds: C3 (8 levels) -1.0 %, zymo-like -2.1 %, C4 slice -1.3 % on one box
+            // (9: -0.4 / -2.1 / -1.3).
+            constexpr uint32_t NID_REGS = NODE_RELOAD ? 0u : 12u;
             static_assert(NID_REGS <= 20u, "a 128-byte row holds 20 node ids");
             uint4 w[8];
-#if BLU_REF_NT
-            {
-                const u32x4* refv = reinterpret_cast<const u32x4*>(ref);
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { const u32x4 x = __builtin_nontemporal_load(refv + k); w[k] = make_uint4(x.x, x.y, x.z, x.w); }
-            }
-#elif defined(BLU_REF_AUX)
-            {   // (experiment: cache-policy bits on the reference-row loads; tables under 4 GB only)
-                const auto rs_lin = __builtin_amdgcn_make_buffer_rsrc((void*)t.lin, 0, (uint32_t)(t.n_tax * t.stride * 4u), 0x00020000);
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rs_lin, r_row * (t.stride * 4u) + 16u * k, 0, BLU_REF_AUX); w[k] = make_uint4(x.x, x.y, x.z, x.w); }
-            }
-#else
 #pragma unroll
             for (int k = 0; k < (NODE_RELOAD ? 3 : (int)((BLU_ROW_NODE_BASE + NID_REGS + 3u) / 4u)); ++k) w[k] = ref4[k];
-#endif
             // What the finalisation needs per LEVEL depends on the row's shape only (TaxDev::kthr: threshold, rank code and
             // max-allowed-rank bit in one word per level).  In the packed layout the side record of the reference hit carries
             // the shape as a hint, so those words are requested NOW, together with the row, instead of after it: one memory
@@ -2095,9 +1840,7 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                 }
                 if (wn == 0xFFFFFFFFu) d_tab = shared_levels(t, g_lo, g_hi);
             } else if (wide) d_tab = shared_levels(t, g_lo, g_hi);
-            if (BLU_PRIO && BLU_PRIO != 3) __builtin_amdgcn_s_setprio(BLU_PRIO == 4 || BLU_PRIO == 6 ? 1 : (BLU_PRIO == 5 ? 2 : 0));
-            STAMP_DRAIN
-            STAMP(4)   // reference rows arrive
+            __builtin_amdgcn_s_setprio(1);   // (see the head of the task loop)
             r_hdr = w[0].x;   // (requesting it back in phase 2a costs a second fetch: the line leaves L2 in between)
             // its length field equals the id's for a well-formed id and bounds the loops for a corrupt one
             const uint32_t len_ref = umin(r_len, r_hdr & 0xFF);
@@ -2116,7 +1859,6 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                 if (cnt >= BLU_ROW_IV_LEVELS && minlen > BLU_ROW_IV_LEVELS) d = umin(minlen, shared_levels(t, g_lo, g_hi));   // agreement deeper than the row's run lengths
                 else d = umin(minlen, cnt);
             }
-            STAMP(5)   // shared levels from the run lengths (or the RMQ tables)
             const bool agree = single | (d >= minlen);
             if (!agree && d == 0) { st_code = BLU_ST_ERR_ROOT_DISAGREE; st_ref = row0 + r_pos; rec_kind = 2; }   // `index - 1` underflow (:181)
             else {
@@ -2152,8 +1894,6 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
 #pragma unroll
                         for (int k = 0; k < 4; ++k) ck[k] = lvl4[k];
                     }
-                    STAMP_DRAIN
-                    STAMP(6)   // (5: run lengths / RMQ) level words arrive
                     // bit j of NGE / NGT: identity < / <= the cutoff of level j.  ident_k - threshold is negative exactly then, and
                     // v_alignbit shifts that sign bit into the mask: two instructions per test, levels taken from the deepest down
                     // so that level 0 ends in bit 0.  No dependence between levels.
@@ -2170,7 +1910,7 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                     {
                         uint32_t nge = 0, ngt = 0;
 #pragma unroll
-                        for (int k = (BLU_X_SKIP_LEVELS ? -1 : 3); k >= 0; --k) test4(ck[k], nge, ngt);
+                        for (int k = 3; k >= 0; --k) test4(ck[k], nge, ngt);
                         NGE = nge & 0xFFFFu; NGT = ngt & 0xFFFFu;
                     }
                     for (uint32_t k = 4; 4 * k < len_ref; ++k) {   // lineages deeper than 16 levels
@@ -2216,10 +1956,8 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                     };
 #pragma unroll
                     for (int k = 0; k < 4; ++k) c[k] = codes4[k];
-                    STAMP_DRAIN
-                    STAMP(6)   // (5: run lengths / RMQ) codes arrive
 #pragma unroll
-                    for (int k = 0; k < (BLU_X_SKIP_LEVELS ? 0 : 4); ++k) { level(4 * k, c[k].x); level(4 * k + 1, c[k].y); level(4 * k + 2, c[k].z); level(4 * k + 3, c[k].w); }
+                    for (int k = 0; k < 4; ++k) { level(4 * k, c[k].x); level(4 * k + 1, c[k].y); level(4 * k + 2, c[k].z); level(4 * k + 3, c[k].w); }
                     for (uint32_t k = 4; 4 * k < len_ref; ++k) {   // lineages deeper than 16 levels
                         const uint4 x = codes4[k]; level(4 * k, x.x); level(4 * k + 1, x.y); level(4 * k + 2, x.z); level(4 * k + 3, x.w);
                     }
@@ -2239,7 +1977,7 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                 };
                 // node id of level j: words 11..30 of the line are in registers, deeper levels are read from the row
                 auto node_of = [&](uint32_t j) {
-                    if (NODE_RELOAD) return ref[BLU_ROW_NODE_BASE + j];   // (read back from the row's line: see BLU_NODE_RELOAD_LAYOUTS)
+                    if (NODE_RELOAD) return ref[BLU_ROW_NODE_BASE + j];   // (read back from the row's line: see NODE_RELOAD)
                     uint32_t v = 0;
                     if (j >= NID_REGS) v = ref[BLU_ROW_NODE_BASE + j];
 #pragma unroll
@@ -2277,10 +2015,8 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                 }
             }
         }
-        STAMP(7)   // levels, record
         // what was requested ahead for the next task has to be in the ring before that task counts its own requests
         if (ring_landed < ring_head) { wait_vmcnt(0u); ring_mark_landed(ring_head); }
-        STAMP(8)   // drain of the requests made ahead
         // ---------------- records: staged through LDS, stored as two fully coalesced 1 KiB rows ----------------
         // (a 32-byte record per lane straight to memory is 64 scattered 16-byte pieces per store instruction;
         // measured: 0.7 ms of a 2.7 ms launch.)  The list area is dead after phase 2a and is reused.
@@ -2301,7 +2037,7 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const uint32_t c = (uint32_t)lane + 64u * half, qc = c >> 1;
-            if (qc < nq && L.meta[qc] && !BLU_X_SKIP_STORES) {
+            if (qc < nq && L.meta[qc]) {
                 const uint4 v = rec[c];
                 const u32x4 w = {v.x, v.y, v.z, v.w};
                 __builtin_amdgcn_raw_buffer_store_b128(w, rs_out, c * 16u, 0, RECORD_AUX);
@@ -2309,16 +2045,7 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
-        STAMP(9)   // record staging and stores
     }
-#if defined(BLU_EXPERIMENTS) && defined(BLU_X_STAMPS)
-    if (lane < 12 && wave < 8192) {
-        uint32_t v = 0;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) v = lane == i ? (uint32_t)st_sum[i] : v;
-        g_stamps[wave * 16 + lane] = v;
-    }
-#endif
     // The last block to finish publishes the queue length for the worklist kernel and zeroes the two counters: a run
     // leaves them as it found them — no memset between runs, and a captured graph of the kernels can be replayed.  The length
     // also goes to a pinned host word: the next call on this table launches no worklist kernel when it was (next to) nothing
@@ -2409,7 +2136,7 @@ template <int STRAT, int LAYOUT>
 __device__ __forceinline__ void consensus_of_long_query(const HitsDev& h, const TaxDev& t, blu_result* __restrict__ out, const uint64_t q,
                                                         uint32_t* const slot, const int lane) {
     constexpr bool PID32 = LAYOUT == 1 || LAYOUT == 2, PACKED = LAYOUT == 2, WIDE = LAYOUT == 3;
-    if (BLU_PRIO_LONG) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     uint64_t start = h.seg_off[q], end = h.seg_off[q + 1];
     if (end > h.n_hits) end = h.n_hits;
     if (start > end) start = end;
@@ -2583,7 +2310,9 @@ __device__ __forceinline__ void consensus_of_long_query(const HitsDev& h, const 
     }
     }
     }   // (segments over KEEP_ROWS rows)
-    if (BLU_PRIO_LONG) __builtin_amdgcn_s_setprio(2);   // (the round trips of the finalisation in front of other waves' streaming passes)
+    // the finalisation (side-record gather, reference row, record) at raised wave priority: its round trips go in front of other
+    // waves' streaming passes (C5 0.4149 -> 0.4110 ms)
+    __builtin_amdgcn_s_setprio(2);
     if (kk) flush();
     {
         const uint32_t first_err = wave_min_u32(l_err_row);
@@ -2682,11 +2411,9 @@ __global__ __launch_bounds__(BLOCK_B, BLU_B_WAVES_PER_SIMD) void blu_consensus_l
     const uint32_t cap = wl_capacity(h.n_queries);
     const uint32_t incl = wave_incl_scan_u32(work_count[WL_BASE + (uint32_t)lane * WL_STRIDE + 1u]);   // lane = queue: its published length
     for (uint32_t wi = wave; wi < n_work; wi += n_waves) {
-        int lane_q = lane;
-#if BLU_LANE_LAUNDER_LONG
-        asm volatile("" : "+v"(lane_q));   // (nothing derived from the lane id is loop-invariant: see the stream kernel's task loop)
-#endif
-        consensus_of_long_query<STRAT, LAYOUT>(h, t, out, (uint64_t)wl_entry(worklist, cap, incl, wi), slot, lane_q);
+        // (the lane id is not laundered here as in the stream kernel's task loop: at 64 registers that moved scratch from 8 to
+        // 28 B/lane in the packed build)
+        consensus_of_long_query<STRAT, LAYOUT>(h, t, out, (uint64_t)wl_entry(worklist, cap, incl, wi), slot, lane);
     }
 }
 
@@ -2759,7 +2486,7 @@ static int launch_t(const TaxDev& tax, const HitsDev& hits, blu_result* out, hip
     const uint32_t forced = ((known_kind == 1u || known_kind == 2u) ? 1u : 0u) | (no_long ? 2u : 0u);
     if (known_kind != 2u) {
         constexpr uint32_t block_r = (LAYOUT == 0 || LAYOUT == 3) ? BLOCK_F : BLOCK_A;
-        const uint64_t want = BLU_TAIL_SPLIT ? (hits.n_queries + 16ull * (block_r / WAVE) - 1) / (16ull * (block_r / WAVE)) : (n_tasks + (block_r / WAVE) - 1) / (block_r / WAVE);
+        const uint64_t want = (hits.n_queries + 16ull * (block_r / WAVE) - 1) / (16ull * (block_r / WAVE));
         const uint32_t grid = (uint32_t)(want < cus ? (want ? want : 1) : cus);
         g_grid = grid;
         g_block = block_r;
@@ -2767,7 +2494,7 @@ static int launch_t(const TaxDev& tax, const HitsDev& hits, blu_result* out, hip
     }
     if (known_kind != 1u) {
         constexpr uint32_t block_n = (LAYOUT == 0 || LAYOUT == 3) ? BLOCK_A : BLOCK_N;
-        const uint64_t want = BLU_TAIL_SPLIT ? (hits.n_queries + 16ull * (block_n / WAVE) - 1) / (16ull * (block_n / WAVE)) : (n_tasks + (block_n / WAVE) - 1) / (block_n / WAVE);
+        const uint64_t want = (hits.n_queries + 16ull * (block_n / WAVE) - 1) / (16ull * (block_n / WAVE));
         const uint32_t grid = (uint32_t)(want < cus ? (want ? want : 1) : cus);
         if (known_kind == 2u) { g_grid = grid; g_block = block_n; }
         hipLaunchKernelGGL((blu_consensus_stream_kernel<STRAT, LAYOUT, false>), dim3(grid), dim3(block_n), 0, s, hits, tax, out, worklist, work_count, forced, host_len);
@@ -2799,9 +2526,3 @@ int launch_consensus(const TaxDev& tax, const HitsDev& hits, int strategy, blu_r
 }
 
 }  // namespace blu
-
-#if defined(BLU_EXPERIMENTS) && defined(BLU_X_STAMPS)
-extern "C" int blu_debug_stamps(uint32_t* dst, size_t n_words) {   // experiment builds only (scripts/stamps.py)
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(blu::g_stamps), n_words * sizeof(uint32_t), 0, hipMemcpyDeviceToHost);
-}
-#endif
