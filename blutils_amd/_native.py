@@ -14,7 +14,7 @@ EXPORTS = (
     "blu_taxonomy_n_shapes", "blu_taxonomy_n_rank_codes", "blu_taxonomy_max_depth", "blu_taxonomy_device_bytes",
     "blu_taxonomy_rank_name", "blu_taxonomy_row_cutoffs", "blu_taxonomy_lookup", "blu_taxonomy_row_map", "blu_consensus_run",
     "blu_consensus_last_launch", "blu_hits_pack", "blu_hits_pack64", "blu_taxonomy_shared_levels", "blu_taxonomy_trim",
-    "blu_consensus_report", "blu_report_free",
+    "blu_consensus_report", "blu_report_free", "blu_dev_exclusive_scan", "blu_dev_radix_sort_pairs", "blu_dev_line_index",
 )
 # include/blu_pipeline.h
 PIPELINE_EXPORTS = ("blu_build_consensus_identities", "blu_free_text", "blu_custom_taxon_from_file", "blu_ingest_only",
@@ -102,6 +102,13 @@ def lib() -> C.CDLL:
         L.blu_taxonomy_shared_levels.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
         L.blu_taxonomy_trim.restype = C.c_int
         L.blu_taxonomy_trim.argtypes = [C.c_void_p]
+    if hasattr(L, "blu_dev_exclusive_scan"):
+        L.blu_dev_exclusive_scan.restype = C.c_int
+        L.blu_dev_exclusive_scan.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+        L.blu_dev_radix_sort_pairs.restype = C.c_int
+        L.blu_dev_radix_sort_pairs.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]
+        L.blu_dev_line_index.restype = C.c_int
+        L.blu_dev_line_index.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.blu_consensus_last_launch.restype = C.c_int
     L.blu_consensus_last_launch.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     _lib = L

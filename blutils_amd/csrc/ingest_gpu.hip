@@ -177,7 +177,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_apply(const T* __restrict__
     for (int k = 0; k < SCAN_ITEMS; ++k) { if (base + k < n) out[base + k] = run; run += x[k]; }
 }
 template <class T> size_t scan_tmp_bytes(size_t n) { return 2 * ((n + SCAN_BLOCK - 1) / SCAN_BLOCK) * sizeof(T) + 16; }
-// out[i] = in[0] + ... + in[i - 1] for i < n (in and out distinct); tmp: scan_tmp_bytes<T>(n) bytes of device memory
+// out[i] = in[0] + ... + in[i - 1] for i < n, modulo 2^(8 sizeof(T)); in == out is allowed: scan_block_sums only reads, and
+// scan_apply reads each element into a register of the thread that writes it back (tests/test_gpu_prims.py checks both
+// ways).  tmp: scan_tmp_bytes<T>(n) bytes of device memory
 template <class T>
 hipError_t exclusive_scan_dev(const T* in, T* out, size_t n, void* tmp) {
     if (n == 0) return hipSuccess;
@@ -244,8 +246,8 @@ __global__ __launch_bounds__(RS_THREADS) void radix_scatter(const uint32_t* __re
     }
 }
 
-// sorts n pairs by the low `bits` bits of the key; the sorted arrays are (*keys, *vals) on return (the two buffers of each swap roles
-// per pass).  table: 2 x 256 x ceil(n / 4096) words of device memory; scan_tmp: scan_tmp_bytes<uint32_t>(256 x ceil(n / 4096))
+// sorts n pairs by the low 8 * ceil(bits / 8) bits of the key (callers pass keys < 2^bits, so: by the key); the sorted arrays are
+// (*keys, *vals) on return (the two buffers of each swap roles per pass).  table: 2 x 256 x ceil(n / 4096) words of device memory; scan_tmp: scan_tmp_bytes<uint32_t>(256 x ceil(n / 4096))
 static hipError_t radix_sort_pairs_dev(uint32_t** keys, uint32_t** keys_alt, uint32_t** vals, uint32_t** vals_alt, uint32_t n, int bits,
                                        uint32_t* table, void* scan_tmp) {
     if (n == 0) return hipSuccess;
@@ -1489,3 +1491,109 @@ done:
 }
 
 }  // namespace blu
+
+// ---- (introspection) the primitives above on their own (include/blu_consensus.h: blu_dev_*), for the tests: each call
+// synchronises the device on entry and on return and allocates its own scratch.  The product paths call blu:: directly.
+using namespace blu;
+
+namespace {
+
+struct DevCall {
+    std::vector<void*> ptrs;
+    ~DevCall() { for (void* p : ptrs) (void)hipFree(p); }
+    hipError_t alloc(void** p, size_t bytes) {
+        const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
+        if (e == hipSuccess) ptrs.push_back(*p);
+        return e;
+    }
+};
+
+int dev_enter(int device, const char* who) {
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipSetDevice(%d) failed", who, device); return BLU_ERR_NO_DEVICE; }
+    const hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) { set_error("%s: hipDeviceSynchronize failed: %s", who, hipGetErrorString(e)); return BLU_ERR_HIP; }
+    return BLU_OK;
+}
+
+int dev_fail(const char* who, const char* what, hipError_t e) {
+    (void)hipGetLastError();
+    if (e == hipErrorOutOfMemory) { set_error("%s: %s: out of device memory", who, what); return BLU_ERR_ALLOC; }
+    set_error("%s: %s failed: %s", who, what, hipGetErrorString(e));
+    return BLU_ERR_HIP;
+}
+
+}  // namespace
+
+#define DEVCHK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return dev_fail(WHO, #x, e_); } while (0)
+
+extern "C" {
+
+int blu_dev_exclusive_scan(int device, const void* in, void* out, uint64_t n, int elem_bytes) {
+    static const char WHO[] = "blu_dev_exclusive_scan";
+    if ((elem_bytes != 4 && elem_bytes != 8) || (n && (!in || !out))) { set_error("%s: invalid argument", WHO); return BLU_ERR_INVALID_ARG; }
+    if (const int rc = dev_enter(device, WHO)) return rc;
+    DevCall c;
+    void* tmp = nullptr;
+    DEVCHK(c.alloc(&tmp, elem_bytes == 4 ? scan_tmp_bytes_u32(n) : scan_tmp_bytes_u64(n)));
+    if (elem_bytes == 4) DEVCHK(exclusive_scan_u32((const uint32_t*)in, (uint32_t*)out, n, tmp));
+    else DEVCHK(exclusive_scan_u64((const unsigned long long*)in, (unsigned long long*)out, n, tmp));
+    DEVCHK(hipDeviceSynchronize());
+    return BLU_OK;
+}
+
+int blu_dev_radix_sort_pairs(int device, uint32_t* keys, uint32_t* vals, uint32_t n, int bits) {
+    static const char WHO[] = "blu_dev_radix_sort_pairs";
+    if (bits < 0 || bits > 32 || (n && (!keys || !vals))) { set_error("%s: invalid argument", WHO); return BLU_ERR_INVALID_ARG; }
+    if (const int rc = dev_enter(device, WHO)) return rc;
+    if (n == 0) return BLU_OK;
+    DevCall c;
+    uint32_t *keys_alt = nullptr, *vals_alt = nullptr, *table = nullptr;
+    void* tmp = nullptr;
+    DEVCHK(c.alloc((void**)&keys_alt, (size_t)n * 4));
+    DEVCHK(c.alloc((void**)&vals_alt, (size_t)n * 4));
+    DEVCHK(c.alloc((void**)&table, radix_table_words(n) * 4));
+    DEVCHK(c.alloc(&tmp, radix_scan_tmp_bytes(n)));
+    uint32_t *k = keys, *ka = keys_alt, *v = vals, *va = vals_alt;
+    DEVCHK(radix_sort_pairs(&k, &ka, &v, &va, n, bits, table, tmp));
+    if (k != keys) {   // an odd number of passes: the result is in the scratch pair
+        DEVCHK(hipMemcpy(keys, k, (size_t)n * 4, hipMemcpyDeviceToDevice));
+        DEVCHK(hipMemcpy(vals, v, (size_t)n * 4, hipMemcpyDeviceToDevice));
+    }
+    DEVCHK(hipDeviceSynchronize());
+    return BLU_OK;
+}
+
+int blu_dev_line_index(int device, const unsigned char* text, uint64_t size, uint64_t* line, uint64_t cap, uint64_t* n_newlines) {
+    static const char WHO[] = "blu_dev_line_index";
+    if (!n_newlines || (size && !text) || ((uintptr_t)text & 15u) || (cap && !line)) { set_error("%s: invalid argument", WHO); return BLU_ERR_INVALID_ARG; }
+    *n_newlines = 0;
+    if (const int rc = dev_enter(device, WHO)) return rc;
+    const uint64_t n_tiles = line_tiles(size);
+    DevCall c;
+    uint32_t *d_tile = nullptr, *d_tile_base = nullptr;
+    void* tmp = nullptr;
+    DEVCHK(c.alloc((void**)&d_tile, (n_tiles + 1) * 4));
+    DEVCHK(c.alloc((void**)&d_tile_base, (n_tiles + 1) * 4));
+    DEVCHK(c.alloc(&tmp, scan_tmp_bytes_u32(n_tiles + 1)));
+    DEVCHK(line_count_tiles(text, size, d_tile));
+    // the total in 64 bits on the host: the device scan of the tile counts is u32 and must not wrap
+    std::vector<uint32_t> tiles(n_tiles);
+    if (n_tiles) DEVCHK(hipMemcpy(tiles.data(), d_tile, n_tiles * 4, hipMemcpyDeviceToHost));
+    uint64_t total = 0;
+    for (uint32_t t : tiles) total += t;
+    *n_newlines = total;
+    if (total > 0xFFFFFFFFull || total + 1 > cap) {
+        set_error("%s: %llu newlines need %llu line entries (cap %llu, at most 2^32 newlines)", WHO, (unsigned long long)total,
+                  (unsigned long long)(total + 1), (unsigned long long)cap);
+        return BLU_ERR_INVALID_ARG;
+    }
+    DEVCHK(hipMemset(d_tile + n_tiles, 0, 4));
+    DEVCHK(exclusive_scan_u32(d_tile, d_tile_base, n_tiles + 1, tmp));
+    DEVCHK(hipMemset(line, 0, 8));
+    DEVCHK(line_write_starts(text, size, d_tile_base, line));
+    DEVCHK(hipDeviceSynchronize());
+    return BLU_OK;
+}
+
+}  // extern "C"
+#undef DEVCHK

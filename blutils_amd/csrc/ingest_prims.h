@@ -20,14 +20,17 @@ hipError_t line_count_tiles(const unsigned char* d_text, uint64_t size, uint32_t
 // d_line[k + 1] = offset after newline k, from the exclusive scan of the tile counts; d_line[0] is the caller's
 hipError_t line_write_starts(const unsigned char* d_text, uint64_t size, const uint32_t* d_tile_base, uint64_t* d_line);
 
-// ---- device-wide exclusive prefix sums: out[i] = in[0] + ... + in[i - 1]; tmp = scan_tmp_bytes_*(n) bytes
+// ---- device-wide exclusive prefix sums: out[i] = in[0] + ... + in[i - 1] (wrapping); tmp = scan_tmp_bytes_*(n) bytes.
+// in == out is allowed (every element is read and written by the same thread, after the block sums are taken)
 size_t scan_tmp_bytes_u32(size_t n);
 size_t scan_tmp_bytes_u64(size_t n);
 hipError_t exclusive_scan_u32(const uint32_t* in, uint32_t* out, size_t n, void* tmp);
 hipError_t exclusive_scan_u64(const unsigned long long* in, unsigned long long* out, size_t n, void* tmp);
 
-// ---- stable LSD radix sort of (key, value) pairs by the low `bits` bits of the key, 8 bits per pass; the sorted pairs
-// are (*keys, *vals) on return.  table: radix_table_words(n) words; scan_tmp: radix_scan_tmp_bytes(n) bytes
+// ---- stable LSD radix sort of (key, value) pairs, 8 bits per pass, ceil(bits / 8) passes: the pairs end ordered by the low
+// 8 * ceil(bits / 8) bits of the key (equal keys in input order), which is the whole key for the keys < 2^bits the callers
+// must pass.  bits = 0: no pass.  The sorted pairs are (*keys, *vals) on return (the alternate buffers after an odd number
+// of passes).  table: radix_table_words(n) words; scan_tmp: radix_scan_tmp_bytes(n) bytes
 size_t radix_table_words(uint32_t n);
 size_t radix_scan_tmp_bytes(uint32_t n);
 hipError_t radix_sort_pairs(uint32_t** keys, uint32_t** keys_alt, uint32_t** vals, uint32_t** vals_alt, uint32_t n, int bits,

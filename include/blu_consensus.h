@@ -215,6 +215,24 @@ int blu_taxonomy_shared_levels(const blu_taxonomy* tax, uint32_t lo, uint32_t hi
  * allocates what it needs again.  No run on the handle may be in flight. */
 int blu_taxonomy_trim(const blu_taxonomy* tax);
 
+/* (introspection) The device primitives the GPU ingest, the database builders and the report stand on
+ * (csrc/ingest_gpu.hip), callable on their own so that they can be checked against plain references.  Arrays are
+ * device pointers on `device` (n_newlines is a host pointer).  Each call synchronises the device on entry and on return, allocates its own scratch,
+ * and returns a blu_error code (BLU_ERR_INVALID_ARG for a bad argument, BLU_ERR_ALLOC, BLU_ERR_HIP).
+ *
+ * Exclusive prefix sum out[i] = in[0] + ... + in[i - 1] (i < n) of n unsigned integers of elem_bytes = 4 or 8 bytes,
+ * modulo 2^(8 elem_bytes); in == out is allowed. */
+int blu_dev_exclusive_scan(int device, const void* in, void* out, uint64_t n, int elem_bytes);
+/* Stable LSD radix sort of n (key, value) pairs in place, 8 bits per pass, ceil(bits / 8) passes (bits 0..32): the
+ * pairs end in the order of the low 8 ceil(bits / 8) bits of the key, equal keys in their input order.  Callers pass
+ * keys below 2^bits. */
+int blu_dev_radix_sort_pairs(int device, uint32_t* keys, uint32_t* vals, uint32_t n, int bits);
+/* Line index of text[0, size): *n_newlines = the '\n' bytes in it; line[0] = 0 and line[k + 1] = the offset after
+ * newline k.  `text` is 16-byte aligned and readable (padded) for at least 64 bytes past `size`; bytes past `size` are
+ * never counted.  The newlines are counted first: if *n_newlines + 1 > cap, or *n_newlines >= 2^32, nothing is written
+ * to `line` and the call is BLU_ERR_INVALID_ARG. */
+int blu_dev_line_index(int device, const unsigned char* text, uint64_t size, uint64_t* line, uint64_t cap, uint64_t* n_newlines);
+
 /* The hot path: one blu_result per query.  `out` has n_queries records, on the
  * device when hits->on_device, else on the host.  Asynchronous on
  * params->stream when on_device (no host sync inside); synchronous otherwise.

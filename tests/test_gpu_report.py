@@ -224,3 +224,186 @@ def test_engine_report_ten_million_queries(few):
     assert rep["unclassified"] == u and rep["unplaced"] == n and rep["total"] == dh.n_queries
     if few:
         assert len([p for p, v in paths.items() if v[0]]) <= 10 * 9
+
+
+# ---- engine level, hand-built records: the table rebuild, 64-bit counts, 64-level lineages, statuses, bad records ------
+
+U32_MAX = (1 << 32) - 1
+
+
+def _hand_taxonomy(lineages):
+    """engine.Taxonomy of the given node-id lineages (every level ranked `clade`), and the engine row id of each row."""
+    lens = np.array([len(l) for l in lineages], np.uint64)
+    lin_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    lin_node = np.concatenate([np.asarray(l, np.uint32) for l in lineages])
+    lin_rank = np.full(len(lin_node), synth.RANK_NAMES.index("clade"), np.uint16)
+    t = engine.Taxonomy(lin_off, lin_node, lin_rank, synth.RANK_NAMES, taxon="bacteria", device=0)
+    return t, t.row_map()[0].copy()
+
+
+def _records(n):
+    recs = np.zeros(n, engine.RESULT_DTYPE)
+    recs["ref_row"] = U32_MAX
+    return recs
+
+
+def _int_aggregate(lineages, recs, weights):
+    """{node tuple: [direct, clade]}, unclassified, unplaced, in Python integers; ref_row = the desc row."""
+    w = np.ones(len(recs), np.uint64) if weights is None else weights.astype(np.uint64)
+    cls = recs["status"] < 2
+    unclassified = int(w[~cls].sum(dtype=np.uint64))
+    lens = np.array([len(l) for l in lineages], np.uint64)
+    desc = recs["ref_row"][cls].astype(np.int64)
+    ln = lens[desc]
+    full = np.uint64(U32_MAX) << np.uint64(32) | np.uint64(U32_MAX)
+    low = np.where(ln >= 64, full, (np.uint64(1) << np.minimum(ln, 63)) - np.uint64(1))
+    m = recs["level_mask"][cls] & low
+    uniq, inv = np.unique(np.stack([desc.astype(np.uint64), m], axis=1), axis=0, return_inverse=True)
+    sums = np.zeros(len(uniq), np.uint64)
+    np.add.at(sums, inv.ravel(), w[cls])
+    unplaced, paths = 0, {}
+    for (d, mm), s in zip(uniq.tolist(), sums.tolist()):
+        if mm == 0:
+            unplaced += s
+            continue
+        p = ()
+        for j, node in enumerate(lineages[d]):
+            if (mm >> j) & 1:
+                p += (int(node),)
+                paths.setdefault(p, [0, 0])[1] += s
+        paths[p][0] += s
+    return paths, unclassified, unplaced
+
+
+def _report_both(t, fwd, recs, weights=None, tax_row=None):
+    """blu_consensus_report through the device-pointer and the host-pointer path; both must agree."""
+    tax_row = fwd if tax_row is None else tax_row
+    dev = report.consensus_report(t, torch.from_numpy(tax_row.view(np.int32)).to("cuda:0"),
+                                  torch.from_numpy(recs.view(np.uint8)).to("cuda:0"), len(tax_row),
+                                  weights=None if weights is None else torch.from_numpy(weights.view(np.int32)).to("cuda:0"))
+    host = report.consensus_report(t, tax_row, recs, len(tax_row), weights=weights)
+    for k in ("unclassified", "unplaced", "total", "attempts", "table_slots"):
+        assert dev[k] == host[k], k
+    return dev, host
+
+
+def _check_exact(lineages, t, fwd, recs, weights):
+    paths, u, n = _int_aggregate(lineages, recs, weights)
+    total = len(recs) if weights is None else int(weights.astype(np.uint64).sum(dtype=np.uint64))
+    reps = _report_both(t, fwd, recs, weights)
+    for rep in reps:
+        assert rep["unclassified"] == u and rep["unplaced"] == n and rep["total"] == total
+        assert _as_tuples(rep) == paths
+    return reps[0], paths
+
+
+def test_engine_report_rebuilds_the_table_from_the_bound():
+    """Deep lineages, random level masks: far more distinct paths than the first table (sized from 2 n_tax) holds, so
+    the count starts again at 2 x sum(popcount(level_mask)) slots: more than 4 M, so the compaction's prefix sum over
+    cap + 1 slot flags runs its carry loop too."""
+    rng = np.random.default_rng(40)
+    lineages = [[1] + [100 * (i + 1) + j for j in range(39)] for i in range(6)]
+    t, fwd = _hand_taxonomy(lineages)
+    nq = 100_000
+    recs = _records(nq)
+    recs["status"] = rng.choice([0, 1, 2, 3], nq, p=[0.6, 0.3, 0.05, 0.05])
+    recs["ref_row"] = np.where(recs["status"] < 2, rng.integers(0, len(lineages), nq), U32_MAX)
+    levels = (rng.random((nq, 40)) < 0.2).astype(np.uint64) << np.arange(40, dtype=np.uint64)
+    # bits 40..63 are beyond every lineage: ignored by the count, counted by the bound
+    recs["level_mask"] = np.bitwise_or.reduce(levels, axis=1) | (np.uint64((1 << 24) - 1) << np.uint64(40))
+    recs["level_mask"][:50] &= np.uint64(((1 << 24) - 1) << 40)          # nothing within the length: unplaced
+    weights = rng.integers(1, 6, nq).astype(np.uint32)
+    rep, paths = _check_exact(lineages, t, fwd, recs, weights)
+    assert rep["attempts"] == 2
+    assert rep["table_slots"] + 1 > 4096 * 1024
+    assert len(paths) > 2 * len(lineages) + 4096
+    assert rep["unplaced"] > 0 and rep["unclassified"] > 0
+
+
+def test_engine_report_first_table_suffices():
+    rng = np.random.default_rng(41)
+    lineages = [[1, 10 + i // 8, 1000 + i] for i in range(64)]
+    t, fwd = _hand_taxonomy(lineages)
+    recs = _records(5000)
+    recs["ref_row"] = rng.integers(0, len(lineages), len(recs))
+    recs["level_mask"] = rng.integers(0, 8, len(recs)).astype(np.uint64)
+    rep, _ = _check_exact(lineages, t, fwd, recs, None)
+    assert rep["attempts"] == 1
+
+
+def test_engine_report_counts_past_2_to_the_53():
+    """Weights of 2^32 - 1: one leaf holds a little more than 2^21 queries, so its direct count (1 024 queries of a block
+    summed in LDS, then the blocks in global memory) passes 2^53; then blocks in which every query has a leaf of its own
+    (1 024 keys in the 2 048-slot LDS table: some run past its probe limit and count in global memory directly)."""
+    n_leaf = 4096
+    lineages = [[7, 20 + i // 64, 5000 + i] for i in range(n_leaf)]
+    t, fwd = _hand_taxonomy(lineages)
+    hot = (1 << 21) + 2048
+    spread = 4 * 1024
+    tail = 1024
+    nq = hot + spread + tail
+    recs = _records(nq)
+    recs["level_mask"] = 0b111
+    recs["ref_row"][:hot] = 0
+    recs["ref_row"][hot:hot + spread] = np.arange(spread) % n_leaf
+    recs["status"][hot + spread:] = np.arange(tail) % 4 + 2                # unclassified: 2..5
+    recs["status"][hot + spread::2] = 1                                    # half of the tail: unplaced (mask 0)
+    recs["ref_row"][hot + spread::2] = 3
+    recs["level_mask"][hot + spread::2] = 0
+    recs["level_mask"][hot + spread + 2::4] = np.uint64(0b111 << 3)      # only bits beyond the 3 levels: unplaced too
+    weights = np.full(nq, U32_MAX, np.uint32)
+    rep, paths = _check_exact(lineages, t, fwd, recs, weights)
+    leaf = (7, 20, 5000)
+    assert paths[leaf][0] > 1 << 53
+    assert rep["unclassified"] > 1 << 32 and rep["unplaced"] > 1 << 32
+    assert sum(1 for p, (d, c) in paths.items() if len(p) == 3 and d) == n_leaf
+
+
+def test_engine_report_64_level_lineages_and_statuses():
+    rng = np.random.default_rng(64)
+    lineages = [[1] + [1000 * (i + 1) + j for j in range(63)] for i in range(3)]      # 64 levels
+    lineages += [[1] + [9000 + 100 * i + j for j in range(n - 1)] for i, n in enumerate((10, 33, 63))]
+    t, fwd = _hand_taxonomy(lineages)
+    assert t.max_depth == 64
+    nq = 20_000
+    recs = _records(nq)
+    recs["status"] = rng.choice([0, 1, 2, 3, 16, 17, 20], nq, p=[0.5, 0.3, 0.08, 0.04, 0.04, 0.02, 0.02])
+    cls = recs["status"] < 2
+    recs["ref_row"][cls] = rng.integers(0, len(lineages), int(cls.sum()))
+    recs["level_mask"] = rng.integers(0, 1 << 64, nq, dtype=np.uint64, endpoint=False)
+    recs["level_mask"][::3] |= np.uint64(1 << 63)                        # the 64th level on the 64-level lineages
+    recs["level_mask"][::7] = np.uint64((1 << 64) - 1)                    # every level
+    recs["level_mask"][::11] = np.uint64(1 << 63)                         # the 64th level alone: unplaced below 64 levels
+    recs["level_mask"][::13] = 0
+    weights = rng.integers(0, 1 << 32, nq, dtype=np.uint64).astype(np.uint32)
+    rep, paths = _check_exact(lineages, t, fwd, recs, weights)
+    last = {1000 * (i + 1) + 62 for i in range(3)}
+    assert any(len(p) == 64 and paths[p][0] for p in paths)
+    assert any(p[-1] in last and len(p) < 64 and paths[p][0] for p in paths)
+    assert rep["unplaced"] > 0 and rep["unclassified"] > 0
+    unw = _check_exact(lineages, t, fwd, recs, None)[0]
+    assert unw["total"] == nq
+
+
+@pytest.mark.parametrize("how", ["unmatched_row", "row_out_of_range"])
+def test_engine_report_bad_record_is_an_error_naming_it(how):
+    lineages = [[1, 2, 3], [1, 2, 4]]
+    t, fwd = _hand_taxonomy(lineages)
+    tax_row = np.concatenate([fwd, [N.BLU_UNMATCHED_TAXID]]).astype(np.uint32)
+    recs = _records(3000)
+    recs["ref_row"] = np.arange(3000) % 2
+    recs["level_mask"] = 0b111
+    recs["status"][::5] = 2                                                # ref_row U32_MAX, status >= 2: fine
+    recs["ref_row"][::5] = U32_MAX
+    bad = 2047
+    recs["ref_row"][bad] = 2 if how == "unmatched_row" else len(tax_row) + 5
+    for side in ("device", "host"):
+        if side == "device":
+            args = (torch.from_numpy(tax_row.view(np.int32)).to("cuda:0"), torch.from_numpy(recs.view(np.uint8)).to("cuda:0"))
+        else:
+            args = (tax_row, recs)
+        with pytest.raises(N.BluError, match=f"record {bad} ") as e:
+            report.consensus_report(t, args[0], args[1], len(tax_row))
+        assert e.value.code == N.BLU_ERR_INVALID_ARG
+    recs["status"][bad] = 2
+    _report_both(t, fwd, recs, tax_row=tax_row)
