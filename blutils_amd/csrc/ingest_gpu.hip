@@ -65,13 +65,6 @@ struct Slot {            // 32 bytes
 
 struct DevTaxidMap { const TaxidMap::E* tab; uint64_t mask; };
 
-// out of device memory is not an error of the call: the CPU parser takes the file (oom_fallback is set by the callers
-// that have one)
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-        if (e_ == hipErrorOutOfMemory && oom_fallback) { (void)hipGetLastError(); if (oom_why) *oom_why = "not enough free device memory"; rc = BLU_INGEST_FALLBACK; } \
-        else { set_error("GPU ingest: %s failed: %s", #x, hipGetErrorString(e_)); rc = BLU_ERR_HIP; } \
-        goto done; } } while (0)
-
 // ---- block-level sum and exclusive scan: 64-wide wavefronts reduce / scan in registers (DPP), the wave totals meet in LDS ----
 template <int CTRL>
 __device__ __forceinline__ uint32_t dpp_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true); }
@@ -716,48 +709,40 @@ const char* fallback_text(uint32_t f) {
 
 uint64_t pow2_at_least(uint64_t x) { uint64_t p = 1024; while (p < x) p <<= 1; return p; }
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// stage trace of the GPU ingest (BLU_INGEST_TRACE=1): one stderr line per lap, the device drained first
+struct IngestTrace {
+    const bool on = getenv("BLU_INGEST_TRACE") != nullptr;
+    double tp = now_s();
+    void operator()(const char* what) {
+        if (!on) return;
+        (void)hipDeviceSynchronize();
+        const double t = now_s();
+        fprintf(stderr, "[ingest-gpu] %-26s %.3f s\n", what, t - tp);
+        tp = t;
+    }
+};
 
 }  // namespace
 
-// Device allocations of one ingest: everything still registered is freed when the arena goes out of scope, whichever
-// way the function is left.
-struct DeviceArena {
-    std::vector<void*> ptrs;
-    // keep: work buffers that are done with are handed back only when the arena goes (on some boxes an allocation that
-    // follows a hipFree of GBs takes 0.1 - 0.4 s per GB: 0.3 s of a 0.7 s ingest); set when the device has room for it
-    bool keep = false;
-    hipError_t alloc(void** p, size_t bytes) {
-        const hipError_t e = hipMalloc(p, bytes);
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-    void free(void* p) {
-        if (keep) return;
-        auto it = std::find(ptrs.begin(), ptrs.end(), p);
-        if (it == ptrs.end()) return;
-        (void)hipFree(p);
-        ptrs.erase(it);
-    }
-    void release(void* p) {   // ownership moves elsewhere
-        auto it = std::find(ptrs.begin(), ptrs.end(), p);
-        if (it != ptrs.end()) ptrs.erase(it);
-    }
-    void free_all() { for (void* p : ptrs) (void)hipFree(p); ptrs.clear(); }
-    ~DeviceArena() { free_all(); }
-};
-
-// ---- the ingest's pieces for the taxonomies-database builder (ingest_prims.h): host wrappers, the kernels stay here
+// ---- the ingest's pieces for the other GPU programs (ingest_prims.h): host wrappers, the kernels stay here
 uint64_t line_tiles(uint64_t size) { return (size + TILE_BYTES - 1) / TILE_BYTES; }
-hipError_t line_count_tiles(const unsigned char* d_text, uint64_t size, uint32_t* d_tile) {
+hipError_t line_count(const unsigned char* d_text, uint64_t size, uint32_t* d_tile, uint32_t* d_base, void* d_tmp, uint32_t* n_newlines) {
     const uint64_t n_tiles = line_tiles(size);
     if (n_tiles) hipLaunchKernelGGL(count_newlines, dim3((unsigned)n_tiles), dim3(TILE_THREADS), 0, 0, (const uint4*)d_text, size, d_tile);
-    return hipGetLastError();
+    hipError_t e = hipMemset(d_tile + n_tiles, 0, 4);
+    if (e == hipSuccess) e = exclusive_scan_dev<uint32_t>(d_tile, d_base, (size_t)n_tiles + 1, d_tmp);   // (also reports the launch above)
+    if (e == hipSuccess) e = hipMemcpy(n_newlines, d_base + n_tiles, 4, hipMemcpyDeviceToHost);
+    return e;
 }
-hipError_t line_write_starts(const unsigned char* d_text, uint64_t size, const uint32_t* d_tile_base, uint64_t* d_line) {
+hipError_t line_write(const unsigned char* d_text, uint64_t size, const uint32_t* d_base, uint64_t* d_line, uint64_t n_lines, bool open_tail) {
     const uint64_t n_tiles = line_tiles(size);
-    if (n_tiles) hipLaunchKernelGGL(write_line_starts, dim3((unsigned)n_tiles), dim3(TILE_THREADS), 0, 0, (const uint4*)d_text, size, d_tile_base, d_line);
-    return hipGetLastError();
+    hipError_t e = hipMemset(d_line, 0, 8);
+    if (e != hipSuccess) return e;
+    if (n_tiles) hipLaunchKernelGGL(write_line_starts, dim3((unsigned)n_tiles), dim3(TILE_THREADS), 0, 0, (const uint4*)d_text, size, d_base, d_line);
+    e = hipGetLastError();
+    if (e != hipSuccess || !open_tail) return e;
+    const uint64_t end = size + 1;
+    return hipMemcpy(d_line + n_lines, &end, 8, hipMemcpyHostToDevice);
 }
 size_t scan_tmp_bytes_u32(size_t n) { return scan_tmp_bytes<uint32_t>(n); }
 size_t scan_tmp_bytes_u64(size_t n) { return scan_tmp_bytes<unsigned long long>(n); }
@@ -851,6 +836,24 @@ int upload_file(int fd, size_t size, unsigned char* d_text, int device, std::str
     return BLU_OK;
 }
 
+int upload_text(int fd, size_t size, int device, const char* name, DeviceArena& mem, unsigned char** d_text, bool* open_tail,
+                const std::function<void()>& allocated) {
+    HipPolicy& pol = mem.pol;
+    HIP_CHECK(pol, mem.alloc(d_text, ((size + 15) & ~(size_t)15) + 64, name));
+    HIP_CHECK(pol, hipMemset(*d_text + size, 0, 64));
+    if (allocated) allocated();
+    *open_tail = false;
+    if (size == 0) return BLU_OK;
+    std::string io;
+    const int rc = upload_file(fd, size, *d_text, device, &io);
+    if (rc == BLU_INGEST_FALLBACK && pol.why) { *pol.why = "the pinned staging path failed (" + io + ")"; return rc; }
+    if (rc != BLU_OK) { set_error("%s: reading %s failed: %s", pol.who, name, io.c_str()); return rc == BLU_ERR_IO ? BLU_ERR_IO : BLU_ERR_HIP; }
+    char last = 0;
+    if (pread(fd, &last, 1, (off_t)(size - 1)) != 1) { set_error("%s: reading %s failed", pol.who, name); return BLU_ERR_IO; }
+    *open_tail = last != '\n';
+    return BLU_OK;
+}
+
 // (defined in consensus_kernel.hip; named here only so that the warm-up can ask for its attributes, which makes the runtime load
 // the code object of that translation unit — the two dozen builds of the consensus kernels — ahead of the engine stage)
 __global__ void blu_classify_tasks(const uint64_t* __restrict__ seg_off, uint64_t n_queries, uint64_t n_hits, uint64_t, uint64_t, uint32_t, uint32_t*, uint32_t*);
@@ -870,31 +873,13 @@ void warm_up_device(int device) {
     (void)hipGetLastError();
 }
 
-int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, std::string* why) {
-    int rc = BLU_OK;
-    DeviceArena mem;
-    const bool oom_fallback = true;
-    std::string* const oom_why = why;
-    const bool trace = getenv("BLU_INGEST_TRACE") != nullptr;
-    double tp = now_s();
-    auto lap = [&](const char* what) {
-        if (!trace) return;
-        (void)hipDeviceSynchronize();
-        const double t = now_s();
-        fprintf(stderr, "[ingest-gpu] %-26s %.3f s\n", what, t - tp);
-        tp = t;
-    };
-    auto fallback = [&](const char* reason) { if (why) *why = reason; return BLU_INGEST_FALLBACK; };
-    if (size == 0) return fallback("an empty file");
-    if (size >= (1ull << 44)) return fallback("a file of 16 TiB or more");
-    if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice(%d) failed", device); return BLU_ERR_NO_DEVICE; }
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)size * 2.8 + (1ull << 30) > (double)free_b)
-            return fallback("a file too large for this device's free memory");
-        mem.keep = (double)size * 4.0 + (4ull << 30) < (double)free_b;
-    }
+namespace {
 
+// load_hits_gpu's work on the device, in the arena the caller frees; any failure returns at once
+int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, DeviceArena& mem,
+                     IngestTrace& lap) {
+    HipPolicy& pol = mem.pol;
+    auto fallback = [&](const char* reason) { *pol.why = reason; return BLU_INGEST_FALLBACK; };
     unsigned char* d_text = nullptr;
     uint32_t *d_tile = nullptr, *d_tile_base = nullptr, *d_flags = nullptr, *d_counter = nullptr;
     uint64_t* d_line = nullptr;
@@ -920,93 +905,75 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
     std::thread acc_sort;                        // the host's sort of the distinct accessions, beside the query dictionary
     std::atomic<bool> acc_sort_failed{false};
     struct JoinSort { std::thread& t; ~JoinSort() { if (t.joinable()) t.join(); } } join_acc_sort{acc_sort};
-    uint64_t n_tiles = (size + TILE_BYTES - 1) / TILE_BYTES;
+    const uint64_t n_tiles = line_tiles(size);
     auto need_tmp = [&](size_t bytes) -> hipError_t {
         if (bytes <= tmp_bytes) return hipSuccess;
         if (d_tmp) mem.free(d_tmp);
         d_tmp = nullptr; tmp_bytes = 0;
-        hipError_t e = mem.alloc(&d_tmp, bytes);
+        hipError_t e = mem.alloc(&d_tmp, bytes, "scan scratch");
         if (e == hipSuccess) tmp_bytes = bytes;
         return e;
     };
-    auto grid = [](uint64_t n, uint32_t b = 256) { return dim3((unsigned)((n + b - 1) / b)); };
     // distinct strings at d_pos[0 .. n) of the device text -> host
     auto download_strings = [&](const unsigned long long* d_pos, uint32_t n, std::vector<char>& bytes, std::vector<unsigned long long>& off) -> int {
-        int rc = BLU_OK;
         unsigned long long *d_len = nullptr, *d_off = nullptr;
         unsigned char* d_out = nullptr;
         off.assign((size_t)n + 1, 0);
-        HIPCHK(mem.alloc((void**)&d_len, ((size_t)n + 1) * 8));
-        HIPCHK(mem.alloc((void**)&d_off, ((size_t)n + 1) * 8));
+        HIP_CHECK(pol, mem.alloc(&d_len, ((size_t)n + 1) * 8, "string offsets"));
+        HIP_CHECK(pol, mem.alloc(&d_off, ((size_t)n + 1) * 8, "string offsets"));
         hipLaunchKernelGGL(pos_lengths, dim3((n + 256) / 256), dim3(256), 0, 0, d_pos, n, d_len);
-        {
-            HIPCHK(need_tmp(scan_tmp_bytes<unsigned long long>((size_t)n + 1)));
-            HIPCHK(exclusive_scan_dev<unsigned long long>(d_len, d_off, (size_t)n + 1, d_tmp));
-        }
-        HIPCHK(hipMemcpy(off.data(), d_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, need_tmp(scan_tmp_bytes<unsigned long long>((size_t)n + 1)));
+        HIP_CHECK(pol, exclusive_scan_dev<unsigned long long>(d_len, d_off, (size_t)n + 1, d_tmp));
+        HIP_CHECK(pol, hipMemcpy(off.data(), d_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost));
         bytes.resize(off[n]);
-        HIPCHK(mem.alloc((void**)&d_out, std::max<size_t>(off[n], 16)));
+        HIP_CHECK(pol, mem.alloc(&d_out, off[n], "strings"));
         if (n) hipLaunchKernelGGL(gather_bytes, dim3((n + 255) / 256), dim3(256), 0, 0, d_pos, n, d_text, d_off, d_out);
-        HIPCHK(hipMemcpy(bytes.data(), d_out, off[n], hipMemcpyDeviceToHost));
-    done:
+        HIP_CHECK(pol, hipMemcpy(bytes.data(), d_out, off[n], hipMemcpyDeviceToHost));
         mem.free(d_len); mem.free(d_off); mem.free(d_out);
-        return rc;
+        return BLU_OK;
     };
 
     // ---- upload + line index
     lap("device start-up");
-    HIPCHK(mem.alloc((void**)&d_text, size + 64));
-    HIPCHK(hipMemset(d_text + size, 0, 64));
-    lap("  upload: device buffer");   // the padding only (the readers' pieces end at `size`)
+    bool open_tail = false;
     {
-        std::string io;
-        rc = upload_file(fd, size, d_text, device, &io);
-        if (rc == BLU_INGEST_FALLBACK) { if (why) *why = "the pinned staging path failed (" + io + ")"; goto done; }
-        if (rc != BLU_OK) { set_error("GPU ingest: reading the table failed: %s", io.c_str()); goto done; }
+        // (the device-buffer lap times the padding only: the readers' pieces end at `size`)
+        const int rc = upload_text(fd, size, device, "the table", mem, &d_text, &open_tail, [&] { lap("  upload: device buffer"); });
+        if (rc != BLU_OK) return rc;
     }
     lap("upload text");
-    HIPCHK(mem.alloc((void**)&d_tile, (n_tiles + 1) * 4));
-    HIPCHK(mem.alloc((void**)&d_tile_base, (n_tiles + 1) * 4));
-    HIPCHK(mem.alloc((void**)&d_flags, 64));
-    HIPCHK(hipMemset(d_flags, 0, 64));
+    HIP_CHECK(pol, mem.alloc(&d_tile, (n_tiles + 1) * 4, "line index"));
+    HIP_CHECK(pol, mem.alloc(&d_tile_base, (n_tiles + 1) * 4, "line index"));
+    HIP_CHECK(pol, mem.alloc(&d_flags, 64, "flags"));
+    HIP_CHECK(pol, hipMemset(d_flags, 0, 64));
     d_counter = d_flags + 4;                                         // {flags, -, -, -, counter, -, big counters at +8}
     d_big = reinterpret_cast<unsigned long long*>(d_flags + 8);      // [0] unmatched rows, [1] run heads
-    hipLaunchKernelGGL(count_newlines, grid(n_tiles, 1), dim3(TILE_THREADS), 0, 0, (const uint4*)d_text, (uint64_t)size, d_tile);
-    {
-        HIPCHK(need_tmp(scan_tmp_bytes<uint32_t>((size_t)n_tiles + 1)));
-        HIPCHK(hipMemset(d_tile + n_tiles, 0, 4));
-        HIPCHK(exclusive_scan_dev<uint32_t>(d_tile, d_tile_base, (size_t)n_tiles + 1, d_tmp));
-    }
+    HIP_CHECK(pol, need_tmp(scan_tmp_bytes<uint32_t>((size_t)n_tiles + 1)));
     {
         uint32_t n_newlines = 0;
-        HIPCHK(hipMemcpy(&n_newlines, d_tile_base + n_tiles, 4, hipMemcpyDeviceToHost));
-        char last = 0;
-        if (pread(fd, &last, 1, (off_t)(size - 1)) != 1) { set_error("GPU ingest: reading the table failed"); rc = BLU_ERR_IO; goto done; }
-        const bool open_tail = last != '\n';
+        HIP_CHECK(pol, line_count(d_text, size, d_tile, d_tile_base, d_tmp, &n_newlines));
         const uint64_t rows64 = (uint64_t)n_newlines + (open_tail ? 1 : 0);
-        if (rows64 >= 0x7FFFFFF0ull) { rc = fallback("2^31 rows or more"); goto done; }
+        if (rows64 >= 0x7FFFFFF0ull) return fallback("2^31 rows or more");
         n_rows = (uint32_t)rows64;
-        if (n_rows == 0) { rc = fallback("no rows"); goto done; }
-        HIPCHK(mem.alloc((void**)&d_line, ((size_t)n_rows + 2) * 8));
-        HIPCHK(hipMemset(d_line, 0, 8));
-        hipLaunchKernelGGL(write_line_starts, grid(n_tiles, 1), dim3(TILE_THREADS), 0, 0, (const uint4*)d_text, (uint64_t)size, d_tile_base, d_line);
-        if (open_tail) { const uint64_t end = size + 1; HIPCHK(hipMemcpy(d_line + n_rows, &end, 8, hipMemcpyHostToDevice)); }
+        if (n_rows == 0) return fallback("no rows");
+        HIP_CHECK(pol, mem.alloc(&d_line, ((size_t)n_rows + 2) * 8, "line index"));
+        HIP_CHECK(pol, line_write(d_text, size, d_tile_base, d_line, n_rows, open_tail));
     }
     lap("line index");
 
     // ---- parse
-    HIPCHK(mem.alloc((void**)&d_taxmap, row_of.tab.size() * sizeof(TaxidMap::E)));
-    HIPCHK(hipMemcpy(d_taxmap, row_of.tab.data(), row_of.tab.size() * sizeof(TaxidMap::E), hipMemcpyHostToDevice));
-    HIPCHK(mem.alloc((void**)&d_qh, (size_t)n_rows * 8)); HIPCHK(mem.alloc((void**)&d_ah, (size_t)n_rows * 8));
-    HIPCHK(mem.alloc((void**)&d_qpos, (size_t)n_rows * 8)); HIPCHK(mem.alloc((void**)&d_apos, (size_t)n_rows * 8));
-    HIPCHK(mem.alloc((void**)&d_tax, (size_t)n_rows * 4)); HIPCHK(mem.alloc((void**)&d_pid, (size_t)n_rows * 8));
-    HIPCHK(mem.alloc((void**)&d_aln, (size_t)n_rows * 4)); HIPCHK(mem.alloc((void**)&d_bs, (size_t)n_rows * 4));
+    HIP_CHECK(pol, mem.alloc(&d_taxmap, row_of.tab.size() * sizeof(TaxidMap::E), "taxid map"));
+    HIP_CHECK(pol, hipMemcpy(d_taxmap, row_of.tab.data(), row_of.tab.size() * sizeof(TaxidMap::E), hipMemcpyHostToDevice));
+    HIP_CHECK(pol, mem.alloc(&d_qh, (size_t)n_rows * 8, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_ah, (size_t)n_rows * 8, "parsed rows"));
+    HIP_CHECK(pol, mem.alloc(&d_qpos, (size_t)n_rows * 8, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_apos, (size_t)n_rows * 8, "parsed rows"));
+    HIP_CHECK(pol, mem.alloc(&d_tax, (size_t)n_rows * 4, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_pid, (size_t)n_rows * 8, "parsed rows"));
+    HIP_CHECK(pol, mem.alloc(&d_aln, (size_t)n_rows * 4, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_bs, (size_t)n_rows * 4, "parsed rows"));
     {
         RowOut o{d_qh, d_ah, d_qpos, d_apos, d_tax, d_pid, d_aln, d_bs};
         DevTaxidMap tm{d_taxmap, row_of.tab.size() - 1};
         hipLaunchKernelGGL(parse_rows, grid(n_rows, PARSE_THREADS), dim3(PARSE_THREADS), 0, 0, d_text, d_line, n_rows, tm, o, d_flags, d_big);
-        HIPCHK(hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
-        if (h_flags) { rc = fallback(fallback_text(h_flags)); goto done; }
+        HIP_CHECK(pol, hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
+        if (h_flags) return fallback(fallback_text(h_flags));
     }
     lap("parse");
 
@@ -1016,29 +983,28 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
     {
         uint64_t cap = pow2_at_least(std::min<uint64_t>((uint64_t)n_rows * 2 + 16, 1ull << 20));   // (32 MB: stays in the caches while 100 M rows probe it; x4 when more than half full)
         for (;;) {
-            HIPCHK(mem.alloc((void**)&d_atab, cap * sizeof(Slot)));
+            HIP_CHECK(pol, mem.alloc(&d_atab, cap * sizeof(Slot), "accession table"));
             lap("  acc: table allocation");
             hipLaunchKernelGGL(dict_init, grid(cap), dim3(256), 0, 0, d_atab, cap);
-            HIPCHK(hipMemset(d_counter, 0, 4));
-            HIPCHK(hipMemset(d_flags, 0, 4));
+            HIP_CHECK(pol, hipMemset(d_counter, 0, 4));
+            HIP_CHECK(pol, hipMemset(d_flags, 0, 4));
             hipLaunchKernelGGL(dict_insert, grid(n_rows), dim3(256), 0, 0, d_ah, n_rows, d_atab, cap - 1, false, d_counter, d_flags);
             hipLaunchKernelGGL(dict_count, grid(cap, 1024), dim3(1024), 0, 0, d_atab, cap, d_counter);
-            HIPCHK(hipMemcpy(&n_acc, d_counter, 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(pol, hipMemcpy(&n_acc, d_counter, 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(pol, hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
             if (!(h_flags & FB_TABLE_FULL) && (uint64_t)n_acc * 2 <= cap) break;
             mem.free(d_atab); d_atab = nullptr;
-            if (cap >= pow2_at_least((uint64_t)n_rows * 2 + 16)) { rc = fallback(fallback_text(FB_TABLE_FULL)); goto done; }
+            if (cap >= pow2_at_least((uint64_t)n_rows * 2 + 16)) return fallback(fallback_text(FB_TABLE_FULL));
             cap *= 4;
         }
         lap("  acc: insert");
-        HIPCHK(hipMemset(d_flags, 0, 4));
-        HIPCHK(mem.alloc((void**)&d_alist_row, (size_t)n_acc * 4)); HIPCHK(mem.alloc((void**)&d_alist_slot, (size_t)n_acc * 4));
-        HIPCHK(hipMemset(d_counter, 0, 4));
+        HIP_CHECK(pol, hipMemset(d_flags, 0, 4));
+        HIP_CHECK(pol, mem.alloc(&d_alist_row, (size_t)n_acc * 4, "accession list")); HIP_CHECK(pol, mem.alloc(&d_alist_slot, (size_t)n_acc * 4, "accession list"));
+        HIP_CHECK(pol, hipMemset(d_counter, 0, 4));
         hipLaunchKernelGGL(dict_finalize, grid(cap), dim3(256), 0, 0, d_atab, cap, d_text, d_apos, d_alist_row, d_alist_slot, d_counter);
-        HIPCHK(mem.alloc((void**)&d_aposlist, (size_t)n_acc * 8));
+        HIP_CHECK(pol, mem.alloc(&d_aposlist, (size_t)n_acc * 8, "accession list"));
         hipLaunchKernelGGL(gather_pos, grid(n_acc), dim3(256), 0, 0, d_apos, d_alist_row, n_acc, d_aposlist);
-        rc = download_strings(d_aposlist, n_acc, a_bytes, a_off);
-        if (rc != BLU_OK) goto done;
+        if (const int rc = download_strings(d_aposlist, n_acc, a_bytes, a_off); rc != BLU_OK) return rc;
         lap("  acc: distinct to host");
         // byte order of the distinct accessions (String::cmp), on the host: only the distinct strings are touched, and
         // mostly not even those — the GPU hands over their first 16 bytes as two big-endian integers; the text is read
@@ -1046,16 +1012,13 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
         k0.resize(n_acc); k1.resize(n_acc);
         {
             unsigned long long *d_k0 = nullptr, *d_k1 = nullptr;
-            HIPCHK(mem.alloc((void**)&d_k0, (size_t)n_acc * 8 + 8));
-            hipError_t e2 = mem.alloc((void**)&d_k1, (size_t)n_acc * 8 + 8);
-            if (e2 == hipSuccess) {
-                hipLaunchKernelGGL(gather_key16, grid(n_acc), dim3(256), 0, 0, d_aposlist, n_acc, d_text, d_k0, d_k1);
-                e2 = hipMemcpy(k0.data(), d_k0, (size_t)n_acc * 8, hipMemcpyDeviceToHost);
-                if (e2 == hipSuccess) e2 = hipMemcpy(k1.data(), d_k1, (size_t)n_acc * 8, hipMemcpyDeviceToHost);
-            }
+            HIP_CHECK(pol, mem.alloc(&d_k0, (size_t)n_acc * 8 + 8, "accession keys"));
+            HIP_CHECK(pol, mem.alloc(&d_k1, (size_t)n_acc * 8 + 8, "accession keys"));
+            hipLaunchKernelGGL(gather_key16, grid(n_acc), dim3(256), 0, 0, d_aposlist, n_acc, d_text, d_k0, d_k1);
+            HIP_CHECK(pol, hipMemcpy(k0.data(), d_k0, (size_t)n_acc * 8, hipMemcpyDeviceToHost));
+            HIP_CHECK(pol, hipMemcpy(k1.data(), d_k1, (size_t)n_acc * 8, hipMemcpyDeviceToHost));
             mem.free(d_k0);
             mem.free(d_k1);
-            HIPCHK(e2);
         }
         acap = cap;
         order.resize(n_acc);
@@ -1092,37 +1055,36 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
     {
         hipLaunchKernelGGL(count_run_heads, grid(n_rows, 1024), dim3(1024), 0, 0, d_qh, n_rows, d_big + 1);
         unsigned long long runs = 0;
-        HIPCHK(hipMemcpy(&runs, d_big + 1, 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(&runs, d_big + 1, 8, hipMemcpyDeviceToHost));
         const uint64_t cap = pow2_at_least(runs * 2 + 16);
-        HIPCHK(mem.alloc((void**)&d_qtab, cap * sizeof(Slot)));
+        HIP_CHECK(pol, mem.alloc(&d_qtab, cap * sizeof(Slot), "query table"));
         hipLaunchKernelGGL(dict_init, grid(cap), dim3(256), 0, 0, d_qtab, cap);   // empty slots, first_row = all ones for atomicMin
-        HIPCHK(hipMemset(d_counter, 0, 4));
+        HIP_CHECK(pol, hipMemset(d_counter, 0, 4));
         hipLaunchKernelGGL(dict_insert, grid(n_rows), dim3(256), 0, 0, d_qh, n_rows, d_qtab, cap - 1, true, d_counter, d_flags);
         hipLaunchKernelGGL(dict_count, grid(cap, 1024), dim3(1024), 0, 0, d_qtab, cap, d_counter);
-        HIPCHK(hipMemcpy(&n_queries, d_counter, 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
-        if (h_flags) { rc = fallback(fallback_text(h_flags)); goto done; }
+        HIP_CHECK(pol, hipMemcpy(&n_queries, d_counter, 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
+        if (h_flags) return fallback(fallback_text(h_flags));
         lap("  query: insert");
-        HIPCHK(mem.alloc((void**)&d_list_row, (size_t)n_queries * 4)); HIPCHK(mem.alloc((void**)&d_list_slot, (size_t)n_queries * 4));
-        HIPCHK(hipMemset(d_counter, 0, 4));
+        HIP_CHECK(pol, mem.alloc(&d_list_row, (size_t)n_queries * 4, "query list")); HIP_CHECK(pol, mem.alloc(&d_list_slot, (size_t)n_queries * 4, "query list"));
+        HIP_CHECK(pol, hipMemset(d_counter, 0, 4));
         hipLaunchKernelGGL(dict_finalize, grid(cap), dim3(256), 0, 0, d_qtab, cap, d_text, d_qpos, d_list_row, d_list_slot, d_counter);
         // ids in first-appearance order, and the names' positions in id order
-        HIPCHK(mem.alloc((void**)&d_mark, ((size_t)n_rows + 1) * 4)); HIPCHK(mem.alloc((void**)&d_rank_of_row, ((size_t)n_rows + 1) * 4));
-        HIPCHK(hipMemset(d_mark, 0, ((size_t)n_rows + 1) * 4));
+        HIP_CHECK(pol, mem.alloc(&d_mark, ((size_t)n_rows + 1) * 4, "query ids")); HIP_CHECK(pol, mem.alloc(&d_rank_of_row, ((size_t)n_rows + 1) * 4, "query ids"));
+        HIP_CHECK(pol, hipMemset(d_mark, 0, ((size_t)n_rows + 1) * 4));
         hipLaunchKernelGGL(mark_first_rows, grid(n_queries), dim3(256), 0, 0, (const uint32_t*)d_list_row, n_queries, d_mark);
-        HIPCHK(need_tmp(scan_tmp_bytes<uint32_t>((size_t)n_rows + 1)));
-        HIPCHK(exclusive_scan_dev<uint32_t>(d_mark, d_rank_of_row, (size_t)n_rows + 1, d_tmp));
-        HIPCHK(mem.alloc((void**)&d_poslist, (size_t)n_queries * 8));
+        HIP_CHECK(pol, need_tmp(scan_tmp_bytes<uint32_t>((size_t)n_rows + 1)));
+        HIP_CHECK(pol, exclusive_scan_dev<uint32_t>(d_mark, d_rank_of_row, (size_t)n_rows + 1, d_tmp));
+        HIP_CHECK(pol, mem.alloc(&d_poslist, (size_t)n_queries * 8, "query list"));
         hipLaunchKernelGGL(number_queries, grid(n_queries), dim3(256), 0, 0, d_qtab, (const uint32_t*)d_list_row, (const uint32_t*)d_list_slot, n_queries,
                            (const uint32_t*)d_rank_of_row, (const unsigned long long*)d_qpos, d_poslist);
-        HIPCHK(mem.alloc((void**)&d_qid, (size_t)n_rows * 4));
+        HIP_CHECK(pol, mem.alloc(&d_qid, (size_t)n_rows * 4, "query ids"));
         hipLaunchKernelGGL(dict_lookup, grid(n_rows), dim3(256), 0, 0, d_qh, d_qpos, n_rows, d_qtab, cap - 1, d_text, d_qpos, d_qid, d_flags);
-        HIPCHK(hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
-        if (h_flags) { rc = fallback(fallback_text(h_flags)); goto done; }
+        HIP_CHECK(pol, hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
+        if (h_flags) return fallback(fallback_text(h_flags));
         lap("  query: ids of the rows");
         // query names: the text of each query's first row, in id order
-        rc = download_strings(d_poslist, n_queries, q_bytes, q_off);
-        if (rc != BLU_OK) goto done;
+        if (const int rc = download_strings(d_poslist, n_queries, q_bytes, q_off); rc != BLU_OK) return rc;
         lap("  query: names");
         mem.free(d_poslist); d_poslist = nullptr;
         mem.free(d_list_row); mem.free(d_list_slot); mem.free(d_mark); mem.free(d_rank_of_row);
@@ -1136,18 +1098,18 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
     // ---- accession dictionary, second half: the ranks go up, every row gets its accession's
     {
         acc_sort.join();
-        if (acc_sort_failed) { rc = fallback("the host could not sort the accessions"); goto done; }
+        if (acc_sort_failed) return fallback("the host could not sort the accessions");
         lap("  acc: wait for the host sort");
         const uint64_t cap = acap;
         std::vector<uint32_t> rank_of(n_acc);
         for (uint32_t r = 0; r < n_acc; ++r) rank_of[order[r]] = r;
-        HIPCHK(mem.alloc((void**)&d_ranks, (size_t)n_acc * 4));
-        HIPCHK(hipMemcpy(d_ranks, rank_of.data(), (size_t)n_acc * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(pol, mem.alloc(&d_ranks, (size_t)n_acc * 4, "accession ranks"));
+        HIP_CHECK(pol, hipMemcpy(d_ranks, rank_of.data(), (size_t)n_acc * 4, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(dict_assign_ids, grid(n_acc), dim3(256), 0, 0, d_atab, d_alist_slot, (const uint32_t*)d_ranks, n_acc);
-        HIPCHK(mem.alloc((void**)&d_arank, (size_t)n_rows * 4));
+        HIP_CHECK(pol, mem.alloc(&d_arank, (size_t)n_rows * 4, "accession ranks"));
         hipLaunchKernelGGL(dict_lookup, grid(n_rows), dim3(256), 0, 0, d_ah, d_apos, n_rows, d_atab, cap - 1, d_text, d_apos, d_arank, d_flags);
-        HIPCHK(hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
-        if (h_flags) { rc = fallback(fallback_text(h_flags)); goto done; }
+        HIP_CHECK(pol, hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
+        if (h_flags) return fallback(fallback_text(h_flags));
         lap("  acc: ranks of the rows");
         mem.free(d_atab); d_atab = nullptr;
         mem.free(d_ah); d_ah = nullptr;
@@ -1158,34 +1120,34 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
 
     // ---- grouping: queries in first-appearance order, file order inside a query (mod.rs:192-208)
     {
-        HIPCHK(hipMemset(d_counter, 0, 4));
+        HIP_CHECK(pol, hipMemset(d_counter, 0, 4));
         hipLaunchKernelGGL(check_grouped, grid(n_rows), dim3(256), 0, 0, d_qid, n_rows, d_counter);
         uint32_t unsorted = 0;
-        HIPCHK(hipMemcpy(&unsorted, d_counter, 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(&unsorted, d_counter, 4, hipMemcpyDeviceToHost));
         lap(unsorted ? "  grouping: check (unsorted)" : "  grouping: check (sorted)");
         if (unsorted) {
-            HIPCHK(mem.alloc((void**)&d_perm, (size_t)n_rows * 4)); HIPCHK(mem.alloc((void**)&d_perm2, (size_t)n_rows * 4));
-            HIPCHK(mem.alloc((void**)&d_qid2, (size_t)n_rows * 4));
+            HIP_CHECK(pol, mem.alloc(&d_perm, (size_t)n_rows * 4, "regrouping")); HIP_CHECK(pol, mem.alloc(&d_perm2, (size_t)n_rows * 4, "regrouping"));
+            HIP_CHECK(pol, mem.alloc(&d_qid2, (size_t)n_rows * 4, "regrouping"));
             hipLaunchKernelGGL(iota_u32, grid(n_rows), dim3(256), 0, 0, d_perm, n_rows);
             int bits = 1;
             while ((1ull << bits) < n_queries) ++bits;
             const size_t cells = (size_t)256 * (((size_t)n_rows + RS_BLOCK - 1) / RS_BLOCK);
             uint32_t* d_table = nullptr;
-            HIPCHK(mem.alloc((void**)&d_table, 2 * cells * 4));
-            HIPCHK(need_tmp(scan_tmp_bytes<uint32_t>(cells)));
+            HIP_CHECK(pol, mem.alloc(&d_table, 2 * cells * 4, "regrouping"));
+            HIP_CHECK(pol, need_tmp(scan_tmp_bytes<uint32_t>(cells)));
             // (stable: file order survives inside a query; afterwards d_qid2 / d_perm2 name the sorted arrays whichever buffer they are)
             uint32_t *k0 = d_qid, *k1 = d_qid2, *v0 = d_perm, *v1 = d_perm2;
-            HIPCHK(radix_sort_pairs_dev(&k0, &k1, &v0, &v1, n_rows, bits, d_table, d_tmp));
+            HIP_CHECK(pol, radix_sort_pairs_dev(&k0, &k1, &v0, &v1, n_rows, bits, d_table, d_tmp));
             d_qid2 = k0; d_qid = k1; d_perm2 = v0; d_perm = v1;
             mem.free(d_table);
         }
-        HIPCHK(mem.alloc((void**)&d_seg, ((size_t)n_queries + 1) * 8 * 2));
-        HIPCHK(hipMemset(d_seg, 0, ((size_t)n_queries + 1) * 8 * 2));
+        HIP_CHECK(pol, mem.alloc(&d_seg, ((size_t)n_queries + 1) * 8 * 2, "segment offsets"));
+        HIP_CHECK(pol, hipMemset(d_seg, 0, ((size_t)n_queries + 1) * 8 * 2));
         hipLaunchKernelGGL(segment_starts, grid(n_rows), dim3(256), 0, 0, (const uint32_t*)(unsorted ? d_qid2 : d_qid), n_rows, n_queries,
                            d_seg + n_queries + 1);
-        HIPCHK(mem.alloc((void**)&d_bs2, (size_t)n_rows * 4)); HIPCHK(mem.alloc((void**)&d_aln2, (size_t)n_rows * 4));
-        HIPCHK(mem.alloc((void**)&d_tax2, (size_t)n_rows * 4)); HIPCHK(mem.alloc((void**)&d_arank2, (size_t)n_rows * 4));
-        HIPCHK(mem.alloc((void**)&d_pid2, (size_t)n_rows * 8));
+        HIP_CHECK(pol, mem.alloc(&d_bs2, (size_t)n_rows * 4, "grouped columns")); HIP_CHECK(pol, mem.alloc(&d_aln2, (size_t)n_rows * 4, "grouped columns"));
+        HIP_CHECK(pol, mem.alloc(&d_tax2, (size_t)n_rows * 4, "grouped columns")); HIP_CHECK(pol, mem.alloc(&d_arank2, (size_t)n_rows * 4, "grouped columns"));
+        HIP_CHECK(pol, mem.alloc(&d_pid2, (size_t)n_rows * 8, "grouped columns"));
         lap("  grouping: offsets + allocations");
         Cols in{d_bs, d_aln, d_tax, d_arank, d_pid};
         ColsOut out{d_bs2, d_aln2, d_tax2, d_arank2, d_pid2};
@@ -1196,7 +1158,7 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
     // ---- the grouped columns stay on the device for the engine; the host copies are made only on request
     {
         unsigned long long unmatched = 0;
-        HIPCHK(hipMemcpy(&unmatched, d_big, 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(&unmatched, d_big, 8, hipMemcpyDeviceToHost));
         ht.unmatched = unmatched;
         ht.n_hits = n_rows;
         ht.host_columns = false;
@@ -1206,8 +1168,8 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
         ht.dev->seg_off = d_seg + n_queries + 1; ht.dev->seg_block = d_seg;
         for (void* q : {(void*)d_bs2, (void*)d_aln2, (void*)d_tax2, (void*)d_arank2, (void*)d_pid2, (void*)d_seg}) mem.release(q);
         if (host_columns) {
-            rc = download_columns(ht);
-            if (rc != BLU_OK) goto done;
+            const int rc = download_columns(ht);
+            if (rc != BLU_OK) return rc;
             lap("download columns");
         }
         // the host strings (query names in id order, accessions in byte order) are built from the packed bytes by a
@@ -1244,15 +1206,35 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
             if (oom) hp->strings_ok = false;
         });
     }
+    return BLU_OK;
+}
 
-done:
-    if (rc != BLU_OK) {
-        ht.clear();
+}  // namespace
+
+int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, std::string* why) {
+    IngestTrace lap;
+    std::string why_unread;
+    if (!why) why = &why_unread;
+    if (size == 0) { *why = "an empty file"; return BLU_INGEST_FALLBACK; }
+    if (size >= (1ull << 44)) { *why = "a file of 16 TiB or more"; return BLU_INGEST_FALLBACK; }
+    if (hipSetDevice(device) != hipSuccess) { set_error("hipSetDevice(%d) failed", device); return BLU_ERR_NO_DEVICE; }
+    // out of device memory is no error of the call: the CPU parser takes the file
+    HipPolicy pol{"GPU ingest", BLU_INGEST_FALLBACK, why};
+    DeviceArena mem(pol);
+    {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)size * 2.8 + (1ull << 30) > (double)free_b) {
+            *why = "a file too large for this device's free memory";
+            return BLU_INGEST_FALLBACK;
+        }
+        mem.keep = (double)size * 4.0 + (4ull << 30) < (double)free_b;
     }
+    const int rc = ingest_on_device(fd, size, row_of, device, host_columns, ht, mem, lap);
+    if (rc != BLU_OK) ht.clear();
     lap("hand-over");
     // with room on the card (mem.keep) the work buffers — the text, the hashes, the dictionaries: 10 GB for a 2 M-query table —
     // are freed with the columns, off the caller's path (5-7 ms of hipFree); otherwise here
-    if (rc == BLU_OK && mem.keep && ht.dev) { ht.dev->trash.insert(ht.dev->trash.end(), mem.ptrs.begin(), mem.ptrs.end()); mem.ptrs.clear(); }
+    if (rc == BLU_OK && mem.keep && ht.dev) mem.hand_over(ht.dev->trash);
     mem.free_all();
     lap("free the work buffers");
     return rc;
@@ -1401,9 +1383,6 @@ DeviceHits::~DeviceHits() {
 
 int device_run_consensus(const blu_taxonomy* tax, DeviceHits& dev, const uint32_t* fwd, uint64_t n_tax, int strategy, blu_result* out,
                          TopTable* top, DeviceRecords* kept) {
-    int rc = BLU_OK;
-    const bool oom_fallback = false;
-    std::string* const oom_why = nullptr;
     uint32_t *d_fwd = nullptr, *d_milli = nullptr, *d_rows = nullptr, *d_flag = nullptr;
     uint4* d_rec = nullptr;
     blu_result* d_out = nullptr;
@@ -1413,81 +1392,80 @@ int device_run_consensus(const blu_taxonomy* tax, DeviceHits& dev, const uint32_
     int32_t* d_score = nullptr;
     uint32_t inexact = 0;
     const uint64_t n = dev.n_hits, nq = dev.n_queries;
-    auto grid = [](uint64_t m) { return dim3((unsigned)((m + 255) / 256)); };
     if (hipSetDevice(dev.device) != hipSuccess) { set_error("hipSetDevice(%d) failed", dev.device); return BLU_ERR_NO_DEVICE; }
-    HIPCHK(hipMalloc((void**)&d_fwd, std::max<uint64_t>(n_tax, 1) * 4));
-    HIPCHK(hipMemcpy(d_fwd, fwd, n_tax * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void**)&d_flag, 4));
-    HIPCHK(hipMemset(d_flag, 0, 4));
-    HIPCHK(hipMalloc((void**)&d_out, std::max<uint64_t>(nq, 1) * sizeof(blu_result)));
+    HipPolicy pol{"GPU ingest", BLU_ERR_HIP};
+    DeviceArena mem(pol);
+    // the work buffers are freed with the columns (DeviceHits::trash), whichever way this is left: ten hipFree calls were
+    // 10-15 ms of this function
+    struct ToTrash { DeviceArena& mem; DeviceHits& dev; ~ToTrash() { mem.hand_over(dev.trash); } } to_trash{mem, dev};
+    HIP_CHECK(pol, mem.alloc(&d_fwd, n_tax * 4, "row map"));
+    HIP_CHECK(pol, hipMemcpy(d_fwd, fwd, n_tax * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(pol, mem.alloc(&d_flag, 4, "flag"));
+    HIP_CHECK(pol, hipMemset(d_flag, 0, 4));
+    HIP_CHECK(pol, mem.alloc(&d_out, nq * sizeof(blu_result), "records"));
     {
         blu_hits h{};
         h.bitscore = dev.bitscore;
         h.seg_off = (const uint64_t*)dev.seg_off;
         // packed layout: a top row's four values in one memory line (if the records do not fit, or a perc_identity is not
         // exactly k/1000, the columns go in)
-        bool packed = n && hipMalloc((void**)&d_rec, n * 16) == hipSuccess;
+        bool packed = n && mem.alloc(&d_rec, n * 16, "packed records") == hipSuccess;
         if (!packed) (void)hipGetLastError();
         if (packed) {
             hipLaunchKernelGGL(pack_side_records, grid(n), dim3(256), 0, 0, dev.tax_desc_row, dev.pident, dev.align_len, dev.acc_rank, n,
                                d_fwd, n_tax, tax->d_hint_of_pos, d_rec, d_flag);
-            HIPCHK(hipMemcpy(&inexact, d_flag, 4, hipMemcpyDeviceToHost));
-            if (inexact) { (void)hipFree(d_rec); d_rec = nullptr; packed = false; }
+            HIP_CHECK(pol, hipMemcpy(&inexact, d_flag, 4, hipMemcpyDeviceToHost));
+            if (inexact) { mem.free(d_rec); d_rec = nullptr; packed = false; }
         }
         if (packed) h.packed = (const uint32_t*)d_rec;
         else {
-            HIPCHK(hipMalloc((void**)&d_rows, std::max<uint64_t>(n, 1) * 4));
+            HIP_CHECK(pol, mem.alloc(&d_rows, n * 4, "engine rows"));
             if (n) hipLaunchKernelGGL(to_engine_rows, grid(n), dim3(256), 0, 0, dev.tax_desc_row, n, d_fwd, n_tax, d_rows);
             h.tax_row = d_rows; h.align_len = dev.align_len; h.acc_rank = dev.acc_rank;
             if (!inexact && n) {   // the records did not fit: milli-percent column
-                HIPCHK(hipMalloc((void**)&d_milli, n * 4));
+                HIP_CHECK(pol, mem.alloc(&d_milli, n * 4, "milli-percent column"));
                 hipLaunchKernelGGL(to_milli, grid(n), dim3(256), 0, 0, dev.pident, n, d_milli, d_flag);
-                HIPCHK(hipMemcpy(&inexact, d_flag, 4, hipMemcpyDeviceToHost));
+                HIP_CHECK(pol, hipMemcpy(&inexact, d_flag, 4, hipMemcpyDeviceToHost));
             }
             if (inexact || !n) h.pident = dev.pident; else h.pident_milli = d_milli;
         }
         h.n_hits = n; h.n_queries = nq; h.on_device = 1;
         blu_run_params rp{strategy, 0, nullptr};
-        rc = blu_consensus_run(tax, &h, &rp, d_out);
-        if (rc != BLU_OK) goto done;
+        const int rc = blu_consensus_run(tax, &h, &rp, d_out);
+        if (rc != BLU_OK) return rc;
         if (kept) { kept->recs = d_out; kept->rows = packed ? (const uint32_t*)d_rec : d_rows; kept->row_stride = packed ? 4u : 1u; }
     }
-    HIPCHK(hipStreamSynchronize(nullptr));
+    HIP_CHECK(pol, hipStreamSynchronize(nullptr));
     {
         std::vector<D2HPiece> pieces;
         d2h_add(pieces, out, d_out, nq * sizeof(blu_result));
-        HIPCHK(d2h_parallel(pieces, dev.device));
+        HIP_CHECK(pol, d2h_parallel(pieces, dev.device));
     }
     if (top) {
         const uint64_t waves = (nq + TOP_QPW - 1) / TOP_QPW;
         const dim3 g((unsigned)((waves * 64 + 255) / 256));
-        HIPCHK(hipMalloc((void**)&d_cnt, (nq + 1) * 8 * 2));
-        HIPCHK(hipMemset(d_cnt, 0, (nq + 1) * 8 * 2));
-        HIPCHK(hipMalloc((void**)&d_score, std::max<uint64_t>(nq, 1) * 4));
+        HIP_CHECK(pol, mem.alloc(&d_cnt, (nq + 1) * 8 * 2, "top-row counts"));
+        HIP_CHECK(pol, hipMemset(d_cnt, 0, (nq + 1) * 8 * 2));
+        HIP_CHECK(pol, mem.alloc(&d_score, nq * 4, "top scores"));
         if (nq) hipLaunchKernelGGL(top_rows_kernel, g, dim3(256), 0, 0, d_out, dev.seg_off, dev.bitscore, nq, d_cnt, nullptr, nullptr, nullptr,
                                    nullptr, nullptr, nullptr, nullptr);
-        HIPCHK(hipMalloc(&d_tmp, scan_tmp_bytes<unsigned long long>((size_t)nq + 1)));
-        HIPCHK(exclusive_scan_dev<unsigned long long>(d_cnt, d_cnt + nq + 1, (size_t)nq + 1, d_tmp));
+        HIP_CHECK(pol, mem.alloc(&d_tmp, scan_tmp_bytes<unsigned long long>((size_t)nq + 1), "scan scratch"));
+        HIP_CHECK(pol, exclusive_scan_dev<unsigned long long>(d_cnt, d_cnt + nq + 1, (size_t)nq + 1, d_tmp));
         top->off.resize(nq + 1);
-        HIPCHK(hipMemcpy(top->off.data(), d_cnt + nq + 1, (nq + 1) * 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(top->off.data(), d_cnt + nq + 1, (nq + 1) * 8, hipMemcpyDeviceToHost));
         const uint64_t n_top = top->off[nq];
-        HIPCHK(hipMalloc((void**)&d_top, std::max<uint64_t>(n_top, 1) * sizeof(TopRow)));
+        HIP_CHECK(pol, mem.alloc(&d_top, n_top * sizeof(TopRow), "top rows"));
         if (nq) hipLaunchKernelGGL(top_rows_kernel, g, dim3(256), 0, 0, d_out, dev.seg_off, dev.bitscore, nq, nullptr, d_cnt + nq + 1,
                                    dev.tax_desc_row, dev.acc_rank, dev.align_len, dev.pident, d_top, d_score);
         top->rows.resize(n_top);
         top->score.resize(nq);
-        HIPCHK(hipStreamSynchronize(nullptr));
+        HIP_CHECK(pol, hipStreamSynchronize(nullptr));
         std::vector<D2HPiece> pieces;
         d2h_add(pieces, top->rows.data(), d_top, n_top * sizeof(TopRow));
         d2h_add(pieces, top->score.data(), d_score, nq * 4);
-        HIPCHK(d2h_parallel(pieces, dev.device));
+        HIP_CHECK(pol, d2h_parallel(pieces, dev.device));
     }
-done:
-    // the work buffers are freed with the columns (DeviceHits::trash): ten hipFree calls were 10-15 ms of this function
-    for (void* p : {(void*)d_fwd, (void*)d_milli, (void*)d_rows, (void*)d_flag, (void*)d_out, (void*)d_rec, (void*)d_cnt, d_tmp, (void*)d_top,
-                    (void*)d_score})
-        if (p) dev.trash.push_back(p);
-    return rc;
+    return BLU_OK;
 }
 
 }  // namespace blu
@@ -1498,16 +1476,6 @@ using namespace blu;
 
 namespace {
 
-struct DevCall {
-    std::vector<void*> ptrs;
-    ~DevCall() { for (void* p : ptrs) (void)hipFree(p); }
-    hipError_t alloc(void** p, size_t bytes) {
-        const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
-
 int dev_enter(int device, const char* who) {
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipSetDevice(%d) failed", who, device); return BLU_ERR_NO_DEVICE; }
     const hipError_t e = hipDeviceSynchronize();
@@ -1515,16 +1483,7 @@ int dev_enter(int device, const char* who) {
     return BLU_OK;
 }
 
-int dev_fail(const char* who, const char* what, hipError_t e) {
-    (void)hipGetLastError();
-    if (e == hipErrorOutOfMemory) { set_error("%s: %s: out of device memory", who, what); return BLU_ERR_ALLOC; }
-    set_error("%s: %s failed: %s", who, what, hipGetErrorString(e));
-    return BLU_ERR_HIP;
-}
-
 }  // namespace
-
-#define DEVCHK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return dev_fail(WHO, #x, e_); } while (0)
 
 extern "C" {
 
@@ -1532,12 +1491,13 @@ int blu_dev_exclusive_scan(int device, const void* in, void* out, uint64_t n, in
     static const char WHO[] = "blu_dev_exclusive_scan";
     if ((elem_bytes != 4 && elem_bytes != 8) || (n && (!in || !out))) { set_error("%s: invalid argument", WHO); return BLU_ERR_INVALID_ARG; }
     if (const int rc = dev_enter(device, WHO)) return rc;
-    DevCall c;
+    HipPolicy pol{WHO, BLU_ERR_ALLOC};
+    DeviceArena mem(pol);
     void* tmp = nullptr;
-    DEVCHK(c.alloc(&tmp, elem_bytes == 4 ? scan_tmp_bytes_u32(n) : scan_tmp_bytes_u64(n)));
-    if (elem_bytes == 4) DEVCHK(exclusive_scan_u32((const uint32_t*)in, (uint32_t*)out, n, tmp));
-    else DEVCHK(exclusive_scan_u64((const unsigned long long*)in, (unsigned long long*)out, n, tmp));
-    DEVCHK(hipDeviceSynchronize());
+    HIP_CHECK(pol, mem.alloc(&tmp, elem_bytes == 4 ? scan_tmp_bytes_u32(n) : scan_tmp_bytes_u64(n), "scan scratch"));
+    if (elem_bytes == 4) HIP_CHECK(pol, exclusive_scan_u32((const uint32_t*)in, (uint32_t*)out, n, tmp));
+    else HIP_CHECK(pol, exclusive_scan_u64((const unsigned long long*)in, (unsigned long long*)out, n, tmp));
+    HIP_CHECK(pol, hipDeviceSynchronize());
     return BLU_OK;
 }
 
@@ -1546,20 +1506,21 @@ int blu_dev_radix_sort_pairs(int device, uint32_t* keys, uint32_t* vals, uint32_
     if (bits < 0 || bits > 32 || (n && (!keys || !vals))) { set_error("%s: invalid argument", WHO); return BLU_ERR_INVALID_ARG; }
     if (const int rc = dev_enter(device, WHO)) return rc;
     if (n == 0) return BLU_OK;
-    DevCall c;
+    HipPolicy pol{WHO, BLU_ERR_ALLOC};
+    DeviceArena mem(pol);
     uint32_t *keys_alt = nullptr, *vals_alt = nullptr, *table = nullptr;
     void* tmp = nullptr;
-    DEVCHK(c.alloc((void**)&keys_alt, (size_t)n * 4));
-    DEVCHK(c.alloc((void**)&vals_alt, (size_t)n * 4));
-    DEVCHK(c.alloc((void**)&table, radix_table_words(n) * 4));
-    DEVCHK(c.alloc(&tmp, radix_scan_tmp_bytes(n)));
+    HIP_CHECK(pol, mem.alloc(&keys_alt, (size_t)n * 4, "alternate keys"));
+    HIP_CHECK(pol, mem.alloc(&vals_alt, (size_t)n * 4, "alternate values"));
+    HIP_CHECK(pol, mem.alloc(&table, radix_table_words(n) * 4, "digit table"));
+    HIP_CHECK(pol, mem.alloc(&tmp, radix_scan_tmp_bytes(n), "scan scratch"));
     uint32_t *k = keys, *ka = keys_alt, *v = vals, *va = vals_alt;
-    DEVCHK(radix_sort_pairs(&k, &ka, &v, &va, n, bits, table, tmp));
+    HIP_CHECK(pol, radix_sort_pairs(&k, &ka, &v, &va, n, bits, table, tmp));
     if (k != keys) {   // an odd number of passes: the result is in the scratch pair
-        DEVCHK(hipMemcpy(keys, k, (size_t)n * 4, hipMemcpyDeviceToDevice));
-        DEVCHK(hipMemcpy(vals, v, (size_t)n * 4, hipMemcpyDeviceToDevice));
+        HIP_CHECK(pol, hipMemcpy(keys, k, (size_t)n * 4, hipMemcpyDeviceToDevice));
+        HIP_CHECK(pol, hipMemcpy(vals, v, (size_t)n * 4, hipMemcpyDeviceToDevice));
     }
-    DEVCHK(hipDeviceSynchronize());
+    HIP_CHECK(pol, hipDeviceSynchronize());
     return BLU_OK;
 }
 
@@ -1569,16 +1530,17 @@ int blu_dev_line_index(int device, const unsigned char* text, uint64_t size, uin
     *n_newlines = 0;
     if (const int rc = dev_enter(device, WHO)) return rc;
     const uint64_t n_tiles = line_tiles(size);
-    DevCall c;
-    uint32_t *d_tile = nullptr, *d_tile_base = nullptr;
+    HipPolicy pol{WHO, BLU_ERR_ALLOC};
+    DeviceArena mem(pol);
+    uint32_t *d_tile = nullptr, *d_tile_base = nullptr, n32 = 0;
     void* tmp = nullptr;
-    DEVCHK(c.alloc((void**)&d_tile, (n_tiles + 1) * 4));
-    DEVCHK(c.alloc((void**)&d_tile_base, (n_tiles + 1) * 4));
-    DEVCHK(c.alloc(&tmp, scan_tmp_bytes_u32(n_tiles + 1)));
-    DEVCHK(line_count_tiles(text, size, d_tile));
-    // the total in 64 bits on the host: the device scan of the tile counts is u32 and must not wrap
+    HIP_CHECK(pol, mem.alloc(&d_tile, (n_tiles + 1) * 4, "line index"));
+    HIP_CHECK(pol, mem.alloc(&d_tile_base, (n_tiles + 1) * 4, "line index"));
+    HIP_CHECK(pol, mem.alloc(&tmp, scan_tmp_bytes_u32(n_tiles + 1), "scan scratch"));
+    HIP_CHECK(pol, line_count(text, size, d_tile, d_tile_base, tmp, &n32));
+    // the total in 64 bits on the host: the device scan of the tile counts is u32 and wraps
     std::vector<uint32_t> tiles(n_tiles);
-    if (n_tiles) DEVCHK(hipMemcpy(tiles.data(), d_tile, n_tiles * 4, hipMemcpyDeviceToHost));
+    if (n_tiles) HIP_CHECK(pol, hipMemcpy(tiles.data(), d_tile, n_tiles * 4, hipMemcpyDeviceToHost));
     uint64_t total = 0;
     for (uint32_t t : tiles) total += t;
     *n_newlines = total;
@@ -1587,13 +1549,9 @@ int blu_dev_line_index(int device, const unsigned char* text, uint64_t size, uin
                   (unsigned long long)(total + 1), (unsigned long long)cap);
         return BLU_ERR_INVALID_ARG;
     }
-    DEVCHK(hipMemset(d_tile + n_tiles, 0, 4));
-    DEVCHK(exclusive_scan_u32(d_tile, d_tile_base, n_tiles + 1, tmp));
-    DEVCHK(hipMemset(line, 0, 8));
-    DEVCHK(line_write_starts(text, size, d_tile_base, line));
-    DEVCHK(hipDeviceSynchronize());
+    HIP_CHECK(pol, line_write(text, size, d_tile_base, line, total + 1, false));
+    HIP_CHECK(pol, hipDeviceSynchronize());
     return BLU_OK;
 }
 
 }  // extern "C"
-#undef DEVCHK

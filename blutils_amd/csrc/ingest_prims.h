@@ -1,24 +1,104 @@
-// Pieces of the GPU ingest (ingest_gpu.hip) that the taxonomies-database builder (taxdb_gpu.hip) reuses.  They are host
-// wrappers around the ingest's own kernels, which stay compiled once, in ingest_gpu.hip.
+// Host side shared by the library's GPU programs: the GPU ingest (ingest_gpu.hip), the engine on its columns, the taxon
+// report (report_kernel.hip), `build-db blu` (taxdb_gpu.hip) and the kraken2 / qiime2 export (seqdb_gpu.hip).
+//   - the error path of a HIP call (HipPolicy, hip_fail, HIP_CHECK) and the owner of one call's device memory (DeviceArena)
+//   - the ingest's device primitives (line index, prefix sums, radix sort, upload, parallel download): host wrappers around
+//     kernels that stay compiled once, in ingest_gpu.hip
+//   - host one-liners: a monotonic clock, launch grids, write_all, JSON string escapes
 #ifndef BLU_INGEST_PRIMS_H
 #define BLU_INGEST_PRIMS_H
 
 #include <hip/hip_runtime.h>
+#include <unistd.h>
 
+#include <algorithm>
+#include <cerrno>
+#include <chrono>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
+#include <functional>
 #include <string>
+#include <string_view>
 #include <vector>
+
+#include "blu_internal.h"
 
 namespace blu {
 
-// ---- line index of a device text d_text[0, size), padded with >= 64 zero bytes (16-byte loads)
+// ---- the error path.  Each entry point passes its policy in: a failed HIP call that ran out of device memory returns
+// oom_rc, any other failure BLU_ERR_HIP.  The message is "<who>: <call> failed: <HIP's text>"; an allocation names its
+// bytes and label instead of the call.  why set: running out of memory is a fall-back, not an error (the GPU ingest hands
+// the file to the CPU parser): the reason goes to *why and no message is set.
+struct HipPolicy {
+    const char* who;
+    int oom_rc;
+    std::string* why = nullptr;
+    size_t alloc_bytes = 0;            // the allocation that failed last (DeviceArena::alloc, DevBuf), for the message
+    const char* alloc_what = nullptr;
+    // an allocation's status, noted on the way back to its caller
+    hipError_t noted(hipError_t e, size_t bytes, const char* what) { alloc_bytes = bytes; alloc_what = e == hipSuccess ? nullptr : what; return e; }
+};
+
+// sets the message, clears HIP's last error, returns the policy's code
+inline int hip_fail(HipPolicy& pol, hipError_t e, const char* call) {
+    (void)hipGetLastError();
+    const bool oom = e == hipErrorOutOfMemory;
+    if (oom && pol.why) *pol.why = "not enough free device memory";
+    else if (pol.alloc_what)
+        set_error("%s: device allocation of %zu bytes (%s) failed: %s", pol.who, pol.alloc_bytes, pol.alloc_what, hipGetErrorString(e));
+    else set_error("%s: %s failed: %s", pol.who, call, hipGetErrorString(e));
+    pol.alloc_what = nullptr;
+    return oom ? pol.oom_rc : BLU_ERR_HIP;
+}
+
+#define HIP_CHECK(pol, x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return ::blu::hip_fail((pol), e_, #x); } while (0)
+
+// The device allocations of one call: whatever is still recorded is freed when the arena goes, whichever way the call is
+// left.  alloc() returns HIP's status and leaves the verdict to the caller (HIP_CHECK, or a fall-back of its own).
+struct DeviceArena {
+    HipPolicy& pol;
+    std::vector<void*> ptrs;
+    // keep: free() leaves the buffer to the end of the call (on some boxes an allocation that follows a hipFree of GBs takes
+    // 0.1 - 0.4 s per GB: 0.3 s of a 0.7 s ingest); the GPU ingest sets it when the device has room for it
+    bool keep = false;
+
+    explicit DeviceArena(HipPolicy& p) : pol(p) {}
+    DeviceArena(const DeviceArena&) = delete;
+    DeviceArena& operator=(const DeviceArena&) = delete;
+    ~DeviceArena() { free_all(); }
+
+    template <class T>
+    hipError_t alloc(T** out, size_t bytes, const char* what) {
+        void* p = nullptr;
+        const hipError_t e = pol.noted(hipMalloc(&p, std::max<size_t>(bytes, 16)), bytes, what);
+        if (e == hipSuccess) { ptrs.push_back(p); *out = (T*)p; }
+        return e;
+    }
+    void free(void* p) {
+        if (keep) return;
+        auto it = std::find(ptrs.begin(), ptrs.end(), p);
+        if (it == ptrs.end()) return;
+        (void)hipFree(p);
+        ptrs.erase(it);
+    }
+    void release(void* p) {   // ownership moves elsewhere
+        auto it = std::find(ptrs.begin(), ptrs.end(), p);
+        if (it != ptrs.end()) ptrs.erase(it);
+    }
+    // every recorded buffer goes to `to` (DeviceHits::trash: freed with the device columns, off the caller's path)
+    void hand_over(std::vector<void*>& to) { to.insert(to.end(), ptrs.begin(), ptrs.end()); ptrs.clear(); }
+    void free_all() { for (void* p : ptrs) (void)hipFree(p); ptrs.clear(); }
+};
+
+// ---- line index of a device text d_text[0, size), padded with >= 64 zero bytes (16-byte loads): line k is
+// [line[k], line[k + 1] - 1).  Two steps, so that the caller sizes line[] (and applies its own limit) in between.
 // tiles of the newline count
 uint64_t line_tiles(uint64_t size);
-// d_tile[k] = newlines in tile k (n = line_tiles(size) entries)
-hipError_t line_count_tiles(const unsigned char* d_text, uint64_t size, uint32_t* d_tile);
-// d_line[k + 1] = offset after newline k, from the exclusive scan of the tile counts; d_line[0] is the caller's
-hipError_t line_write_starts(const unsigned char* d_text, uint64_t size, const uint32_t* d_tile_base, uint64_t* d_line);
+// 1. the newlines: tile counts, the pad entry, their exclusive scan into d_base, the total to the host (u32: it wraps at
+//    2^32).  d_tile, d_base: line_tiles(size) + 1 words; d_tmp: scan_tmp_bytes_u32(line_tiles(size) + 1) bytes
+hipError_t line_count(const unsigned char* d_text, uint64_t size, uint32_t* d_tile, uint32_t* d_base, void* d_tmp, uint32_t* n_newlines);
+// 2. line[0] = 0, line[k + 1] = offset after newline k; open_tail (the last line has no newline): line[n_lines] = size + 1
+hipError_t line_write(const unsigned char* d_text, uint64_t size, const uint32_t* d_base, uint64_t* d_line, uint64_t n_lines, bool open_tail);
 
 // ---- device-wide exclusive prefix sums: out[i] = in[0] + ... + in[i - 1] (wrapping); tmp = scan_tmp_bytes_*(n) bytes.
 // in == out is allowed (every element is read and written by the same thread, after the block sums are taken)
@@ -38,11 +118,58 @@ hipError_t radix_sort_pairs(uint32_t** keys, uint32_t** keys_alt, uint32_t** val
 
 // ---- file -> HBM through pinned staging (pread, never mapped); BLU_OK, BLU_ERR_IO, or BLU_INGEST_FALLBACK (HIP staging)
 int upload_file(int fd, size_t size, unsigned char* d_text, int device, std::string* err);
+// file -> padded device text in the arena: (size rounded up to 16) + 64 bytes, the 64 after `size` zeroed, the file
+// uploaded; *open_tail: its last byte is not a newline.  A file that cannot be read is BLU_ERR_IO ("<who>: reading <name>
+// failed"); a staging path that fails is a fall-back under a policy with `why`, else BLU_ERR_HIP.  `allocated` runs once
+// the padded buffer is there (a trace lap)
+int upload_text(int fd, size_t size, int device, const char* name, DeviceArena& mem, unsigned char** d_text, bool* open_tail,
+                const std::function<void()>& allocated = nullptr);
 
 // ---- device -> pageable host memory by a pool of host threads
 struct D2HPiece { char* dst; const char* src; size_t bytes; };
 void d2h_add(std::vector<D2HPiece>& v, void* dst, const void* src, size_t bytes, size_t piece = 8u << 20);
 hipError_t d2h_parallel(const std::vector<D2HPiece>& pieces, int device, unsigned max_threads = 16);
+
+// ---- host one-liners
+inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// blocks of `block` threads over n items (at least one)
+inline unsigned grid(uint64_t n, uint64_t block = 256) { return (unsigned)std::max<uint64_t>((n + block - 1) / block, 1); }
+
+inline bool write_all(int fd, const void* buf, size_t n) {
+    const char* p = (const char*)buf;
+    while (n) {
+        const ssize_t w = write(fd, p, std::min<size_t>(n, 1u << 30));
+        if (w < 0 && errno == EINTR) continue;
+        if (w <= 0) return false;
+        p += w; n -= (size_t)w;
+    }
+    return true;
+}
+
+// body of a JSON string (no quotes), serde_json's escapes: runs of plain bytes are appended whole
+template <class O>
+void json_esc(O& o, const char* p, size_t n) {
+    size_t i0 = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const unsigned char c = (unsigned char)p[i];
+        if (c >= 0x20 && c != '"' && c != '\\') continue;
+        o.append(p + i0, i - i0);
+        i0 = i + 1;
+        switch (c) {
+            case '"': o += "\\\""; break; case '\\': o += "\\\\"; break; case '\n': o += "\\n"; break;
+            case '\r': o += "\\r"; break; case '\t': o += "\\t"; break; case '\b': o += "\\b"; break; case '\f': o += "\\f"; break;
+            default: { char b[8]; snprintf(b, sizeof b, "\\u%04x", c); o += b; }
+        }
+    }
+    o.append(p + i0, n - i0);
+}
+template <class O>
+void json_str(O& o, std::string_view s) {
+    o.push_back('"');
+    json_esc(o, s.data(), s.size());
+    o.push_back('"');
+}
 
 }  // namespace blu
 #endif

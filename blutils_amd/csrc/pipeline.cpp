@@ -38,12 +38,11 @@
 #include "blu_internal.h"
 #include "blu_pipeline.h"
 #include "ingest.h"
+#include "ingest_prims.h"
 
 using namespace blu;
 
 namespace {
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // The memory of a finished use-case call (the hit table's strings, the records, the top rows, the taxonomy DB: 30 ms of
 // free() and munmap() for a 2 M-query table) is given back by a thread of its own instead of on the caller's path.  At most
@@ -803,29 +802,6 @@ struct Out {
     void clear() { len = 0; }
 };
 
-// body of a JSON string (no quotes): runs of plain bytes are appended whole
-template <class O>
-void json_esc(O& o, const char* p, size_t n) {
-    size_t i0 = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const unsigned char c = (unsigned char)p[i];
-        if (c >= 0x20 && c != '"' && c != '\\') continue;
-        o.append(p + i0, i - i0);
-        i0 = i + 1;
-        switch (c) {
-            case '"': o += "\\\""; break; case '\\': o += "\\\\"; break; case '\n': o += "\\n"; break;
-            case '\r': o += "\\r"; break; case '\t': o += "\\t"; break; case '\b': o += "\\b"; break; case '\f': o += "\\f"; break;
-            default: { char b[8]; snprintf(b, sizeof b, "\\u%04x", c); o += b; }
-        }
-    }
-    o.append(p + i0, n - i0);
-}
-template <class O>
-void json_str(O& o, std::string_view s) {
-    o.push_back('"');
-    json_esc(o, s.data(), s.size());
-    o.push_back('"');
-}
 template <class O>
 void json_f64(O& o, double v) {   // serde_json: shortest digits that round-trip, integral values keep ".0"
     if (!std::isfinite(v)) { o += "null"; return; }
@@ -1109,8 +1085,6 @@ const char* status_site(uint8_t st) {
     }
 }
 
-bool write_all(int fd, const char* p, size_t left);
-
 // ---- taxon abundance report ---------------------------------------------------------------------------
 // Weight of a query under `size` weighting: the first ';'-separated field that is exactly `size=` + decimal digits, else a
 // name ending in `_size_` + digits, else 1.  false: the value does not fit 32 bits.
@@ -1205,14 +1179,6 @@ struct Document {
     size_t size() const { size_t n = 0; for (auto& p : pieces) n += p.size(); return n; }
 };
 
-bool write_all(int fd, const char* p, size_t left) {
-    while (left) {
-        const ssize_t w = write(fd, p, left);
-        if (w < 0) { if (errno == EINTR) continue; return false; }
-        p += w; left -= (size_t)w;
-    }
-    return true;
-}
 double thread_cpu_s() { timespec ts; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 
 unsigned worker_threads() {
@@ -1261,20 +1227,15 @@ int build_report(const Db& db, const HitTable& ht, const blu_taxonomy* tax, cons
     struct Free { blu_report& r; ~Free() { blu_report_free(&r); } } free_rep{rep};
     int rc;
     if (on_device && nq) {
+        HipPolicy pol{"report", BLU_ERR_ALLOC};
+        DeviceArena mem(pol);
         uint32_t* d_w = nullptr;
         if (!w.empty()) {
-            hipError_t e = hipMalloc((void**)&d_w, nq * 4);
-            if (e == hipSuccess) e = hipMemcpy(d_w, w.data(), nq * 4, hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                if (d_w) (void)hipFree(d_w);
-                set_error("report: weights upload failed: %s", hipGetErrorString(e));
-                return e == hipErrorOutOfMemory ? BLU_ERR_ALLOC : BLU_ERR_HIP;
-            }
+            HIP_CHECK(pol, mem.alloc(&d_w, nq * 4, "weights"));
+            HIP_CHECK(pol, hipMemcpy(d_w, w.data(), nq * 4, hipMemcpyHostToDevice));
         }
         ReportInput in{kept.recs, nq, kept.rows, ht.n_hits, kept.row_stride, false, d_w};
         rc = report_device(tax, in, &rep);
-        if (d_w) (void)hipFree(d_w);
     } else {
         blu_hits h{};
         h.tax_row = eng_rows.data();

@@ -189,24 +189,22 @@ uint64_t next_pow2(uint64_t x) { uint64_t c = 1; while (c < x) c <<= 1; return c
 }  // namespace
 
 int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* out) {
-    int rc = BLU_OK;
     const uint64_t nq = in.n_queries;
     unsigned long long *d_keys = nullptr, *d_direct = nullptr, *d_ctl = nullptr;
     uint32_t* d_at = nullptr;
     void* d_tmp = nullptr;
     blu_report_path* d_paths = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     unsigned long long ctl[4] = {0, 0, 0, 0};
     uint64_t cap = 0, n_paths = 0;
     uint32_t attempts = 0;
     std::vector<blu_report_path> paths;
-#define RTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
-        if (e_ == hipErrorOutOfMemory) { (void)hipGetLastError(); set_error("report: %s: out of device memory", #expr); rc = BLU_ERR_ALLOC; } \
-        else { set_error("report: %s failed: %s", #expr, hipGetErrorString(e_)); rc = BLU_ERR_HIP; } \
-        goto done; } } while (0)
-    RTRY(hipEventCreate(&ev0));
-    RTRY(hipEventCreate(&ev1));
-    RTRY(hipMalloc((void**)&d_ctl, 4 * 8));
+    HipPolicy pol{"report", BLU_ERR_ALLOC};
+    DeviceArena mem(pol);
+    struct Events { hipEvent_t ev0 = nullptr, ev1 = nullptr; ~Events() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); } } ev;
+    hipEvent_t &ev0 = ev.ev0, &ev1 = ev.ev1;
+    HIP_CHECK(pol, hipEventCreate(&ev0));
+    HIP_CHECK(pol, hipEventCreate(&ev1));
+    HIP_CHECK(pol, mem.alloc(&d_ctl, 4 * 8, "counters"));
     {
         const uint64_t guess = std::min<uint64_t>(nq * std::max<uint32_t>(tax->max_depth, 1), 2 * tax->n_tax + 4096);
         cap = std::max<uint64_t>(next_pow2(2 * guess), 1024);
@@ -216,53 +214,52 @@ int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* ou
         d.max_depth = tax->max_depth;
         d.recs = in.recs; d.n_queries = nq; d.row_src = in.row_src; d.n_rows = in.n_rows; d.row_stride = in.row_stride;
         d.by_query = in.by_query ? 1u : 0u; d.weight = in.weight; d.ctl = d_ctl;
-        RTRY(hipEventRecord(ev0, nullptr));
+        HIP_CHECK(pol, hipEventRecord(ev0, nullptr));
         for (;;) {
             ++attempts;
-            if (cap > (1ull << 32)) { set_error("report: a table of %llu slots exceeds 32-bit path ids", (unsigned long long)cap); rc = BLU_ERR_ALLOC; goto done; }
-            RTRY(hipMalloc((void**)&d_keys, cap * 8));
-            RTRY(hipMalloc((void**)&d_direct, cap * 8));
-            RTRY(hipMemsetAsync(d_keys, 0xFF, cap * 8, nullptr));
-            RTRY(hipMemsetAsync(d_direct, 0, cap * 8, nullptr));
-            RTRY(hipMemsetAsync(d_ctl, 0, 4 * 8, nullptr));
+            if (cap > (1ull << 32)) { set_error("report: a table of %llu slots exceeds 32-bit path ids", (unsigned long long)cap); return BLU_ERR_ALLOC; }
+            HIP_CHECK(pol, mem.alloc(&d_keys, cap * 8, "path table"));
+            HIP_CHECK(pol, mem.alloc(&d_direct, cap * 8, "path table"));
+            HIP_CHECK(pol, hipMemsetAsync(d_keys, 0xFF, cap * 8, nullptr));
+            HIP_CHECK(pol, hipMemsetAsync(d_direct, 0, cap * 8, nullptr));
+            HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, 4 * 8, nullptr));
             d.keys = d_keys; d.direct = d_direct; d.cap_mask = (uint32_t)(cap - 1); d.max_probe = max_probe;
             if (nq) hipLaunchKernelGGL(report_paths, dim3((unsigned)((nq + RB * RQ - 1) / (RB * RQ))), dim3(RB), 0, 0, d);
-            RTRY(hipGetLastError());
-            RTRY(hipMemcpy(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+            HIP_CHECK(pol, hipGetLastError());
+            HIP_CHECK(pol, hipMemcpy(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost));
             if (ctl[2] & FLAG_BAD_RECORD) {
                 set_error("report: record %llu has a taxon (status 0 / 1) but its reference row names no taxonomy row",
                           (unsigned long long)ctl[3]);
-                rc = BLU_ERR_INVALID_ARG;
-                goto done;
+                return BLU_ERR_INVALID_ARG;
             }
             if (!(ctl[2] & FLAG_OVERFLOW)) break;
-            if (max_probe != REPORT_PROBE_FIRST) { set_error("report: path table overflow"); rc = BLU_ERR_HIP; goto done; }   // (cannot happen at load <= 1/2)
+            if (max_probe != REPORT_PROBE_FIRST) { set_error("report: path table overflow"); return BLU_ERR_HIP; }   // (cannot happen at load <= 1/2)
             // the estimate was short: again from zero, sized from the bound
-            (void)hipFree(d_keys); (void)hipFree(d_direct); d_keys = d_direct = nullptr;
-            RTRY(hipMemsetAsync(d_ctl, 0, 8, nullptr));
+            mem.free(d_keys); mem.free(d_direct); d_keys = d_direct = nullptr;
+            HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, 8, nullptr));
             hipLaunchKernelGGL(report_bound, dim3((unsigned)std::min<uint64_t>((nq + RB - 1) / RB, 4096)), dim3(RB), 0, 0, in.recs, nq, d_ctl);
-            RTRY(hipGetLastError());
+            HIP_CHECK(pol, hipGetLastError());
             unsigned long long bound = 0;
-            RTRY(hipMemcpy(&bound, d_ctl, 8, hipMemcpyDeviceToHost));
+            HIP_CHECK(pol, hipMemcpy(&bound, d_ctl, 8, hipMemcpyDeviceToHost));
             cap = std::max<uint64_t>(next_pow2(2 * bound), 1024);
             max_probe = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
         }
-        RTRY(hipMalloc((void**)&d_at, (cap + 1) * 4));
+        HIP_CHECK(pol, mem.alloc(&d_at, (cap + 1) * 4, "path ids"));
         hipLaunchKernelGGL(report_flags, dim3((unsigned)((cap + 1 + 255) / 256)), dim3(256), 0, 0, d_keys, cap, d_at);
-        RTRY(hipGetLastError());
-        RTRY(hipMalloc(&d_tmp, scan_tmp_bytes_u32(cap + 1)));
-        RTRY(exclusive_scan_u32(d_at, d_at, cap + 1, d_tmp));
+        HIP_CHECK(pol, hipGetLastError());
+        HIP_CHECK(pol, mem.alloc(&d_tmp, scan_tmp_bytes_u32(cap + 1), "scan scratch"));
+        HIP_CHECK(pol, exclusive_scan_u32(d_at, d_at, cap + 1, d_tmp));
         uint32_t np32 = 0;
-        RTRY(hipMemcpy(&np32, d_at + cap, 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(&np32, d_at + cap, 4, hipMemcpyDeviceToHost));
         n_paths = np32;
-        RTRY(hipMalloc((void**)&d_paths, std::max<uint64_t>(n_paths, 1) * sizeof(blu_report_path)));
+        HIP_CHECK(pol, mem.alloc(&d_paths, n_paths * sizeof(blu_report_path), "paths"));
         hipLaunchKernelGGL(report_compact, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, 0, d_keys, d_direct, d_at, cap, d_paths);
-        RTRY(hipGetLastError());
-        RTRY(hipEventRecord(ev1, nullptr));
+        HIP_CHECK(pol, hipGetLastError());
+        HIP_CHECK(pol, hipEventRecord(ev1, nullptr));
         paths.resize(n_paths);
-        if (n_paths) RTRY(hipMemcpy(paths.data(), d_paths, n_paths * sizeof(blu_report_path), hipMemcpyDeviceToHost));
+        if (n_paths) HIP_CHECK(pol, hipMemcpy(paths.data(), d_paths, n_paths * sizeof(blu_report_path), hipMemcpyDeviceToHost));
         float ms = 0;
-        RTRY(hipEventElapsedTime(&ms, ev0, ev1));
+        HIP_CHECK(pol, hipEventElapsedTime(&ms, ev0, ev1));
         out->t_device_ms = ms;
     }
     {
@@ -282,7 +279,7 @@ int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* ou
         std::vector<uint32_t> at(n_paths);
         for (uint64_t i = 0; i < n_paths; ++i) at[i] = (uint32_t)first[depth[i]]++;
         blu_report_path* o = n_paths ? (blu_report_path*)malloc(n_paths * sizeof(blu_report_path)) : nullptr;
-        if (n_paths && !o) { set_error("report: out of memory"); rc = BLU_ERR_ALLOC; goto done; }
+        if (n_paths && !o) { set_error("report: out of memory"); return BLU_ERR_ALLOC; }
         for (uint64_t i = 0; i < n_paths; ++i) {
             blu_report_path p = paths[i];
             p.parent = p.parent == NONE ? NONE : at[p.parent];
@@ -301,13 +298,7 @@ int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* ou
         out->table_slots = cap;
         out->attempts = attempts;
     }
-done:
-#undef RTRY
-    for (void* p : {(void*)d_keys, (void*)d_direct, (void*)d_ctl, (void*)d_at, d_tmp, (void*)d_paths})
-        if (p) (void)hipFree(p);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    return rc;
+    return BLU_OK;
 }
 
 }  // namespace blu
@@ -335,30 +326,25 @@ int blu_consensus_report(const blu_taxonomy* tax, const blu_hits* hits, const bl
     }
     // host pointers: the records, each record's engine row (gathered here: 4 bytes a query instead of the whole column)
     // and the weights go up
-    int rc = BLU_OK;
+    HipPolicy pol{"blu_consensus_report", BLU_ERR_ALLOC};
+    DeviceArena mem(pol);
     blu_result* d_recs = nullptr;
     uint32_t *d_rows = nullptr, *d_w = nullptr;
     try {
         std::vector<uint32_t> rows(nq, BLU_UNMATCHED_TAXID);
         for (uint64_t q = 0; q < nq; ++q)
             if (results[q].status < 2 && results[q].ref_row < nh) rows[q] = src[(uint64_t)results[q].ref_row * stride];
-        hipError_t e = hipMalloc((void**)&d_recs, std::max<uint64_t>(nq, 1) * sizeof(blu_result));
-        if (e == hipSuccess) e = hipMalloc((void**)&d_rows, std::max<uint64_t>(nq, 1) * 4);
-        if (e == hipSuccess && weights) e = hipMalloc((void**)&d_w, std::max<uint64_t>(nq, 1) * 4);
-        if (e == hipSuccess && nq) e = hipMemcpy(d_recs, results, nq * sizeof(blu_result), hipMemcpyHostToDevice);
-        if (e == hipSuccess && nq) e = hipMemcpy(d_rows, rows.data(), nq * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && nq && weights) e = hipMemcpy(d_w, weights, nq * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("blu_consensus_report: staging failed: %s", hipGetErrorString(e));
-            rc = e == hipErrorOutOfMemory ? BLU_ERR_ALLOC : BLU_ERR_HIP;
-        } else {
-            ReportInput hin{d_recs, nq, d_rows, nq, 1u, true, d_w};
-            rc = report_device(tax, hin, out);
+        HIP_CHECK(pol, mem.alloc(&d_recs, nq * sizeof(blu_result), "records"));
+        HIP_CHECK(pol, mem.alloc(&d_rows, nq * 4, "rows"));
+        if (weights) HIP_CHECK(pol, mem.alloc(&d_w, nq * 4, "weights"));
+        if (nq) {
+            HIP_CHECK(pol, hipMemcpy(d_recs, results, nq * sizeof(blu_result), hipMemcpyHostToDevice));
+            HIP_CHECK(pol, hipMemcpy(d_rows, rows.data(), nq * 4, hipMemcpyHostToDevice));
+            if (weights) HIP_CHECK(pol, hipMemcpy(d_w, weights, nq * 4, hipMemcpyHostToDevice));
         }
-    } catch (const std::bad_alloc&) { set_error("out of memory"); rc = BLU_ERR_ALLOC; }
-    for (void* p : {(void*)d_recs, (void*)d_rows, (void*)d_w}) if (p) (void)hipFree(p);
-    return rc;
+        ReportInput hin{d_recs, nq, d_rows, nq, 1u, true, d_w};
+        return report_device(tax, hin, out);
+    } catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
 }
 
 void blu_report_free(blu_report* report) {

@@ -171,8 +171,6 @@ __device__ __forceinline__ uint64_t last_le(const unsigned long long* __restrict
     return lo;
 }
 
-__device__ __forceinline__ uint32_t n_digits(unsigned long long v) { uint32_t d = 1; while (v >= 10) { v /= 10; ++d; } return d; }
-
 // usize::from_str (core::num, from_str_radix): one optional leading '+', then decimal digits only, no overflow
 __device__ __forceinline__ bool parse_usize(const unsigned char* __restrict__ text, uint64_t a, uint64_t b, unsigned long long* out) {
     if (a < b && text[a] == '+') ++a;
@@ -326,10 +324,6 @@ __global__ __launch_bounds__(TPB) void seqdb_write_fna(const unsigned char* __re
     *reinterpret_cast<uint4*>(out + o0) = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-__device__ __forceinline__ void put_u64(unsigned char* o, unsigned long long v, uint32_t d) {
-    for (uint32_t k = d; k-- > 0;) { o[k] = (unsigned char)('0' + v % 10); v /= 10; }
-}
-
 // kraken2 prelim_map.txt: one thread per line, `TAXID\tkraken:taxid|N|ACC\tN\n`
 __global__ __launch_bounds__(TPB) void seqdb_write_map(const unsigned char* __restrict__ text, uint32_t n, const unsigned long long* __restrict__ off,
                                                        const unsigned long long* __restrict__ len, const uint64_t* __restrict__ acc_a,
@@ -342,12 +336,12 @@ __global__ __launch_bounds__(TPB) void seqdb_write_map(const unsigned char* __re
     for (int k = 0; k < 19; ++k) *o++ = (unsigned char)head[k];
     const unsigned long long v = num[i];
     const uint32_t d = n_digits(v);
-    put_u64(o, v, d); o += d;
+    put_digits(o, v, d); o += d;
     *o++ = '|';
     const uint64_t a = acc_a[i];
     for (uint32_t k = 0; k < acc_n[i]; ++k) *o++ = text[a + k];
     *o++ = '\t';
-    put_u64(o, v, d); o += d;
+    put_digits(o, v, d); o += d;
     *o = '\n';
 }
 
@@ -355,34 +349,23 @@ __global__ __launch_bounds__(TPB) void seqdb_write_map(const unsigned char* __re
 
 namespace {
 
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-unsigned grid(uint64_t n, uint64_t per = TPB) { return (unsigned)std::max<uint64_t>((n + per - 1) / per, 1); }
-
-#define HIPTRY(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { \
-        set_error("seqdb: %s failed: %s", #x, hipGetErrorString(e_)); return BLU_ERR_HIP; } } while (0)
-#define TRY(x) do { const int rc_ = (x); if (rc_ != BLU_OK) return rc_; } while (0)
-
-// a device buffer that only grows (bytes rounded up, 1/8 slack so that chunks of similar sizes reuse it)
+// a device buffer that only grows (bytes rounded up, 1/8 slack so that chunks of similar sizes reuse it); a failed
+// allocation is noted in the caller's policy
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
     ~DevBuf() { if (p) (void)hipFree(p); }
     template <class T>
-    int get(T** out, size_t bytes, const char* what) {
+    hipError_t get(T** out, size_t bytes, const char* what, HipPolicy& pol) {
         if (bytes > cap) {
             if (p) (void)hipFree(p);
             p = nullptr; cap = 0;
             const size_t want = ((bytes + bytes / 8) + 4095) & ~(size_t)4095;
-            const hipError_t e = hipMalloc(&p, want);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                set_error("seqdb: device allocation of %zu bytes (%s) failed: %s", want, what, hipGetErrorString(e));
-                return BLU_ERR_ALLOC;
-            }
+            if (const hipError_t e = pol.noted(hipMalloc(&p, want), want, what); e != hipSuccess) { p = nullptr; return e; }
             cap = want;
         }
         *out = (T*)p;
-        return BLU_OK;
+        return hipSuccess;
     }
 };
 
@@ -417,16 +400,6 @@ struct Chan {
     }
 };
 
-bool write_all(int fd, const unsigned char* p, size_t n) {
-    while (n) {
-        const ssize_t w = write(fd, p, std::min<size_t>(n, 1u << 30));
-        if (w < 0 && errno == EINTR) continue;
-        if (w <= 0) return false;
-        p += w; n -= (size_t)w;
-    }
-    return true;
-}
-
 struct InSlot { Pinned buf; size_t len = 0; };
 struct OutSlot { Pinned fna, map; size_t fna_len = 0, map_len = 0; };
 
@@ -444,6 +417,7 @@ struct Export {
     std::atomic<bool> stop{false};
     std::string read_err, write_err;        // set by the reader / writer thread before it ends
     double t_read = 0, t_write = 0;
+    HipPolicy pol{"seqdb", BLU_ERR_ALLOC};  // (the device stage's: the calling thread's)
 
     // device buffers (one set: the device stage is the calling thread's, chunk after chunk)
     DevBuf d_text, d_tile, d_tbase, d_stile, d_sbase, d_scan, d_line, d_sep, d_cnt, d_acc_a, d_acc_n, d_tax_a, d_tax_n, d_oid_a,
@@ -476,9 +450,9 @@ struct Export {
                 if (stop.load()) { ok = false; break; }
                 if (pr < 0 && errno != EINTR) { read_err = std::string("poll: ") + strerror(errno); ok = false; break; }
                 if (pr <= 0) continue;
-                const double t0 = now_ms();
+                const double t0 = now_s();
                 const ssize_t r = read(in_fd, I.buf.p + len, I.buf.cap - len);
-                t_read += now_ms() - t0;
+                t_read += 1e3 * (now_s() - t0);
                 if (r < 0) {
                     if (errno == EINTR || errno == EAGAIN) continue;
                     read_err = std::string("read: ") + strerror(errno); ok = false; break;
@@ -501,9 +475,9 @@ struct Export {
             const int s = out_full.pop();
             if (s < 0) break;
             OutSlot& O = out[s];
-            const double t0 = now_ms();
+            const double t0 = now_s();
             const bool ok = write_all(fna_fd, O.fna.p, O.fna_len) && (map_fd < 0 || write_all(map_fd, O.map.p, O.map_len));
-            t_write += now_ms() - t0;
+            t_write += 1e3 * (now_s() - t0);
             if (!ok && write_err.empty()) { write_err = strerror(errno); stop = true; }
             out_free.push(s);
         }
@@ -518,95 +492,90 @@ struct Export {
                                                      (unsigned long long)line_base + 1); return BLU_ERR_INVALID_ARG; }
         const uint64_t n_tiles = (size + TILE - 1) / TILE;
         unsigned char* text;
-        TRY(d_text.get(&text, n_tiles * TILE + PAD, "chunk"));
-        HIPTRY(hipMemcpy(text, I.buf.p, size, hipMemcpyHostToDevice));
-        HIPTRY(hipMemset(text + size, 0, n_tiles * TILE + PAD - size));
+        HIP_CHECK(pol, d_text.get(&text, n_tiles * TILE + PAD, "chunk", pol));
+        HIP_CHECK(pol, hipMemcpy(text, I.buf.p, size, hipMemcpyHostToDevice));
+        HIP_CHECK(pol, hipMemset(text + size, 0, n_tiles * TILE + PAD - size));
         uint32_t *tile, *tbase, *stile, *sbase;
         unsigned long long* cnt;                         // [0] first bad byte, [1] error word, [2] max line, [3] stop line (u32)
         void* tmp;
-        TRY(d_tile.get(&tile, (n_tiles + 1) * 4, "line index"));
-        TRY(d_tbase.get(&tbase, (n_tiles + 1) * 4, "line index"));
-        TRY(d_stile.get(&stile, (n_tiles + 1) * 4, "separators"));
-        TRY(d_sbase.get(&sbase, (n_tiles + 1) * 4, "separators"));
-        TRY(d_cnt.get(&cnt, 64, "counters"));
-        HIPTRY(hipMemset(cnt, 0xFF, 16));
-        HIPTRY(hipMemset(cnt + 2, 0, 8));
-        HIPTRY(hipMemset(cnt + 3, 0xFF, 8));
-        HIPTRY(line_count_tiles(text, size, tile));
-        HIPTRY(hipMemset(tile + n_tiles, 0, 4));
+        HIP_CHECK(pol, d_tile.get(&tile, (n_tiles + 1) * 4, "line index", pol));
+        HIP_CHECK(pol, d_tbase.get(&tbase, (n_tiles + 1) * 4, "line index", pol));
+        HIP_CHECK(pol, d_stile.get(&stile, (n_tiles + 1) * 4, "separators", pol));
+        HIP_CHECK(pol, d_sbase.get(&sbase, (n_tiles + 1) * 4, "separators", pol));
+        HIP_CHECK(pol, d_cnt.get(&cnt, 64, "counters", pol));
+        HIP_CHECK(pol, hipMemset(cnt, 0xFF, 16));
+        HIP_CHECK(pol, hipMemset(cnt + 2, 0, 8));
+        HIP_CHECK(pol, hipMemset(cnt + 3, 0xFF, 8));
+        HIP_CHECK(pol, d_scan.get(&tmp, std::max(scan_tmp_bytes_u32(n_tiles + 1), scan_tmp_bytes_u64(1)), "scan", pol));
+        uint32_t n_nl = 0, n_sep32 = 0;
+        HIP_CHECK(pol, line_count(text, size, tile, tbase, tmp, &n_nl));
         hipLaunchKernelGGL(seqdb_scan_bytes, dim3(grid(n_tiles, 1)), dim3(TPB), 0, 0, text, size, stile, cnt);
-        HIPTRY(hipGetLastError());
-        HIPTRY(hipMemset(stile + n_tiles, 0, 4));
-        TRY(d_scan.get(&tmp, std::max(scan_tmp_bytes_u32(n_tiles + 1), scan_tmp_bytes_u64(1)), "scan"));
-        HIPTRY(exclusive_scan_u32(tile, tbase, n_tiles + 1, tmp));
-        HIPTRY(exclusive_scan_u32(stile, sbase, n_tiles + 1, tmp));
-        uint32_t counts[2];
-        HIPTRY(hipMemcpy(&counts[0], tbase + n_tiles, 4, hipMemcpyDeviceToHost));
-        HIPTRY(hipMemcpy(&counts[1], sbase + n_tiles, 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipGetLastError());
+        HIP_CHECK(pol, hipMemset(stile + n_tiles, 0, 4));
+        HIP_CHECK(pol, exclusive_scan_u32(stile, sbase, n_tiles + 1, tmp));
+        HIP_CHECK(pol, hipMemcpy(&n_sep32, sbase + n_tiles, 4, hipMemcpyDeviceToHost));
         const bool tail = I.buf.p[size - 1] != '\n';     // only the last chunk of the listing may end without a newline
-        const uint64_t n = (uint64_t)counts[0] + (tail ? 1 : 0), n_sep = counts[1];
+        const uint64_t n = (uint64_t)n_nl + (tail ? 1 : 0), n_sep = n_sep32;
         if (n >= NONE32 - 1) { set_error("seqdb: %s: 2^32 lines in one chunk are not supported", input.c_str()); return BLU_ERR_INVALID_ARG; }
         uint64_t *line, *sep;
-        TRY(d_line.get(&line, (n + 2) * 8, "line index"));
-        TRY(d_sep.get(&sep, (n_sep + 1) * 8, "separators"));
-        HIPTRY(hipMemset(line, 0, 8));
-        HIPTRY(line_write_starts(text, size, tbase, line));
-        if (tail) { const uint64_t end = size + 1; HIPTRY(hipMemcpy(line + n, &end, 8, hipMemcpyHostToDevice)); }
+        HIP_CHECK(pol, d_line.get(&line, (n + 2) * 8, "line index", pol));
+        HIP_CHECK(pol, d_sep.get(&sep, (n_sep + 1) * 8, "separators", pol));
+        HIP_CHECK(pol, line_write(text, size, tbase, line, n, tail));
         hipLaunchKernelGGL(seqdb_sep_write, dim3(grid(n_tiles, 1)), dim3(TPB), 0, 0, text, size, sbase, sep);
-        HIPTRY(hipGetLastError());
+        HIP_CHECK(pol, hipGetLastError());
 
         LineOut lo;
-        TRY(d_acc_a.get(&lo.acc_a, n * 8, "pieces")); TRY(d_acc_n.get(&lo.acc_n, n * 4, "pieces"));
-        TRY(d_tax_a.get(&lo.tax_a, n * 8, "pieces")); TRY(d_tax_n.get(&lo.tax_n, n * 4, "pieces"));
-        TRY(d_oid_a.get(&lo.oid_a, n * 8, "pieces")); TRY(d_oid_n.get(&lo.oid_n, n * 4, "pieces"));
-        TRY(d_seq_a.get(&lo.seq_a, n * 8, "pieces")); TRY(d_seq_n.get(&lo.seq_n, n * 8, "pieces"));
-        TRY(d_num.get(&lo.num, n * 8, "taxids"));
+        HIP_CHECK(pol, d_acc_a.get(&lo.acc_a, n * 8, "pieces", pol)); HIP_CHECK(pol, d_acc_n.get(&lo.acc_n, n * 4, "pieces", pol));
+        HIP_CHECK(pol, d_tax_a.get(&lo.tax_a, n * 8, "pieces", pol)); HIP_CHECK(pol, d_tax_n.get(&lo.tax_n, n * 4, "pieces", pol));
+        HIP_CHECK(pol, d_oid_a.get(&lo.oid_a, n * 8, "pieces", pol)); HIP_CHECK(pol, d_oid_n.get(&lo.oid_n, n * 4, "pieces", pol));
+        HIP_CHECK(pol, d_seq_a.get(&lo.seq_a, n * 8, "pieces", pol)); HIP_CHECK(pol, d_seq_n.get(&lo.seq_n, n * 8, "pieces", pol));
+        HIP_CHECK(pol, d_num.get(&lo.num, n * 8, "taxids", pol));
         unsigned long long *fna_off, *map_off;
-        TRY(d_fna_len.get(&lo.fna_len, (n + 1) * 8, "lengths")); TRY(d_fna_off.get(&fna_off, (n + 1) * 8, "lengths"));
-        TRY(d_map_len.get(&lo.map_len, (n + 1) * 8, "lengths")); TRY(d_map_off.get(&map_off, (n + 1) * 8, "lengths"));
+        HIP_CHECK(pol, d_fna_len.get(&lo.fna_len, (n + 1) * 8, "lengths", pol)); HIP_CHECK(pol, d_fna_off.get(&fna_off, (n + 1) * 8, "lengths", pol));
+        HIP_CHECK(pol, d_map_len.get(&lo.map_len, (n + 1) * 8, "lengths", pol)); HIP_CHECK(pol, d_map_off.get(&map_off, (n + 1) * 8, "lengths", pol));
         lo.err = cnt + 1; lo.max_line = cnt + 2; lo.stop_line = (uint32_t*)(cnt + 3);
-        HIPTRY(hipMemset(lo.fna_len + n, 0, 8));
-        HIPTRY(hipMemset(lo.map_len, 0, (n + 1) * 8));
+        HIP_CHECK(pol, hipMemset(lo.fna_len + n, 0, 8));
+        HIP_CHECK(pol, hipMemset(lo.map_len, 0, (n + 1) * 8));
         hipLaunchKernelGGL(seqdb_lines, dim3(grid(n)), dim3(TPB), 0, 0, text, line, (uint32_t)n, sep, n_sep, qiime, cnt, lo);
-        HIPTRY(hipGetLastError());
-        TRY(d_scan.get(&tmp, std::max(scan_tmp_bytes_u32(n_tiles + 1), scan_tmp_bytes_u64(n + 1)), "scan"));
-        HIPTRY(exclusive_scan_u64(lo.fna_len, fna_off, n + 1, tmp));
-        if (!qiime) HIPTRY(exclusive_scan_u64(lo.map_len, map_off, n + 1, tmp));
+        HIP_CHECK(pol, hipGetLastError());
+        HIP_CHECK(pol, d_scan.get(&tmp, std::max(scan_tmp_bytes_u32(n_tiles + 1), scan_tmp_bytes_u64(n + 1)), "scan", pol));
+        HIP_CHECK(pol, exclusive_scan_u64(lo.fna_len, fna_off, n + 1, tmp));
+        if (!qiime) HIP_CHECK(pol, exclusive_scan_u64(lo.map_len, map_off, n + 1, tmp));
         unsigned long long fna_total = 0, map_total = 0;
-        HIPTRY(hipMemcpy(&fna_total, fna_off + n, 8, hipMemcpyDeviceToHost));
-        if (!qiime) HIPTRY(hipMemcpy(&map_total, map_off + n, 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(&fna_total, fna_off + n, 8, hipMemcpyDeviceToHost));
+        if (!qiime) HIP_CHECK(pol, hipMemcpy(&map_total, map_off + n, 8, hipMemcpyDeviceToHost));
         const uint64_t fna_tiles = (fna_total + TILE - 1) / TILE;
         unsigned char *fna, *map = nullptr;
-        TRY(d_fna.get(&fna, fna_tiles * TILE + PAD, "output"));
+        HIP_CHECK(pol, d_fna.get(&fna, fna_tiles * TILE + PAD, "output", pol));
         if (fna_total) {
             const LineIn li{fna_off, lo.acc_a, lo.acc_n, lo.tax_a, lo.tax_n, lo.oid_a, lo.oid_n, lo.seq_a, lo.seq_n};
             hipLaunchKernelGGL(seqdb_write_fna, dim3((unsigned)fna_tiles), dim3(TPB), 0, 0, text, (uint32_t)n, li, qiime, lo.err, fna);
-            HIPTRY(hipGetLastError());
+            HIP_CHECK(pol, hipGetLastError());
         }
         if (!qiime) {
-            TRY(d_map.get(&map, map_total + PAD, "output"));
+            HIP_CHECK(pol, d_map.get(&map, map_total + PAD, "output", pol));
             hipLaunchKernelGGL(seqdb_write_map, dim3(grid(n)), dim3(TPB), 0, 0, text, (uint32_t)n, map_off, lo.map_len, lo.acc_a, lo.acc_n,
                                lo.num, map);
-            HIPTRY(hipGetLastError());
+            HIP_CHECK(pol, hipGetLastError());
         }
         unsigned long long c[4];
-        HIPTRY(hipMemcpy(c, cnt, 32, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(c, cnt, 32, hipMemcpyDeviceToHost));
         S.max_line_bytes = std::max<uint64_t>(S.max_line_bytes, c[2]);
         const uint64_t stop_line = (uint32_t)c[3], err_line = c[1] == ~0ull ? NONE32 : (c[1] >> 3);
         const uint64_t keep = std::min<uint64_t>({n, stop_line, err_line});   // records before the first stop or error
         unsigned long long keep_off[2] = {fna_total, map_total};
         uint64_t keep_in = size;
         if (keep < n) {
-            HIPTRY(hipMemcpy(&keep_off[0], fna_off + keep, 8, hipMemcpyDeviceToHost));
-            if (!qiime) HIPTRY(hipMemcpy(&keep_off[1], map_off + keep, 8, hipMemcpyDeviceToHost));
-            HIPTRY(hipMemcpy(&keep_in, line + keep, 8, hipMemcpyDeviceToHost));
+            HIP_CHECK(pol, hipMemcpy(&keep_off[0], fna_off + keep, 8, hipMemcpyDeviceToHost));
+            if (!qiime) HIP_CHECK(pol, hipMemcpy(&keep_off[1], map_off + keep, 8, hipMemcpyDeviceToHost));
+            HIP_CHECK(pol, hipMemcpy(&keep_in, line + keep, 8, hipMemcpyDeviceToHost));
         }
         if (!O.fna.grow(keep_off[0] + 1, 0) || !O.map.grow(keep_off[1] + 1, 0)) {
             set_error("seqdb: pinned host allocation of %llu bytes failed", keep_off[0] + keep_off[1]);
             return BLU_ERR_ALLOC;
         }
-        if (keep_off[0]) HIPTRY(hipMemcpy(O.fna.p, fna, keep_off[0], hipMemcpyDeviceToHost));
-        if (keep_off[1]) HIPTRY(hipMemcpy(O.map.p, map, keep_off[1], hipMemcpyDeviceToHost));
+        if (keep_off[0]) HIP_CHECK(pol, hipMemcpy(O.fna.p, fna, keep_off[0], hipMemcpyDeviceToHost));
+        if (keep_off[1]) HIP_CHECK(pol, hipMemcpy(O.map.p, map, keep_off[1], hipMemcpyDeviceToHost));
         O.fna_len = keep_off[0];
         O.map_len = keep_off[1];
         S.n_lines += keep;
@@ -632,7 +601,7 @@ struct Export {
         int n_dev = 0;
         if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); set_error("seqdb: no HIP device"); return BLU_ERR_NO_DEVICE; }
         if (D.device < 0 || D.device >= n_dev) { set_error("seqdb: device %d does not exist (%d devices)", D.device, n_dev); return BLU_ERR_INVALID_ARG; }
-        HIPTRY(hipSetDevice(D.device));
+        HIP_CHECK(pol, hipSetDevice(D.device));
         chunk = D.chunk_bytes ? (size_t)D.chunk_bytes : (size_t)BLU_SEQDB_DEFAULT_CHUNK;
         chunk = std::max<size_t>(chunk, 4096);
         input = D.input_path ? D.input_path : ("fd " + std::to_string(D.input_fd));
@@ -660,11 +629,11 @@ struct Export {
             const int s = in_full.pop();
             if (s < 0) break;
             const int o = out_free.pop();
-            const double t0 = now_ms();
+            const double t0 = now_s();
             bool done = false;
             const uint64_t lines_before = S.n_lines;
             rc = chunk_on_device(in[s], out[o], line_base, &done);
-            S.t_gpu_ms += now_ms() - t0;
+            S.t_gpu_ms += 1e3 * (now_s() - t0);
             line_base += S.n_lines - lines_before;
             in_free.push(s);
             if (rc != BLU_OK) { out_free.push(o); }
@@ -705,9 +674,9 @@ extern "C" int blu_seqdb_export(const blu_seqdb_desc* desc, blu_seqdb_stats* sta
     blu_seqdb_stats local;
     blu_seqdb_stats& S = stats ? *stats : local;
     memset(&S, 0, sizeof S);
-    const double t0 = blu::now_ms();
+    const double t0 = blu::now_s();
     blu::Export e(*desc, S);
     const int rc = e.run();
-    S.t_wall_ms = blu::now_ms() - t0;
+    S.t_wall_ms = 1e3 * (blu::now_s() - t0);
     return rc;
 }

@@ -391,10 +391,6 @@ struct RankTabs {
 };
 struct LinText { const unsigned char* text; const uint64_t* a; const uint32_t* len; };   // taxidlineage.dmp lineage spans
 
-__device__ __forceinline__ uint32_t n_digits(unsigned long long v) { uint32_t d = 1; while (v >= 10) { v /= 10; ++d; } return d; }
-__device__ __forceinline__ void put_digits(unsigned char* out, unsigned long long v, uint32_t d) {
-    for (uint32_t k = d; k > 0; --k) { out[k - 1] = (unsigned char)('0' + v % 10); v /= 10; }
-}
 __device__ __forceinline__ bool exists(const NodeTabs& T, uint32_t t) { return t < T.n_ids && T.node_rank[t] != NO_RANK; }
 
 // slug of a taxon's name (rs:226-231: quotes removed; empty or "null" -> taxid-<id>; then slugify_ascii); out may be null
@@ -667,34 +663,6 @@ __global__ __launch_bounds__(TPB) void taxdb_gather_u64(const unsigned long long
 
 namespace {
 
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// every device allocation of one build; a failed hipMalloc is an error that names the bytes (no fall-back)
-struct DevMem {
-    std::vector<void*> ptrs;
-    ~DevMem() { for (void* p : ptrs) (void)hipFree(p); }
-    template <class T>
-    int alloc(T** out, size_t bytes, const char* what) {
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 16));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("build-db: device allocation of %zu bytes (%s) failed: %s; inputs larger than device memory are not supported",
-                      bytes, what, hipGetErrorString(e));
-            return BLU_ERR_ALLOC;
-        }
-        ptrs.push_back(p);
-        *out = (T*)p;
-        return BLU_OK;
-    }
-};
-
-#define TRY(x) do { const int rc_ = (x); if (rc_ != BLU_OK) return rc_; } while (0)
-#define HIPTRY(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { \
-        set_error("build-db: %s failed: %s", #x, hipGetErrorString(e_)); return BLU_ERR_HIP; } } while (0)
-
-unsigned grid(uint64_t n) { return (unsigned)std::max<uint64_t>((n + TPB - 1) / TPB, 1); }
-
 // a text file in HBM and its line index: line k is [line[k], line[k + 1] - 1)
 struct Text {
     std::string path;
@@ -704,7 +672,8 @@ struct Text {
     uint32_t n_lines = 0;
 };
 
-int load_text(const char* path, int device, DevMem& mem, Text& t) {
+int load_text(const char* path, int device, DeviceArena& mem, Text& t) {
+    HipPolicy& pol = mem.pol;
     t.path = path;
     const int fd = open(path, O_RDONLY | O_CLOEXEC);
     if (fd < 0) { set_error("build-db: cannot open %s: %s", path, strerror(errno)); return BLU_ERR_IO; }
@@ -713,33 +682,20 @@ int load_text(const char* path, int device, DevMem& mem, Text& t) {
     if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { set_error("build-db: %s is not a regular file", path); return BLU_ERR_IO; }
     t.size = (size_t)sb.st_size;
     if (t.size >= (1ull << 40)) { set_error("build-db: %s is too large (%zu bytes)", path, t.size); return BLU_ERR_INVALID_ARG; }
-    TRY(mem.alloc(&t.d, ((t.size + 15) & ~(size_t)15) + 64, path));
-    HIPTRY(hipMemset(t.d + t.size, 0, 64));
-    if (t.size) {
-        std::string io;
-        const int rc = upload_file(fd, t.size, t.d, device, &io);
-        if (rc != BLU_OK) { set_error("build-db: reading %s failed: %s", path, io.c_str()); return rc == BLU_ERR_IO ? BLU_ERR_IO : BLU_ERR_HIP; }
-    }
+    bool open_tail = false;
+    if (const int rc = upload_text(fd, t.size, device, path, mem, &t.d, &open_tail); rc != BLU_OK) return rc;
     const uint64_t n_tiles = line_tiles(t.size);
-    uint32_t *tile = nullptr, *base = nullptr;
+    uint32_t *tile = nullptr, *base = nullptr, n_nl = 0;
     void* tmp = nullptr;
-    TRY(mem.alloc(&tile, (n_tiles + 1) * 4, "line index"));
-    TRY(mem.alloc(&base, (n_tiles + 1) * 4, "line index"));
-    TRY(mem.alloc(&tmp, scan_tmp_bytes_u32(n_tiles + 1), "line index"));
-    HIPTRY(line_count_tiles(t.d, t.size, tile));
-    HIPTRY(hipMemset(tile + n_tiles, 0, 4));
-    HIPTRY(exclusive_scan_u32(tile, base, n_tiles + 1, tmp));
-    uint32_t n_nl = 0;
-    HIPTRY(hipMemcpy(&n_nl, base + n_tiles, 4, hipMemcpyDeviceToHost));
-    char last = '\n';
-    if (t.size && pread(fd, &last, 1, (off_t)(t.size - 1)) != 1) { set_error("build-db: reading %s failed", path); return BLU_ERR_IO; }
-    const uint64_t n = (uint64_t)n_nl + (last != '\n' ? 1 : 0);
+    HIP_CHECK(pol, mem.alloc(&tile, (n_tiles + 1) * 4, "line index"));
+    HIP_CHECK(pol, mem.alloc(&base, (n_tiles + 1) * 4, "line index"));
+    HIP_CHECK(pol, mem.alloc(&tmp, scan_tmp_bytes_u32(n_tiles + 1), "line index"));
+    HIP_CHECK(pol, line_count(t.d, t.size, tile, base, tmp, &n_nl));
+    const uint64_t n = (uint64_t)n_nl + (open_tail ? 1 : 0);
     if (n >= 0x7FFFFFF0ull) { set_error("build-db: %s has 2^31 lines or more", path); return BLU_ERR_INVALID_ARG; }
     t.n_lines = (uint32_t)n;
-    TRY(mem.alloc(&t.line, (n + 2) * 8, "line index"));
-    HIPTRY(hipMemset(t.line, 0, 8));
-    HIPTRY(line_write_starts(t.d, t.size, base, t.line));
-    if (last != '\n') { const uint64_t end = t.size + 1; HIPTRY(hipMemcpy(t.line + n, &end, 8, hipMemcpyHostToDevice)); }
+    HIP_CHECK(pol, mem.alloc(&t.line, (n + 2) * 8, "line index"));
+    HIP_CHECK(pol, line_write(t.d, t.size, base, t.line, n, open_tail));
     return BLU_OK;
 }
 
@@ -749,41 +705,12 @@ struct Parsed {
     uint32_t max_id = 0;
 };
 
-std::string json_str(const std::string& s) {   // serde_json's string escapes
-    std::string o = "\"";
-    for (unsigned char c : s) {
-        switch (c) {
-            case '"': o += "\\\""; break;
-            case '\\': o += "\\\\"; break;
-            case '\b': o += "\\b"; break;
-            case '\f': o += "\\f"; break;
-            case '\n': o += "\\n"; break;
-            case '\r': o += "\\r"; break;
-            case '\t': o += "\\t"; break;
-            default:
-                if (c < 0x20) { char b[8]; snprintf(b, sizeof b, "\\u%04x", c); o += b; }
-                else o += (char)c;
-        }
-    }
-    return o + "\"";
-}
-
 // LinnaeanRank::from_str + Display (linnaean_ranks.rs:55-90): the letter, or the slug of an Other rank
 std::string rank_token(const std::string& r, bool* other) {
     std::string slug;
     const uint16_t k = parse_rank(r.c_str(), &slug);
     *other = k == K_FIRST_OTHER;
     return *other ? slug : std::string(1, "udkpcofgs"[k]);
-}
-
-bool write_all(int fd, const char* p, size_t n) {
-    while (n) {
-        const ssize_t w = write(fd, p, std::min<size_t>(n, 1u << 30));
-        if (w < 0 && errno == EINTR) continue;
-        if (w <= 0) return false;
-        p += w; n -= (size_t)w;
-    }
-    return true;
 }
 
 int build(const blu_taxdb_desc& D, blu_taxdb_stats& S) {
@@ -794,15 +721,17 @@ int build(const blu_taxdb_desc& D, blu_taxdb_stats& S) {
         return BLU_ERR_NO_DEVICE;
     }
     if (D.device < 0 || D.device >= n_dev || hipSetDevice(D.device) != hipSuccess) { set_error("build-db: no HIP device %d", D.device); return BLU_ERR_NO_DEVICE; }
-    DevMem mem;
-    double t0 = now_ms();
-    auto lap = [&](double* field) { (void)hipDeviceSynchronize(); const double t = now_ms(); *field += t - t0; t0 = t; };
+    HipPolicy pol{"build-db", BLU_ERR_ALLOC};
+    DeviceArena mem(pol);
+    double t0 = now_s();
+    auto lap = [&](double* field) { (void)hipDeviceSynchronize(); const double t = now_s(); *field += 1e3 * (t - t0); t0 = t; };
 
     // ---- upload + line index of every input (the line index is part of the parse stage's time)
     const char* paths[N_DUMPS] = {D.nodes_path, D.lineage_path, D.names_path, D.merged_path, D.delnodes_path};
     Text txt[N_DUMPS], acc;
-    for (int m = 0; m < N_DUMPS; ++m) TRY(load_text(paths[m], D.device, mem, txt[m]));
-    TRY(load_text(D.accessions_path, D.device, mem, acc));
+    for (int m = 0; m < N_DUMPS; ++m)
+        if (const int rc = load_text(paths[m], D.device, mem, txt[m]); rc != BLU_OK) return rc;
+    if (const int rc = load_text(D.accessions_path, D.device, mem, acc); rc != BLU_OK) return rc;
     lap(&S.t_upload_ms);
 
     // ---- parse the dumps
@@ -810,29 +739,29 @@ int build(const blu_taxdb_desc& D, blu_taxdb_stats& S) {
     unsigned long long* d_err = nullptr;
     unsigned long long* d_cnt = nullptr;
     uint32_t* d_max = nullptr;
-    TRY(mem.alloc(&d_err, 8 * N_DUMPS, "counters"));
-    TRY(mem.alloc(&d_cnt, 32 * N_DUMPS, "counters"));
-    TRY(mem.alloc(&d_max, 4 * N_DUMPS, "counters"));
-    HIPTRY(hipMemset(d_err, 0xFF, 8 * N_DUMPS));
-    HIPTRY(hipMemset(d_cnt, 0, 32 * N_DUMPS));
-    HIPTRY(hipMemset(d_max, 0, 4 * N_DUMPS));
+    HIP_CHECK(pol, mem.alloc(&d_err, 8 * N_DUMPS, "counters"));
+    HIP_CHECK(pol, mem.alloc(&d_cnt, 32 * N_DUMPS, "counters"));
+    HIP_CHECK(pol, mem.alloc(&d_max, 4 * N_DUMPS, "counters"));
+    HIP_CHECK(pol, hipMemset(d_err, 0xFF, 8 * N_DUMPS));
+    HIP_CHECK(pol, hipMemset(d_cnt, 0, 32 * N_DUMPS));
+    HIP_CHECK(pol, hipMemset(d_max, 0, 4 * N_DUMPS));
     for (int m = 0; m < N_DUMPS; ++m) {
         const uint32_t n = txt[m].n_lines;
         Parsed& p = P[m];
-        TRY(mem.alloc(&p.id, (size_t)n * 4, "parsed dump"));
-        TRY(mem.alloc(&p.span_a, (size_t)n * 8, "parsed dump"));
-        TRY(mem.alloc(&p.span_len, (size_t)n * 4, "parsed dump"));
-        TRY(mem.alloc(&p.aux, (size_t)n * 4, "parsed dump"));
+        HIP_CHECK(pol, mem.alloc(&p.id, (size_t)n * 4, "parsed dump"));
+        HIP_CHECK(pol, mem.alloc(&p.span_a, (size_t)n * 8, "parsed dump"));
+        HIP_CHECK(pol, mem.alloc(&p.span_len, (size_t)n * 4, "parsed dump"));
+        HIP_CHECK(pol, mem.alloc(&p.aux, (size_t)n * 4, "parsed dump"));
         DumpOut o{p.id, p.span_a, p.span_len, p.aux, d_err + m, d_cnt + 4 * m, d_max + m};
         if (n) hipLaunchKernelGGL(taxdb_parse_dump, dim3(grid(n)), dim3(TPB), 0, 0, (const unsigned char*)txt[m].d, (const uint64_t*)txt[m].line, n, m, o);
     }
-    HIPTRY(hipGetLastError());
+    HIP_CHECK(pol, hipGetLastError());
     {
         unsigned long long err[N_DUMPS], cnt[4 * N_DUMPS];
         uint32_t mx[N_DUMPS];
-        HIPTRY(hipMemcpy(err, d_err, sizeof err, hipMemcpyDeviceToHost));
-        HIPTRY(hipMemcpy(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost));
-        HIPTRY(hipMemcpy(mx, d_max, sizeof mx, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(err, d_err, sizeof err, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(mx, d_max, sizeof mx, hipMemcpyDeviceToHost));
         for (int m = 0; m < N_DUMPS; ++m) {
             if (err[m] != ~0ull) {
                 const uint32_t code = (uint32_t)(err[m] & 7);
@@ -859,16 +788,16 @@ int build(const blu_taxdb_desc& D, blu_taxdb_stats& S) {
     uint8_t* deleted;
     unsigned long long* node_hash;
     uint16_t* node_rank;
-    TRY(mem.alloc(&node_row, (size_t)n_ids * 4, "taxid tables"));
-    TRY(mem.alloc(&lin_row, (size_t)n_ids * 4, "taxid tables"));
-    TRY(mem.alloc(&name_row, (size_t)n_ids * 4, "taxid tables"));
-    TRY(mem.alloc(&merged_row, (size_t)n_ids * 4, "taxid tables"));
-    TRY(mem.alloc(&deleted, (size_t)n_ids, "taxid tables"));
-    TRY(mem.alloc(&node_hash, (size_t)n_ids * 8, "taxid tables"));
-    TRY(mem.alloc(&node_rank, (size_t)n_ids * 2, "taxid tables"));
-    HIPTRY(hipMemset(node_row, 0, (size_t)n_ids * 4)); HIPTRY(hipMemset(lin_row, 0, (size_t)n_ids * 4));
-    HIPTRY(hipMemset(name_row, 0, (size_t)n_ids * 4)); HIPTRY(hipMemset(merged_row, 0, (size_t)n_ids * 4));
-    HIPTRY(hipMemset(deleted, 0, n_ids));
+    HIP_CHECK(pol, mem.alloc(&node_row, (size_t)n_ids * 4, "taxid tables"));
+    HIP_CHECK(pol, mem.alloc(&lin_row, (size_t)n_ids * 4, "taxid tables"));
+    HIP_CHECK(pol, mem.alloc(&name_row, (size_t)n_ids * 4, "taxid tables"));
+    HIP_CHECK(pol, mem.alloc(&merged_row, (size_t)n_ids * 4, "taxid tables"));
+    HIP_CHECK(pol, mem.alloc(&deleted, (size_t)n_ids, "taxid tables"));
+    HIP_CHECK(pol, mem.alloc(&node_hash, (size_t)n_ids * 8, "taxid tables"));
+    HIP_CHECK(pol, mem.alloc(&node_rank, (size_t)n_ids * 2, "taxid tables"));
+    HIP_CHECK(pol, hipMemset(node_row, 0, (size_t)n_ids * 4)); HIP_CHECK(pol, hipMemset(lin_row, 0, (size_t)n_ids * 4));
+    HIP_CHECK(pol, hipMemset(name_row, 0, (size_t)n_ids * 4)); HIP_CHECK(pol, hipMemset(merged_row, 0, (size_t)n_ids * 4));
+    HIP_CHECK(pol, hipMemset(deleted, 0, n_ids));
     auto last_line = [&](int m, const uint32_t* only, uint32_t* row) {
         if (txt[m].n_lines) hipLaunchKernelGGL(taxdb_last_line, dim3(grid(txt[m].n_lines)), dim3(TPB), 0, 0, (const uint32_t*)P[m].id, only, txt[m].n_lines, row);
     };
@@ -885,32 +814,32 @@ int build(const blu_taxdb_desc& D, blu_taxdb_stats& S) {
         skip_limit = std::max(skip_limit, (uint32_t)D.skip_taxids[k] + 1);
     }
     const size_t skip_words = ((size_t)skip_limit + 31) / 32;
-    TRY(mem.alloc(&skip_bits, skip_words * 4, "skip bitmap"));
-    HIPTRY(hipMemset(skip_bits, 0, skip_words * 4));
+    HIP_CHECK(pol, mem.alloc(&skip_bits, skip_words * 4, "skip bitmap"));
+    HIP_CHECK(pol, hipMemset(skip_bits, 0, skip_words * 4));
     if (!skip_ids.empty()) {
         uint32_t* d_ids;
-        TRY(mem.alloc(&d_ids, skip_ids.size() * 4, "skip list"));
-        HIPTRY(hipMemcpy(d_ids, skip_ids.data(), skip_ids.size() * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(pol, mem.alloc(&d_ids, skip_ids.size() * 4, "skip list"));
+        HIP_CHECK(pol, hipMemcpy(d_ids, skip_ids.data(), skip_ids.size() * 4, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(taxdb_mark_bits, dim3(grid(skip_ids.size())), dim3(TPB), 0, 0, (const uint32_t*)d_ids, (uint32_t)skip_ids.size(), skip_bits);
     }
     // ranks: slots on the device, strings and tokens on the host
     unsigned long long* slot_hash;
     uint32_t *slot_line, *flags;
-    TRY(mem.alloc(&slot_hash, RANK_SLOTS * 8, "rank slots"));
-    TRY(mem.alloc(&slot_line, RANK_SLOTS * 4, "rank slots"));
-    TRY(mem.alloc(&flags, 8, "rank slots"));
-    HIPTRY(hipMemset(slot_hash, 0, RANK_SLOTS * 8));
-    HIPTRY(hipMemset(flags, 0, 8));
+    HIP_CHECK(pol, mem.alloc(&slot_hash, RANK_SLOTS * 8, "rank slots"));
+    HIP_CHECK(pol, mem.alloc(&slot_line, RANK_SLOTS * 4, "rank slots"));
+    HIP_CHECK(pol, mem.alloc(&flags, 8, "rank slots"));
+    HIP_CHECK(pol, hipMemset(slot_hash, 0, RANK_SLOTS * 8));
+    HIP_CHECK(pol, hipMemset(flags, 0, 8));
     hipLaunchKernelGGL(taxdb_rank_slots, dim3(grid(n_ids)), dim3(TPB), 0, 0, (const unsigned char*)txt[D_NODES].d, (const uint64_t*)P[D_NODES].span_a,
                        (const uint32_t*)P[D_NODES].span_len, (const uint32_t*)node_row, (const uint32_t*)lin_row, n_ids, node_hash, slot_hash, slot_line, flags);
-    HIPTRY(hipGetLastError());
+    HIP_CHECK(pol, hipGetLastError());
     std::vector<unsigned long long> h_slot_hash(RANK_SLOTS);
     std::vector<uint32_t> h_slot_line(RANK_SLOTS);
     uint32_t h_flags[2];
-    HIPTRY(hipMemcpy(h_flags, flags, 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(pol, hipMemcpy(h_flags, flags, 8, hipMemcpyDeviceToHost));
     if (h_flags[0]) { set_error("build-db: %s has more distinct ranks than the rank table holds (%u)", D.nodes_path, RANK_SLOTS); return BLU_ERR_INVALID_ARG; }
-    HIPTRY(hipMemcpy(h_slot_hash.data(), slot_hash, RANK_SLOTS * 8, hipMemcpyDeviceToHost));
-    HIPTRY(hipMemcpy(h_slot_line.data(), slot_line, RANK_SLOTS * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(pol, hipMemcpy(h_slot_hash.data(), slot_hash, RANK_SLOTS * 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(pol, hipMemcpy(h_slot_line.data(), slot_line, RANK_SLOTS * 4, hipMemcpyDeviceToHost));
     std::vector<uint16_t> slot_rank(RANK_SLOTS, 0);
     std::string rank_text, tok;
     std::vector<uint32_t> rank_off{0}, lin_off, leaf_off;
@@ -928,10 +857,10 @@ int build(const blu_taxdb_desc& D, blu_taxdb_stats& S) {
         if (ranks.size() >= MAX_RANKS) { set_error("build-db: %s has more than %u distinct ranks", D.nodes_path, MAX_RANKS); return BLU_ERR_INVALID_ARG; }
         uint64_t a = 0;
         uint32_t len = 0;
-        HIPTRY(hipMemcpy(&a, P[D_NODES].span_a + h_slot_line[k], 8, hipMemcpyDeviceToHost));
-        HIPTRY(hipMemcpy(&len, P[D_NODES].span_len + h_slot_line[k], 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(&a, P[D_NODES].span_a + h_slot_line[k], 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(&len, P[D_NODES].span_len + h_slot_line[k], 4, hipMemcpyDeviceToHost));
         std::string raw(len, '\0'), r;
-        if (len) HIPTRY(hipMemcpy(&raw[0], txt[D_NODES].d + a, len, hipMemcpyDeviceToHost));
+        if (len) HIP_CHECK(pol, hipMemcpy(&raw[0], txt[D_NODES].d + a, len, hipMemcpyDeviceToHost));
         for (char c : raw) if (c != '"' && c != '\t') r.push_back((c >= 'A' && c <= 'Z') ? (char)(c + 32) : c);   // rs:199-206
         slot_rank[k] = (uint16_t)ranks.size();
         ranks.push_back(r);
@@ -959,25 +888,25 @@ int build(const blu_taxdb_desc& D, blu_taxdb_stats& S) {
     unsigned char *d_rank_text, *d_tok;
     uint32_t *d_rank_off, *d_lin_off, *d_leaf_off;
     uint8_t *d_lin_drop, *d_leaf_drop;
-    auto up = [&](auto** dst, const void* src, size_t bytes) -> int {
-        TRY(mem.alloc(dst, bytes, "rank tables"));
-        if (bytes) HIPTRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-        return BLU_OK;
+    auto up = [&](auto** dst, const void* src, size_t bytes) -> hipError_t {
+        hipError_t e = mem.alloc(dst, bytes, "rank tables");
+        if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+        return e;
     };
-    TRY(up(&d_slot_rank, slot_rank.data(), RANK_SLOTS * 2));
-    TRY(up(&d_rank_text, rank_text.data(), rank_text.size()));
-    TRY(up(&d_rank_off, rank_off.data(), rank_off.size() * 4));
-    TRY(up(&d_tok, tok.data(), tok.size()));
-    TRY(up(&d_lin_off, lin_off.data(), lin_off.size() * 4));
-    TRY(up(&d_leaf_off, leaf_off.data(), leaf_off.size() * 4));
-    TRY(up(&d_lin_drop, lin_drop.data(), n_ranks));
-    TRY(up(&d_leaf_drop, leaf_drop.data(), n_ranks));
+    HIP_CHECK(pol, up(&d_slot_rank, slot_rank.data(), RANK_SLOTS * 2));
+    HIP_CHECK(pol, up(&d_rank_text, rank_text.data(), rank_text.size()));
+    HIP_CHECK(pol, up(&d_rank_off, rank_off.data(), rank_off.size() * 4));
+    HIP_CHECK(pol, up(&d_tok, tok.data(), tok.size()));
+    HIP_CHECK(pol, up(&d_lin_off, lin_off.data(), lin_off.size() * 4));
+    HIP_CHECK(pol, up(&d_leaf_off, leaf_off.data(), leaf_off.size() * 4));
+    HIP_CHECK(pol, up(&d_lin_drop, lin_drop.data(), n_ranks));
+    HIP_CHECK(pol, up(&d_leaf_drop, leaf_drop.data(), n_ranks));
     hipLaunchKernelGGL(taxdb_rank_assign, dim3(grid(n_ids)), dim3(TPB), 0, 0, (const unsigned char*)txt[D_NODES].d, (const uint64_t*)P[D_NODES].span_a,
                        (const uint32_t*)P[D_NODES].span_len, (const uint32_t*)node_row, n_ids, (const unsigned long long*)node_hash,
                        (const unsigned long long*)slot_hash, (const uint16_t*)d_slot_rank, (const unsigned char*)d_rank_text, (const uint32_t*)d_rank_off,
                        node_rank, flags + 1);
-    HIPTRY(hipGetLastError());
-    HIPTRY(hipMemcpy(h_flags, flags, 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(pol, hipGetLastError());
+    HIP_CHECK(pol, hipMemcpy(h_flags, flags, 8, hipMemcpyDeviceToHost));
     if (h_flags[1]) { set_error("build-db: two rank strings of %s share one 64-bit hash", D.nodes_path); return BLU_ERR_INVALID_ARG; }
     lap(&S.t_tables_ms);
 
@@ -985,24 +914,24 @@ int build(const blu_taxdb_desc& D, blu_taxdb_stats& S) {
     uint32_t n = acc.n_lines;
     AccOut ao{};
     uint32_t *keys_alt, *vals_alt, *first_bad;
-    TRY(mem.alloc(&ao.key, (size_t)n * 4, "accession rows")); TRY(mem.alloc(&ao.val, (size_t)n * 4, "accession rows"));
-    TRY(mem.alloc(&ao.tax64, (size_t)n * 8, "accession rows"));
-    TRY(mem.alloc(&ao.acc_a, (size_t)n * 8, "accession rows")); TRY(mem.alloc(&ao.acc_len, (size_t)n * 4, "accession rows"));
-    TRY(mem.alloc(&ao.oid_a, (size_t)n * 8, "accession rows")); TRY(mem.alloc(&ao.oid_len, (size_t)n * 4, "accession rows"));
-    TRY(mem.alloc(&ao.esc_len, (size_t)n * 4, "accession rows"));
-    TRY(mem.alloc(&keys_alt, (size_t)n * 4, "accession rows")); TRY(mem.alloc(&vals_alt, (size_t)n * 4, "accession rows"));
-    TRY(mem.alloc(&first_bad, 4, "accession rows"));
-    HIPTRY(hipMemset(first_bad, 0xFF, 4));
-    HIPTRY(hipMemset(d_err, 0xFF, 8));
+    HIP_CHECK(pol, mem.alloc(&ao.key, (size_t)n * 4, "accession rows")); HIP_CHECK(pol, mem.alloc(&ao.val, (size_t)n * 4, "accession rows"));
+    HIP_CHECK(pol, mem.alloc(&ao.tax64, (size_t)n * 8, "accession rows"));
+    HIP_CHECK(pol, mem.alloc(&ao.acc_a, (size_t)n * 8, "accession rows")); HIP_CHECK(pol, mem.alloc(&ao.acc_len, (size_t)n * 4, "accession rows"));
+    HIP_CHECK(pol, mem.alloc(&ao.oid_a, (size_t)n * 8, "accession rows")); HIP_CHECK(pol, mem.alloc(&ao.oid_len, (size_t)n * 4, "accession rows"));
+    HIP_CHECK(pol, mem.alloc(&ao.esc_len, (size_t)n * 4, "accession rows"));
+    HIP_CHECK(pol, mem.alloc(&keys_alt, (size_t)n * 4, "accession rows")); HIP_CHECK(pol, mem.alloc(&vals_alt, (size_t)n * 4, "accession rows"));
+    HIP_CHECK(pol, mem.alloc(&first_bad, 4, "accession rows"));
+    HIP_CHECK(pol, hipMemset(first_bad, 0xFF, 4));
+    HIP_CHECK(pol, hipMemset(d_err, 0xFF, 8));
     ao.err = d_err;
     ao.first_bad = first_bad;
     if (n) hipLaunchKernelGGL(taxdb_parse_acc, dim3(grid(n)), dim3(TPB), 0, 0, (const unsigned char*)acc.d, (const uint64_t*)acc.line, n, n_ids, ao);
-    HIPTRY(hipGetLastError());
+    HIP_CHECK(pol, hipGetLastError());
     {
         uint32_t fb = NONE32;
         unsigned long long err = ~0ull;
-        HIPTRY(hipMemcpy(&fb, first_bad, 4, hipMemcpyDeviceToHost));
-        HIPTRY(hipMemcpy(&err, d_err, 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(&fb, first_bad, 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(&err, d_err, 8, hipMemcpyDeviceToHost));
         if (fb < n) n = fb;                         // the reference's read loop ends at the first line that is not UTF-8
         if (err != ~0ull && (err >> 3) < n) {
             set_error("%s:%llu: %s", D.accessions_path, (err >> 3) + 1,
@@ -1017,35 +946,35 @@ int build(const blu_taxdb_desc& D, blu_taxdb_stats& S) {
     {
         uint32_t* table;
         void* tmp;
-        TRY(mem.alloc(&table, radix_table_words(n) * 4, "radix sort"));
-        TRY(mem.alloc(&tmp, radix_scan_tmp_bytes(n), "radix sort"));
-        HIPTRY(radix_sort_pairs(&keys, &keys_alt, &vals, &vals_alt, n, bits, table, tmp));
+        HIP_CHECK(pol, mem.alloc(&table, radix_table_words(n) * 4, "radix sort"));
+        HIP_CHECK(pol, mem.alloc(&tmp, radix_scan_tmp_bytes(n), "radix sort"));
+        HIP_CHECK(pol, radix_sort_pairs(&keys, &keys_alt, &vals, &vals_alt, n, bits, table, tmp));
     }
     uint32_t *head, *excl, *seg_of, *seg_start, *seg_key;
     void* stmp;
-    TRY(mem.alloc(&head, ((size_t)n + 1) * 4, "segments")); TRY(mem.alloc(&excl, ((size_t)n + 1) * 4, "segments"));
-    TRY(mem.alloc(&seg_of, (size_t)n * 4, "segments")); TRY(mem.alloc(&seg_start, ((size_t)n + 1) * 4, "segments"));
-    TRY(mem.alloc(&seg_key, (size_t)n * 4, "segments"));
-    TRY(mem.alloc(&stmp, std::max(scan_tmp_bytes_u32((size_t)n + 1), scan_tmp_bytes_u64((size_t)n + 1)), "scan"));
-    HIPTRY(hipMemset(head + n, 0, 4));
+    HIP_CHECK(pol, mem.alloc(&head, ((size_t)n + 1) * 4, "segments")); HIP_CHECK(pol, mem.alloc(&excl, ((size_t)n + 1) * 4, "segments"));
+    HIP_CHECK(pol, mem.alloc(&seg_of, (size_t)n * 4, "segments")); HIP_CHECK(pol, mem.alloc(&seg_start, ((size_t)n + 1) * 4, "segments"));
+    HIP_CHECK(pol, mem.alloc(&seg_key, (size_t)n * 4, "segments"));
+    HIP_CHECK(pol, mem.alloc(&stmp, std::max(scan_tmp_bytes_u32((size_t)n + 1), scan_tmp_bytes_u64((size_t)n + 1)), "scan"));
+    HIP_CHECK(pol, hipMemset(head + n, 0, 4));
     if (n) hipLaunchKernelGGL(taxdb_heads, dim3(grid(n)), dim3(TPB), 0, 0, (const uint32_t*)keys, n, head);
-    HIPTRY(exclusive_scan_u32(head, excl, (size_t)n + 1, stmp));
+    HIP_CHECK(pol, exclusive_scan_u32(head, excl, (size_t)n + 1, stmp));
     if (n) hipLaunchKernelGGL(taxdb_seg_ids, dim3(grid(n)), dim3(TPB), 0, 0, (const uint32_t*)head, (const uint32_t*)excl, (const uint32_t*)keys, n,
                               seg_of, seg_start, seg_key);
     uint32_t n_seg = 0;
-    HIPTRY(hipMemcpy(&n_seg, excl + n, 4, hipMemcpyDeviceToHost));
-    HIPTRY(hipMemcpy(seg_start + n_seg, &n, 4, hipMemcpyHostToDevice));
+    HIP_CHECK(pol, hipMemcpy(&n_seg, excl + n, 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(pol, hipMemcpy(seg_start + n_seg, &n, 4, hipMemcpyHostToDevice));
     lap(&S.t_group_ms);
 
     // ---- resolve + assemble the lineages
     SegOut so{};
     unsigned long long *num_off, *txt_off;
-    TRY(mem.alloc(&so.status, n_seg, "segments")); TRY(mem.alloc(&so.node, (size_t)n_seg * 4, "segments"));
-    TRY(mem.alloc(&so.warn, (size_t)n_seg * 4, "segments"));
-    TRY(mem.alloc(&so.num_len, ((size_t)n_seg + 1) * 8, "segments")); TRY(mem.alloc(&so.txt_len, ((size_t)n_seg + 1) * 8, "segments"));
-    TRY(mem.alloc(&num_off, ((size_t)n_seg + 1) * 8, "segments")); TRY(mem.alloc(&txt_off, ((size_t)n_seg + 1) * 8, "segments"));
-    HIPTRY(hipMemset(so.num_len + n_seg, 0, 8)); HIPTRY(hipMemset(so.txt_len + n_seg, 0, 8));
-    HIPTRY(hipMemset(d_err, 0xFF, 8));
+    HIP_CHECK(pol, mem.alloc(&so.status, n_seg, "segments")); HIP_CHECK(pol, mem.alloc(&so.node, (size_t)n_seg * 4, "segments"));
+    HIP_CHECK(pol, mem.alloc(&so.warn, (size_t)n_seg * 4, "segments"));
+    HIP_CHECK(pol, mem.alloc(&so.num_len, ((size_t)n_seg + 1) * 8, "segments")); HIP_CHECK(pol, mem.alloc(&so.txt_len, ((size_t)n_seg + 1) * 8, "segments"));
+    HIP_CHECK(pol, mem.alloc(&num_off, ((size_t)n_seg + 1) * 8, "segments")); HIP_CHECK(pol, mem.alloc(&txt_off, ((size_t)n_seg + 1) * 8, "segments"));
+    HIP_CHECK(pol, hipMemset(so.num_len + n_seg, 0, 8)); HIP_CHECK(pol, hipMemset(so.txt_len + n_seg, 0, 8));
+    HIP_CHECK(pol, hipMemset(d_err, 0xFF, 8));
     so.err = d_err;
     Ctx C{};
     C.T = NodeTabs{node_row, lin_row, name_row, merged_row, deleted, skip_bits, skip_limit, node_rank, n_ids};
@@ -1055,58 +984,58 @@ int build(const blu_taxdb_desc& D, blu_taxdb_stats& S) {
     C.drop = D.drop_non_linnaean ? 1 : 0;
     C.merged_to = P[D_MERGED].aux;
     if (n_seg) hipLaunchKernelGGL(taxdb_resolve, dim3(grid(n_seg)), dim3(TPB), 0, 0, (const uint32_t*)seg_key, n_seg, C, so);
-    HIPTRY(hipGetLastError());
+    HIP_CHECK(pol, hipGetLastError());
     {
         unsigned long long err = ~0ull;
-        HIPTRY(hipMemcpy(&err, d_err, 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(&err, d_err, 8, hipMemcpyDeviceToHost));
         if (err != ~0ull) {
             set_error("%s:%llu: %s", D.lineage_path, (err >> 3) + 1,
                       (err & 7) == E_ANCESTOR ? "an ancestor that is not a taxid" : "an ancestor outside 0..2147483647");
             return BLU_ERR_PARSE;
         }
     }
-    HIPTRY(exclusive_scan_u64(so.num_len, num_off, (size_t)n_seg + 1, stmp));
-    HIPTRY(exclusive_scan_u64(so.txt_len, txt_off, (size_t)n_seg + 1, stmp));
+    HIP_CHECK(pol, exclusive_scan_u64(so.num_len, num_off, (size_t)n_seg + 1, stmp));
+    HIP_CHECK(pol, exclusive_scan_u64(so.txt_len, txt_off, (size_t)n_seg + 1, stmp));
     unsigned long long num_total = 0, txt_total = 0;
-    HIPTRY(hipMemcpy(&num_total, num_off + n_seg, 8, hipMemcpyDeviceToHost));
-    HIPTRY(hipMemcpy(&txt_total, txt_off + n_seg, 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(pol, hipMemcpy(&num_total, num_off + n_seg, 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(pol, hipMemcpy(&txt_total, txt_off + n_seg, 8, hipMemcpyDeviceToHost));
     unsigned char *num, *txtb;
-    TRY(mem.alloc(&num, num_total + 16, "numeric lineages"));
-    TRY(mem.alloc(&txtb, txt_total + 16, "text lineages"));
+    HIP_CHECK(pol, mem.alloc(&num, num_total + 16, "numeric lineages"));
+    HIP_CHECK(pol, mem.alloc(&txtb, txt_total + 16, "text lineages"));
     if (n_seg) hipLaunchKernelGGL(taxdb_lineages, dim3(grid(n_seg)), dim3(TPB), 0, 0, (const uint32_t*)seg_key, n_seg, C, (const uint8_t*)so.status,
                                   (const uint32_t*)so.node, (const unsigned long long*)num_off, (const unsigned long long*)txt_off, num, txtb);
-    HIPTRY(hipGetLastError());
+    HIP_CHECK(pol, hipGetLastError());
     lap(&S.t_assemble_ms);
 
     // ---- render the taxonomies array
     RowIn R{seg_of, seg_start, seg_key, so.status, so.node, num_off, so.num_len, txt_off, so.txt_len, num, txtb, vals,
             ao.esc_len, ao.acc_a, ao.acc_len, ao.oid_a, ao.oid_len, acc.d, d_tok, d_leaf_off, node_rank};
     unsigned long long *row_len, *row_off;
-    TRY(mem.alloc(&row_len, ((size_t)n + 1) * 8, "render"));
-    TRY(mem.alloc(&row_off, ((size_t)n + 1) * 8, "render"));
+    HIP_CHECK(pol, mem.alloc(&row_len, ((size_t)n + 1) * 8, "render"));
+    HIP_CHECK(pol, mem.alloc(&row_off, ((size_t)n + 1) * 8, "render"));
     hipLaunchKernelGGL(taxdb_row_len, dim3(grid((uint64_t)n + 1)), dim3(TPB), 0, 0, R, n, row_len);
-    HIPTRY(exclusive_scan_u64(row_len, row_off, (size_t)n + 1, stmp));
+    HIP_CHECK(pol, exclusive_scan_u64(row_len, row_off, (size_t)n + 1, stmp));
     unsigned long long body = 0;
-    HIPTRY(hipMemcpy(&body, row_off + n, 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(pol, hipMemcpy(&body, row_off + n, 8, hipMemcpyDeviceToHost));
     unsigned char* d_doc;
-    TRY(mem.alloc(&d_doc, body + 16, "document"));
+    HIP_CHECK(pol, mem.alloc(&d_doc, body + 16, "document"));
     if (n) hipLaunchKernelGGL(taxdb_row_write, dim3(grid(n)), dim3(TPB), 0, 0, R, n, (const unsigned long long*)row_off, d_doc);
-    HIPTRY(hipGetLastError());
+    HIP_CHECK(pol, hipGetLastError());
     Column<char> h_doc;
     h_doc.resize(body);
     {
         std::vector<D2HPiece> pieces;
         d2h_add(pieces, h_doc.data(), d_doc, body);
-        HIPTRY(d2h_parallel(pieces, D.device));
+        HIP_CHECK(pol, d2h_parallel(pieces, D.device));
     }
     // per-taxid outcome -> stats and the TSV (ascending taxid: the segments are in key order, the taxids beyond the
     // tables come last and are sorted here)
     std::vector<uint8_t> st(n_seg);
     std::vector<uint32_t> skey(n_seg), warn(n_seg);
     if (n_seg) {
-        HIPTRY(hipMemcpy(st.data(), so.status, n_seg, hipMemcpyDeviceToHost));
-        HIPTRY(hipMemcpy(skey.data(), seg_key, (size_t)n_seg * 4, hipMemcpyDeviceToHost));
-        HIPTRY(hipMemcpy(warn.data(), so.warn, (size_t)n_seg * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(st.data(), so.status, n_seg, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(skey.data(), seg_key, (size_t)n_seg * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(warn.data(), so.warn, (size_t)n_seg * 4, hipMemcpyDeviceToHost));
     }
     std::string tsv;
     uint64_t distinct = 0;
@@ -1127,13 +1056,13 @@ int build(const blu_taxdb_desc& D, blu_taxdb_stats& S) {
     }
     if (n_seg && st[n_seg - 1] == S_BEYOND) {
         uint32_t first = 0;
-        HIPTRY(hipMemcpy(&first, seg_start + n_seg - 1, 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(&first, seg_start + n_seg - 1, 4, hipMemcpyDeviceToHost));
         const uint32_t nb = n - first;
         unsigned long long* d_big;
-        TRY(mem.alloc(&d_big, (size_t)nb * 8, "taxids beyond the tables"));
+        HIP_CHECK(pol, mem.alloc(&d_big, (size_t)nb * 8, "taxids beyond the tables"));
         hipLaunchKernelGGL(taxdb_gather_u64, dim3(grid(nb)), dim3(TPB), 0, 0, (const unsigned long long*)ao.tax64, (const uint32_t*)(vals + first), nb, d_big);
         std::vector<unsigned long long> big(nb);
-        HIPTRY(hipMemcpy(big.data(), d_big, (size_t)nb * 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(big.data(), d_big, (size_t)nb * 8, hipMemcpyDeviceToHost));
         std::sort(big.begin(), big.end());
         big.erase(std::unique(big.begin(), big.end()), big.end());
         for (unsigned long long v : big) { tsv += std::to_string(v); tsv += "\tunknown\n"; ++S.n_unknown; ++distinct; }
@@ -1142,7 +1071,9 @@ int build(const blu_taxdb_desc& D, blu_taxdb_stats& S) {
     lap(&S.t_render_ms);
 
     // ---- write: the head and tail around the rendered array (serde_json::to_string_pretty of TaxonomiesMap)
-    std::string headtxt = "{\n  \"blutilsVersion\": " + json_str(D.blutils_version ? D.blutils_version : BLU_TAXDB_DEFAULT_VERSION) + ",\n";
+    std::string headtxt = "{\n  \"blutilsVersion\": ";
+    json_str(headtxt, D.blutils_version ? D.blutils_version : BLU_TAXDB_DEFAULT_VERSION);
+    headtxt += ",\n";
     if (!D.has_skip) headtxt += "  \"ignoreTaxids\": null,\n";
     else if (D.n_skip == 0) headtxt += "  \"ignoreTaxids\": [],\n";
     else {
@@ -1154,11 +1085,18 @@ int build(const blu_taxdb_desc& D, blu_taxdb_stats& S) {
     else if (rep.empty()) headtxt += "  \"replaceRank\": {},\n";
     else {
         headtxt += "  \"replaceRank\": {";
-        for (size_t k = 0; k < rep.size(); ++k) headtxt += (k ? ",\n    " : "\n    ") + json_str(rep[k].first) + ": " + json_str(rep[k].second);
+        for (size_t k = 0; k < rep.size(); ++k) {
+            headtxt += k ? ",\n    " : "\n    ";
+            json_str(headtxt, rep[k].first);
+            headtxt += ": ";
+            json_str(headtxt, rep[k].second);
+        }
         headtxt += "\n  },\n";
     }
     headtxt += std::string("  \"dropNonLinnaeanTaxonomies\": ") + (D.drop_non_linnaean ? "true" : "false") + ",\n";
-    headtxt += "  \"sourceDatabase\": " + json_str(D.source_database ? D.source_database : "") + ",\n";
+    headtxt += "  \"sourceDatabase\": ";
+    json_str(headtxt, D.source_database ? D.source_database : "");
+    headtxt += ",\n";
     const std::string stem = D.output_stem;
     const std::string json_path = stem + ".blutils.json", tsv_path = stem + ".non-mapped.tsv";
     {   // rs:256-262: the TSV is removed and created again on every run

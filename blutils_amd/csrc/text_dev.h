@@ -50,6 +50,12 @@ __device__ __forceinline__ bool utf8_valid(const unsigned char* __restrict__ tex
     return ok && need == 0;
 }
 
+// decimal digits of v, and v written as d digits at out[0, d)
+__device__ __forceinline__ uint32_t n_digits(unsigned long long v) { uint32_t d = 1; while (v >= 10) { v /= 10; ++d; } return d; }
+__device__ __forceinline__ void put_digits(unsigned char* out, unsigned long long v, uint32_t d) {
+    for (uint32_t k = d; k > 0; --k) { out[k - 1] = (unsigned char)('0' + v % 10); v /= 10; }
+}
+
 __device__ __forceinline__ void trim(const unsigned char* __restrict__ text, uint64_t& a, uint64_t& b) {
     while (a < b && is_ws(text[a])) ++a;
     while (b > a && is_ws(text[b - 1])) --b;
