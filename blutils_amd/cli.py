@@ -15,12 +15,17 @@ the format's (write_blutils_output.rs:39-52) and JSON is pretty-printed.
     python -m blutils_amd.cli blastn build-consensus ... --report FILE [--report-weight one|size]
     python -m blutils_amd.cli blastn run-with-consensus ... --report FILE [--report-weight one|size]
     python -m blutils_amd.cli blastn build-report [BLU_RESULT|-] [-o OUT] [-i json|jsonl|yaml] [--weight one|size]
+    python -m blutils_amd.cli blastn build-consensus ... --sample-table FILE [--report-weight one|size]
+    python -m blutils_amd.cli blastn run-with-consensus ... --sample-table FILE [--report-weight one|size]
+    python -m blutils_amd.cli blastn build-report [BLU_RESULT|-] --by-sample [-o OUT] [-i json|jsonl|yaml] [--weight one|size]
 
 not in the reference: the taxon abundance report — how many queries, or with `size` weighting how many
 dereplicated reads (`;size=N` / `_size_N` in the query name), each taxon holds, summed up the lineage.  With --report it is
 counted on the GPU from the run's own records and written after the document, which stays what it is without the flag;
 build-report makes it on the host from an existing document, including one written by reference blutils
-(blutils_amd/report.py, csrc/report_kernel.hip).
+(blutils_amd/report.py, csrc/report_kernel.hip).  --sample-table (and build-report --by-sample) writes the same counts as a
+taxon x sample table, one column per sample named in the query names (`;sample=S`, or a `S.<n>` label as
+vsearch --relabel writes it); a query that names no sample is an error.
 
     python -m blutils_amd.cli cache-db TAX.json CACHE [-u]
 
@@ -93,12 +98,18 @@ def build_parser() -> argparse.ArgumentParser:
         sp.add_argument("--report", help="also write the taxon abundance report of the results to this file, counted on the "
                                          "GPU (not in the reference CLI)")
         sp.add_argument("--report-weight", default="one", choices=["one", "size"],
-                        help="count results (one) or the dereplicated reads in the query names (size)")
+                        help="count results (one) or the dereplicated reads in the query names (size); for --report and "
+                             "--sample-table")
+        sp.add_argument("--sample-table", help="also write the taxon x sample table of the results to this file, counted "
+                                               "on the GPU; samples from `;sample=S` or `S.<n>` query names (not in the "
+                                               "reference CLI)")
     br = blastn.add_parser("build-report", help="blutils result document -> taxon abundance report (not in the reference)")
     br.add_argument("blu_result", nargs="?", default="-")
     br.add_argument("-o", "--output-file")
     br.add_argument("-i", "--input-format", default="json", choices=["json", "jsonl", "yaml"])
     br.add_argument("--weight", default="one", choices=["one", "size"])
+    br.add_argument("--by-sample", action="store_true",
+                    help="write the taxon x sample table instead of the report (not in the reference CLI)")
     bt = blastn.add_parser("build-tabular", help="blutils result document -> TSV")
     bt.add_argument("blu_result", nargs="?", default="-")
     bt.add_argument("-o", "--output-file")
@@ -193,7 +204,8 @@ def _run_with_consensus(args) -> int:
         blast.run_blast_and_build_consensus(args.query, args.tax_file, args.blast_out_file, args.blutils_out_file, config,
                                             blast.ExecuteBlastnProcRepository(args.blastn), args.force_overwrite,
                                             args.threads, args.strategy, args.use_taxid, args.out_format, custom,
-                                            device=args.device, report_path=args.report, report_weight=args.report_weight)
+                                            device=args.device, report_path=args.report, report_weight=args.report_weight,
+                                            sample_table_path=args.sample_table)
     except blast.BlastError as e:
         raise SystemExit(str(e))
     return 0
@@ -214,7 +226,7 @@ def main(argv=None) -> int:
         return 0
     if args.sub == "build-report":
         try:
-            report.build_report(args.blu_result, args.output_file, args.input_format, args.weight)
+            report.build_report(args.blu_result, args.output_file, args.input_format, args.weight, by_sample=args.by_sample)
         except (tabular.TabularError, report.ReportError) as e:
             raise SystemExit(str(e))
         return 0
@@ -230,7 +242,10 @@ def main(argv=None) -> int:
     fmt = args.out_format if (to_file or args.out_format != "json") else "json-compact"
     # (with --report: the same document, plus the report file)
     build = pipeline.build_consensus_identities
-    if args.report is not None:
+    if args.sample_table is not None:
+        build = functools.partial(pipeline.build_consensus_identities_with_tables, report_path=args.report,
+                                  sample_table_path=args.sample_table, report_weight=args.report_weight)
+    elif args.report is not None:
         build = functools.partial(pipeline.build_consensus_identities_with_report, report_path=args.report,
                                   report_weight=args.report_weight)
     if to_file:

@@ -129,6 +129,9 @@ struct ReportInput {
     const uint32_t* weight;   // [n_queries] or null
 };
 int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* out);
+// the per-sample table of the same records: sample_of[n_queries] on the device
+int sample_table_device(const blu_taxonomy* tax, const ReportInput& in, const uint32_t* sample_of, uint32_t n_samples,
+                        blu_sample_table* out);
 
 void set_error(const char* fmt, ...);
 // LinnaeanRank::from_str (linnaean_ranks.rs:52-72): enum kind 0..8, or K_FIRST_OTHER with the slug in *other

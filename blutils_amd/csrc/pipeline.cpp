@@ -1109,18 +1109,11 @@ bool size_weight(std::string_view name, uint32_t* w) {
     return true;
 }
 
-// The report's text: header, unclassified, unplaced (when any), then the paths depth first, siblings by clade descending
-// and element text ascending (bytewise).  rep.paths has parents before children (blu_consensus_report).
-std::string render_report(const Db& db, const blu_report& rep) {
-    std::string o = "#percent\tclade\tdirect\trank\tidentifier\ttaxonomy\n";
-    const double total = (double)rep.total;
-    auto num = [&](uint64_t v) { char b[24]; auto r = std::to_chars(b, b + sizeof b, v); o.append(b, (size_t)(r.ptr - b)); };
-    auto pct = [&](uint64_t c) { char b[64]; const int n = snprintf(b, sizeof b, "%.2f", rep.total ? 100.0 * (double)c / total : 0.0); o.append(b, (size_t)n); };
-    auto fixed_row = [&](uint64_t c, const char* what) { pct(c); o.push_back('\t'); num(c); o.push_back('\t'); num(c); o += "\t-\t"; o += what; o += "\t\n"; };
-    fixed_row(rep.unclassified, "unclassified");
-    if (rep.unplaced) fixed_row(rep.unplaced, "unplaced");
-    const uint64_t n = rep.n_paths;
-    const blu_report_path* P = rep.paths;
+// The report's row order: the paths depth first, siblings by clade descending and element text `rank__identifier`
+// ascending (bytewise).  P has parents before children (blu_consensus_report, blu_consensus_sample_table).
+// row(i, rank, identifier, taxonomy) for every path in that order.
+template <class Row>
+void report_rows(const Db& db, const blu_report_path* P, uint64_t n, Row&& row) {
     // children of path i at kids[off[i + 1] .. off[i + 2]); the first-level paths at kids[off[0] .. off[1])
     std::vector<uint64_t> off(n + 2, 0);
     for (uint64_t i = 0; i < n; ++i) ++off[(P[i].parent == BLU_REPORT_NO_PARENT ? 0 : (uint64_t)P[i].parent + 1) + 1];
@@ -1154,10 +1147,81 @@ std::string render_report(const Db& db, const blu_report& rep) {
         path += rk; path += "__"; path += id;
         if (len_at.size() <= d) len_at.resize(d + 1);
         len_at[d] = path.size();
-        pct(P[i].clade); o.push_back('\t'); num(P[i].clade); o.push_back('\t'); num(P[i].direct); o.push_back('\t');
-        o += rk; o.push_back('\t'); o += id; o.push_back('\t'); o += path; o.push_back('\n');
+        row(i, rk, id, path);
         for (uint64_t k = off[(uint64_t)i + 2]; k-- > off[(uint64_t)i + 1];) stack.emplace_back(kids[k], d + 1);
     }
+}
+
+// The report's text: header, unclassified, unplaced (when any), then the paths in report_rows' order.
+std::string render_report(const Db& db, const blu_report& rep) {
+    std::string o = "#percent\tclade\tdirect\trank\tidentifier\ttaxonomy\n";
+    const double total = (double)rep.total;
+    auto num = [&](uint64_t v) { char b[24]; auto r = std::to_chars(b, b + sizeof b, v); o.append(b, (size_t)(r.ptr - b)); };
+    auto pct = [&](uint64_t c) { char b[64]; const int n = snprintf(b, sizeof b, "%.2f", rep.total ? 100.0 * (double)c / total : 0.0); o.append(b, (size_t)n); };
+    auto fixed_row = [&](uint64_t c, const char* what) { pct(c); o.push_back('\t'); num(c); o.push_back('\t'); num(c); o += "\t-\t"; o += what; o += "\t\n"; };
+    fixed_row(rep.unclassified, "unclassified");
+    if (rep.unplaced) fixed_row(rep.unplaced, "unplaced");
+    const blu_report_path* P = rep.paths;
+    report_rows(db, P, rep.n_paths, [&](uint32_t i, const std::string& rk, const std::string& id, const std::string& path) {
+        pct(P[i].clade); o.push_back('\t'); num(P[i].clade); o.push_back('\t'); num(P[i].direct); o.push_back('\t');
+        o += rk; o.push_back('\t'); o += id; o.push_back('\t'); o += path; o.push_back('\n');
+    });
+    return o;
+}
+
+// ---- per-sample table ---------------------------------------------------------------------------------
+// The sample a query name names: the first ';'-field `sample=` + at least one byte; else, in the label (the name up to its
+// first ';', a trailing `_size_` + digits removed), the part left of the last '.' when it is non-empty and the part right
+// of that '.' is one or more ASCII digits.  false: no sample.
+bool sample_of(std::string_view name, std::string_view* out) {
+    auto digits = [](std::string_view v) { if (v.empty()) return false; for (char c : v) if (c < '0' || c > '9') return false; return true; };
+    for (size_t pos = 0;;) {
+        const size_t semi = name.find(';', pos);
+        const std::string_view f = name.substr(pos, semi == std::string_view::npos ? std::string_view::npos : semi - pos);
+        if (f.size() > 7 && f.compare(0, 7, "sample=") == 0) { *out = f.substr(7); return true; }
+        if (semi == std::string_view::npos) break;
+        pos = semi + 1;
+    }
+    std::string_view label = name.substr(0, name.find(';'));
+    const size_t at = label.rfind("_size_");
+    if (at != std::string_view::npos && digits(label.substr(at + 6))) label = label.substr(0, at);
+    const size_t dot = label.rfind('.');
+    if (dot == std::string_view::npos || dot == 0 || !digits(label.substr(dot + 1))) return false;
+    *out = label.substr(0, dot);
+    return true;
+}
+
+// The table's text: header with the sample names, unclassified, unplaced (when any), then one line per path in the
+// report's order; a path's cells are tab.cells[cell_at[i] .. cell_at[i + 1]) (sorted by sample).
+std::string render_sample_table(const Db& db, const blu_sample_table& tab, const std::vector<std::string_view>& names) {
+    std::string o = "#rank\tidentifier\ttaxonomy\ttotal";
+    for (std::string_view s : names) { o.push_back('\t'); o.append(s.data(), s.size()); }
+    o.push_back('\n');
+    const uint32_t ns = tab.n_samples;
+    auto num = [&](uint64_t v) { char b[24]; auto r = std::to_chars(b, b + sizeof b, v); o.append(b, (size_t)(r.ptr - b)); };
+    auto fixed_row = [&](const uint64_t* per, const char* what) {
+        uint64_t t = 0;
+        for (uint32_t s = 0; s < ns; ++s) t += per[s];
+        if (!t && per == tab.unplaced) return;
+        o += "-\t"; o += what; o += "\t\t"; num(t);
+        for (uint32_t s = 0; s < ns; ++s) { o.push_back('\t'); num(per[s]); }
+        o.push_back('\n');
+    };
+    fixed_row(tab.unclassified, "unclassified");
+    fixed_row(tab.unplaced, "unplaced");
+    std::vector<uint64_t> cell_at(tab.n_paths + 1, 0);
+    for (uint64_t k = 0; k < tab.n_cells; ++k) ++cell_at[tab.cells[k].path + 1];
+    for (uint64_t i = 0; i < tab.n_paths; ++i) cell_at[i + 1] += cell_at[i];
+    report_rows(db, tab.paths, tab.n_paths, [&](uint32_t i, const std::string& rk, const std::string& id, const std::string& path) {
+        o += rk; o.push_back('\t'); o += id; o.push_back('\t'); o += path; o.push_back('\t'); num(tab.paths[i].clade);
+        uint64_t k = cell_at[i];
+        for (uint32_t s = 0; s < ns; ++s) {
+            o.push_back('\t');
+            if (k < cell_at[i + 1] && tab.cells[k].sample == s) num(tab.cells[k++].clade);
+            else o.push_back('0');
+        }
+        o.push_back('\n');
+    });
     return o;
 }
 
@@ -1176,6 +1240,8 @@ struct Document {
     bool written = false;      // the pieces went to the output file while they were rendered (and were freed)
     bool has_report = false;   // report: the taxon report's text, written by the caller once the document is out
     std::string report;
+    bool has_table = false;    // table: the per-sample table's text, written after the report
+    std::string table;
     size_t size() const { size_t n = 0; for (auto& p : pieces) n += p.size(); return n; }
 };
 
@@ -1251,14 +1317,90 @@ int build_report(const Db& db, const HitTable& ht, const blu_taxonomy* tax, cons
     return BLU_OK;
 }
 
+// The per-sample table of one pipeline run (blu_build_consensus_identities_tables): the samples from the query names and
+// the header-only names (ids in ascending byte order = column order), the weights, the device pass over the records (in
+// place on the device path; uploaded on the host path), the header-only queries as unclassified in their sample, the text.
+int build_sample_table(const Db& db, const HitTable& ht, const blu_taxonomy* tax, const Column<blu_result>& recs,
+                       const DeviceRecords& kept, bool on_device, const std::vector<uint32_t>& eng_rows,
+                       const std::vector<std::string>& extra, int32_t weight, std::string& text) {
+    const uint64_t nq = recs.size();
+    std::vector<uint32_t> sid(nq + extra.size());
+    std::vector<std::string_view> names;          // in order of first appearance, then sorted
+    {
+        std::unordered_map<std::string_view, uint32_t> seen;
+        std::string_view last;
+        uint32_t last_id = 0;
+        for (uint64_t k = 0; k < sid.size(); ++k) {
+            const std::string& name = k < nq ? ht.query_names[k] : extra[k - nq];
+            std::string_view smp;
+            if (!sample_of(name, &smp)) {
+                set_error("query `%s` names no sample: neither a `sample=` field nor a `<sample>.<digits>` label", name.c_str());
+                return BLU_ERR_INVALID_ARG;
+            }
+            // (a pooled file is per-sample files back to back: the previous query's sample first)
+            if (names.empty() || smp != last) {
+                auto it = seen.emplace(smp, (uint32_t)names.size());
+                if (it.second) names.push_back(smp);
+                last = smp;
+                last_id = it.first->second;
+            }
+            sid[k] = last_id;
+        }
+        std::vector<uint32_t> order(names.size()), rank(names.size());
+        for (uint32_t i = 0; i < order.size(); ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return names[a] < names[b]; });
+        std::vector<std::string_view> sorted(names.size());
+        for (uint32_t r = 0; r < order.size(); ++r) { rank[order[r]] = r; sorted[r] = names[order[r]]; }
+        names.swap(sorted);
+        for (uint32_t& x : sid) x = rank[x];
+    }
+    const uint32_t ns = (uint32_t)names.size();
+    std::vector<uint32_t> w, extra_w(extra.size(), 1);
+    if (weight == BLU_REPORT_WEIGHT_SIZE) {
+        w.resize(nq);
+        for (uint64_t q = 0; q < nq; ++q)
+            if (!size_weight(ht.query_names[q], &w[q])) { set_error("query `%s`: its size is 2^32 or more", ht.query_names[q].c_str()); return BLU_ERR_INVALID_ARG; }
+        for (size_t k = 0; k < extra.size(); ++k)
+            if (!size_weight(extra[k], &extra_w[k])) { set_error("query `%s`: its size is 2^32 or more", extra[k].c_str()); return BLU_ERR_INVALID_ARG; }
+    }
+    blu_sample_table tab{};
+    struct Free { blu_sample_table& t; ~Free() { blu_sample_table_free(&t); } } free_tab{tab};
+    int rc;
+    if (on_device && nq) {
+        HipPolicy pol{"sample table", BLU_ERR_ALLOC};
+        DeviceArena mem(pol);
+        uint32_t *d_w = nullptr, *d_s = nullptr;
+        if (!w.empty()) {
+            HIP_CHECK(pol, mem.alloc(&d_w, nq * 4, "weights"));
+            HIP_CHECK(pol, hipMemcpy(d_w, w.data(), nq * 4, hipMemcpyHostToDevice));
+        }
+        HIP_CHECK(pol, mem.alloc(&d_s, nq * 4, "sample ids"));
+        HIP_CHECK(pol, hipMemcpy(d_s, sid.data(), nq * 4, hipMemcpyHostToDevice));
+        ReportInput in{kept.recs, nq, kept.rows, ht.n_hits, kept.row_stride, false, d_w};
+        rc = sample_table_device(tax, in, d_s, ns, &tab);
+    } else {
+        blu_hits h{};
+        h.tax_row = eng_rows.data();
+        h.n_hits = eng_rows.size();
+        h.n_queries = nq;
+        h.on_device = 0;
+        rc = blu_consensus_sample_table(tax, &h, recs.data(), w.empty() ? nullptr : w.data(), sid.data(), ns, nullptr, &tab);
+    }
+    if (rc != BLU_OK) return rc;
+    for (size_t k = 0; k < extra.size(); ++k) tab.unclassified[sid[nq + k]] += extra_w[k];
+    text = render_sample_table(db, tab, names);
+    return BLU_OK;
+}
+
 // out_path != nullptr: the document is written there (an existing file is replaced, write_blutils_output.rs:57-63) by a
 // writer thread that follows the renderers piece by piece; otherwise the pieces are left in `document`.
 int build_document(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
                    const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
                    const char* config_text, const char* out_path, Document* document, blu_pipeline_stats* stats,
-                   const blu_report_params* report = nullptr) {
+                   const blu_tables_params* tables = nullptr) {
     if (!blast_output_file || !taxonomies_file || !params || !document) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
-    if (report && (!report->report_path || (report->weight != BLU_REPORT_WEIGHT_ONE && report->weight != BLU_REPORT_WEIGHT_SIZE))) {
+    if (tables && ((!tables->report_path && !tables->sample_table_path) ||
+                   (tables->weight != BLU_REPORT_WEIGHT_ONE && tables->weight != BLU_REPORT_WEIGHT_SIZE))) {
         set_error("report: a path and weight BLU_REPORT_WEIGHT_ONE or BLU_REPORT_WEIGHT_SIZE are needed");
         return BLU_ERR_INVALID_ARG;
     }
@@ -1426,12 +1568,18 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
             return BLU_ERR_REFERENCE_PANIC;
         }
     }
-    if (report) {
+    if (tables && tables->report_path) {
         // the taxon report, from the records while they (on the device path: and the engine rows) are still on the device
-        rc = build_report(db, ht, tax, recs, kept, done_on_device, eng_rows, extra, report->weight, document->report);
+        rc = build_report(db, ht, tax, recs, kept, done_on_device, eng_rows, extra, tables->weight, document->report);
         if (rc != BLU_OK) return rc;
         document->has_report = true;
         tr.lap("report");
+    }
+    if (tables && tables->sample_table_path) {
+        rc = build_sample_table(db, ht, tax, recs, kept, done_on_device, eng_rows, extra, tables->weight, document->table);
+        if (rc != BLU_OK) return rc;
+        document->has_table = true;
+        tr.lap("sample table");
     }
     const bool pretty = params->out_format == BLU_OUT_JSON;
     const bool doc = pretty || params->out_format == BLU_OUT_JSON_COMPACT;   // one {results, config} document
@@ -1589,18 +1737,25 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     return BLU_OK;
 }
 
+// the report, then the per-sample table, after the document
+int put_tables(const Document& d, const blu_tables_params* tables) {
+    if (d.has_report && !write_text_file(tables->report_path, d.report)) { set_error("cannot write %s", tables->report_path); return BLU_ERR_IO; }
+    if (d.has_table && !write_text_file(tables->sample_table_path, d.table)) { set_error("cannot write %s", tables->sample_table_path); return BLU_ERR_IO; }
+    return BLU_OK;
+}
+
 int consensus_to_text(const char* blast_output_file, const char* const* headers, uint64_t n_headers, const char* taxonomies_file,
-                      const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const blu_report_params* report,
+                      const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const blu_tables_params* tables,
                       char** out_text, size_t* out_len, blu_pipeline_stats* stats) {
     if (!out_text) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     *out_text = nullptr;
     if (out_len) *out_len = 0;
     Document d;
     int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats, report); }
+    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats, tables); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }   // (no exception crosses the C ABI)
     if (rc != BLU_OK) return rc;
-    if (d.has_report && !write_text_file(report->report_path, d.report)) { set_error("cannot write %s", report->report_path); return BLU_ERR_IO; }
+    if ((rc = put_tables(d, tables)) != BLU_OK) return rc;
     const size_t total = d.size();
     char* buf = (char*)malloc(total + 1);
     if (!buf) { set_error("out of memory"); return BLU_ERR_ALLOC; }
@@ -1614,21 +1769,18 @@ int consensus_to_text(const char* blast_output_file, const char* const* headers,
     return BLU_OK;
 }
 
-// (the report file, when asked for, is written once the document is out)
+// (the report and table files, when asked for, are written once the document is out)
 int consensus_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers, const char* taxonomies_file,
                       const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const char* out_path,
-                      const blu_report_params* report, blu_pipeline_stats* stats) {
+                      const blu_tables_params* tables, blu_pipeline_stats* stats) {
     if (!out_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     Document d;
     int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats, report); }
+    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats, tables); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
     if (rc != BLU_OK) return rc;
     if (getenv("BLU_INGEST_TRACE")) fprintf(stderr, "[pipeline] %-26s %.3f s\n", "tear-down (tables, strings)", now_s() - g_t_body_end);
-    auto put_report = [&]() -> int {
-        if (d.has_report && !write_text_file(report->report_path, d.report)) { set_error("cannot write %s", report->report_path); return BLU_ERR_IO; }
-        return BLU_OK;
-    };
+    auto put_report = [&]() { return put_tables(d, tables); };
     if (d.written) return put_report();
     // (YAML: one piece, written here) write_blutils_output.rs:57-63: an existing file is replaced
     Trace tr;
@@ -1676,10 +1828,20 @@ int blu_build_consensus_identities_report(const char* blast_output_file, const c
                                           const char* config_text, const char* out_path, const blu_report_params* report,
                                           char** out_text, size_t* out_len, blu_pipeline_stats* stats) {
     if (!report || !report->report_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    const blu_tables_params tables{report->report_path, nullptr, report->weight, 0};
+    return blu_build_consensus_identities_tables(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text,
+                                                 out_path, &tables, out_text, out_len, stats);
+}
+
+int blu_build_consensus_identities_tables(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                          const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
+                                          const char* config_text, const char* out_path, const blu_tables_params* tables,
+                                          char** out_text, size_t* out_len, blu_pipeline_stats* stats) {
+    if (!tables || (!tables->report_path && !tables->sample_table_path)) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     if (out_path)
-        return consensus_to_file(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, report,
+        return consensus_to_file(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, tables,
                                  stats);
-    return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, report, out_text,
+    return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, tables, out_text,
                              out_len, stats);
 }
 

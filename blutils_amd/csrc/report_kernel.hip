@@ -184,7 +184,157 @@ __global__ void report_compact(const unsigned long long* __restrict__ keys, cons
     out[at[i]] = p;
 }
 
+// ---- per-sample table (blu_consensus_sample_table) -------------------------------------------------------
+// One walk per query, as report_paths: every prefix path p of the query's path is interned in the report's path table and
+// the query's weight goes to the cell (p, sample), so a cell is a clade count with no roll-up.  Cells live in a second
+// open-addressing table keyed (path id << 32 | sample id), u64 integer adds.  Each block pre-aggregates its cells in LDS
+// first: a pooled file is per-sample files back to back, so a block of consecutive queries mostly shares one sample and
+// its upper levels.  The per-sample unclassified / unplaced counts travel through the same LDS table under two path ids
+// no path table reaches (the tables are limited to 2^31 slots).
+constexpr uint32_t CELL_UNCLASSIFIED = 0xFFFFFFFEu, CELL_UNPLACED = 0xFFFFFFFDu;
+constexpr uint32_t CELL_LDS_SLOTS = 2048;       // block-local cell table (32 KB)
+constexpr uint32_t FLAG_BAD_SAMPLE = 4u;
+
+struct SampleDev {
+    ReportDev r;                    // the report's walk and path table (r.direct is not used); r.ctl[4]: a bad sample's query
+    const uint32_t* sample_of;      // [n_queries]
+    uint32_t n_samples;
+    uint32_t cell_mask;
+    unsigned long long* cell_keys;  // [cell_mask + 1]
+    unsigned long long* cell_val;   // [cell_mask + 1]
+    unsigned long long* fixed;      // [2 n_samples]: unclassified per sample, then unplaced per sample
+};
+
+// adds w to a cell of the global table; false when max_probe slots were all taken by other keys
+__device__ __forceinline__ bool cell_add(const SampleDev& d, unsigned long long key, unsigned long long w) {
+    uint32_t h = mix_key(key) & d.cell_mask;
+    for (uint32_t p = 0; p < d.r.max_probe; ++p, h = (h + 1) & d.cell_mask) {
+        unsigned long long cur = d.cell_keys[h];
+        if (cur == REPORT_EMPTY) {
+            cur = atomicCAS(d.cell_keys + h, REPORT_EMPTY, key);
+            if (cur == REPORT_EMPTY) cur = key;
+        }
+        if (cur == key) { atomicAdd(d.cell_val + h, w); return true; }
+    }
+    return false;
+}
+
+// a block's sum for one key reaches global memory: the fixed rows' arrays, or the cell table
+__device__ __forceinline__ uint32_t cell_flush(const SampleDev& d, unsigned long long key, unsigned long long w) {
+    const uint32_t path = (uint32_t)(key >> 32), s = (uint32_t)key;
+    if (path == CELL_UNCLASSIFIED) { atomicAdd(d.fixed + s, w); return 0; }
+    if (path == CELL_UNPLACED) { atomicAdd(d.fixed + d.n_samples + s, w); return 0; }
+    return cell_add(d, key, w) ? 0u : FLAG_OVERFLOW;
+}
+
+__global__ __launch_bounds__(RB) void sample_cells(SampleDev d) {
+    __shared__ unsigned long long s_key[CELL_LDS_SLOTS];
+    __shared__ unsigned long long s_cnt[CELL_LDS_SLOTS];
+    for (uint32_t i = threadIdx.x; i < CELL_LDS_SLOTS; i += RB) { s_key[i] = REPORT_EMPTY; s_cnt[i] = 0; }
+    __syncthreads();
+    uint32_t flags = 0;
+    // block-local table first, global memory when it is crowded (w > 0: a zero weight leaves no cell behind)
+    auto add = [&](uint32_t path, uint32_t s, unsigned long long w) {
+        const unsigned long long key = ((unsigned long long)path << 32) | s;
+        uint32_t h = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 53);   // 11 bits: CELL_LDS_SLOTS
+        for (uint32_t p = 0; p < LDS_PROBE; ++p, h = (h + 1) & (CELL_LDS_SLOTS - 1)) {
+            unsigned long long cur = s_key[h];
+            if (cur == REPORT_EMPTY) {
+                cur = atomicCAS(s_key + h, REPORT_EMPTY, key);
+                if (cur == REPORT_EMPTY) cur = key;
+            }
+            if (cur == key) { atomicAdd(s_cnt + h, w); return; }
+        }
+        flags |= cell_flush(d, key, w);
+    };
+    const uint64_t base = (uint64_t)blockIdx.x * (RB * RQ) + threadIdx.x;
+    for (uint32_t k = 0; k < RQ; ++k) {
+        const uint64_t q = base + (uint64_t)k * RB;
+        if (q >= d.r.n_queries) break;
+        const uint4* rp = reinterpret_cast<const uint4*>(d.r.recs + q);
+        const uint4 a = rp[0], b = rp[1];
+        const uint32_t s = d.sample_of[q];
+        if (s >= d.n_samples) { flags |= FLAG_BAD_SAMPLE; d.r.ctl[4] = q; continue; }
+        const uint32_t status = a.x & 0xFFu;
+        const uint32_t ref_row = a.w;
+        const unsigned long long mask = (unsigned long long)b.x | ((unsigned long long)b.y << 32);
+        const unsigned long long w = d.r.weight ? (unsigned long long)d.r.weight[q] : 1ull;
+        if (status >= 2) { if (w) add(CELL_UNCLASSIFIED, s, w); continue; }   // taxon: null
+        const uint64_t idx = d.r.by_query ? q : (uint64_t)ref_row;
+        uint32_t row = REPORT_NONE;
+        if (idx < d.r.n_rows) row = d.r.row_src[idx * d.r.row_stride];
+        const uint32_t pos = row & ((1u << BLU_ROW_BITS) - 1u);
+        if (row == BLU_UNMATCHED_TAXID || pos >= d.r.n_tax) { flags |= FLAG_BAD_RECORD; d.r.ctl[3] = q; continue; }
+        const uint32_t* lin = d.r.lin + (uint64_t)pos * d.r.stride;
+        const uint32_t len = min(lin[0] & 0xFFu, d.r.max_depth);
+        const unsigned long long m = len >= 64 ? mask : mask & ((1ull << len) - 1ull);
+        if (m == 0) { if (w) add(CELL_UNPLACED, s, w); continue; }           // taxonomy: ""
+        uint32_t path = REPORT_NONE;
+        for (uint32_t j = 0; j < len; ++j) {
+            if (!((m >> j) & 1ull)) continue;
+            path = intern(d.r, path, lin[d.r.node_base + j]);
+            if (path == REPORT_NONE) { flags |= FLAG_OVERFLOW; break; }
+            if (w) add(path, s, w);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < CELL_LDS_SLOTS; i += RB)
+        if (s_key[i] != REPORT_EMPTY && s_cnt[i]) flags |= cell_flush(d, s_key[i], s_cnt[i]);
+    if (flags) atomicOr(reinterpret_cast<unsigned int*>(d.r.ctl + 2), flags);
+}
+
+// the occupied path slots in slot order, parents renamed to their index in that order (report_compact without counts)
+__global__ void sample_paths_compact(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ at, uint64_t cap,
+                                     blu_report_path* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap) return;
+    const unsigned long long k = keys[i];
+    if (k == REPORT_EMPTY) return;
+    const uint32_t parent = (uint32_t)(k >> 32);
+    blu_report_path p;
+    p.node = (uint32_t)k;
+    p.parent = parent == REPORT_NONE ? REPORT_NONE : at[parent];
+    p.direct = 0;
+    p.clade = 0;
+    out[at[i]] = p;
+}
+
+// the occupied cells in slot order, their path slots renamed to the compacted path index
+__global__ void sample_cells_compact(const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ val,
+                                     const uint32_t* __restrict__ at, const uint32_t* __restrict__ path_at, uint64_t cap,
+                                     blu_sample_cell* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap) return;
+    const unsigned long long k = keys[i];
+    if (k == REPORT_EMPTY) return;
+    blu_sample_cell c;
+    c.path = path_at[(uint32_t)(k >> 32)];
+    c.sample = (uint32_t)k;
+    c.clade = val[i];
+    out[at[i]] = c;
+}
+
 uint64_t next_pow2(uint64_t x) { uint64_t c = 1; while (c < x) c <<= 1; return c; }
+
+// paths[] (parents named by index, in any order) -> at[i], the position of path i when parents come first: depth order,
+// input order inside a depth
+void parents_first(const std::vector<blu_report_path>& paths, std::vector<uint32_t>& at) {
+    const uint64_t n_paths = paths.size();
+    const uint32_t NONE = REPORT_NONE;
+    std::vector<uint8_t> depth(n_paths, 0xFF);
+    std::vector<uint32_t> stack;
+    for (uint64_t i = 0; i < n_paths; ++i) {
+        uint32_t x = (uint32_t)i;
+        while (depth[x] == 0xFF && paths[x].parent != NONE && depth[paths[x].parent] == 0xFF) { stack.push_back(x); x = paths[x].parent; }
+        if (depth[x] == 0xFF) depth[x] = paths[x].parent == NONE ? 0 : (uint8_t)(depth[paths[x].parent] + 1);
+        while (!stack.empty()) { const uint32_t y = stack.back(); stack.pop_back(); depth[y] = (uint8_t)(depth[paths[y].parent] + 1); }
+    }
+    std::vector<uint64_t> first(BLU_MAX_DEPTH + 1, 0);
+    for (uint64_t i = 0; i < n_paths; ++i) ++first[depth[i] + 1];
+    for (uint32_t k = 0; k < BLU_MAX_DEPTH; ++k) first[k + 1] += first[k];
+    at.resize(n_paths);
+    for (uint64_t i = 0; i < n_paths; ++i) at[i] = (uint32_t)first[depth[i]]++;
+}
 
 }  // namespace
 
@@ -265,19 +415,8 @@ int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* ou
     {
         // parents first (depth order, slot order inside a depth), then clade = direct + the children's clades
         const uint32_t NONE = REPORT_NONE;
-        std::vector<uint8_t> depth(n_paths, 0xFF);
-        std::vector<uint32_t> stack;
-        for (uint64_t i = 0; i < n_paths; ++i) {
-            uint32_t x = (uint32_t)i;
-            while (depth[x] == 0xFF && paths[x].parent != NONE && depth[paths[x].parent] == 0xFF) { stack.push_back(x); x = paths[x].parent; }
-            if (depth[x] == 0xFF) depth[x] = paths[x].parent == NONE ? 0 : (uint8_t)(depth[paths[x].parent] + 1);
-            while (!stack.empty()) { const uint32_t y = stack.back(); stack.pop_back(); depth[y] = (uint8_t)(depth[paths[y].parent] + 1); }
-        }
-        std::vector<uint64_t> first(BLU_MAX_DEPTH + 1, 0);
-        for (uint64_t i = 0; i < n_paths; ++i) ++first[depth[i] + 1];
-        for (uint32_t k = 0; k < BLU_MAX_DEPTH; ++k) first[k + 1] += first[k];
-        std::vector<uint32_t> at(n_paths);
-        for (uint64_t i = 0; i < n_paths; ++i) at[i] = (uint32_t)first[depth[i]]++;
+        std::vector<uint32_t> at;
+        parents_first(paths, at);
         blu_report_path* o = n_paths ? (blu_report_path*)malloc(n_paths * sizeof(blu_report_path)) : nullptr;
         if (n_paths && !o) { set_error("report: out of memory"); return BLU_ERR_ALLOC; }
         for (uint64_t i = 0; i < n_paths; ++i) {
@@ -296,6 +435,152 @@ int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* ou
         for (uint64_t i = 0; i < n_paths; ++i) if (o[i].parent == NONE) classified += o[i].clade;
         out->total = ctl[0] + ctl[1] + classified;
         out->table_slots = cap;
+        out->attempts = attempts;
+    }
+    return BLU_OK;
+}
+
+int sample_table_device(const blu_taxonomy* tax, const ReportInput& in, const uint32_t* sample_of, uint32_t n_samples,
+                        blu_sample_table* out) {
+    const uint64_t nq = in.n_queries;
+    unsigned long long *d_keys = nullptr, *d_ckeys = nullptr, *d_cval = nullptr, *d_ctl = nullptr, *d_fixed = nullptr;
+    uint32_t *d_at = nullptr, *d_cat = nullptr;
+    void* d_tmp = nullptr;
+    blu_report_path* d_paths = nullptr;
+    blu_sample_cell* d_cells = nullptr;
+    unsigned long long ctl[5] = {0, 0, 0, 0, 0};
+    uint64_t cap = 0, ccap = 0, n_paths = 0, n_cells = 0;
+    uint32_t attempts = 0;
+    std::vector<blu_report_path> paths;
+    std::vector<blu_sample_cell> cells;
+    std::vector<uint64_t> fixed(2 * (uint64_t)n_samples);
+    HipPolicy pol{"sample table", BLU_ERR_ALLOC};
+    DeviceArena mem(pol);
+    struct Events { hipEvent_t ev0 = nullptr, ev1 = nullptr; ~Events() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); } } ev;
+    HIP_CHECK(pol, hipEventCreate(&ev.ev0));
+    HIP_CHECK(pol, hipEventCreate(&ev.ev1));
+    HIP_CHECK(pol, mem.alloc(&d_ctl, sizeof ctl, "counters"));
+    HIP_CHECK(pol, mem.alloc(&d_fixed, fixed.size() * 8, "per-sample counters"));
+    {
+        // paths as the report sizes them; cells: the paths plus one per query (a sample's queries mostly share their upper
+        // levels), at most one per level of every query
+        const uint64_t depth = std::max<uint32_t>(tax->max_depth, 1);
+        const uint64_t guess = std::min<uint64_t>(nq * depth, 2 * tax->n_tax + 4096);
+        const uint64_t cguess = std::min<uint64_t>(nq * depth, guess + nq);
+        cap = std::max<uint64_t>(next_pow2(2 * guess), 1024);
+        ccap = std::max<uint64_t>(next_pow2(2 * cguess), 1024);
+        uint32_t max_probe = REPORT_PROBE_FIRST;
+        SampleDev d{};
+        d.r.lin = tax->d_lin; d.r.n_tax = tax->n_tax; d.r.stride = tax->dev_stride; d.r.node_base = tax->node_base;
+        d.r.max_depth = tax->max_depth;
+        d.r.recs = in.recs; d.r.n_queries = nq; d.r.row_src = in.row_src; d.r.n_rows = in.n_rows; d.r.row_stride = in.row_stride;
+        d.r.by_query = in.by_query ? 1u : 0u; d.r.weight = in.weight; d.r.ctl = d_ctl;
+        d.sample_of = sample_of; d.n_samples = n_samples; d.fixed = d_fixed;
+        HIP_CHECK(pol, hipEventRecord(ev.ev0, nullptr));
+        for (;;) {
+            ++attempts;
+            // (path ids below 2^31: the two ids above are the fixed rows' in the cell keys)
+            if (cap > (1ull << 31) || ccap > (1ull << 32)) {
+                set_error("sample table: tables of %llu / %llu slots exceed 32-bit ids", (unsigned long long)cap, (unsigned long long)ccap);
+                return BLU_ERR_ALLOC;
+            }
+            HIP_CHECK(pol, mem.alloc(&d_keys, cap * 8, "path table"));
+            HIP_CHECK(pol, mem.alloc(&d_ckeys, ccap * 8, "cell table"));
+            HIP_CHECK(pol, mem.alloc(&d_cval, ccap * 8, "cell table"));
+            HIP_CHECK(pol, hipMemsetAsync(d_keys, 0xFF, cap * 8, nullptr));
+            HIP_CHECK(pol, hipMemsetAsync(d_ckeys, 0xFF, ccap * 8, nullptr));
+            HIP_CHECK(pol, hipMemsetAsync(d_cval, 0, ccap * 8, nullptr));
+            HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, sizeof ctl, nullptr));
+            HIP_CHECK(pol, hipMemsetAsync(d_fixed, 0, fixed.size() * 8, nullptr));
+            d.r.keys = d_keys; d.r.cap_mask = (uint32_t)(cap - 1); d.r.max_probe = max_probe;
+            d.cell_keys = d_ckeys; d.cell_val = d_cval; d.cell_mask = (uint32_t)(ccap - 1);
+            if (nq) hipLaunchKernelGGL(sample_cells, dim3((unsigned)((nq + RB * RQ - 1) / (RB * RQ))), dim3(RB), 0, 0, d);
+            HIP_CHECK(pol, hipGetLastError());
+            HIP_CHECK(pol, hipMemcpy(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+            if (ctl[2] & FLAG_BAD_SAMPLE) {
+                set_error("sample table: query %llu has a sample id that is not below n_samples = %u", (unsigned long long)ctl[4], n_samples);
+                return BLU_ERR_INVALID_ARG;
+            }
+            if (ctl[2] & FLAG_BAD_RECORD) {
+                set_error("sample table: record %llu has a taxon (status 0 / 1) but its reference row names no taxonomy row",
+                          (unsigned long long)ctl[3]);
+                return BLU_ERR_INVALID_ARG;
+            }
+            if (!(ctl[2] & FLAG_OVERFLOW)) break;
+            if (max_probe != REPORT_PROBE_FIRST) { set_error("sample table: table overflow"); return BLU_ERR_HIP; }   // (cannot happen at load <= 1/2)
+            // the estimate was short: both tables again from zero, sized from the bound on paths and on cells
+            mem.free(d_keys); mem.free(d_ckeys); mem.free(d_cval); d_keys = d_ckeys = d_cval = nullptr;
+            HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, 8, nullptr));
+            hipLaunchKernelGGL(report_bound, dim3((unsigned)std::min<uint64_t>((nq + RB - 1) / RB, 4096)), dim3(RB), 0, 0, in.recs, nq, d_ctl);
+            HIP_CHECK(pol, hipGetLastError());
+            unsigned long long bound = 0;
+            HIP_CHECK(pol, hipMemcpy(&bound, d_ctl, 8, hipMemcpyDeviceToHost));
+            cap = ccap = std::max<uint64_t>(next_pow2(2 * bound), 1024);
+            max_probe = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
+        }
+        HIP_CHECK(pol, mem.alloc(&d_at, (cap + 1) * 4, "path ids"));
+        HIP_CHECK(pol, mem.alloc(&d_cat, (ccap + 1) * 4, "cell ids"));
+        HIP_CHECK(pol, mem.alloc(&d_tmp, scan_tmp_bytes_u32(std::max(cap, ccap) + 1), "scan scratch"));
+        hipLaunchKernelGGL(report_flags, dim3((unsigned)((cap + 1 + 255) / 256)), dim3(256), 0, 0, d_keys, cap, d_at);
+        HIP_CHECK(pol, hipGetLastError());
+        HIP_CHECK(pol, exclusive_scan_u32(d_at, d_at, cap + 1, d_tmp));
+        hipLaunchKernelGGL(report_flags, dim3((unsigned)((ccap + 1 + 255) / 256)), dim3(256), 0, 0, d_ckeys, ccap, d_cat);
+        HIP_CHECK(pol, hipGetLastError());
+        HIP_CHECK(pol, exclusive_scan_u32(d_cat, d_cat, ccap + 1, d_tmp));
+        uint32_t n32[2] = {0, 0};
+        HIP_CHECK(pol, hipMemcpy(&n32[0], d_at + cap, 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(&n32[1], d_cat + ccap, 4, hipMemcpyDeviceToHost));
+        n_paths = n32[0];
+        n_cells = n32[1];
+        HIP_CHECK(pol, mem.alloc(&d_paths, n_paths * sizeof(blu_report_path), "paths"));
+        HIP_CHECK(pol, mem.alloc(&d_cells, n_cells * sizeof(blu_sample_cell), "cells"));
+        hipLaunchKernelGGL(sample_paths_compact, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, 0, d_keys, d_at, cap, d_paths);
+        HIP_CHECK(pol, hipGetLastError());
+        hipLaunchKernelGGL(sample_cells_compact, dim3((unsigned)((ccap + 255) / 256)), dim3(256), 0, 0, d_ckeys, d_cval, d_cat, d_at, ccap, d_cells);
+        HIP_CHECK(pol, hipGetLastError());
+        HIP_CHECK(pol, hipEventRecord(ev.ev1, nullptr));
+        paths.resize(n_paths);
+        cells.resize(n_cells);
+        if (n_paths) HIP_CHECK(pol, hipMemcpy(paths.data(), d_paths, n_paths * sizeof(blu_report_path), hipMemcpyDeviceToHost));
+        if (n_cells) HIP_CHECK(pol, hipMemcpy(cells.data(), d_cells, n_cells * sizeof(blu_sample_cell), hipMemcpyDeviceToHost));
+        if (n_samples) HIP_CHECK(pol, hipMemcpy(fixed.data(), d_fixed, fixed.size() * 8, hipMemcpyDeviceToHost));
+        float ms = 0;
+        HIP_CHECK(pol, hipEventElapsedTime(&ms, ev.ev0, ev.ev1));
+        out->t_device_ms = ms;
+    }
+    {
+        // parents first as in the report; a path's clade = the sum of its cells, direct = clade - the children's clades;
+        // the cells ordered by path (a counting sort), then by sample inside a path
+        const uint32_t NONE = REPORT_NONE;
+        std::vector<uint32_t> at;
+        parents_first(paths, at);
+        blu_report_path* o = (blu_report_path*)malloc(std::max<uint64_t>(n_paths, 1) * sizeof(blu_report_path));
+        blu_sample_cell* c = (blu_sample_cell*)malloc(std::max<uint64_t>(n_cells, 1) * sizeof(blu_sample_cell));
+        uint64_t* un = (uint64_t*)malloc(std::max<uint64_t>(fixed.size(), 1) * 8);
+        if (!o || !c || !un) { free(o); free(c); free(un); set_error("sample table: out of memory"); return BLU_ERR_ALLOC; }
+        for (uint64_t i = 0; i < n_paths; ++i) {
+            blu_report_path p = paths[i];
+            p.parent = p.parent == NONE ? NONE : at[p.parent];
+            o[at[i]] = p;
+        }
+        std::vector<uint64_t> first(n_paths + 1, 0);
+        for (const blu_sample_cell& x : cells) { o[at[x.path]].clade += x.clade; ++first[at[x.path] + 1]; }
+        for (uint64_t i = 0; i < n_paths; ++i) first[i + 1] += first[i];
+        for (const blu_sample_cell& x : cells) { blu_sample_cell y = x; y.path = at[x.path]; c[first[y.path]++] = y; }
+        for (uint64_t i = 0, lo = 0; i < n_paths; lo = first[i++])
+            if (first[i] - lo > 1) std::sort(c + lo, c + first[i], [](const blu_sample_cell& a, const blu_sample_cell& b) { return a.sample < b.sample; });
+        for (uint64_t i = 0; i < n_paths; ++i) o[i].direct = o[i].clade;
+        for (uint64_t i = n_paths; i-- > 0;)
+            if (o[i].parent != NONE) o[o[i].parent].direct -= o[i].clade;
+        std::copy(fixed.begin(), fixed.end(), un);
+        out->paths = o;
+        out->n_paths = n_paths;
+        out->cells = c;
+        out->n_cells = n_cells;
+        out->n_samples = n_samples;
+        out->unclassified = un;
+        out->unplaced = un + n_samples;
+        out->table_slots = ccap;
         out->attempts = attempts;
     }
     return BLU_OK;
@@ -345,6 +630,58 @@ int blu_consensus_report(const blu_taxonomy* tax, const blu_hits* hits, const bl
         ReportInput hin{d_recs, nq, d_rows, nq, 1u, true, d_w};
         return report_device(tax, hin, out);
     } catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
+}
+
+int blu_consensus_sample_table(const blu_taxonomy* tax, const blu_hits* hits, const blu_result* results, const uint32_t* weights,
+                               const uint32_t* sample_of, uint32_t n_samples, void* stream, blu_sample_table* out) {
+    if (!tax || !hits || !out || (hits->n_queries && (!results || !sample_of))) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    memset(out, 0, sizeof *out);
+    if (tax->device < 0) { set_error("host-only taxonomy handle: blu_consensus_sample_table needs a HIP device (no CPU fallback)"); return BLU_ERR_NO_DEVICE; }
+    const uint32_t* src = hits->packed ? hits->packed : hits->packed64 ? hits->packed64 : hits->tax_row;
+    const uint32_t stride = hits->packed ? 4u : hits->packed64 ? 6u : 1u;
+    const uint64_t nq = hits->n_queries, nh = hits->n_hits;
+    if (nq && !src) { set_error("blu_consensus_sample_table: no tax_row column"); return BLU_ERR_INVALID_ARG; }
+    if (hipSetDevice(tax->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", tax->device); return BLU_ERR_NO_DEVICE; }
+    ReportInput in{results, nq, src, nh, stride, false, weights};
+    if (hits->on_device) {
+        if (((uintptr_t)results & 15u) != 0) { set_error("blu_consensus_sample_table: device records must be 16-byte aligned"); return BLU_ERR_INVALID_ARG; }
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) { set_error("blu_consensus_sample_table: stream synchronise failed"); return BLU_ERR_HIP; }
+        try { return sample_table_device(tax, in, sample_of, n_samples, out); }
+        catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
+    }
+    // host pointers: the records, each record's engine row, the weights and the sample ids go up
+    HipPolicy pol{"blu_consensus_sample_table", BLU_ERR_ALLOC};
+    DeviceArena mem(pol);
+    blu_result* d_recs = nullptr;
+    uint32_t *d_rows = nullptr, *d_w = nullptr, *d_s = nullptr;
+    try {
+        std::vector<uint32_t> rows(nq, BLU_UNMATCHED_TAXID);
+        for (uint64_t q = 0; q < nq; ++q)
+            if (results[q].status < 2 && results[q].ref_row < nh) rows[q] = src[(uint64_t)results[q].ref_row * stride];
+        HIP_CHECK(pol, mem.alloc(&d_recs, nq * sizeof(blu_result), "records"));
+        HIP_CHECK(pol, mem.alloc(&d_rows, nq * 4, "rows"));
+        HIP_CHECK(pol, mem.alloc(&d_s, nq * 4, "sample ids"));
+        if (weights) HIP_CHECK(pol, mem.alloc(&d_w, nq * 4, "weights"));
+        if (nq) {
+            HIP_CHECK(pol, hipMemcpy(d_recs, results, nq * sizeof(blu_result), hipMemcpyHostToDevice));
+            HIP_CHECK(pol, hipMemcpy(d_rows, rows.data(), nq * 4, hipMemcpyHostToDevice));
+            HIP_CHECK(pol, hipMemcpy(d_s, sample_of, nq * 4, hipMemcpyHostToDevice));
+            if (weights) HIP_CHECK(pol, hipMemcpy(d_w, weights, nq * 4, hipMemcpyHostToDevice));
+        }
+        ReportInput hin{d_recs, nq, d_rows, nq, 1u, true, d_w};
+        return sample_table_device(tax, hin, d_s, n_samples, out);
+    } catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
+}
+
+void blu_sample_table_free(blu_sample_table* table) {
+    if (!table) return;
+    free(table->paths);
+    free(table->cells);
+    free(table->unclassified);   // (unplaced points into the same block)
+    table->paths = nullptr;
+    table->cells = nullptr;
+    table->unclassified = table->unplaced = nullptr;
+    table->n_paths = table->n_cells = 0;
 }
 
 void blu_report_free(blu_report* report) {

@@ -113,6 +113,10 @@ class ReportParams(C.Structure):
     _fields_ = [("report_path", C.c_char_p), ("weight", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TablesParams(C.Structure):
+    _fields_ = [("report_path", C.c_char_p), ("sample_table_path", C.c_char_p), ("weight", C.c_int32), ("reserved", C.c_int32)]
+
+
 REPORT_WEIGHT = {"one": 0, "size": 1}
 
 
@@ -143,8 +147,23 @@ def build_consensus_identities_with_report(blast_output: str, taxonomies_file: s
                   lenient, parse, config, out_path, report_path, report_weight)
 
 
+def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
+                                           strategy: str = "relaxed", use_taxid: Optional[bool] = None,
+                                           custom_taxon_values: Optional[dict] = None,
+                                           headers: Optional[Sequence[str]] = None, out_format: str = "json",
+                                           device: int = 0, lenient: bool = False, parse: bool = True, config=None,
+                                           out_path: Optional[str] = None, report_path: Optional[str] = None,
+                                           sample_table_path: Optional[str] = None, report_weight: str = "one"):
+    """build_consensus_identities plus the taxon abundance report (report_path), the per-sample table (sample_table_path,
+    DESIGN.md §13), or both, counted on the GPU and written in the order document, report, table
+    (include/blu_pipeline.h: blu_build_consensus_identities_tables).  report_weight serves both files.  A query whose name
+    names no sample fails the call before any file is written."""
+    return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
+                  lenient, parse, config, out_path, report_path, report_weight, sample_table_path)
+
+
 def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device, lenient,
-           parse, config, out_path, report_path, report_weight):
+           parse, config, out_path, report_path, report_weight, sample_table_path=None):
     L = _bind()
     p = PipelineParams()
     p.cutoffs.taxon = N.TAXON[taxon]
@@ -172,7 +191,22 @@ def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_tax
                                                      C.POINTER(PipelineStats)]
     run_id = str(config.run_id).encode() if config is not None else None
     cfg_text = config.render(out_format).encode() if config is not None else None
-    if report_path is not None:
+    if sample_table_path is not None:
+        tp = TablesParams(str(report_path).encode() if report_path is not None else None, str(sample_table_path).encode(),
+                          REPORT_WEIGHT[report_weight], 0)
+        L.blu_build_consensus_identities_tables.restype = C.c_int
+        L.blu_build_consensus_identities_tables.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
+                                                            C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(TablesParams),
+                                                            C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(PipelineStats)]
+        rc = L.blu_build_consensus_identities_tables(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
+                                                     taxonomies_file.encode(), C.byref(p), run_id, cfg_text,
+                                                     out_path.encode() if out_path is not None else None, C.byref(tp),
+                                                     C.byref(text), C.byref(n), C.byref(st))
+        if rc != N.BLU_OK:
+            raise N.BluError(rc, "blu_build_consensus_identities_tables")
+        if out_path is not None:
+            return None, {f: getattr(st, f) for f, _ in PipelineStats._fields_}
+    elif report_path is not None:
         rp = ReportParams(str(report_path).encode(), REPORT_WEIGHT[report_weight], 0)
         L.blu_build_consensus_identities_report.restype = C.c_int
         L.blu_build_consensus_identities_report.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),

@@ -12,6 +12,11 @@ reference.  Two ways in:
   text written by the library.  Both give the same bytes for the same results.
 
 `consensus_report` binds the engine-level call for callers that hold the records themselves.
+
+The per-sample table is the report split into one column per sample, the sample read off the query name
+(`sample_of`): `sample_table_from_results` / `build_report(..., by_sample=True)` on the host, `build-consensus
+--sample-table` counted on the GPU (pipeline.build_consensus_identities_with_tables), `consensus_sample_table` at the engine
+level.  Both paths give the same bytes for the same results.
 """
 from __future__ import annotations
 
@@ -69,6 +74,15 @@ def render(unclassified: int, unplaced: int, paths) -> str:
     out = [HEADER, f"{_pct(unclassified, total)}\t{unclassified}\t{unclassified}\t-\tunclassified\t\n"]
     if unplaced:
         out.append(f"{_pct(unplaced, total)}\t{unplaced}\t{unplaced}\t-\tunplaced\t\n")
+    for p in _row_order(paths):
+        direct, clade = paths[p]
+        rank, _, ident = p[-1].partition("__")
+        out.append(f"{_pct(clade, total)}\t{clade}\t{direct}\t{rank}\t{ident}\t{';'.join(p)}\n")
+    return "".join(out)
+
+
+def _row_order(paths):
+    """The report's rows: depth first, siblings by clade descending, then element text ascending (bytewise)."""
     kids = {}
     for p in paths:
         kids.setdefault(p[:-1], []).append(p)
@@ -77,11 +91,8 @@ def render(unclassified: int, unplaced: int, paths) -> str:
     stack = list(reversed(kids.get((), [])))
     while stack:
         p = stack.pop()
-        direct, clade = paths[p]
-        rank, _, ident = p[-1].partition("__")
-        out.append(f"{_pct(clade, total)}\t{clade}\t{direct}\t{rank}\t{ident}\t{';'.join(p)}\n")
+        yield p
         stack.extend(reversed(kids.get(p, [])))
-    return "".join(out)
 
 
 def report_from_results(results, weight: str = "one") -> str:
@@ -106,14 +117,72 @@ def report_from_results(results, weight: str = "one") -> str:
     return render(unclassified, unplaced, paths)
 
 
+def sample_of(query: str) -> str:
+    """The sample a query name names: the first ';'-separated field that is `sample=` + at least one character; else, in
+    the label (the name up to its first ';', a trailing `_size_` + digits removed), the part left of the last '.' when it
+    is non-empty and the part right of it is ASCII digits (vsearch --relabel `<sample>.<n>`).  No sample is an error
+    naming the query."""
+    for field in query.split(";"):
+        if field.startswith("sample=") and len(field) > 7:
+            return field[7:]
+    label = query.split(";", 1)[0]
+    at = label.rfind("_size_")
+    if at >= 0 and _digits(label[at + 6:]):
+        label = label[:at]
+    dot = label.rfind(".")
+    if dot > 0 and _digits(label[dot + 1:]):
+        return label[:dot]
+    raise ReportError(f"query `{query}` names no sample: neither a `sample=` field nor a `<sample>.<digits>` label")
+
+
+def sample_table_from_results(results, weight: str = "one") -> str:
+    """The per-sample table of a document's `results` list: one column per sample, in ascending byte order of the names;
+    the report's rows in the report's order, each a clade count per sample."""
+    samples = {}
+    unclassified, unplaced = {}, {}
+    paths, cells = {}, {}
+    for r in results:
+        q = str(r["query"])
+        s = sample_of(q)
+        w = weight_of(q, weight)
+        samples[s] = None
+        taxon = r.get("taxon")
+        if taxon is None:
+            unclassified[s] = unclassified.get(s, 0) + w
+            continue
+        tax = taxon.get("taxonomy")
+        if not tax:
+            unplaced[s] = unplaced.get(s, 0) + w
+            continue
+        els = tuple(tax.split(";"))
+        for i in range(1, len(els) + 1):
+            paths.setdefault(els[:i], [0, 0])[1] += w
+            c = cells.setdefault(els[:i], {})
+            c[s] = c.get(s, 0) + w
+        paths[els][0] += w
+    cols = sorted(samples, key=lambda s: s.encode("utf-8", "surrogatepass"))
+
+    def line(rank, ident, taxonomy, per):
+        return "\t".join([rank, ident, taxonomy, str(sum(per.values()))] + [str(per.get(s, 0)) for s in cols]) + "\n"
+
+    out = ["\t".join(["#rank", "identifier", "taxonomy", "total"] + cols) + "\n", line("-", "unclassified", "", unclassified)]
+    if sum(unplaced.values()):
+        out.append(line("-", "unplaced", "", unplaced))
+    for p in _row_order(paths):
+        rank, _, ident = p[-1].partition("__")
+        out.append(line(rank, ident, ";".join(p), cells[p]))
+    return "".join(out)
+
+
 def build_report(blu_result: str = "-", output_file: Optional[str] = None, input_format: str = "json",
-                 weight: str = "one", stdout=None) -> str:
-    """`blastn build-report`: the report of an existing document, to output_file or stdout."""
+                 weight: str = "one", stdout=None, by_sample: bool = False) -> str:
+    """`blastn build-report`: the report of an existing document, to output_file or stdout; by_sample: the per-sample
+    table instead."""
     try:
         content = tabular.load_content(blu_result, input_format)
     except FileNotFoundError:
         raise ReportError(f"The file `{blu_result}` does not exist.") from None
-    text = report_from_results(content["results"], weight)
+    text = (sample_table_from_results if by_sample else report_from_results)(content["results"], weight)
     if output_file is None:
         (stdout if stdout is not None else sys.stdout).write(text)
     else:
@@ -185,3 +254,72 @@ def consensus_report(tax, tax_row, records, n_hits: int, weights=None, on_device
                 "table_slots": int(rep.table_slots), "attempts": int(rep.attempts), "t_device_ms": float(rep.t_device_ms)}
     finally:
         L.blu_report_free(C.byref(rep))
+
+
+# ---- engine-level binding (include/blu_consensus.h: blu_consensus_sample_table) -------------------------------------
+
+class SampleCell(C.Structure):
+    _fields_ = [("path", C.c_uint32), ("sample", C.c_uint32), ("clade", C.c_uint64)]
+
+
+class SampleTable(C.Structure):
+    _fields_ = [("n_paths", C.c_uint64), ("paths", C.POINTER(ReportPath)), ("n_cells", C.c_uint64),
+                ("cells", C.POINTER(SampleCell)), ("n_samples", C.c_uint32), ("reserved", C.c_uint32),
+                ("unclassified", C.POINTER(C.c_uint64)), ("unplaced", C.POINTER(C.c_uint64)), ("table_slots", C.c_uint64),
+                ("attempts", C.c_uint32), ("reserved2", C.c_uint32), ("t_device_ms", C.c_double)]
+
+
+def consensus_sample_table(tax, tax_row, records, n_hits: int, sample_of, n_samples: int, weights=None,
+                           on_device: Optional[bool] = None, stream=None, packed: Optional[str] = None) -> dict:
+    """blu_consensus_sample_table on one run's records: the arguments of consensus_report plus sample_of (uint32 per
+    query, on the records' side) and n_samples.  Returns {"paths": as consensus_report, "cells": structured numpy array
+    (path, sample, clade) sorted by (path, sample), "unclassified", "unplaced": uint64 arrays [n_samples], "table_slots",
+    "attempts", "t_device_ms"}."""
+    import numpy as np
+
+    def ptr(a):
+        if a is None:
+            return None
+        return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+    if on_device is None:
+        on_device = bool(getattr(records, "is_cuda", False))
+    nbytes = records.numel() * records.element_size() if hasattr(records, "numel") else records.nbytes
+    nq = nbytes // 32
+    keep = []
+    if not on_device:
+        tax_row = np.ascontiguousarray(tax_row).view(np.uint32)
+        records = np.ascontiguousarray(records)
+        sample_of = np.ascontiguousarray(sample_of, dtype=np.uint32)
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.uint32)
+        keep += [tax_row, records, sample_of, weights]
+    col = {"packed": (None, ptr(tax_row), None), "packed64": (None, None, ptr(tax_row))}.get(packed, (ptr(tax_row), None, None))
+    h = N.Hits(None, col[0], None, None, None, None, int(n_hits), int(nq), 1 if on_device else 0, 0, None, col[1], col[2])
+    if stream is None and on_device:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    L = N.lib()
+    L.blu_consensus_sample_table.restype = C.c_int
+    L.blu_consensus_sample_table.argtypes = [C.c_void_p, C.POINTER(N.Hits), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                             C.c_void_p, C.POINTER(SampleTable)]
+    L.blu_sample_table_free.argtypes = [C.POINTER(SampleTable)]
+    tab = SampleTable()
+    rc = L.blu_consensus_sample_table(tax.handle, C.byref(h), ptr(records), ptr(weights), ptr(sample_of), int(n_samples), stream,
+                                      C.byref(tab))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_consensus_sample_table")
+    try:
+        pdt = np.dtype([("node", np.uint32), ("parent", np.uint32), ("direct", np.uint64), ("clade", np.uint64)])
+        cdt = np.dtype([("path", np.uint32), ("sample", np.uint32), ("clade", np.uint64)])
+
+        def take(p, n, dt):
+            return np.frombuffer(C.string_at(p, n * dt.itemsize), dtype=dt).copy() if n else np.zeros(0, dtype=dt)
+
+        ns = int(tab.n_samples)
+        return {"paths": take(tab.paths, int(tab.n_paths), pdt), "cells": take(tab.cells, int(tab.n_cells), cdt),
+                "unclassified": take(tab.unclassified, ns, np.dtype(np.uint64)),
+                "unplaced": take(tab.unplaced, ns, np.dtype(np.uint64)), "table_slots": int(tab.table_slots),
+                "attempts": int(tab.attempts), "t_device_ms": float(tab.t_device_ms)}
+    finally:
+        L.blu_sample_table_free(C.byref(tab))

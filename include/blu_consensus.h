@@ -303,6 +303,40 @@ int blu_consensus_report(const blu_taxonomy* tax, const blu_hits* hits, const bl
                          void* stream, blu_report* out);
 void blu_report_free(blu_report* report);
 
+/* -------------------------------------------------------------------------- */
+/* Per-sample taxon abundance table (additive, ABI v5).  The report above split by sample: every query names a sample id
+ * (sample_of[q] < n_samples), and a cell (path, sample) holds the summed weight of that sample's queries whose path has
+ * `path` as a prefix — a clade count per sample.  Counted on the device in one walk per query (csrc/report_kernel.hip,
+ * the report's path table shared); DESIGN.md §13. */
+typedef struct blu_sample_cell {
+    uint32_t path;     /* index into blu_sample_table.paths */
+    uint32_t sample;   /* < n_samples */
+    uint64_t clade;    /* > 0 */
+} blu_sample_cell;     /* 16 bytes */
+
+typedef struct blu_sample_table {
+    uint64_t n_paths;
+    blu_report_path* paths;   /* [n_paths] parents before their children, as blu_report.paths; direct and clade are summed
+                                 over the samples (the report's numbers) */
+    uint64_t n_cells;
+    blu_sample_cell* cells;   /* [n_cells] the non-zero cells, sorted by (path, sample) */
+    uint32_t n_samples;
+    uint32_t reserved;
+    uint64_t* unclassified;   /* [n_samples] weight of the records with status >= 2, per sample */
+    uint64_t* unplaced;       /* [n_samples] weight of the records with a taxon whose level_mask selects no level */
+    uint64_t table_slots;     /* size of the device cell table of the last attempt */
+    uint32_t attempts;        /* 1, or 2 when the first tables (sized from an estimate) were rebuilt from the bound */
+    uint32_t reserved2;
+    double t_device_ms;       /* table clear + count + compaction on the device, by events */
+} blu_sample_table;           /* every array malloc'd by the library: blu_sample_table_free */
+
+/* The per-sample table of one run's records: hits, results, weights and stream as for blu_consensus_report;
+ * sample_of[n_queries] the sample id of each query, on the same side as the records.  A sample id >= n_samples is
+ * BLU_ERR_INVALID_ARG naming the query index; a table that cannot be allocated is BLU_ERR_ALLOC. */
+int blu_consensus_sample_table(const blu_taxonomy* tax, const blu_hits* hits, const blu_result* results, const uint32_t* weights,
+                               const uint32_t* sample_of, uint32_t n_samples, void* stream, blu_sample_table* out);
+void blu_sample_table_free(blu_sample_table* table);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,27 @@ int blu_build_consensus_identities_report(const char* blast_output_file, const c
                                           const char* config_text, const char* out_path, const blu_report_params* report,
                                           char** out_text, size_t* out_len, blu_pipeline_stats* stats);
 
+/* The same with the report, a per-sample table, or both: either path may be NULL.  Files are written in the
+ * order document, report, table.  The table is counted on the device (blu_consensus_sample_table) and is tab-separated:
+ *   #rank  identifier  taxonomy  total  <sample 1>  <sample 2> ...   (header; samples ascending bytewise)
+ *   -  unclassified  (empty)  U  u1  u2 ...                          always
+ *   -  unplaced  (empty)  N  n1  n2 ...                              when N > 0
+ *   rank  identifier  taxonomy  clade  <clade in sample 1> ...       one line per path, in the report's order
+ * The sample of a query: the first ';'-field `sample=<one or more bytes>`; else, in the label (the name up to its first ';'
+ * with a trailing `_size_<digits>` removed), the part left of the last '.' when that part is non-empty and the part right
+ * of it is ASCII digits (vsearch --relabel `<sample>.<n>`).  A query (hit or header) with neither is BLU_ERR_INVALID_ARG
+ * naming it, before any file is written.  `weight` applies to both files. */
+typedef struct blu_tables_params {
+    const char* report_path;         /* NULL: no report */
+    const char* sample_table_path;   /* NULL: no per-sample table */
+    int32_t weight;                  /* enum blu_report_weight */
+    int32_t reserved;
+} blu_tables_params;
+int blu_build_consensus_identities_tables(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                          const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
+                                          const char* config_text, const char* out_path, const blu_tables_params* tables,
+                                          char** out_text, size_t* out_len, blu_pipeline_stats* stats);
+
 /* The text-ingest half alone (no GPU): DB JSON + outfmt-6 TSV -> SoA columns, as blu_build_consensus_identities does it.
  * Fills stats (rows, queries, taxids, unmatched rows, load times) and *checksum with an FNV-1a hash over every SoA
  * column, the segment offsets and the query names — identical for any BLU_INGEST_THREADS value.  For tests and for

@@ -1,6 +1,8 @@
 /* Synthetic BlastN outfmt-6 table (13 columns, the form `blutils build-consensus` reads) and the matching blutils
  * taxonomy JSON, written fast enough for the 2 M-query end-to-end run (100 M rows, 6.7 GB) to be set up in seconds.
- *   gen_blast table <out.tsv> <queries> <hits> <taxa> <seed> [clustered|uniform]
+ *   gen_blast table <out.tsv> <queries> <hits> <taxa> <seed> [clustered|uniform] [samples]
+ *     samples > 0: query names `S<k>.<q>` (k zero-padded to 3 digits) in `samples` contiguous runs, the pooled-sample
+ *     labels of vsearch --relabel; otherwise `q<8 digits>`
  *   gen_blast db    <out.json> <taxa>
  * Same row format as scripts/ingest_bench.py's generator. */
 #include <stdint.h>
@@ -46,6 +48,7 @@ int main(int argc, char** argv) {
     const long queries = atol(argv[3]), hits = atol(argv[4]), taxa = atol(argv[5]);
     s_state = (uint64_t)atol(argv[6]) * 0x2545F4914F6CDD1Dull + 1;
     const int uniform = argc > 7 && strcmp(argv[7], "uniform") == 0;
+    const long samples = argc > 8 ? atol(argv[8]) : 0;
     const size_t cap = 1u << 22;
     char* buf = (char*)malloc(cap + 256);
     char* p = buf;
@@ -54,7 +57,9 @@ int main(int argc, char** argv) {
         for (long h = 0; h < hits; ++h) {
             const uint64_t sub = uniform ? rnd() % (uint64_t)taxa : (centre + rnd() % 96) % (uint64_t)taxa;
             const uint64_t pid = 80000 + rnd() % 20001, aln = 380 + rnd() % 100, bs = 200 + rnd() % 1800;
-            *p++ = 'q'; p = put_u(p, (uint64_t)q, 8);
+            if (samples > 0) { *p++ = 'S'; p = put_u(p, (uint64_t)(q * samples / queries), 3); *p++ = '.'; }
+            else *p++ = 'q';
+            p = put_u(p, (uint64_t)q, 8);
             p = put_s(p, "\tNR_"); p = put_u(p, sub, 6); p = put_s(p, ".1\t");
             p = put_u(p, 1000 + sub, 0); *p++ = '\t';
             p = put_u(p, pid / 1000, 0); *p++ = '.'; p = put_u(p, pid % 1000, 3); *p++ = '\t';
