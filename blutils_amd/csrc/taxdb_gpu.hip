@@ -707,8 +707,11 @@ struct Parsed {
 
 // LinnaeanRank::from_str + Display (linnaean_ranks.rs:55-90): the letter, or the slug of an Other rank
 std::string rank_token(const std::string& r, bool* other) {
-    std::string slug;
-    const uint16_t k = parse_rank(r.c_str(), &slug);
+    // parse_rank reads a C string and a rank may hold a NUL: to both of its rules (trim + letter match, slug) NUL is what 0x01
+    // is, a byte that is neither white space nor [a-z0-9]
+    std::string s = r, slug;
+    std::replace(s.begin(), s.end(), '\0', '\x01');
+    const uint16_t k = parse_rank(s.c_str(), &slug);
     *other = k == K_FIRST_OTHER;
     return *other ? slug : std::string(1, "udkpcofgs"[k]);
 }

@@ -25,9 +25,10 @@ def write_case(d: str, nodes=None, names=None, lineage=None, merged="", delnodes
     nodes = nodes if nodes is not None else "".join(dmp(t, 1, r, "", 0) for t, r, _ in BASE_NODES)
     base_names = "".join(dmp(t, n, "", "scientific name") for t, _, n in BASE_NODES)
     lineage = lineage if lineage is not None else "".join(dmp(t, (l + " ") if l else "") for t, l in BASE_LINEAGE.items())
-    files = {"nodes.dmp": nodes.encode(), "names.dmp": raw_names if raw_names is not None else (base_names + (names or "")).encode(),
-             "taxidlineage.dmp": lineage.encode(), "merged.dmp": merged.encode(), "delnodes.dmp": delnodes.encode(),
-             "accessions.txt": accessions if isinstance(accessions, bytes) else accessions.encode()}
+    raw = lambda x: x if isinstance(x, bytes) else x.encode()          # every file may be given as raw bytes
+    files = {"nodes.dmp": raw(nodes), "names.dmp": raw_names if raw_names is not None else (base_names + (names or "")).encode(),
+             "taxidlineage.dmp": raw(lineage), "merged.dmp": raw(merged), "delnodes.dmp": raw(delnodes),
+             "accessions.txt": raw(accessions)}
     for name, data in files.items():
         with open(os.path.join(d, name), "wb") as f:
             f.write(data)
