@@ -27,6 +27,15 @@ build-report makes it on the host from an existing document, including one writt
 taxon x sample table, one column per sample named in the query names (`;sample=S`, or a `S.<n>` label as
 vsearch --relabel writes it); a query that names no sample is an error.
 
+    python -m blutils_amd.cli blastn build-consensus ... [--min-perc-identity P] [--min-align-length L] [--max-e-value E]
+        [--min-bit-score B]
+    python -m blutils_amd.cli blastn run-with-consensus ... (the same four)
+
+not in the reference: hit filters.  Only the lines of the table that meet every threshold given take part, as
+if the others had been deleted from the file first; the GPU parser applies them.  With run-with-consensus the BLAST table is
+still written in full (`-p/-q/-e` go to blastn itself); the filter applies to the consensus step.  One line goes to stderr:
+`hit filter: kept K of N lines`.
+
     python -m blutils_amd.cli cache-db TAX.json CACHE [-u]
 
 writes the binary cache of a taxonomies file (not in the reference CLI; pass CACHE as -t afterwards).  
@@ -103,6 +112,17 @@ def build_parser() -> argparse.ArgumentParser:
         sp.add_argument("--sample-table", help="also write the taxon x sample table of the results to this file, counted "
                                                "on the GPU; samples from `;sample=S` or `S.<n>` query names (not in the "
                                                "reference CLI)")
+        flt = sp.add_argument_group("hit filters (not in the reference CLI)",
+                                    "a line of the table takes part only if it meets every threshold given; applied by "
+                                    "the parser, on the GPU where it parses")
+        flt.add_argument("--min-perc-identity", type=_threshold, metavar="P",
+                         help="keep lines with perc_identity (column 4) >= P (not in the reference CLI)")
+        flt.add_argument("--min-align-length", type=_length, metavar="L",
+                         help="keep lines with align_length (column 5) >= L (not in the reference CLI)")
+        flt.add_argument("--max-e-value", type=_threshold, metavar="E",
+                         help="keep lines with e_value (column 12) <= E (not in the reference CLI)")
+        flt.add_argument("--min-bit-score", type=_threshold, metavar="B",
+                         help="keep lines with bit_score (column 13) as written >= B (not in the reference CLI)")
     br = blastn.add_parser("build-report", help="blutils result document -> taxon abundance report (not in the reference)")
     br.add_argument("blu_result", nargs="?", default="-")
     br.add_argument("-o", "--output-file")
@@ -159,6 +179,33 @@ def _u64(text: str) -> int:
     return v
 
 
+def _threshold(text: str) -> float:
+    """a float threshold of a hit filter: NaN compares false with everything and is refused"""
+    v = float(text)
+    if v != v:
+        raise argparse.ArgumentTypeError("NaN is not a threshold")
+    return v
+
+
+def _length(text: str) -> int:
+    """an alignment length: a non-negative integer"""
+    v = int(text)
+    if v < 0 or v >= (1 << 63):
+        raise argparse.ArgumentTypeError(f"invalid length: {text!r}")
+    return v
+
+
+def _hit_filter(args):
+    """the four flags -> pipeline.HitFilter, or None when none was given (today's calls)"""
+    f = pipeline.HitFilter(args.min_perc_identity, args.min_align_length, args.max_e_value, args.min_bit_score)
+    return f if f.active() else None
+
+
+def _say_kept(stats) -> None:
+    if stats and "n_kept" in stats:
+        print(f"hit filter: kept {stats['n_kept']} of {stats['n_lines']} lines", file=sys.stderr)
+
+
 def _build_db(args) -> int:
     """ports/cli/src/cmds/db_builder/mod.rs:12-44"""
     try:
@@ -200,14 +247,17 @@ def _run_with_consensus(args) -> int:
         custom = pipeline.custom_taxon_from_file(args.custom_taxon_cutoff_file)
     elif args.taxon == "custom":
         raise SystemExit("Custom taxon values are required when the custom taxon option is selected.")
+    stats = {}
     try:
         blast.run_blast_and_build_consensus(args.query, args.tax_file, args.blast_out_file, args.blutils_out_file, config,
                                             blast.ExecuteBlastnProcRepository(args.blastn), args.force_overwrite,
                                             args.threads, args.strategy, args.use_taxid, args.out_format, custom,
                                             device=args.device, report_path=args.report, report_weight=args.report_weight,
-                                            sample_table_path=args.sample_table)
+                                            sample_table_path=args.sample_table, hit_filter=_hit_filter(args),
+                                            filter_stats=stats)
     except blast.BlastError as e:
         raise SystemExit(str(e))
+    _say_kept(stats)
     return 0
 
 
@@ -242,6 +292,8 @@ def main(argv=None) -> int:
     fmt = args.out_format if (to_file or args.out_format != "json") else "json-compact"
     # (with --report: the same document, plus the report file)
     build = pipeline.build_consensus_identities
+    hit_filter = _hit_filter(args)
+    extra = {"hit_filter": hit_filter} if hit_filter is not None else {}
     if args.sample_table is not None:
         build = functools.partial(pipeline.build_consensus_identities_with_tables, report_path=args.report,
                                   sample_table_path=args.sample_table, report_weight=args.report_weight)
@@ -253,12 +305,13 @@ def main(argv=None) -> int:
         parent = os.path.dirname(path)
         if parent and not os.path.exists(parent):
             os.makedirs(parent)
-        build(args.blast_out, args.tax_file, args.taxon, args.strategy, args.use_taxid, custom, headers=None, out_format=fmt,
-              device=args.device, parse=False, out_path=path)
+        _, stats = build(args.blast_out, args.tax_file, args.taxon, args.strategy, args.use_taxid, custom, headers=None,
+                         out_format=fmt, device=args.device, parse=False, out_path=path, **extra)
     else:
-        text, _ = build(args.blast_out, args.tax_file, args.taxon, args.strategy, args.use_taxid, custom, headers=None,
-                        out_format=fmt, device=args.device, parse=False)
+        text, stats = build(args.blast_out, args.tax_file, args.taxon, args.strategy, args.use_taxid, custom, headers=None,
+                            out_format=fmt, device=args.device, parse=False, **extra)
         sys.stdout.write(text)
+    _say_kept(stats)
     return 0
 
 

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "blu_consensus.h"
+#include "blu_pipeline.h"
 
 namespace blu {
 
@@ -94,6 +95,7 @@ struct HitTable {
     uint64_t unmatched = 0;
     uint64_t n_hits = 0;                         // rows of the table (the host columns may be absent, see below)
     uint64_t n_queries = 0;                      // = query_names.size() once the strings are there (wait_strings())
+    uint64_t n_lines = 0, n_kept = 0;            // under a hit filter: non-empty lines read, lines kept
     bool host_columns = true;                    // false: the GPU ingest was asked to leave the columns on the device only
     std::unique_ptr<DeviceHits> dev;             // set by the GPU ingest
     // The GPU ingest returns as soon as the device columns are complete; query_names and accessions are still being
@@ -106,7 +108,7 @@ struct HitTable {
         wait_strings();
         query_names.clear(); accessions.clear();
         seg_off = {}; bitscore = {}; align_len = {}; tax_desc_row = {}; acc_rank = {}; pident = {};
-        unmatched = n_hits = n_queries = 0; host_columns = true; strings_ok = true;
+        unmatched = n_hits = n_queries = n_lines = n_kept = 0; host_columns = true; strings_ok = true;
         dev.reset();
     }
     HitTable() = default;
@@ -134,7 +136,13 @@ struct TopTable {
 // host_columns = false: the grouped columns stay on the device only (ht.dev) — download_columns() fetches them later
 // if they turn out to be needed.
 // fd: the table, open for reading (the text is read with pread straight into pinned staging buffers).
-int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, std::string* why);
+// flt: a hit filter with a non-empty mask, or null: the rows that fail it are dropped between the parse and
+// the dictionaries, so that everything after sees the kept lines only; ht.n_lines / ht.n_kept are set.
+int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, std::string* why,
+                  const blu_hit_filter* flt = nullptr);
+// an f64 field as the host parser types it (pipeline.cpp: parse_f64 — strtod's value); false: not a number.  The GPU ingest
+// decides with it the e-values its own arithmetic leaves open.
+bool parse_f64_field(const char* p, size_t n, double* out);
 int download_columns(HitTable& ht);
 // Brings the HIP runtime and the device's null stream up (the first call into the runtime costs 0.06-0.26 s, the first
 // queue another 0.04-0.17 s: whoever comes first pays); the use-case starts it on a thread of its own before it reads

@@ -34,6 +34,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
+#include <cmath>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -41,6 +42,7 @@
 #include <string>
 #include <string_view>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "blu_consensus.h"
@@ -339,7 +341,67 @@ struct NumState {
         *out = neg ? -x : x;
         return true;
     }
+    // the grammar value() takes, whatever the exponent: the e-value column of a filtered parse (its decision: e_value_verdict)
+    __device__ bool plain() const { return !(bad || !any || digits > 15 || frac > 300 || (seen_exp && exp_digits == 0)); }
+    __device__ int exponent() const { return (exp_neg ? -exp10 : exp10) - frac; }
 };
+
+// ---- hit filter.  The parse kernels' filtered builds evaluate the thresholds of include/blu_pipeline.h's
+// blu_hit_filter on the values they parsed and leave one word per line: 0 dropped, 1 kept, 2 = e-value left to the host.
+struct DevFilter {
+    uint32_t mask;               // BLU_FILTER_* bits
+    uint32_t e_band;             // 1: an e-value within a few decades of max_e may be computed here (max_e in [1e-280, 1e280])
+    double min_pid, min_bs, max_e;
+    long long min_aln;
+    int k_keep, k_drop;          // decimal magnitude tests: digits + exponent <= k_keep -> below max_e; digits - 1 + exponent >= k_drop -> above
+    double e_lo, e_hi;           // max_e (1 -+ 2^-46): a computed value at or below e_lo is kept, at or above e_hi dropped
+    uint32_t* keep;              // [n_rows]
+    unsigned long long* counts;  // [0 .. FCNT_SPREAD) kept lines (spread over blocks), [FCNT_SPREAD] lines left to the host
+};
+constexpr uint32_t FCNT_SPREAD = 64;
+enum : uint32_t { KEEP_NO = 0, KEEP_YES = 1, KEEP_ASK_HOST = 2 };
+
+// `strtod(field) <= max_e` for a field of the plain grammar (NumState::plain), value = mant x 10^e with mant < 10^15.
+//   1. mant == 0: the value is zero.  A minus sign: left to the host (BLAST writes none).
+//   2. d = decimal digits of mant: 10^(d - 1 + e) <= value < 10^(d + e); the host derived k_keep / k_drop from max_e with two
+//      decades of slack, so these two tests are safe whatever strtod rounds to (overflow to inf and underflow to 0 included).
+//   3. |e| <= 22: one correctly rounded operation on exact operands gives strtod's value (as NumState::value): compared as is.
+//   4. otherwise mant is scaled by exact powers of ten, 22 decades per step: at most 14 steps inside the band, each within
+//      2^-53 relative, so the result x is within 2^-49 of the decimal value v.  x <= max_e (1 - 2^-46) gives v < max_e, hence
+//      strtod(v) <= max_e (rounding is monotonic); x >= max_e (1 + 2^-46) gives v > max_e (1 + 2^-47), beyond the double
+//      above max_e, hence strtod(v) > max_e.  In between — in practice a field spelled like the threshold — the host decides
+//      from the field's bytes.
+__device__ __noinline__ uint32_t e_value_verdict(unsigned long long mant, int e, bool neg, const DevFilter& f) {
+    if (mant == 0) return f.max_e >= 0.0 ? KEEP_YES : KEEP_NO;
+    if (neg) return KEEP_ASK_HOST;
+    const double m = (double)mant;
+    int d = 1;
+    while (d < 15 && m >= P10[d]) ++d;
+    if (d + e <= f.k_keep) return KEEP_YES;
+    if (d - 1 + e >= f.k_drop) return KEEP_NO;
+    if (e >= -22 && e <= 22) return (e < 0 ? m / P10[-e] : m * P10[e]) <= f.max_e ? KEEP_YES : KEEP_NO;
+    if (!f.e_band) return KEEP_ASK_HOST;
+    double x = m;
+    for (int r = e; r > 0; r -= 22) x *= P10[r < 22 ? r : 22];
+    for (int r = -e; r > 0; r -= 22) x /= P10[r < 22 ? r : 22];
+    return x <= f.e_lo ? KEEP_YES : (x >= f.e_hi ? KEEP_NO : KEEP_ASK_HOST);
+}
+
+// the four thresholds on one validated line -> its keep word, and the two counts (one atomic per wave and count)
+__device__ __forceinline__ void filter_row(const DevFilter& f, uint32_t i, double v_pid, double v_aln, double v_bs,
+                                           unsigned long long e_mant, int e_exp, bool e_neg) {
+    bool pass = true;
+    if ((f.mask & BLU_FILTER_MIN_PERC_IDENTITY) && !(v_pid >= f.min_pid)) pass = false;
+    if ((f.mask & BLU_FILTER_MIN_ALIGN_LENGTH) && !((long long)v_aln >= f.min_aln)) pass = false;   // (v_aln passed the 32-bit range check)
+    if ((f.mask & BLU_FILTER_MIN_BIT_SCORE) && !(v_bs >= f.min_bs)) pass = false;                   // as written: before the truncation
+    uint32_t k = pass ? KEEP_YES : KEEP_NO;
+    if (pass && (f.mask & BLU_FILTER_MAX_E_VALUE)) k = e_value_verdict(e_mant, e_exp, e_neg, f);
+    f.keep[i] = k;
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long kept = __ballot(k == KEEP_YES), ask = __ballot(k == KEEP_ASK_HOST);
+    if (k == KEEP_YES && (kept & ((1ull << lane) - 1ull)) == 0) atomicAdd(&f.counts[blockIdx.x % FCNT_SPREAD], (unsigned long long)__popcll(kept));
+    if (k == KEEP_ASK_HOST && (ask & ((1ull << lane) - 1ull)) == 0) atomicAdd(&f.counts[FCNT_SPREAD], (unsigned long long)__popcll(ask));
+}
 
 __device__ __forceinline__ unsigned long long hash_step(unsigned long long h, uint32_t c) { return (h ^ c) * 1099511628211ull; }
 __device__ __forceinline__ unsigned long long hash_finish(unsigned long long h, uint32_t len) {
@@ -356,9 +418,14 @@ struct RowOut {
 
 // One line, read from global memory a byte at a time through one state machine for all thirteen columns: the form that
 // takes any line length.  parse_rows uses it for the blocks whose 256 lines do not fit its LDS stage.
-__device__ __noinline__ void parse_row_general(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
-                                               const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
-                                               unsigned long long* __restrict__ n_unmatched) {
+// FILTER: also reads column 11 when the e-value threshold is on, leaves the line's keep word (filter_row) and does not count
+// unmatched rows (they are counted over the kept rows, after the compaction).
+// Built twice behind two functions of their own: parse_row_general (FILTER = false: the function of every unfiltered call,
+// its signature as it was) and parse_row_general_filtered.
+template <bool FILTER>
+__device__ __forceinline__ void parse_row_general_body(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
+                                                       const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
+                                                       unsigned long long* __restrict__ n_unmatched, const DevFilter* flt) {
     const uint64_t p = line_start[i];
     uint64_t e = line_start[i + 1] - 1;                 // the newline (or one past the end of a last line without one)
     if (e > p && text[e - 1] == '\r') --e;
@@ -370,6 +437,11 @@ __device__ __noinline__ void parse_row_general(const unsigned char* __restrict__
     num.reset();
     double v_tax = 0, v_pid = 0, v_aln = 0, v_bs = 0;
     uint32_t fb = 0;
+    bool want_e = false;
+    if constexpr (FILTER) want_e = (flt->mask & BLU_FILTER_MAX_E_VALUE) != 0;
+    unsigned long long e_mant = 0;
+    int e_exp = 0;
+    bool e_neg = false;
     auto end_field = [&](uint64_t fend) {
         const uint64_t len = fend - fstart;
         if (col == 0) { o.qh[i] = hash_finish(h, (uint32_t)len); o.qpos[i] = fstart | (len << 44); if (len >= (1u << 20)) fb |= FB_COLUMNS; }
@@ -380,6 +452,7 @@ __device__ __noinline__ void parse_row_general(const unsigned char* __restrict__
         else if (col == 3) { if (!num.value(&v_pid)) fb |= FB_NUMBER; }
         else if (col == 4) { if (!num.value(&v_aln) || num.seen_dot || num.seen_exp) fb |= FB_NUMBER; }
         else if (col == 12) { if (!num.value(&v_bs)) fb |= FB_NUMBER; }
+        else if (FILTER && col == 11 && want_e) { if (!num.plain()) fb |= FB_NUMBER; e_mant = num.mant; e_exp = num.exponent(); e_neg = num.neg; }
         ++col;
         fstart = fend + 1;
         h = 1469598103934665603ull;
@@ -396,7 +469,7 @@ __device__ __noinline__ void parse_row_general(const unsigned char* __restrict__
             const uint32_t c = (w[k >> 2] >> (8 * (k & 3))) & 0xFF;
             if (c == '\t') { end_field(q); continue; }
             if (col <= 1) { h = hash_step(h, c); if (c == '"') fb |= FB_QUOTE; }
-            else if (col <= 4 || col == 12) num.feed(c, q == fstart);
+            else if (col <= 4 || col == 12 || (FILTER && col == 11 && want_e)) num.feed(c, q == fstart);
         }
     }
     if (col < 13) end_field(e);                         // the last field ends with the line
@@ -407,8 +480,19 @@ __device__ __noinline__ void parse_row_general(const unsigned char* __restrict__
     if (!(bs_t >= -2147483648.0 && bs_t <= 2147483647.0) || !(v_aln >= -2147483648.0 && v_aln <= 2147483647.0) ||
         !(v_tax >= -9.2e18 && v_tax <= 9.2e18)) { atomicOr(flags, FB_RANGE); return; }
     const uint32_t row = taxid_lookup(taxmap, (long long)v_tax);   // left join (mod.rs:72-76)
-    if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull);
+    if constexpr (FILTER) filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
+    else if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull);
     o.tax[i] = row; o.pid[i] = v_pid; o.aln[i] = (int32_t)v_aln; o.bs[i] = (int32_t)bs_t;
+}
+__device__ __noinline__ void parse_row_general(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
+                                               const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
+                                               unsigned long long* __restrict__ n_unmatched) {
+    parse_row_general_body<false>(text, line_start, i, taxmap, o, flags, n_unmatched, nullptr);
+}
+__device__ __noinline__ void parse_row_general_filtered(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
+                                                        const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
+                                                        const DevFilter* __restrict__ flt) {
+    parse_row_general_body<true>(text, line_start, i, taxmap, o, flags, nullptr, flt);
 }
 
 // The parse kernel proper: a block takes 256 consecutive lines, whose text is one contiguous span of the file (17 KB for
@@ -422,9 +506,14 @@ __device__ __noinline__ void parse_row_general(const unsigned char* __restrict__
 constexpr uint32_t STAGE_BYTES = 32768;
 constexpr int PARSE_THREADS = 256;
 
-__global__ __launch_bounds__(PARSE_THREADS) void parse_rows(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t n_rows,
-                                                            DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
-                                                            unsigned long long* __restrict__ n_unmatched) {
+//
+// The body is built twice: parse_rows (FILTER = false: the kernel of every unfiltered call, flt unused) and
+// parse_rows_filtered (FILTER = true: column 11 read when its threshold is on, the predicate evaluated on the parsed values,
+// one keep word per line — filter_row; unmatched rows are counted after the compaction instead).
+template <bool FILTER>
+__device__ __forceinline__ void parse_rows_body(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t n_rows,
+                                                const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
+                                                unsigned long long* __restrict__ n_unmatched, const DevFilter* flt) {
     __shared__ uint4 stage16[STAGE_BYTES / 16];
     __shared__ uint16_t tab_at[13 * PARSE_THREADS];                  // [column][thread]: position of the tab that ends the column
     const uint32_t r0 = blockIdx.x * PARSE_THREADS, r1 = min(r0 + (uint32_t)PARSE_THREADS, n_rows), i = r0 + threadIdx.x;
@@ -433,7 +522,10 @@ __global__ __launch_bounds__(PARSE_THREADS) void parse_rows(const unsigned char*
     const uint64_t my_p = line_start[min(i, r1 - 1)], my_e = line_start[min(i, r1 - 1) + 1];
     const uint64_t s0 = ls0 & ~15ull;
     if (s1 - s0 > STAGE_BYTES) {                                     // uniform over the block
-        if (i < r1) parse_row_general(text, line_start, i, taxmap, o, flags, n_unmatched);
+        if (i < r1) {
+            if constexpr (FILTER) parse_row_general_filtered(text, line_start, i, taxmap, o, flags, flt);
+            else parse_row_general(text, line_start, i, taxmap, o, flags, n_unmatched);
+        }
         return;
     }
     {
@@ -491,15 +583,92 @@ __global__ __launch_bounds__(PARSE_THREADS) void parse_rows(const unsigned char*
     number(t2 + 1, t3, false, &v_pid);
     number(t3 + 1, tab(4), true, &v_aln);
     number(tab(11) + 1, n_tabs == 13 ? tab(12) : e, false, &v_bs);
+    unsigned long long e_mant = 0;
+    int e_exp = 0;
+    bool e_neg = false;
+    if constexpr (FILTER) {
+        if (flt->mask & BLU_FILTER_MAX_E_VALUE) {                   // column 11, read only under its threshold
+            NumState num;
+            num.reset();
+            const uint32_t s = tab(10) + 1, t = tab(11);
+            for (uint32_t q = s; q < t; ++q) num.feed(sb[q], q == s);
+            if (!num.plain()) fb |= FB_NUMBER;
+            e_mant = num.mant; e_exp = num.exponent(); e_neg = num.neg;
+        }
+    }
     if (fb) { atomicOr(flags, fb); return; }
     const double bs_t = trunc(v_bs);                                // mod.rs:184 AnyValue::Float64 -> try_extract::<i64> (truncation)
     if (!(bs_t >= -2147483648.0 && bs_t <= 2147483647.0) || !(v_aln >= -2147483648.0 && v_aln <= 2147483647.0) ||
         !(v_tax >= -9.2e18 && v_tax <= 9.2e18)) { atomicOr(flags, FB_RANGE); return; }
     const uint32_t row = taxid_lookup(taxmap, (long long)v_tax);   // left join (mod.rs:72-76)
-    if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull);
+    if constexpr (FILTER) filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
+    else if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull);
     o.qh[i] = qh; o.qpos[i] = (s0 + p) | ((unsigned long long)(t0 - p) << 44);
     o.ah[i] = ah; o.apos[i] = (s0 + t0 + 1) | ((unsigned long long)(t1 - t0 - 1) << 44);
     o.tax[i] = row; o.pid[i] = v_pid; o.aln[i] = (int32_t)v_aln; o.bs[i] = (int32_t)bs_t;
+}
+
+__global__ __launch_bounds__(PARSE_THREADS) void parse_rows(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t n_rows,
+                                                            DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
+                                                            unsigned long long* __restrict__ n_unmatched) {
+    parse_rows_body<false>(text, line_start, n_rows, taxmap, o, flags, n_unmatched, nullptr);
+}
+__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_filtered(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
+                                                                     uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
+                                                                     const DevFilter* __restrict__ flt) {   // (in device memory: read with scalar loads)
+    parse_rows_body<true>(text, line_start, n_rows, taxmap, o, flags, nullptr, flt);
+}
+
+// ---- 2b. hit filter: the e-values left to the host, and the stable compaction of the parsed rows ---------------------------
+// rows whose keep word is KEEP_ASK_HOST, in any order, each with the place of its column 11 (field offset | length << 44)
+__global__ void list_undecided(const uint32_t* __restrict__ keep, uint32_t n, const unsigned char* __restrict__ text,
+                               const uint64_t* __restrict__ line_start, uint32_t cap, uint32_t* __restrict__ rows,
+                               unsigned long long* __restrict__ pos, uint32_t* __restrict__ cursor) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || keep[i] != KEEP_ASK_HOST) return;
+    const uint64_t p = line_start[i];
+    uint64_t e = line_start[i + 1] - 1;
+    if (e > p && text[e - 1] == '\r') --e;
+    uint64_t q = p;
+    for (int tabs = 0; q < e && tabs < 11; ++q) if (text[q] == '\t') ++tabs;
+    const uint64_t s = q;
+    while (q < e && text[q] != '\t') ++q;
+    const uint32_t at = atomicAdd(cursor, 1u);
+    if (at < cap) { rows[at] = i; pos[at] = s | ((q - s) << 44); }
+}
+__global__ void apply_decisions(const uint32_t* __restrict__ rows, const uint32_t* __restrict__ decision, uint32_t n, uint32_t n_rows,
+                                uint32_t* __restrict__ keep) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n && rows[k] < n_rows) keep[rows[k]] = decision[k] ? KEEP_YES : KEEP_NO;
+}
+// One column of the parsed rows: element i goes to out[pos[i]] when keep[i] is set, pos = the exclusive prefix sum of the keep
+// words — so file order survives and nothing is placed by an atomic.  A thread takes 16 bytes of the column (two 8-byte or
+// four 4-byte elements) and their keep words in one load each; the kept elements of neighbouring lanes land next to each
+// other.  n_out = the kept count: no store goes beyond it whatever the keep words hold.
+constexpr int COMPACT_THREADS = 256;
+template <class T>
+__global__ __launch_bounds__(COMPACT_THREADS) void compact_column(const T* __restrict__ in, const uint32_t* __restrict__ keep,
+                                                                  const uint32_t* __restrict__ pos, uint32_t n, uint32_t n_out, T* __restrict__ out) {
+    constexpr uint32_t V = 16 / sizeof(T);
+    struct alignas(16) Elems { T v[V]; };
+    struct alignas(4 * V) Keeps { uint32_t k[V]; };
+    const uint64_t base = ((uint64_t)blockIdx.x * COMPACT_THREADS + threadIdx.x) * V;
+    if (base >= n) return;
+    uint32_t at = pos[base];
+    if (base + V <= n) {
+        const Elems x = *reinterpret_cast<const Elems*>(in + base);
+        const Keeps k = *reinterpret_cast<const Keeps*>(keep + base);
+#pragma unroll
+        for (uint32_t j = 0; j < V; ++j) if (k.k[j] == KEEP_YES && at < n_out) out[at++] = x.v[j];
+    } else {
+        for (uint64_t j = base; j < n; ++j) if (keep[j] == KEEP_YES && at < n_out) out[at++] = in[j];
+    }
+}
+__global__ __launch_bounds__(1024) void count_unmatched(const uint32_t* __restrict__ tax, uint32_t n, unsigned long long* __restrict__ count) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    __shared__ uint32_t wave_sums[1024 / 64];
+    const uint32_t total = block_sum<1024>(i < n && tax[i] == BLU_UNMATCHED_TAXID, wave_sums);
+    if (threadIdx.x == 0 && total) atomicAdd(count, (unsigned long long)total);
 }
 
 // ---- 3. dictionaries ---------------------------------------------------------------------------------------------
@@ -875,9 +1044,30 @@ void warm_up_device(int device) {
 
 namespace {
 
+// the thresholds as the kernels read them; the e-value's decimal magnitude tests and bracket (e_value_verdict) from max_e
+DevFilter device_filter(const blu_hit_filter& f) {
+    DevFilter d{};
+    d.mask = f.mask & 15u;
+    d.min_pid = f.min_perc_identity; d.min_bs = f.min_bit_score; d.max_e = f.max_e_value; d.min_aln = f.min_align_length;
+    const double E = f.max_e_value;
+    constexpr int NEVER = -(1 << 30), ALWAYS = 1 << 30;
+    if (!(E >= 0.0)) { d.k_keep = NEVER; d.k_drop = NEVER; }                  // negative or NaN: no value above zero passes
+    else if (E == 0.0) { d.k_keep = -325; d.k_drop = -322; }                  // below 10^-325 strtod gives 0; from 10^-322 it does not
+    else if (std::isinf(E)) { d.k_keep = ALWAYS; d.k_drop = ALWAYS; }
+    else {
+        // t = floor(log10 E) give or take one (the library's rounding at a power of ten): value < 10^(t - 2) <= E / 10 is kept,
+        // value >= 10^(t + 3) >= 10 E is dropped
+        const int t = (int)std::floor(std::log10(E));
+        d.k_keep = t - 2; d.k_drop = t + 3;
+        d.e_band = E >= 1e-280 && E <= 1e280;
+        d.e_lo = E * (1.0 - 0x1p-46); d.e_hi = E * (1.0 + 0x1p-46);
+    }
+    return d;
+}
+
 // load_hits_gpu's work on the device, in the arena the caller frees; any failure returns at once
 int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, DeviceArena& mem,
-                     IngestTrace& lap) {
+                     IngestTrace& lap, const blu_hit_filter* flt) {
     HipPolicy& pol = mem.pol;
     auto fallback = [&](const char* reason) { *pol.why = reason; return BLU_INGEST_FALLBACK; };
     unsigned char* d_text = nullptr;
@@ -944,8 +1134,10 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
     lap("upload text");
     HIP_CHECK(pol, mem.alloc(&d_tile, (n_tiles + 1) * 4, "line index"));
     HIP_CHECK(pol, mem.alloc(&d_tile_base, (n_tiles + 1) * 4, "line index"));
-    HIP_CHECK(pol, mem.alloc(&d_flags, 64, "flags"));
-    HIP_CHECK(pol, hipMemset(d_flags, 0, 64));
+    // {flags, -, -, -, counter, -, -, -, big counters}; under a hit filter the kept / undecided counts follow
+    const size_t flag_bytes = flt ? 64 + (FCNT_SPREAD + 1) * 8 : 64;
+    HIP_CHECK(pol, mem.alloc(&d_flags, flag_bytes, "flags"));
+    HIP_CHECK(pol, hipMemset(d_flags, 0, flag_bytes));
     d_counter = d_flags + 4;                                         // {flags, -, -, -, counter, -, big counters at +8}
     d_big = reinterpret_cast<unsigned long long*>(d_flags + 8);      // [0] unmatched rows, [1] run heads
     HIP_CHECK(pol, need_tmp(scan_tmp_bytes<uint32_t>((size_t)n_tiles + 1)));
@@ -968,12 +1160,101 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
     HIP_CHECK(pol, mem.alloc(&d_qpos, (size_t)n_rows * 8, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_apos, (size_t)n_rows * 8, "parsed rows"));
     HIP_CHECK(pol, mem.alloc(&d_tax, (size_t)n_rows * 4, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_pid, (size_t)n_rows * 8, "parsed rows"));
     HIP_CHECK(pol, mem.alloc(&d_aln, (size_t)n_rows * 4, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_bs, (size_t)n_rows * 4, "parsed rows"));
-    {
+    if (!flt) {
         RowOut o{d_qh, d_ah, d_qpos, d_apos, d_tax, d_pid, d_aln, d_bs};
         DevTaxidMap tm{d_taxmap, row_of.tab.size() - 1};
         hipLaunchKernelGGL(parse_rows, grid(n_rows, PARSE_THREADS), dim3(PARSE_THREADS), 0, 0, d_text, d_line, n_rows, tm, o, d_flags, d_big);
         HIP_CHECK(pol, hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
         if (h_flags) return fallback(fallback_text(h_flags));
+    } else {
+        // ---- hit filter: the filtered parse leaves a keep word per line; the kept and undecided counts come
+        // back with the flags; the rows are compacted in file order before anything else sees them
+        uint32_t *d_keep = nullptr, *d_kpos = nullptr;
+        DevFilter* d_filter = nullptr;
+        HIP_CHECK(pol, mem.alloc(&d_keep, (size_t)n_rows * 4, "keep words"));
+        HIP_CHECK(pol, mem.alloc(&d_filter, sizeof(DevFilter), "hit filter"));
+        unsigned long long* const d_fcnt = reinterpret_cast<unsigned long long*>(d_flags + 16);
+        DevFilter hf = device_filter(*flt);
+        hf.keep = d_keep; hf.counts = d_fcnt;
+        HIP_CHECK(pol, hipMemcpy(d_filter, &hf, sizeof hf, hipMemcpyHostToDevice));
+        RowOut o{d_qh, d_ah, d_qpos, d_apos, d_tax, d_pid, d_aln, d_bs};
+        DevTaxidMap tm{d_taxmap, row_of.tab.size() - 1};
+        hipLaunchKernelGGL(parse_rows_filtered, grid(n_rows, PARSE_THREADS), dim3(PARSE_THREADS), 0, 0, d_text, d_line, n_rows, tm, o, d_flags,
+                           (const DevFilter*)d_filter);
+        unsigned long long back[8 + FCNT_SPREAD + 1];
+        HIP_CHECK(pol, hipMemcpy(back, d_flags, sizeof back, hipMemcpyDeviceToHost));
+        h_flags = (uint32_t)back[0];
+        if (h_flags) return fallback(fallback_text(h_flags));
+        uint64_t n_kept = 0;
+        for (uint32_t k = 0; k < FCNT_SPREAD; ++k) n_kept += back[8 + k];
+        const uint64_t n_ask = back[8 + FCNT_SPREAD];
+        lap("parse (filtered)");
+        if (n_ask) {
+            // e-values the device left open (as a rule: fields spelled like the threshold): the host decides them from the
+            // file's bytes with the host parser's own number reader and sends the decisions back
+            if (n_kept + n_ask > n_rows) return fallback("inconsistent hit-filter counts");
+            const uint32_t n_u = (uint32_t)n_ask;
+            uint32_t *d_urow = nullptr, *d_udec = nullptr;
+            unsigned long long* d_upos = nullptr;
+            HIP_CHECK(pol, mem.alloc(&d_urow, (size_t)n_u * 4, "undecided e-values")); HIP_CHECK(pol, mem.alloc(&d_upos, (size_t)n_u * 8, "undecided e-values"));
+            HIP_CHECK(pol, mem.alloc(&d_udec, (size_t)n_u * 4, "undecided e-values"));
+            HIP_CHECK(pol, hipMemset(d_urow, 0xFF, (size_t)n_u * 4));
+            HIP_CHECK(pol, hipMemset(d_upos, 0, (size_t)n_u * 8));
+            HIP_CHECK(pol, hipMemset(d_counter, 0, 4));
+            hipLaunchKernelGGL(list_undecided, grid(n_rows), dim3(256), 0, 0, (const uint32_t*)d_keep, n_rows, d_text, d_line, n_u, d_urow, d_upos, d_counter);
+            std::vector<char> e_bytes;
+            std::vector<unsigned long long> e_off;
+            if (const int rc = download_strings(d_upos, n_u, e_bytes, e_off); rc != BLU_OK) return rc;
+            std::vector<uint32_t> dec(n_u);
+            for (uint32_t k = 0; k < n_u; ++k) {
+                double v = 0;
+                if (!parse_f64_field(e_bytes.data() + e_off[k], (size_t)(e_off[k + 1] - e_off[k]), &v)) return fallback("an e-value the host parser reads differently");
+                dec[k] = v <= flt->max_e_value ? 1u : 0u;
+                n_kept += dec[k];
+            }
+            HIP_CHECK(pol, hipMemcpy(d_udec, dec.data(), (size_t)n_u * 4, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(apply_decisions, grid(n_u), dim3(256), 0, 0, (const uint32_t*)d_urow, (const uint32_t*)d_udec, n_u, n_rows, d_keep);
+            mem.free(d_urow); mem.free(d_upos); mem.free(d_udec);
+            lap("  filter: e-values decided on the host");
+        }
+        if (n_kept > n_rows) return fallback("inconsistent hit-filter counts");
+        const uint64_t n_lines = n_rows;
+        if (n_kept == 0) return fallback("no rows kept by the hit filter");   // (the host parser returns the empty table)
+        if (n_kept < n_rows) {
+            // stable compaction, one column after another through ONE spare buffer: a column is scattered into the spare, the
+            // spare becomes the column and the column's old buffer the next spare (8-byte columns first, so that every spare
+            // is large enough).  Peak: the eight arrays (52 B / line) + keep words and their scan (8 B / line) + 8 B / kept line.
+            const uint32_t n_out = (uint32_t)n_kept;
+            HIP_CHECK(pol, mem.alloc(&d_kpos, (size_t)n_rows * 4, "keep positions"));
+            HIP_CHECK(pol, need_tmp(scan_tmp_bytes<uint32_t>((size_t)n_rows)));
+            HIP_CHECK(pol, exclusive_scan_dev<uint32_t>(d_keep, d_kpos, (size_t)n_rows, d_tmp));
+            void* spare = nullptr;
+            HIP_CHECK(pol, mem.alloc(&spare, (size_t)n_out * 8, "compaction spare"));
+            auto move8 = [&](auto*& col) {
+                using T = std::remove_reference_t<decltype(*col)>;
+                static_assert(sizeof(T) == 8, "8-byte column");
+                hipLaunchKernelGGL((compact_column<T>), grid(n_rows, COMPACT_THREADS * 2), dim3(COMPACT_THREADS), 0, 0, (const T*)col, (const uint32_t*)d_keep,
+                                   (const uint32_t*)d_kpos, n_rows, n_out, (T*)spare);
+                void* old = col; col = (T*)spare; spare = old;
+            };
+            auto move4 = [&](auto*& col) {
+                using T = std::remove_reference_t<decltype(*col)>;
+                static_assert(sizeof(T) == 4, "4-byte column");
+                hipLaunchKernelGGL((compact_column<T>), grid(n_rows, COMPACT_THREADS * 4), dim3(COMPACT_THREADS), 0, 0, (const T*)col, (const uint32_t*)d_keep,
+                                   (const uint32_t*)d_kpos, n_rows, n_out, (T*)spare);
+                void* old = col; col = (T*)spare; spare = old;
+            };
+            move8(d_qh); move8(d_ah); move8(d_qpos); move8(d_apos); move8(d_pid);
+            move4(d_tax); move4(d_aln); move4(d_bs);
+            HIP_CHECK(pol, hipGetLastError());
+            mem.free(spare); mem.free(d_kpos);
+            n_rows = n_out;
+            lap("  filter: compaction");
+        }
+        mem.free(d_keep); mem.free(d_filter);
+        mem.free(d_line); d_line = nullptr;
+        hipLaunchKernelGGL(count_unmatched, grid(n_rows, 1024), dim3(1024), 0, 0, (const uint32_t*)d_tax, n_rows, d_big);
+        ht.n_lines = n_lines; ht.n_kept = n_kept;
     }
     lap("parse");
 
@@ -1211,7 +1492,9 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
 
 }  // namespace
 
-int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, std::string* why) {
+int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, std::string* why,
+                  const blu_hit_filter* flt) {
+    if (flt && !(flt->mask & 15u)) flt = nullptr;
     IngestTrace lap;
     std::string why_unread;
     if (!why) why = &why_unread;
@@ -1229,7 +1512,7 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
         }
         mem.keep = (double)size * 4.0 + (4ull << 30) < (double)free_b;
     }
-    const int rc = ingest_on_device(fd, size, row_of, device, host_columns, ht, mem, lap);
+    const int rc = ingest_on_device(fd, size, row_of, device, host_columns, ht, mem, lap, flt);
     if (rc != BLU_OK) ht.clear();
     lap("hand-over");
     // with room on the card (mem.keep) the work buffers — the text, the hashes, the dictionaries: 10 GB for a 2 M-query table —

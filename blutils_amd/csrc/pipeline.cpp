@@ -540,6 +540,7 @@ struct Chunk {
     std::vector<uint64_t> at;                // local query -> next row slot in the grouped table
     std::vector<std::string_view> acc_sorted;
     uint64_t unmatched = 0, first_line = 0, n_lines = 0;
+    uint64_t n_data_lines = 0, n_kept = 0;   // under a hit filter: non-empty lines, lines kept
     int rc = BLU_OK;
     std::string err;
     std::string_view clean(std::string_view v) {   // mod.rs:169-172 `.replace("\"", "")`
@@ -549,7 +550,17 @@ struct Chunk {
     }
 };
 
-void parse_chunk(Chunk& c, const Db& db, const char* path) {
+// The hit filter's predicate (include/blu_pipeline.h: blu_hit_filter) on the values parse_f64 / parse_i64 gave: plain IEEE
+// comparisons, so a NaN on either side fails.  This is the definition the GPU parser's decisions are held to.
+inline bool filter_keeps(const blu_hit_filter& f, double pid, int64_t aln, double e_value, double bs) {
+    if ((f.mask & BLU_FILTER_MIN_PERC_IDENTITY) && !(pid >= f.min_perc_identity)) return false;
+    if ((f.mask & BLU_FILTER_MIN_ALIGN_LENGTH) && !(aln >= f.min_align_length)) return false;
+    if ((f.mask & BLU_FILTER_MAX_E_VALUE) && !(e_value <= f.max_e_value)) return false;
+    if ((f.mask & BLU_FILTER_MIN_BIT_SCORE) && !(bs >= f.min_bit_score)) return false;   // as written: before the truncation
+    return true;
+}
+
+void parse_chunk(Chunk& c, const Db& db, const char* path, const blu_hit_filter* flt = nullptr) {
     const char* p = c.begin;
     uint64_t line_no = 0;
     c.rows.reserve((size_t)(c.end - c.begin) / 96 + 16);
@@ -591,6 +602,17 @@ void parse_chunk(Chunk& c, const Db& db, const char* path) {
                 snprintf(msg, sizeof msg, "line %llu(+%llu) of %s: bit_score / align_length outside the 32-bit range of the engine columns",
                          (unsigned long long)line_no, (unsigned long long)c.first_line, path);
                 c.rc = BLU_ERR_PARSE; c.err = msg; return;
+            }
+            if (flt) {                                        // (validated like every line; dropped before it reaches a dictionary)
+                double ev = 0;
+                if ((flt->mask & BLU_FILTER_MAX_E_VALUE) && !parse_f64(col[11], &ev)) {
+                    snprintf(msg, sizeof msg, "line %llu(+%llu) of %s: numeric column does not parse (e_value)", (unsigned long long)line_no,
+                             (unsigned long long)c.first_line, path);
+                    c.rc = BLU_ERR_PARSE; c.err = msg; return;
+                }
+                ++c.n_data_lines;
+                if (!filter_keeps(*flt, pid, aln, ev, bs)) { p = nl ? nl + 1 : c.end; continue; }
+                ++c.n_kept;
             }
             RawRow r;
             // rows of one query usually sit next to each other: the previous row's ids are tried before the dictionaries
@@ -638,8 +660,9 @@ void parallel_for(unsigned n, unsigned nthreads, F&& f) {
 thread_local double g_t_body_end = 0;   // stage trace: when build_document's last statement ran (what follows is its tear-down)
 thread_local int g_last_ingest_path = 0;   // 0 = CPU parser, 1 = GPU parser (blu_last_ingest_path)
 
-int load_hits(const char* path, const Db& db, HitTable& ht, int device = -1, bool host_columns = true) {
+int load_hits(const char* path, const Db& db, HitTable& ht, int device = -1, bool host_columns = true, const blu_hit_filter* flt = nullptr) {
     g_last_ingest_path = 0;
+    if (flt && !(flt->mask & 15u)) flt = nullptr;   // no threshold given: today's path
     // GPU parser first (ingest_gpu.hip) when a device is given: same columns bit for bit; files it does not handle
     // (quotes, empty lines, unusual numbers), small files and BLU_INGEST=cpu take the CPU path below.  The GPU path
     // reads the file through its descriptor and never maps it.
@@ -653,7 +676,7 @@ int load_hits(const char* path, const Db& db, HitTable& ht, int device = -1, boo
         const bool want_gpu = device >= 0 && db.dup_rows.empty() && !(mode && strcmp(mode, "cpu") == 0) && (fsize >= (1u << 20) || (mode && strcmp(mode, "gpu") == 0));
         int rc = BLU_INGEST_FALLBACK;
         std::string why;
-        if (want_gpu) rc = load_hits_gpu(fd, fsize, db.row_of, device, host_columns, ht, &why);
+        if (want_gpu) rc = load_hits_gpu(fd, fsize, db.row_of, device, host_columns, ht, &why, flt);
         ::close(fd);
         if (want_gpu) {
             if (rc == BLU_OK) { g_last_ingest_path = 1; return BLU_OK; }
@@ -686,7 +709,7 @@ int load_hits(const char* path, const Db& db, HitTable& ht, int device = -1, boo
     const bool trace = getenv("BLU_INGEST_TRACE") != nullptr;
     double tp = now_s();
     auto lap = [&](const char* what) { if (trace) { const double t = now_s(); fprintf(stderr, "[ingest] %-22s %.3f s\n", what, t - tp); tp = t; } };
-    parallel_for(nthreads, nthreads, [&](unsigned t) { parse_chunk(chunks[t], db, path); });
+    parallel_for(nthreads, nthreads, [&](unsigned t) { parse_chunk(chunks[t], db, path, flt); });
     lap("parse (parallel)");
     uint64_t lines_before = 0;
     size_t nh = 0;
@@ -695,6 +718,7 @@ int load_hits(const char* path, const Db& db, HitTable& ht, int device = -1, boo
         lines_before += c.n_lines;
         nh += c.rows.size();
         ht.unmatched += c.unmatched;
+        ht.n_lines += c.n_data_lines; ht.n_kept += c.n_kept;
     }
     if (nh >= 0xFFFFFFFFull) { set_error("more than 2^32 - 2 hit rows in %s", path); return BLU_ERR_INVALID_ARG; }
     // queries: the chunks' distinct names in file order -> global ids, and each chunk's first slot inside every segment
@@ -1397,8 +1421,9 @@ int build_sample_table(const Db& db, const HitTable& ht, const blu_taxonomy* tax
 int build_document(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
                    const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
                    const char* config_text, const char* out_path, Document* document, blu_pipeline_stats* stats,
-                   const blu_tables_params* tables = nullptr) {
+                   const blu_tables_params* tables = nullptr, const blu_hit_filter* flt = nullptr, blu_hit_filter_stats* fst = nullptr) {
     if (!blast_output_file || !taxonomies_file || !params || !document) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    if (flt && (flt->mask & ~15u)) { set_error("hit filter: unknown bits in the mask"); return BLU_ERR_INVALID_ARG; }
     if (tables && ((!tables->report_path && !tables->sample_table_path) ||
                    (tables->weight != BLU_REPORT_WEIGHT_ONE && tables->weight != BLU_REPORT_WEIGHT_SIZE))) {
         set_error("report: a path and weight BLU_REPORT_WEIGHT_ONE or BLU_REPORT_WEIGHT_SIZE are needed");
@@ -1447,8 +1472,9 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     t0 = now_s();
     auto ht_owner = std::make_unique<HitTable>();
     HitTable& ht = *ht_owner;
-    rc = load_hits(blast_output_file, db, ht, params->device, /*host_columns=*/false);   // mod.rs:54, 72-82
+    rc = load_hits(blast_output_file, db, ht, params->device, /*host_columns=*/false, flt);   // mod.rs:54, 72-82
     if (rc != BLU_OK) return rc;
+    if (fst) { const bool on = flt && (flt->mask & 15u); fst->n_lines = on ? ht.n_lines : ht.n_hits; fst->n_kept = on ? ht.n_kept : ht.n_hits; }
     st.t_load_hits_s = now_s() - t0;
     tr.lap("load hits");
     st.n_hits = ht.n_hits; st.n_queries = ht.n_queries; st.n_taxids = db.taxid.size(); st.n_unmatched_rows = ht.unmatched;
@@ -1746,13 +1772,14 @@ int put_tables(const Document& d, const blu_tables_params* tables) {
 
 int consensus_to_text(const char* blast_output_file, const char* const* headers, uint64_t n_headers, const char* taxonomies_file,
                       const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const blu_tables_params* tables,
-                      char** out_text, size_t* out_len, blu_pipeline_stats* stats) {
+                      char** out_text, size_t* out_len, blu_pipeline_stats* stats, const blu_hit_filter* flt = nullptr,
+                      blu_hit_filter_stats* fst = nullptr) {
     if (!out_text) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     *out_text = nullptr;
     if (out_len) *out_len = 0;
     Document d;
     int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats, tables); }
+    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats, tables, flt, fst); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }   // (no exception crosses the C ABI)
     if (rc != BLU_OK) return rc;
     if ((rc = put_tables(d, tables)) != BLU_OK) return rc;
@@ -1772,11 +1799,12 @@ int consensus_to_text(const char* blast_output_file, const char* const* headers,
 // (the report and table files, when asked for, are written once the document is out)
 int consensus_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers, const char* taxonomies_file,
                       const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const char* out_path,
-                      const blu_tables_params* tables, blu_pipeline_stats* stats) {
+                      const blu_tables_params* tables, blu_pipeline_stats* stats, const blu_hit_filter* flt = nullptr,
+                      blu_hit_filter_stats* fst = nullptr) {
     if (!out_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     Document d;
     int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats, tables); }
+    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats, tables, flt, fst); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
     if (rc != BLU_OK) return rc;
     if (getenv("BLU_INGEST_TRACE")) fprintf(stderr, "[pipeline] %-26s %.3f s\n", "tear-down (tables, strings)", now_s() - g_t_body_end);
@@ -1805,6 +1833,8 @@ int consensus_to_file(const char* blast_output_file, const char* const* headers,
 
 
 }  // namespace
+
+bool blu::parse_f64_field(const char* p, size_t n, double* out) { return parse_f64(std::string_view(p, n), out); }
 
 extern "C" {
 
@@ -1843,6 +1873,20 @@ int blu_build_consensus_identities_tables(const char* blast_output_file, const c
                                  stats);
     return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, tables, out_text,
                              out_len, stats);
+}
+
+int blu_build_consensus_identities_filtered(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                            const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
+                                            const char* config_text, const char* out_path, const blu_tables_params* tables,
+                                            const blu_hit_filter* filter, char** out_text, size_t* out_len,
+                                            blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats) {
+    if (tables && !tables->report_path && !tables->sample_table_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    if (filter_stats) *filter_stats = blu_hit_filter_stats{0, 0};
+    if (out_path)
+        return consensus_to_file(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, tables,
+                                 stats, filter, filter_stats);
+    return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, tables, out_text,
+                             out_len, stats, filter, filter_stats);
 }
 
 int blu_build_consensus_identities_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
@@ -1893,17 +1937,25 @@ int blu_ingest_only_on(const char* blast_output_file, const char* taxonomies_fil
 
 int blu_ingest_columns_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
                           blu_ingest_columns* out) {
+    return blu_ingest_columns_filtered_on(blast_output_file, taxonomies_file, use_taxid, device, nullptr, out, nullptr);
+}
+
+int blu_ingest_columns_filtered_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                                   const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats) {
     if (!blast_output_file || !taxonomies_file || !out) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    if (filter && (filter->mask & ~15u)) { set_error("hit filter: unknown bits in the mask"); return BLU_ERR_INVALID_ARG; }
+    if (filter_stats) *filter_stats = blu_hit_filter_stats{0, 0};
     memset(out, 0, sizeof *out);
     Db db;
     int rc = load_db(taxonomies_file, use_taxid != 0, db);
     if (rc != BLU_OK) return rc;
     HitTable ht;
-    rc = load_hits(blast_output_file, db, ht, device);
+    rc = load_hits(blast_output_file, db, ht, device, true, filter);
     if (rc != BLU_OK) return rc;
     ht.wait_strings();
     if (!ht.strings_ok) { set_error("out of memory while building the query / accession strings"); return BLU_ERR_ALLOC; }
     const size_t nh = ht.bitscore.size(), nq = ht.query_names.size();
+    if (filter_stats) { const bool on = filter && (filter->mask & 15u); filter_stats->n_lines = on ? ht.n_lines : nh; filter_stats->n_kept = on ? ht.n_kept : nh; }
     auto dup = [](const void* src, size_t bytes) -> void* { void* p = malloc(bytes ? bytes : 1); if (p && bytes) memcpy(p, src, bytes); return p; };
     auto pack = [](const std::vector<std::string>& v, uint64_t* bytes) -> char* {
         size_t n = 0;

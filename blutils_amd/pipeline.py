@@ -8,8 +8,9 @@ Same argument names and meaning; the consensus itself runs on the GPU (no CPU fa
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import json
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Union
 
 from . import _native as N
 
@@ -26,6 +27,57 @@ class PipelineStats(C.Structure):
     _fields_ = [("n_hits", C.c_uint64), ("n_queries", C.c_uint64), ("n_taxids", C.c_uint64),
                 ("n_unmatched_rows", C.c_uint64), ("t_load_db_s", C.c_double), ("t_load_hits_s", C.c_double),
                 ("t_engine_s", C.c_double), ("t_render_s", C.c_double)]
+
+
+@dataclasses.dataclass(frozen=True)
+class HitFilter:
+    """Thresholds on the table's lines (include/blu_pipeline.h: blu_hit_filter; not in the reference).  A line
+    is kept when every threshold that is not None holds; the run then gives what it gives on a copy of the table without
+    the other lines.  min_bit_score compares the score as written, before its truncation."""
+    min_perc_identity: Optional[float] = None
+    min_align_length: Optional[int] = None
+    max_e_value: Optional[float] = None
+    min_bit_score: Optional[float] = None
+
+    def active(self) -> bool:
+        return any(v is not None for v in dataclasses.astuple(self))
+
+
+class HitFilterC(C.Structure):
+    _fields_ = [("min_perc_identity", C.c_double), ("min_align_length", C.c_int64), ("max_e_value", C.c_double),
+                ("min_bit_score", C.c_double), ("mask", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class HitFilterStats(C.Structure):
+    _fields_ = [("n_lines", C.c_uint64), ("n_kept", C.c_uint64)]
+
+
+FILTER_BITS = {"min_perc_identity": 1, "min_align_length": 2, "max_e_value": 4, "min_bit_score": 8}
+
+
+def _hit_filter(hit_filter: Union[None, dict, HitFilter]) -> Optional[HitFilterC]:
+    """None -> None (today's calls); a dict or HitFilter -> the C struct (an empty one has an empty mask)."""
+    if hit_filter is None:
+        return None
+    if isinstance(hit_filter, HitFilter):
+        hit_filter = dataclasses.asdict(hit_filter)
+    unknown = set(hit_filter) - set(FILTER_BITS)
+    if unknown:
+        raise ValueError(f"hit_filter: unknown keys {sorted(unknown)}")
+    f = HitFilterC()
+    for key, bit in FILTER_BITS.items():
+        v = hit_filter.get(key)
+        if v is None:
+            continue
+        if key == "min_align_length":
+            if int(v) != v or not -(1 << 63) <= int(v) < (1 << 63):
+                raise ValueError(f"hit_filter: min_align_length must be an integer, got {v!r}")
+            v = int(v)
+        else:
+            v = float(v)
+        setattr(f, key, v)
+        f.mask |= bit
+    return f
 
 
 def _bind():
@@ -59,17 +111,30 @@ class IngestColumns(C.Structure):
                 ("query_names_bytes", C.c_uint64), ("accessions", C.c_void_p), ("accessions_bytes", C.c_uint64)]
 
 
-def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = False, device: int = -1) -> dict:
-    """The SoA columns of the ingest (include/blu_pipeline.h: blu_ingest_columns_on) as numpy arrays + the two string tables."""
+def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = False, device: int = -1,
+                   hit_filter: Union[None, dict, HitFilter] = None) -> dict:
+    """The SoA columns of the ingest (include/blu_pipeline.h: blu_ingest_columns_on) as numpy arrays + the two string tables.
+    hit_filter (a dict or HitFilter): the columns of the lines it keeps (blu_ingest_columns_filtered_on), plus `n_lines` and
+    `n_kept`."""
     import numpy as np
     L = _bind()
     L.blu_ingest_columns_on.restype = C.c_int
     L.blu_ingest_columns_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(IngestColumns)]
     L.blu_ingest_columns_free.argtypes = [C.POINTER(IngestColumns)]
     c = IngestColumns()
-    rc = L.blu_ingest_columns_on(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device, C.byref(c))
-    if rc != N.BLU_OK:
-        raise N.BluError(rc, "blu_ingest_columns_on")
+    flt, fst = _hit_filter(hit_filter), HitFilterStats()
+    if flt is None:
+        rc = L.blu_ingest_columns_on(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device, C.byref(c))
+        if rc != N.BLU_OK:
+            raise N.BluError(rc, "blu_ingest_columns_on")
+    else:
+        L.blu_ingest_columns_filtered_on.restype = C.c_int
+        L.blu_ingest_columns_filtered_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(HitFilterC),
+                                                     C.POINTER(IngestColumns), C.POINTER(HitFilterStats)]
+        rc = L.blu_ingest_columns_filtered_on(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
+                                              C.byref(flt), C.byref(c), C.byref(fst))
+        if rc != N.BLU_OK:
+            raise N.BluError(rc, "blu_ingest_columns_filtered_on")
     try:
         nh, nq = int(c.n_hits), int(c.n_queries)
         arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(max(n, 1),))[:n].astype(dt, copy=True)
@@ -79,6 +144,8 @@ def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = Fa
         split = lambda p, n: C.string_at(p, n).split(b"\0")[:-1] if n else []
         out["query_names"] = split(c.query_names, int(c.query_names_bytes))
         out["accessions"] = split(c.accessions, int(c.accessions_bytes))
+        if flt is not None:
+            out["n_lines"], out["n_kept"] = int(fst.n_lines), int(fst.n_kept)
         return out
     finally:
         L.blu_ingest_columns_free(C.byref(c))
@@ -124,13 +191,15 @@ def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: s
                                strategy: str = "relaxed", use_taxid: Optional[bool] = None,
                                custom_taxon_values: Optional[dict] = None, headers: Optional[Sequence[str]] = None,
                                out_format: str = "json", device: int = 0, lenient: bool = False, parse: bool = True,
-                               config=None, out_path: Optional[str] = None):
+                               config=None, out_path: Optional[str] = None, hit_filter: Union[None, dict, HitFilter] = None):
     """Returns (results, stats).  With out_path the document is written there by the library (no copy through Python) and
     (None, stats) is returned.  results: the parsed `results` list (json) / list of records (jsonl), sorted by
     query, or the raw text when parse=False.  config: Some(BlastBuilder) of the run-with-consensus path
-    (blutils_amd.blast.BlastBuilder): its run id goes on every result and it is written as the document's config."""
+    (blutils_amd.blast.BlastBuilder): its run id goes on every result and it is written as the document's config.
+    hit_filter (a dict or HitFilter; None = no filter): only the lines it keeps take part; stats then
+    also has `n_lines` and `n_kept`."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
-                  lenient, parse, config, out_path, None, "one")
+                  lenient, parse, config, out_path, None, "one", hit_filter=hit_filter)
 
 
 def build_consensus_identities_with_report(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -139,12 +208,12 @@ def build_consensus_identities_with_report(blast_output: str, taxonomies_file: s
                                            headers: Optional[Sequence[str]] = None, out_format: str = "json",
                                            device: int = 0, lenient: bool = False, parse: bool = True, config=None,
                                            out_path: Optional[str] = None, report_path: str = "report.tsv",
-                                           report_weight: str = "one"):
+                                           report_weight: str = "one", hit_filter: Union[None, dict, HitFilter] = None):
     """build_consensus_identities plus the taxon abundance report of its results, counted on the GPU and written to
     report_path after the document (include/blu_pipeline.h: blu_build_consensus_identities_report).
     report_weight: "one" (results) or "size" (dereplicated reads named in the query)."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
-                  lenient, parse, config, out_path, report_path, report_weight)
+                  lenient, parse, config, out_path, report_path, report_weight, hit_filter=hit_filter)
 
 
 def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -153,18 +222,20 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
                                            headers: Optional[Sequence[str]] = None, out_format: str = "json",
                                            device: int = 0, lenient: bool = False, parse: bool = True, config=None,
                                            out_path: Optional[str] = None, report_path: Optional[str] = None,
-                                           sample_table_path: Optional[str] = None, report_weight: str = "one"):
+                                           sample_table_path: Optional[str] = None, report_weight: str = "one",
+                                           hit_filter: Union[None, dict, HitFilter] = None):
     """build_consensus_identities plus the taxon abundance report (report_path), the per-sample table (sample_table_path,
     DESIGN.md §13), or both, counted on the GPU and written in the order document, report, table
     (include/blu_pipeline.h: blu_build_consensus_identities_tables).  report_weight serves both files.  A query whose name
     names no sample fails the call before any file is written."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
-                  lenient, parse, config, out_path, report_path, report_weight, sample_table_path)
+                  lenient, parse, config, out_path, report_path, report_weight, sample_table_path, hit_filter=hit_filter)
 
 
 def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device, lenient,
-           parse, config, out_path, report_path, report_weight, sample_table_path=None):
+           parse, config, out_path, report_path, report_weight, sample_table_path=None, hit_filter=None):
     L = _bind()
+    flt, fst = _hit_filter(hit_filter), HitFilterStats()
     p = PipelineParams()
     p.cutoffs.taxon = N.TAXON[taxon]
     p.cutoffs.has_custom = 1 if custom_taxon_values is not None else 0
@@ -191,7 +262,34 @@ def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_tax
                                                      C.POINTER(PipelineStats)]
     run_id = str(config.run_id).encode() if config is not None else None
     cfg_text = config.render(out_format).encode() if config is not None else None
-    if sample_table_path is not None:
+    def stats_of():
+        stats = {f: getattr(st, f) for f, _ in PipelineStats._fields_}
+        if flt is not None:
+            stats["n_lines"], stats["n_kept"] = int(fst.n_lines), int(fst.n_kept)
+        return stats
+
+    if flt is not None:
+        # one entry point for every combination under a filter (include/blu_pipeline.h: blu_build_consensus_identities_filtered)
+        tp = None
+        if report_path is not None or sample_table_path is not None:
+            tp = TablesParams(str(report_path).encode() if report_path is not None else None,
+                              str(sample_table_path).encode() if sample_table_path is not None else None,
+                              REPORT_WEIGHT[report_weight], 0)
+        L.blu_build_consensus_identities_filtered.restype = C.c_int
+        L.blu_build_consensus_identities_filtered.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
+                                                              C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(TablesParams),
+                                                              C.POINTER(HitFilterC), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                              C.POINTER(PipelineStats), C.POINTER(HitFilterStats)]
+        rc = L.blu_build_consensus_identities_filtered(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
+                                                       taxonomies_file.encode(), C.byref(p), run_id, cfg_text,
+                                                       out_path.encode() if out_path is not None else None,
+                                                       C.byref(tp) if tp is not None else None, C.byref(flt),
+                                                       C.byref(text), C.byref(n), C.byref(st), C.byref(fst))
+        if rc != N.BLU_OK:
+            raise N.BluError(rc, "blu_build_consensus_identities_filtered")
+        if out_path is not None:
+            return None, stats_of()
+    elif sample_table_path is not None:
         tp = TablesParams(str(report_path).encode() if report_path is not None else None, str(sample_table_path).encode(),
                           REPORT_WEIGHT[report_weight], 0)
         L.blu_build_consensus_identities_tables.restype = C.c_int
@@ -240,7 +338,7 @@ def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_tax
         raw = C.string_at(text, n.value).decode("utf-8")
     finally:
         L.blu_free_text(text)
-    stats = {f: getattr(st, f) for f, _ in PipelineStats._fields_}
+    stats = stats_of()
     if not parse:
         return raw, stats
     if out_format in ("json", "json-compact"):

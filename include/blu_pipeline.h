@@ -122,6 +122,42 @@ int blu_build_consensus_identities_tables(const char* blast_output_file, const c
                                           const char* config_text, const char* out_path, const blu_tables_params* tables,
                                           char** out_text, size_t* out_len, blu_pipeline_stats* stats);
 
+/* Hit filters (not in the reference): thresholds on four columns of the table, applied by the parser.  A line
+ * is kept when every threshold named in `mask` holds, as IEEE comparisons (a NaN fails):
+ *   BLU_FILTER_MIN_PERC_IDENTITY  column 3  perc_identity >= min_perc_identity
+ *   BLU_FILTER_MIN_ALIGN_LENGTH   column 4  align_length  >= min_align_length
+ *   BLU_FILTER_MAX_E_VALUE        column 11 e_value       <= max_e_value
+ *   BLU_FILTER_MIN_BIT_SCORE      column 12 bit_score as written (before its truncation) >= min_bit_score
+ * The result is what the unfiltered call gives on a copy of the table without the dropped lines: queries numbered by their
+ * first kept line, accession ranks over the kept accessions, n_unmatched_rows over kept lines; a query that keeps no line
+ * is not in the table.  Every line is validated as without a filter, kept or not.  Column 11 is read — as an f64 column:
+ * a field that is no number is BLU_ERR_PARSE naming the line — only under BLU_FILTER_MAX_E_VALUE.  A NULL filter or an
+ * empty mask is the unfiltered call. */
+#define BLU_FILTER_MIN_PERC_IDENTITY 1u
+#define BLU_FILTER_MIN_ALIGN_LENGTH 2u
+#define BLU_FILTER_MAX_E_VALUE 4u
+#define BLU_FILTER_MIN_BIT_SCORE 8u
+typedef struct blu_hit_filter {
+    double min_perc_identity;
+    int64_t min_align_length;
+    double max_e_value;
+    double min_bit_score;
+    uint32_t mask;                 /* BLU_FILTER_* bits: which of the four are active */
+    uint32_t reserved;
+} blu_hit_filter;
+typedef struct blu_hit_filter_stats {
+    uint64_t n_lines;              /* non-empty lines of the table */
+    uint64_t n_kept;               /* lines the filter kept (= n_lines without a filter) */
+} blu_hit_filter_stats;
+/* The use-case with a filter: the arguments of blu_build_consensus_identities_tables, of which `tables` may be NULL here
+ * (no report, no per-sample table) and out_path selects file or text as there, plus the filter and its counts
+ * (filter_stats may be NULL). */
+int blu_build_consensus_identities_filtered(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                            const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
+                                            const char* config_text, const char* out_path, const blu_tables_params* tables,
+                                            const blu_hit_filter* filter, char** out_text, size_t* out_len,
+                                            blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats);
+
 /* The text-ingest half alone (no GPU): DB JSON + outfmt-6 TSV -> SoA columns, as blu_build_consensus_identities does it.
  * Fills stats (rows, queries, taxids, unmatched rows, load times) and *checksum with an FNV-1a hash over every SoA
  * column, the segment offsets and the query names — identical for any BLU_INGEST_THREADS value.  For tests and for
@@ -151,6 +187,9 @@ typedef struct blu_ingest_columns {
 } blu_ingest_columns;
 int blu_ingest_columns_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
                           blu_ingest_columns* out);
+/* The same under a hit filter (above), on either parser: the columns of the kept lines.  filter_stats may be NULL. */
+int blu_ingest_columns_filtered_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                                   const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats);
 void blu_ingest_columns_free(blu_ingest_columns* cols);
 
 /* Which parser the calling thread's last ingest used: 0 = CPU, 1 = GPU. */
