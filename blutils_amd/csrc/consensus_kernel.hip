@@ -60,10 +60,21 @@ constexpr int BLOCK_A = 768;             // 12 waves per CU (three per SIMD): wh
 constexpr int BLU_WAVES_PER_SIMD = 3;    // one 768-thread block per CU: 168 VGPRs
 constexpr int BLOCK_N = 1024;            // the kernel without the ring: 16 waves per CU (four per SIMD, 128 VGPRs)
 constexpr int BLU_N_WAVES_PER_SIMD = 4;
-constexpr int BLOCK_F = 704;             // f64 layouts, kernel with the ring (11 waves per CU: see LIST_CAP_F64)
-constexpr int LIST_CAP = 208;            // top-group entries per wave task (64 queries; mean ~183, sigma ~18 at geometric(0.35) groups)
-constexpr int LIST_CAP_F64 = 232;        // the same in the f64 layouts (4 more bytes per entry) with the ring: 11 waves per CU (BLOCK_F) so that a C3 task's top
-                                         // rows (mean 183) fit one round — at 12 waves the list held 160 entries and most tasks took two
+constexpr int BLOCK_F = 704;             // f64 layouts, kernel with the ring (11 waves per CU: see LIST_CAP_F64_RING)
+// Top-group entries per wave task (64 queries): the per-wave LDS list.  A C3 task (geometric(0.35) top groups) carries 183
+// top rows on average, sigma 18.  A ring step whose top rows no longer fit the list is not lost but costs round trips of the
+// task's own chain: in the milli-percent layouts its scanning lanes fetch and reduce their own records (a dense step: half
+// of a C3 task), in the f64 layouts the rest of the task takes another round.  C3 tasks (10 000 of them, counted from the
+// generator's table) whose top rows do not fit a list of
+//     160: 89.8 %   208: 8.67 %   224: 1.64 %   232: 0.56 %   240: 0.14 %   248: 0.01 %   256: 0
+// so the ring builds take every byte the LDS has (12 waves x 13 616 B = 163 392 of 163 840 B at 248 entries, 18 B each; a
+// multiple of 8, and at most 256 so that the gather stays at four entries per lane).  scripts/tools/resource_gate.py holds
+// every build to its LDS, occupancy and scratch.
+constexpr int LIST_CAP = 208;            // milli-percent layouts, kernel without the ring (16 waves per CU: bound by its 128 VGPRs, not by the LDS)
+constexpr int LIST_CAP_RING = 248;       // milli-percent layouts, kernel with the ring (12 waves per CU; no LDS cutoff table in these builds)
+constexpr int LIST_CAP_F64 = 232;        // f64 layouts (22 B per entry), kernel without the ring
+constexpr int LIST_CAP_F64_RING = 240;   // f64 layouts with the ring: 11 waves per CU (BLOCK_F) so that a C3 task's top rows fit one round — at 12 waves
+                                         // the list held 160 entries and most tasks took two (11 x 14 416 B + the 4 KiB cutoff table = 162 672 B)
 // Phase 1
 constexpr uint32_t SHORT_SEG = 128u;     // segments up to here are streamed (4 .. 32 lanes per query); longer ones take the sparse long pass
 constexpr uint32_t MAX_TASK_SEG = 512u;  // longest segment the stream kernel takes (64 lanes x 4 rows, twice); longer ones go to the worklist
@@ -393,7 +404,7 @@ __device__ __forceinline__ double pid_f64(typename PidKey<PID32>::type k) {
 #define KEEP_ROWS 1024u         // worklist kernel: a segment of up to this many rows is held in registers (4 x 16 bytes per lane)
 #define SLOT_CAP 256u           // worklist kernel: rows of a top group collected before their side records are gathered
 #define TASK_SPAN (1ull << 27)   // rows one task's buffer descriptors cover
-#define CUT_LDS 512        // distinct cutoff values kept in LDS (4 KiB); larger tables are read from global memory
+#define CUT_LDS 512        // f64 layouts: distinct cutoff values kept in LDS (4 KiB); larger tables are read from global memory
 #define ROW_MASK ((1u << BLU_ROW_BITS) - 1u)
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -408,7 +419,8 @@ static_assert((RING_ROWS & RING_MASK) == 0 && RING_ROWS >= 1024u, "ring size");
 // holds long segments).
 #define DESC_SUB_BITS 8u
 #define DESC_WORD1(RPL, row0, sub) (((row0) << DESC_SUB_BITS) | (sub))   // first row relative to the task (13 bits) | its position in the segment (< 128)
-static_assert(LIST_CAP >= 128 && LIST_CAP_F64 >= 128, "the list area also stages the 64 records of a task");
+static_assert(LIST_CAP >= 128 && LIST_CAP_RING >= 128 && LIST_CAP_F64 >= 128 && LIST_CAP_F64_RING >= 128, "the list area also stages the 64 records of a task");
+static_assert(LIST_CAP_RING % 8 == 0 && LIST_CAP_RING <= 256 && LIST_CAP_F64_RING % 8 == 0 && LIST_CAP_F64_RING <= 256, "four list entries per lane in the gather");
 
 // the flat pass of the kernel without the ring (tasks of mixed segment lengths): per query its first 4-row quad in the round's
 // quad numbering, its top bit-score and its top-row count
@@ -416,7 +428,7 @@ struct FlatLds { uint32_t qs[WAVE + 4]; int32_t qm[WAVE]; uint32_t qk[WAVE]; };
 struct NoFlatLds {};
 template <bool F64, bool RING>
 struct WaveLds : std::conditional_t<RING, NoFlatLds, FlatLds> {
-    static constexpr uint32_t CAP = F64 ? LIST_CAP_F64 : LIST_CAP;
+    static constexpr uint32_t CAP = F64 ? (RING ? LIST_CAP_F64_RING : LIST_CAP_F64) : (RING ? LIST_CAP_RING : LIST_CAP);
     alignas(16) uint32_t ring[RING ? RING_ROWS + RING_PAD : 4u];   // bit-scores: row v sits at ring[v & RING_MASK]; the pad mirrors ring[0 .. RING_PAD) so that a lane's run of rows never wraps
     // top-group rows of the task's queries in file order: {engine row id (sorted position | length << BLU_ROW_BITS),
     // perc_identity (milli-percent, or the low f64 word), align_length, accession rank} — a side record of the packed
@@ -425,8 +437,7 @@ struct WaveLds : std::conditional_t<RING, NoFlatLds, FlatLds> {
     uint32_t p1[F64 ? CAP : 1];             // high f64 word of perc_identity (f64 layout only)
     uint16_t pq[CAP];                       // position of the row in its segment
     uint32_t meta[WAVE + 4];    // first entry | k << 16, or META_SLOW
-    uint2 seg[WAVE + 4];        // {first row relative to the task's first row, row count (0 if > MAX_TASK_SEG or outside the span)}
-    uint32_t vx[WAVE + 4];      // first row in the task's ring numbering
+    uint2 seg[WAVE + 4];        // {first row relative to the task's first row (= in the task's ring numbering), row count (0 if > MAX_TASK_SEG or outside the span)}
 };
 
 // waits until at most k of the wave's vector-memory operations are outstanding (k is wave-uniform; s_waitcnt takes an immediate)
@@ -478,12 +489,17 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
     if (!forced && __hip_atomic_load(work_count + 9, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (RING ? 1u : 2u)) return;
     // work_count = {queue length, blocks done, published length}: the first two are zero on entry and on exit
     __shared__ WaveLds<!PID32, RING> s_lds[WAVES_T];
-    // the distinct cutoff values of this (taxonomy, backbone): a few hundred doubles, read per level in phase 2c
-    __shared__ double s_cut[CUT_LDS];
-    const bool cut_in_lds = t.n_cutvals <= CUT_LDS;
-    if (cut_in_lds) {
-        for (uint32_t i = threadIdx.x; i < t.n_cutvals; i += BLOCK_T) s_cut[i] = t.cutvals[i];
-        __syncthreads();
+    // the distinct cutoff values of this (taxonomy, backbone): a few hundred doubles, read per level in phase 2c by the f64
+    // tests.  The milli-percent layouts take those only for identities of 131.071 % and more (column layout) or never
+    // (packed): they keep no table — its 4 KiB are list entries there — and read the cutoff from global memory.
+    constexpr bool CUT_TABLE = !PID32;
+    __shared__ double s_cut[CUT_TABLE ? CUT_LDS : 1];
+    const bool cut_in_lds = CUT_TABLE && t.n_cutvals <= CUT_LDS;
+    if constexpr (CUT_TABLE) {
+        if (cut_in_lds) {
+            for (uint32_t i = threadIdx.x; i < t.n_cutvals; i += BLOCK_T) s_cut[i] = t.cutvals[i];
+            __syncthreads();
+        }
     }
     int lane = lane_id();   // (not const: see the head of the task loop)
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
@@ -668,7 +684,6 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
         const uint32_t task_nrows = (uint32_t)rl((int)task_rows, (int)nq - 1);   // rows of the whole task (contiguous tasks)
         const uint64_t vbase = (uint64_t)task_start + mis;                       // v of the task's first row
         const uint32_t seg_x = my_off - task_start;   // lane i: first row of query i in the ring's numbering, relative to the task
-        L.vx[lane] = seg_x;
         // ---------------- phase 1: LPQ lanes per query, 4 consecutive rows per lane, 64 / LPQ queries per step ----------------
         // LPQ is chosen per task from its longest segment: 4 lanes (<= 16 rows: blutils' own default is
         // max_target_seqs = 10), 8 (<= 32), 16 (<= 64), 32 (<= 128) or all 64 lanes (<= 256 rows: BLAST's own default
@@ -1162,7 +1177,7 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                 const uint32_t sub_e = sub - over;                                   // position of the lane's first row in its segment
                 const int left = FULL ? (left0 > 0 ? (int)RPL : 0) : left0;          // rows the lane holds
                 const uint32_t row0 = sg.x + sub_e;                                  // (in the column, relative to the task: what the gather reads)
-                const uint32_t a = ((uint32_t)vbase + L.vx[qi] + sub_e) & RING_MASK;
+                const uint32_t a = ((uint32_t)vbase + sg.x + sub_e) & RING_MASK;
                 int b[RPL];
 #pragma unroll
                 for (uint32_t i = 0; i < RPL; ++i) b[i] = (int)L.ring[a + i];
@@ -1943,9 +1958,12 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                     auto level = [&](uint32_t j, uint32_t packed) {
                         if (j < len_ref) {
                             const uint32_t cid = packed & ((1u << BLU_PACK_CUT_BITS) - 1u);
-                            double cj = s_cut[cut_in_lds ? cid : 0u];
-                            asm volatile("" : "+v"(cj));     // (an LDS read of its own: see ranks_of)
-                            if (!cut_in_lds) cj = t.cutvals[cid];
+                            double cj;
+                            if constexpr (CUT_TABLE) {
+                                cj = s_cut[cut_in_lds ? cid : 0u];
+                                asm volatile("" : "+v"(cj));     // (an LDS read of its own: see ranks_of)
+                                if (!cut_in_lds) cj = t.cutvals[cid];
+                            } else cj = t.cutvals[cid];
                             if (mar_level == BLU_NONE_U8 && !(ident > cj)) mar_level = j;   // skip_while(identity > cutoff)
                             if (ident >= cj) {                                             // filter(identity >= cutoff)
                                 F |= 1ull << j;
