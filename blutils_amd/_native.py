@@ -15,7 +15,7 @@ EXPORTS = (
     "blu_taxonomy_rank_name", "blu_taxonomy_row_cutoffs", "blu_taxonomy_lookup", "blu_taxonomy_row_map", "blu_consensus_run",
     "blu_consensus_last_launch", "blu_hits_pack", "blu_hits_pack64", "blu_taxonomy_shared_levels", "blu_taxonomy_trim",
     "blu_consensus_report", "blu_report_free", "blu_dev_exclusive_scan", "blu_dev_radix_sort_pairs", "blu_dev_line_index",
-    "blu_consensus_sample_table", "blu_sample_table_free",
+    "blu_consensus_sample_table", "blu_sample_table_free", "blu_consensus_support",
 )
 # include/blu_pipeline.h
 PIPELINE_EXPORTS = ("blu_build_consensus_identities", "blu_free_text", "blu_custom_taxon_from_file", "blu_ingest_only",
@@ -23,7 +23,7 @@ PIPELINE_EXPORTS = ("blu_build_consensus_identities", "blu_free_text", "blu_cust
                     "blu_build_consensus_identities_to_file", "blu_ingest_columns_on", "blu_ingest_columns_free",
                     "blu_taxdb_build", "blu_seqdb_export", "blu_qiime_taxonomy_tsv", "blu_build_consensus_identities_report",
                     "blu_build_consensus_identities_tables", "blu_build_consensus_identities_filtered",
-                    "blu_ingest_columns_filtered_on")
+                    "blu_ingest_columns_filtered_on", "blu_build_consensus_identities_support")
 
 BLU_UNMATCHED_TAXID = 0xFFFFFFFF
 BLU_NONE_U8, BLU_NONE_U16, BLU_MAR_NEVER_EQUAL = 0xFF, 0xFFFF, 0xFFFE

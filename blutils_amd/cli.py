@@ -36,6 +36,16 @@ if the others had been deleted from the file first; the GPU parser applies them.
 still written in full (`-p/-q/-e` go to blastn itself); the filter applies to the consensus step.  One line goes to stderr:
 `hit filter: kept K of N lines`.
 
+    python -m blutils_amd.cli blastn build-consensus ... --support-table FILE
+    python -m blutils_amd.cli blastn run-with-consensus ... --support-table FILE
+
+not in the reference: the per-query support table.  One tab-separated line per result, in the document's
+order: the last element of its taxonomy, the number of hits, how many of them name a taxon of the database, the size of the
+top bit-score group, and how many hits — of the top group and of all — lie in the clade the result names, with the bit-score
+sums and `confidence` = support / hits.  Counted on the GPU from the run's own records and columns (csrc/support_kernel.hip)
+and written after the document, the report and the sample table; it combines with those flags and with the hit filters
+(the counts are then over the kept lines).  The document stays what it is without the flag.
+
     python -m blutils_amd.cli cache-db TAX.json CACHE [-u]
 
 writes the binary cache of a taxonomies file (not in the reference CLI; pass CACHE as -t afterwards).  
@@ -112,6 +122,9 @@ def build_parser() -> argparse.ArgumentParser:
         sp.add_argument("--sample-table", help="also write the taxon x sample table of the results to this file, counted "
                                                "on the GPU; samples from `;sample=S` or `S.<n>` query names (not in the "
                                                "reference CLI)")
+        sp.add_argument("--support-table", help="also write the per-query support table to this file: how many of a query's "
+                                                "hits lie in the clade it was assigned to, counted on the GPU (not in the "
+                                                "reference CLI)")
         flt = sp.add_argument_group("hit filters (not in the reference CLI)",
                                     "a line of the table takes part only if it meets every threshold given; applied by "
                                     "the parser, on the GPU where it parses")
@@ -254,7 +267,7 @@ def _run_with_consensus(args) -> int:
                                             args.threads, args.strategy, args.use_taxid, args.out_format, custom,
                                             device=args.device, report_path=args.report, report_weight=args.report_weight,
                                             sample_table_path=args.sample_table, hit_filter=_hit_filter(args),
-                                            filter_stats=stats)
+                                            filter_stats=stats, support_table_path=args.support_table)
     except blast.BlastError as e:
         raise SystemExit(str(e))
     _say_kept(stats)
@@ -294,7 +307,11 @@ def main(argv=None) -> int:
     build = pipeline.build_consensus_identities
     hit_filter = _hit_filter(args)
     extra = {"hit_filter": hit_filter} if hit_filter is not None else {}
-    if args.sample_table is not None:
+    if args.support_table is not None:
+        build = functools.partial(pipeline.build_consensus_identities_with_tables, report_path=args.report,
+                                  sample_table_path=args.sample_table, report_weight=args.report_weight,
+                                  support_table_path=args.support_table)
+    elif args.sample_table is not None:
         build = functools.partial(pipeline.build_consensus_identities_with_tables, report_path=args.report,
                                   sample_table_path=args.sample_table, report_weight=args.report_weight)
     elif args.report is not None:

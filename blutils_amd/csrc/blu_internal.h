@@ -133,6 +133,19 @@ int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* ou
 int sample_table_device(const blu_taxonomy* tax, const ReportInput& in, const uint32_t* sample_of, uint32_t n_samples,
                         blu_sample_table* out);
 
+// support_kernel.hip: the per-query support counts of one run's records (device pointers, d_out too; blu_consensus_support
+// stages host ones).  The engine row of hit i is row_src[i * row_stride].  Returns when d_out is complete.
+struct SupportInput {
+    const blu_result* recs;
+    uint64_t n_queries;
+    const uint64_t* seg_off;
+    const int32_t* bitscore;
+    const uint32_t* row_src;
+    uint32_t row_stride;
+    uint64_t n_hits;
+};
+int support_device(const blu_taxonomy* tax, const SupportInput& in, blu_support* d_out);
+
 void set_error(const char* fmt, ...);
 // LinnaeanRank::from_str (linnaean_ranks.rs:52-72): enum kind 0..8, or K_FIRST_OTHER with the slug in *other
 uint16_t parse_rank(const char* name, std::string* other);

@@ -1266,6 +1266,8 @@ struct Document {
     std::string report;
     bool has_table = false;    // table: the per-sample table's text, written after the report
     std::string table;
+    bool has_support = false;  // support: the per-query support table's text, written last
+    std::string support;
     size_t size() const { size_t n = 0; for (auto& p : pieces) n += p.size(); return n; }
 };
 
@@ -1416,12 +1418,74 @@ int build_sample_table(const Db& db, const HitTable& ht, const blu_taxonomy* tax
     return BLU_OK;
 }
 
+// The support table of one pipeline run (blu_build_consensus_identities_support): the device pass over the
+// run's records and columns (in place on the device path; the two columns, the offsets and the records uploaded on the host
+// path), then one line per result in the document's order.  Item: {name, q}, q < 0 for a header without hits.
+template <class Items>
+int build_support(const Db& db, const HitTable& ht, const blu_taxonomy* tax, const Column<blu_result>& recs, const DeviceRecords& kept,
+                  bool on_device, const std::vector<uint32_t>& eng_rows, const TopTable& top, const Items& items, std::string& text) {
+    const uint64_t nq = recs.size();
+    std::vector<blu_support> sup(nq);
+    if (on_device && nq) {
+        HipPolicy pol{"support", BLU_ERR_ALLOC};
+        DeviceArena mem(pol);
+        blu_support* d_sup = nullptr;
+        HIP_CHECK(pol, mem.alloc(&d_sup, nq * sizeof(blu_support), "counts"));
+        SupportInput in{kept.recs, nq, (const uint64_t*)ht.dev->seg_off, ht.dev->bitscore, kept.rows, kept.row_stride, ht.n_hits};
+        const int rc = support_device(tax, in, d_sup);
+        if (rc != BLU_OK) return rc;
+        HIP_CHECK(pol, hipMemcpy(sup.data(), d_sup, nq * sizeof(blu_support), hipMemcpyDeviceToHost));
+    } else if (nq) {
+        blu_hits h{};
+        h.bitscore = ht.bitscore.data();
+        h.tax_row = eng_rows.data();
+        h.seg_off = ht.seg_off.data();
+        h.n_hits = eng_rows.size();
+        h.n_queries = nq;
+        h.on_device = 0;
+        const int rc = blu_consensus_support(tax, &h, recs.data(), nullptr, sup.data());
+        if (rc != BLU_OK) return rc;
+    }
+    std::string& o = text;
+    o = "#query\trank\tidentifier\thits\tmatched\ttop_hits\ttop_support\tsupport\tbit_score\tbits\tsupport_bits\tconfidence\n";
+    o.reserve(o.size() + items.size() * 96);
+    auto num = [&](int64_t v) { char b[24]; auto r = std::to_chars(b, b + sizeof b, v); o.append(b, (size_t)(r.ptr - b)); o.push_back('\t'); };
+    const blu_support none{};
+    for (const auto& it : items) {
+        o += *it.name; o.push_back('\t');
+        const blu_support& c = it.q < 0 ? none : sup[(size_t)it.q];
+        const blu_result* r = it.q < 0 ? nullptr : &recs[(size_t)it.q];
+        if (!r || r->status >= 2) o += "-\tunclassified\t";
+        else {
+            // the last element of the result's `taxonomy` (Renderer::lineage): the highest level of level_mask the lineage has
+            uint32_t drow = 0;
+            for (uint64_t i = top.off[(size_t)it.q], e = top.off[(size_t)it.q + 1]; i < e; ++i) {
+                if (i == top.off[(size_t)it.q]) drow = top.rows[i].desc_row;
+                if (top.rows[i].row == r->ref_row) { drow = top.rows[i].desc_row; break; }
+            }
+            const uint64_t len = db.lin_off[drow + 1] - db.lin_off[drow];
+            const uint64_t m = len >= 64 ? r->level_mask : r->level_mask & ((1ull << len) - 1ull);
+            if (m == 0) o += "-\tunplaced\t";
+            else {
+                const uint64_t at = db.lin_off[drow] + (63u - (uint32_t)__builtin_clzll(m));
+                o += db.rank_display[db.lin_rank[at]]; o.push_back('\t'); o += db.node_ident[db.lin_node[at]]; o.push_back('\t');
+            }
+        }
+        num(c.n_hits); num(c.n_matched); num(c.n_top); num(c.n_top_support); num(c.n_support); num(c.top_score); num(c.bits); num(c.support_bits);
+        char b[64];
+        const int n = snprintf(b, sizeof b, "%.4f\n", c.n_hits ? (double)c.n_support / (double)c.n_hits : 0.0);
+        o.append(b, (size_t)n);
+    }
+    return BLU_OK;
+}
+
 // out_path != nullptr: the document is written there (an existing file is replaced, write_blutils_output.rs:57-63) by a
 // writer thread that follows the renderers piece by piece; otherwise the pieces are left in `document`.
 int build_document(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
                    const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
                    const char* config_text, const char* out_path, Document* document, blu_pipeline_stats* stats,
-                   const blu_tables_params* tables = nullptr, const blu_hit_filter* flt = nullptr, blu_hit_filter_stats* fst = nullptr) {
+                   const blu_tables_params* tables = nullptr, const blu_hit_filter* flt = nullptr, blu_hit_filter_stats* fst = nullptr,
+                   const char* support_path = nullptr) {
     if (!blast_output_file || !taxonomies_file || !params || !document) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     if (flt && (flt->mask & ~15u)) { set_error("hit filter: unknown bits in the mask"); return BLU_ERR_INVALID_ARG; }
     if (tables && ((!tables->report_path && !tables->sample_table_path) ||
@@ -1607,6 +1671,12 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
         document->has_table = true;
         tr.lap("sample table");
     }
+    if (support_path) {
+        rc = build_support(db, ht, tax, recs, kept, done_on_device, eng_rows, top, items, document->support);
+        if (rc != BLU_OK) return rc;
+        document->has_support = true;
+        tr.lap("support table");
+    }
     const bool pretty = params->out_format == BLU_OUT_JSON;
     const bool doc = pretty || params->out_format == BLU_OUT_JSON_COMPACT;   // one {results, config} document
     // write_blutils_output.rs:82-85: the config's run id, or a fresh one
@@ -1763,26 +1833,27 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     return BLU_OK;
 }
 
-// the report, then the per-sample table, after the document
-int put_tables(const Document& d, const blu_tables_params* tables) {
+// the report, then the per-sample table, then the support table, after the document
+int put_tables(const Document& d, const blu_tables_params* tables, const char* support_path) {
     if (d.has_report && !write_text_file(tables->report_path, d.report)) { set_error("cannot write %s", tables->report_path); return BLU_ERR_IO; }
     if (d.has_table && !write_text_file(tables->sample_table_path, d.table)) { set_error("cannot write %s", tables->sample_table_path); return BLU_ERR_IO; }
+    if (d.has_support && !write_text_file(support_path, d.support)) { set_error("cannot write %s", support_path); return BLU_ERR_IO; }
     return BLU_OK;
 }
 
 int consensus_to_text(const char* blast_output_file, const char* const* headers, uint64_t n_headers, const char* taxonomies_file,
                       const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const blu_tables_params* tables,
                       char** out_text, size_t* out_len, blu_pipeline_stats* stats, const blu_hit_filter* flt = nullptr,
-                      blu_hit_filter_stats* fst = nullptr) {
+                      blu_hit_filter_stats* fst = nullptr, const char* support_path = nullptr) {
     if (!out_text) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     *out_text = nullptr;
     if (out_len) *out_len = 0;
     Document d;
     int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats, tables, flt, fst); }
+    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats, tables, flt, fst, support_path); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }   // (no exception crosses the C ABI)
     if (rc != BLU_OK) return rc;
-    if ((rc = put_tables(d, tables)) != BLU_OK) return rc;
+    if ((rc = put_tables(d, tables, support_path)) != BLU_OK) return rc;
     const size_t total = d.size();
     char* buf = (char*)malloc(total + 1);
     if (!buf) { set_error("out of memory"); return BLU_ERR_ALLOC; }
@@ -1800,15 +1871,15 @@ int consensus_to_text(const char* blast_output_file, const char* const* headers,
 int consensus_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers, const char* taxonomies_file,
                       const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const char* out_path,
                       const blu_tables_params* tables, blu_pipeline_stats* stats, const blu_hit_filter* flt = nullptr,
-                      blu_hit_filter_stats* fst = nullptr) {
+                      blu_hit_filter_stats* fst = nullptr, const char* support_path = nullptr) {
     if (!out_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     Document d;
     int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats, tables, flt, fst); }
+    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats, tables, flt, fst, support_path); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
     if (rc != BLU_OK) return rc;
     if (getenv("BLU_INGEST_TRACE")) fprintf(stderr, "[pipeline] %-26s %.3f s\n", "tear-down (tables, strings)", now_s() - g_t_body_end);
-    auto put_report = [&]() { return put_tables(d, tables); };
+    auto put_report = [&]() { return put_tables(d, tables, support_path); };
     if (d.written) return put_report();
     // (YAML: one piece, written here) write_blutils_output.rs:57-63: an existing file is replaced
     Trace tr;
@@ -1887,6 +1958,20 @@ int blu_build_consensus_identities_filtered(const char* blast_output_file, const
                                  stats, filter, filter_stats);
     return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, tables, out_text,
                              out_len, stats, filter, filter_stats);
+}
+
+int blu_build_consensus_identities_support(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                           const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
+                                           const char* config_text, const char* out_path, const blu_tables_params* tables,
+                                           const blu_hit_filter* filter, char** out_text, size_t* out_len,
+                                           blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats, const char* support_table_path) {
+    if (tables && !tables->report_path && !tables->sample_table_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    if (filter_stats) *filter_stats = blu_hit_filter_stats{0, 0};
+    if (out_path)
+        return consensus_to_file(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, tables,
+                                 stats, filter, filter_stats, support_table_path);
+    return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, tables, out_text,
+                             out_len, stats, filter, filter_stats, support_table_path);
 }
 
 int blu_build_consensus_identities_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers,

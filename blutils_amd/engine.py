@@ -22,6 +22,14 @@ RESULT_DTYPE = np.dtype([
 assert RESULT_DTYPE.itemsize == 32
 
 
+# include/blu_consensus.h: blu_support
+SUPPORT_DTYPE = np.dtype([
+    ("n_hits", "<u4"), ("n_matched", "<u4"), ("n_top", "<u4"), ("n_top_support", "<u4"), ("n_support", "<u4"),
+    ("top_score", "<i4"), ("bits", "<i8"), ("support_bits", "<i8"),
+])
+assert SUPPORT_DTYPE.itemsize == 40
+
+
 def _cutoff_config(taxon: str, custom: Optional[dict]) -> N.CutoffConfig:
     cfg = N.CutoffConfig()
     cfg.taxon = N.TAXON[taxon]
@@ -329,6 +337,62 @@ def run_consensus_device(tax: Taxonomy, hits: dict, out, strategy: str = "relaxe
     rc = N.lib().blu_consensus_run(tax.handle, C.byref(h), C.byref(params), out.data_ptr())
     if rc != N.BLU_OK:
         raise N.BluError(rc, "blu_consensus_run")
+
+
+def support_host(tax: Taxonomy, seg_off, bitscore, tax_row, records, packed=None, packed64=None) -> np.ndarray:
+    """blu_consensus_support on host arrays: the support counts (SUPPORT_DTYPE) of `records`, a run's RESULT_DTYPE array.
+    tax_row: ENGINE row ids; or pass the [n, 4] side records as packed= / the [n, 6] ones as packed64= (tax_row=None): their
+    word 0 is read."""
+    seg = np.ascontiguousarray(seg_off, dtype=np.uint64)
+    bs = np.ascontiguousarray(bitscore, dtype=np.int32)
+    recs = np.ascontiguousarray(records, dtype=RESULT_DTYPE)
+    nq, nh = len(seg) - 1, len(bs)
+    assert len(recs) == nq
+    tx = _u32(tax_row) if tax_row is not None else None
+    pk = np.ascontiguousarray(packed, dtype=np.uint32) if packed is not None else None
+    pk64 = np.ascontiguousarray(packed64, dtype=np.uint32) if packed64 is not None else None
+    assert (tx is not None) + (pk is not None) + (pk64 is not None) == 1
+    assert tx is None or len(tx) == nh
+    assert pk is None or pk.size == 4 * nh
+    assert pk64 is None or pk64.size == 6 * nh
+    hits = N.Hits(bs.ctypes.data, tx.ctypes.data if tx is not None else None, None, None, None, seg.ctypes.data, nh, nq, 0, 0, None,
+                  pk.ctypes.data if pk is not None else None, pk64.ctypes.data if pk64 is not None else None)
+    out = np.zeros(nq, dtype=SUPPORT_DTYPE)
+    L = N.lib()
+    L.blu_consensus_support.restype = C.c_int
+    L.blu_consensus_support.argtypes = [C.c_void_p, C.POINTER(N.Hits), C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = L.blu_consensus_support(tax.handle, C.byref(hits), recs.ctypes.data, None, out.ctypes.data)
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_consensus_support")
+    return out
+
+
+def support_device(tax: Taxonomy, hits: dict, records, stream: Optional[int] = None) -> np.ndarray:
+    """blu_consensus_support on torch CUDA tensors: `hits` as for run_consensus_device (seg_off, bitscore and tax_row, packed
+    or packed64 are read), `records` the uint8 CUDA tensor a run wrote.  Returns the counts on the host (SUPPORT_DTYPE)."""
+    import torch
+
+    nq = hits["seg_off"].numel() - 1
+    nh = hits["bitscore"].numel()
+    side = "packed64" if hits.get("packed64") is not None else "packed" if hits.get("packed") is not None else "tax_row"
+    for k, dt in (("seg_off", torch.int64), ("bitscore", torch.int32), (side, torch.int32)):
+        t = hits[k]
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dt, (k, t.dtype, t.device)
+    assert hits[side].numel() == {"tax_row": 1, "packed": 4, "packed64": 6}[side] * nh
+    assert records.is_cuda and records.is_contiguous() and records.numel() * records.element_size() >= 32 * nq
+    out = torch.zeros(max(nq, 1) * 5, dtype=torch.int64, device=records.device)   # 40 bytes a query, 8-byte aligned
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    h = N.Hits(hits["bitscore"].data_ptr(), hits["tax_row"].data_ptr() if side == "tax_row" else None, None, None, None,
+               hits["seg_off"].data_ptr(), nh, nq, 1, 0, None, hits["packed"].data_ptr() if side == "packed" else None,
+               hits["packed64"].data_ptr() if side == "packed64" else None)
+    L = N.lib()
+    L.blu_consensus_support.restype = C.c_int
+    L.blu_consensus_support.argtypes = [C.c_void_p, C.POINTER(N.Hits), C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = L.blu_consensus_support(tax.handle, C.byref(h), records.data_ptr(), stream, out.data_ptr())
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_consensus_support")
+    return out.cpu().numpy().view(np.uint8)[: 40 * nq].view(SUPPORT_DTYPE).copy()
 
 
 def records_from_tensor(out) -> np.ndarray:

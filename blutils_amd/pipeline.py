@@ -223,17 +223,22 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
                                            device: int = 0, lenient: bool = False, parse: bool = True, config=None,
                                            out_path: Optional[str] = None, report_path: Optional[str] = None,
                                            sample_table_path: Optional[str] = None, report_weight: str = "one",
-                                           hit_filter: Union[None, dict, HitFilter] = None):
+                                           hit_filter: Union[None, dict, HitFilter] = None,
+                                           support_table_path: Optional[str] = None):
     """build_consensus_identities plus the taxon abundance report (report_path), the per-sample table (sample_table_path,
     DESIGN.md §13), or both, counted on the GPU and written in the order document, report, table
     (include/blu_pipeline.h: blu_build_consensus_identities_tables).  report_weight serves both files.  A query whose name
-    names no sample fails the call before any file is written."""
+    names no sample fails the call before any file is written.  support_table_path: also the per-query support table
+    (blu_build_consensus_identities_support), counted on the GPU and written last; it combines with the
+    other files and with hit_filter, and may be the only one asked for."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
-                  lenient, parse, config, out_path, report_path, report_weight, sample_table_path, hit_filter=hit_filter)
+                  lenient, parse, config, out_path, report_path, report_weight, sample_table_path, hit_filter=hit_filter,
+                  support_table_path=support_table_path)
 
 
 def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device, lenient,
-           parse, config, out_path, report_path, report_weight, sample_table_path=None, hit_filter=None):
+           parse, config, out_path, report_path, report_weight, sample_table_path=None, hit_filter=None,
+           support_table_path=None):
     L = _bind()
     flt, fst = _hit_filter(hit_filter), HitFilterStats()
     p = PipelineParams()
@@ -268,7 +273,30 @@ def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_tax
             stats["n_lines"], stats["n_kept"] = int(fst.n_lines), int(fst.n_kept)
         return stats
 
-    if flt is not None:
+    if support_table_path is not None:
+        # the support table: one entry point for every combination (include/blu_pipeline.h: blu_build_consensus_identities_support)
+        tp = None
+        if report_path is not None or sample_table_path is not None:
+            tp = TablesParams(str(report_path).encode() if report_path is not None else None,
+                              str(sample_table_path).encode() if sample_table_path is not None else None,
+                              REPORT_WEIGHT[report_weight], 0)
+        L.blu_build_consensus_identities_support.restype = C.c_int
+        L.blu_build_consensus_identities_support.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
+                                                             C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(TablesParams),
+                                                             C.POINTER(HitFilterC), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                             C.POINTER(PipelineStats), C.POINTER(HitFilterStats), C.c_char_p]
+        rc = L.blu_build_consensus_identities_support(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
+                                                      taxonomies_file.encode(), C.byref(p), run_id, cfg_text,
+                                                      out_path.encode() if out_path is not None else None,
+                                                      C.byref(tp) if tp is not None else None,
+                                                      C.byref(flt) if flt is not None else None,
+                                                      C.byref(text), C.byref(n), C.byref(st), C.byref(fst),
+                                                      str(support_table_path).encode())
+        if rc != N.BLU_OK:
+            raise N.BluError(rc, "blu_build_consensus_identities_support")
+        if out_path is not None:
+            return None, stats_of()
+    elif flt is not None:
         # one entry point for every combination under a filter (include/blu_pipeline.h: blu_build_consensus_identities_filtered)
         tp = None
         if report_path is not None or sample_table_path is not None:

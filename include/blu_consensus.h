@@ -337,6 +337,38 @@ int blu_consensus_sample_table(const blu_taxonomy* tax, const blu_hits* hits, co
                                const uint32_t* sample_of, uint32_t n_samples, void* stream, blu_sample_table* out);
 void blu_sample_table_free(blu_sample_table* table);
 
+/* -------------------------------------------------------------------------- */
+/* Per-query assignment support (additive, ABI v5): how well the hits of a query back the taxon its record names.
+ * A hit is MATCHED when its row id names a taxonomy row whose lineage parsed (not BLU_UNMATCHED_TAXID, not a `bad` or empty
+ * lineage).  The ASSIGNED CLADE of a record with a taxon (status 0 / 1) is every taxonomy row whose lineage has more than L
+ * levels and shares its first L + 1 nodes with the lineage of the reference row, L = the highest bit of level_mask (the last
+ * level the `taxonomy` string shows; the levels the cutoffs filtered out of the string are compared too); level_mask == 0
+ * (taxonomy "") is the empty prefix: every matched hit.  A record with status >= 2 has no clade.  A hit SUPPORTS the
+ * assignment when it is matched and its row lies in the clade.  All counts are integers: exact and deterministic.
+ * Counted on the device (csrc/support_kernel.hip): the clade is one range of sorted positions, found once per query from
+ * the lcp8 / rmq tables, and every hit is one range compare; DESIGN.md §15. */
+typedef struct blu_support {
+    uint32_t n_hits;           /* rows of the segment */
+    uint32_t n_matched;        /* matched rows */
+    uint32_t n_top;            /* rows whose bit-score equals the segment's maximum */
+    uint32_t n_top_support;    /* of those, the supporting ones */
+    uint32_t n_support;        /* supporting rows of the whole segment */
+    int32_t top_score;         /* the maximum bit-score (0 for an empty segment) */
+    int64_t bits;              /* sum of bit-scores over the segment */
+    int64_t support_bits;      /* sum of bit-scores over the supporting rows */
+} blu_support;                 /* 40 bytes */
+
+/* The support counts of one run's records: `hits` as for blu_consensus_run, of which seg_off, bitscore, the engine row id of
+ * each hit (tax_row, or word 0 of the packed / packed64 records), n_hits, n_queries and on_device are read; results[n_queries]
+ * are its records.  Device pointers: results 16-byte aligned, `out` a device pointer too (8-byte aligned); the call waits
+ * for `stream` (a hipStream_t, NULL = default) before reading and returns when `out` is complete.  Host pointers: the two
+ * columns, the offsets and the records are uploaded and the counts copied back.  For status >= 2, n_top_support, n_support
+ * and support_bits are 0 and the rest are still filled; an empty segment gives zeros.  A record with a taxon whose ref_row
+ * names no taxonomy row is BLU_ERR_INVALID_ARG naming the query index; a host-only handle is BLU_ERR_NO_DEVICE: there is no
+ * CPU fallback. */
+int blu_consensus_support(const blu_taxonomy* tax, const blu_hits* hits, const blu_result* results, void* stream,
+                          blu_support* out /* [n_queries] */);
+
 #ifdef __cplusplus
 }
 #endif

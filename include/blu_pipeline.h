@@ -158,6 +158,24 @@ int blu_build_consensus_identities_filtered(const char* blast_output_file, const
                                             const blu_hit_filter* filter, char** out_text, size_t* out_len,
                                             blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats);
 
+/* The use-case with a per-query support table (not in the reference): the arguments of
+ * blu_build_consensus_identities_filtered (tables and filter may be NULL) plus support_table_path; NULL is that call.  The
+ * counts come from the device (blu_consensus_support) — on the records and columns the run left there, or through the
+ * host-pointer route when the columns are on the host — over the kept lines under a filter, and are written after the
+ * document, the report and the sample table, tab-separated:
+ *   #query  rank  identifier  hits  matched  top_hits  top_support  support  bit_score  bits  support_bits  confidence
+ * one line per result of the document, in the document's order (headers without hits included, every count zero).  rank and
+ * identifier: the last element of the result's `taxonomy`, as the report's rows have them; `-` and `unclassified` when
+ * `taxon` is null, `-` and `unplaced` when `taxonomy` is "".  The counts are blu_support's, in decimal; confidence is
+ * "%.4f" of support / hits (0.0000 without hits).  In strict mode a reference panic fails the call before any file is
+ * written; in lenient mode those queries are `unclassified` lines.  The document is what the call without the path writes. */
+int blu_build_consensus_identities_support(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                           const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
+                                           const char* config_text, const char* out_path, const blu_tables_params* tables,
+                                           const blu_hit_filter* filter, char** out_text, size_t* out_len,
+                                           blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats,
+                                           const char* support_table_path);
+
 /* The text-ingest half alone (no GPU): DB JSON + outfmt-6 TSV -> SoA columns, as blu_build_consensus_identities does it.
  * Fills stats (rows, queries, taxids, unmatched rows, load times) and *checksum with an FNV-1a hash over every SoA
  * column, the segment offsets and the query names — identical for any BLU_INGEST_THREADS value.  For tests and for
