@@ -483,7 +483,7 @@ struct Export {
         }
     }
 
-    // ---- one chunk on the device into O; *done: a stop or an error ended the listing in this chunk
+    // ---- one chunk on the device into O; *done: a stop or an error ended the listing in this chunk (set once O is filled)
     int chunk_on_device(const InSlot& I, OutSlot& O, uint64_t line_base, bool* done) {
         const int qiime = D.format == BLU_SEQDB_QIIME2;
         const uint64_t size = I.len;
@@ -636,8 +636,10 @@ struct Export {
             S.t_gpu_ms += 1e3 * (now_s() - t0);
             line_base += S.n_lines - lines_before;
             in_free.push(s);
-            if (rc != BLU_OK) { out_free.push(o); }
-            else out_full.push(o);
+            // a line the export refuses (BLU_ERR_PARSE with *done set) leaves the records before it in the slot: they are
+            // written like any other chunk's, so that the .fna does not depend on where the chunks were cut
+            if (rc == BLU_OK || (rc == BLU_ERR_PARSE && done)) out_full.push(o);
+            else out_free.push(o);
             if (rc != BLU_OK || done || stop.load()) break;
         }
         stop = true;

@@ -21,7 +21,8 @@ QIIME2_OUTFMT = "%a  %T  %o  %s"          # build_qiime_db_from_blutils_db/mod.r
 
 
 class SeqdbError(RuntimeError):
-    pass
+    """`stats`: the counts up to the refused line, when blu_seqdb_export raised it (else None)."""
+    stats: Optional[Dict[str, float]] = None
 
 
 class SeqdbDesc(C.Structure):
@@ -64,7 +65,9 @@ def export(fmt: int, fna_path: str, map_path: Optional[str] = None, listing_path
     st = SeqdbStats()
     rc = L.blu_seqdb_export(C.byref(d), C.byref(st))
     if rc != N.BLU_OK:
-        raise SeqdbError(f"build-db failed (blu_error {rc}): {N.last_error()}")
+        e = SeqdbError(f"build-db failed (blu_error {rc}): {N.last_error()}")
+        e.stats = st.as_dict()
+        raise e
     return st.as_dict()
 
 

@@ -11,11 +11,23 @@ _USIZE = re.compile(rb"\+?[0-9]+")
 
 
 class RefError(Exception):
-    """The reference panics (or, for the divergences DESIGN.md lists, this engine refuses) at 1-based `line`."""
+    """The reference panics (or, for the divergences DESIGN.md lists, this engine refuses) at 1-based `line`.  `fna` is the
+    output written before that line (what the .fna holds after an error), `records` their number and `prelim`
+    the prelim_map.txt lines of those records (kraken2; the file itself is not left behind)."""
 
-    def __init__(self, line: int, why: str):
-        self.line = line
+    def __init__(self, line: int, why: str, fna: bytes = b"", records: int = 0, prelim: bytes = b""):
+        self.line, self.why, self.fna, self.records, self.prelim = line, why, fna, records, prelim
         super().__init__(f"line {line}: {why}")
+
+
+class Result(tuple):
+    """What a restated function returns: the tuple its docstring names, and `records`, the number of records written."""
+    records = 0
+
+    def __new__(cls, items, records: int):
+        self = super().__new__(cls, items)
+        self.records = records
+        return self
 
 
 def _lines(listing: bytes):
@@ -51,36 +63,66 @@ def usize(text: bytes) -> Optional[int]:
 
 
 def kraken2(listing: bytes) -> Tuple[bytes, bytes, Optional[int]]:
-    """(library.fna, prelim_map.txt, the line of an invalid-UTF-8 stop or None)"""
+    """(library.fna, prelim_map.txt, the line of an invalid-UTF-8 stop or None), with .records"""
     fna, heads, stop = [], [], None
     last = 0
     for no, line in _lines(listing):
         last = no
-        acc, taxid, seq = _pieces(line, 3, no)
-        if not seq.isascii():                   # divergence: to_uppercase/chunks(80) work on chars (DESIGN.md)
-            raise RefError(no, "the sequence holds a byte >= 0x80")
-        up = seq.upper()                                  # K rs:80-89: to_uppercase, chunks(80), join("\n")
-        body = b"\n".join(up[i:i + 80] for i in range(0, len(up), 80))
+        try:
+            acc, taxid, seq = _pieces(line, 3, no)
+            if not seq.isascii():               # divergence: to_uppercase/chunks(80) work on chars (DESIGN.md)
+                raise RefError(no, "the sequence holds a byte >= 0x80")
+            up = seq.upper()                              # K rs:80-89: to_uppercase, chunks(80), join("\n")
+            body = b"\n".join(up[i:i + 80] for i in range(0, len(up), 80))
+            n = usize(taxid)                              # K rs:98: taxid.parse().unwrap()
+            if n is None:                                 # (the reference has written this line's record by then; here the
+                raise RefError(no, "the taxid is not an unsigned integer")    # .fna holds the records before the bad line)
+        except RefError as e:
+            raise RefError(e.line, e.why, b"".join(fna), len(fna), _prelim(heads)) from None
         fna.append(b">kraken:taxid|" + taxid + b"|" + acc + b"\n" + body + b"\n")   # K rs:78-79
-        n = usize(taxid)                                  # K rs:98: taxid.parse().unwrap()
-        if n is None:
-            raise RefError(no, "the taxid is not an unsigned integer")
         heads.append((acc, n))
     if listing and last < _count_lines(listing):
         stop = last + 1
-    prelim = b"".join(b"TAXID\tkraken:taxid|%d|%s\t%d\n" % (n, acc, n) for acc, n in heads)   # generate_taxonomies_file.rs:28-36
-    return b"".join(fna), prelim, stop
+    return Result((b"".join(fna), _prelim(heads), stop), len(fna))
+
+
+def _prelim(heads) -> bytes:
+    return b"".join(b"TAXID\tkraken:taxid|%d|%s\t%d\n" % (n, acc, n) for acc, n in heads)   # generate_taxonomies_file.rs:28-36
 
 
 def qiime2_sequences(listing: bytes) -> Tuple[bytes, Optional[int]]:
-    """(the .fna, the line of an invalid-UTF-8 stop or None); Q:127-145"""
+    """(the .fna, the line of an invalid-UTF-8 stop or None), with .records; Q:127-145"""
     out, last = [], 0
     for no, line in _lines(listing):
         last = no
-        acc, taxid, oid, seq = _pieces(line, 4, no)
+        try:
+            acc, taxid, oid, seq = _pieces(line, 4, no)
+        except RefError as e:
+            raise RefError(e.line, e.why, b"".join(out), len(out)) from None
         out.append(b">" + taxid + b"-" + oid + b"-" + acc + b"\n" + seq + b"\n")
     stop = last + 1 if listing and last < _count_lines(listing) else None
-    return b"".join(out), stop
+    return Result((b"".join(out), stop), len(out))
+
+
+def export(qiime: bool, listing: bytes) -> dict:
+    """What one export of the listing leaves behind, for a test to compare whole: "outcome" is ("ok",), ("stop", line) or
+    ("error", line, reason) with reason "pieces", "nonascii" or "taxid"; "fna" the .fna (after an error: the records before
+    the bad line); "map" prelim_map.txt (None for qiime2 and after an error: the file does not exist); "records" their
+    number, "input_bytes" the offset of the first line that gave none and "map_bytes" the prelim_map.txt bytes of those
+    records (after an error too, when no file is left)."""
+    try:
+        r = qiime2_sequences(listing) if qiime else kraken2(listing)
+        fna, prelim, stop, records = r[0], (None if qiime else r[1]), r[-1], r.records
+        map_bytes = len(prelim or b"")
+        outcome = ("ok",) if stop is None else ("stop", stop)
+    except RefError as e:
+        reason = "pieces" if "Invalid line" in e.why else "nonascii" if "0x80" in e.why else "taxid"
+        fna, prelim, records, outcome, map_bytes = e.fna, None, e.records, ("error", e.line, reason), len(e.prelim)
+    pos = 0
+    for _ in range(records):
+        nl = listing.find(b"\n", pos)
+        pos = nl + 1 if nl >= 0 else len(listing)
+    return {"outcome": outcome, "fna": fna, "map": prelim, "records": records, "input_bytes": pos, "map_bytes": map_bytes}
 
 
 def _count_lines(listing: bytes) -> int:
