@@ -23,7 +23,8 @@ PIPELINE_EXPORTS = ("blu_build_consensus_identities", "blu_free_text", "blu_cust
                     "blu_build_consensus_identities_to_file", "blu_ingest_columns_on", "blu_ingest_columns_free",
                     "blu_taxdb_build", "blu_seqdb_export", "blu_qiime_taxonomy_tsv", "blu_build_consensus_identities_report",
                     "blu_build_consensus_identities_tables", "blu_build_consensus_identities_filtered",
-                    "blu_ingest_columns_filtered_on", "blu_build_consensus_identities_support")
+                    "blu_ingest_columns_filtered_on", "blu_build_consensus_identities_support",
+                    "blu_build_consensus_identities_taxa", "blu_ingest_columns_taxa_on")
 
 BLU_UNMATCHED_TAXID = 0xFFFFFFFF
 BLU_NONE_U8, BLU_NONE_U16, BLU_MAR_NEVER_EQUAL = 0xFF, 0xFFFF, 0xFFFE

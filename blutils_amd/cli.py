@@ -46,6 +46,19 @@ sums and `confidence` = support / hits.  Counted on the GPU from the run's own r
 and written after the document, the report and the sample table; it combines with those flags and with the hit filters
 (the counts are then over the kept lines).  The document stays what it is without the flag.
 
+    python -m blutils_amd.cli blastn build-consensus ... [--exclude-taxon EL]... [--only-taxon EL]...
+        [--exclude-taxon-file FILE] [--only-taxon-file FILE]
+    python -m blutils_amd.cli blastn run-with-consensus ... (the same four)
+
+not in the reference: taxon filters.  EL is an element as the lineages of the run spell it, `RANK__IDENTIFIER`
+(`s__uncultured-bacterium`, `species__x` for `s__x`, `s__1423` under -u); an identifier ending in `*` is a prefix pattern
+(`s__uncultured-*`).  A line of the table takes part only if the lineage of its subject holds no --exclude-taxon element and,
+when --only-taxon is given, at least one of those; lines whose subject is not in the taxonomies file have no elements.  The
+flags repeat; the FILE forms hold one element per line (blank lines and `#` comments skipped).  An element that names no taxon
+of the taxonomies file is an error.  The verdict is taken by the parser, on the GPU where it parses, before the hit filters,
+and the run gives what it gives on a copy of the table without the dropped lines.  To stderr:
+`taxon filter: excluded X, not in --only-taxon Y, of N lines`, then `  EL: count` per exclude element that dropped lines.
+
     python -m blutils_amd.cli cache-db TAX.json CACHE [-u]
 
 writes the binary cache of a taxonomies file (not in the reference CLI; pass CACHE as -t afterwards).  
@@ -75,7 +88,7 @@ import functools
 import os
 import sys
 
-from . import blast, pipeline, report, seqdb, tabular, taxdb
+from . import _native, blast, pipeline, report, seqdb, tabular, taxdb
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -136,6 +149,18 @@ def build_parser() -> argparse.ArgumentParser:
                          help="keep lines with e_value (column 12) <= E (not in the reference CLI)")
         flt.add_argument("--min-bit-score", type=_threshold, metavar="B",
                          help="keep lines with bit_score (column 13) as written >= B (not in the reference CLI)")
+        tfl = sp.add_argument_group("taxon filters (not in the reference CLI)",
+                                    "a line of the table takes part only if its subject's lineage passes; elements are "
+                                    "RANK__IDENTIFIER as the lineages spell them, a trailing * makes a prefix pattern; "
+                                    "applied by the parser, on the GPU where it parses")
+        tfl.add_argument("--exclude-taxon", action="append", default=[], metavar="EL",
+                         help="drop lines whose lineage holds EL; repeatable (not in the reference CLI)")
+        tfl.add_argument("--only-taxon", action="append", default=[], metavar="EL",
+                         help="keep only lines whose lineage holds one of these; repeatable (not in the reference CLI)")
+        tfl.add_argument("--exclude-taxon-file", metavar="FILE",
+                         help="--exclude-taxon elements, one per line; blank lines and # comments skipped")
+        tfl.add_argument("--only-taxon-file", metavar="FILE",
+                         help="--only-taxon elements, one per line; blank lines and # comments skipped")
     br = blastn.add_parser("build-report", help="blutils result document -> taxon abundance report (not in the reference)")
     br.add_argument("blu_result", nargs="?", default="-")
     br.add_argument("-o", "--output-file")
@@ -214,8 +239,36 @@ def _hit_filter(args):
     return f if f.active() else None
 
 
-def _say_kept(stats) -> None:
-    if stats and "n_kept" in stats:
+def _elements_file(path):
+    """one element per line; blank lines and `#` comments skipped"""
+    try:
+        with open(path) as f:
+            lines = [l.strip() for l in f]
+    except OSError as e:
+        raise SystemExit(f"cannot read {path}: {e.strerror}")
+    return [l for l in lines if l and not l.startswith("#")]
+
+
+def _taxon_filter(args):
+    """the four flags -> pipeline.TaxonFilter (flag elements first, then the file's), or None when none was given"""
+    exclude, only = list(args.exclude_taxon), list(args.only_taxon)
+    if args.exclude_taxon_file:
+        exclude += _elements_file(args.exclude_taxon_file)
+    if args.only_taxon_file:
+        only += _elements_file(args.only_taxon_file)
+    f = pipeline.TaxonFilter(tuple(exclude), tuple(only))
+    return f if f.active() else None
+
+
+def _say_kept(stats, hit_filter=True) -> None:
+    t = stats.get("taxon_filter") if stats else None
+    if t:
+        print(f"taxon filter: excluded {t['n_excluded']}, not in --only-taxon {t['n_not_only']}, of {t['n_lines']} lines",
+              file=sys.stderr)
+        for el, count in zip(t["exclude"], t["excluded_by"]):
+            if count:
+                print(f"  {el}: {count}", file=sys.stderr)
+    if hit_filter and stats and "n_kept" in stats:
         print(f"hit filter: kept {stats['n_kept']} of {stats['n_lines']} lines", file=sys.stderr)
 
 
@@ -261,16 +314,22 @@ def _run_with_consensus(args) -> int:
     elif args.taxon == "custom":
         raise SystemExit("Custom taxon values are required when the custom taxon option is selected.")
     stats = {}
+    hit_filter, taxon_filter = _hit_filter(args), _taxon_filter(args)
     try:
         blast.run_blast_and_build_consensus(args.query, args.tax_file, args.blast_out_file, args.blutils_out_file, config,
                                             blast.ExecuteBlastnProcRepository(args.blastn), args.force_overwrite,
                                             args.threads, args.strategy, args.use_taxid, args.out_format, custom,
                                             device=args.device, report_path=args.report, report_weight=args.report_weight,
-                                            sample_table_path=args.sample_table, hit_filter=_hit_filter(args),
-                                            filter_stats=stats, support_table_path=args.support_table)
+                                            sample_table_path=args.sample_table, hit_filter=hit_filter,
+                                            filter_stats=stats, support_table_path=args.support_table,
+                                            taxon_filter=taxon_filter)
     except blast.BlastError as e:
         raise SystemExit(str(e))
-    _say_kept(stats)
+    except _native.BluError as e:
+        if taxon_filter is None:
+            raise
+        raise SystemExit(str(e))                                                       # (an unknown element: the library's message)
+    _say_kept(stats, hit_filter is not None)
     return 0
 
 
@@ -307,6 +366,9 @@ def main(argv=None) -> int:
     build = pipeline.build_consensus_identities
     hit_filter = _hit_filter(args)
     extra = {"hit_filter": hit_filter} if hit_filter is not None else {}
+    taxon_filter = _taxon_filter(args)
+    if taxon_filter is not None:
+        extra["taxon_filter"] = taxon_filter
     if args.support_table is not None:
         build = functools.partial(pipeline.build_consensus_identities_with_tables, report_path=args.report,
                                   sample_table_path=args.sample_table, report_weight=args.report_weight,
@@ -317,18 +379,23 @@ def main(argv=None) -> int:
     elif args.report is not None:
         build = functools.partial(pipeline.build_consensus_identities_with_report, report_path=args.report,
                                   report_weight=args.report_weight)
-    if to_file:
-        path = os.path.splitext(args.blutils_out_file)[0] + "." + args.out_format      # PathBuf::set_extension
-        parent = os.path.dirname(path)
-        if parent and not os.path.exists(parent):
-            os.makedirs(parent)
-        _, stats = build(args.blast_out, args.tax_file, args.taxon, args.strategy, args.use_taxid, custom, headers=None,
-                         out_format=fmt, device=args.device, parse=False, out_path=path, **extra)
-    else:
-        text, stats = build(args.blast_out, args.tax_file, args.taxon, args.strategy, args.use_taxid, custom, headers=None,
-                            out_format=fmt, device=args.device, parse=False, **extra)
-        sys.stdout.write(text)
-    _say_kept(stats)
+    try:
+        if to_file:
+            path = os.path.splitext(args.blutils_out_file)[0] + "." + args.out_format      # PathBuf::set_extension
+            parent = os.path.dirname(path)
+            if parent and not os.path.exists(parent):
+                os.makedirs(parent)
+            _, stats = build(args.blast_out, args.tax_file, args.taxon, args.strategy, args.use_taxid, custom, headers=None,
+                             out_format=fmt, device=args.device, parse=False, out_path=path, **extra)
+        else:
+            text, stats = build(args.blast_out, args.tax_file, args.taxon, args.strategy, args.use_taxid, custom, headers=None,
+                                out_format=fmt, device=args.device, parse=False, **extra)
+            sys.stdout.write(text)
+    except _native.BluError as e:
+        if taxon_filter is None:
+            raise
+        raise SystemExit(str(e))                                                       # (an unknown element: the library's message)
+    _say_kept(stats, hit_filter is not None)
     return 0
 
 

@@ -95,7 +95,7 @@ struct HitTable {
     uint64_t unmatched = 0;
     uint64_t n_hits = 0;                         // rows of the table (the host columns may be absent, see below)
     uint64_t n_queries = 0;                      // = query_names.size() once the strings are there (wait_strings())
-    uint64_t n_lines = 0, n_kept = 0;            // under a hit filter: non-empty lines read, lines kept
+    uint64_t n_lines = 0, n_kept = 0;            // under a hit or taxon filter: non-empty lines read, lines kept
     bool host_columns = true;                    // false: the GPU ingest was asked to leave the columns on the device only
     std::unique_ptr<DeviceHits> dev;             // set by the GPU ingest
     // The GPU ingest returns as soon as the device columns are complete; query_names and accessions are still being
@@ -128,6 +128,18 @@ struct TopTable {
 };
 
 
+// Taxon filter as the parsers read it: one code per taxonomy row, made on the host from the lineages
+// (pipeline.cpp: taxon_codes).  0 = the row passes; k = the first exclude element in list order its lineage holds is k - 1;
+// TAXON_NOT_ONLY = it holds none of the only list (exclude wins over only).  The parser that ran leaves the counts here.
+constexpr uint16_t TAXON_NOT_ONLY = 0xFFFF;
+struct TaxonCodes {
+    std::vector<uint16_t> code;                  // [n_tax]
+    uint16_t unmatched = 0;                      // a line whose taxid is not in the taxonomy: 0, or TAXON_NOT_ONLY under an only list
+    uint32_t n_exclude = 0;
+    uint64_t n_excluded = 0, n_not_only = 0;     // lines, whatever the thresholds say
+    std::vector<uint64_t> excluded_by;           // [n_exclude]
+};
+
 #define BLU_INGEST_FALLBACK (-100)   // load_hits_gpu: the file is not in the plain form the GPU parser handles; use the CPU path
 
 // outfmt-6 text -> grouped SoA columns on the GPU (ingest_gpu.hip).  Same result as the CPU ingest, bit for bit, for
@@ -138,8 +150,10 @@ struct TopTable {
 // fd: the table, open for reading (the text is read with pread straight into pinned staging buffers).
 // flt: a hit filter with a non-empty mask, or null: the rows that fail it are dropped between the parse and
 // the dictionaries, so that everything after sees the kept lines only; ht.n_lines / ht.n_kept are set.
+// taxa: a taxon filter's codes, or null: the parse takes each line's verdict from its row's code before the
+// thresholds, and the counts are left in *taxa.  Rows are dropped as under flt; either may be given without the other.
 int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, std::string* why,
-                  const blu_hit_filter* flt = nullptr);
+                  const blu_hit_filter* flt = nullptr, TaxonCodes* taxa = nullptr);
 // an f64 field as the host parser types it (pipeline.cpp: parse_f64 — strtod's value); false: not a number.  The GPU ingest
 // decides with it the e-values its own arithmetic leaves open.
 bool parse_f64_field(const char* p, size_t n, double* out);

@@ -403,6 +403,40 @@ __device__ __forceinline__ void filter_row(const DevFilter& f, uint32_t i, doubl
     if (k == KEEP_ASK_HOST && (ask & ((1ull << lane) - 1ull)) == 0) atomicAdd(&f.counts[FCNT_SPREAD], (unsigned long long)__popcll(ask));
 }
 
+// ---- taxon filter.  The host made one 16-bit code per taxonomy row from the lineages (ingest.h: TaxonCodes);
+// the third build of the parse kernels reads the code of the row a line joined to — 2 bytes beside the 16-byte map entry the
+// join just read — and takes the line's verdict from it before the thresholds: a failing line's keep word is 0 at once and
+// its e-value is never looked at.
+struct DevTaxa {
+    const uint16_t* code;                  // [n_tax]
+    uint32_t n_tax;
+    uint32_t unmatched;                    // the verdict of a line whose taxid is not in the taxonomy
+    unsigned long long* excluded_by;       // [n_exclude] lines whose first matching exclude element it is
+    unsigned long long* not_only;          // [FCNT_SPREAD] lines failing only the only list (spread over blocks)
+};
+struct DevFilterTaxa { DevFilter f; DevTaxa t; };
+
+// The counts are per wave, not per line.  Excluded lanes: the code of the first one left is broadcast, the lanes that share it
+// are found with one ballot, one lane adds their number to that element's count, and they retire — one round per distinct
+// code in the wave (one or two as a rule, since neighbouring lines hit neighbouring taxa), so an element that removes most
+// of a table costs one atomic per wave.  `left` is the same in every lane: the loop is uniform over the wave's active lanes.
+__device__ __forceinline__ uint32_t taxon_verdict(const DevTaxa& t, uint32_t row) {
+    const uint32_t code = row < t.n_tax ? (uint32_t)t.code[row] : t.unmatched;   // (BLU_UNMATCHED_TAXID is no row)
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool excl = code != 0 && code != TAXON_NOT_ONLY;
+    unsigned long long left = __ballot(excl);
+    while (left) {
+        const int first = __builtin_amdgcn_readfirstlane(__ffsll(left) - 1);
+        const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)code, first);
+        const unsigned long long same = __ballot(excl && code == c);
+        if (lane == (uint32_t)first) atomicAdd(&t.excluded_by[c - 1], (unsigned long long)__popcll(same));
+        left &= ~same;
+    }
+    const unsigned long long no = __ballot(code == TAXON_NOT_ONLY);
+    if (code == TAXON_NOT_ONLY && (no & ((1ull << lane) - 1ull)) == 0) atomicAdd(&t.not_only[blockIdx.x % FCNT_SPREAD], (unsigned long long)__popcll(no));
+    return code;
+}
+
 __device__ __forceinline__ unsigned long long hash_step(unsigned long long h, uint32_t c) { return (h ^ c) * 1099511628211ull; }
 __device__ __forceinline__ unsigned long long hash_finish(unsigned long long h, uint32_t len) {
     h ^= (unsigned long long)len * 0x9E3779B97F4A7C15ull;
@@ -420,12 +454,15 @@ struct RowOut {
 // takes any line length.  parse_rows uses it for the blocks whose 256 lines do not fit its LDS stage.
 // FILTER: also reads column 11 when the e-value threshold is on, leaves the line's keep word (filter_row) and does not count
 // unmatched rows (they are counted over the kept rows, after the compaction).
-// Built twice behind two functions of their own: parse_row_general (FILTER = false: the function of every unfiltered call,
-// its signature as it was) and parse_row_general_filtered.
-template <bool FILTER>
+// Built three times behind functions of their own: parse_row_general (MODE = PARSE_PLAIN: the function of every unfiltered
+// call, its signature as it was), parse_row_general_filtered (PARSE_FILTER) and parse_row_general_taxa (PARSE_TAXA: flt is the
+// DevFilter of a DevFilterTaxa; the taxon verdict first, then the thresholds if any).
+enum : int { PARSE_PLAIN = 0, PARSE_FILTER = 1, PARSE_TAXA = 2 };
+template <int MODE>
 __device__ __forceinline__ void parse_row_general_body(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
                                                        const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
                                                        unsigned long long* __restrict__ n_unmatched, const DevFilter* flt) {
+    constexpr bool FILTER = MODE != PARSE_PLAIN;
     const uint64_t p = line_start[i];
     uint64_t e = line_start[i + 1] - 1;                 // the newline (or one past the end of a last line without one)
     if (e > p && text[e - 1] == '\r') --e;
@@ -480,19 +517,27 @@ __device__ __forceinline__ void parse_row_general_body(const unsigned char* __re
     if (!(bs_t >= -2147483648.0 && bs_t <= 2147483647.0) || !(v_aln >= -2147483648.0 && v_aln <= 2147483647.0) ||
         !(v_tax >= -9.2e18 && v_tax <= 9.2e18)) { atomicOr(flags, FB_RANGE); return; }
     const uint32_t row = taxid_lookup(taxmap, (long long)v_tax);   // left join (mod.rs:72-76)
-    if constexpr (FILTER) filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
+    if constexpr (MODE == PARSE_TAXA) {
+        if (taxon_verdict(reinterpret_cast<const DevFilterTaxa*>(flt)->t, row)) flt->keep[i] = KEEP_NO;
+        else filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
+    } else if constexpr (FILTER) filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
     else if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull);
     o.tax[i] = row; o.pid[i] = v_pid; o.aln[i] = (int32_t)v_aln; o.bs[i] = (int32_t)bs_t;
 }
 __device__ __noinline__ void parse_row_general(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
                                                const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
                                                unsigned long long* __restrict__ n_unmatched) {
-    parse_row_general_body<false>(text, line_start, i, taxmap, o, flags, n_unmatched, nullptr);
+    parse_row_general_body<PARSE_PLAIN>(text, line_start, i, taxmap, o, flags, n_unmatched, nullptr);
 }
 __device__ __noinline__ void parse_row_general_filtered(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
                                                         const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
                                                         const DevFilter* __restrict__ flt) {
-    parse_row_general_body<true>(text, line_start, i, taxmap, o, flags, nullptr, flt);
+    parse_row_general_body<PARSE_FILTER>(text, line_start, i, taxmap, o, flags, nullptr, flt);
+}
+__device__ __noinline__ void parse_row_general_taxa(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
+                                                    const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
+                                                    const DevFilter* __restrict__ flt) {
+    parse_row_general_body<PARSE_TAXA>(text, line_start, i, taxmap, o, flags, nullptr, flt);
 }
 
 // The parse kernel proper: a block takes 256 consecutive lines, whose text is one contiguous span of the file (17 KB for
@@ -507,13 +552,15 @@ constexpr uint32_t STAGE_BYTES = 32768;
 constexpr int PARSE_THREADS = 256;
 
 //
-// The body is built twice: parse_rows (FILTER = false: the kernel of every unfiltered call, flt unused) and
-// parse_rows_filtered (FILTER = true: column 11 read when its threshold is on, the predicate evaluated on the parsed values,
-// one keep word per line — filter_row; unmatched rows are counted after the compaction instead).
-template <bool FILTER>
+// The body is built three times: parse_rows (PARSE_PLAIN: the kernel of every unfiltered call, flt unused),
+// parse_rows_filtered (PARSE_FILTER: column 11 read when its threshold is on, the predicate evaluated on the parsed values,
+// one keep word per line — filter_row; unmatched rows are counted after the compaction instead) and parse_rows_taxa
+// (PARSE_TAXA: as filtered, with the taxon verdict — taxon_verdict — taken first; the thresholds may all be off).
+template <int MODE>
 __device__ __forceinline__ void parse_rows_body(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t n_rows,
                                                 const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
                                                 unsigned long long* __restrict__ n_unmatched, const DevFilter* flt) {
+    constexpr bool FILTER = MODE != PARSE_PLAIN;
     __shared__ uint4 stage16[STAGE_BYTES / 16];
     __shared__ uint16_t tab_at[13 * PARSE_THREADS];                  // [column][thread]: position of the tab that ends the column
     const uint32_t r0 = blockIdx.x * PARSE_THREADS, r1 = min(r0 + (uint32_t)PARSE_THREADS, n_rows), i = r0 + threadIdx.x;
@@ -523,7 +570,8 @@ __device__ __forceinline__ void parse_rows_body(const unsigned char* __restrict_
     const uint64_t s0 = ls0 & ~15ull;
     if (s1 - s0 > STAGE_BYTES) {                                     // uniform over the block
         if (i < r1) {
-            if constexpr (FILTER) parse_row_general_filtered(text, line_start, i, taxmap, o, flags, flt);
+            if constexpr (MODE == PARSE_TAXA) parse_row_general_taxa(text, line_start, i, taxmap, o, flags, flt);
+            else if constexpr (FILTER) parse_row_general_filtered(text, line_start, i, taxmap, o, flags, flt);
             else parse_row_general(text, line_start, i, taxmap, o, flags, n_unmatched);
         }
         return;
@@ -601,7 +649,10 @@ __device__ __forceinline__ void parse_rows_body(const unsigned char* __restrict_
     if (!(bs_t >= -2147483648.0 && bs_t <= 2147483647.0) || !(v_aln >= -2147483648.0 && v_aln <= 2147483647.0) ||
         !(v_tax >= -9.2e18 && v_tax <= 9.2e18)) { atomicOr(flags, FB_RANGE); return; }
     const uint32_t row = taxid_lookup(taxmap, (long long)v_tax);   // left join (mod.rs:72-76)
-    if constexpr (FILTER) filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
+    if constexpr (MODE == PARSE_TAXA) {
+        if (taxon_verdict(reinterpret_cast<const DevFilterTaxa*>(flt)->t, row)) flt->keep[i] = KEEP_NO;
+        else filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
+    } else if constexpr (FILTER) filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
     else if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull);
     o.qh[i] = qh; o.qpos[i] = (s0 + p) | ((unsigned long long)(t0 - p) << 44);
     o.ah[i] = ah; o.apos[i] = (s0 + t0 + 1) | ((unsigned long long)(t1 - t0 - 1) << 44);
@@ -611,12 +662,17 @@ __device__ __forceinline__ void parse_rows_body(const unsigned char* __restrict_
 __global__ __launch_bounds__(PARSE_THREADS) void parse_rows(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t n_rows,
                                                             DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
                                                             unsigned long long* __restrict__ n_unmatched) {
-    parse_rows_body<false>(text, line_start, n_rows, taxmap, o, flags, n_unmatched, nullptr);
+    parse_rows_body<PARSE_PLAIN>(text, line_start, n_rows, taxmap, o, flags, n_unmatched, nullptr);
 }
 __global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_filtered(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
                                                                      uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
                                                                      const DevFilter* __restrict__ flt) {   // (in device memory: read with scalar loads)
-    parse_rows_body<true>(text, line_start, n_rows, taxmap, o, flags, nullptr, flt);
+    parse_rows_body<PARSE_FILTER>(text, line_start, n_rows, taxmap, o, flags, nullptr, flt);
+}
+__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_taxa(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
+                                                                 uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
+                                                                 const DevFilterTaxa* __restrict__ flt) {   // (in device memory, as the filter alone is)
+    parse_rows_body<PARSE_TAXA>(text, line_start, n_rows, taxmap, o, flags, nullptr, &flt->f);
 }
 
 // ---- 2b. hit filter: the e-values left to the host, and the stable compaction of the parsed rows ---------------------------
@@ -1067,7 +1123,7 @@ DevFilter device_filter(const blu_hit_filter& f) {
 
 // load_hits_gpu's work on the device, in the arena the caller frees; any failure returns at once
 int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, DeviceArena& mem,
-                     IngestTrace& lap, const blu_hit_filter* flt) {
+                     IngestTrace& lap, const blu_hit_filter* flt, TaxonCodes* taxa) {
     HipPolicy& pol = mem.pol;
     auto fallback = [&](const char* reason) { *pol.why = reason; return BLU_INGEST_FALLBACK; };
     unsigned char* d_text = nullptr;
@@ -1134,8 +1190,10 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
     lap("upload text");
     HIP_CHECK(pol, mem.alloc(&d_tile, (n_tiles + 1) * 4, "line index"));
     HIP_CHECK(pol, mem.alloc(&d_tile_base, (n_tiles + 1) * 4, "line index"));
-    // {flags, -, -, -, counter, -, -, -, big counters}; under a hit filter the kept / undecided counts follow
-    const size_t flag_bytes = flt ? 64 + (FCNT_SPREAD + 1) * 8 : 64;
+    // {flags, -, -, -, counter, -, -, -, big counters}; under a hit filter the kept / undecided counts follow, and under a taxon
+    // filter the not-only counts and one count per exclude element after them: all of it comes back in one copy
+    const size_t n_back = 8 + FCNT_SPREAD + 1 + (taxa ? FCNT_SPREAD + (size_t)taxa->n_exclude : 0);
+    const size_t flag_bytes = flt || taxa ? n_back * 8 : 64;
     HIP_CHECK(pol, mem.alloc(&d_flags, flag_bytes, "flags"));
     HIP_CHECK(pol, hipMemset(d_flags, 0, flag_bytes));
     d_counter = d_flags + 4;                                         // {flags, -, -, -, counter, -, big counters at +8}
@@ -1160,7 +1218,7 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
     HIP_CHECK(pol, mem.alloc(&d_qpos, (size_t)n_rows * 8, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_apos, (size_t)n_rows * 8, "parsed rows"));
     HIP_CHECK(pol, mem.alloc(&d_tax, (size_t)n_rows * 4, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_pid, (size_t)n_rows * 8, "parsed rows"));
     HIP_CHECK(pol, mem.alloc(&d_aln, (size_t)n_rows * 4, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_bs, (size_t)n_rows * 4, "parsed rows"));
-    if (!flt) {
+    if (!flt && !taxa) {
         RowOut o{d_qh, d_ah, d_qpos, d_apos, d_tax, d_pid, d_aln, d_bs};
         DevTaxidMap tm{d_taxmap, row_of.tab.size() - 1};
         hipLaunchKernelGGL(parse_rows, grid(n_rows, PARSE_THREADS), dim3(PARSE_THREADS), 0, 0, d_text, d_line, n_rows, tm, o, d_flags, d_big);
@@ -1170,24 +1228,45 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
         // ---- hit filter: the filtered parse leaves a keep word per line; the kept and undecided counts come
         // back with the flags; the rows are compacted in file order before anything else sees them
         uint32_t *d_keep = nullptr, *d_kpos = nullptr;
-        DevFilter* d_filter = nullptr;
+        DevFilterTaxa* d_filter = nullptr;                           // (its first member is the DevFilter parse_rows_filtered reads)
+        uint16_t* d_code = nullptr;
         HIP_CHECK(pol, mem.alloc(&d_keep, (size_t)n_rows * 4, "keep words"));
-        HIP_CHECK(pol, mem.alloc(&d_filter, sizeof(DevFilter), "hit filter"));
+        HIP_CHECK(pol, mem.alloc(&d_filter, sizeof(DevFilterTaxa), "hit filter"));
         unsigned long long* const d_fcnt = reinterpret_cast<unsigned long long*>(d_flags + 16);
-        DevFilter hf = device_filter(*flt);
-        hf.keep = d_keep; hf.counts = d_fcnt;
-        HIP_CHECK(pol, hipMemcpy(d_filter, &hf, sizeof hf, hipMemcpyHostToDevice));
+        DevFilterTaxa hf{};
+        if (flt) hf.f = device_filter(*flt);                         // (no threshold beside a taxon filter: an empty mask keeps every line)
+        hf.f.keep = d_keep; hf.f.counts = d_fcnt;
         RowOut o{d_qh, d_ah, d_qpos, d_apos, d_tax, d_pid, d_aln, d_bs};
         DevTaxidMap tm{d_taxmap, row_of.tab.size() - 1};
-        hipLaunchKernelGGL(parse_rows_filtered, grid(n_rows, PARSE_THREADS), dim3(PARSE_THREADS), 0, 0, d_text, d_line, n_rows, tm, o, d_flags,
-                           (const DevFilter*)d_filter);
-        unsigned long long back[8 + FCNT_SPREAD + 1];
-        HIP_CHECK(pol, hipMemcpy(back, d_flags, sizeof back, hipMemcpyDeviceToHost));
+        std::vector<unsigned long long> back(n_back);
+        if (!taxa) {
+            HIP_CHECK(pol, hipMemcpy(d_filter, &hf.f, sizeof hf.f, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(parse_rows_filtered, grid(n_rows, PARSE_THREADS), dim3(PARSE_THREADS), 0, 0, d_text, d_line, n_rows, tm, o, d_flags,
+                               (const DevFilter*)&d_filter->f);
+        } else {
+            // ---- taxon filter: the row codes go up next to the taxid map; the verdict is taken in the parse
+            const size_t n_tax = taxa->code.size();
+            HIP_CHECK(pol, mem.alloc(&d_code, std::max<size_t>(n_tax, 1) * 2, "taxon codes"));
+            if (n_tax) { HIP_CHECK(pol, hipMemcpy(d_code, taxa->code.data(), n_tax * 2, hipMemcpyHostToDevice)); }
+            hf.t.code = d_code; hf.t.n_tax = (uint32_t)n_tax; hf.t.unmatched = taxa->unmatched;
+            hf.t.not_only = d_fcnt + FCNT_SPREAD + 1; hf.t.excluded_by = hf.t.not_only + FCNT_SPREAD;
+            HIP_CHECK(pol, hipMemcpy(d_filter, &hf, sizeof hf, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(parse_rows_taxa, grid(n_rows, PARSE_THREADS), dim3(PARSE_THREADS), 0, 0, d_text, d_line, n_rows, tm, o, d_flags,
+                               (const DevFilterTaxa*)d_filter);
+        }
+        HIP_CHECK(pol, hipMemcpy(back.data(), d_flags, n_back * 8, hipMemcpyDeviceToHost));
         h_flags = (uint32_t)back[0];
         if (h_flags) return fallback(fallback_text(h_flags));
         uint64_t n_kept = 0;
         for (uint32_t k = 0; k < FCNT_SPREAD; ++k) n_kept += back[8 + k];
         const uint64_t n_ask = back[8 + FCNT_SPREAD];
+        uint64_t n_excluded = 0, n_not_only = 0;
+        if (taxa) {
+            const unsigned long long* tb = back.data() + 8 + FCNT_SPREAD + 1;
+            for (uint32_t k = 0; k < FCNT_SPREAD; ++k) n_not_only += tb[k];
+            for (uint32_t k = 0; k < taxa->n_exclude; ++k) n_excluded += tb[FCNT_SPREAD + k];
+            if (n_excluded + n_not_only + n_kept + n_ask > n_rows) return fallback("inconsistent taxon-filter counts");
+        }
         lap("parse (filtered)");
         if (n_ask) {
             // e-values the device left open (as a rule: fields spelled like the threshold): the host decides them from the
@@ -1209,7 +1288,7 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
             for (uint32_t k = 0; k < n_u; ++k) {
                 double v = 0;
                 if (!parse_f64_field(e_bytes.data() + e_off[k], (size_t)(e_off[k + 1] - e_off[k]), &v)) return fallback("an e-value the host parser reads differently");
-                dec[k] = v <= flt->max_e_value ? 1u : 0u;
+                dec[k] = flt && v <= flt->max_e_value ? 1u : 0u;
                 n_kept += dec[k];
             }
             HIP_CHECK(pol, hipMemcpy(d_udec, dec.data(), (size_t)n_u * 4, hipMemcpyHostToDevice));
@@ -1219,7 +1298,7 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
         }
         if (n_kept > n_rows) return fallback("inconsistent hit-filter counts");
         const uint64_t n_lines = n_rows;
-        if (n_kept == 0) return fallback("no rows kept by the hit filter");   // (the host parser returns the empty table)
+        if (n_kept == 0) return fallback("no rows kept by the filters");   // (the host parser returns the empty table)
         if (n_kept < n_rows) {
             // stable compaction, one column after another through ONE spare buffer: a column is scattered into the spare, the
             // spare becomes the column and the column's old buffer the next spare (8-byte columns first, so that every spare
@@ -1252,9 +1331,15 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
             lap("  filter: compaction");
         }
         mem.free(d_keep); mem.free(d_filter);
+        if (d_code) mem.free(d_code);
         mem.free(d_line); d_line = nullptr;
         hipLaunchKernelGGL(count_unmatched, grid(n_rows, 1024), dim3(1024), 0, 0, (const uint32_t*)d_tax, n_rows, d_big);
         ht.n_lines = n_lines; ht.n_kept = n_kept;
+        if (taxa) {
+            const unsigned long long* tb = back.data() + 8 + FCNT_SPREAD + 1 + FCNT_SPREAD;
+            taxa->n_excluded = n_excluded; taxa->n_not_only = n_not_only;
+            taxa->excluded_by.assign(tb, tb + taxa->n_exclude);
+        }
     }
     lap("parse");
 
@@ -1493,7 +1578,7 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
 }  // namespace
 
 int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, std::string* why,
-                  const blu_hit_filter* flt) {
+                  const blu_hit_filter* flt, TaxonCodes* taxa) {
     if (flt && !(flt->mask & 15u)) flt = nullptr;
     IngestTrace lap;
     std::string why_unread;
@@ -1512,7 +1597,7 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
         }
         mem.keep = (double)size * 4.0 + (4ull << 30) < (double)free_b;
     }
-    const int rc = ingest_on_device(fd, size, row_of, device, host_columns, ht, mem, lap, flt);
+    const int rc = ingest_on_device(fd, size, row_of, device, host_columns, ht, mem, lap, flt, taxa);
     if (rc != BLU_OK) ht.clear();
     lap("hand-over");
     // with room on the card (mem.keep) the work buffers — the text, the hashes, the dictionaries: 10 GB for a 2 M-query table —

@@ -540,7 +540,9 @@ struct Chunk {
     std::vector<uint64_t> at;                // local query -> next row slot in the grouped table
     std::vector<std::string_view> acc_sorted;
     uint64_t unmatched = 0, first_line = 0, n_lines = 0;
-    uint64_t n_data_lines = 0, n_kept = 0;   // under a hit filter: non-empty lines, lines kept
+    uint64_t n_data_lines = 0, n_kept = 0;   // under a hit or taxon filter: non-empty lines, lines kept
+    uint64_t n_not_only = 0;                 // under a taxon filter: lines failing only the only list, and per exclude element
+    std::vector<uint64_t> excluded_by;       // the lines whose first matching element it is
     int rc = BLU_OK;
     std::string err;
     std::string_view clean(std::string_view v) {   // mod.rs:169-172 `.replace("\"", "")`
@@ -560,7 +562,8 @@ inline bool filter_keeps(const blu_hit_filter& f, double pid, int64_t aln, doubl
     return true;
 }
 
-void parse_chunk(Chunk& c, const Db& db, const char* path, const blu_hit_filter* flt = nullptr) {
+void parse_chunk(Chunk& c, const Db& db, const char* path, const blu_hit_filter* flt = nullptr, const TaxonCodes* taxa = nullptr) {
+    if (taxa) c.excluded_by.assign(taxa->n_exclude, 0);
     const char* p = c.begin;
     uint64_t line_no = 0;
     c.rows.reserve((size_t)(c.end - c.begin) / 96 + 16);
@@ -603,15 +606,24 @@ void parse_chunk(Chunk& c, const Db& db, const char* path, const blu_hit_filter*
                          (unsigned long long)line_no, (unsigned long long)c.first_line, path);
                 c.rc = BLU_ERR_PARSE; c.err = msg; return;
             }
-            if (flt) {                                        // (validated like every line; dropped before it reaches a dictionary)
+            if (flt || taxa) {                                // (validated like every line; dropped before it reaches a dictionary)
                 double ev = 0;
-                if ((flt->mask & BLU_FILTER_MAX_E_VALUE) && !parse_f64(col[11], &ev)) {
+                if (flt && (flt->mask & BLU_FILTER_MAX_E_VALUE) && !parse_f64(col[11], &ev)) {
                     snprintf(msg, sizeof msg, "line %llu(+%llu) of %s: numeric column does not parse (e_value)", (unsigned long long)line_no,
                              (unsigned long long)c.first_line, path);
                     c.rc = BLU_ERR_PARSE; c.err = msg; return;
                 }
                 ++c.n_data_lines;
-                if (!filter_keeps(*flt, pid, aln, ev, bs)) { p = nl ? nl + 1 : c.end; continue; }
+                // the taxon verdict: the code of the row the line joins to, first and whatever the thresholds say.
+                // This is the definition the GPU parser's verdicts are held to.
+                uint16_t code = 0;
+                if (taxa) {
+                    const uint32_t row = db.row_of.find_or(taxid_i, BLU_UNMATCHED_TAXID);
+                    code = row == BLU_UNMATCHED_TAXID ? taxa->unmatched : taxa->code[row];
+                    if (code == TAXON_NOT_ONLY) ++c.n_not_only;
+                    else if (code) ++c.excluded_by[code - 1];
+                }
+                if (code || (flt && !filter_keeps(*flt, pid, aln, ev, bs))) { p = nl ? nl + 1 : c.end; continue; }
                 ++c.n_kept;
             }
             RawRow r;
@@ -652,6 +664,100 @@ void parallel_for(unsigned n, unsigned nthreads, F&& f) {
     for (auto& th : pool) th.join();
 }
 
+// ---- taxon filter (include/blu_pipeline.h: blu_taxon_filter): the two lists -> one code per taxonomy row.
+// An element `RANK__IDENTIFIER` names the node a lineage element of that spelling is interned as (Display(rank), identifier);
+// an identifier ending in '*' is a prefix over the identifiers of that rank.  Only nodes that some lineage holds count (a
+// node met in front of a bad element of a refused lineage is in the dictionary but in no lineage).
+struct TaxonElement { std::string rank, ident; bool prefix = false; };
+
+int parse_taxon_element(const char* text, const char* list, TaxonElement* el) {
+    const std::string s = text ? text : "";
+    const size_t sep = s.find("__");
+    if (sep == std::string::npos || sep == 0 || sep + 2 >= s.size() || s.find("__", sep + 2) != std::string::npos) {
+        set_error("taxon filter: %s element `%s` is not RANK__IDENTIFIER (two non-empty parts around one `__`)", list, s.c_str());
+        return BLU_ERR_INVALID_ARG;
+    }
+    el->rank = canonical_display(s.substr(0, sep));
+    el->ident = s.substr(sep + 2);
+    el->prefix = el->ident.back() == '*';
+    if (el->prefix) el->ident.pop_back();
+    return BLU_OK;
+}
+
+int taxon_codes(const Db& db, const blu_taxon_filter& f, unsigned nthreads, TaxonCodes& tc) {
+    if ((f.n_exclude && !f.exclude) || (f.n_only && !f.only)) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    if (f.n_exclude > BLU_TAXON_FILTER_MAX_EXCLUDE) {
+        set_error("taxon filter: %llu exclude elements, at most %u are taken", (unsigned long long)f.n_exclude, BLU_TAXON_FILTER_MAX_EXCLUDE);
+        return BLU_ERR_INVALID_ARG;
+    }
+    const size_t n_ex = (size_t)f.n_exclude, n_el = n_ex + (size_t)f.n_only, n_nodes = db.node_ident.size(), n_tax = db.taxid.size();
+    // the elements: exact ones by key, patterns by rank; the first of equal spellings stands for all of them
+    std::vector<TaxonElement> els(n_el);
+    std::unordered_map<std::string, std::vector<uint32_t>> exact, patterns;   // key / rank -> element indices (exclude first, list order)
+    for (size_t k = 0; k < n_el; ++k) {
+        const bool ex = k < n_ex;
+        if (int rc = parse_taxon_element(ex ? f.exclude[k] : f.only[k - n_ex], ex ? "exclude" : "only", &els[k]); rc != BLU_OK) return rc;
+        if (els[k].prefix) patterns[els[k].rank].push_back((uint32_t)k);
+        else exact[els[k].rank + '\x1f' + els[k].ident].push_back((uint32_t)k);
+    }
+    std::vector<uint8_t> in_lineage(n_nodes, 0);
+    for (uint32_t node : db.lin_node) in_lineage[node] = 1;
+    // per node: the first exclude element that names it (+ 1), whether an only element names it; per element: named a node?
+    std::vector<uint16_t> node_ex(n_nodes, 0);
+    std::vector<uint8_t> node_only(n_nodes, 0);
+    if (nthreads < 1 || n_nodes + n_tax < (1u << 16)) nthreads = 1;
+    std::vector<std::vector<uint8_t>> found(nthreads, std::vector<uint8_t>(n_el, 0));
+    parallel_for(nthreads, nthreads, [&](unsigned t) {
+        std::string key;
+        auto take = [&](uint32_t node, uint32_t k) {
+            found[t][k] = 1;
+            if (k >= n_ex) node_only[node] = 1;
+            else if (!node_ex[node] || k + 1 < node_ex[node]) node_ex[node] = (uint16_t)(k + 1);
+        };
+        for (size_t node = n_nodes * t / nthreads; node < n_nodes * (t + 1) / nthreads; ++node) {
+            if (!in_lineage[node]) continue;
+            const std::string& rank = db.rank_display[db.node_rank[node]];
+            const std::string& ident = db.node_ident[node];
+            if (!exact.empty()) {
+                key.assign(rank); key.push_back('\x1f'); key += ident;
+                if (auto it = exact.find(key); it != exact.end()) for (uint32_t k : it->second) take((uint32_t)node, k);
+            }
+            if (!patterns.empty())
+                if (auto it = patterns.find(rank); it != patterns.end())
+                    for (uint32_t k : it->second)
+                        if (ident.size() >= els[k].ident.size() && memcmp(ident.data(), els[k].ident.data(), els[k].ident.size()) == 0) take((uint32_t)node, k);
+        }
+    });
+    for (size_t k = 0; k < n_el; ++k) {
+        bool any = false;
+        for (unsigned t = 0; t < nthreads && !any; ++t) any = found[t][k] != 0;
+        if (!any) {
+            set_error("taxon filter: %s element `%s` names no taxon of the taxonomies file", k < n_ex ? "exclude" : "only", k < n_ex ? f.exclude[k] : f.only[k - n_ex]);
+            return BLU_ERR_INVALID_ARG;
+        }
+    }
+    // one pass over the CSR: a row's code from its nodes (a bad row's lineage is empty: no elements)
+    tc.code.assign(n_tax, 0);
+    tc.unmatched = f.n_only ? TAXON_NOT_ONLY : 0;
+    tc.n_exclude = (uint32_t)n_ex;
+    tc.n_excluded = tc.n_not_only = 0;
+    tc.excluded_by.assign(n_ex, 0);
+    const bool has_only = f.n_only != 0;
+    parallel_for(nthreads, nthreads, [&](unsigned t) {
+        for (size_t r = n_tax * t / nthreads; r < n_tax * (t + 1) / nthreads; ++r) {
+            uint16_t ex = 0;
+            bool only = false;
+            for (uint64_t j = db.lin_off[r]; j < db.lin_off[r + 1]; ++j) {
+                const uint32_t node = db.lin_node[j];
+                if (node_ex[node] && (!ex || node_ex[node] < ex)) ex = node_ex[node];
+                only |= node_only[node] != 0;
+            }
+            tc.code[r] = ex ? ex : (has_only && !only ? TAXON_NOT_ONLY : (uint16_t)0);
+        }
+    });
+    return BLU_OK;
+}
+
 // a2 + a4 + a5: outfmt-6 text -> SoA columns.  The file is cut into line-aligned chunks; each worker parses its
 // chunk (numbers, tab scanning, the taxid join) and interns query / accession strings in dictionaries of its own.
 // Afterwards only the DISTINCT strings are merged — queries in file order (first appearance decides a query's
@@ -660,7 +766,8 @@ void parallel_for(unsigned n, unsigned nthreads, F&& f) {
 thread_local double g_t_body_end = 0;   // stage trace: when build_document's last statement ran (what follows is its tear-down)
 thread_local int g_last_ingest_path = 0;   // 0 = CPU parser, 1 = GPU parser (blu_last_ingest_path)
 
-int load_hits(const char* path, const Db& db, HitTable& ht, int device = -1, bool host_columns = true, const blu_hit_filter* flt = nullptr) {
+int load_hits(const char* path, const Db& db, HitTable& ht, int device = -1, bool host_columns = true, const blu_hit_filter* flt = nullptr,
+              TaxonCodes* taxa = nullptr) {
     g_last_ingest_path = 0;
     if (flt && !(flt->mask & 15u)) flt = nullptr;   // no threshold given: today's path
     // GPU parser first (ingest_gpu.hip) when a device is given: same columns bit for bit; files it does not handle
@@ -676,7 +783,7 @@ int load_hits(const char* path, const Db& db, HitTable& ht, int device = -1, boo
         const bool want_gpu = device >= 0 && db.dup_rows.empty() && !(mode && strcmp(mode, "cpu") == 0) && (fsize >= (1u << 20) || (mode && strcmp(mode, "gpu") == 0));
         int rc = BLU_INGEST_FALLBACK;
         std::string why;
-        if (want_gpu) rc = load_hits_gpu(fd, fsize, db.row_of, device, host_columns, ht, &why, flt);
+        if (want_gpu) rc = load_hits_gpu(fd, fsize, db.row_of, device, host_columns, ht, &why, flt, taxa);
         ::close(fd);
         if (want_gpu) {
             if (rc == BLU_OK) { g_last_ingest_path = 1; return BLU_OK; }
@@ -709,16 +816,21 @@ int load_hits(const char* path, const Db& db, HitTable& ht, int device = -1, boo
     const bool trace = getenv("BLU_INGEST_TRACE") != nullptr;
     double tp = now_s();
     auto lap = [&](const char* what) { if (trace) { const double t = now_s(); fprintf(stderr, "[ingest] %-22s %.3f s\n", what, t - tp); tp = t; } };
-    parallel_for(nthreads, nthreads, [&](unsigned t) { parse_chunk(chunks[t], db, path, flt); });
+    parallel_for(nthreads, nthreads, [&](unsigned t) { parse_chunk(chunks[t], db, path, flt, taxa); });
     lap("parse (parallel)");
     uint64_t lines_before = 0;
     size_t nh = 0;
+    if (taxa) { taxa->n_excluded = taxa->n_not_only = 0; taxa->excluded_by.assign(taxa->n_exclude, 0); }
     for (auto& c : chunks) {
         if (c.rc != BLU_OK) { set_error("%s (chunk starting at line %llu)", c.err.c_str(), (unsigned long long)(lines_before + 1)); return c.rc; }
         lines_before += c.n_lines;
         nh += c.rows.size();
         ht.unmatched += c.unmatched;
         ht.n_lines += c.n_data_lines; ht.n_kept += c.n_kept;
+        if (taxa) {
+            taxa->n_not_only += c.n_not_only;
+            for (uint32_t k = 0; k < taxa->n_exclude; ++k) { taxa->excluded_by[k] += c.excluded_by[k]; taxa->n_excluded += c.excluded_by[k]; }
+        }
     }
     if (nh >= 0xFFFFFFFFull) { set_error("more than 2^32 - 2 hit rows in %s", path); return BLU_ERR_INVALID_ARG; }
     // queries: the chunks' distinct names in file order -> global ids, and each chunk's first slot inside every segment
@@ -1481,11 +1593,18 @@ int build_support(const Db& db, const HitTable& ht, const blu_taxonomy* tax, con
 
 // out_path != nullptr: the document is written there (an existing file is replaced, write_blutils_output.rs:57-63) by a
 // writer thread that follows the renderers piece by piece; otherwise the pieces are left in `document`.
+// the taxon filter's counts as the C ABI returns them
+void put_taxon_stats(const TaxonCodes* taxa, uint64_t n_lines, blu_taxon_filter_stats* tst) {
+    if (!tst || !taxa) return;
+    tst->n_lines = n_lines; tst->n_excluded = taxa->n_excluded; tst->n_not_only = taxa->n_not_only;
+    if (tst->excluded_by) for (uint32_t k = 0; k < taxa->n_exclude; ++k) tst->excluded_by[k] = taxa->excluded_by[k];
+}
+
 int build_document(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
                    const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
                    const char* config_text, const char* out_path, Document* document, blu_pipeline_stats* stats,
                    const blu_tables_params* tables = nullptr, const blu_hit_filter* flt = nullptr, blu_hit_filter_stats* fst = nullptr,
-                   const char* support_path = nullptr) {
+                   const char* support_path = nullptr, const blu_taxon_filter* tflt = nullptr, blu_taxon_filter_stats* tst = nullptr) {
     if (!blast_output_file || !taxonomies_file || !params || !document) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     if (flt && (flt->mask & ~15u)) { set_error("hit filter: unknown bits in the mask"); return BLU_ERR_INVALID_ARG; }
     if (tables && ((!tables->report_path && !tables->sample_table_path) ||
@@ -1506,6 +1625,13 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     Db& db = *db_owner;
     int rc = load_db(taxonomies_file, params->use_taxid != 0, db);     // mod.rs:64
     if (rc != BLU_OK) return rc;
+    // (a taxon filter: the lists resolved against the lineages -> one code per row)
+    if (tflt && !tflt->n_exclude && !tflt->n_only) tflt = nullptr;
+    std::unique_ptr<TaxonCodes> taxa;
+    if (tflt) {
+        taxa = std::make_unique<TaxonCodes>();
+        if ((rc = taxon_codes(db, *tflt, nthreads, *taxa)) != BLU_OK) return rc;
+    }
     st.t_load_db_s = now_s() - t0;
     tr.lap("load db");
     // the taxonomy table (sorted lineages, cutoff tables, upload) is built by a second thread while the hits are ingested
@@ -1536,9 +1662,10 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     t0 = now_s();
     auto ht_owner = std::make_unique<HitTable>();
     HitTable& ht = *ht_owner;
-    rc = load_hits(blast_output_file, db, ht, params->device, /*host_columns=*/false, flt);   // mod.rs:54, 72-82
+    rc = load_hits(blast_output_file, db, ht, params->device, /*host_columns=*/false, flt, taxa.get());   // mod.rs:54, 72-82
     if (rc != BLU_OK) return rc;
-    if (fst) { const bool on = flt && (flt->mask & 15u); fst->n_lines = on ? ht.n_lines : ht.n_hits; fst->n_kept = on ? ht.n_kept : ht.n_hits; }
+    if (fst) { const bool on = (flt && (flt->mask & 15u)) || taxa; fst->n_lines = on ? ht.n_lines : ht.n_hits; fst->n_kept = on ? ht.n_kept : ht.n_hits; }
+    put_taxon_stats(taxa.get(), ht.n_lines, tst);
     st.t_load_hits_s = now_s() - t0;
     tr.lap("load hits");
     st.n_hits = ht.n_hits; st.n_queries = ht.n_queries; st.n_taxids = db.taxid.size(); st.n_unmatched_rows = ht.unmatched;
@@ -1844,13 +1971,14 @@ int put_tables(const Document& d, const blu_tables_params* tables, const char* s
 int consensus_to_text(const char* blast_output_file, const char* const* headers, uint64_t n_headers, const char* taxonomies_file,
                       const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const blu_tables_params* tables,
                       char** out_text, size_t* out_len, blu_pipeline_stats* stats, const blu_hit_filter* flt = nullptr,
-                      blu_hit_filter_stats* fst = nullptr, const char* support_path = nullptr) {
+                      blu_hit_filter_stats* fst = nullptr, const char* support_path = nullptr, const blu_taxon_filter* tflt = nullptr,
+                      blu_taxon_filter_stats* tst = nullptr) {
     if (!out_text) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     *out_text = nullptr;
     if (out_len) *out_len = 0;
     Document d;
     int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats, tables, flt, fst, support_path); }
+    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats, tables, flt, fst, support_path, tflt, tst); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }   // (no exception crosses the C ABI)
     if (rc != BLU_OK) return rc;
     if ((rc = put_tables(d, tables, support_path)) != BLU_OK) return rc;
@@ -1871,11 +1999,12 @@ int consensus_to_text(const char* blast_output_file, const char* const* headers,
 int consensus_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers, const char* taxonomies_file,
                       const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const char* out_path,
                       const blu_tables_params* tables, blu_pipeline_stats* stats, const blu_hit_filter* flt = nullptr,
-                      blu_hit_filter_stats* fst = nullptr, const char* support_path = nullptr) {
+                      blu_hit_filter_stats* fst = nullptr, const char* support_path = nullptr, const blu_taxon_filter* tflt = nullptr,
+                      blu_taxon_filter_stats* tst = nullptr) {
     if (!out_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     Document d;
     int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats, tables, flt, fst, support_path); }
+    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats, tables, flt, fst, support_path, tflt, tst); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
     if (rc != BLU_OK) return rc;
     if (getenv("BLU_INGEST_TRACE")) fprintf(stderr, "[pipeline] %-26s %.3f s\n", "tear-down (tables, strings)", now_s() - g_t_body_end);
@@ -1974,6 +2103,29 @@ int blu_build_consensus_identities_support(const char* blast_output_file, const 
                              out_len, stats, filter, filter_stats, support_table_path);
 }
 
+// (the caller's counts start at zero, its excluded_by array included, whatever the call then does)
+static void clear_taxon_stats(const blu_taxon_filter* f, blu_taxon_filter_stats* s) {
+    if (!s) return;
+    s->n_lines = s->n_excluded = s->n_not_only = 0;
+    if (s->excluded_by && f && f->n_exclude <= BLU_TAXON_FILTER_MAX_EXCLUDE) for (uint64_t k = 0; k < f->n_exclude; ++k) s->excluded_by[k] = 0;
+}
+
+int blu_build_consensus_identities_taxa(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                        const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
+                                        const char* config_text, const char* out_path, const blu_tables_params* tables,
+                                        const blu_hit_filter* filter, char** out_text, size_t* out_len,
+                                        blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats, const char* support_table_path,
+                                        const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats) {
+    if (tables && !tables->report_path && !tables->sample_table_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    if (filter_stats) *filter_stats = blu_hit_filter_stats{0, 0};
+    clear_taxon_stats(taxon_filter, taxon_stats);
+    if (out_path)
+        return consensus_to_file(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, tables,
+                                 stats, filter, filter_stats, support_table_path, taxon_filter, taxon_stats);
+    return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, tables, out_text,
+                             out_len, stats, filter, filter_stats, support_table_path, taxon_filter, taxon_stats);
+}
+
 int blu_build_consensus_identities_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
                                            const char* taxonomies_file, const blu_pipeline_params* params,
                                            const char* run_id_text, const char* config_text, const char* out_path,
@@ -2027,20 +2179,36 @@ int blu_ingest_columns_on(const char* blast_output_file, const char* taxonomies_
 
 int blu_ingest_columns_filtered_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
                                    const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats) {
+    return blu_ingest_columns_taxa_on(blast_output_file, taxonomies_file, use_taxid, device, filter, out, filter_stats, nullptr, nullptr);
+}
+
+int blu_ingest_columns_taxa_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                               const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
+                               const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats) {
     if (!blast_output_file || !taxonomies_file || !out) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     if (filter && (filter->mask & ~15u)) { set_error("hit filter: unknown bits in the mask"); return BLU_ERR_INVALID_ARG; }
     if (filter_stats) *filter_stats = blu_hit_filter_stats{0, 0};
+    clear_taxon_stats(taxon_filter, taxon_stats);
     memset(out, 0, sizeof *out);
     Db db;
     int rc = load_db(taxonomies_file, use_taxid != 0, db);
     if (rc != BLU_OK) return rc;
+    if (taxon_filter && !taxon_filter->n_exclude && !taxon_filter->n_only) taxon_filter = nullptr;
+    std::unique_ptr<TaxonCodes> taxa;
+    if (taxon_filter) {
+        taxa = std::make_unique<TaxonCodes>();
+        try { rc = taxon_codes(db, *taxon_filter, worker_threads(), *taxa); }
+        catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
+        if (rc != BLU_OK) return rc;
+    }
     HitTable ht;
-    rc = load_hits(blast_output_file, db, ht, device, true, filter);
+    rc = load_hits(blast_output_file, db, ht, device, true, filter, taxa.get());
     if (rc != BLU_OK) return rc;
+    put_taxon_stats(taxa.get(), ht.n_lines, taxon_stats);
     ht.wait_strings();
     if (!ht.strings_ok) { set_error("out of memory while building the query / accession strings"); return BLU_ERR_ALLOC; }
     const size_t nh = ht.bitscore.size(), nq = ht.query_names.size();
-    if (filter_stats) { const bool on = filter && (filter->mask & 15u); filter_stats->n_lines = on ? ht.n_lines : nh; filter_stats->n_kept = on ? ht.n_kept : nh; }
+    if (filter_stats) { const bool on = (filter && (filter->mask & 15u)) || taxa; filter_stats->n_lines = on ? ht.n_lines : nh; filter_stats->n_kept = on ? ht.n_kept : nh; }
     auto dup = [](const void* src, size_t bytes) -> void* { void* p = malloc(bytes ? bytes : 1); if (p && bytes) memcpy(p, src, bytes); return p; };
     auto pack = [](const std::vector<std::string>& v, uint64_t* bytes) -> char* {
         size_t n = 0;

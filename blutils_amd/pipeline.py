@@ -80,6 +80,63 @@ def _hit_filter(hit_filter: Union[None, dict, HitFilter]) -> Optional[HitFilterC
     return f
 
 
+@dataclasses.dataclass(frozen=True)
+class TaxonFilter:
+    """Lines dropped by the lineage of their subject (include/blu_pipeline.h: blu_taxon_filter; not in the
+    reference).  Elements are spelled `RANK__IDENTIFIER` as in the lineage flavour of the run (`s__1423` under use_taxid); an
+    identifier ending in `*` is a prefix pattern.  A line passes when none of its lineage's elements is in `exclude` and, if
+    `only` is not empty, at least one is in `only`; an element that names no taxon of the taxonomies file is an error."""
+    exclude: Sequence[str] = ()
+    only: Sequence[str] = ()
+
+    def active(self) -> bool:
+        return bool(self.exclude) or bool(self.only)
+
+
+class TaxonFilterC(C.Structure):
+    _fields_ = [("exclude", C.POINTER(C.c_char_p)), ("n_exclude", C.c_uint64), ("only", C.POINTER(C.c_char_p)),
+                ("n_only", C.c_uint64)]
+
+
+class TaxonFilterStats(C.Structure):
+    _fields_ = [("n_lines", C.c_uint64), ("n_excluded", C.c_uint64), ("n_not_only", C.c_uint64),
+                ("excluded_by", C.POINTER(C.c_uint64))]
+
+
+class _TaxonArgs:
+    """The C structs of one call and the arrays they point into."""
+
+    def __init__(self, exclude, only):
+        self.exclude, self.only = [str(e) for e in exclude], [str(e) for e in only]
+        self._ex = (C.c_char_p * max(1, len(self.exclude)))(*[e.encode() for e in self.exclude])
+        self._on = (C.c_char_p * max(1, len(self.only)))(*[e.encode() for e in self.only])
+        self._by = (C.c_uint64 * max(1, len(self.exclude)))()
+        self.filter = TaxonFilterC(self._ex, len(self.exclude), self._on, len(self.only))
+        self.stats = TaxonFilterStats(0, 0, 0, self._by)
+
+    def counts(self) -> dict:
+        return {"n_lines": int(self.stats.n_lines), "n_excluded": int(self.stats.n_excluded),
+                "n_not_only": int(self.stats.n_not_only), "exclude": list(self.exclude),
+                "excluded_by": [int(self._by[k]) for k in range(len(self.exclude))]}
+
+
+def _taxon_filter(taxon_filter: Union[None, dict, TaxonFilter]) -> Optional[_TaxonArgs]:
+    """None or two empty lists -> None (the calls without it); a dict or TaxonFilter -> the C structs."""
+    if taxon_filter is None:
+        return None
+    if isinstance(taxon_filter, TaxonFilter):
+        taxon_filter = {"exclude": taxon_filter.exclude, "only": taxon_filter.only}
+    unknown = set(taxon_filter) - {"exclude", "only"}
+    if unknown:
+        raise ValueError(f"taxon_filter: unknown keys {sorted(unknown)}")
+    exclude, only = taxon_filter.get("exclude") or (), taxon_filter.get("only") or ()
+    if isinstance(exclude, str) or isinstance(only, str):
+        raise ValueError("taxon_filter: exclude and only are lists of elements")
+    if not exclude and not only:
+        return None
+    return _TaxonArgs(exclude, only)
+
+
 def _bind():
     L = N.lib()
     L.blu_build_consensus_identities.restype = C.c_int
@@ -112,10 +169,12 @@ class IngestColumns(C.Structure):
 
 
 def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = False, device: int = -1,
-                   hit_filter: Union[None, dict, HitFilter] = None) -> dict:
+                   hit_filter: Union[None, dict, HitFilter] = None,
+                   taxon_filter: Union[None, dict, TaxonFilter] = None) -> dict:
     """The SoA columns of the ingest (include/blu_pipeline.h: blu_ingest_columns_on) as numpy arrays + the two string tables.
     hit_filter (a dict or HitFilter): the columns of the lines it keeps (blu_ingest_columns_filtered_on), plus `n_lines` and
-    `n_kept`."""
+    `n_kept`.  taxon_filter (a dict or TaxonFilter): the same under a taxon filter (blu_ingest_columns_taxa_on), alone or
+    beside hit_filter, plus `taxon_filter`: its counts (n_lines, n_excluded, n_not_only, exclude, excluded_by)."""
     import numpy as np
     L = _bind()
     L.blu_ingest_columns_on.restype = C.c_int
@@ -123,7 +182,18 @@ def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = Fa
     L.blu_ingest_columns_free.argtypes = [C.POINTER(IngestColumns)]
     c = IngestColumns()
     flt, fst = _hit_filter(hit_filter), HitFilterStats()
-    if flt is None:
+    tf = _taxon_filter(taxon_filter)
+    if tf is not None:
+        L.blu_ingest_columns_taxa_on.restype = C.c_int
+        L.blu_ingest_columns_taxa_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(HitFilterC),
+                                                 C.POINTER(IngestColumns), C.POINTER(HitFilterStats),
+                                                 C.POINTER(TaxonFilterC), C.POINTER(TaxonFilterStats)]
+        rc = L.blu_ingest_columns_taxa_on(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
+                                          C.byref(flt) if flt is not None else None, C.byref(c), C.byref(fst),
+                                          C.byref(tf.filter), C.byref(tf.stats))
+        if rc != N.BLU_OK:
+            raise N.BluError(rc, "blu_ingest_columns_taxa_on")
+    elif flt is None:
         rc = L.blu_ingest_columns_on(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device, C.byref(c))
         if rc != N.BLU_OK:
             raise N.BluError(rc, "blu_ingest_columns_on")
@@ -144,8 +214,10 @@ def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = Fa
         split = lambda p, n: C.string_at(p, n).split(b"\0")[:-1] if n else []
         out["query_names"] = split(c.query_names, int(c.query_names_bytes))
         out["accessions"] = split(c.accessions, int(c.accessions_bytes))
-        if flt is not None:
+        if flt is not None or tf is not None:
             out["n_lines"], out["n_kept"] = int(fst.n_lines), int(fst.n_kept)
+        if tf is not None:
+            out["taxon_filter"] = tf.counts()
         return out
     finally:
         L.blu_ingest_columns_free(C.byref(c))
@@ -191,15 +263,17 @@ def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: s
                                strategy: str = "relaxed", use_taxid: Optional[bool] = None,
                                custom_taxon_values: Optional[dict] = None, headers: Optional[Sequence[str]] = None,
                                out_format: str = "json", device: int = 0, lenient: bool = False, parse: bool = True,
-                               config=None, out_path: Optional[str] = None, hit_filter: Union[None, dict, HitFilter] = None):
+                               config=None, out_path: Optional[str] = None, hit_filter: Union[None, dict, HitFilter] = None,
+                               taxon_filter: Union[None, dict, TaxonFilter] = None):
     """Returns (results, stats).  With out_path the document is written there by the library (no copy through Python) and
     (None, stats) is returned.  results: the parsed `results` list (json) / list of records (jsonl), sorted by
     query, or the raw text when parse=False.  config: Some(BlastBuilder) of the run-with-consensus path
     (blutils_amd.blast.BlastBuilder): its run id goes on every result and it is written as the document's config.
     hit_filter (a dict or HitFilter; None = no filter): only the lines it keeps take part; stats then
-    also has `n_lines` and `n_kept`."""
+    also has `n_lines` and `n_kept`.  taxon_filter (a dict or TaxonFilter; None = no filter): only the lines whose lineage
+    passes take part; stats then also has `taxon_filter`, its counts."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
-                  lenient, parse, config, out_path, None, "one", hit_filter=hit_filter)
+                  lenient, parse, config, out_path, None, "one", hit_filter=hit_filter, taxon_filter=taxon_filter)
 
 
 def build_consensus_identities_with_report(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -208,12 +282,13 @@ def build_consensus_identities_with_report(blast_output: str, taxonomies_file: s
                                            headers: Optional[Sequence[str]] = None, out_format: str = "json",
                                            device: int = 0, lenient: bool = False, parse: bool = True, config=None,
                                            out_path: Optional[str] = None, report_path: str = "report.tsv",
-                                           report_weight: str = "one", hit_filter: Union[None, dict, HitFilter] = None):
+                                           report_weight: str = "one", hit_filter: Union[None, dict, HitFilter] = None,
+                                           taxon_filter: Union[None, dict, TaxonFilter] = None):
     """build_consensus_identities plus the taxon abundance report of its results, counted on the GPU and written to
     report_path after the document (include/blu_pipeline.h: blu_build_consensus_identities_report).
     report_weight: "one" (results) or "size" (dereplicated reads named in the query)."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
-                  lenient, parse, config, out_path, report_path, report_weight, hit_filter=hit_filter)
+                  lenient, parse, config, out_path, report_path, report_weight, hit_filter=hit_filter, taxon_filter=taxon_filter)
 
 
 def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -224,7 +299,8 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
                                            out_path: Optional[str] = None, report_path: Optional[str] = None,
                                            sample_table_path: Optional[str] = None, report_weight: str = "one",
                                            hit_filter: Union[None, dict, HitFilter] = None,
-                                           support_table_path: Optional[str] = None):
+                                           support_table_path: Optional[str] = None,
+                                           taxon_filter: Union[None, dict, TaxonFilter] = None):
     """build_consensus_identities plus the taxon abundance report (report_path), the per-sample table (sample_table_path,
     DESIGN.md §13), or both, counted on the GPU and written in the order document, report, table
     (include/blu_pipeline.h: blu_build_consensus_identities_tables).  report_weight serves both files.  A query whose name
@@ -233,14 +309,15 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
     other files and with hit_filter, and may be the only one asked for."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, report_path, report_weight, sample_table_path, hit_filter=hit_filter,
-                  support_table_path=support_table_path)
+                  support_table_path=support_table_path, taxon_filter=taxon_filter)
 
 
 def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device, lenient,
            parse, config, out_path, report_path, report_weight, sample_table_path=None, hit_filter=None,
-           support_table_path=None):
+           support_table_path=None, taxon_filter=None):
     L = _bind()
     flt, fst = _hit_filter(hit_filter), HitFilterStats()
+    tf = _taxon_filter(taxon_filter)
     p = PipelineParams()
     p.cutoffs.taxon = N.TAXON[taxon]
     p.cutoffs.has_custom = 1 if custom_taxon_values is not None else 0
@@ -269,11 +346,38 @@ def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_tax
     cfg_text = config.render(out_format).encode() if config is not None else None
     def stats_of():
         stats = {f: getattr(st, f) for f, _ in PipelineStats._fields_}
-        if flt is not None:
+        if flt is not None or tf is not None:
             stats["n_lines"], stats["n_kept"] = int(fst.n_lines), int(fst.n_kept)
+        if tf is not None:
+            stats["taxon_filter"] = tf.counts()
         return stats
 
-    if support_table_path is not None:
+    if tf is not None:
+        # a taxon filter: one entry point for every combination (include/blu_pipeline.h: blu_build_consensus_identities_taxa)
+        tp = None
+        if report_path is not None or sample_table_path is not None:
+            tp = TablesParams(str(report_path).encode() if report_path is not None else None,
+                              str(sample_table_path).encode() if sample_table_path is not None else None,
+                              REPORT_WEIGHT[report_weight], 0)
+        L.blu_build_consensus_identities_taxa.restype = C.c_int
+        L.blu_build_consensus_identities_taxa.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
+                                                          C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(TablesParams),
+                                                          C.POINTER(HitFilterC), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                          C.POINTER(PipelineStats), C.POINTER(HitFilterStats), C.c_char_p,
+                                                          C.POINTER(TaxonFilterC), C.POINTER(TaxonFilterStats)]
+        rc = L.blu_build_consensus_identities_taxa(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
+                                                   taxonomies_file.encode(), C.byref(p), run_id, cfg_text,
+                                                   out_path.encode() if out_path is not None else None,
+                                                   C.byref(tp) if tp is not None else None,
+                                                   C.byref(flt) if flt is not None else None,
+                                                   C.byref(text), C.byref(n), C.byref(st), C.byref(fst),
+                                                   str(support_table_path).encode() if support_table_path is not None else None,
+                                                   C.byref(tf.filter), C.byref(tf.stats))
+        if rc != N.BLU_OK:
+            raise N.BluError(rc, "blu_build_consensus_identities_taxa")
+        if out_path is not None:
+            return None, stats_of()
+    elif support_table_path is not None:
         # the support table: one entry point for every combination (include/blu_pipeline.h: blu_build_consensus_identities_support)
         tp = None
         if report_path is not None or sample_table_path is not None:

@@ -176,6 +176,40 @@ int blu_build_consensus_identities_support(const char* blast_output_file, const 
                                            blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats,
                                            const char* support_table_path);
 
+/* Taxon filters (not in the reference): lines are dropped by the lineage of their subject, in the parser, so
+ * that hits to uninformative or out-of-scope taxa do not take part.  An element is spelled `RANK__IDENTIFIER` as it appears in
+ * the lineage flavour of the run (textLineage, or numericLineage under use_taxid): split at `__` into exactly two non-empty
+ * parts; the rank goes through the normalisation lineage ranks go through (lower-cased, `species__x` is `s__x`); an identifier
+ * that ends in `*` is a prefix pattern over the identifiers of that rank (`s__uncultured-*`; a lone `*` is every identifier of
+ * the rank) and counts as one element.  An element or pattern that names no node of a lineage of the taxonomies file is
+ * BLU_ERR_INVALID_ARG naming it; so are more than BLU_TAXON_FILTER_MAX_EXCLUDE exclude elements.
+ * The elements of a line are the nodes of the lineage of the taxonomy row its column 3 joins to (the first listing of a taxid
+ * listed more than once); a line whose taxid is not in the file, or whose row's lineage is bad or empty, has none.  A line
+ * passes when none of its elements is on `exclude` and, if `only` is not empty, at least one is on `only`.  The verdict comes
+ * before the thresholds of a blu_hit_filter given alongside and does not depend on them; a line is kept when it passes and
+ * every threshold holds, and the result is what the call without filters gives on a copy of the table without the other lines
+ * (as under blu_hit_filter, above).  A NULL filter or two empty lists is the call without it. */
+#define BLU_TAXON_FILTER_MAX_EXCLUDE 65534u
+typedef struct blu_taxon_filter {
+    const char* const* exclude; uint64_t n_exclude;
+    const char* const* only; uint64_t n_only;
+} blu_taxon_filter;
+typedef struct blu_taxon_filter_stats {
+    uint64_t n_lines;              /* non-empty lines of the table */
+    uint64_t n_excluded;           /* lines with an element on the exclude list, whatever the thresholds say */
+    uint64_t n_not_only;           /* lines that pass the exclude list and have no element on the only list */
+    uint64_t* excluded_by;         /* caller's [n_exclude], or NULL: lines whose first matching exclude element, in list order, is k */
+} blu_taxon_filter_stats;
+/* The arguments of blu_build_consensus_identities_support plus the taxon filter and its counts (taxon_stats may be NULL).
+ * filter_stats->n_kept stays "lines kept by everything". */
+int blu_build_consensus_identities_taxa(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                        const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
+                                        const char* config_text, const char* out_path, const blu_tables_params* tables,
+                                        const blu_hit_filter* filter, char** out_text, size_t* out_len,
+                                        blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats,
+                                        const char* support_table_path, const blu_taxon_filter* taxon_filter,
+                                        blu_taxon_filter_stats* taxon_stats);
+
 /* The text-ingest half alone (no GPU): DB JSON + outfmt-6 TSV -> SoA columns, as blu_build_consensus_identities does it.
  * Fills stats (rows, queries, taxids, unmatched rows, load times) and *checksum with an FNV-1a hash over every SoA
  * column, the segment offsets and the query names — identical for any BLU_INGEST_THREADS value.  For tests and for
@@ -208,6 +242,10 @@ int blu_ingest_columns_on(const char* blast_output_file, const char* taxonomies_
 /* The same under a hit filter (above), on either parser: the columns of the kept lines.  filter_stats may be NULL. */
 int blu_ingest_columns_filtered_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
                                    const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats);
+/* The same under a taxon filter as well (above): the arguments of blu_ingest_columns_filtered_on plus the filter and its counts. */
+int blu_ingest_columns_taxa_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                               const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
+                               const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats);
 void blu_ingest_columns_free(blu_ingest_columns* cols);
 
 /* Which parser the calling thread's last ingest used: 0 = CPU, 1 = GPU. */
