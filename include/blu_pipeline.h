@@ -225,7 +225,9 @@ int blu_ingest_only_on(const char* blast_output_file, const char* taxonomies_fil
 /* The columns themselves (what blu_ingest_only[_on] hashes), for a caller that wants the SoA table and for tests that
  * compare the parsers column by column with an independent reading of the file.  Every array is malloc'd by the library
  * and released by blu_ingest_columns_free; query_names / accessions are the strings back to back, each NUL-terminated
- * (queries in first-appearance order, accessions in byte order = acc_rank order). */
+ * (queries in first-appearance order, accessions in byte order = acc_rank order).  A name that itself holds a NUL byte
+ * cannot be told from two names in these tables: n_queries / n_accessions, the byte counts and the checksum of
+ * blu_ingest_only still count it as one. */
 typedef struct blu_ingest_columns {
     uint64_t n_hits, n_queries, n_accessions;
     uint64_t* seg_off;        /* [n_queries + 1] */

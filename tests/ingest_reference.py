@@ -33,6 +33,8 @@ def read_table(blast_path, db_path):
     for ln in lines:
         if ln.endswith(b"\r"):
             ln = ln[:-1]
+        if not ln:                                 # a blank line (or a bare CR LF) is no row: both product parsers skip it
+            continue
         c = ln.split(b"\t")
         assert len(c) >= 13, ln
         q = c[0].replace(b'"', b"")
