@@ -15,7 +15,7 @@ EXPORTS = (
     "blu_taxonomy_rank_name", "blu_taxonomy_row_cutoffs", "blu_taxonomy_lookup", "blu_taxonomy_row_map", "blu_consensus_run",
     "blu_consensus_last_launch", "blu_hits_pack", "blu_hits_pack64", "blu_taxonomy_shared_levels", "blu_taxonomy_trim",
     "blu_consensus_report", "blu_report_free", "blu_dev_exclusive_scan", "blu_dev_radix_sort_pairs", "blu_dev_line_index",
-    "blu_consensus_sample_table", "blu_sample_table_free", "blu_consensus_support",
+    "blu_consensus_sample_table", "blu_sample_table_free", "blu_consensus_support", "blu_hits_score_band",
 )
 # include/blu_pipeline.h
 PIPELINE_EXPORTS = ("blu_build_consensus_identities", "blu_free_text", "blu_custom_taxon_from_file", "blu_ingest_only",
@@ -24,7 +24,8 @@ PIPELINE_EXPORTS = ("blu_build_consensus_identities", "blu_free_text", "blu_cust
                     "blu_taxdb_build", "blu_seqdb_export", "blu_qiime_taxonomy_tsv", "blu_build_consensus_identities_report",
                     "blu_build_consensus_identities_tables", "blu_build_consensus_identities_filtered",
                     "blu_ingest_columns_filtered_on", "blu_build_consensus_identities_support",
-                    "blu_build_consensus_identities_taxa", "blu_ingest_columns_taxa_on")
+                    "blu_build_consensus_identities_taxa", "blu_ingest_columns_taxa_on",
+                    "blu_build_consensus_identities_band", "blu_ingest_columns_band_on")
 
 BLU_UNMATCHED_TAXID = 0xFFFFFFFF
 BLU_NONE_U8, BLU_NONE_U16, BLU_MAR_NEVER_EQUAL = 0xFF, 0xFFFF, 0xFFFE
@@ -56,6 +57,23 @@ class Hits(C.Structure):
 
 class RunParams(C.Structure):
     _fields_ = [("strategy", C.c_int32), ("flags", C.c_int32), ("stream", C.c_void_p)]
+
+
+BAND_TOP_PERCENT, BAND_TOP_BITS = 1, 2
+
+
+class ScoreBandC(C.Structure):
+    """include/blu_consensus.h: blu_score_band"""
+    _fields_ = [("top_percent_milli", C.c_uint32), ("mask", C.c_uint32), ("top_bits", C.c_uint64)]
+
+
+class ScoreBandStats(C.Structure):
+    """include/blu_consensus.h: blu_score_band_stats"""
+    _fields_ = [("n_hits", C.c_uint64), ("n_raised", C.c_uint64), ("n_queries", C.c_uint64), ("n_widened", C.c_uint64)]
+
+
+def band_counts(st: ScoreBandStats) -> dict:
+    return {f: int(getattr(st, f)) for f, _ in ScoreBandStats._fields_}
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -113,6 +131,10 @@ def lib() -> C.CDLL:
         L.blu_dev_radix_sort_pairs.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]
         L.blu_dev_line_index.restype = C.c_int
         L.blu_dev_line_index.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    if hasattr(L, "blu_hits_score_band"):        # (an A/B library of an older build: BLU_CONSENSUS_LIB)
+        L.blu_hits_score_band.restype = C.c_int
+        L.blu_hits_score_band.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(ScoreBandC),
+                                          C.c_void_p, C.c_void_p, C.POINTER(ScoreBandStats)]
     L.blu_consensus_last_launch.restype = C.c_int
     L.blu_consensus_last_launch.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     _lib = L

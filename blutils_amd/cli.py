@@ -59,6 +59,20 @@ of the taxonomies file is an error.  The verdict is taken by the parser, on the 
 and the run gives what it gives on a copy of the table without the dropped lines.  To stderr:
 `taxon filter: excluded X, not in --only-taxon Y, of N lines`, then `  EL: count` per exclude element that dropped lines.
 
+    python -m blutils_amd.cli blastn build-consensus ... [--top-percent P] [--top-bits D]
+    python -m blutils_amd.cli blastn run-with-consensus ... (the same two)
+
+not in the reference: the bit-score band.  The reference decides a query by the hits that tie exactly on its top
+truncated bit-score; with a band, the hits just under the top count as tied with it, as MEGAN's top-percent or BASTA's band do.
+A hit with truncated score b is in the band under the top t when b * 100000 >= t * (100000 - 1000 P) (--top-percent: P a decimal
+with at most three decimals, 0 .. 100; read exactly, compared in integers) and b >= t - D (--top-bits: D an integer below 2^32);
+with both flags both must hold.  The top is taken over the lines the filters above keep.  The run gives what it gives on a copy
+of the table in which column 12 of every in-band line is replaced by its query's top score — the document, --report,
+--sample-table and --support-table (whose top_hits is then the band's size, and whose bits / support_bits sum the raised scores);
+one pass over the bit-score column on the GPU (csrc/band_kernel.hip) makes it so.  `--top-percent 0` and `--top-bits 0` are the
+exact ties: the bytes of the run without the flag.  To stderr, after the filter lines:
+`score band: raised R of N lines in W of Q queries`.
+
     python -m blutils_amd.cli cache-db TAX.json CACHE [-u]
 
 writes the binary cache of a taxonomies file (not in the reference CLI; pass CACHE as -t afterwards).  
@@ -161,6 +175,15 @@ def build_parser() -> argparse.ArgumentParser:
                          help="--exclude-taxon elements, one per line; blank lines and # comments skipped")
         tfl.add_argument("--only-taxon-file", metavar="FILE",
                          help="--only-taxon elements, one per line; blank lines and # comments skipped")
+        bnd = sp.add_argument_group("bit-score band (not in the reference CLI)",
+                                    "hits inside a band under a query's top bit-score count as tied with it; applied after "
+                                    "the filters, on the GPU, before the consensus")
+        bnd.add_argument("--top-percent", type=_top_percent, metavar="P",
+                         help="hits whose truncated bit-score is within P percent of the query's top count as tied with it; "
+                              "a decimal with at most three decimals, 0 .. 100 (not in the reference CLI)")
+        bnd.add_argument("--top-bits", type=_top_bits, metavar="D",
+                         help="hits whose truncated bit-score is at most D below the query's top count as tied with it; an "
+                              "integer, 0 .. 2^32 - 1 (not in the reference CLI)")
     br = blastn.add_parser("build-report", help="blutils result document -> taxon abundance report (not in the reference)")
     br.add_argument("blu_result", nargs="?", default="-")
     br.add_argument("-o", "--output-file")
@@ -233,6 +256,30 @@ def _length(text: str) -> int:
     return v
 
 
+def _top_percent(text: str):
+    """--top-percent: a decimal with at most three decimals in 0 .. 100, kept exact (decimal.Decimal)"""
+    import decimal
+    try:
+        pipeline.top_percent_milli(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return decimal.Decimal(text.strip())
+
+
+def _top_bits(text: str) -> int:
+    """--top-bits: an integer in 0 .. 2^32 - 1"""
+    try:
+        return pipeline.top_bits_value(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def _score_band(args):
+    """the two flags -> pipeline.ScoreBand, or None when neither was given (today's calls)"""
+    b = pipeline.ScoreBand(args.top_percent, args.top_bits)
+    return b if b.active() else None
+
+
 def _hit_filter(args):
     """the four flags -> pipeline.HitFilter, or None when none was given (today's calls)"""
     f = pipeline.HitFilter(args.min_perc_identity, args.min_align_length, args.max_e_value, args.min_bit_score)
@@ -270,6 +317,10 @@ def _say_kept(stats, hit_filter=True) -> None:
                 print(f"  {el}: {count}", file=sys.stderr)
     if hit_filter and stats and "n_kept" in stats:
         print(f"hit filter: kept {stats['n_kept']} of {stats['n_lines']} lines", file=sys.stderr)
+    b = stats.get("score_band") if stats else None
+    if b:
+        print(f"score band: raised {b['n_raised']} of {b['n_hits']} lines in {b['n_widened']} of {b['n_queries']} queries",
+              file=sys.stderr)
 
 
 def _build_db(args) -> int:
@@ -322,7 +373,7 @@ def _run_with_consensus(args) -> int:
                                             device=args.device, report_path=args.report, report_weight=args.report_weight,
                                             sample_table_path=args.sample_table, hit_filter=hit_filter,
                                             filter_stats=stats, support_table_path=args.support_table,
-                                            taxon_filter=taxon_filter)
+                                            taxon_filter=taxon_filter, score_band=_score_band(args))
     except blast.BlastError as e:
         raise SystemExit(str(e))
     except _native.BluError as e:
@@ -369,6 +420,9 @@ def main(argv=None) -> int:
     taxon_filter = _taxon_filter(args)
     if taxon_filter is not None:
         extra["taxon_filter"] = taxon_filter
+    score_band = _score_band(args)
+    if score_band is not None:
+        extra["score_band"] = score_band
     if args.support_table is not None:
         build = functools.partial(pipeline.build_consensus_identities_with_tables, report_path=args.report,
                                   sample_table_path=args.sample_table, report_weight=args.report_weight,

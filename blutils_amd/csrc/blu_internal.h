@@ -146,6 +146,15 @@ struct SupportInput {
 };
 int support_device(const blu_taxonomy* tax, const SupportInput& in, blu_support* d_out);
 
+// band_kernel.hip: the bit-score band on a device column (device pointers; blu_hits_score_band stages host ones).  d_out == d_in
+// is the in-place call.  Runs on `stream` and returns when d_out and the two counts are complete.  The device is the current one.
+#define BLU_BAND_QUERIES_PER_WAVE 4u   // consecutive queries of one wave; four waves a block
+// a band's arguments: BLU_ERR_INVALID_ARG (and the message) for unknown mask bits, top_percent_milli > 100000 or top_bits >= 2^32;
+// a null band is fine.  The one set of refusals of blu_hits_score_band and of the pipeline's entry points.
+int check_score_band(const blu_score_band* band);
+int score_band_device(const int32_t* d_in, const uint64_t* d_seg_off, uint64_t n_hits, uint64_t n_queries, const blu_score_band& band,
+                      hipStream_t stream, int32_t* d_out, uint64_t* n_raised, uint64_t* n_widened);
+
 void set_error(const char* fmt, ...);
 // LinnaeanRank::from_str (linnaean_ranks.rs:52-72): enum kind 0..8, or K_FIRST_OTHER with the slug in *other
 uint16_t parse_rank(const char* name, std::string* other);

@@ -1604,9 +1604,12 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
                    const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
                    const char* config_text, const char* out_path, Document* document, blu_pipeline_stats* stats,
                    const blu_tables_params* tables = nullptr, const blu_hit_filter* flt = nullptr, blu_hit_filter_stats* fst = nullptr,
-                   const char* support_path = nullptr, const blu_taxon_filter* tflt = nullptr, blu_taxon_filter_stats* tst = nullptr) {
+                   const char* support_path = nullptr, const blu_taxon_filter* tflt = nullptr, blu_taxon_filter_stats* tst = nullptr,
+                   const blu_score_band* band = nullptr, blu_score_band_stats* bst = nullptr) {
     if (!blast_output_file || !taxonomies_file || !params || !document) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     if (flt && (flt->mask & ~15u)) { set_error("hit filter: unknown bits in the mask"); return BLU_ERR_INVALID_ARG; }
+    if (int brc = check_score_band(band)) return brc;
+    if (band && !band->mask) band = nullptr;      // (an empty mask: the call without a band)
     if (tables && ((!tables->report_path && !tables->sample_table_path) ||
                    (tables->weight != BLU_REPORT_WEIGHT_ONE && tables->weight != BLU_REPORT_WEIGHT_SIZE))) {
         set_error("report: a path and weight BLU_REPORT_WEIGHT_ONE or BLU_REPORT_WEIGHT_SIZE are needed");
@@ -1693,6 +1696,17 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     // (BLU_PIPELINE_HOST_COLUMNS=1, tests: take the fallback below although the device path would work)
     const bool force_host = getenv("BLU_PIPELINE_HOST_COLUMNS") != nullptr;
     if (force_host && ht.dev) { rc = download_columns(ht); if (rc != BLU_OK) return rc; }
+    // the bit-score band, once per run: on the device column where the engine will read it in place — a
+    // download after a failed device run then brings the raised column — else on the host column through the host-pointer route
+    bool band_applied = false;
+    blu_score_band_stats band_st{ht.n_hits, 0, ht.n_queries, 0};
+    if (band && ht.dev && !recs.empty() && !force_host) {
+        rc = blu_hits_score_band(ht.dev->device, ht.dev->bitscore, (const uint64_t*)ht.dev->seg_off, ht.dev->n_hits, ht.dev->n_queries, 1,
+                                 band, nullptr, ht.dev->bitscore, &band_st);
+        if (rc != BLU_OK) return rc;
+        band_applied = true;
+        tr.lap("score band (device)");
+    }
     if (ht.dev && !recs.empty() && !force_host) {
         // the GPU ingest left the grouped columns on the device: the engine reads them in place and only the records and
         // the top-score rows come back (if that fails — e.g. no room for the work buffers — the columns are downloaded and
@@ -1706,6 +1720,13 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
         eng_rows.resize(ht.tax_desc_row.size());
         for (size_t i = 0; i < eng_rows.size(); ++i)
             eng_rows[i] = ht.tax_desc_row[i] == BLU_UNMATCHED_TAXID ? BLU_UNMATCHED_TAXID : fwd[ht.tax_desc_row[i]];
+        if (band && !band_applied && !recs.empty()) {
+            rc = blu_hits_score_band(params->device, ht.bitscore.data(), ht.seg_off.data(), ht.bitscore.size(), ht.n_queries, 0, band, nullptr,
+                                     ht.bitscore.data(), &band_st);
+            if (rc != BLU_OK) return rc;
+            band_applied = true;
+            tr.lap("score band (host columns)");
+        }
         if (!recs.empty()) {
             blu_hits h{};
             h.bitscore = ht.bitscore.data(); h.tax_row = eng_rows.data();
@@ -1730,6 +1751,7 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
         }
         top_rows_from_columns(ht, recs, nthreads, top);
     }
+    if (bst) *bst = band_st;
     st.t_engine_s = now_s() - t0;
     tr.lap("engine + top rows");
 
@@ -1972,13 +1994,13 @@ int consensus_to_text(const char* blast_output_file, const char* const* headers,
                       const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const blu_tables_params* tables,
                       char** out_text, size_t* out_len, blu_pipeline_stats* stats, const blu_hit_filter* flt = nullptr,
                       blu_hit_filter_stats* fst = nullptr, const char* support_path = nullptr, const blu_taxon_filter* tflt = nullptr,
-                      blu_taxon_filter_stats* tst = nullptr) {
+                      blu_taxon_filter_stats* tst = nullptr, const blu_score_band* band = nullptr, blu_score_band_stats* bst = nullptr) {
     if (!out_text) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     *out_text = nullptr;
     if (out_len) *out_len = 0;
     Document d;
     int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats, tables, flt, fst, support_path, tflt, tst); }
+    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats, tables, flt, fst, support_path, tflt, tst, band, bst); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }   // (no exception crosses the C ABI)
     if (rc != BLU_OK) return rc;
     if ((rc = put_tables(d, tables, support_path)) != BLU_OK) return rc;
@@ -2000,11 +2022,11 @@ int consensus_to_file(const char* blast_output_file, const char* const* headers,
                       const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const char* out_path,
                       const blu_tables_params* tables, blu_pipeline_stats* stats, const blu_hit_filter* flt = nullptr,
                       blu_hit_filter_stats* fst = nullptr, const char* support_path = nullptr, const blu_taxon_filter* tflt = nullptr,
-                      blu_taxon_filter_stats* tst = nullptr) {
+                      blu_taxon_filter_stats* tst = nullptr, const blu_score_band* band = nullptr, blu_score_band_stats* bst = nullptr) {
     if (!out_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     Document d;
     int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats, tables, flt, fst, support_path, tflt, tst); }
+    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats, tables, flt, fst, support_path, tflt, tst, band, bst); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
     if (rc != BLU_OK) return rc;
     if (getenv("BLU_INGEST_TRACE")) fprintf(stderr, "[pipeline] %-26s %.3f s\n", "tear-down (tables, strings)", now_s() - g_t_body_end);
@@ -2116,14 +2138,27 @@ int blu_build_consensus_identities_taxa(const char* blast_output_file, const cha
                                         const blu_hit_filter* filter, char** out_text, size_t* out_len,
                                         blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats, const char* support_table_path,
                                         const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats) {
+    return blu_build_consensus_identities_band(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path,
+                                               tables, filter, out_text, out_len, stats, filter_stats, support_table_path, taxon_filter,
+                                               taxon_stats, nullptr, nullptr);
+}
+
+int blu_build_consensus_identities_band(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                        const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
+                                        const char* config_text, const char* out_path, const blu_tables_params* tables,
+                                        const blu_hit_filter* filter, char** out_text, size_t* out_len,
+                                        blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats, const char* support_table_path,
+                                        const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
+                                        const blu_score_band* band, blu_score_band_stats* band_stats) {
     if (tables && !tables->report_path && !tables->sample_table_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     if (filter_stats) *filter_stats = blu_hit_filter_stats{0, 0};
     clear_taxon_stats(taxon_filter, taxon_stats);
+    if (band_stats) *band_stats = blu_score_band_stats{0, 0, 0, 0};
     if (out_path)
         return consensus_to_file(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, tables,
-                                 stats, filter, filter_stats, support_table_path, taxon_filter, taxon_stats);
+                                 stats, filter, filter_stats, support_table_path, taxon_filter, taxon_stats, band, band_stats);
     return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, tables, out_text,
-                             out_len, stats, filter, filter_stats, support_table_path, taxon_filter, taxon_stats);
+                             out_len, stats, filter, filter_stats, support_table_path, taxon_filter, taxon_stats, band, band_stats);
 }
 
 int blu_build_consensus_identities_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
@@ -2185,8 +2220,19 @@ int blu_ingest_columns_filtered_on(const char* blast_output_file, const char* ta
 int blu_ingest_columns_taxa_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
                                const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
                                const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats) {
+    return blu_ingest_columns_band_on(blast_output_file, taxonomies_file, use_taxid, device, filter, out, filter_stats, taxon_filter, taxon_stats,
+                                      nullptr, nullptr);
+}
+
+int blu_ingest_columns_band_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                               const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
+                               const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
+                               const blu_score_band* band, blu_score_band_stats* band_stats) {
     if (!blast_output_file || !taxonomies_file || !out) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     if (filter && (filter->mask & ~15u)) { set_error("hit filter: unknown bits in the mask"); return BLU_ERR_INVALID_ARG; }
+    if (band_stats) *band_stats = blu_score_band_stats{0, 0, 0, 0};
+    if (int brc = check_score_band(band)) return brc;
+    if (band && !band->mask) band = nullptr;
     if (filter_stats) *filter_stats = blu_hit_filter_stats{0, 0};
     clear_taxon_stats(taxon_filter, taxon_stats);
     memset(out, 0, sizeof *out);
@@ -2208,6 +2254,11 @@ int blu_ingest_columns_taxa_on(const char* blast_output_file, const char* taxono
     ht.wait_strings();
     if (!ht.strings_ok) { set_error("out of memory while building the query / accession strings"); return BLU_ERR_ALLOC; }
     const size_t nh = ht.bitscore.size(), nq = ht.query_names.size();
+    if (band_stats) { band_stats->n_hits = nh; band_stats->n_queries = nq; }
+    if (band && nh) {   // (the use-case's host-column hook: the host-pointer route of the one kernel)
+        rc = blu_hits_score_band(device, ht.bitscore.data(), ht.seg_off.data(), nh, nq, 0, band, nullptr, ht.bitscore.data(), band_stats);
+        if (rc != BLU_OK) return rc;
+    }
     if (filter_stats) { const bool on = (filter && (filter->mask & 15u)) || taxa; filter_stats->n_lines = on ? ht.n_lines : nh; filter_stats->n_kept = on ? ht.n_kept : nh; }
     auto dup = [](const void* src, size_t bytes) -> void* { void* p = malloc(bytes ? bytes : 1); if (p && bytes) memcpy(p, src, bytes); return p; };
     auto pack = [](const std::vector<std::string>& v, uint64_t* bytes) -> char* {

@@ -395,6 +395,56 @@ def support_device(tax: Taxonomy, hits: dict, records, stream: Optional[int] = N
     return out.cpu().numpy().view(np.uint8)[: 40 * nq].view(SUPPORT_DTYPE).copy()
 
 
+def _band_c(top_percent_milli, top_bits) -> Optional[N.ScoreBandC]:
+    """the two criteria (None = not given) -> blu_score_band, or None when neither is given; values are passed as they are:
+    the library refuses the ones out of range"""
+    if top_percent_milli is None and top_bits is None:
+        return None
+    b = N.ScoreBandC(0, 0, 0)
+    if top_percent_milli is not None:
+        b.top_percent_milli, b.mask = int(top_percent_milli), b.mask | N.BAND_TOP_PERCENT
+    if top_bits is not None:
+        b.top_bits, b.mask = int(top_bits), b.mask | N.BAND_TOP_BITS
+    return b
+
+
+def score_band_host(seg_off, bitscore, top_percent_milli: Optional[int] = None, top_bits: Optional[int] = None, device: int = 0):
+    """blu_hits_score_band on host arrays: -> (the raised int32 column, the counts).  The column and the
+    offsets are uploaded and the device kernel runs; top_percent_milli is the percentage times 1000."""
+    seg = np.ascontiguousarray(seg_off, dtype=np.uint64)
+    bs = np.ascontiguousarray(bitscore, dtype=np.int32)
+    out = np.empty_like(bs)
+    band, st = _band_c(top_percent_milli, top_bits), N.ScoreBandStats()
+    rc = N.lib().blu_hits_score_band(device, bs.ctypes.data if len(bs) else None, seg.ctypes.data, len(bs), len(seg) - 1, 0,
+                                     C.byref(band) if band is not None else None, None, out.ctypes.data if len(bs) else None,
+                                     C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_hits_score_band")
+    return out, N.band_counts(st)
+
+
+def score_band_device(seg_off, bitscore, top_percent_milli: Optional[int] = None, top_bits: Optional[int] = None, out=None,
+                      stream: Optional[int] = None) -> dict:
+    """blu_hits_score_band on torch CUDA tensors (seg_off int64, bitscore int32): the raised column goes to `out` (None: in
+    place); -> the counts.  Returns when the column is complete."""
+    import torch
+
+    if out is None:
+        out = bitscore
+    for t, dt in ((seg_off, torch.int64), (bitscore, torch.int32), (out, torch.int32)):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dt, (t.dtype, t.device)
+    assert out.numel() == bitscore.numel()
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    band, st = _band_c(top_percent_milli, top_bits), N.ScoreBandStats()
+    dev = bitscore.device.index or 0
+    rc = N.lib().blu_hits_score_band(dev, bitscore.data_ptr(), seg_off.data_ptr(), bitscore.numel(), seg_off.numel() - 1, 1,
+                                     C.byref(band) if band is not None else None, stream, out.data_ptr(), C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_hits_score_band")
+    return N.band_counts(st)
+
+
 def records_from_tensor(out) -> np.ndarray:
     """uint8 CUDA/CPU tensor -> numpy structured array of blu_result."""
     return out.detach().cpu().numpy().view(np.uint8).reshape(-1)[: (out.numel() * out.element_size()) // 32 * 32].view(RESULT_DTYPE)

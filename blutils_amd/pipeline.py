@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import decimal
 import json
 from typing import Optional, Sequence, Union
 
@@ -137,6 +138,69 @@ def _taxon_filter(taxon_filter: Union[None, dict, TaxonFilter]) -> Optional[_Tax
     return _TaxonArgs(exclude, only)
 
 
+def top_percent_milli(value) -> int:
+    """A --top-percent value -> thousandths of a percent (0 .. 100000), exactly: a decimal with at most three decimals in
+    0 .. 100.  Read with decimal.Decimal (never through a float); anything else — NaN, infinities, a fourth decimal, an
+    exponent form that is no whole number of thousandths — is a ValueError."""
+    if isinstance(value, (float, bool)):
+        raise ValueError(f"top_percent: pass a decimal string or decimal.Decimal, not {value!r}")
+    try:
+        d = value if isinstance(value, decimal.Decimal) else decimal.Decimal(str(value).strip())
+    except decimal.InvalidOperation:
+        raise ValueError(f"top_percent: not a decimal number: {value!r}")
+    if not d.is_finite():
+        raise ValueError(f"top_percent: not a finite number: {value!r}")
+    if not 0 <= d <= 100:
+        raise ValueError(f"top_percent: must be between 0 and 100, got {value!r}")
+    m = d * 1000
+    if m != m.to_integral_value():
+        raise ValueError(f"top_percent: at most three decimals, got {value!r}")
+    return int(m)
+
+
+def top_bits_value(value) -> int:
+    """A --top-bits value: an integer in 0 .. 2^32 - 1."""
+    if isinstance(value, (float, bool)) or (not isinstance(value, int) and not str(value).strip().lstrip("+-").isdigit()):
+        raise ValueError(f"top_bits: not an integer: {value!r}")
+    v = int(value)
+    if not 0 <= v < (1 << 32):
+        raise ValueError(f"top_bits: must be between 0 and 2^32 - 1, got {value!r}")
+    return v
+
+
+@dataclasses.dataclass(frozen=True)
+class ScoreBand:
+    """A band under each query's top bit-score inside which hits count as tied (include/blu_consensus.h: blu_score_band;
+    DESIGN.md §17; not in the reference).  top_percent: a decimal string or Decimal with at most three decimals, 0 .. 100 —
+    a hit with truncated score b is in the band under the top t when b * 100000 >= t * (100000 - 1000 * top_percent);
+    top_bits: an integer — when b >= t - top_bits.  Both given: both must hold.  In-band hits get the score t before the
+    engine runs; the run then gives what it gives on a copy of the table with column 12 of those lines rewritten."""
+    top_percent: Union[None, str, decimal.Decimal] = None
+    top_bits: Optional[int] = None
+
+    def active(self) -> bool:
+        return self.top_percent is not None or self.top_bits is not None
+
+
+def _score_band(score_band: Union[None, dict, ScoreBand]) -> Optional[N.ScoreBandC]:
+    """None or no criterion -> None (the calls without it); a dict or ScoreBand -> the C struct."""
+    if score_band is None:
+        return None
+    if isinstance(score_band, ScoreBand):
+        score_band = {"top_percent": score_band.top_percent, "top_bits": score_band.top_bits}
+    unknown = set(score_band) - {"top_percent", "top_bits"}
+    if unknown:
+        raise ValueError(f"score_band: unknown keys {sorted(unknown)}")
+    b = N.ScoreBandC(0, 0, 0)
+    if score_band.get("top_percent") is not None:
+        b.top_percent_milli = top_percent_milli(score_band["top_percent"])
+        b.mask |= N.BAND_TOP_PERCENT
+    if score_band.get("top_bits") is not None:
+        b.top_bits = top_bits_value(score_band["top_bits"])
+        b.mask |= N.BAND_TOP_BITS
+    return b if b.mask else None
+
+
 def _bind():
     L = N.lib()
     L.blu_build_consensus_identities.restype = C.c_int
@@ -170,11 +234,14 @@ class IngestColumns(C.Structure):
 
 def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = False, device: int = -1,
                    hit_filter: Union[None, dict, HitFilter] = None,
-                   taxon_filter: Union[None, dict, TaxonFilter] = None) -> dict:
+                   taxon_filter: Union[None, dict, TaxonFilter] = None,
+                   score_band: Union[None, dict, ScoreBand] = None) -> dict:
     """The SoA columns of the ingest (include/blu_pipeline.h: blu_ingest_columns_on) as numpy arrays + the two string tables.
     hit_filter (a dict or HitFilter): the columns of the lines it keeps (blu_ingest_columns_filtered_on), plus `n_lines` and
     `n_kept`.  taxon_filter (a dict or TaxonFilter): the same under a taxon filter (blu_ingest_columns_taxa_on), alone or
-    beside hit_filter, plus `taxon_filter`: its counts (n_lines, n_excluded, n_not_only, exclude, excluded_by)."""
+    beside hit_filter, plus `taxon_filter`: its counts (n_lines, n_excluded, n_not_only, exclude, excluded_by).  score_band (a
+    dict or ScoreBand): the bitscore column with the band applied (blu_ingest_columns_band_on; needs device >= 0), plus
+    `score_band`: its counts (n_hits, n_raised, n_queries, n_widened)."""
     import numpy as np
     L = _bind()
     L.blu_ingest_columns_on.restype = C.c_int
@@ -183,7 +250,20 @@ def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = Fa
     c = IngestColumns()
     flt, fst = _hit_filter(hit_filter), HitFilterStats()
     tf = _taxon_filter(taxon_filter)
-    if tf is not None:
+    band, bst = _score_band(score_band), N.ScoreBandStats()
+    if band is not None:
+        L.blu_ingest_columns_band_on.restype = C.c_int
+        L.blu_ingest_columns_band_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(HitFilterC),
+                                                 C.POINTER(IngestColumns), C.POINTER(HitFilterStats),
+                                                 C.POINTER(TaxonFilterC), C.POINTER(TaxonFilterStats),
+                                                 C.POINTER(N.ScoreBandC), C.POINTER(N.ScoreBandStats)]
+        rc = L.blu_ingest_columns_band_on(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
+                                          C.byref(flt) if flt is not None else None, C.byref(c), C.byref(fst),
+                                          C.byref(tf.filter) if tf is not None else None,
+                                          C.byref(tf.stats) if tf is not None else None, C.byref(band), C.byref(bst))
+        if rc != N.BLU_OK:
+            raise N.BluError(rc, "blu_ingest_columns_band_on")
+    elif tf is not None:
         L.blu_ingest_columns_taxa_on.restype = C.c_int
         L.blu_ingest_columns_taxa_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(HitFilterC),
                                                  C.POINTER(IngestColumns), C.POINTER(HitFilterStats),
@@ -218,6 +298,8 @@ def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = Fa
             out["n_lines"], out["n_kept"] = int(fst.n_lines), int(fst.n_kept)
         if tf is not None:
             out["taxon_filter"] = tf.counts()
+        if band is not None:
+            out["score_band"] = N.band_counts(bst)
         return out
     finally:
         L.blu_ingest_columns_free(C.byref(c))
@@ -264,16 +346,20 @@ def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: s
                                custom_taxon_values: Optional[dict] = None, headers: Optional[Sequence[str]] = None,
                                out_format: str = "json", device: int = 0, lenient: bool = False, parse: bool = True,
                                config=None, out_path: Optional[str] = None, hit_filter: Union[None, dict, HitFilter] = None,
-                               taxon_filter: Union[None, dict, TaxonFilter] = None):
+                               taxon_filter: Union[None, dict, TaxonFilter] = None,
+                               score_band: Union[None, dict, ScoreBand] = None):
     """Returns (results, stats).  With out_path the document is written there by the library (no copy through Python) and
     (None, stats) is returned.  results: the parsed `results` list (json) / list of records (jsonl), sorted by
     query, or the raw text when parse=False.  config: Some(BlastBuilder) of the run-with-consensus path
     (blutils_amd.blast.BlastBuilder): its run id goes on every result and it is written as the document's config.
     hit_filter (a dict or HitFilter; None = no filter): only the lines it keeps take part; stats then
     also has `n_lines` and `n_kept`.  taxon_filter (a dict or TaxonFilter; None = no filter): only the lines whose lineage
-    passes take part; stats then also has `taxon_filter`, its counts."""
+    passes take part; stats then also has `taxon_filter`, its counts.  score_band (a dict or ScoreBand; None =
+    exact ties): the hits inside the band under a query's top bit-score count as tied with it, after the
+    filters; stats then also has `score_band`, its counts (n_hits, n_raised, n_queries, n_widened)."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
-                  lenient, parse, config, out_path, None, "one", hit_filter=hit_filter, taxon_filter=taxon_filter)
+                  lenient, parse, config, out_path, None, "one", hit_filter=hit_filter, taxon_filter=taxon_filter,
+                  score_band=score_band)
 
 
 def build_consensus_identities_with_report(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -283,12 +369,14 @@ def build_consensus_identities_with_report(blast_output: str, taxonomies_file: s
                                            device: int = 0, lenient: bool = False, parse: bool = True, config=None,
                                            out_path: Optional[str] = None, report_path: str = "report.tsv",
                                            report_weight: str = "one", hit_filter: Union[None, dict, HitFilter] = None,
-                                           taxon_filter: Union[None, dict, TaxonFilter] = None):
+                                           taxon_filter: Union[None, dict, TaxonFilter] = None,
+                                           score_band: Union[None, dict, ScoreBand] = None):
     """build_consensus_identities plus the taxon abundance report of its results, counted on the GPU and written to
     report_path after the document (include/blu_pipeline.h: blu_build_consensus_identities_report).
     report_weight: "one" (results) or "size" (dereplicated reads named in the query)."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
-                  lenient, parse, config, out_path, report_path, report_weight, hit_filter=hit_filter, taxon_filter=taxon_filter)
+                  lenient, parse, config, out_path, report_path, report_weight, hit_filter=hit_filter, taxon_filter=taxon_filter,
+                  score_band=score_band)
 
 
 def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -300,24 +388,27 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
                                            sample_table_path: Optional[str] = None, report_weight: str = "one",
                                            hit_filter: Union[None, dict, HitFilter] = None,
                                            support_table_path: Optional[str] = None,
-                                           taxon_filter: Union[None, dict, TaxonFilter] = None):
+                                           taxon_filter: Union[None, dict, TaxonFilter] = None,
+                                           score_band: Union[None, dict, ScoreBand] = None):
     """build_consensus_identities plus the taxon abundance report (report_path), the per-sample table (sample_table_path,
     DESIGN.md §13), or both, counted on the GPU and written in the order document, report, table
     (include/blu_pipeline.h: blu_build_consensus_identities_tables).  report_weight serves both files.  A query whose name
     names no sample fails the call before any file is written.  support_table_path: also the per-query support table
     (blu_build_consensus_identities_support), counted on the GPU and written last; it combines with the
-    other files and with hit_filter, and may be the only one asked for."""
+    other files and with hit_filter, and may be the only one asked for.  Under a score_band its top_hits is the band's size
+    and bits / support_bits sum the raised scores."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, report_path, report_weight, sample_table_path, hit_filter=hit_filter,
-                  support_table_path=support_table_path, taxon_filter=taxon_filter)
+                  support_table_path=support_table_path, taxon_filter=taxon_filter, score_band=score_band)
 
 
 def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device, lenient,
            parse, config, out_path, report_path, report_weight, sample_table_path=None, hit_filter=None,
-           support_table_path=None, taxon_filter=None):
+           support_table_path=None, taxon_filter=None, score_band=None):
     L = _bind()
     flt, fst = _hit_filter(hit_filter), HitFilterStats()
     tf = _taxon_filter(taxon_filter)
+    band, bst = _score_band(score_band), N.ScoreBandStats()
     p = PipelineParams()
     p.cutoffs.taxon = N.TAXON[taxon]
     p.cutoffs.has_custom = 1 if custom_taxon_values is not None else 0
@@ -350,31 +441,37 @@ def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_tax
             stats["n_lines"], stats["n_kept"] = int(fst.n_lines), int(fst.n_kept)
         if tf is not None:
             stats["taxon_filter"] = tf.counts()
+        if band is not None:
+            stats["score_band"] = N.band_counts(bst)
         return stats
 
-    if tf is not None:
-        # a taxon filter: one entry point for every combination (include/blu_pipeline.h: blu_build_consensus_identities_taxa)
+    if band is not None or tf is not None:
+        # a score band or a taxon filter: one entry point for every combination (include/blu_pipeline.h:
+        # blu_build_consensus_identities_band; blu_build_consensus_identities_taxa is this call without a band)
         tp = None
         if report_path is not None or sample_table_path is not None:
             tp = TablesParams(str(report_path).encode() if report_path is not None else None,
                               str(sample_table_path).encode() if sample_table_path is not None else None,
                               REPORT_WEIGHT[report_weight], 0)
-        L.blu_build_consensus_identities_taxa.restype = C.c_int
-        L.blu_build_consensus_identities_taxa.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
+        L.blu_build_consensus_identities_band.restype = C.c_int
+        L.blu_build_consensus_identities_band.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
                                                           C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(TablesParams),
                                                           C.POINTER(HitFilterC), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                           C.POINTER(PipelineStats), C.POINTER(HitFilterStats), C.c_char_p,
-                                                          C.POINTER(TaxonFilterC), C.POINTER(TaxonFilterStats)]
-        rc = L.blu_build_consensus_identities_taxa(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
+                                                          C.POINTER(TaxonFilterC), C.POINTER(TaxonFilterStats),
+                                                          C.POINTER(N.ScoreBandC), C.POINTER(N.ScoreBandStats)]
+        rc = L.blu_build_consensus_identities_band(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
                                                    taxonomies_file.encode(), C.byref(p), run_id, cfg_text,
                                                    out_path.encode() if out_path is not None else None,
                                                    C.byref(tp) if tp is not None else None,
                                                    C.byref(flt) if flt is not None else None,
                                                    C.byref(text), C.byref(n), C.byref(st), C.byref(fst),
                                                    str(support_table_path).encode() if support_table_path is not None else None,
-                                                   C.byref(tf.filter), C.byref(tf.stats))
+                                                   C.byref(tf.filter) if tf is not None else None,
+                                                   C.byref(tf.stats) if tf is not None else None,
+                                                   C.byref(band) if band is not None else None, C.byref(bst))
         if rc != N.BLU_OK:
-            raise N.BluError(rc, "blu_build_consensus_identities_taxa")
+            raise N.BluError(rc, "blu_build_consensus_identities_band" if band is not None else "blu_build_consensus_identities_taxa")
         if out_path is not None:
             return None, stats_of()
     elif support_table_path is not None:

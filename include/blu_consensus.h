@@ -369,6 +369,38 @@ typedef struct blu_support {
 int blu_consensus_support(const blu_taxonomy* tax, const blu_hits* hits, const blu_result* results, void* stream,
                           blu_support* out /* [n_queries] */);
 
+/* -------------------------------------------------------------------------- */
+/* Bit-score band (additive, ABI v5; not in the reference).  The consensus of a query is decided by the rows that
+ * tie on its top truncated bit-score t; a band lets the rows just under t count as tied.  A row with score b < t is IN THE BAND
+ * when every criterion named in `mask` holds, in 64-bit integers (no floating point):
+ *   BLU_BAND_TOP_BITS     b >= t - top_bits                                  (top_bits < 2^32)
+ *   BLU_BAND_TOP_PERCENT  b * 100000 >= t * (100000 - top_percent_milli)     (top_percent_milli = percent * 1000, <= 100000)
+ * (for t < 0 no row meets the percent criterion).  In-band rows get the score t; nothing else changes.  Everything that finds
+ * the top group by comparing the column with its maximum — the engine, the top rows, the report, the support counts — then
+ * sees the band as the top group.  top_bits = 0 and top_percent_milli = 0 are the exact ties: the column is unchanged.  The
+ * pass is idempotent: a raised column raised again is unchanged. */
+#define BLU_BAND_TOP_PERCENT 1u
+#define BLU_BAND_TOP_BITS    2u
+typedef struct blu_score_band { uint32_t top_percent_milli; uint32_t mask; uint64_t top_bits; } blu_score_band;
+typedef struct blu_score_band_stats {
+    uint64_t n_hits;      /* rows of the column */
+    uint64_t n_raised;    /* rows whose score changed */
+    uint64_t n_queries;
+    uint64_t n_widened;   /* queries with at least one such row */
+} blu_score_band_stats;
+/* bitscore[n_hits] -> out[n_hits] (out == bitscore: in place; otherwise the two must not overlap) under seg_off[n_queries + 1];
+ * stats may be NULL.  Counted on the device (csrc/band_kernel.hip).  on_device = 1: device pointers on `device`; the call waits
+ * for `stream` (a hipStream_t, NULL = default), runs on it and returns when `out` and the counts are complete.  OUT OF PLACE
+ * WITH AN ACTIVE BAND ONLY THE ROWS THAT A SEGMENT NAMES ARE WRITTEN: where seg_off[0] = 0 and seg_off[n_queries] = n_hits, as in
+ * every blu_hits table, that is the whole column; rows outside every segment (n_queries = 0 aside, which copies the column)
+ * keep what `out` held.  on_device = 0: the column and the offsets are uploaded, the same kernel runs, the
+ * column is copied back — there is no second implementation.  Offsets beyond n_hits are clamped to it and a decreasing pair is
+ * an empty segment: a corrupt table reads and writes nothing outside the columns.  A NULL band or an empty mask copies the
+ * column.  BLU_ERR_INVALID_ARG: top_percent_milli > 100000, top_bits >= 2^32 (whatever the mask says), unknown mask bits, a
+ * NULL array with a non-zero count. */
+int blu_hits_score_band(int device, const int32_t* bitscore, const uint64_t* seg_off, uint64_t n_hits, uint64_t n_queries,
+                        int on_device, const blu_score_band* band, void* stream, int32_t* out, blu_score_band_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

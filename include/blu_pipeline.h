@@ -210,6 +210,24 @@ int blu_build_consensus_identities_taxa(const char* blast_output_file, const cha
                                         const char* support_table_path, const blu_taxon_filter* taxon_filter,
                                         blu_taxon_filter_stats* taxon_stats);
 
+/* Bit-score band (not in the reference; include/blu_consensus.h: blu_score_band).  The arguments of
+ * blu_build_consensus_identities_taxa plus the band and its counts (band_stats may be NULL).  The rows of a query whose
+ * truncated bit-score lies in the band under the query's top score are given the top score before the engine runs; the top is
+ * taken over the lines the hit and taxon filters keep.  The run gives, byte for byte, what the run without a band gives on a
+ * copy of the (filtered) table in which column 12 of every in-band line is the decimal text of its query's top score: the
+ * document, the report, the sample table and the support table, whose top_hits is then the band's size and whose bits /
+ * support_bits sum the raised scores.  Applied once per run on the device (csrc/band_kernel.hip): on the column the GPU ingest
+ * left there, or through the host-pointer route on host columns.  A NULL band or an empty mask is the call without it;
+ * top_percent_milli = 0 and top_bits = 0 give its bytes. */
+int blu_build_consensus_identities_band(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                        const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
+                                        const char* config_text, const char* out_path, const blu_tables_params* tables,
+                                        const blu_hit_filter* filter, char** out_text, size_t* out_len,
+                                        blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats,
+                                        const char* support_table_path, const blu_taxon_filter* taxon_filter,
+                                        blu_taxon_filter_stats* taxon_stats, const blu_score_band* band,
+                                        blu_score_band_stats* band_stats);
+
 /* The text-ingest half alone (no GPU): DB JSON + outfmt-6 TSV -> SoA columns, as blu_build_consensus_identities does it.
  * Fills stats (rows, queries, taxids, unmatched rows, load times) and *checksum with an FNV-1a hash over every SoA
  * column, the segment offsets and the query names — identical for any BLU_INGEST_THREADS value.  For tests and for
@@ -248,6 +266,12 @@ int blu_ingest_columns_filtered_on(const char* blast_output_file, const char* ta
 int blu_ingest_columns_taxa_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
                                const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
                                const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats);
+/* The same with a bit-score band applied to the bitscore column (above): the arguments of blu_ingest_columns_taxa_on plus the
+ * band and its counts.  A band with a non-empty mask needs a device (device >= 0) whichever parser ran. */
+int blu_ingest_columns_band_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                               const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
+                               const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
+                               const blu_score_band* band, blu_score_band_stats* band_stats);
 void blu_ingest_columns_free(blu_ingest_columns* cols);
 
 /* Which parser the calling thread's last ingest used: 0 = CPU, 1 = GPU. */
