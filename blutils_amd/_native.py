@@ -16,6 +16,7 @@ EXPORTS = (
     "blu_consensus_last_launch", "blu_hits_pack", "blu_hits_pack64", "blu_taxonomy_shared_levels", "blu_taxonomy_trim",
     "blu_consensus_report", "blu_report_free", "blu_dev_exclusive_scan", "blu_dev_radix_sort_pairs", "blu_dev_line_index",
     "blu_consensus_sample_table", "blu_sample_table_free", "blu_consensus_support", "blu_hits_score_band",
+    "blu_hits_subject_keep", "blu_hits_subject_best",
 )
 # include/blu_pipeline.h
 PIPELINE_EXPORTS = ("blu_build_consensus_identities", "blu_free_text", "blu_custom_taxon_from_file", "blu_ingest_only",
@@ -25,7 +26,8 @@ PIPELINE_EXPORTS = ("blu_build_consensus_identities", "blu_free_text", "blu_cust
                     "blu_build_consensus_identities_tables", "blu_build_consensus_identities_filtered",
                     "blu_ingest_columns_filtered_on", "blu_build_consensus_identities_support",
                     "blu_build_consensus_identities_taxa", "blu_ingest_columns_taxa_on",
-                    "blu_build_consensus_identities_band", "blu_ingest_columns_band_on")
+                    "blu_build_consensus_identities_band", "blu_ingest_columns_band_on",
+                    "blu_build_consensus_identities_subject", "blu_ingest_columns_subject_on")
 
 BLU_UNMATCHED_TAXID = 0xFFFFFFFF
 BLU_NONE_U8, BLU_NONE_U16, BLU_MAR_NEVER_EQUAL = 0xFF, 0xFFFF, 0xFFFE
@@ -74,6 +76,23 @@ class ScoreBandStats(C.Structure):
 
 def band_counts(st: ScoreBandStats) -> dict:
     return {f: int(getattr(st, f)) for f, _ in ScoreBandStats._fields_}
+
+
+SUBJECT_BEST_PER_QUERY = 1
+
+
+class SubjectBestC(C.Structure):
+    """include/blu_consensus.h: blu_subject_best"""
+    _fields_ = [("mask", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SubjectBestStats(C.Structure):
+    """include/blu_consensus.h: blu_subject_best_stats"""
+    _fields_ = [("n_hits", C.c_uint64), ("n_kept", C.c_uint64), ("n_queries", C.c_uint64), ("n_thinned", C.c_uint64)]
+
+
+def subject_counts(st: SubjectBestStats) -> dict:
+    return {f: int(getattr(st, f)) for f, _ in SubjectBestStats._fields_}
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -135,6 +154,14 @@ def lib() -> C.CDLL:
         L.blu_hits_score_band.restype = C.c_int
         L.blu_hits_score_band.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(ScoreBandC),
                                           C.c_void_p, C.c_void_p, C.POINTER(ScoreBandStats)]
+    if hasattr(L, "blu_hits_subject_keep"):      # (an A/B library of an older build: BLU_CONSENSUS_LIB)
+        L.blu_hits_subject_keep.restype = C.c_int
+        L.blu_hits_subject_keep.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.POINTER(SubjectBestStats)]
+        L.blu_hits_subject_best.restype = C.c_int
+        L.blu_hits_subject_best.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                            C.c_uint64, C.c_int, C.POINTER(SubjectBestC), C.c_void_p, C.c_uint32,
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(SubjectBestStats)]
     L.blu_consensus_last_launch.restype = C.c_int
     L.blu_consensus_last_launch.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     _lib = L

@@ -229,7 +229,8 @@ def run_blast_and_build_consensus(input_sequences: str, input_taxonomies: str, b
                                   out_format: str = "json", custom_taxon_values: Optional[dict] = None, device: int = 0,
                                   lenient: bool = False, report_path: Optional[str] = None, report_weight: str = "one",
                                   sample_table_path: Optional[str] = None, hit_filter=None, filter_stats: Optional[dict] = None,
-                                  support_table_path: Optional[str] = None, taxon_filter=None, score_band=None):
+                                  support_table_path: Optional[str] = None, taxon_filter=None, score_band=None,
+                                  best_hit_per_subject: bool = False):
     """-> the document text (also written to blutils_out_file with the format's extension, or to stdout).  report_path:
     also the taxon abundance report of the results (pipeline.build_consensus_identities_with_report); sample_table_path:
     also the per-sample table (pipeline.build_consensus_identities_with_tables).  hit_filter (pipeline.HitFilter or a dict):
@@ -238,7 +239,9 @@ def run_blast_and_build_consensus(input_sequences: str, input_taxonomies: str, b
     (DESIGN.md §15), written last.  taxon_filter (pipeline.TaxonFilter or a dict): as hit_filter, by the subject's lineage
     (DESIGN.md §16); its counts come back in filter_stats["taxon_filter"].  score_band (pipeline.ScoreBand or a dict): the band under
     each query's top bit-score inside which hits count as tied (DESIGN.md §17), applied by the consensus step after the filters;
-    its counts come back in filter_stats["score_band"]."""
+    its counts come back in filter_stats["score_band"].  best_hit_per_subject: only the best line of every (query, subject) pair
+    takes part, selected by the consensus step after the filters and before the band — the BLAST table is still
+    written in full; its counts come back in filter_stats["subject_best"]."""
     output_file, headers = run_parallel_blast(input_sequences, blast_out_file, blast_config, blast_execution_repo,
                                               overwrite, threads)
     to_file = blutils_out_file is not None
@@ -248,24 +251,27 @@ def run_blast_and_build_consensus(input_sequences: str, input_taxonomies: str, b
             output_file, input_taxonomies, blast_config.taxon, strategy, use_taxid, custom_taxon_values, headers=headers,
             out_format=fmt, device=device, lenient=lenient, parse=False, config=blast_config, report_path=report_path,
             sample_table_path=sample_table_path, report_weight=report_weight, hit_filter=hit_filter,
-            taxon_filter=taxon_filter, support_table_path=support_table_path, score_band=score_band)
+            taxon_filter=taxon_filter, support_table_path=support_table_path, score_band=score_band,
+            best_hit_per_subject=best_hit_per_subject)
     elif sample_table_path is not None:
         text, stats = pipeline.build_consensus_identities_with_tables(
             output_file, input_taxonomies, blast_config.taxon, strategy, use_taxid, custom_taxon_values, headers=headers,
             out_format=fmt, device=device, lenient=lenient, parse=False, config=blast_config, report_path=report_path,
             sample_table_path=sample_table_path, report_weight=report_weight, hit_filter=hit_filter, taxon_filter=taxon_filter,
-            score_band=score_band)
+            score_band=score_band, best_hit_per_subject=best_hit_per_subject)
     elif report_path is not None:
         text, stats = pipeline.build_consensus_identities_with_report(
             output_file, input_taxonomies, blast_config.taxon, strategy, use_taxid, custom_taxon_values, headers=headers,
             out_format=fmt, device=device, lenient=lenient, parse=False, config=blast_config, report_path=report_path,
-            report_weight=report_weight, hit_filter=hit_filter, taxon_filter=taxon_filter, score_band=score_band)
+            report_weight=report_weight, hit_filter=hit_filter, taxon_filter=taxon_filter, score_band=score_band,
+            best_hit_per_subject=best_hit_per_subject)
     else:
         text, stats = pipeline.build_consensus_identities(output_file, input_taxonomies, blast_config.taxon, strategy, use_taxid,
                                                           custom_taxon_values, headers=headers, out_format=fmt, device=device,
                                                           lenient=lenient, parse=False, config=blast_config,
                                                           hit_filter=hit_filter, taxon_filter=taxon_filter,
-                                                          score_band=score_band)
+                                                          score_band=score_band,
+                                                          best_hit_per_subject=best_hit_per_subject)
     if filter_stats is not None:
         filter_stats.update(stats)
     if to_file:

@@ -59,6 +59,17 @@ of the taxonomies file is an error.  The verdict is taken by the parser, on the 
 and the run gives what it gives on a copy of the table without the dropped lines.  To stderr:
 `taxon filter: excluded X, not in --only-taxon Y, of N lines`, then `  EL: count` per exclude element that dropped lines.
 
+    python -m blutils_amd.cli blastn build-consensus ... [--best-hit-per-subject]
+    python -m blutils_amd.cli blastn run-with-consensus ... (the same)
+
+not in the reference: the best hit per subject.  BLAST writes one line per HSP, so a subject that aligns to a
+query in several places — a genome with seven rRNA operons — occurs several times among the query's hits.  With the flag, of the
+lines of one (query, subject accession) pair that the filters above keep, only the best takes part: the highest truncated
+bit-score, the first in file order among equals.  The run gives what it gives on a copy of the table without the other lines
+— the document, --report, --sample-table and --support-table; one pass over the grouped columns on the GPU
+(csrc/subject_kernel.hip) makes it so, before the band below.  What `blastn -max_hsps 1` would have given, without running
+BLAST again.  To stderr, after the filter lines: `subject best hit: kept K of N lines, thinned W of Q queries`.
+
     python -m blutils_amd.cli blastn build-consensus ... [--top-percent P] [--top-bits D]
     python -m blutils_amd.cli blastn run-with-consensus ... (the same two)
 
@@ -175,6 +186,12 @@ def build_parser() -> argparse.ArgumentParser:
                          help="--exclude-taxon elements, one per line; blank lines and # comments skipped")
         tfl.add_argument("--only-taxon-file", metavar="FILE",
                          help="--only-taxon elements, one per line; blank lines and # comments skipped")
+        sbj = sp.add_argument_group("best hit per subject (not in the reference CLI)",
+                                    "one line per (query, subject accession) pair; applied after the filters, on the GPU, "
+                                    "before the band")
+        sbj.add_argument("--best-hit-per-subject", action="store_true",
+                         help="of the lines of one (query, subject accession) pair keep the one with the highest truncated "
+                              "bit-score, the first in file order among equals (not in the reference CLI)")
         bnd = sp.add_argument_group("bit-score band (not in the reference CLI)",
                                     "hits inside a band under a query's top bit-score count as tied with it; applied after "
                                     "the filters, on the GPU, before the consensus")
@@ -317,6 +334,10 @@ def _say_kept(stats, hit_filter=True) -> None:
                 print(f"  {el}: {count}", file=sys.stderr)
     if hit_filter and stats and "n_kept" in stats:
         print(f"hit filter: kept {stats['n_kept']} of {stats['n_lines']} lines", file=sys.stderr)
+    s = stats.get("subject_best") if stats else None
+    if s:
+        print(f"subject best hit: kept {s['n_kept']} of {s['n_hits']} lines, thinned {s['n_thinned']} of {s['n_queries']} queries",
+              file=sys.stderr)
     b = stats.get("score_band") if stats else None
     if b:
         print(f"score band: raised {b['n_raised']} of {b['n_hits']} lines in {b['n_widened']} of {b['n_queries']} queries",
@@ -373,7 +394,8 @@ def _run_with_consensus(args) -> int:
                                             device=args.device, report_path=args.report, report_weight=args.report_weight,
                                             sample_table_path=args.sample_table, hit_filter=hit_filter,
                                             filter_stats=stats, support_table_path=args.support_table,
-                                            taxon_filter=taxon_filter, score_band=_score_band(args))
+                                            taxon_filter=taxon_filter, score_band=_score_band(args),
+                                            **({"best_hit_per_subject": True} if args.best_hit_per_subject else {}))
     except blast.BlastError as e:
         raise SystemExit(str(e))
     except _native.BluError as e:
@@ -423,6 +445,8 @@ def main(argv=None) -> int:
     score_band = _score_band(args)
     if score_band is not None:
         extra["score_band"] = score_band
+    if args.best_hit_per_subject:
+        extra["best_hit_per_subject"] = True
     if args.support_table is not None:
         build = functools.partial(pipeline.build_consensus_identities_with_tables, report_path=args.report,
                                   sample_table_path=args.sample_table, report_weight=args.report_weight,

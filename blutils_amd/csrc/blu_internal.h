@@ -155,6 +155,29 @@ int check_score_band(const blu_score_band* band);
 int score_band_device(const int32_t* d_in, const uint64_t* d_seg_off, uint64_t n_hits, uint64_t n_queries, const blu_score_band& band,
                       hipStream_t stream, int32_t* d_out, uint64_t* n_raised, uint64_t* n_widened);
 
+// subject_kernel.hip: the best hit per subject on device columns (device pointers; blu_hits_subject_keep / blu_hits_subject_best stage
+// host ones).  Everything runs on the null stream of the current device and the calls return when their outputs are complete.
+#define BLU_SUBJECT_QUERIES_PER_WAVE 4u   // consecutive queries of one wave in the short kernel; four waves a block
+// BLU_ERR_INVALID_ARG (and the message) for unknown mask bits; a null selection is fine
+int check_subject_best(const blu_subject_best* sel);
+// BLU_ERR_INVALID_ARG for n_hits >= 2^32 or n_queries >= 2^32
+int check_subject_counts(uint64_t n_hits, uint64_t n_queries);
+// the verdicts: d_keep[n_hits] = 1 / 0
+int subject_keep_device(const int32_t* d_bitscore, const uint32_t* d_acc_rank, const uint64_t* d_seg_off, uint64_t n_hits, uint64_t n_queries,
+                        uint32_t* d_keep, uint64_t* n_kept, uint64_t* n_thinned);
+// the verdicts and the compaction of the five columns and seg_off.  rotate: each column is its own hipMalloc allocation and may be
+// replaced -- the compacted column takes the spare buffer, the column's old buffer becomes the next spare and the last one is
+// pushed to *retired (null: freed); else the kept rows are copied back to the front of the same buffers.  count_only: no pass,
+// only *n_unmatched (rows whose tax_desc_row is the marker; may be null) is counted.
+struct SubjectColumns { int32_t** bitscore; int32_t** align_len; uint32_t** tax_desc_row; uint32_t** acc_rank; double** pident; unsigned long long* seg_off; };
+int subject_best_device(SubjectColumns& c, uint64_t n_hits, uint64_t n_queries, bool rotate, uint32_t unmatched_marker,
+                        uint64_t* n_hits_out, uint64_t* n_unmatched, uint64_t* n_thinned, std::vector<void*>* retired, bool count_only);
+
+// the same on the columns the GPU ingest left on the device (ingest.h: DeviceHits): compacted by rotation, the retired buffer goes
+// to its trash, n_hits shrinks and seg_off is rewritten in place; *unmatched: the kept rows with no taxonomy row
+struct DeviceHits;
+int subject_best_hits(DeviceHits& dev, blu_subject_best_stats* stats, uint64_t* unmatched);
+
 void set_error(const char* fmt, ...);
 // LinnaeanRank::from_str (linnaean_ranks.rs:52-72): enum kind 0..8, or K_FIRST_OTHER with the slug in *other
 uint16_t parse_rank(const char* name, std::string* other);

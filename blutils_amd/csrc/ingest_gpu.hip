@@ -975,6 +975,15 @@ hipError_t exclusive_scan_u32(const uint32_t* in, uint32_t* out, size_t n, void*
 hipError_t exclusive_scan_u64(const unsigned long long* in, unsigned long long* out, size_t n, void* tmp) {
     return exclusive_scan_dev<unsigned long long>(in, out, n, tmp);
 }
+hipError_t compact_column_u32(const uint32_t* in, const uint32_t* keep, const uint32_t* pos, uint32_t n, uint32_t n_out, uint32_t* out) {
+    if (n) hipLaunchKernelGGL((compact_column<uint32_t>), grid(n, COMPACT_THREADS * 4), dim3(COMPACT_THREADS), 0, 0, in, keep, pos, n, n_out, out);
+    return hipGetLastError();
+}
+hipError_t compact_column_u64(const unsigned long long* in, const uint32_t* keep, const uint32_t* pos, uint32_t n, uint32_t n_out,
+                              unsigned long long* out) {
+    if (n) hipLaunchKernelGGL((compact_column<unsigned long long>), grid(n, COMPACT_THREADS * 2), dim3(COMPACT_THREADS), 0, 0, in, keep, pos, n, n_out, out);
+    return hipGetLastError();
+}
 size_t radix_table_words(uint32_t n) { return (size_t)2 * 256 * (((size_t)n + RS_BLOCK - 1) / RS_BLOCK); }
 size_t radix_scan_tmp_bytes(uint32_t n) { return scan_tmp_bytes<uint32_t>((size_t)256 * (((size_t)n + RS_BLOCK - 1) / RS_BLOCK)); }
 hipError_t radix_sort_pairs(uint32_t** keys, uint32_t** keys_alt, uint32_t** vals, uint32_t** vals_alt, uint32_t n, int bits,

@@ -116,6 +116,13 @@ size_t radix_scan_tmp_bytes(uint32_t n);
 hipError_t radix_sort_pairs(uint32_t** keys, uint32_t** keys_alt, uint32_t** vals, uint32_t** vals_alt, uint32_t n, int bits,
                             uint32_t* table, void* scan_tmp);
 
+// ---- stable compaction of one column: in[i] goes to out[pos[i]] where keep[i] == 1, pos = the exclusive scan of the keep words
+// (the hit filter's kernel); no store lands at or beyond n_out.  in, keep and pos are read 16 bytes at a time:
+// 16-byte aligned.  Launched on the null stream; returns the launch's status
+hipError_t compact_column_u32(const uint32_t* in, const uint32_t* keep, const uint32_t* pos, uint32_t n, uint32_t n_out, uint32_t* out);
+hipError_t compact_column_u64(const unsigned long long* in, const uint32_t* keep, const uint32_t* pos, uint32_t n, uint32_t n_out,
+                              unsigned long long* out);
+
 // ---- file -> HBM through pinned staging (pread, never mapped); BLU_OK, BLU_ERR_IO, or BLU_INGEST_FALLBACK (HIP staging)
 int upload_file(int fd, size_t size, unsigned char* d_text, int device, std::string* err);
 // file -> padded device text in the arena: (size rounded up to 16) + 64 bytes, the 64 after `size` zeroed, the file

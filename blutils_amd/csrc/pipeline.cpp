@@ -1605,11 +1605,14 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
                    const char* config_text, const char* out_path, Document* document, blu_pipeline_stats* stats,
                    const blu_tables_params* tables = nullptr, const blu_hit_filter* flt = nullptr, blu_hit_filter_stats* fst = nullptr,
                    const char* support_path = nullptr, const blu_taxon_filter* tflt = nullptr, blu_taxon_filter_stats* tst = nullptr,
-                   const blu_score_band* band = nullptr, blu_score_band_stats* bst = nullptr) {
+                   const blu_score_band* band = nullptr, blu_score_band_stats* bst = nullptr,
+                   const blu_subject_best* subj = nullptr, blu_subject_best_stats* sst = nullptr) {
     if (!blast_output_file || !taxonomies_file || !params || !document) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     if (flt && (flt->mask & ~15u)) { set_error("hit filter: unknown bits in the mask"); return BLU_ERR_INVALID_ARG; }
     if (int brc = check_score_band(band)) return brc;
     if (band && !band->mask) band = nullptr;      // (an empty mask: the call without a band)
+    if (int src = check_subject_best(subj)) return src;
+    if (subj && !subj->mask) subj = nullptr;      // (an empty mask: the call without the selection)
     if (tables && ((!tables->report_path && !tables->sample_table_path) ||
                    (tables->weight != BLU_REPORT_WEIGHT_ONE && tables->weight != BLU_REPORT_WEIGHT_SIZE))) {
         set_error("report: a path and weight BLU_REPORT_WEIGHT_ONE or BLU_REPORT_WEIGHT_SIZE are needed");
@@ -1696,6 +1699,19 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     // (BLU_PIPELINE_HOST_COLUMNS=1, tests: take the fallback below although the device path would work)
     const bool force_host = getenv("BLU_PIPELINE_HOST_COLUMNS") != nullptr;
     if (force_host && ht.dev) { rc = download_columns(ht); if (rc != BLU_OK) return rc; }
+    // the best hit per subject, once per run and before the band: on the device columns, which are compacted
+    // where the engine will read them — a download after a failed device run then brings the thinned table — else on the host
+    // columns through the host-pointer route (below).  The table's counts follow the kept rows.
+    bool subject_applied = false;
+    blu_subject_best_stats subj_st{ht.n_hits, ht.n_hits, ht.n_queries, 0};
+    if (subj && ht.dev && !recs.empty() && !force_host) {
+        uint64_t unmatched = ht.unmatched;
+        rc = subject_best_hits(*ht.dev, &subj_st, &unmatched);
+        if (rc != BLU_OK) return rc;
+        ht.n_hits = ht.dev->n_hits; ht.unmatched = unmatched;
+        subject_applied = true;
+        tr.lap("subject best hit (device)");
+    }
     // the bit-score band, once per run: on the device column where the engine will read it in place — a
     // download after a failed device run then brings the raised column — else on the host column through the host-pointer route
     bool band_applied = false;
@@ -1717,6 +1733,18 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     // (the device columns and the engine's work buffers stay with the hit table: they are freed off the caller's path at the end)
     if (!done_on_device) ht.dev.reset();
     if (!done_on_device) {
+        if (subj && !subject_applied && !recs.empty()) {
+            uint64_t n_out = ht.bitscore.size(), unmatched = ht.unmatched;
+            rc = blu_hits_subject_best(params->device, ht.bitscore.data(), ht.align_len.data(), ht.tax_desc_row.data(), ht.acc_rank.data(),
+                                       ht.pident.data(), ht.seg_off.data(), ht.bitscore.size(), ht.n_queries, 0, subj, nullptr, BLU_UNMATCHED_TAXID,
+                                       &n_out, &unmatched, &subj_st);
+            if (rc != BLU_OK) return rc;
+            ht.bitscore.resize(n_out); ht.align_len.resize(n_out); ht.tax_desc_row.resize(n_out); ht.acc_rank.resize(n_out); ht.pident.resize(n_out);
+            ht.n_hits = n_out; ht.unmatched = unmatched;
+            subject_applied = true;
+            band_st.n_hits = n_out;
+            tr.lap("subject best hit (host columns)");
+        }
         eng_rows.resize(ht.tax_desc_row.size());
         for (size_t i = 0; i < eng_rows.size(); ++i)
             eng_rows[i] = ht.tax_desc_row[i] == BLU_UNMATCHED_TAXID ? BLU_UNMATCHED_TAXID : fwd[ht.tax_desc_row[i]];
@@ -1752,6 +1780,8 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
         top_rows_from_columns(ht, recs, nthreads, top);
     }
     if (bst) *bst = band_st;
+    if (sst) *sst = subj_st;
+    if (subject_applied) { st.n_hits = ht.n_hits; st.n_unmatched_rows = ht.unmatched; }
     st.t_engine_s = now_s() - t0;
     tr.lap("engine + top rows");
 
@@ -1994,13 +2024,14 @@ int consensus_to_text(const char* blast_output_file, const char* const* headers,
                       const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const blu_tables_params* tables,
                       char** out_text, size_t* out_len, blu_pipeline_stats* stats, const blu_hit_filter* flt = nullptr,
                       blu_hit_filter_stats* fst = nullptr, const char* support_path = nullptr, const blu_taxon_filter* tflt = nullptr,
-                      blu_taxon_filter_stats* tst = nullptr, const blu_score_band* band = nullptr, blu_score_band_stats* bst = nullptr) {
+                      blu_taxon_filter_stats* tst = nullptr, const blu_score_band* band = nullptr, blu_score_band_stats* bst = nullptr,
+                      const blu_subject_best* subj = nullptr, blu_subject_best_stats* sst = nullptr) {
     if (!out_text) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     *out_text = nullptr;
     if (out_len) *out_len = 0;
     Document d;
     int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats, tables, flt, fst, support_path, tflt, tst, band, bst); }
+    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats, tables, flt, fst, support_path, tflt, tst, band, bst, subj, sst); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }   // (no exception crosses the C ABI)
     if (rc != BLU_OK) return rc;
     if ((rc = put_tables(d, tables, support_path)) != BLU_OK) return rc;
@@ -2022,11 +2053,12 @@ int consensus_to_file(const char* blast_output_file, const char* const* headers,
                       const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const char* out_path,
                       const blu_tables_params* tables, blu_pipeline_stats* stats, const blu_hit_filter* flt = nullptr,
                       blu_hit_filter_stats* fst = nullptr, const char* support_path = nullptr, const blu_taxon_filter* tflt = nullptr,
-                      blu_taxon_filter_stats* tst = nullptr, const blu_score_band* band = nullptr, blu_score_band_stats* bst = nullptr) {
+                      blu_taxon_filter_stats* tst = nullptr, const blu_score_band* band = nullptr, blu_score_band_stats* bst = nullptr,
+                      const blu_subject_best* subj = nullptr, blu_subject_best_stats* sst = nullptr) {
     if (!out_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     Document d;
     int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats, tables, flt, fst, support_path, tflt, tst, band, bst); }
+    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats, tables, flt, fst, support_path, tflt, tst, band, bst, subj, sst); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
     if (rc != BLU_OK) return rc;
     if (getenv("BLU_INGEST_TRACE")) fprintf(stderr, "[pipeline] %-26s %.3f s\n", "tear-down (tables, strings)", now_s() - g_t_body_end);
@@ -2150,15 +2182,31 @@ int blu_build_consensus_identities_band(const char* blast_output_file, const cha
                                         blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats, const char* support_table_path,
                                         const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
                                         const blu_score_band* band, blu_score_band_stats* band_stats) {
+    return blu_build_consensus_identities_subject(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path,
+                                                  tables, filter, out_text, out_len, stats, filter_stats, support_table_path, taxon_filter,
+                                                  taxon_stats, band, band_stats, nullptr, nullptr);
+}
+
+int blu_build_consensus_identities_subject(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                           const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
+                                           const char* config_text, const char* out_path, const blu_tables_params* tables,
+                                           const blu_hit_filter* filter, char** out_text, size_t* out_len,
+                                           blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats, const char* support_table_path,
+                                           const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
+                                           const blu_score_band* band, blu_score_band_stats* band_stats,
+                                           const blu_subject_best* subject_best, blu_subject_best_stats* subject_stats) {
     if (tables && !tables->report_path && !tables->sample_table_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     if (filter_stats) *filter_stats = blu_hit_filter_stats{0, 0};
     clear_taxon_stats(taxon_filter, taxon_stats);
     if (band_stats) *band_stats = blu_score_band_stats{0, 0, 0, 0};
+    if (subject_stats) *subject_stats = blu_subject_best_stats{0, 0, 0, 0};
     if (out_path)
         return consensus_to_file(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, tables,
-                                 stats, filter, filter_stats, support_table_path, taxon_filter, taxon_stats, band, band_stats);
+                                 stats, filter, filter_stats, support_table_path, taxon_filter, taxon_stats, band, band_stats, subject_best,
+                                 subject_stats);
     return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, tables, out_text,
-                             out_len, stats, filter, filter_stats, support_table_path, taxon_filter, taxon_stats, band, band_stats);
+                             out_len, stats, filter, filter_stats, support_table_path, taxon_filter, taxon_stats, band, band_stats,
+                             subject_best, subject_stats);
 }
 
 int blu_build_consensus_identities_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
@@ -2228,9 +2276,21 @@ int blu_ingest_columns_band_on(const char* blast_output_file, const char* taxono
                                const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
                                const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
                                const blu_score_band* band, blu_score_band_stats* band_stats) {
+    return blu_ingest_columns_subject_on(blast_output_file, taxonomies_file, use_taxid, device, filter, out, filter_stats, taxon_filter, taxon_stats,
+                                         band, band_stats, nullptr, nullptr);
+}
+
+int blu_ingest_columns_subject_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                                  const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
+                                  const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
+                                  const blu_score_band* band, blu_score_band_stats* band_stats,
+                                  const blu_subject_best* subject_best, blu_subject_best_stats* subject_stats) {
     if (!blast_output_file || !taxonomies_file || !out) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     if (filter && (filter->mask & ~15u)) { set_error("hit filter: unknown bits in the mask"); return BLU_ERR_INVALID_ARG; }
     if (band_stats) *band_stats = blu_score_band_stats{0, 0, 0, 0};
+    if (subject_stats) *subject_stats = blu_subject_best_stats{0, 0, 0, 0};
+    if (int src = check_subject_best(subject_best)) return src;
+    if (subject_best && !subject_best->mask) subject_best = nullptr;
     if (int brc = check_score_band(band)) return brc;
     if (band && !band->mask) band = nullptr;
     if (filter_stats) *filter_stats = blu_hit_filter_stats{0, 0};
@@ -2253,13 +2313,22 @@ int blu_ingest_columns_band_on(const char* blast_output_file, const char* taxono
     put_taxon_stats(taxa.get(), ht.n_lines, taxon_stats);
     ht.wait_strings();
     if (!ht.strings_ok) { set_error("out of memory while building the query / accession strings"); return BLU_ERR_ALLOC; }
-    const size_t nh = ht.bitscore.size(), nq = ht.query_names.size();
+    size_t nh = ht.bitscore.size();
+    const size_t nq = ht.query_names.size(), nh_in = nh;   // (nh_in: the rows the filters kept, whatever is selected below)
+    if (subject_stats) *subject_stats = blu_subject_best_stats{nh, nh, nq, 0};
+    if (subject_best && nh) {   // (the host-column hook, before the band's)
+        uint64_t n_out = nh;
+        rc = blu_hits_subject_best(device, ht.bitscore.data(), ht.align_len.data(), ht.tax_desc_row.data(), ht.acc_rank.data(), ht.pident.data(),
+                                   ht.seg_off.data(), nh, nq, 0, subject_best, nullptr, BLU_UNMATCHED_TAXID, &n_out, nullptr, subject_stats);
+        if (rc != BLU_OK) return rc;
+        nh = n_out;
+    }
     if (band_stats) { band_stats->n_hits = nh; band_stats->n_queries = nq; }
     if (band && nh) {   // (the use-case's host-column hook: the host-pointer route of the one kernel)
         rc = blu_hits_score_band(device, ht.bitscore.data(), ht.seg_off.data(), nh, nq, 0, band, nullptr, ht.bitscore.data(), band_stats);
         if (rc != BLU_OK) return rc;
     }
-    if (filter_stats) { const bool on = (filter && (filter->mask & 15u)) || taxa; filter_stats->n_lines = on ? ht.n_lines : nh; filter_stats->n_kept = on ? ht.n_kept : nh; }
+    if (filter_stats) { const bool on = (filter && (filter->mask & 15u)) || taxa; filter_stats->n_lines = on ? ht.n_lines : nh_in; filter_stats->n_kept = on ? ht.n_kept : nh_in; }
     auto dup = [](const void* src, size_t bytes) -> void* { void* p = malloc(bytes ? bytes : 1); if (p && bytes) memcpy(p, src, bytes); return p; };
     auto pack = [](const std::vector<std::string>& v, uint64_t* bytes) -> char* {
         size_t n = 0;

@@ -445,6 +445,84 @@ def score_band_device(seg_off, bitscore, top_percent_milli: Optional[int] = None
     return N.band_counts(st)
 
 
+def subject_keep_host(seg_off, bitscore, acc_rank, device: int = 0):
+    """blu_hits_subject_keep on host arrays: -> (the uint32 keep words, the counts).  The two columns and the
+    offsets are uploaded and the device kernels run."""
+    seg = np.ascontiguousarray(seg_off, dtype=np.uint64)
+    bs = np.ascontiguousarray(bitscore, dtype=np.int32)
+    acc = np.ascontiguousarray(acc_rank, dtype=np.uint32)
+    assert len(acc) == len(bs)
+    keep, st = np.empty(len(bs), dtype=np.uint32), N.SubjectBestStats()
+    rc = N.lib().blu_hits_subject_keep(device, bs.ctypes.data if len(bs) else None, acc.ctypes.data if len(bs) else None, seg.ctypes.data,
+                                       len(bs), len(seg) - 1, 0, None, keep.ctypes.data if len(bs) else None, C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_hits_subject_keep")
+    return keep, N.subject_counts(st)
+
+
+def subject_keep_device(seg_off, bitscore, acc_rank, keep, stream: Optional[int] = None) -> dict:
+    """blu_hits_subject_keep on torch CUDA tensors (seg_off int64, bitscore int32, acc_rank int32 holding the uint32 bits, keep
+    int32): the verdicts go to `keep`; -> the counts.  Returns when `keep` is complete."""
+    import torch
+
+    for t, dt in ((seg_off, torch.int64), (bitscore, torch.int32), (acc_rank, torch.int32), (keep, torch.int32)):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dt, (t.dtype, t.device)
+    assert keep.numel() == bitscore.numel() == acc_rank.numel()
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    st = N.SubjectBestStats()
+    dev = bitscore.device.index or 0
+    rc = N.lib().blu_hits_subject_keep(dev, bitscore.data_ptr(), acc_rank.data_ptr(), seg_off.data_ptr(), bitscore.numel(),
+                                       seg_off.numel() - 1, 1, stream, keep.data_ptr(), C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_hits_subject_keep")
+    return N.subject_counts(st)
+
+
+def subject_best_host(seg_off, bitscore, align_len, tax_desc_row, acc_rank, pident, device: int = 0,
+                      unmatched_marker: int = N.BLU_UNMATCHED_TAXID, mask: Optional[int] = N.SUBJECT_BEST_PER_QUERY):
+    """blu_hits_subject_best on host arrays: -> (a dict of the compacted seg_off and five columns, n_unmatched,
+    the counts).  The arguments are not changed; mask None passes a NULL selection."""
+    seg = np.array(seg_off, dtype=np.uint64)
+    cols = [np.array(bitscore, dtype=np.int32), np.array(align_len, dtype=np.int32), np.array(tax_desc_row, dtype=np.uint32),
+            np.array(acc_rank, dtype=np.uint32), np.array(pident, dtype=np.float64)]
+    n = len(cols[0])
+    assert all(len(c) == n for c in cols)
+    sel = N.SubjectBestC(mask, 0) if mask is not None else None
+    st, n_out, n_un = N.SubjectBestStats(), C.c_uint64(0), C.c_uint64(0)
+    rc = N.lib().blu_hits_subject_best(device, *[c.ctypes.data if n else None for c in cols], seg.ctypes.data, n, len(seg) - 1, 0,
+                                       C.byref(sel) if sel is not None else None, None, unmatched_marker, C.byref(n_out),
+                                       C.byref(n_un), C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_hits_subject_best")
+    k = int(n_out.value)
+    names = ("bitscore", "align_len", "tax_desc_row", "acc_rank", "pident")
+    out = {name: c[:k].copy() for name, c in zip(names, cols)}
+    out["seg_off"] = seg
+    return out, int(n_un.value), N.subject_counts(st)
+
+
+def subject_best_device(seg_off, bitscore, align_len, tax_desc_row, acc_rank, pident, unmatched_marker: int = N.BLU_UNMATCHED_TAXID,
+                        stream: Optional[int] = None):
+    """blu_hits_subject_best on torch CUDA tensors, in place (seg_off int64, the 32-bit columns int32, pident float64):
+    -> (the rows left, n_unmatched, the counts); the kept rows are the front of each tensor."""
+    import torch
+
+    for t, dt in ((seg_off, torch.int64), (bitscore, torch.int32), (align_len, torch.int32), (tax_desc_row, torch.int32),
+                  (acc_rank, torch.int32), (pident, torch.float64)):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dt, (t.dtype, t.device)
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    sel, st, n_out, n_un = N.SubjectBestC(N.SUBJECT_BEST_PER_QUERY, 0), N.SubjectBestStats(), C.c_uint64(0), C.c_uint64(0)
+    dev = bitscore.device.index or 0
+    rc = N.lib().blu_hits_subject_best(dev, bitscore.data_ptr(), align_len.data_ptr(), tax_desc_row.data_ptr(), acc_rank.data_ptr(),
+                                       pident.data_ptr(), seg_off.data_ptr(), bitscore.numel(), seg_off.numel() - 1, 1, C.byref(sel),
+                                       stream, unmatched_marker, C.byref(n_out), C.byref(n_un), C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_hits_subject_best")
+    return int(n_out.value), int(n_un.value), N.subject_counts(st)
+
+
 def records_from_tensor(out) -> np.ndarray:
     """uint8 CUDA/CPU tensor -> numpy structured array of blu_result."""
     return out.detach().cpu().numpy().view(np.uint8).reshape(-1)[: (out.numel() * out.element_size()) // 32 * 32].view(RESULT_DTYPE)

@@ -235,13 +235,15 @@ class IngestColumns(C.Structure):
 def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = False, device: int = -1,
                    hit_filter: Union[None, dict, HitFilter] = None,
                    taxon_filter: Union[None, dict, TaxonFilter] = None,
-                   score_band: Union[None, dict, ScoreBand] = None) -> dict:
+                   score_band: Union[None, dict, ScoreBand] = None, best_hit_per_subject: bool = False) -> dict:
     """The SoA columns of the ingest (include/blu_pipeline.h: blu_ingest_columns_on) as numpy arrays + the two string tables.
     hit_filter (a dict or HitFilter): the columns of the lines it keeps (blu_ingest_columns_filtered_on), plus `n_lines` and
     `n_kept`.  taxon_filter (a dict or TaxonFilter): the same under a taxon filter (blu_ingest_columns_taxa_on), alone or
     beside hit_filter, plus `taxon_filter`: its counts (n_lines, n_excluded, n_not_only, exclude, excluded_by).  score_band (a
     dict or ScoreBand): the bitscore column with the band applied (blu_ingest_columns_band_on; needs device >= 0), plus
-    `score_band`: its counts (n_hits, n_raised, n_queries, n_widened)."""
+    `score_band`: its counts (n_hits, n_raised, n_queries, n_widened).  best_hit_per_subject: the columns with only the best
+    row of every (query, subject accession) pair, selected before the band (blu_ingest_columns_subject_on; needs
+    device >= 0), plus `subject_best`: its counts (n_hits, n_kept, n_queries, n_thinned)."""
     import numpy as np
     L = _bind()
     L.blu_ingest_columns_on.restype = C.c_int
@@ -251,7 +253,22 @@ def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = Fa
     flt, fst = _hit_filter(hit_filter), HitFilterStats()
     tf = _taxon_filter(taxon_filter)
     band, bst = _score_band(score_band), N.ScoreBandStats()
-    if band is not None:
+    sel, sst = (N.SubjectBestC(N.SUBJECT_BEST_PER_QUERY, 0) if best_hit_per_subject else None), N.SubjectBestStats()
+    if sel is not None:
+        L.blu_ingest_columns_subject_on.restype = C.c_int
+        L.blu_ingest_columns_subject_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(HitFilterC),
+                                                    C.POINTER(IngestColumns), C.POINTER(HitFilterStats),
+                                                    C.POINTER(TaxonFilterC), C.POINTER(TaxonFilterStats),
+                                                    C.POINTER(N.ScoreBandC), C.POINTER(N.ScoreBandStats),
+                                                    C.POINTER(N.SubjectBestC), C.POINTER(N.SubjectBestStats)]
+        rc = L.blu_ingest_columns_subject_on(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
+                                             C.byref(flt) if flt is not None else None, C.byref(c), C.byref(fst),
+                                             C.byref(tf.filter) if tf is not None else None,
+                                             C.byref(tf.stats) if tf is not None else None,
+                                             C.byref(band) if band is not None else None, C.byref(bst), C.byref(sel), C.byref(sst))
+        if rc != N.BLU_OK:
+            raise N.BluError(rc, "blu_ingest_columns_subject_on")
+    elif band is not None:
         L.blu_ingest_columns_band_on.restype = C.c_int
         L.blu_ingest_columns_band_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(HitFilterC),
                                                  C.POINTER(IngestColumns), C.POINTER(HitFilterStats),
@@ -300,6 +317,8 @@ def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = Fa
             out["taxon_filter"] = tf.counts()
         if band is not None:
             out["score_band"] = N.band_counts(bst)
+        if sel is not None:
+            out["subject_best"] = N.subject_counts(sst)
         return out
     finally:
         L.blu_ingest_columns_free(C.byref(c))
@@ -347,7 +366,7 @@ def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: s
                                out_format: str = "json", device: int = 0, lenient: bool = False, parse: bool = True,
                                config=None, out_path: Optional[str] = None, hit_filter: Union[None, dict, HitFilter] = None,
                                taxon_filter: Union[None, dict, TaxonFilter] = None,
-                               score_band: Union[None, dict, ScoreBand] = None):
+                               score_band: Union[None, dict, ScoreBand] = None, best_hit_per_subject: bool = False):
     """Returns (results, stats).  With out_path the document is written there by the library (no copy through Python) and
     (None, stats) is returned.  results: the parsed `results` list (json) / list of records (jsonl), sorted by
     query, or the raw text when parse=False.  config: Some(BlastBuilder) of the run-with-consensus path
@@ -356,10 +375,13 @@ def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: s
     also has `n_lines` and `n_kept`.  taxon_filter (a dict or TaxonFilter; None = no filter): only the lines whose lineage
     passes take part; stats then also has `taxon_filter`, its counts.  score_band (a dict or ScoreBand; None =
     exact ties): the hits inside the band under a query's top bit-score count as tied with it, after the
-    filters; stats then also has `score_band`, its counts (n_hits, n_raised, n_queries, n_widened)."""
+    filters; stats then also has `score_band`, its counts (n_hits, n_raised, n_queries, n_widened).  best_hit_per_subject: of
+    the lines of one (query, subject accession) pair only the best takes part — the highest truncated bit-score, the first in
+    file order among equals — after the filters and before the band; stats then also has `subject_best`, its
+    counts (n_hits, n_kept, n_queries, n_thinned), and n_hits / n_unmatched_rows count the kept lines."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, None, "one", hit_filter=hit_filter, taxon_filter=taxon_filter,
-                  score_band=score_band)
+                  score_band=score_band, best_hit_per_subject=best_hit_per_subject)
 
 
 def build_consensus_identities_with_report(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -370,13 +392,14 @@ def build_consensus_identities_with_report(blast_output: str, taxonomies_file: s
                                            out_path: Optional[str] = None, report_path: str = "report.tsv",
                                            report_weight: str = "one", hit_filter: Union[None, dict, HitFilter] = None,
                                            taxon_filter: Union[None, dict, TaxonFilter] = None,
-                                           score_band: Union[None, dict, ScoreBand] = None):
+                                           score_band: Union[None, dict, ScoreBand] = None,
+                                           best_hit_per_subject: bool = False):
     """build_consensus_identities plus the taxon abundance report of its results, counted on the GPU and written to
     report_path after the document (include/blu_pipeline.h: blu_build_consensus_identities_report).
     report_weight: "one" (results) or "size" (dereplicated reads named in the query)."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, report_path, report_weight, hit_filter=hit_filter, taxon_filter=taxon_filter,
-                  score_band=score_band)
+                  score_band=score_band, best_hit_per_subject=best_hit_per_subject)
 
 
 def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -389,7 +412,8 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
                                            hit_filter: Union[None, dict, HitFilter] = None,
                                            support_table_path: Optional[str] = None,
                                            taxon_filter: Union[None, dict, TaxonFilter] = None,
-                                           score_band: Union[None, dict, ScoreBand] = None):
+                                           score_band: Union[None, dict, ScoreBand] = None,
+                                           best_hit_per_subject: bool = False):
     """build_consensus_identities plus the taxon abundance report (report_path), the per-sample table (sample_table_path,
     DESIGN.md §13), or both, counted on the GPU and written in the order document, report, table
     (include/blu_pipeline.h: blu_build_consensus_identities_tables).  report_weight serves both files.  A query whose name
@@ -399,16 +423,18 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
     and bits / support_bits sum the raised scores."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, report_path, report_weight, sample_table_path, hit_filter=hit_filter,
-                  support_table_path=support_table_path, taxon_filter=taxon_filter, score_band=score_band)
+                  support_table_path=support_table_path, taxon_filter=taxon_filter, score_band=score_band,
+                  best_hit_per_subject=best_hit_per_subject)
 
 
 def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device, lenient,
            parse, config, out_path, report_path, report_weight, sample_table_path=None, hit_filter=None,
-           support_table_path=None, taxon_filter=None, score_band=None):
+           support_table_path=None, taxon_filter=None, score_band=None, best_hit_per_subject=False):
     L = _bind()
     flt, fst = _hit_filter(hit_filter), HitFilterStats()
     tf = _taxon_filter(taxon_filter)
     band, bst = _score_band(score_band), N.ScoreBandStats()
+    sel, sst = (N.SubjectBestC(N.SUBJECT_BEST_PER_QUERY, 0) if best_hit_per_subject else None), N.SubjectBestStats()
     p = PipelineParams()
     p.cutoffs.taxon = N.TAXON[taxon]
     p.cutoffs.has_custom = 1 if custom_taxon_values is not None else 0
@@ -443,9 +469,42 @@ def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_tax
             stats["taxon_filter"] = tf.counts()
         if band is not None:
             stats["score_band"] = N.band_counts(bst)
+        if sel is not None:
+            stats["subject_best"] = N.subject_counts(sst)
         return stats
 
-    if band is not None or tf is not None:
+    if sel is not None:
+        # the best hit per subject: the entry point that takes everything (include/blu_pipeline.h:
+        # blu_build_consensus_identities_subject; the calls below are this one with a NULL selection)
+        tp = None
+        if report_path is not None or sample_table_path is not None:
+            tp = TablesParams(str(report_path).encode() if report_path is not None else None,
+                              str(sample_table_path).encode() if sample_table_path is not None else None,
+                              REPORT_WEIGHT[report_weight], 0)
+        L.blu_build_consensus_identities_subject.restype = C.c_int
+        L.blu_build_consensus_identities_subject.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
+                                                             C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(TablesParams),
+                                                             C.POINTER(HitFilterC), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                             C.POINTER(PipelineStats), C.POINTER(HitFilterStats), C.c_char_p,
+                                                             C.POINTER(TaxonFilterC), C.POINTER(TaxonFilterStats),
+                                                             C.POINTER(N.ScoreBandC), C.POINTER(N.ScoreBandStats),
+                                                             C.POINTER(N.SubjectBestC), C.POINTER(N.SubjectBestStats)]
+        rc = L.blu_build_consensus_identities_subject(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
+                                                      taxonomies_file.encode(), C.byref(p), run_id, cfg_text,
+                                                      out_path.encode() if out_path is not None else None,
+                                                      C.byref(tp) if tp is not None else None,
+                                                      C.byref(flt) if flt is not None else None,
+                                                      C.byref(text), C.byref(n), C.byref(st), C.byref(fst),
+                                                      str(support_table_path).encode() if support_table_path is not None else None,
+                                                      C.byref(tf.filter) if tf is not None else None,
+                                                      C.byref(tf.stats) if tf is not None else None,
+                                                      C.byref(band) if band is not None else None, C.byref(bst),
+                                                      C.byref(sel), C.byref(sst))
+        if rc != N.BLU_OK:
+            raise N.BluError(rc, "blu_build_consensus_identities_subject")
+        if out_path is not None:
+            return None, stats_of()
+    elif band is not None or tf is not None:
         # a score band or a taxon filter: one entry point for every combination (include/blu_pipeline.h:
         # blu_build_consensus_identities_band; blu_build_consensus_identities_taxa is this call without a band)
         tp = None

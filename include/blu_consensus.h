@@ -401,6 +401,43 @@ typedef struct blu_score_band_stats {
 int blu_hits_score_band(int device, const int32_t* bitscore, const uint64_t* seg_off, uint64_t n_hits, uint64_t n_queries,
                         int on_device, const blu_score_band* band, void* stream, int32_t* out, blu_score_band_stats* stats);
 
+/* -------------------------------------------------------------------------- */
+/* Best hit per subject (additive, ABI v5; not in the reference).  BLAST writes one line per HSP, so a subject
+ * that aligns to a query in several places occurs several times in the query's segment.  A PAIR is (query, acc_rank): the
+ * rows of one segment with one acc_rank, whatever their tax rows.  Of a pair's rows the BEST is kept and the others are
+ * dropped: the best has the highest truncated bit-score, and of equal scores it is the first row of the segment.  In one
+ * 64-bit value, with i the row's index inside its segment:
+ *   pack = (uint64)((uint32)bitscore ^ 0x80000000) << 32 | (0xFFFFFFFF - i)
+ * and a row is kept iff no row of its segment has its acc_rank and a larger pack.  Every query keeps at least one row and
+ * every pair keeps exactly one; the pass is idempotent. */
+#define BLU_SUBJECT_BEST_PER_QUERY 1u
+typedef struct blu_subject_best { uint32_t mask; uint32_t reserved; } blu_subject_best;
+typedef struct blu_subject_best_stats {
+    uint64_t n_hits;      /* rows in */
+    uint64_t n_kept;      /* rows kept */
+    uint64_t n_queries;
+    uint64_t n_thinned;   /* queries that lost at least one row */
+} blu_subject_best_stats;
+/* The verdicts alone: keep_out[i] = 1 (row i is its pair's best) or 0, one 32-bit word per row, under seg_off[n_queries + 1];
+ * stats may be NULL.  Decided on the device (csrc/subject_kernel.hip).  on_device = 1: device pointers on `device`; the call
+ * waits for `stream` (a hipStream_t, NULL = default), runs on the default stream and returns when keep_out and the counts are
+ * complete.  on_device = 0: the two columns and the offsets are uploaded, the same kernels run, the verdicts are copied back
+ * -- there is no second implementation.  Offsets beyond n_hits are clamped to it and a decreasing pair is an empty segment: a
+ * corrupt table reads and writes nothing outside the columns; a row that no segment names gets 0.  BLU_ERR_INVALID_ARG, before
+ * any device is asked for: a NULL array with a non-zero count, n_hits >= 2^32 or n_queries >= 2^32 (the row index inside a
+ * segment and the query in the long path's key are 32 bits; with n_queries < 2^32 no key equals the table's empty key ~0);
+ * after the device pass: segments longer than 64 rows that overlap (their rows sum to more than n_hits). */
+int blu_hits_subject_keep(int device, const int32_t* bitscore, const uint32_t* acc_rank, const uint64_t* seg_off, uint64_t n_hits,
+                          uint64_t n_queries, int on_device, void* stream, uint32_t* keep_out, blu_subject_best_stats* stats);
+/* The same pass, then the compaction of the five columns and seg_off IN PLACE: the kept rows move to the front of each column in
+ * their order (the placement is an exclusive scan of the verdicts), seg_off[q] becomes the number of kept rows before it.
+ * *n_hits_out: the rows left; *n_unmatched_out: how many of them have tax_desc_row == unmatched_marker (either may be NULL).
+ * When every row is kept the columns are not touched.  `sel`: NULL or an empty mask leaves the table as it is and asks for no
+ * device; unknown mask bits are BLU_ERR_INVALID_ARG.  Device pointers must be 16-byte aligned.  Otherwise as above. */
+int blu_hits_subject_best(int device, int32_t* bitscore, int32_t* align_len, uint32_t* tax_desc_row, uint32_t* acc_rank, double* pident,
+                          uint64_t* seg_off, uint64_t n_hits, uint64_t n_queries, int on_device, const blu_subject_best* sel, void* stream,
+                          uint32_t unmatched_marker, uint64_t* n_hits_out, uint64_t* n_unmatched_out, blu_subject_best_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

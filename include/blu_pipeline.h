@@ -228,6 +228,24 @@ int blu_build_consensus_identities_band(const char* blast_output_file, const cha
                                         blu_taxon_filter_stats* taxon_stats, const blu_score_band* band,
                                         blu_score_band_stats* band_stats);
 
+/* Best hit per subject (not in the reference; include/blu_consensus.h: blu_subject_best).  The arguments of
+ * blu_build_consensus_identities_band plus the selection and its counts (subject_stats may be NULL).  Of the lines of one
+ * (query, subject accession) pair that the hit and taxon filters keep, the one with the highest truncated bit-score stays,
+ * the first in file order among equals, and the others are dropped before the band and the engine run.  The run gives, byte
+ * for byte, what the run without the selection gives on a copy of the (filtered) table without the dropped lines: the document,
+ * the report, the sample table and the support table; the stats' n_hits and n_unmatched_rows are those of the copy.  Applied
+ * once per run on the device (csrc/subject_kernel.hip): on the columns the GPU ingest left there, or through the host-pointer
+ * route on host columns.  A NULL selection or an empty mask is the call without it. */
+int blu_build_consensus_identities_subject(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                           const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
+                                           const char* config_text, const char* out_path, const blu_tables_params* tables,
+                                           const blu_hit_filter* filter, char** out_text, size_t* out_len,
+                                           blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats,
+                                           const char* support_table_path, const blu_taxon_filter* taxon_filter,
+                                           blu_taxon_filter_stats* taxon_stats, const blu_score_band* band,
+                                           blu_score_band_stats* band_stats, const blu_subject_best* subject_best,
+                                           blu_subject_best_stats* subject_stats);
+
 /* The text-ingest half alone (no GPU): DB JSON + outfmt-6 TSV -> SoA columns, as blu_build_consensus_identities does it.
  * Fills stats (rows, queries, taxids, unmatched rows, load times) and *checksum with an FNV-1a hash over every SoA
  * column, the segment offsets and the query names — identical for any BLU_INGEST_THREADS value.  For tests and for
@@ -272,6 +290,13 @@ int blu_ingest_columns_band_on(const char* blast_output_file, const char* taxono
                                const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
                                const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
                                const blu_score_band* band, blu_score_band_stats* band_stats);
+/* The same with the best hit per subject selected first (above): the arguments of blu_ingest_columns_band_on plus the selection
+ * and its counts.  A selection with a non-empty mask needs a device (device >= 0) whichever parser ran. */
+int blu_ingest_columns_subject_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                                  const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
+                                  const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
+                                  const blu_score_band* band, blu_score_band_stats* band_stats,
+                                  const blu_subject_best* subject_best, blu_subject_best_stats* subject_stats);
 void blu_ingest_columns_free(blu_ingest_columns* cols);
 
 /* Which parser the calling thread's last ingest used: 0 = CPU, 1 = GPU. */
