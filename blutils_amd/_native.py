@@ -19,15 +19,10 @@ EXPORTS = (
     "blu_hits_subject_keep", "blu_hits_subject_best",
 )
 # include/blu_pipeline.h
-PIPELINE_EXPORTS = ("blu_build_consensus_identities", "blu_free_text", "blu_custom_taxon_from_file", "blu_ingest_only",
-                    "blu_db_cache_build", "blu_build_consensus_identities_cfg", "blu_ingest_only_on", "blu_last_ingest_path",
-                    "blu_build_consensus_identities_to_file", "blu_ingest_columns_on", "blu_ingest_columns_free",
-                    "blu_taxdb_build", "blu_seqdb_export", "blu_qiime_taxonomy_tsv", "blu_build_consensus_identities_report",
-                    "blu_build_consensus_identities_tables", "blu_build_consensus_identities_filtered",
-                    "blu_ingest_columns_filtered_on", "blu_build_consensus_identities_support",
-                    "blu_build_consensus_identities_taxa", "blu_ingest_columns_taxa_on",
-                    "blu_build_consensus_identities_band", "blu_ingest_columns_band_on",
-                    "blu_build_consensus_identities_subject", "blu_ingest_columns_subject_on")
+PIPELINE_EXPORTS = ("blu_build_consensus", "blu_build_consensus_identities", "blu_build_consensus_identities_cfg",
+                    "blu_build_consensus_identities_to_file", "blu_free_text", "blu_custom_taxon_from_file", "blu_ingest_only",
+                    "blu_ingest_only_on", "blu_ingest_columns_on", "blu_ingest_columns_selected", "blu_ingest_columns_free",
+                    "blu_last_ingest_path", "blu_db_cache_build", "blu_taxdb_build", "blu_seqdb_export", "blu_qiime_taxonomy_tsv")
 
 BLU_UNMATCHED_TAXID = 0xFFFFFFFF
 BLU_NONE_U8, BLU_NONE_U16, BLU_MAR_NEVER_EQUAL = 0xFF, 0xFFFF, 0xFFFE

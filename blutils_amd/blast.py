@@ -120,7 +120,7 @@ class BlastBuilder:
                 ("wordSize", str(self.word_size))]
 
     def render(self, out_format: str) -> str:
-        """The config as it stands in the result document (include/blu_pipeline.h: blu_build_consensus_identities_cfg)."""
+        """The config as it stands in the result document (include/blu_pipeline.h: blu_consensus_request.config_text)."""
         items = self.as_items()
         if out_format == "json":                 # serde_json::to_string_pretty, nested one level deep
             return "{\n" + ",\n".join(f'    "{k}": {v}' for k, v in items) + "\n  }"

@@ -1409,7 +1409,7 @@ bool parallel_dynamic(size_t n, unsigned nthreads, F&& f) {
     return !oom;
 }
 
-// The report of one pipeline run (blu_build_consensus_identities_report): weights from the query names, the device pass over
+// The report of one pipeline run (blu_consensus_request.report_path): weights from the query names, the device pass over
 // the records (in place on the device path; uploaded on the host path), the header-only queries as unclassified, the text.
 int build_report(const Db& db, const HitTable& ht, const blu_taxonomy* tax, const Column<blu_result>& recs, const DeviceRecords& kept,
                  bool on_device, const std::vector<uint32_t>& eng_rows, const std::vector<std::string>& extra, int32_t weight,
@@ -1455,7 +1455,7 @@ int build_report(const Db& db, const HitTable& ht, const blu_taxonomy* tax, cons
     return BLU_OK;
 }
 
-// The per-sample table of one pipeline run (blu_build_consensus_identities_tables): the samples from the query names and
+// The per-sample table of one pipeline run (blu_consensus_request.sample_table_path): the samples from the query names and
 // the header-only names (ids in ascending byte order = column order), the weights, the device pass over the records (in
 // place on the device path; uploaded on the host path), the header-only queries as unclassified in their sample, the text.
 int build_sample_table(const Db& db, const HitTable& ht, const blu_taxonomy* tax, const Column<blu_result>& recs,
@@ -1530,7 +1530,7 @@ int build_sample_table(const Db& db, const HitTable& ht, const blu_taxonomy* tax
     return BLU_OK;
 }
 
-// The support table of one pipeline run (blu_build_consensus_identities_support): the device pass over the
+// The support table of one pipeline run (blu_consensus_request.support_table_path): the device pass over the
 // run's records and columns (in place on the device path; the two columns, the offsets and the records uploaded on the host
 // path), then one line per result in the document's order.  Item: {name, q}, q < 0 for a header without hits.
 template <class Items>
@@ -1591,30 +1591,91 @@ int build_support(const Db& db, const HitTable& ht, const blu_taxonomy* tax, con
     return BLU_OK;
 }
 
+// One run's hit selection (include/blu_pipeline.h: blu_hit_selection) as the use-case and the
+// ingest-columns call both take it: an option with an empty mask or two empty lists is absent, the taxon lists are resolved
+// against the loaded lineages, and the counts are filled where the caller will read them.
+struct Selection {
+    const blu_hit_selection asked;                // (as the caller gave it; the four below: what of it is active)
+    const blu_hit_filter* flt = nullptr;
+    const blu_taxon_filter* tflt = nullptr;
+    const blu_subject_best* subj = nullptr;
+    const blu_score_band* band = nullptr;
+    std::unique_ptr<TaxonCodes> taxa;             // (the taxon filter as the parsers read it)
+    blu_hit_selection_stats own{};                // (a caller that wants no counts)
+    blu_hit_selection_stats* const st;
+    bool subject_done = false, band_done = false; // (once per run, on the device columns or on the host columns)
+
+    // the caller's counts start at zero, its excluded_by array included, whatever the call then does
+    Selection(const blu_hit_selection* sel, blu_hit_selection_stats* stats) : asked(sel ? *sel : blu_hit_selection{}), st(stats ? stats : &own) {
+        uint64_t* const by = st->taxon_filter.excluded_by;
+        *st = blu_hit_selection_stats{};
+        st->taxon_filter.excluded_by = by;
+        const blu_taxon_filter* f = asked.taxon_filter;
+        if (by && f && f->n_exclude <= BLU_TAXON_FILTER_MAX_EXCLUDE) for (uint64_t k = 0; k < f->n_exclude; ++k) by[k] = 0;
+    }
+    // before any file is opened: unknown mask bits and band values out of range are refused
+    int check() {
+        if (asked.hit_filter && (asked.hit_filter->mask & ~15u)) { set_error("hit filter: unknown bits in the mask"); return BLU_ERR_INVALID_ARG; }
+        if (int rc = check_score_band(asked.score_band)) return rc;
+        if (int rc = check_subject_best(asked.subject_best)) return rc;
+        if (asked.hit_filter && (asked.hit_filter->mask & 15u)) flt = asked.hit_filter;
+        if (asked.taxon_filter && (asked.taxon_filter->n_exclude || asked.taxon_filter->n_only)) tflt = asked.taxon_filter;
+        if (asked.subject_best && asked.subject_best->mask) subj = asked.subject_best;
+        if (asked.score_band && asked.score_band->mask) band = asked.score_band;
+        return BLU_OK;
+    }
+    // a taxon filter: the lists resolved against the lineages -> one code per row
+    int resolve(const Db& db, unsigned nthreads) {
+        if (!tflt) return BLU_OK;
+        taxa = std::make_unique<TaxonCodes>();
+        return taxon_codes(db, *tflt, nthreads, *taxa);
+    }
+    // the parser's counts, and the table as it stands before options 2 and 3
+    void loaded(const HitTable& ht) {
+        const bool on = flt || taxa;
+        st->hit_filter = blu_hit_filter_stats{on ? ht.n_lines : ht.n_hits, on ? ht.n_kept : ht.n_hits};
+        if (taxa) {
+            st->taxon_filter.n_lines = ht.n_lines; st->taxon_filter.n_excluded = taxa->n_excluded; st->taxon_filter.n_not_only = taxa->n_not_only;
+            if (st->taxon_filter.excluded_by) for (uint32_t k = 0; k < taxa->n_exclude; ++k) st->taxon_filter.excluded_by[k] = taxa->excluded_by[k];
+        }
+        st->subject_best = blu_subject_best_stats{ht.n_hits, ht.n_hits, ht.n_queries, 0};
+        st->score_band = blu_score_band_stats{ht.n_hits, 0, ht.n_queries, 0};
+    }
+    // Options 2 and 3 on host columns, through the host-pointer route of their kernels: whatever of the two has not been
+    // applied on the device columns.  The table's counts follow the kept rows.
+    int on_host_columns(int device, HitTable& ht, Trace* tr = nullptr) {
+        if (subj && !subject_done && ht.n_hits) {
+            uint64_t n_out = ht.n_hits, unmatched = ht.unmatched;
+            int rc = blu_hits_subject_best(device, ht.bitscore.data(), ht.align_len.data(), ht.tax_desc_row.data(), ht.acc_rank.data(),
+                                           ht.pident.data(), ht.seg_off.data(), ht.n_hits, ht.n_queries, 0, subj, nullptr, BLU_UNMATCHED_TAXID,
+                                           &n_out, &unmatched, &st->subject_best);
+            if (rc != BLU_OK) return rc;
+            ht.bitscore.resize(n_out); ht.align_len.resize(n_out); ht.tax_desc_row.resize(n_out); ht.acc_rank.resize(n_out); ht.pident.resize(n_out);
+            ht.n_hits = n_out; ht.unmatched = unmatched;
+            subject_done = true;
+            st->score_band.n_hits = n_out;
+            if (tr) tr->lap("subject best hit (host columns)");
+        }
+        if (band && !band_done && ht.n_hits) {
+            int rc = blu_hits_score_band(device, ht.bitscore.data(), ht.seg_off.data(), ht.n_hits, ht.n_queries, 0, band, nullptr,
+                                         ht.bitscore.data(), &st->score_band);
+            if (rc != BLU_OK) return rc;
+            band_done = true;
+            if (tr) tr->lap("score band (host columns)");
+        }
+        return BLU_OK;
+    }
+};
+
 // out_path != nullptr: the document is written there (an existing file is replaced, write_blutils_output.rs:57-63) by a
 // writer thread that follows the renderers piece by piece; otherwise the pieces are left in `document`.
-// the taxon filter's counts as the C ABI returns them
-void put_taxon_stats(const TaxonCodes* taxa, uint64_t n_lines, blu_taxon_filter_stats* tst) {
-    if (!tst || !taxa) return;
-    tst->n_lines = n_lines; tst->n_excluded = taxa->n_excluded; tst->n_not_only = taxa->n_not_only;
-    if (tst->excluded_by) for (uint32_t k = 0; k < taxa->n_exclude; ++k) tst->excluded_by[k] = taxa->excluded_by[k];
-}
-
-int build_document(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                   const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                   const char* config_text, const char* out_path, Document* document, blu_pipeline_stats* stats,
-                   const blu_tables_params* tables = nullptr, const blu_hit_filter* flt = nullptr, blu_hit_filter_stats* fst = nullptr,
-                   const char* support_path = nullptr, const blu_taxon_filter* tflt = nullptr, blu_taxon_filter_stats* tst = nullptr,
-                   const blu_score_band* band = nullptr, blu_score_band_stats* bst = nullptr,
-                   const blu_subject_best* subj = nullptr, blu_subject_best_stats* sst = nullptr) {
-    if (!blast_output_file || !taxonomies_file || !params || !document) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
-    if (flt && (flt->mask & ~15u)) { set_error("hit filter: unknown bits in the mask"); return BLU_ERR_INVALID_ARG; }
-    if (int brc = check_score_band(band)) return brc;
-    if (band && !band->mask) band = nullptr;      // (an empty mask: the call without a band)
-    if (int src = check_subject_best(subj)) return src;
-    if (subj && !subj->mask) subj = nullptr;      // (an empty mask: the call without the selection)
-    if (tables && ((!tables->report_path && !tables->sample_table_path) ||
-                   (tables->weight != BLU_REPORT_WEIGHT_ONE && tables->weight != BLU_REPORT_WEIGHT_SIZE))) {
+int build_document(const blu_consensus_request& rq, Document* document, blu_consensus_outcome* outcome) {
+    const blu_pipeline_params* const params = rq.params;
+    const char* const out_path = rq.out_path;
+    Selection sel(&rq.selection, &outcome->selection);
+    if (!rq.blast_output_file || !rq.taxonomies_file || !params) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    if (int rc = sel.check()) return rc;
+    if ((rq.report_path || rq.sample_table_path) && rq.weight != BLU_REPORT_WEIGHT_ONE && rq.weight != BLU_REPORT_WEIGHT_SIZE) {
         set_error("report: a path and weight BLU_REPORT_WEIGHT_ONE or BLU_REPORT_WEIGHT_SIZE are needed");
         return BLU_ERR_INVALID_ARG;
     }
@@ -1629,15 +1690,9 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     if (params->device >= 0) warm_up = std::thread([dev = params->device]() { warm_up_device(dev); });
     auto db_owner = std::make_unique<Db>();       // (on the heap, as the hit table below: handed to g_graveyard at the end)
     Db& db = *db_owner;
-    int rc = load_db(taxonomies_file, params->use_taxid != 0, db);     // mod.rs:64
+    int rc = load_db(rq.taxonomies_file, params->use_taxid != 0, db);     // mod.rs:64
     if (rc != BLU_OK) return rc;
-    // (a taxon filter: the lists resolved against the lineages -> one code per row)
-    if (tflt && !tflt->n_exclude && !tflt->n_only) tflt = nullptr;
-    std::unique_ptr<TaxonCodes> taxa;
-    if (tflt) {
-        taxa = std::make_unique<TaxonCodes>();
-        if ((rc = taxon_codes(db, *tflt, nthreads, *taxa)) != BLU_OK) return rc;
-    }
+    if ((rc = sel.resolve(db, nthreads)) != BLU_OK) return rc;
     st.t_load_db_s = now_s() - t0;
     tr.lap("load db");
     // the taxonomy table (sorted lineages, cutoff tables, upload) is built by a second thread while the hits are ingested
@@ -1668,10 +1723,9 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     t0 = now_s();
     auto ht_owner = std::make_unique<HitTable>();
     HitTable& ht = *ht_owner;
-    rc = load_hits(blast_output_file, db, ht, params->device, /*host_columns=*/false, flt, taxa.get());   // mod.rs:54, 72-82
+    rc = load_hits(rq.blast_output_file, db, ht, params->device, /*host_columns=*/false, sel.flt, sel.taxa.get());   // mod.rs:54, 72-82
     if (rc != BLU_OK) return rc;
-    if (fst) { const bool on = (flt && (flt->mask & 15u)) || taxa; fst->n_lines = on ? ht.n_lines : ht.n_hits; fst->n_kept = on ? ht.n_kept : ht.n_hits; }
-    put_taxon_stats(taxa.get(), ht.n_lines, tst);
+    sel.loaded(ht);
     st.t_load_hits_s = now_s() - t0;
     tr.lap("load hits");
     st.n_hits = ht.n_hits; st.n_queries = ht.n_queries; st.n_taxids = db.taxid.size(); st.n_unmatched_rows = ht.unmatched;
@@ -1701,29 +1755,27 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     if (force_host && ht.dev) { rc = download_columns(ht); if (rc != BLU_OK) return rc; }
     // the best hit per subject, once per run and before the band: on the device columns, which are compacted
     // where the engine will read them — a download after a failed device run then brings the thinned table — else on the host
-    // columns through the host-pointer route (below).  The table's counts follow the kept rows.
-    bool subject_applied = false;
-    blu_subject_best_stats subj_st{ht.n_hits, ht.n_hits, ht.n_queries, 0};
-    if (subj && ht.dev && !recs.empty() && !force_host) {
+    // columns (Selection::on_host_columns, below).  The table's counts follow the kept rows.
+    const bool on_device = ht.dev && !recs.empty() && !force_host;
+    if (sel.subj && on_device) {
         uint64_t unmatched = ht.unmatched;
-        rc = subject_best_hits(*ht.dev, &subj_st, &unmatched);
+        rc = subject_best_hits(*ht.dev, &sel.st->subject_best, &unmatched);
         if (rc != BLU_OK) return rc;
         ht.n_hits = ht.dev->n_hits; ht.unmatched = unmatched;
-        subject_applied = true;
+        sel.st->score_band.n_hits = ht.n_hits;
+        sel.subject_done = true;
         tr.lap("subject best hit (device)");
     }
     // the bit-score band, once per run: on the device column where the engine will read it in place — a
-    // download after a failed device run then brings the raised column — else on the host column through the host-pointer route
-    bool band_applied = false;
-    blu_score_band_stats band_st{ht.n_hits, 0, ht.n_queries, 0};
-    if (band && ht.dev && !recs.empty() && !force_host) {
+    // download after a failed device run then brings the raised column — else on the host column
+    if (sel.band && on_device) {
         rc = blu_hits_score_band(ht.dev->device, ht.dev->bitscore, (const uint64_t*)ht.dev->seg_off, ht.dev->n_hits, ht.dev->n_queries, 1,
-                                 band, nullptr, ht.dev->bitscore, &band_st);
+                                 sel.band, nullptr, ht.dev->bitscore, &sel.st->score_band);
         if (rc != BLU_OK) return rc;
-        band_applied = true;
+        sel.band_done = true;
         tr.lap("score band (device)");
     }
-    if (ht.dev && !recs.empty() && !force_host) {
+    if (on_device) {
         // the GPU ingest left the grouped columns on the device: the engine reads them in place and only the records and
         // the top-score rows come back (if that fails — e.g. no room for the work buffers — the columns are downloaded and
         // go through the staging path below)
@@ -1733,28 +1785,10 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     // (the device columns and the engine's work buffers stay with the hit table: they are freed off the caller's path at the end)
     if (!done_on_device) ht.dev.reset();
     if (!done_on_device) {
-        if (subj && !subject_applied && !recs.empty()) {
-            uint64_t n_out = ht.bitscore.size(), unmatched = ht.unmatched;
-            rc = blu_hits_subject_best(params->device, ht.bitscore.data(), ht.align_len.data(), ht.tax_desc_row.data(), ht.acc_rank.data(),
-                                       ht.pident.data(), ht.seg_off.data(), ht.bitscore.size(), ht.n_queries, 0, subj, nullptr, BLU_UNMATCHED_TAXID,
-                                       &n_out, &unmatched, &subj_st);
-            if (rc != BLU_OK) return rc;
-            ht.bitscore.resize(n_out); ht.align_len.resize(n_out); ht.tax_desc_row.resize(n_out); ht.acc_rank.resize(n_out); ht.pident.resize(n_out);
-            ht.n_hits = n_out; ht.unmatched = unmatched;
-            subject_applied = true;
-            band_st.n_hits = n_out;
-            tr.lap("subject best hit (host columns)");
-        }
+        if ((rc = sel.on_host_columns(params->device, ht, &tr)) != BLU_OK) return rc;
         eng_rows.resize(ht.tax_desc_row.size());
         for (size_t i = 0; i < eng_rows.size(); ++i)
             eng_rows[i] = ht.tax_desc_row[i] == BLU_UNMATCHED_TAXID ? BLU_UNMATCHED_TAXID : fwd[ht.tax_desc_row[i]];
-        if (band && !band_applied && !recs.empty()) {
-            rc = blu_hits_score_band(params->device, ht.bitscore.data(), ht.seg_off.data(), ht.bitscore.size(), ht.n_queries, 0, band, nullptr,
-                                     ht.bitscore.data(), &band_st);
-            if (rc != BLU_OK) return rc;
-            band_applied = true;
-            tr.lap("score band (host columns)");
-        }
         if (!recs.empty()) {
             blu_hits h{};
             h.bitscore = ht.bitscore.data(); h.tax_row = eng_rows.data();
@@ -1779,9 +1813,7 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
         }
         top_rows_from_columns(ht, recs, nthreads, top);
     }
-    if (bst) *bst = band_st;
-    if (sst) *sst = subj_st;
-    if (subject_applied) { st.n_hits = ht.n_hits; st.n_unmatched_rows = ht.unmatched; }
+    if (sel.subject_done) { st.n_hits = ht.n_hits; st.n_unmatched_rows = ht.unmatched; }
     st.t_engine_s = now_s() - t0;
     tr.lap("engine + top rows");
 
@@ -1795,12 +1827,12 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     items.reserve(ht.query_names.size());
     for (size_t q = 0; q < ht.query_names.size(); ++q) items.push_back({&ht.query_names[q], (int64_t)q});
     std::vector<std::string> extra;
-    if (headers) {
+    if (rq.headers) {
         std::unordered_map<std::string, uint32_t> have;
         for (size_t q = 0; q < ht.query_names.size(); ++q) have.emplace(ht.query_names[q], (uint32_t)q);
-        extra.reserve(n_headers);
-        for (uint64_t i = 0; i < n_headers; ++i)
-            if (!have.count(headers[i])) extra.emplace_back(headers[i]);
+        extra.reserve(rq.n_headers);
+        for (uint64_t i = 0; i < rq.n_headers; ++i)
+            if (!have.count(rq.headers[i])) extra.emplace_back(rq.headers[i]);
         for (auto& s : extra) items.push_back({&s, -1});
     }
     {
@@ -1837,20 +1869,20 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
             return BLU_ERR_REFERENCE_PANIC;
         }
     }
-    if (tables && tables->report_path) {
+    if (rq.report_path) {
         // the taxon report, from the records while they (on the device path: and the engine rows) are still on the device
-        rc = build_report(db, ht, tax, recs, kept, done_on_device, eng_rows, extra, tables->weight, document->report);
+        rc = build_report(db, ht, tax, recs, kept, done_on_device, eng_rows, extra, rq.weight, document->report);
         if (rc != BLU_OK) return rc;
         document->has_report = true;
         tr.lap("report");
     }
-    if (tables && tables->sample_table_path) {
-        rc = build_sample_table(db, ht, tax, recs, kept, done_on_device, eng_rows, extra, tables->weight, document->table);
+    if (rq.sample_table_path) {
+        rc = build_sample_table(db, ht, tax, recs, kept, done_on_device, eng_rows, extra, rq.weight, document->table);
         if (rc != BLU_OK) return rc;
         document->has_table = true;
         tr.lap("sample table");
     }
-    if (support_path) {
+    if (rq.support_table_path) {
         rc = build_support(db, ht, tax, recs, kept, done_on_device, eng_rows, top, items, document->support);
         if (rc != BLU_OK) return rc;
         document->has_support = true;
@@ -1859,8 +1891,8 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
     const bool pretty = params->out_format == BLU_OUT_JSON;
     const bool doc = pretty || params->out_format == BLU_OUT_JSON_COMPACT;   // one {results, config} document
     // write_blutils_output.rs:82-85: the config's run id, or a fresh one
-    const std::string run_id = (run_id_text && *run_id_text) ? std::string(run_id_text) : uuid_v4();
-    const std::string cfg = (config_text && *config_text) ? std::string(config_text) : std::string();
+    const std::string run_id = (rq.run_id_text && *rq.run_id_text) ? std::string(rq.run_id_text) : uuid_v4();
+    const std::string cfg = (rq.config_text && *rq.config_text) ? std::string(rq.config_text) : std::string();
     Renderer R{db, ht.accessions, top, tax};
     std::vector<Out>& pieces = document->pieces;
     pieces.clear();
@@ -1996,7 +2028,7 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
         if (render_oom) { set_error("out of memory while rendering the results"); return BLU_ERR_ALLOC; }
     }
     st.t_render_s = now_s() - t0;
-    if (stats) *stats = st;
+    outcome->stats = st;
     // the big objects and the taxonomy handle (whose 2 GB of packed staging take 25 ms to hipFree) go to the graveyard thread;
     // if it cannot be started they die here, as they would have anyway
     {
@@ -2013,28 +2045,19 @@ int build_document(const char* blast_output_file, const char* const* headers, ui
 }
 
 // the report, then the per-sample table, then the support table, after the document
-int put_tables(const Document& d, const blu_tables_params* tables, const char* support_path) {
-    if (d.has_report && !write_text_file(tables->report_path, d.report)) { set_error("cannot write %s", tables->report_path); return BLU_ERR_IO; }
-    if (d.has_table && !write_text_file(tables->sample_table_path, d.table)) { set_error("cannot write %s", tables->sample_table_path); return BLU_ERR_IO; }
-    if (d.has_support && !write_text_file(support_path, d.support)) { set_error("cannot write %s", support_path); return BLU_ERR_IO; }
+int put_tables(const Document& d, const blu_consensus_request& rq) {
+    if (d.has_report && !write_text_file(rq.report_path, d.report)) { set_error("cannot write %s", rq.report_path); return BLU_ERR_IO; }
+    if (d.has_table && !write_text_file(rq.sample_table_path, d.table)) { set_error("cannot write %s", rq.sample_table_path); return BLU_ERR_IO; }
+    if (d.has_support && !write_text_file(rq.support_table_path, d.support)) { set_error("cannot write %s", rq.support_table_path); return BLU_ERR_IO; }
     return BLU_OK;
 }
 
-int consensus_to_text(const char* blast_output_file, const char* const* headers, uint64_t n_headers, const char* taxonomies_file,
-                      const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const blu_tables_params* tables,
-                      char** out_text, size_t* out_len, blu_pipeline_stats* stats, const blu_hit_filter* flt = nullptr,
-                      blu_hit_filter_stats* fst = nullptr, const char* support_path = nullptr, const blu_taxon_filter* tflt = nullptr,
-                      blu_taxon_filter_stats* tst = nullptr, const blu_score_band* band = nullptr, blu_score_band_stats* bst = nullptr,
-                      const blu_subject_best* subj = nullptr, blu_subject_best_stats* sst = nullptr) {
-    if (!out_text) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
-    *out_text = nullptr;
-    if (out_len) *out_len = 0;
+// rq.out_path == NULL: the pieces joined into one malloc'd text
+int consensus_to_text(const blu_consensus_request& rq, blu_consensus_outcome* outcome) {
     Document d;
-    int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, &d, stats, tables, flt, fst, support_path, tflt, tst, band, bst, subj, sst); }
-    catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }   // (no exception crosses the C ABI)
+    int rc = build_document(rq, &d, outcome);
     if (rc != BLU_OK) return rc;
-    if ((rc = put_tables(d, tables, support_path)) != BLU_OK) return rc;
+    if ((rc = put_tables(d, rq)) != BLU_OK) return rc;
     const size_t total = d.size();
     char* buf = (char*)malloc(total + 1);
     if (!buf) { set_error("out of memory"); return BLU_ERR_ALLOC; }
@@ -2043,27 +2066,19 @@ int consensus_to_text(const char* blast_output_file, const char* const* headers,
     parallel_dynamic(d.pieces.size(), total < (1u << 24) ? 1 : worker_threads(),
                      [&](size_t k) { memcpy(buf + at[k], d.pieces[k].data(), d.pieces[k].size()); });
     buf[total] = 0;
-    *out_text = buf;
-    if (out_len) *out_len = total;
+    outcome->text = buf;
+    outcome->text_len = total;
     return BLU_OK;
 }
 
 // (the report and table files, when asked for, are written once the document is out)
-int consensus_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers, const char* taxonomies_file,
-                      const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const char* out_path,
-                      const blu_tables_params* tables, blu_pipeline_stats* stats, const blu_hit_filter* flt = nullptr,
-                      blu_hit_filter_stats* fst = nullptr, const char* support_path = nullptr, const blu_taxon_filter* tflt = nullptr,
-                      blu_taxon_filter_stats* tst = nullptr, const blu_score_band* band = nullptr, blu_score_band_stats* bst = nullptr,
-                      const blu_subject_best* subj = nullptr, blu_subject_best_stats* sst = nullptr) {
-    if (!out_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+int consensus_to_file(const blu_consensus_request& rq, blu_consensus_outcome* outcome) {
+    const char* const out_path = rq.out_path;
     Document d;
-    int rc;
-    try { rc = build_document(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, &d, stats, tables, flt, fst, support_path, tflt, tst, band, bst, subj, sst); }
-    catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
+    int rc = build_document(rq, &d, outcome);
     if (rc != BLU_OK) return rc;
     if (getenv("BLU_INGEST_TRACE")) fprintf(stderr, "[pipeline] %-26s %.3f s\n", "tear-down (tables, strings)", now_s() - g_t_body_end);
-    auto put_report = [&]() { return put_tables(d, tables, support_path); };
-    if (d.written) return put_report();
+    if (d.written) return put_tables(d, rq);
     // (YAML: one piece, written here) write_blutils_output.rs:57-63: an existing file is replaced
     Trace tr;
     const int fd = open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
@@ -2082,9 +2097,53 @@ int consensus_to_file(const char* blast_output_file, const char* const* headers,
     });
     if (close(fd) != 0 || !ok) { set_error("cannot write %s", out_path); return BLU_ERR_IO; }
     tr.lap("write file");
-    return put_report();
+    return put_tables(d, rq);
 }
 
+// The ingest half under a selection, into malloc'd copies of the host columns.
+int ingest_columns_selected(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                            const blu_hit_selection* selection, blu_ingest_columns* out, blu_hit_selection_stats* stats) {
+    Selection sel(selection, stats);
+    if (int rc = sel.check()) return rc;
+    Db db;
+    int rc = load_db(taxonomies_file, use_taxid != 0, db);
+    if (rc != BLU_OK) return rc;
+    if ((rc = sel.resolve(db, worker_threads())) != BLU_OK) return rc;
+    HitTable ht;
+    rc = load_hits(blast_output_file, db, ht, device, true, sel.flt, sel.taxa.get());
+    if (rc != BLU_OK) return rc;
+    ht.wait_strings();
+    if (!ht.strings_ok) { set_error("out of memory while building the query / accession strings"); return BLU_ERR_ALLOC; }
+    sel.loaded(ht);
+    if ((rc = sel.on_host_columns(device, ht)) != BLU_OK) return rc;
+    const size_t nh = ht.n_hits, nq = ht.n_queries;
+    auto dup = [](const void* src, size_t bytes) -> void* { void* p = malloc(bytes ? bytes : 1); if (p && bytes) memcpy(p, src, bytes); return p; };
+    auto pack = [](const std::vector<std::string>& v, uint64_t* bytes) -> char* {
+        size_t n = 0;
+        for (auto& s : v) n += s.size() + 1;
+        char* p = (char*)malloc(n ? n : 1);
+        if (!p) return nullptr;
+        size_t at = 0;
+        for (auto& s : v) { memcpy(p + at, s.data(), s.size()); at += s.size(); p[at++] = 0; }
+        *bytes = n;
+        return p;
+    };
+    out->n_hits = nh; out->n_queries = nq; out->n_accessions = ht.accessions.size();
+    out->seg_off = (uint64_t*)dup(ht.seg_off.data(), (nq + 1) * 8);
+    out->bitscore = (int32_t*)dup(ht.bitscore.data(), nh * 4);
+    out->align_len = (int32_t*)dup(ht.align_len.data(), nh * 4);
+    out->tax_desc_row = (uint32_t*)dup(ht.tax_desc_row.data(), nh * 4);
+    out->acc_rank = (uint32_t*)dup(ht.acc_rank.data(), nh * 4);
+    out->pident = (double*)dup(ht.pident.data(), nh * 8);
+    out->query_names = pack(ht.query_names, &out->query_names_bytes);
+    out->accessions = pack(ht.accessions, &out->accessions_bytes);
+    if (!out->seg_off || !out->bitscore || !out->align_len || !out->tax_desc_row || !out->acc_rank || !out->pident || !out->query_names || !out->accessions) {
+        blu_ingest_columns_free(out);
+        set_error("out of memory");
+        return BLU_ERR_ALLOC;
+    }
+    return BLU_OK;
+}
 
 }  // namespace
 
@@ -2092,129 +2151,54 @@ bool blu::parse_f64_field(const char* p, size_t n, double* out) { return parse_f
 
 extern "C" {
 
+int blu_build_consensus(const blu_consensus_request* request, blu_consensus_outcome* outcome) {
+    if (!request || !outcome) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    if (request->struct_size != sizeof(blu_consensus_request)) {
+        set_error("blu_build_consensus: struct_size %u is not a blu_consensus_request this library knows (%zu bytes)", request->struct_size,
+                  sizeof(blu_consensus_request));
+        return BLU_ERR_INVALID_ARG;
+    }
+    outcome->text = nullptr; outcome->text_len = 0; outcome->stats = blu_pipeline_stats{};   // (outcome->selection: by Selection)
+    try { return request->out_path ? consensus_to_file(*request, outcome) : consensus_to_text(*request, outcome); }
+    catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }   // (no exception crosses the C ABI)
+}
+
+// the reference's three signatures: the fields they name, everything else absent
+static int build_as_the_reference(const char* blast_output_file, const char* const* headers, uint64_t n_headers, const char* taxonomies_file,
+                                  const blu_pipeline_params* params, const char* run_id_text, const char* config_text, const char* out_path,
+                                  char** out_text, size_t* out_len, blu_pipeline_stats* stats) {
+    if (!out_path && !out_text) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    blu_consensus_request rq{};
+    rq.struct_size = sizeof rq;
+    rq.blast_output_file = blast_output_file; rq.headers = headers; rq.n_headers = n_headers; rq.taxonomies_file = taxonomies_file;
+    rq.params = params; rq.run_id_text = run_id_text; rq.config_text = config_text; rq.out_path = out_path;
+    blu_consensus_outcome oc{};
+    const int rc = blu_build_consensus(&rq, &oc);
+    if (out_text) *out_text = oc.text;
+    if (out_len) *out_len = oc.text_len;
+    if (stats && rc == BLU_OK) *stats = oc.stats;
+    return rc;
+}
+
 int blu_build_consensus_identities(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
                                    const char* taxonomies_file, const blu_pipeline_params* params, char** out_text,
                                    size_t* out_len, blu_pipeline_stats* stats) {
-    return blu_build_consensus_identities_cfg(blast_output_file, headers, n_headers, taxonomies_file, params, nullptr, nullptr,
-                                              out_text, out_len, stats);
+    return build_as_the_reference(blast_output_file, headers, n_headers, taxonomies_file, params, nullptr, nullptr, nullptr, out_text, out_len, stats);
 }
 
 int blu_build_consensus_identities_cfg(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
                                        const char* taxonomies_file, const blu_pipeline_params* params,
                                        const char* run_id_text, const char* config_text, char** out_text, size_t* out_len,
                                        blu_pipeline_stats* stats) {
-    return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, out_text,
-                             out_len, stats);
-}
-
-int blu_build_consensus_identities_report(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                          const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                                          const char* config_text, const char* out_path, const blu_report_params* report,
-                                          char** out_text, size_t* out_len, blu_pipeline_stats* stats) {
-    if (!report || !report->report_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
-    const blu_tables_params tables{report->report_path, nullptr, report->weight, 0};
-    return blu_build_consensus_identities_tables(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text,
-                                                 out_path, &tables, out_text, out_len, stats);
-}
-
-int blu_build_consensus_identities_tables(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                          const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                                          const char* config_text, const char* out_path, const blu_tables_params* tables,
-                                          char** out_text, size_t* out_len, blu_pipeline_stats* stats) {
-    if (!tables || (!tables->report_path && !tables->sample_table_path)) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
-    if (out_path)
-        return consensus_to_file(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, tables,
-                                 stats);
-    return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, tables, out_text,
-                             out_len, stats);
-}
-
-int blu_build_consensus_identities_filtered(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                            const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                                            const char* config_text, const char* out_path, const blu_tables_params* tables,
-                                            const blu_hit_filter* filter, char** out_text, size_t* out_len,
-                                            blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats) {
-    if (tables && !tables->report_path && !tables->sample_table_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
-    if (filter_stats) *filter_stats = blu_hit_filter_stats{0, 0};
-    if (out_path)
-        return consensus_to_file(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, tables,
-                                 stats, filter, filter_stats);
-    return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, tables, out_text,
-                             out_len, stats, filter, filter_stats);
-}
-
-int blu_build_consensus_identities_support(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                           const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                                           const char* config_text, const char* out_path, const blu_tables_params* tables,
-                                           const blu_hit_filter* filter, char** out_text, size_t* out_len,
-                                           blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats, const char* support_table_path) {
-    if (tables && !tables->report_path && !tables->sample_table_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
-    if (filter_stats) *filter_stats = blu_hit_filter_stats{0, 0};
-    if (out_path)
-        return consensus_to_file(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, tables,
-                                 stats, filter, filter_stats, support_table_path);
-    return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, tables, out_text,
-                             out_len, stats, filter, filter_stats, support_table_path);
-}
-
-// (the caller's counts start at zero, its excluded_by array included, whatever the call then does)
-static void clear_taxon_stats(const blu_taxon_filter* f, blu_taxon_filter_stats* s) {
-    if (!s) return;
-    s->n_lines = s->n_excluded = s->n_not_only = 0;
-    if (s->excluded_by && f && f->n_exclude <= BLU_TAXON_FILTER_MAX_EXCLUDE) for (uint64_t k = 0; k < f->n_exclude; ++k) s->excluded_by[k] = 0;
-}
-
-int blu_build_consensus_identities_taxa(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                        const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                                        const char* config_text, const char* out_path, const blu_tables_params* tables,
-                                        const blu_hit_filter* filter, char** out_text, size_t* out_len,
-                                        blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats, const char* support_table_path,
-                                        const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats) {
-    return blu_build_consensus_identities_band(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path,
-                                               tables, filter, out_text, out_len, stats, filter_stats, support_table_path, taxon_filter,
-                                               taxon_stats, nullptr, nullptr);
-}
-
-int blu_build_consensus_identities_band(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                        const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                                        const char* config_text, const char* out_path, const blu_tables_params* tables,
-                                        const blu_hit_filter* filter, char** out_text, size_t* out_len,
-                                        blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats, const char* support_table_path,
-                                        const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
-                                        const blu_score_band* band, blu_score_band_stats* band_stats) {
-    return blu_build_consensus_identities_subject(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path,
-                                                  tables, filter, out_text, out_len, stats, filter_stats, support_table_path, taxon_filter,
-                                                  taxon_stats, band, band_stats, nullptr, nullptr);
-}
-
-int blu_build_consensus_identities_subject(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                           const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                                           const char* config_text, const char* out_path, const blu_tables_params* tables,
-                                           const blu_hit_filter* filter, char** out_text, size_t* out_len,
-                                           blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats, const char* support_table_path,
-                                           const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
-                                           const blu_score_band* band, blu_score_band_stats* band_stats,
-                                           const blu_subject_best* subject_best, blu_subject_best_stats* subject_stats) {
-    if (tables && !tables->report_path && !tables->sample_table_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
-    if (filter_stats) *filter_stats = blu_hit_filter_stats{0, 0};
-    clear_taxon_stats(taxon_filter, taxon_stats);
-    if (band_stats) *band_stats = blu_score_band_stats{0, 0, 0, 0};
-    if (subject_stats) *subject_stats = blu_subject_best_stats{0, 0, 0, 0};
-    if (out_path)
-        return consensus_to_file(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, tables,
-                                 stats, filter, filter_stats, support_table_path, taxon_filter, taxon_stats, band, band_stats, subject_best,
-                                 subject_stats);
-    return consensus_to_text(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, tables, out_text,
-                             out_len, stats, filter, filter_stats, support_table_path, taxon_filter, taxon_stats, band, band_stats,
-                             subject_best, subject_stats);
+    return build_as_the_reference(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, nullptr, out_text, out_len, stats);
 }
 
 int blu_build_consensus_identities_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
                                            const char* taxonomies_file, const blu_pipeline_params* params,
                                            const char* run_id_text, const char* config_text, const char* out_path,
                                            blu_pipeline_stats* stats) {
-    return consensus_to_file(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, nullptr,
-                             stats);
+    if (!out_path) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    return build_as_the_reference(blast_output_file, headers, n_headers, taxonomies_file, params, run_id_text, config_text, out_path, nullptr, nullptr, stats);
 }
 
 void blu_free_text(char* text) { free(text); }
@@ -2257,104 +2241,15 @@ int blu_ingest_only_on(const char* blast_output_file, const char* taxonomies_fil
 
 int blu_ingest_columns_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
                           blu_ingest_columns* out) {
-    return blu_ingest_columns_filtered_on(blast_output_file, taxonomies_file, use_taxid, device, nullptr, out, nullptr);
+    return blu_ingest_columns_selected(blast_output_file, taxonomies_file, use_taxid, device, nullptr, out, nullptr);
 }
 
-int blu_ingest_columns_filtered_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
-                                   const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats) {
-    return blu_ingest_columns_taxa_on(blast_output_file, taxonomies_file, use_taxid, device, filter, out, filter_stats, nullptr, nullptr);
-}
-
-int blu_ingest_columns_taxa_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
-                               const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
-                               const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats) {
-    return blu_ingest_columns_band_on(blast_output_file, taxonomies_file, use_taxid, device, filter, out, filter_stats, taxon_filter, taxon_stats,
-                                      nullptr, nullptr);
-}
-
-int blu_ingest_columns_band_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
-                               const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
-                               const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
-                               const blu_score_band* band, blu_score_band_stats* band_stats) {
-    return blu_ingest_columns_subject_on(blast_output_file, taxonomies_file, use_taxid, device, filter, out, filter_stats, taxon_filter, taxon_stats,
-                                         band, band_stats, nullptr, nullptr);
-}
-
-int blu_ingest_columns_subject_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
-                                  const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
-                                  const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
-                                  const blu_score_band* band, blu_score_band_stats* band_stats,
-                                  const blu_subject_best* subject_best, blu_subject_best_stats* subject_stats) {
+int blu_ingest_columns_selected(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                                const blu_hit_selection* selection, blu_ingest_columns* out, blu_hit_selection_stats* stats) {
     if (!blast_output_file || !taxonomies_file || !out) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
-    if (filter && (filter->mask & ~15u)) { set_error("hit filter: unknown bits in the mask"); return BLU_ERR_INVALID_ARG; }
-    if (band_stats) *band_stats = blu_score_band_stats{0, 0, 0, 0};
-    if (subject_stats) *subject_stats = blu_subject_best_stats{0, 0, 0, 0};
-    if (int src = check_subject_best(subject_best)) return src;
-    if (subject_best && !subject_best->mask) subject_best = nullptr;
-    if (int brc = check_score_band(band)) return brc;
-    if (band && !band->mask) band = nullptr;
-    if (filter_stats) *filter_stats = blu_hit_filter_stats{0, 0};
-    clear_taxon_stats(taxon_filter, taxon_stats);
     memset(out, 0, sizeof *out);
-    Db db;
-    int rc = load_db(taxonomies_file, use_taxid != 0, db);
-    if (rc != BLU_OK) return rc;
-    if (taxon_filter && !taxon_filter->n_exclude && !taxon_filter->n_only) taxon_filter = nullptr;
-    std::unique_ptr<TaxonCodes> taxa;
-    if (taxon_filter) {
-        taxa = std::make_unique<TaxonCodes>();
-        try { rc = taxon_codes(db, *taxon_filter, worker_threads(), *taxa); }
-        catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
-        if (rc != BLU_OK) return rc;
-    }
-    HitTable ht;
-    rc = load_hits(blast_output_file, db, ht, device, true, filter, taxa.get());
-    if (rc != BLU_OK) return rc;
-    put_taxon_stats(taxa.get(), ht.n_lines, taxon_stats);
-    ht.wait_strings();
-    if (!ht.strings_ok) { set_error("out of memory while building the query / accession strings"); return BLU_ERR_ALLOC; }
-    size_t nh = ht.bitscore.size();
-    const size_t nq = ht.query_names.size(), nh_in = nh;   // (nh_in: the rows the filters kept, whatever is selected below)
-    if (subject_stats) *subject_stats = blu_subject_best_stats{nh, nh, nq, 0};
-    if (subject_best && nh) {   // (the host-column hook, before the band's)
-        uint64_t n_out = nh;
-        rc = blu_hits_subject_best(device, ht.bitscore.data(), ht.align_len.data(), ht.tax_desc_row.data(), ht.acc_rank.data(), ht.pident.data(),
-                                   ht.seg_off.data(), nh, nq, 0, subject_best, nullptr, BLU_UNMATCHED_TAXID, &n_out, nullptr, subject_stats);
-        if (rc != BLU_OK) return rc;
-        nh = n_out;
-    }
-    if (band_stats) { band_stats->n_hits = nh; band_stats->n_queries = nq; }
-    if (band && nh) {   // (the use-case's host-column hook: the host-pointer route of the one kernel)
-        rc = blu_hits_score_band(device, ht.bitscore.data(), ht.seg_off.data(), nh, nq, 0, band, nullptr, ht.bitscore.data(), band_stats);
-        if (rc != BLU_OK) return rc;
-    }
-    if (filter_stats) { const bool on = (filter && (filter->mask & 15u)) || taxa; filter_stats->n_lines = on ? ht.n_lines : nh_in; filter_stats->n_kept = on ? ht.n_kept : nh_in; }
-    auto dup = [](const void* src, size_t bytes) -> void* { void* p = malloc(bytes ? bytes : 1); if (p && bytes) memcpy(p, src, bytes); return p; };
-    auto pack = [](const std::vector<std::string>& v, uint64_t* bytes) -> char* {
-        size_t n = 0;
-        for (auto& s : v) n += s.size() + 1;
-        char* p = (char*)malloc(n ? n : 1);
-        if (!p) return nullptr;
-        size_t at = 0;
-        for (auto& s : v) { memcpy(p + at, s.data(), s.size()); at += s.size(); p[at++] = 0; }
-        *bytes = n;
-        return p;
-    };
-    out->n_hits = nh; out->n_queries = nq; out->n_accessions = ht.accessions.size();
-    out->seg_off = (uint64_t*)dup(ht.seg_off.data(), (nq + 1) * 8);
-    out->bitscore = (int32_t*)dup(ht.bitscore.data(), nh * 4);
-    out->align_len = (int32_t*)dup(ht.align_len.data(), nh * 4);
-    out->tax_desc_row = (uint32_t*)dup(ht.tax_desc_row.data(), nh * 4);
-    out->acc_rank = (uint32_t*)dup(ht.acc_rank.data(), nh * 4);
-    out->pident = (double*)dup(ht.pident.data(), nh * 8);
-    out->query_names = pack(ht.query_names, &out->query_names_bytes);
-    out->accessions = pack(ht.accessions, &out->accessions_bytes);
-    if (!out->seg_off || !out->bitscore || !out->align_len || !out->tax_desc_row || !out->acc_rank || !out->pident || !out->query_names || !out->accessions) {
-        blu_ingest_columns_free(out);
-        set_error("out of memory");
-        return BLU_ERR_ALLOC;
-    }
-    return BLU_OK;
+    try { return ingest_columns_selected(blast_output_file, taxonomies_file, use_taxid, device, selection, out, stats); }
+    catch (const std::bad_alloc&) { blu_ingest_columns_free(out); set_error("out of memory"); return BLU_ERR_ALLOC; }
 }
 
 void blu_ingest_columns_free(blu_ingest_columns* c) {

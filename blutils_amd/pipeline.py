@@ -105,20 +105,18 @@ class TaxonFilterStats(C.Structure):
 
 
 class _TaxonArgs:
-    """The C structs of one call and the arrays they point into."""
+    """The C filter of one call and the arrays it points into."""
 
     def __init__(self, exclude, only):
         self.exclude, self.only = [str(e) for e in exclude], [str(e) for e in only]
         self._ex = (C.c_char_p * max(1, len(self.exclude)))(*[e.encode() for e in self.exclude])
         self._on = (C.c_char_p * max(1, len(self.only)))(*[e.encode() for e in self.only])
-        self._by = (C.c_uint64 * max(1, len(self.exclude)))()
+        self.by = (C.c_uint64 * max(1, len(self.exclude)))()      # (the caller's excluded_by array)
         self.filter = TaxonFilterC(self._ex, len(self.exclude), self._on, len(self.only))
-        self.stats = TaxonFilterStats(0, 0, 0, self._by)
 
-    def counts(self) -> dict:
-        return {"n_lines": int(self.stats.n_lines), "n_excluded": int(self.stats.n_excluded),
-                "n_not_only": int(self.stats.n_not_only), "exclude": list(self.exclude),
-                "excluded_by": [int(self._by[k]) for k in range(len(self.exclude))]}
+    def counts(self, st: TaxonFilterStats) -> dict:
+        return {"n_lines": int(st.n_lines), "n_excluded": int(st.n_excluded), "n_not_only": int(st.n_not_only),
+                "exclude": list(self.exclude), "excluded_by": [int(self.by[k]) for k in range(len(self.exclude))]}
 
 
 def _taxon_filter(taxon_filter: Union[None, dict, TaxonFilter]) -> Optional[_TaxonArgs]:
@@ -201,11 +199,69 @@ def _score_band(score_band: Union[None, dict, ScoreBand]) -> Optional[N.ScoreBan
     return b if b.mask else None
 
 
+class HitSelection(C.Structure):
+    """include/blu_pipeline.h: blu_hit_selection (NULL members: not asked for)"""
+    _fields_ = [("hit_filter", C.POINTER(HitFilterC)), ("taxon_filter", C.POINTER(TaxonFilterC)),
+                ("subject_best", C.POINTER(N.SubjectBestC)), ("score_band", C.POINTER(N.ScoreBandC))]
+
+
+class HitSelectionStats(C.Structure):
+    """include/blu_pipeline.h: blu_hit_selection_stats"""
+    _fields_ = [("hit_filter", HitFilterStats), ("taxon_filter", TaxonFilterStats), ("subject_best", N.SubjectBestStats),
+                ("score_band", N.ScoreBandStats)]
+
+
+class ConsensusRequest(C.Structure):
+    """include/blu_pipeline.h: blu_consensus_request"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("blast_output_file", C.c_char_p),
+                ("headers", C.POINTER(C.c_char_p)), ("n_headers", C.c_uint64), ("taxonomies_file", C.c_char_p),
+                ("params", C.POINTER(PipelineParams)), ("run_id_text", C.c_char_p), ("config_text", C.c_char_p),
+                ("out_path", C.c_char_p), ("report_path", C.c_char_p), ("sample_table_path", C.c_char_p), ("weight", C.c_int32),
+                ("reserved2", C.c_int32), ("support_table_path", C.c_char_p), ("selection", HitSelection)]
+
+
+class ConsensusOutcome(C.Structure):
+    """include/blu_pipeline.h: blu_consensus_outcome"""
+    _fields_ = [("text", C.c_void_p), ("text_len", C.c_size_t), ("stats", PipelineStats), ("selection", HitSelectionStats)]
+
+
+class _Selection:
+    """The keywords hit_filter / taxon_filter / score_band / best_hit_per_subject as the C struct, with what it points to kept
+    alive, and the stats keys each of them adds."""
+
+    def __init__(self, hit_filter, taxon_filter, score_band, best_hit_per_subject):
+        self.flt, self.tf, self.band = _hit_filter(hit_filter), _taxon_filter(taxon_filter), _score_band(score_band)
+        self.sel = N.SubjectBestC(N.SUBJECT_BEST_PER_QUERY, 0) if best_hit_per_subject else None
+        ptr = lambda x: C.pointer(x) if x is not None else None
+        self.c = HitSelection(ptr(self.flt), ptr(self.tf.filter) if self.tf is not None else None, ptr(self.sel), ptr(self.band))
+
+    def stats(self) -> HitSelectionStats:
+        st = HitSelectionStats()
+        if self.tf is not None:
+            st.taxon_filter.excluded_by = self.tf.by
+        return st
+
+    def counts(self, st: HitSelectionStats) -> dict:
+        out = {}
+        if self.flt is not None or self.tf is not None:
+            out["n_lines"], out["n_kept"] = int(st.hit_filter.n_lines), int(st.hit_filter.n_kept)
+        if self.tf is not None:
+            out["taxon_filter"] = self.tf.counts(st.taxon_filter)
+        if self.band is not None:
+            out["score_band"] = N.band_counts(st.score_band)
+        if self.sel is not None:
+            out["subject_best"] = N.subject_counts(st.subject_best)
+        return out
+
+
 def _bind():
     L = N.lib()
-    L.blu_build_consensus_identities.restype = C.c_int
-    L.blu_build_consensus_identities.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
-                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(PipelineStats)]
+    L.blu_build_consensus.restype = C.c_int
+    L.blu_build_consensus.argtypes = [C.POINTER(ConsensusRequest), C.POINTER(ConsensusOutcome)]
+    L.blu_ingest_columns_selected.restype = C.c_int
+    L.blu_ingest_columns_selected.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(HitSelection),
+                                              C.POINTER(IngestColumns), C.POINTER(HitSelectionStats)]
+    L.blu_ingest_columns_free.argtypes = [C.POINTER(IngestColumns)]
     L.blu_free_text.argtypes = [C.c_void_p]
     L.blu_custom_taxon_from_file.restype = C.c_int
     L.blu_custom_taxon_from_file.argtypes = [C.c_char_p, C.POINTER(N.CutoffConfig)]
@@ -236,72 +292,22 @@ def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = Fa
                    hit_filter: Union[None, dict, HitFilter] = None,
                    taxon_filter: Union[None, dict, TaxonFilter] = None,
                    score_band: Union[None, dict, ScoreBand] = None, best_hit_per_subject: bool = False) -> dict:
-    """The SoA columns of the ingest (include/blu_pipeline.h: blu_ingest_columns_on) as numpy arrays + the two string tables.
-    hit_filter (a dict or HitFilter): the columns of the lines it keeps (blu_ingest_columns_filtered_on), plus `n_lines` and
-    `n_kept`.  taxon_filter (a dict or TaxonFilter): the same under a taxon filter (blu_ingest_columns_taxa_on), alone or
-    beside hit_filter, plus `taxon_filter`: its counts (n_lines, n_excluded, n_not_only, exclude, excluded_by).  score_band (a
-    dict or ScoreBand): the bitscore column with the band applied (blu_ingest_columns_band_on; needs device >= 0), plus
-    `score_band`: its counts (n_hits, n_raised, n_queries, n_widened).  best_hit_per_subject: the columns with only the best
-    row of every (query, subject accession) pair, selected before the band (blu_ingest_columns_subject_on; needs
+    """The SoA columns of the ingest (include/blu_pipeline.h: blu_ingest_columns_selected) as numpy arrays + the two string
+    tables.  hit_filter (a dict or HitFilter): the columns of the lines it keeps, plus `n_lines` and `n_kept`.  taxon_filter (a
+    dict or TaxonFilter): the same under a taxon filter, alone or beside hit_filter, plus `taxon_filter`: its counts (n_lines,
+    n_excluded, n_not_only, exclude, excluded_by).  score_band (a dict or ScoreBand): the bitscore column with the band applied
+    (needs device >= 0), plus `score_band`: its counts (n_hits, n_raised, n_queries, n_widened).  best_hit_per_subject: the
+    columns with only the best row of every (query, subject accession) pair, selected before the band (needs
     device >= 0), plus `subject_best`: its counts (n_hits, n_kept, n_queries, n_thinned)."""
     import numpy as np
     L = _bind()
-    L.blu_ingest_columns_on.restype = C.c_int
-    L.blu_ingest_columns_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(IngestColumns)]
-    L.blu_ingest_columns_free.argtypes = [C.POINTER(IngestColumns)]
     c = IngestColumns()
-    flt, fst = _hit_filter(hit_filter), HitFilterStats()
-    tf = _taxon_filter(taxon_filter)
-    band, bst = _score_band(score_band), N.ScoreBandStats()
-    sel, sst = (N.SubjectBestC(N.SUBJECT_BEST_PER_QUERY, 0) if best_hit_per_subject else None), N.SubjectBestStats()
-    if sel is not None:
-        L.blu_ingest_columns_subject_on.restype = C.c_int
-        L.blu_ingest_columns_subject_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(HitFilterC),
-                                                    C.POINTER(IngestColumns), C.POINTER(HitFilterStats),
-                                                    C.POINTER(TaxonFilterC), C.POINTER(TaxonFilterStats),
-                                                    C.POINTER(N.ScoreBandC), C.POINTER(N.ScoreBandStats),
-                                                    C.POINTER(N.SubjectBestC), C.POINTER(N.SubjectBestStats)]
-        rc = L.blu_ingest_columns_subject_on(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
-                                             C.byref(flt) if flt is not None else None, C.byref(c), C.byref(fst),
-                                             C.byref(tf.filter) if tf is not None else None,
-                                             C.byref(tf.stats) if tf is not None else None,
-                                             C.byref(band) if band is not None else None, C.byref(bst), C.byref(sel), C.byref(sst))
-        if rc != N.BLU_OK:
-            raise N.BluError(rc, "blu_ingest_columns_subject_on")
-    elif band is not None:
-        L.blu_ingest_columns_band_on.restype = C.c_int
-        L.blu_ingest_columns_band_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(HitFilterC),
-                                                 C.POINTER(IngestColumns), C.POINTER(HitFilterStats),
-                                                 C.POINTER(TaxonFilterC), C.POINTER(TaxonFilterStats),
-                                                 C.POINTER(N.ScoreBandC), C.POINTER(N.ScoreBandStats)]
-        rc = L.blu_ingest_columns_band_on(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
-                                          C.byref(flt) if flt is not None else None, C.byref(c), C.byref(fst),
-                                          C.byref(tf.filter) if tf is not None else None,
-                                          C.byref(tf.stats) if tf is not None else None, C.byref(band), C.byref(bst))
-        if rc != N.BLU_OK:
-            raise N.BluError(rc, "blu_ingest_columns_band_on")
-    elif tf is not None:
-        L.blu_ingest_columns_taxa_on.restype = C.c_int
-        L.blu_ingest_columns_taxa_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(HitFilterC),
-                                                 C.POINTER(IngestColumns), C.POINTER(HitFilterStats),
-                                                 C.POINTER(TaxonFilterC), C.POINTER(TaxonFilterStats)]
-        rc = L.blu_ingest_columns_taxa_on(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
-                                          C.byref(flt) if flt is not None else None, C.byref(c), C.byref(fst),
-                                          C.byref(tf.filter), C.byref(tf.stats))
-        if rc != N.BLU_OK:
-            raise N.BluError(rc, "blu_ingest_columns_taxa_on")
-    elif flt is None:
-        rc = L.blu_ingest_columns_on(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device, C.byref(c))
-        if rc != N.BLU_OK:
-            raise N.BluError(rc, "blu_ingest_columns_on")
-    else:
-        L.blu_ingest_columns_filtered_on.restype = C.c_int
-        L.blu_ingest_columns_filtered_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(HitFilterC),
-                                                     C.POINTER(IngestColumns), C.POINTER(HitFilterStats)]
-        rc = L.blu_ingest_columns_filtered_on(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
-                                              C.byref(flt), C.byref(c), C.byref(fst))
-        if rc != N.BLU_OK:
-            raise N.BluError(rc, "blu_ingest_columns_filtered_on")
+    sel = _Selection(hit_filter, taxon_filter, score_band, best_hit_per_subject)
+    st = sel.stats()
+    rc = L.blu_ingest_columns_selected(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
+                                       C.byref(sel.c), C.byref(c), C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_ingest_columns_selected")
     try:
         nh, nq = int(c.n_hits), int(c.n_queries)
         arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(max(n, 1),))[:n].astype(dt, copy=True)
@@ -311,14 +317,7 @@ def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = Fa
         split = lambda p, n: C.string_at(p, n).split(b"\0")[:-1] if n else []
         out["query_names"] = split(c.query_names, int(c.query_names_bytes))
         out["accessions"] = split(c.accessions, int(c.accessions_bytes))
-        if flt is not None or tf is not None:
-            out["n_lines"], out["n_kept"] = int(fst.n_lines), int(fst.n_kept)
-        if tf is not None:
-            out["taxon_filter"] = tf.counts()
-        if band is not None:
-            out["score_band"] = N.band_counts(bst)
-        if sel is not None:
-            out["subject_best"] = N.subject_counts(sst)
+        out.update(sel.counts(st))
         return out
     finally:
         L.blu_ingest_columns_free(C.byref(c))
@@ -347,14 +346,6 @@ def custom_taxon_from_file(path: str) -> dict:
     if rc != N.BLU_OK:
         raise N.BluError(rc, "blu_custom_taxon_from_file")
     return {k: int(cfg.custom[i]) for i, k in enumerate(N.CUSTOM_FIELDS) if cfg.custom_has[i]}
-
-
-class ReportParams(C.Structure):
-    _fields_ = [("report_path", C.c_char_p), ("weight", C.c_int32), ("reserved", C.c_int32)]
-
-
-class TablesParams(C.Structure):
-    _fields_ = [("report_path", C.c_char_p), ("sample_table_path", C.c_char_p), ("weight", C.c_int32), ("reserved", C.c_int32)]
 
 
 REPORT_WEIGHT = {"one": 0, "size": 1}
@@ -395,7 +386,7 @@ def build_consensus_identities_with_report(blast_output: str, taxonomies_file: s
                                            score_band: Union[None, dict, ScoreBand] = None,
                                            best_hit_per_subject: bool = False):
     """build_consensus_identities plus the taxon abundance report of its results, counted on the GPU and written to
-    report_path after the document (include/blu_pipeline.h: blu_build_consensus_identities_report).
+    report_path after the document (include/blu_pipeline.h: blu_consensus_request.report_path).
     report_weight: "one" (results) or "size" (dereplicated reads named in the query)."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, report_path, report_weight, hit_filter=hit_filter, taxon_filter=taxon_filter,
@@ -416,9 +407,9 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
                                            best_hit_per_subject: bool = False):
     """build_consensus_identities plus the taxon abundance report (report_path), the per-sample table (sample_table_path,
     DESIGN.md §13), or both, counted on the GPU and written in the order document, report, table
-    (include/blu_pipeline.h: blu_build_consensus_identities_tables).  report_weight serves both files.  A query whose name
+    (include/blu_pipeline.h: blu_consensus_request).  report_weight serves both files.  A query whose name
     names no sample fails the call before any file is written.  support_table_path: also the per-query support table
-    (blu_build_consensus_identities_support), counted on the GPU and written last; it combines with the
+    (DESIGN.md §15), counted on the GPU and written last; it combines with the
     other files and with hit_filter, and may be the only one asked for.  Under a score_band its top_hits is the band's size
     and bits / support_bits sum the raised scores."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
@@ -431,10 +422,7 @@ def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_tax
            parse, config, out_path, report_path, report_weight, sample_table_path=None, hit_filter=None,
            support_table_path=None, taxon_filter=None, score_band=None, best_hit_per_subject=False):
     L = _bind()
-    flt, fst = _hit_filter(hit_filter), HitFilterStats()
-    tf = _taxon_filter(taxon_filter)
-    band, bst = _score_band(score_band), N.ScoreBandStats()
-    sel, sst = (N.SubjectBestC(N.SUBJECT_BEST_PER_QUERY, 0) if best_hit_per_subject else None), N.SubjectBestStats()
+    sel = _Selection(hit_filter, taxon_filter, score_band, best_hit_per_subject)
     p = PipelineParams()
     p.cutoffs.taxon = N.TAXON[taxon]
     p.cutoffs.has_custom = 1 if custom_taxon_values is not None else 0
@@ -448,185 +436,30 @@ def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_tax
     p.device = device
     p.out_format = OUT_FORMAT[out_format]
     p.lenient = 1 if lenient else 0
-    hdr_arr, n_hdr = None, 0
+    enc = lambda x: str(x).encode() if x is not None else None
+    rq = ConsensusRequest(struct_size=C.sizeof(ConsensusRequest), blast_output_file=blast_output.encode(),
+                          taxonomies_file=taxonomies_file.encode(), params=C.pointer(p), out_path=enc(out_path),
+                          report_path=enc(report_path), sample_table_path=enc(sample_table_path),
+                          support_table_path=enc(support_table_path), selection=sel.c)
     if headers is not None:
-        enc = [h.encode() for h in headers]
-        hdr_arr = (C.c_char_p * max(1, len(enc)))(*enc)
-        n_hdr = len(enc)
-    text, n = C.c_void_p(), C.c_size_t()
-    st = PipelineStats()
-    L.blu_build_consensus_identities_cfg.restype = C.c_int
-    L.blu_build_consensus_identities_cfg.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
-                                                     C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
-                                                     C.POINTER(PipelineStats)]
-    run_id = str(config.run_id).encode() if config is not None else None
-    cfg_text = config.render(out_format).encode() if config is not None else None
-    def stats_of():
-        stats = {f: getattr(st, f) for f, _ in PipelineStats._fields_}
-        if flt is not None or tf is not None:
-            stats["n_lines"], stats["n_kept"] = int(fst.n_lines), int(fst.n_kept)
-        if tf is not None:
-            stats["taxon_filter"] = tf.counts()
-        if band is not None:
-            stats["score_band"] = N.band_counts(bst)
-        if sel is not None:
-            stats["subject_best"] = N.subject_counts(sst)
-        return stats
-
-    if sel is not None:
-        # the best hit per subject: the entry point that takes everything (include/blu_pipeline.h:
-        # blu_build_consensus_identities_subject; the calls below are this one with a NULL selection)
-        tp = None
-        if report_path is not None or sample_table_path is not None:
-            tp = TablesParams(str(report_path).encode() if report_path is not None else None,
-                              str(sample_table_path).encode() if sample_table_path is not None else None,
-                              REPORT_WEIGHT[report_weight], 0)
-        L.blu_build_consensus_identities_subject.restype = C.c_int
-        L.blu_build_consensus_identities_subject.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
-                                                             C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(TablesParams),
-                                                             C.POINTER(HitFilterC), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
-                                                             C.POINTER(PipelineStats), C.POINTER(HitFilterStats), C.c_char_p,
-                                                             C.POINTER(TaxonFilterC), C.POINTER(TaxonFilterStats),
-                                                             C.POINTER(N.ScoreBandC), C.POINTER(N.ScoreBandStats),
-                                                             C.POINTER(N.SubjectBestC), C.POINTER(N.SubjectBestStats)]
-        rc = L.blu_build_consensus_identities_subject(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
-                                                      taxonomies_file.encode(), C.byref(p), run_id, cfg_text,
-                                                      out_path.encode() if out_path is not None else None,
-                                                      C.byref(tp) if tp is not None else None,
-                                                      C.byref(flt) if flt is not None else None,
-                                                      C.byref(text), C.byref(n), C.byref(st), C.byref(fst),
-                                                      str(support_table_path).encode() if support_table_path is not None else None,
-                                                      C.byref(tf.filter) if tf is not None else None,
-                                                      C.byref(tf.stats) if tf is not None else None,
-                                                      C.byref(band) if band is not None else None, C.byref(bst),
-                                                      C.byref(sel), C.byref(sst))
-        if rc != N.BLU_OK:
-            raise N.BluError(rc, "blu_build_consensus_identities_subject")
-        if out_path is not None:
-            return None, stats_of()
-    elif band is not None or tf is not None:
-        # a score band or a taxon filter: one entry point for every combination (include/blu_pipeline.h:
-        # blu_build_consensus_identities_band; blu_build_consensus_identities_taxa is this call without a band)
-        tp = None
-        if report_path is not None or sample_table_path is not None:
-            tp = TablesParams(str(report_path).encode() if report_path is not None else None,
-                              str(sample_table_path).encode() if sample_table_path is not None else None,
-                              REPORT_WEIGHT[report_weight], 0)
-        L.blu_build_consensus_identities_band.restype = C.c_int
-        L.blu_build_consensus_identities_band.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
-                                                          C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(TablesParams),
-                                                          C.POINTER(HitFilterC), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
-                                                          C.POINTER(PipelineStats), C.POINTER(HitFilterStats), C.c_char_p,
-                                                          C.POINTER(TaxonFilterC), C.POINTER(TaxonFilterStats),
-                                                          C.POINTER(N.ScoreBandC), C.POINTER(N.ScoreBandStats)]
-        rc = L.blu_build_consensus_identities_band(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
-                                                   taxonomies_file.encode(), C.byref(p), run_id, cfg_text,
-                                                   out_path.encode() if out_path is not None else None,
-                                                   C.byref(tp) if tp is not None else None,
-                                                   C.byref(flt) if flt is not None else None,
-                                                   C.byref(text), C.byref(n), C.byref(st), C.byref(fst),
-                                                   str(support_table_path).encode() if support_table_path is not None else None,
-                                                   C.byref(tf.filter) if tf is not None else None,
-                                                   C.byref(tf.stats) if tf is not None else None,
-                                                   C.byref(band) if band is not None else None, C.byref(bst))
-        if rc != N.BLU_OK:
-            raise N.BluError(rc, "blu_build_consensus_identities_band" if band is not None else "blu_build_consensus_identities_taxa")
-        if out_path is not None:
-            return None, stats_of()
-    elif support_table_path is not None:
-        # the support table: one entry point for every combination (include/blu_pipeline.h: blu_build_consensus_identities_support)
-        tp = None
-        if report_path is not None or sample_table_path is not None:
-            tp = TablesParams(str(report_path).encode() if report_path is not None else None,
-                              str(sample_table_path).encode() if sample_table_path is not None else None,
-                              REPORT_WEIGHT[report_weight], 0)
-        L.blu_build_consensus_identities_support.restype = C.c_int
-        L.blu_build_consensus_identities_support.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
-                                                             C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(TablesParams),
-                                                             C.POINTER(HitFilterC), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
-                                                             C.POINTER(PipelineStats), C.POINTER(HitFilterStats), C.c_char_p]
-        rc = L.blu_build_consensus_identities_support(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
-                                                      taxonomies_file.encode(), C.byref(p), run_id, cfg_text,
-                                                      out_path.encode() if out_path is not None else None,
-                                                      C.byref(tp) if tp is not None else None,
-                                                      C.byref(flt) if flt is not None else None,
-                                                      C.byref(text), C.byref(n), C.byref(st), C.byref(fst),
-                                                      str(support_table_path).encode())
-        if rc != N.BLU_OK:
-            raise N.BluError(rc, "blu_build_consensus_identities_support")
-        if out_path is not None:
-            return None, stats_of()
-    elif flt is not None:
-        # one entry point for every combination under a filter (include/blu_pipeline.h: blu_build_consensus_identities_filtered)
-        tp = None
-        if report_path is not None or sample_table_path is not None:
-            tp = TablesParams(str(report_path).encode() if report_path is not None else None,
-                              str(sample_table_path).encode() if sample_table_path is not None else None,
-                              REPORT_WEIGHT[report_weight], 0)
-        L.blu_build_consensus_identities_filtered.restype = C.c_int
-        L.blu_build_consensus_identities_filtered.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
-                                                              C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(TablesParams),
-                                                              C.POINTER(HitFilterC), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
-                                                              C.POINTER(PipelineStats), C.POINTER(HitFilterStats)]
-        rc = L.blu_build_consensus_identities_filtered(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
-                                                       taxonomies_file.encode(), C.byref(p), run_id, cfg_text,
-                                                       out_path.encode() if out_path is not None else None,
-                                                       C.byref(tp) if tp is not None else None, C.byref(flt),
-                                                       C.byref(text), C.byref(n), C.byref(st), C.byref(fst))
-        if rc != N.BLU_OK:
-            raise N.BluError(rc, "blu_build_consensus_identities_filtered")
-        if out_path is not None:
-            return None, stats_of()
-    elif sample_table_path is not None:
-        tp = TablesParams(str(report_path).encode() if report_path is not None else None, str(sample_table_path).encode(),
-                          REPORT_WEIGHT[report_weight], 0)
-        L.blu_build_consensus_identities_tables.restype = C.c_int
-        L.blu_build_consensus_identities_tables.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
-                                                            C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(TablesParams),
-                                                            C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(PipelineStats)]
-        rc = L.blu_build_consensus_identities_tables(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
-                                                     taxonomies_file.encode(), C.byref(p), run_id, cfg_text,
-                                                     out_path.encode() if out_path is not None else None, C.byref(tp),
-                                                     C.byref(text), C.byref(n), C.byref(st))
-        if rc != N.BLU_OK:
-            raise N.BluError(rc, "blu_build_consensus_identities_tables")
-        if out_path is not None:
-            return None, {f: getattr(st, f) for f, _ in PipelineStats._fields_}
-    elif report_path is not None:
-        rp = ReportParams(str(report_path).encode(), REPORT_WEIGHT[report_weight], 0)
-        L.blu_build_consensus_identities_report.restype = C.c_int
-        L.blu_build_consensus_identities_report.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
-                                                            C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(ReportParams),
-                                                            C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(PipelineStats)]
-        rc = L.blu_build_consensus_identities_report(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
-                                                     taxonomies_file.encode(), C.byref(p), run_id, cfg_text,
-                                                     out_path.encode() if out_path is not None else None, C.byref(rp),
-                                                     C.byref(text), C.byref(n), C.byref(st))
-        if rc != N.BLU_OK:
-            raise N.BluError(rc, "blu_build_consensus_identities_report")
-        if out_path is not None:
-            return None, {f: getattr(st, f) for f, _ in PipelineStats._fields_}
-    elif out_path is not None:
-        L.blu_build_consensus_identities_to_file.restype = C.c_int
-        L.blu_build_consensus_identities_to_file.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_char_p, C.POINTER(PipelineParams),
-                                                             C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PipelineStats)]
-        rc = L.blu_build_consensus_identities_to_file(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
-                                                      taxonomies_file.encode(), C.byref(p), run_id, cfg_text, out_path.encode(),
-                                                      C.byref(st))
-        if rc != N.BLU_OK:
-            raise N.BluError(rc, "blu_build_consensus_identities_to_file")
-        return None, {f: getattr(st, f) for f, _ in PipelineStats._fields_}
-    else:
-        rc = L.blu_build_consensus_identities_cfg(blast_output.encode(), C.cast(hdr_arr, C.c_void_p) if hdr_arr else None, n_hdr,
-                                                  taxonomies_file.encode(), C.byref(p), run_id, cfg_text, C.byref(text),
-                                                  C.byref(n), C.byref(st))
-        if rc != N.BLU_OK:
-            raise N.BluError(rc, "blu_build_consensus_identities")
+        names = [h.encode() for h in headers]
+        rq.headers, rq.n_headers = (C.c_char_p * max(1, len(names)))(*names), len(names)
+    if config is not None:
+        rq.run_id_text, rq.config_text = str(config.run_id).encode(), config.render(out_format).encode()
+    if report_path is not None or sample_table_path is not None:
+        rq.weight = REPORT_WEIGHT[report_weight]
+    oc = ConsensusOutcome(selection=sel.stats())
+    rc = L.blu_build_consensus(C.byref(rq), C.byref(oc))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_build_consensus")
+    stats = {f: getattr(oc.stats, f) for f, _ in PipelineStats._fields_}
+    stats.update(sel.counts(oc.selection))
+    if out_path is not None:
+        return None, stats
     try:
-        raw = C.string_at(text, n.value).decode("utf-8")
+        raw = C.string_at(oc.text, oc.text_len).decode("utf-8")
     finally:
-        L.blu_free_text(text)
-    stats = stats_of()
+        L.blu_free_text(oc.text)
     if not parse:
         return raw, stats
     if out_format in ("json", "json-compact"):

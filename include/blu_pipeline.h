@@ -48,80 +48,6 @@ typedef struct blu_pipeline_stats {
     double t_load_db_s, t_load_hits_s, t_engine_s, t_render_s;
 } blu_pipeline_stats;
 
-/* Runs the whole use-case.  headers/n_headers: Option<Vec<String>> of FASTA ids (NULL/0 = None): ids without a
- * hit row become NoConsensusFound entries (mod.rs:86-102).  On success *out_text is a malloc'd buffer with the
- * serialized results, sorted by query (write_blutils_output.rs:111), in `out_format`:
- *   JSON : {"results":[QueryWithConsensus...],"config":null} pretty-printed like serde_json::to_string_pretty
- *          (runId is a fresh UUID v4 per call; config is None on this path, cmds/blast/mod.rs:137-142)
- *   JSON_COMPACT: the same document on one line
- *   JSONL: the config line (`null`) then one QueryWithConsensus per line
- *   YAML : block style as serde_yaml 0.9 emits BlutilsOutput (scalar quoting rules of the third-party emitter are
- *          approximated: parity unpinned there)
- * Free with blu_free_text. */
-int blu_build_consensus_identities(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                   const char* taxonomies_file, const blu_pipeline_params* params, char** out_text,
-                                   size_t* out_len, blu_pipeline_stats* stats);
-/* The same with Some(BlastBuilder) as `config` (run_blast_and_build_consensus/mod.rs:53-67 -> write_blutils_output):
- * run_id_text = the config's run id (36 characters; NULL/"" = a fresh UUID), which every result carries
- * (write_blutils_output.rs:82-104); config_text = the config already serialized for `out_format` at its place in the
- * document (JSON: the value after "config": — for the pretty form with its inner lines indented by two spaces;
- * JSONL: the first line; YAML: the block under `config:`), NULL/"" = null.  blutils_amd/blast.py produces it. */
-int blu_build_consensus_identities_cfg(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                       const char* taxonomies_file, const blu_pipeline_params* params,
-                                       const char* run_id_text, const char* config_text, char** out_text, size_t* out_len,
-                                       blu_pipeline_stats* stats);
-/* The same, with the document written straight to `out_path` (no copy through the caller): what the CLI does with
- * --blutils-out-file. */
-int blu_build_consensus_identities_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                           const char* taxonomies_file, const blu_pipeline_params* params,
-                                           const char* run_id_text, const char* config_text, const char* out_path,
-                                           blu_pipeline_stats* stats);
-void blu_free_text(char* text);
-
-/* The use-case plus a taxon abundance report of its results in one run.  The document is what
- * blu_build_consensus_identities_to_file (out_path != NULL) or blu_build_consensus_identities_cfg (out_path == NULL: into
- * *out_text / *out_len) produces, byte for byte.  The report is counted on the device from the run's records
- * (blu_consensus_report) and written to report->report_path after the document, tab-separated:
- *   #percent  clade  direct  rank  identifier  taxonomy                 (header)
- *   pct  U  U  -  unclassified  (empty)      always; U = weight of the results with "taxon": null (headers without hits too)
- *   pct  N  N  -  unplaced  (empty)          when N > 0: results whose taxonomy is ""
- *   one line per path, depth first; siblings by clade descending, then element text `rank__identifier` ascending (bytewise)
- * percent = "%.2f" of 100.0 * clade / total (0.00 when total is 0).  Weights: BLU_REPORT_WEIGHT_ONE counts results;
- * BLU_REPORT_WEIGHT_SIZE counts the dereplicated reads in the query name: the first ';'-field `size=<digits>`, else a
- * `_size_<digits>` suffix, else 1 — a size of 2^32 or more is BLU_ERR_INVALID_ARG naming the query.  In strict mode a
- * reference panic fails the call before either file is written. */
-enum blu_report_weight { BLU_REPORT_WEIGHT_ONE = 0, BLU_REPORT_WEIGHT_SIZE = 1 };
-typedef struct blu_report_params {
-    const char* report_path;   /* created or truncated */
-    int32_t weight;            /* enum blu_report_weight */
-    int32_t reserved;
-} blu_report_params;
-int blu_build_consensus_identities_report(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                          const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                                          const char* config_text, const char* out_path, const blu_report_params* report,
-                                          char** out_text, size_t* out_len, blu_pipeline_stats* stats);
-
-/* The same with the report, a per-sample table, or both: either path may be NULL.  Files are written in the
- * order document, report, table.  The table is counted on the device (blu_consensus_sample_table) and is tab-separated:
- *   #rank  identifier  taxonomy  total  <sample 1>  <sample 2> ...   (header; samples ascending bytewise)
- *   -  unclassified  (empty)  U  u1  u2 ...                          always
- *   -  unplaced  (empty)  N  n1  n2 ...                              when N > 0
- *   rank  identifier  taxonomy  clade  <clade in sample 1> ...       one line per path, in the report's order
- * The sample of a query: the first ';'-field `sample=<one or more bytes>`; else, in the label (the name up to its first ';'
- * with a trailing `_size_<digits>` removed), the part left of the last '.' when that part is non-empty and the part right
- * of it is ASCII digits (vsearch --relabel `<sample>.<n>`).  A query (hit or header) with neither is BLU_ERR_INVALID_ARG
- * naming it, before any file is written.  `weight` applies to both files. */
-typedef struct blu_tables_params {
-    const char* report_path;         /* NULL: no report */
-    const char* sample_table_path;   /* NULL: no per-sample table */
-    int32_t weight;                  /* enum blu_report_weight */
-    int32_t reserved;
-} blu_tables_params;
-int blu_build_consensus_identities_tables(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                          const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                                          const char* config_text, const char* out_path, const blu_tables_params* tables,
-                                          char** out_text, size_t* out_len, blu_pipeline_stats* stats);
-
 /* Hit filters (not in the reference): thresholds on four columns of the table, applied by the parser.  A line
  * is kept when every threshold named in `mask` holds, as IEEE comparisons (a NaN fails):
  *   BLU_FILTER_MIN_PERC_IDENTITY  column 3  perc_identity >= min_perc_identity
@@ -147,34 +73,8 @@ typedef struct blu_hit_filter {
 } blu_hit_filter;
 typedef struct blu_hit_filter_stats {
     uint64_t n_lines;              /* non-empty lines of the table */
-    uint64_t n_kept;               /* lines the filter kept (= n_lines without a filter) */
+    uint64_t n_kept;               /* lines kept by the hit and the taxon filter together (= n_lines without either) */
 } blu_hit_filter_stats;
-/* The use-case with a filter: the arguments of blu_build_consensus_identities_tables, of which `tables` may be NULL here
- * (no report, no per-sample table) and out_path selects file or text as there, plus the filter and its counts
- * (filter_stats may be NULL). */
-int blu_build_consensus_identities_filtered(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                            const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                                            const char* config_text, const char* out_path, const blu_tables_params* tables,
-                                            const blu_hit_filter* filter, char** out_text, size_t* out_len,
-                                            blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats);
-
-/* The use-case with a per-query support table (not in the reference): the arguments of
- * blu_build_consensus_identities_filtered (tables and filter may be NULL) plus support_table_path; NULL is that call.  The
- * counts come from the device (blu_consensus_support) — on the records and columns the run left there, or through the
- * host-pointer route when the columns are on the host — over the kept lines under a filter, and are written after the
- * document, the report and the sample table, tab-separated:
- *   #query  rank  identifier  hits  matched  top_hits  top_support  support  bit_score  bits  support_bits  confidence
- * one line per result of the document, in the document's order (headers without hits included, every count zero).  rank and
- * identifier: the last element of the result's `taxonomy`, as the report's rows have them; `-` and `unclassified` when
- * `taxon` is null, `-` and `unplaced` when `taxonomy` is "".  The counts are blu_support's, in decimal; confidence is
- * "%.4f" of support / hits (0.0000 without hits).  In strict mode a reference panic fails the call before any file is
- * written; in lenient mode those queries are `unclassified` lines.  The document is what the call without the path writes. */
-int blu_build_consensus_identities_support(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                           const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                                           const char* config_text, const char* out_path, const blu_tables_params* tables,
-                                           const blu_hit_filter* filter, char** out_text, size_t* out_len,
-                                           blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats,
-                                           const char* support_table_path);
 
 /* Taxon filters (not in the reference): lines are dropped by the lineage of their subject, in the parser, so
  * that hits to uninformative or out-of-scope taxa do not take part.  An element is spelled `RANK__IDENTIFIER` as it appears in
@@ -200,53 +100,142 @@ typedef struct blu_taxon_filter_stats {
     uint64_t n_not_only;           /* lines that pass the exclude list and have no element on the only list */
     uint64_t* excluded_by;         /* caller's [n_exclude], or NULL: lines whose first matching exclude element, in list order, is k */
 } blu_taxon_filter_stats;
-/* The arguments of blu_build_consensus_identities_support plus the taxon filter and its counts (taxon_stats may be NULL).
- * filter_stats->n_kept stays "lines kept by everything". */
-int blu_build_consensus_identities_taxa(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                        const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                                        const char* config_text, const char* out_path, const blu_tables_params* tables,
-                                        const blu_hit_filter* filter, char** out_text, size_t* out_len,
-                                        blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats,
-                                        const char* support_table_path, const blu_taxon_filter* taxon_filter,
-                                        blu_taxon_filter_stats* taxon_stats);
 
-/* Bit-score band (not in the reference; include/blu_consensus.h: blu_score_band).  The arguments of
- * blu_build_consensus_identities_taxa plus the band and its counts (band_stats may be NULL).  The rows of a query whose
- * truncated bit-score lies in the band under the query's top score are given the top score before the engine runs; the top is
- * taken over the lines the hit and taxon filters keep.  The run gives, byte for byte, what the run without a band gives on a
- * copy of the (filtered) table in which column 12 of every in-band line is the decimal text of its query's top score: the
- * document, the report, the sample table and the support table, whose top_hits is then the band's size and whose bits /
- * support_bits sum the raised scores.  Applied once per run on the device (csrc/band_kernel.hip): on the column the GPU ingest
- * left there, or through the host-pointer route on host columns.  A NULL band or an empty mask is the call without it;
- * top_percent_milli = 0 and top_bits = 0 give its bytes. */
-int blu_build_consensus_identities_band(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                        const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                                        const char* config_text, const char* out_path, const blu_tables_params* tables,
-                                        const blu_hit_filter* filter, char** out_text, size_t* out_len,
-                                        blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats,
-                                        const char* support_table_path, const blu_taxon_filter* taxon_filter,
-                                        blu_taxon_filter_stats* taxon_stats, const blu_score_band* band,
-                                        blu_score_band_stats* band_stats);
+/* Which lines of the table take part, and with which score: the four options of DESIGN.md §14 and §16-§18, each NULL (or with
+ * an empty mask / two empty lists) when not asked for.  They apply in this order, and each one's contract is stated on the
+ * table the ones before it leave: */
+typedef struct blu_hit_selection {
+    const blu_hit_filter* hit_filter;       /* 1. with taxon_filter, in the parser: the lines both keep (above) */
+    const blu_taxon_filter* taxon_filter;
+    const blu_subject_best* subject_best;   /* 2. best hit per subject (include/blu_consensus.h): of the lines of
+                                               one (query, subject accession) pair that the filters keep, the one with the highest
+                                               truncated bit-score stays, the first in file order among equals; the others are
+                                               dropped before the band and the engine run.  The run gives, byte for byte, what the run
+                                               without the selection gives on a copy of the (filtered) table without the dropped
+                                               lines: the document, the report, the sample table and the support table; the stats'
+                                               n_hits and n_unmatched_rows are those of the copy.  Applied once per run on the device
+                                               (csrc/subject_kernel.hip): on the columns the GPU ingest left there, or through the
+                                               host-pointer route on host columns. */
+    const blu_score_band* score_band;       /* 3. bit-score band (include/blu_consensus.h): the rows of a query whose
+                                               truncated bit-score lies in the band under the query's top score are given the top
+                                               score before the engine runs; the top is taken over the lines that 1 and 2 keep.  The
+                                               run gives, byte for byte, what the run without a band gives on a copy of that table in
+                                               which column 12 of every in-band line is the decimal text of its query's top score: the
+                                               document, the report, the sample table and the support table, whose top_hits is then
+                                               the band's size and whose bits / support_bits sum the raised scores.  Applied once per
+                                               run on the device (csrc/band_kernel.hip), like 2.  top_percent_milli = 0 and
+                                               top_bits = 0 give the bytes of the run without a band. */
+} blu_hit_selection;
+/* The counts of a selection; an option that was not asked for reports the table as it passed by (nothing dropped, nothing
+ * raised), the taxon filter zeros.  Zeroed when the call begins — the caller's taxon_filter.excluded_by array [n_exclude] too, which is the one input
+ * here: set the pointer (or NULL) before the call. */
+typedef struct blu_hit_selection_stats {
+    blu_hit_filter_stats hit_filter;         /* n_kept: lines kept by hit_filter and taxon_filter together */
+    blu_taxon_filter_stats taxon_filter;
+    blu_subject_best_stats subject_best;
+    blu_score_band_stats score_band;
+} blu_hit_selection_stats;
 
-/* Best hit per subject (not in the reference; include/blu_consensus.h: blu_subject_best).  The arguments of
- * blu_build_consensus_identities_band plus the selection and its counts (subject_stats may be NULL).  Of the lines of one
- * (query, subject accession) pair that the hit and taxon filters keep, the one with the highest truncated bit-score stays,
- * the first in file order among equals, and the others are dropped before the band and the engine run.  The run gives, byte
- * for byte, what the run without the selection gives on a copy of the (filtered) table without the dropped lines: the document,
- * the report, the sample table and the support table; the stats' n_hits and n_unmatched_rows are those of the copy.  Applied
- * once per run on the device (csrc/subject_kernel.hip): on the columns the GPU ingest left there, or through the host-pointer
- * route on host columns.  A NULL selection or an empty mask is the call without it. */
-int blu_build_consensus_identities_subject(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
-                                           const char* taxonomies_file, const blu_pipeline_params* params, const char* run_id_text,
-                                           const char* config_text, const char* out_path, const blu_tables_params* tables,
-                                           const blu_hit_filter* filter, char** out_text, size_t* out_len,
-                                           blu_pipeline_stats* stats, blu_hit_filter_stats* filter_stats,
-                                           const char* support_table_path, const blu_taxon_filter* taxon_filter,
-                                           blu_taxon_filter_stats* taxon_stats, const blu_score_band* band,
-                                           blu_score_band_stats* band_stats, const blu_subject_best* subject_best,
-                                           blu_subject_best_stats* subject_stats);
+/* Weights of the report and the per-sample table: BLU_REPORT_WEIGHT_ONE counts results; BLU_REPORT_WEIGHT_SIZE counts the
+ * dereplicated reads in the query name: the first ';'-field `size=<digits>`, else a `_size_<digits>` suffix, else 1 — a size
+ * of 2^32 or more is BLU_ERR_INVALID_ARG naming the query. */
+enum blu_report_weight { BLU_REPORT_WEIGHT_ONE = 0, BLU_REPORT_WEIGHT_SIZE = 1 };
 
-/* The text-ingest half alone (no GPU): DB JSON + outfmt-6 TSV -> SoA columns, as blu_build_consensus_identities does it.
+/* One run of the use-case with everything it can write.  Set struct_size = sizeof(blu_consensus_request) and zero the rest
+ * before filling in what is wanted: options are added at the end of the struct, so a caller compiled against an older header
+ * keeps working and a size this library does not know is BLU_ERR_INVALID_ARG. */
+typedef struct blu_consensus_request {
+    uint32_t struct_size;
+    uint32_t reserved;
+    const char* blast_output_file;     /* ParallelBlastOutput.output_file: the outfmt-6 table */
+    const char* const* headers;        /* Option<Vec<String>> of FASTA ids (NULL/0 = None): ids without a hit row become */
+    uint64_t n_headers;                /*   NoConsensusFound entries (mod.rs:86-102) */
+    const char* taxonomies_file;       /* the `*.blutils.json`, or its binary cache (blu_db_cache_build, below) */
+    const blu_pipeline_params* params;
+    const char* run_id_text;           /* Some(BlastBuilder) as `config` (run_blast_and_build_consensus/mod.rs:53-67): the config's
+                                          run id (36 characters; NULL/"" = a fresh UUID v4 per call), which every result carries
+                                          (write_blutils_output.rs:82-104) */
+    const char* config_text;           /* the config already serialized for `out_format` at its place in the document (JSON: the
+                                          value after "config": — for the pretty form with its inner lines indented by two spaces;
+                                          JSONL: the first line; YAML: the block under `config:`), NULL/"" = null.
+                                          blutils_amd/blast.py produces it. */
+    const char* out_path;              /* the document is written straight there (no copy through the caller: what the CLI does
+                                          with --blutils-out-file; an existing file is replaced); NULL: into the outcome's text */
+    /* The three tables below are counted on the device from the run's records and written after the document, in this order;
+     * the document is, byte for byte, what the request without them gives.  In strict mode a reference panic fails the call
+     * before any file is written; so does a query without a sample under sample_table_path. */
+    const char* report_path;           /* NULL: no report.  Taxon abundance report, tab-separated:
+                                            #percent  clade  direct  rank  identifier  taxonomy        (header)
+                                            pct  U  U  -  unclassified  (empty)   always; U = weight of the results with "taxon": null
+                                                                                  (headers without hits too)
+                                            pct  N  N  -  unplaced  (empty)       when N > 0: results whose taxonomy is ""
+                                            one line per path, depth first; siblings by clade descending, then element text
+                                            `rank__identifier` ascending (bytewise)
+                                          percent = "%.2f" of 100.0 * clade / total (0.00 when total is 0). */
+    const char* sample_table_path;     /* NULL: no per-sample table, tab-separated:
+                                            #rank  identifier  taxonomy  total  <sample 1>  <sample 2> ...   (header; samples
+                                                                                                              ascending bytewise)
+                                            -  unclassified  (empty)  U  u1  u2 ...                          always
+                                            -  unplaced  (empty)  N  n1  n2 ...                              when N > 0
+                                            rank  identifier  taxonomy  clade  <clade in sample 1> ...       one line per path, in
+                                                                                                              the report's order
+                                          The sample of a query: the first ';'-field `sample=<one or more bytes>`; else, in the
+                                          label (the name up to its first ';' with a trailing `_size_<digits>` removed), the part
+                                          left of the last '.' when that part is non-empty and the part right of it is ASCII digits
+                                          (vsearch --relabel `<sample>.<n>`).  A query (hit or header) with neither is
+                                          BLU_ERR_INVALID_ARG naming it. */
+    int32_t weight;                    /* enum blu_report_weight, for both files above; read only when one of them is asked for */
+    int32_t reserved2;
+    const char* support_table_path;    /* NULL: no per-query support table (not in the reference).  The counts come
+                                          from the device (blu_consensus_support) — on the records and columns the run left there,
+                                          or through the host-pointer route when the columns are on the host — over the lines the
+                                          selection leaves, tab-separated:
+                                            #query  rank  identifier  hits  matched  top_hits  top_support  support  bit_score  bits
+                                            support_bits  confidence
+                                          one line per result of the document, in the document's order (headers without hits
+                                          included, every count zero).  rank and identifier: the last element of the result's
+                                          `taxonomy`, as the report's rows have them; `-` and `unclassified` when `taxon` is null,
+                                          `-` and `unplaced` when `taxonomy` is "".  The counts are blu_support's, in decimal;
+                                          confidence is "%.4f" of support / hits (0.0000 without hits).  In lenient mode the
+                                          queries of a reference panic are `unclassified` lines. */
+    blu_hit_selection selection;       /* all NULL: every line takes part */
+} blu_consensus_request;
+
+/* What a run gives back.  text: out_path == NULL: a malloc'd buffer with the serialized results (free with blu_free_text),
+ * sorted by query (write_blutils_output.rs:111), in `out_format`:
+ *   JSON : {"results":[QueryWithConsensus...],"config":null} pretty-printed like serde_json::to_string_pretty
+ *   JSON_COMPACT: the same document on one line
+ *   JSONL: the config line (`null` without a config_text) then one QueryWithConsensus per line
+ *   YAML : block style as serde_yaml 0.9 emits BlutilsOutput (scalar quoting rules of the third-party emitter are
+ *          approximated: parity unpinned there)
+ * With an out_path, and after a failure, text is NULL and text_len 0.  The whole outcome is zeroed when the call begins,
+ * selection.taxon_filter.excluded_by aside (blu_hit_selection_stats, above). */
+typedef struct blu_consensus_outcome {
+    char* text;
+    size_t text_len;
+    blu_pipeline_stats stats;
+    blu_hit_selection_stats selection;
+} blu_consensus_outcome;
+
+int blu_build_consensus(const blu_consensus_request* request, blu_consensus_outcome* outcome);
+void blu_free_text(char* text);
+
+/* The reference's own three signatures, each the request above with the named fields set and the rest zero
+ * (mod.rs:40-47 + write_blutils_output.rs:33-38 with config = None; the same with Some(BlastBuilder); the same to a file).
+ * out_len and stats may be NULL. */
+int blu_build_consensus_identities(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                   const char* taxonomies_file, const blu_pipeline_params* params, char** out_text,
+                                   size_t* out_len, blu_pipeline_stats* stats);
+int blu_build_consensus_identities_cfg(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                       const char* taxonomies_file, const blu_pipeline_params* params,
+                                       const char* run_id_text, const char* config_text, char** out_text, size_t* out_len,
+                                       blu_pipeline_stats* stats);
+int blu_build_consensus_identities_to_file(const char* blast_output_file, const char* const* headers, uint64_t n_headers,
+                                           const char* taxonomies_file, const blu_pipeline_params* params,
+                                           const char* run_id_text, const char* config_text, const char* out_path,
+                                           blu_pipeline_stats* stats);
+
+/* The text-ingest half alone (no GPU): DB JSON + outfmt-6 TSV -> SoA columns, as blu_build_consensus does it.
  * Fills stats (rows, queries, taxids, unmatched rows, load times) and *checksum with an FNV-1a hash over every SoA
  * column, the segment offsets and the query names — identical for any BLU_INGEST_THREADS value.  For tests and for
  * timing the ingest (rows/s) apart from the engine. */
@@ -277,26 +266,11 @@ typedef struct blu_ingest_columns {
 } blu_ingest_columns;
 int blu_ingest_columns_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
                           blu_ingest_columns* out);
-/* The same under a hit filter (above), on either parser: the columns of the kept lines.  filter_stats may be NULL. */
-int blu_ingest_columns_filtered_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
-                                   const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats);
-/* The same under a taxon filter as well (above): the arguments of blu_ingest_columns_filtered_on plus the filter and its counts. */
-int blu_ingest_columns_taxa_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
-                               const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
-                               const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats);
-/* The same with a bit-score band applied to the bitscore column (above): the arguments of blu_ingest_columns_taxa_on plus the
- * band and its counts.  A band with a non-empty mask needs a device (device >= 0) whichever parser ran. */
-int blu_ingest_columns_band_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
-                               const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
-                               const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
-                               const blu_score_band* band, blu_score_band_stats* band_stats);
-/* The same with the best hit per subject selected first (above): the arguments of blu_ingest_columns_band_on plus the selection
- * and its counts.  A selection with a non-empty mask needs a device (device >= 0) whichever parser ran. */
-int blu_ingest_columns_subject_on(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
-                                  const blu_hit_filter* filter, blu_ingest_columns* out, blu_hit_filter_stats* filter_stats,
-                                  const blu_taxon_filter* taxon_filter, blu_taxon_filter_stats* taxon_stats,
-                                  const blu_score_band* band, blu_score_band_stats* band_stats,
-                                  const blu_subject_best* subject_best, blu_subject_best_stats* subject_stats);
+/* The same under a selection (blu_hit_selection, above; NULL = none), on either parser: the columns of the lines the filters
+ * keep, thinned to the best hit per subject and with the band applied to the bitscore column, in that order.  stats may be
+ * NULL.  A best-hit selection or a band with a non-empty mask needs a device (device >= 0) whichever parser ran. */
+int blu_ingest_columns_selected(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                                const blu_hit_selection* selection, blu_ingest_columns* out, blu_hit_selection_stats* stats);
 void blu_ingest_columns_free(blu_ingest_columns* cols);
 
 /* Which parser the calling thread's last ingest used: 0 = CPU, 1 = GPU. */
@@ -305,7 +279,7 @@ int blu_last_ingest_path(void);
 /* Binary cache of the taxonomies file.  The reference re-parses the `*.blutils.json` on every run
  * (mod.rs:246-327, taxonomies_map.rs:6-32) and keeps only {taxid, numericLineage | textLineage}; this writes exactly
  * that — interned lineages of the chosen flavour — as a flat file.  Wherever a `taxonomies_file` is taken
- * (blu_build_consensus_identities, blu_ingest_only) a cache file is recognised by its magic and mapped instead of
+ * (blu_build_consensus, blu_ingest_only) a cache file is recognised by its magic and mapped instead of
  * parsed; results are identical.  A cache built for the other lineage flavour is refused (BLU_ERR_INVALID_ARG), a
  * truncated or altered one fails its checksum (BLU_ERR_PARSE). */
 int blu_db_cache_build(const char* taxonomies_file, int use_taxid, const char* cache_file);

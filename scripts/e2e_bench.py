@@ -4,7 +4,7 @@
     python scripts/e2e_bench.py [--queries 2000000] [--hits 50] [--taxa 300000] [--reps 2]
 
 Generates the inputs with scripts/tools/gen_blast.c (compiled here with gcc), then runs
-blu_build_consensus_identities_to_file in a FRESH process per repetition, so that HIP start-up is inside the wall
+blu_build_consensus with an out_path in a FRESH process per repetition, so that HIP start-up is inside the wall
 time, with the stage trace (BLU_INGEST_TRACE) on.  The number quoted in DESIGN.md is queries / wall of the call.
 """
 import argparse

@@ -290,8 +290,8 @@ def test_run_with_consensus_passes_the_flag_through(tmp_path, monkeypatch, capsy
 
 @pytest.mark.parametrize("mode", ["gpu", "host_columns"])
 def test_an_empty_selection_is_the_run_without_the_flag(tmp_path, monkeypatch, mode):
-    """blu_build_consensus_identities_subject with an empty mask (what the older entry points' NULL becomes inside): the bytes
-    and the counts of the run without the keyword."""
+    """blu_build_consensus with a subject_best whose mask is empty (what a NULL member becomes inside): the bytes and the
+    counts of the run without the keyword."""
     _set(monkeypatch, mode)
     rows = make_rows(40, np.random.default_rng(116), sample_names=True)
     src, tj = _table(tmp_path, rows), hf.write_db(tmp_path / "t.json")

@@ -62,9 +62,9 @@ def test_struct_mirrors():
     assert [getattr(N.ScoreBandStats, f).offset for f in ("n_hits", "n_raised", "n_queries", "n_widened")] == [0, 8, 16, 24]
     assert (N.BAND_TOP_PERCENT, N.BAND_TOP_BITS) == (1, 2)
     assert "blu_hits_score_band" in N.EXPORTS
-    assert {"blu_build_consensus_identities_band", "blu_ingest_columns_band_on"} <= set(N.PIPELINE_EXPORTS)
+    assert {"blu_build_consensus", "blu_ingest_columns_selected"} <= set(N.PIPELINE_EXPORTS)
     L = N.lib()
-    for name in ("blu_hits_score_band", "blu_build_consensus_identities_band", "blu_ingest_columns_band_on"):
+    for name in ("blu_hits_score_band", "blu_build_consensus", "blu_ingest_columns_selected"):
         assert hasattr(L, name)
 
 
@@ -96,12 +96,9 @@ def test_c_abi_refusals_need_no_device():
         assert (st.n_hits, st.n_raised, st.n_queries, st.n_widened) == (3, 0, 1, 0)
     # the pipeline's entry points refuse the same values before they read a file
     cols = pipeline.IngestColumns()
-    L = N.lib()
-    L.blu_ingest_columns_band_on.restype = C.c_int
-    L.blu_ingest_columns_band_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(pipeline.IngestColumns),
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(N.ScoreBandC), C.c_void_p]
-    rc = L.blu_ingest_columns_band_on(b"/nonexistent.tsv", b"/nonexistent.json", 0, -1, None, C.byref(cols), None, None, None,
-                                      C.byref(N.ScoreBandC(0, 8, 0)), None)
+    L = pipeline._bind()
+    sel = pipeline.HitSelection(score_band=C.pointer(N.ScoreBandC(0, 8, 0)))
+    rc = L.blu_ingest_columns_selected(b"/nonexistent.tsv", b"/nonexistent.json", 0, -1, C.byref(sel), C.byref(cols), None)
     assert rc == N.BLU_ERR_INVALID_ARG and "mask" in N.last_error()
 
 

@@ -60,10 +60,9 @@ def test_struct_mirrors_and_exports():
     assert [getattr(N.SubjectBestStats, f).offset for f in ("n_hits", "n_kept", "n_queries", "n_thinned")] == [0, 8, 16, 24]
     assert N.SUBJECT_BEST_PER_QUERY == 1
     assert {"blu_hits_subject_keep", "blu_hits_subject_best"} <= set(N.EXPORTS)
-    assert {"blu_build_consensus_identities_subject", "blu_ingest_columns_subject_on"} <= set(N.PIPELINE_EXPORTS)
+    assert {"blu_build_consensus", "blu_ingest_columns_selected"} <= set(N.PIPELINE_EXPORTS)
     L = N.lib()
-    for name in ("blu_hits_subject_keep", "blu_hits_subject_best", "blu_build_consensus_identities_subject",
-                 "blu_ingest_columns_subject_on"):
+    for name in ("blu_hits_subject_keep", "blu_hits_subject_best", "blu_build_consensus", "blu_ingest_columns_selected"):
         assert hasattr(L, name)
 
 
@@ -144,12 +143,8 @@ def test_c_abi_refusals_need_no_device():
         assert (st.n_hits, st.n_kept, st.n_queries, st.n_thinned) == (3, 3, 1, 0)
     # the pipeline's entry points refuse unknown bits before they read a file
     cols = pipeline.IngestColumns()
-    L.blu_ingest_columns_subject_on.restype = C.c_int
-    L.blu_ingest_columns_subject_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(pipeline.IngestColumns),
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(N.SubjectBestC),
-                                                C.c_void_p]
-    rc = L.blu_ingest_columns_subject_on(b"/nonexistent.tsv", b"/nonexistent.json", 0, -1, None, C.byref(cols), None, None, None, None,
-                                         None, C.byref(N.SubjectBestC(4, 0)), None)
+    sel = pipeline.HitSelection(subject_best=C.pointer(N.SubjectBestC(4, 0)))
+    rc = pipeline._bind().blu_ingest_columns_selected(b"/nonexistent.tsv", b"/nonexistent.json", 0, -1, C.byref(sel), C.byref(cols), None)
     assert rc == N.BLU_ERR_INVALID_ARG and "mask" in N.last_error()
 
 
@@ -159,18 +154,15 @@ def _duplicated_rows(rng):
 
 
 def test_a_null_selection_is_the_older_entry_point_on_the_cpu_path(tmp_path, monkeypatch):
-    """blu_build_consensus_identities_subject and blu_ingest_columns_subject_on with NULL or an empty mask: the bytes of
-    blu_build_consensus_identities_band / blu_ingest_columns_band_on (device -1, the CPU parser, the host engine path)."""
+    """blu_ingest_columns_selected with a NULL subject_best member, with the member present and its mask empty, and with a
+    selection struct that is all NULL (and no struct at all): the same bytes (device -1, the CPU parser).  The documents of
+    such requests are compared where there is a device: tests/test_gpu_subject_best.py, tests/test_gpu_consensus_request.py."""
     monkeypatch.setenv("BLU_INGEST", "cpu")
     rng = np.random.default_rng(91)
     src = tmp_path / "b.tsv"
     src.write_bytes(("\n".join(_duplicated_rows(rng)) + "\n").encode())
     tj = hf.write_db(tmp_path / "t.json")
     L = pipeline._bind()
-    L.blu_ingest_columns_band_on.restype = L.blu_ingest_columns_subject_on.restype = C.c_int
-    base = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(pipeline.IngestColumns)] + [C.c_void_p] * 5
-    L.blu_ingest_columns_band_on.argtypes = base
-    L.blu_ingest_columns_subject_on.argtypes = base + [C.POINTER(N.SubjectBestC), C.POINTER(N.SubjectBestStats)]
 
     def columns(c):
         out = {k: np.ctypeslib.as_array(getattr(c, k), shape=(int(c.n_hits),)).copy() for k in ("bitscore", "align_len", "tax_desc_row", "acc_rank", "pident")}
@@ -179,17 +171,20 @@ def test_a_null_selection_is_the_older_entry_point_on_the_cpu_path(tmp_path, mon
         return out
 
     old = pipeline.IngestColumns()
-    assert L.blu_ingest_columns_band_on(str(src).encode(), tj.encode(), 0, -1, None, C.byref(old), None, None, None, None, None) == N.BLU_OK
+    assert L.blu_ingest_columns_selected(str(src).encode(), tj.encode(), 0, -1, None, C.byref(old), None) == N.BLU_OK
     want = columns(old)
     L.blu_ingest_columns_free(C.byref(old))
-    for sel in (None, N.SubjectBestC(0, 0)):
-        new, st = pipeline.IngestColumns(), N.SubjectBestStats()
-        rc = L.blu_ingest_columns_subject_on(str(src).encode(), tj.encode(), 0, -1, None, C.byref(new), None, None, None, None, None,
-                                             C.byref(sel) if sel is not None else None, C.byref(st))
+    empty_band = C.pointer(N.ScoreBandC(0, 0, 0))
+    for sel in (pipeline.HitSelection(), pipeline.HitSelection(score_band=empty_band),                 # all NULL; the member NULL
+                pipeline.HitSelection(subject_best=C.pointer(N.SubjectBestC(0, 0))),                    # present, mask 0
+                pipeline.HitSelection(score_band=empty_band, subject_best=C.pointer(N.SubjectBestC(0, 0)))):
+        new, st = pipeline.IngestColumns(), pipeline.HitSelectionStats()
+        rc = L.blu_ingest_columns_selected(str(src).encode(), tj.encode(), 0, -1, C.byref(sel), C.byref(new), C.byref(st))
         assert rc == N.BLU_OK
         got = columns(new)
         L.blu_ingest_columns_free(C.byref(new))
         assert all(np.array_equal(got[k], want[k]) if k != "names" else got[k] == want[k] for k in want)
+        st = st.subject_best
         assert (st.n_hits, st.n_kept, st.n_thinned) == (len(want["bitscore"]), len(want["bitscore"]), 0)
     # the keyword left False is the call of before, and the stats carry no counts
     a = pipeline.ingest_columns(str(src), tj, device=-1)

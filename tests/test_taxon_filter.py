@@ -193,14 +193,11 @@ def test_no_filter_and_an_empty_filter_are_todays_call(tmp_path):
     # the C entry point with two empty lists is the call without it
     import ctypes as C
     L = pipeline._bind()
-    c, fst, tst = pipeline.IngestColumns(), pipeline.HitFilterStats(), pipeline.TaxonFilterStats()
-    L.blu_ingest_columns_taxa_on.restype = C.c_int
-    L.blu_ingest_columns_taxa_on.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(pipeline.IngestColumns),
-                                             C.POINTER(pipeline.HitFilterStats), C.POINTER(pipeline.TaxonFilterC),
-                                             C.POINTER(pipeline.TaxonFilterStats)]
-    L.blu_ingest_columns_free.argtypes = [C.POINTER(pipeline.IngestColumns)]
+    c, st = pipeline.IngestColumns(), pipeline.HitSelectionStats()
     empty = pipeline.TaxonFilterC(None, 0, None, 0)
-    assert L.blu_ingest_columns_taxa_on(src.encode(), tj.encode(), 0, -1, None, C.byref(c), C.byref(fst), C.byref(empty), C.byref(tst)) == 0
+    sel = pipeline.HitSelection(taxon_filter=C.pointer(empty))
+    assert L.blu_ingest_columns_selected(src.encode(), tj.encode(), 0, -1, C.byref(sel), C.byref(c), C.byref(st)) == 0
+    fst, tst = st.hit_filter, st.taxon_filter
     assert (int(c.n_hits), int(fst.n_lines), int(fst.n_kept)) == (len(today["bitscore"]),) * 3
     assert (int(tst.n_lines), int(tst.n_excluded), int(tst.n_not_only)) == (0, 0, 0)
     L.blu_ingest_columns_free(C.byref(c))
