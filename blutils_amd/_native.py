@@ -16,13 +16,13 @@ EXPORTS = (
     "blu_consensus_last_launch", "blu_hits_pack", "blu_hits_pack64", "blu_taxonomy_shared_levels", "blu_taxonomy_trim",
     "blu_consensus_report", "blu_report_free", "blu_dev_exclusive_scan", "blu_dev_radix_sort_pairs", "blu_dev_line_index",
     "blu_consensus_sample_table", "blu_sample_table_free", "blu_consensus_support", "blu_hits_score_band",
-    "blu_hits_subject_keep", "blu_hits_subject_best",
+    "blu_hits_subject_keep", "blu_hits_subject_best", "blu_hits_cover_keep", "blu_hits_cover_apply",
 )
 # include/blu_pipeline.h
 PIPELINE_EXPORTS = ("blu_build_consensus", "blu_build_consensus_identities", "blu_build_consensus_identities_cfg",
                     "blu_build_consensus_identities_to_file", "blu_free_text", "blu_custom_taxon_from_file", "blu_ingest_only",
                     "blu_ingest_only_on", "blu_ingest_columns_on", "blu_ingest_columns_selected", "blu_ingest_columns_free",
-                    "blu_last_ingest_path", "blu_db_cache_build", "blu_taxdb_build", "blu_seqdb_export", "blu_qiime_taxonomy_tsv")
+                    "blu_last_ingest_path", "blu_last_min_cover_stats", "blu_db_cache_build", "blu_taxdb_build", "blu_seqdb_export", "blu_qiime_taxonomy_tsv")
 
 BLU_UNMATCHED_TAXID = 0xFFFFFFFF
 BLU_NONE_U8, BLU_NONE_U16, BLU_MAR_NEVER_EQUAL = 0xFF, 0xFFFF, 0xFFFE
@@ -88,6 +88,19 @@ class SubjectBestStats(C.Structure):
 
 def subject_counts(st: SubjectBestStats) -> dict:
     return {f: int(getattr(st, f)) for f, _ in SubjectBestStats._fields_}
+
+
+MIN_COVER_MILLI_LOW, MIN_COVER_MILLI_HIGH = 50001, 100000
+
+
+class MinCoverStats(C.Structure):
+    """include/blu_consensus.h: blu_min_cover_stats"""
+    _fields_ = [("n_hits", C.c_uint64), ("n_kept", C.c_uint64), ("n_queries", C.c_uint64), ("n_narrowed", C.c_uint64),
+                ("n_unresolved", C.c_uint64)]
+
+
+def cover_counts(st: MinCoverStats) -> dict:
+    return {f: int(getattr(st, f)) for f, _ in MinCoverStats._fields_}
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -157,6 +170,16 @@ def lib() -> C.CDLL:
         L.blu_hits_subject_best.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                             C.c_uint64, C.c_int, C.POINTER(SubjectBestC), C.c_void_p, C.c_uint32,
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(SubjectBestStats)]
+    if hasattr(L, "blu_hits_cover_keep"):        # (an A/B library of an older build: BLU_CONSENSUS_LIB)
+        L.blu_hits_cover_keep.restype = C.c_int
+        L.blu_hits_cover_keep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
+                                          C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MinCoverStats)]
+        L.blu_hits_cover_apply.restype = C.c_int
+        L.blu_hits_cover_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(MinCoverStats)]
+        L.blu_last_min_cover_stats.restype = C.c_int
+        L.blu_last_min_cover_stats.argtypes = [C.POINTER(MinCoverStats)]
     L.blu_consensus_last_launch.restype = C.c_int
     L.blu_consensus_last_launch.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     _lib = L

@@ -84,6 +84,22 @@ one pass over the bit-score column on the GPU (csrc/band_kernel.hip) makes it so
 exact ties: the bytes of the run without the flag.  To stderr, after the filter lines:
 `score band: raised R of N lines in W of Q queries`.
 
+    python -m blutils_amd.cli blastn build-consensus ... [--min-cover P]
+    python -m blutils_amd.cli blastn run-with-consensus ... (the same)
+
+not in the reference: the minimum cover.  The reference asks every hit of a query's top bit-score group to agree,
+so one mislabelled accession among forty tied hits of one species sends the query to the domain — and a band widens the group.
+With --min-cover P (a decimal with at most three decimals, above 50 and at most 100; read exactly, compared in integers) the
+query is placed at the deepest taxon that still covers P percent of its top hits, as MEGAN's percent-to-cover does: of the n
+lines on the top score — the band's lines included — `need` is the smallest integer with need * 100 >= n * P, the covering
+lineage prefix is the longest one that at least `need` of them start with, and the top lines that do not start with it do not
+take part.  Lines under the top score are never touched; a query with a top line whose taxid is not in the taxonomies file, or
+whose lineage is bad or empty, is left as it is.  Applied last, on the table the filters, --best-hit-per-subject and the band
+leave: the run gives what it gives on a copy of that table without the dropped lines — the document, --report, --sample-table
+and --support-table; one pass over the grouped columns on the GPU (csrc/cover_kernel.hip) makes it so.  `--min-cover 100` drops
+nothing: the bytes of the run without the flag.  To stderr, after the band's line:
+`min cover: kept K of N lines, narrowed W of Q queries, U left alone`.
+
     python -m blutils_amd.cli cache-db TAX.json CACHE [-u]
 
 writes the binary cache of a taxonomies file (not in the reference CLI; pass CACHE as -t afterwards).  
@@ -201,6 +217,13 @@ def build_parser() -> argparse.ArgumentParser:
         bnd.add_argument("--top-bits", type=_top_bits, metavar="D",
                          help="hits whose truncated bit-score is at most D below the query's top count as tied with it; an "
                               "integer, 0 .. 2^32 - 1 (not in the reference CLI)")
+        cov = sp.add_argument_group("minimum cover (not in the reference CLI)",
+                                    "top hits outside the deepest taxon that still covers P percent of a query's top group do "
+                                    "not take part; applied after the band, on the GPU, before the consensus")
+        cov.add_argument("--min-cover", type=_min_cover, metavar="P",
+                         help="place a query at the deepest taxon that covers at least P percent of its top hits and drop the "
+                              "top hits outside it; a decimal with at most three decimals, above 50 and at most 100 (not in the "
+                              "reference CLI)")
     br = blastn.add_parser("build-report", help="blutils result document -> taxon abundance report (not in the reference)")
     br.add_argument("blu_result", nargs="?", default="-")
     br.add_argument("-o", "--output-file")
@@ -283,6 +306,16 @@ def _top_percent(text: str):
     return decimal.Decimal(text.strip())
 
 
+def _min_cover(text: str):
+    """--min-cover: a decimal with at most three decimals, above 50 and at most 100, kept exact (decimal.Decimal)"""
+    import decimal
+    try:
+        pipeline.min_cover_milli(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return decimal.Decimal(text.strip())
+
+
 def _top_bits(text: str) -> int:
     """--top-bits: an integer in 0 .. 2^32 - 1"""
     try:
@@ -342,6 +375,10 @@ def _say_kept(stats, hit_filter=True) -> None:
     if b:
         print(f"score band: raised {b['n_raised']} of {b['n_hits']} lines in {b['n_widened']} of {b['n_queries']} queries",
               file=sys.stderr)
+    c = stats.get("min_cover") if stats else None
+    if c:
+        print(f"min cover: kept {c['n_kept']} of {c['n_hits']} lines, narrowed {c['n_narrowed']} of {c['n_queries']} queries, "
+              f"{c['n_unresolved']} left alone", file=sys.stderr)
 
 
 def _build_db(args) -> int:
@@ -395,7 +432,8 @@ def _run_with_consensus(args) -> int:
                                             sample_table_path=args.sample_table, hit_filter=hit_filter,
                                             filter_stats=stats, support_table_path=args.support_table,
                                             taxon_filter=taxon_filter, score_band=_score_band(args),
-                                            **({"best_hit_per_subject": True} if args.best_hit_per_subject else {}))
+                                            **({"best_hit_per_subject": True} if args.best_hit_per_subject else {}),
+                                            **({"min_cover": args.min_cover} if args.min_cover is not None else {}))
     except blast.BlastError as e:
         raise SystemExit(str(e))
     except _native.BluError as e:
@@ -447,6 +485,8 @@ def main(argv=None) -> int:
         extra["score_band"] = score_band
     if args.best_hit_per_subject:
         extra["best_hit_per_subject"] = True
+    if args.min_cover is not None:
+        extra["min_cover"] = args.min_cover
     if args.support_table is not None:
         build = functools.partial(pipeline.build_consensus_identities_with_tables, report_path=args.report,
                                   sample_table_path=args.sample_table, report_weight=args.report_weight,

@@ -173,10 +173,38 @@ struct SubjectColumns { int32_t** bitscore; int32_t** align_len; uint32_t** tax_
 int subject_best_device(SubjectColumns& c, uint64_t n_hits, uint64_t n_queries, bool rotate, uint32_t unmatched_marker,
                         uint64_t* n_hits_out, uint64_t* n_unmatched, uint64_t* n_thinned, std::vector<void*>* retired, bool count_only);
 
+// the compaction half of the above, for any pass that gives verdicts in that form (cover_kernel.hip too): d_keep[n_hits + 1] = 1 / 0
+// per row and a last word 0 -> the scan of the keep words, the five gathers, seg_off rewritten, the unmatched rows recounted.
+// all_kept (or n_hits == 0): nothing moves and d_keep is not read, only *n_unmatched is counted.  `who` names the pass in messages.
+int compact_kept_device(const char* who, SubjectColumns& c, uint64_t n_hits, uint64_t n_queries, const uint32_t* d_keep, bool all_kept, bool rotate,
+                        uint32_t unmatched_marker, uint64_t* n_hits_out, uint64_t* n_unmatched, std::vector<void*>* retired);
+
 // the same on the columns the GPU ingest left on the device (ingest.h: DeviceHits): compacted by rotation, the retired buffer goes
 // to its trash, n_hits shrinks and seg_off is rewritten in place; *unmatched: the kept rows with no taxonomy row
 struct DeviceHits;
 int subject_best_hits(DeviceHits& dev, blu_subject_best_stats* stats, uint64_t* unmatched);
+
+// cover_kernel.hip: the minimum cover on device columns (device pointers; blu_hits_cover_keep / blu_hits_cover_apply stage host
+// ones).  Everything runs on the null stream of the current device — the taxonomy's — and the calls return when
+// their outputs are complete.
+#define BLU_COVER_QUERIES_PER_WAVE 4u     // consecutive queries of one wave in the short kernel; four waves a block
+// BLU_ERR_INVALID_ARG (and a message that says "min cover") for a value outside 50001 .. 100000
+int check_min_cover(int64_t min_cover_milli);
+// BLU_ERR_INVALID_ARG for n_hits >= 2^32 or n_queries >= 2^32
+int check_cover_counts(uint64_t n_hits, uint64_t n_queries);
+// the verdicts: d_keep[n_hits] = 1 / 0, d_depth[n_queries] (may be null) = d*, BLU_NONE_U8 for a query left alone.  d_tax_row holds
+// engine row ids, or desc rows when d_row_map[n_tax] is given
+int cover_keep_device(const blu_taxonomy* tax, const int32_t* d_bitscore, const uint32_t* d_tax_row, const uint32_t* d_row_map,
+                      const uint64_t* d_seg_off, uint64_t n_hits, uint64_t n_queries, uint32_t min_cover_milli, uint32_t* d_keep,
+                      uint8_t* d_depth, blu_min_cover_stats* stats);
+// the verdicts and the compaction (compact_kept_device, above)
+int cover_apply_device(const blu_taxonomy* tax, SubjectColumns& c, const uint32_t* d_row_map, uint64_t n_hits, uint64_t n_queries,
+                       uint32_t min_cover_milli, bool rotate, uint32_t unmatched_marker, uint64_t* n_hits_out, uint64_t* n_unmatched,
+                       blu_min_cover_stats* stats, std::vector<void*>* retired);
+// the same on the columns the GPU ingest left on the device, which hold desc rows: fwd[n_tax] (host; blu_taxonomy_row_map's forward
+// table) goes up once; compacted by rotation as subject_best_hits does
+int cover_hits(const blu_taxonomy* tax, DeviceHits& dev, const uint32_t* fwd, uint64_t n_tax, uint32_t min_cover_milli,
+               blu_min_cover_stats* stats, uint64_t* unmatched);
 
 void set_error(const char* fmt, ...);
 // LinnaeanRank::from_str (linnaean_ranks.rs:52-72): enum kind 0..8, or K_FIRST_OTHER with the slug in *other

@@ -765,6 +765,8 @@ int taxon_codes(const Db& db, const blu_taxon_filter& f, unsigned nthreads, Taxo
 // and the workers scatter their rows into the grouped table.  The result does not depend on the thread count.
 thread_local double g_t_body_end = 0;   // stage trace: when build_document's last statement ran (what follows is its tear-down)
 thread_local int g_last_ingest_path = 0;   // 0 = CPU parser, 1 = GPU parser (blu_last_ingest_path)
+// the minimum cover's counts (blu_last_min_cover_stats): of the run under way, and of the last run once it has succeeded
+thread_local blu_min_cover_stats g_cover_pending{}, g_last_min_cover{};
 
 int load_hits(const char* path, const Db& db, HitTable& ht, int device = -1, bool host_columns = true, const blu_hit_filter* flt = nullptr,
               TaxonCodes* taxa = nullptr) {
@@ -1603,7 +1605,9 @@ struct Selection {
     std::unique_ptr<TaxonCodes> taxa;             // (the taxon filter as the parsers read it)
     blu_hit_selection_stats own{};                // (a caller that wants no counts)
     blu_hit_selection_stats* const st;
-    bool subject_done = false, band_done = false; // (once per run, on the device columns or on the host columns)
+    int64_t cover_milli = 0;                      // (blu_consensus_request.min_cover_milli; 0 = not asked for: DESIGN.md §20)
+    blu_min_cover_stats cover_st{};               // (its counts: blu_last_min_cover_stats)
+    bool subject_done = false, band_done = false, cover_done = false;   // (once per run, on the device columns or on the host columns)
 
     // the caller's counts start at zero, its excluded_by array included, whatever the call then does
     Selection(const blu_hit_selection* sel, blu_hit_selection_stats* stats) : asked(sel ? *sel : blu_hit_selection{}), st(stats ? stats : &own) {
@@ -1618,6 +1622,7 @@ struct Selection {
         if (asked.hit_filter && (asked.hit_filter->mask & ~15u)) { set_error("hit filter: unknown bits in the mask"); return BLU_ERR_INVALID_ARG; }
         if (int rc = check_score_band(asked.score_band)) return rc;
         if (int rc = check_subject_best(asked.subject_best)) return rc;
+        if (cover_milli != 0) if (int rc = check_min_cover(cover_milli)) return rc;
         if (asked.hit_filter && (asked.hit_filter->mask & 15u)) flt = asked.hit_filter;
         if (asked.taxon_filter && (asked.taxon_filter->n_exclude || asked.taxon_filter->n_only)) tflt = asked.taxon_filter;
         if (asked.subject_best && asked.subject_best->mask) subj = asked.subject_best;
@@ -1641,9 +1646,10 @@ struct Selection {
         st->subject_best = blu_subject_best_stats{ht.n_hits, ht.n_hits, ht.n_queries, 0};
         st->score_band = blu_score_band_stats{ht.n_hits, 0, ht.n_queries, 0};
     }
-    // Options 2 and 3 on host columns, through the host-pointer route of their kernels: whatever of the two has not been
-    // applied on the device columns.  The table's counts follow the kept rows.
-    int on_host_columns(int device, HitTable& ht, Trace* tr = nullptr) {
+    // Options 2 and 3 and the minimum cover on host columns, through the host-pointer route of their kernels: whatever of the
+    // three has not been applied on the device columns.  The table's counts follow the kept rows.  tax, fwd: the taxonomy handle
+    // and its forward row map, which the cover needs (the ingest-columns call has neither, and no cover).
+    int on_host_columns(int device, HitTable& ht, Trace* tr = nullptr, const blu_taxonomy* tax = nullptr, const uint32_t* fwd = nullptr) {
         if (subj && !subject_done && ht.n_hits) {
             uint64_t n_out = ht.n_hits, unmatched = ht.unmatched;
             int rc = blu_hits_subject_best(device, ht.bitscore.data(), ht.align_len.data(), ht.tax_desc_row.data(), ht.acc_rank.data(),
@@ -1663,6 +1669,17 @@ struct Selection {
             band_done = true;
             if (tr) tr->lap("score band (host columns)");
         }
+        if (cover_milli && !cover_done && tax && ht.n_hits) {
+            uint64_t n_out = ht.n_hits, unmatched = ht.unmatched;
+            int rc = blu_hits_cover_apply(tax, ht.bitscore.data(), ht.align_len.data(), ht.tax_desc_row.data(), ht.acc_rank.data(), ht.pident.data(),
+                                          fwd, ht.seg_off.data(), ht.n_hits, ht.n_queries, 0, (uint32_t)cover_milli, nullptr, BLU_UNMATCHED_TAXID,
+                                          &n_out, &unmatched, &cover_st);
+            if (rc != BLU_OK) return rc;
+            ht.bitscore.resize(n_out); ht.align_len.resize(n_out); ht.tax_desc_row.resize(n_out); ht.acc_rank.resize(n_out); ht.pident.resize(n_out);
+            ht.n_hits = n_out; ht.unmatched = unmatched;
+            cover_done = true;
+            if (tr) tr->lap("min cover (host columns)");
+        }
         return BLU_OK;
     }
 };
@@ -1674,6 +1691,7 @@ int build_document(const blu_consensus_request& rq, Document* document, blu_cons
     const char* const out_path = rq.out_path;
     Selection sel(&rq.selection, &outcome->selection);
     if (!rq.blast_output_file || !rq.taxonomies_file || !params) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    sel.cover_milli = rq.min_cover_milli;
     if (int rc = sel.check()) return rc;
     if ((rq.report_path || rq.sample_table_path) && rq.weight != BLU_REPORT_WEIGHT_ONE && rq.weight != BLU_REPORT_WEIGHT_SIZE) {
         set_error("report: a path and weight BLU_REPORT_WEIGHT_ONE or BLU_REPORT_WEIGHT_SIZE are needed");
@@ -1775,6 +1793,16 @@ int build_document(const blu_consensus_request& rq, Document* document, blu_cons
         sel.band_done = true;
         tr.lap("score band (device)");
     }
+    // the minimum cover, once per run and after the band, whose rows are part of the top group it reads: on the
+    // device columns, compacted by rotation as under the best hit per subject, else on the host columns
+    if (sel.cover_milli && on_device && ht.dev->n_hits) {
+        uint64_t unmatched = ht.unmatched;
+        rc = cover_hits(tax, *ht.dev, fwd.data(), db.taxid.size(), (uint32_t)sel.cover_milli, &sel.cover_st, &unmatched);
+        if (rc != BLU_OK) return rc;
+        ht.n_hits = ht.dev->n_hits; ht.unmatched = unmatched;
+        sel.cover_done = true;
+        tr.lap("min cover (device)");
+    }
     if (on_device) {
         // the GPU ingest left the grouped columns on the device: the engine reads them in place and only the records and
         // the top-score rows come back (if that fails — e.g. no room for the work buffers — the columns are downloaded and
@@ -1785,7 +1813,7 @@ int build_document(const blu_consensus_request& rq, Document* document, blu_cons
     // (the device columns and the engine's work buffers stay with the hit table: they are freed off the caller's path at the end)
     if (!done_on_device) ht.dev.reset();
     if (!done_on_device) {
-        if ((rc = sel.on_host_columns(params->device, ht, &tr)) != BLU_OK) return rc;
+        if ((rc = sel.on_host_columns(params->device, ht, &tr, tax, fwd.data())) != BLU_OK) return rc;
         eng_rows.resize(ht.tax_desc_row.size());
         for (size_t i = 0; i < eng_rows.size(); ++i)
             eng_rows[i] = ht.tax_desc_row[i] == BLU_UNMATCHED_TAXID ? BLU_UNMATCHED_TAXID : fwd[ht.tax_desc_row[i]];
@@ -1813,7 +1841,9 @@ int build_document(const blu_consensus_request& rq, Document* document, blu_cons
         }
         top_rows_from_columns(ht, recs, nthreads, top);
     }
-    if (sel.subject_done) { st.n_hits = ht.n_hits; st.n_unmatched_rows = ht.unmatched; }
+    if (sel.subject_done || sel.cover_done) { st.n_hits = ht.n_hits; st.n_unmatched_rows = ht.unmatched; }
+    if (sel.cover_milli && !sel.cover_done) sel.cover_st = blu_min_cover_stats{ht.n_hits, ht.n_hits, ht.n_queries, 0, 0};   // (an empty table)
+    g_cover_pending = sel.cover_st;
     st.t_engine_s = now_s() - t0;
     tr.lap("engine + top rows");
 
@@ -2152,6 +2182,7 @@ bool blu::parse_f64_field(const char* p, size_t n, double* out) { return parse_f
 extern "C" {
 
 int blu_build_consensus(const blu_consensus_request* request, blu_consensus_outcome* outcome) {
+    g_cover_pending = g_last_min_cover = blu_min_cover_stats{};
     if (!request || !outcome) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     if (request->struct_size != sizeof(blu_consensus_request)) {
         set_error("blu_build_consensus: struct_size %u is not a blu_consensus_request this library knows (%zu bytes)", request->struct_size,
@@ -2159,7 +2190,11 @@ int blu_build_consensus(const blu_consensus_request* request, blu_consensus_outc
         return BLU_ERR_INVALID_ARG;
     }
     outcome->text = nullptr; outcome->text_len = 0; outcome->stats = blu_pipeline_stats{};   // (outcome->selection: by Selection)
-    try { return request->out_path ? consensus_to_file(*request, outcome) : consensus_to_text(*request, outcome); }
+    try {
+        const int rc = request->out_path ? consensus_to_file(*request, outcome) : consensus_to_text(*request, outcome);
+        if (rc == BLU_OK) g_last_min_cover = g_cover_pending;
+        return rc;
+    }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }   // (no exception crosses the C ABI)
 }
 
@@ -2261,6 +2296,12 @@ void blu_ingest_columns_free(blu_ingest_columns* c) {
 
 // domain/dtos/taxon.rs:28-66: YAML (flat `key: value` lines) or JSON object with the eight fields
 int blu_last_ingest_path(void) { return g_last_ingest_path; }
+
+int blu_last_min_cover_stats(blu_min_cover_stats* out) {
+    if (!out) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    *out = g_last_min_cover;
+    return BLU_OK;
+}
 
 int blu_db_cache_build(const char* taxonomies_file, int use_taxid, const char* cache_file) {
     if (!taxonomies_file || !cache_file) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }

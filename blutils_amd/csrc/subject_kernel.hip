@@ -281,12 +281,12 @@ int subject_keep_device(const int32_t* d_bitscore, const uint32_t* d_acc_rank, c
     return BLU_OK;
 }
 
-int subject_best_device(SubjectColumns& c, uint64_t n_hits, uint64_t n_queries, bool rotate, uint32_t unmatched_marker,
-                        uint64_t* n_hits_out, uint64_t* n_unmatched, uint64_t* n_thinned, std::vector<void*>* retired, bool count_only) {
-    HipPolicy pol{"best hit per subject", BLU_ERR_ALLOC};
+int compact_kept_device(const char* who, SubjectColumns& c, uint64_t n_hits, uint64_t n_queries, const uint32_t* d_keep, bool all_kept, bool rotate,
+                        uint32_t unmatched_marker, uint64_t* n_hits_out, uint64_t* n_unmatched, std::vector<void*>* retired) {
+    HipPolicy pol{who, BLU_ERR_ALLOC};
     DeviceArena mem(pol);
-    *n_hits_out = n_hits; *n_thinned = 0;
-    uint32_t *d_keep = nullptr, *d_pos = nullptr;
+    *n_hits_out = n_hits;
+    uint32_t* d_pos = nullptr;
     unsigned long long* d_cnt = nullptr;
     HIP_CHECK(pol, mem.alloc(&d_cnt, SUBJ_SPREAD * 8, "unmatched count"));
     auto count_unmatched = [&](uint64_t n) -> int {
@@ -300,13 +300,7 @@ int subject_best_device(SubjectColumns& c, uint64_t n_hits, uint64_t n_queries, 
         for (uint32_t k = 0; k < SUBJ_SPREAD; ++k) *n_unmatched += cnt[k];
         return BLU_OK;
     };
-    if (n_hits == 0 || count_only) return count_unmatched(n_hits);
-    HIP_CHECK(pol, mem.alloc(&d_keep, (n_hits + 1) * 4, "keep words"));
-    HIP_CHECK(pol, hipMemsetAsync(d_keep + n_hits, 0, 4, nullptr));
-    uint64_t n_kept = 0;
-    int rc = subject_keep_device(*c.bitscore, *c.acc_rank, (const uint64_t*)c.seg_off, n_hits, n_queries, d_keep, &n_kept, n_thinned);
-    if (rc != BLU_OK) return rc;
-    if (n_kept == n_hits) return count_unmatched(n_hits);   // every row kept: the columns are not touched
+    if (n_hits == 0 || all_kept) return count_unmatched(n_hits);   // every row kept: the columns are not touched
     void* d_tmp = nullptr;
     HIP_CHECK(pol, mem.alloc(&d_pos, (n_hits + 1) * 4, "keep positions"));
     HIP_CHECK(pol, mem.alloc(&d_tmp, scan_tmp_bytes_u32(n_hits + 1), "scan work"));
@@ -330,7 +324,7 @@ int subject_best_device(SubjectColumns& c, uint64_t n_hits, uint64_t n_queries, 
         return BLU_OK;
     };
     if (rotate) mem.release(spare);                  // (from here the spare is one of the caller's buffers or goes to `retired`)
-    rc = move(c.pident);
+    int rc = move(c.pident);
     if (rc == BLU_OK) rc = move(c.bitscore);
     if (rc == BLU_OK) rc = move(c.align_len);
     if (rc == BLU_OK) rc = move(c.tax_desc_row);
@@ -344,6 +338,22 @@ int subject_best_device(SubjectColumns& c, uint64_t n_hits, uint64_t n_queries, 
     if (rc != BLU_OK) return rc;
     HIP_CHECK(pol, hipStreamSynchronize(nullptr));
     return BLU_OK;
+}
+
+int subject_best_device(SubjectColumns& c, uint64_t n_hits, uint64_t n_queries, bool rotate, uint32_t unmatched_marker,
+                        uint64_t* n_hits_out, uint64_t* n_unmatched, uint64_t* n_thinned, std::vector<void*>* retired, bool count_only) {
+    HipPolicy pol{"best hit per subject", BLU_ERR_ALLOC};
+    DeviceArena mem(pol);
+    *n_hits_out = n_hits; *n_thinned = 0;
+    if (n_hits == 0 || count_only)
+        return compact_kept_device(pol.who, c, n_hits, n_queries, nullptr, true, rotate, unmatched_marker, n_hits_out, n_unmatched, retired);
+    uint32_t* d_keep = nullptr;
+    HIP_CHECK(pol, mem.alloc(&d_keep, (n_hits + 1) * 4, "keep words"));
+    HIP_CHECK(pol, hipMemsetAsync(d_keep + n_hits, 0, 4, nullptr));
+    uint64_t n_kept = 0;
+    int rc = subject_keep_device(*c.bitscore, *c.acc_rank, (const uint64_t*)c.seg_off, n_hits, n_queries, d_keep, &n_kept, n_thinned);
+    if (rc != BLU_OK) return rc;
+    return compact_kept_device(pol.who, c, n_hits, n_queries, d_keep, n_kept == n_hits, rotate, unmatched_marker, n_hits_out, n_unmatched, retired);
 }
 
 int subject_best_hits(DeviceHits& dev, blu_subject_best_stats* stats, uint64_t* unmatched) {

@@ -523,6 +523,105 @@ def subject_best_device(seg_off, bitscore, align_len, tax_desc_row, acc_rank, pi
     return int(n_out.value), int(n_un.value), N.subject_counts(st)
 
 
+def _cover_map(tax: Taxonomy, row_map):
+    """row_map as the host route takes it: None, or [n_tax] uint32 (True: the handle's own forward map)"""
+    if row_map is None:
+        return None
+    if row_map is True:
+        row_map = tax.row_map()[0]
+    m = np.ascontiguousarray(row_map, dtype=np.uint32)
+    assert len(m) == tax.n_tax, (len(m), tax.n_tax)
+    return m
+
+
+def cover_keep_host(tax: Taxonomy, seg_off, bitscore, tax_row, min_cover_milli: int, row_map=None):
+    """blu_hits_cover_keep on host arrays: -> (the uint32 keep words, d* per query as uint8 with 0xFF for a
+    query left alone, the counts).  tax_row holds engine row ids, or desc rows when row_map ([n_tax] uint32, or True for the
+    handle's own) is given.  The columns, the map and the offsets are uploaded and the device kernels run; min_cover_milli is
+    the percentage times 1000 and is passed as it is (the library refuses what is out of range)."""
+    seg = np.ascontiguousarray(seg_off, dtype=np.uint64)
+    bs = np.ascontiguousarray(bitscore, dtype=np.int32)
+    rows = np.ascontiguousarray(tax_row, dtype=np.uint32)
+    assert len(rows) == len(bs)
+    n, nq = len(bs), len(seg) - 1
+    m = _cover_map(tax, row_map)
+    keep, depth, st = np.empty(n, dtype=np.uint32), np.empty(nq, dtype=np.uint8), N.MinCoverStats()
+    rc = N.lib().blu_hits_cover_keep(tax.handle, bs.ctypes.data if n else None, rows.ctypes.data if n else None,
+                                     m.ctypes.data if m is not None else None, seg.ctypes.data, n, nq, 0, int(min_cover_milli), None,
+                                     keep.ctypes.data if n else None, depth.ctypes.data if nq else None, C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_hits_cover_keep")
+    return keep, depth, N.cover_counts(st)
+
+
+def cover_keep_device(tax: Taxonomy, seg_off, bitscore, tax_row, min_cover_milli: int, keep, depth=None, row_map=None,
+                      stream: Optional[int] = None) -> dict:
+    """blu_hits_cover_keep on torch CUDA tensors (seg_off int64, bitscore / tax_row / keep int32 holding the 32-bit words, depth
+    uint8 [n_queries] or None, row_map int32 [n_tax] or None): the verdicts go to `keep`, d* to `depth`; -> the counts."""
+    import torch
+
+    for t, dt in ((seg_off, torch.int64), (bitscore, torch.int32), (tax_row, torch.int32), (keep, torch.int32)) + \
+            (((depth, torch.uint8),) if depth is not None else ()) + (((row_map, torch.int32),) if row_map is not None else ()):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dt, (t.dtype, t.device)
+    assert keep.numel() == bitscore.numel() == tax_row.numel()
+    assert depth is None or depth.numel() == seg_off.numel() - 1
+    assert row_map is None or row_map.numel() == tax.n_tax
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    st = N.MinCoverStats()
+    rc = N.lib().blu_hits_cover_keep(tax.handle, bitscore.data_ptr(), tax_row.data_ptr(), row_map.data_ptr() if row_map is not None else None,
+                                     seg_off.data_ptr(), bitscore.numel(), seg_off.numel() - 1, 1, int(min_cover_milli), stream,
+                                     keep.data_ptr(), depth.data_ptr() if depth is not None else None, C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_hits_cover_keep")
+    return N.cover_counts(st)
+
+
+def cover_apply_host(tax: Taxonomy, seg_off, bitscore, align_len, tax_row, acc_rank, pident, min_cover_milli: int, row_map=None,
+                     unmatched_marker: int = N.BLU_UNMATCHED_TAXID):
+    """blu_hits_cover_apply on host arrays: -> (a dict of the compacted seg_off and five columns, n_unmatched, the
+    counts).  The arguments are not changed; tax_row and row_map as for cover_keep_host."""
+    seg = np.array(seg_off, dtype=np.uint64)
+    cols = [np.array(bitscore, dtype=np.int32), np.array(align_len, dtype=np.int32), np.array(tax_row, dtype=np.uint32),
+            np.array(acc_rank, dtype=np.uint32), np.array(pident, dtype=np.float64)]
+    n = len(cols[0])
+    assert all(len(c) == n for c in cols)
+    m = _cover_map(tax, row_map)
+    st, n_out, n_un = N.MinCoverStats(), C.c_uint64(0), C.c_uint64(0)
+    rc = N.lib().blu_hits_cover_apply(tax.handle, *[c.ctypes.data if n else None for c in cols], m.ctypes.data if m is not None else None,
+                                      seg.ctypes.data, n, len(seg) - 1, 0, int(min_cover_milli), None, unmatched_marker, C.byref(n_out),
+                                      C.byref(n_un), C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_hits_cover_apply")
+    k = int(n_out.value)
+    names = ("bitscore", "align_len", "tax_row", "acc_rank", "pident")
+    out = {name: c[:k].copy() for name, c in zip(names, cols)}
+    out["seg_off"] = seg
+    return out, int(n_un.value), N.cover_counts(st)
+
+
+def cover_apply_device(tax: Taxonomy, seg_off, bitscore, align_len, tax_row, acc_rank, pident, min_cover_milli: int, row_map=None,
+                       unmatched_marker: int = N.BLU_UNMATCHED_TAXID, stream: Optional[int] = None):
+    """blu_hits_cover_apply on torch CUDA tensors, in place (seg_off int64, the 32-bit columns int32, pident float64, row_map int32
+    [n_tax] or None): -> (the rows left, n_unmatched, the counts); the kept rows are the front of each tensor."""
+    import torch
+
+    for t, dt in ((seg_off, torch.int64), (bitscore, torch.int32), (align_len, torch.int32), (tax_row, torch.int32),
+                  (acc_rank, torch.int32), (pident, torch.float64)) + (((row_map, torch.int32),) if row_map is not None else ()):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dt, (t.dtype, t.device)
+    assert row_map is None or row_map.numel() == tax.n_tax
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    st, n_out, n_un = N.MinCoverStats(), C.c_uint64(0), C.c_uint64(0)
+    rc = N.lib().blu_hits_cover_apply(tax.handle, bitscore.data_ptr(), align_len.data_ptr(), tax_row.data_ptr(), acc_rank.data_ptr(),
+                                      pident.data_ptr(), row_map.data_ptr() if row_map is not None else None, seg_off.data_ptr(),
+                                      bitscore.numel(), seg_off.numel() - 1, 1, int(min_cover_milli), stream, unmatched_marker,
+                                      C.byref(n_out), C.byref(n_un), C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_hits_cover_apply")
+    return int(n_out.value), int(n_un.value), N.cover_counts(st)
+
+
 def records_from_tensor(out) -> np.ndarray:
     """uint8 CUDA/CPU tensor -> numpy structured array of blu_result."""
     return out.detach().cpu().numpy().view(np.uint8).reshape(-1)[: (out.numel() * out.element_size()) // 32 * 32].view(RESULT_DTYPE)

@@ -156,6 +156,26 @@ def top_percent_milli(value) -> int:
     return int(m)
 
 
+def min_cover_milli(value) -> int:
+    """A --min-cover value -> thousandths of a percent (50001 .. 100000), exactly: a decimal with at most three decimals, above
+    50 and at most 100.  Read with decimal.Decimal (never through a float); anything else — NaN, infinities, a fourth decimal,
+    50 itself — is a ValueError."""
+    if isinstance(value, (float, bool)):
+        raise ValueError(f"min_cover: pass a decimal string or decimal.Decimal, not {value!r}")
+    try:
+        d = value if isinstance(value, decimal.Decimal) else decimal.Decimal(str(value).strip())
+    except decimal.InvalidOperation:
+        raise ValueError(f"min_cover: not a decimal number: {value!r}")
+    if not d.is_finite():
+        raise ValueError(f"min_cover: not a finite number: {value!r}")
+    m = d * 1000
+    if m != m.to_integral_value():
+        raise ValueError(f"min_cover: at most three decimals, got {value!r}")
+    if not 50 < d <= 100:
+        raise ValueError(f"min_cover: must be above 50 and at most 100, got {value!r}")
+    return int(m)
+
+
 def top_bits_value(value) -> int:
     """A --top-bits value: an integer in 0 .. 2^32 - 1."""
     if isinstance(value, (float, bool)) or (not isinstance(value, int) and not str(value).strip().lstrip("+-").isdigit()):
@@ -217,7 +237,7 @@ class ConsensusRequest(C.Structure):
                 ("headers", C.POINTER(C.c_char_p)), ("n_headers", C.c_uint64), ("taxonomies_file", C.c_char_p),
                 ("params", C.POINTER(PipelineParams)), ("run_id_text", C.c_char_p), ("config_text", C.c_char_p),
                 ("out_path", C.c_char_p), ("report_path", C.c_char_p), ("sample_table_path", C.c_char_p), ("weight", C.c_int32),
-                ("reserved2", C.c_int32), ("support_table_path", C.c_char_p), ("selection", HitSelection)]
+                ("min_cover_milli", C.c_int32), ("support_table_path", C.c_char_p), ("selection", HitSelection)]
 
 
 class ConsensusOutcome(C.Structure):
@@ -252,6 +272,16 @@ class _Selection:
         if self.sel is not None:
             out["subject_best"] = N.subject_counts(st.subject_best)
         return out
+
+
+def last_min_cover_stats() -> dict:
+    """blu_last_min_cover_stats: the minimum cover's counts of this thread's last blu_build_consensus (zeros when that run had no
+    min_cover or failed)"""
+    st = N.MinCoverStats()
+    rc = N.lib().blu_last_min_cover_stats(C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_last_min_cover_stats")
+    return N.cover_counts(st)
 
 
 def _bind():
@@ -357,7 +387,8 @@ def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: s
                                out_format: str = "json", device: int = 0, lenient: bool = False, parse: bool = True,
                                config=None, out_path: Optional[str] = None, hit_filter: Union[None, dict, HitFilter] = None,
                                taxon_filter: Union[None, dict, TaxonFilter] = None,
-                               score_band: Union[None, dict, ScoreBand] = None, best_hit_per_subject: bool = False):
+                               score_band: Union[None, dict, ScoreBand] = None, best_hit_per_subject: bool = False,
+                               min_cover=None):
     """Returns (results, stats).  With out_path the document is written there by the library (no copy through Python) and
     (None, stats) is returned.  results: the parsed `results` list (json) / list of records (jsonl), sorted by
     query, or the raw text when parse=False.  config: Some(BlastBuilder) of the run-with-consensus path
@@ -369,10 +400,14 @@ def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: s
     filters; stats then also has `score_band`, its counts (n_hits, n_raised, n_queries, n_widened).  best_hit_per_subject: of
     the lines of one (query, subject accession) pair only the best takes part — the highest truncated bit-score, the first in
     file order among equals — after the filters and before the band; stats then also has `subject_best`, its
-    counts (n_hits, n_kept, n_queries, n_thinned), and n_hits / n_unmatched_rows count the kept lines."""
+    counts (n_hits, n_kept, n_queries, n_thinned), and n_hits / n_unmatched_rows count the kept lines.  min_cover (a decimal
+    string or Decimal above 50 and at most 100, at most three decimals; None = strict agreement): of the lines on a query's top
+    bit-score, the band's included, those outside the deepest taxon that still covers that percentage of them do not take part
+    (DESIGN.md §20), after everything above; stats then also has `min_cover`, its counts (n_hits, n_kept, n_queries,
+    n_narrowed, n_unresolved), and n_hits / n_unmatched_rows count the kept lines."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, None, "one", hit_filter=hit_filter, taxon_filter=taxon_filter,
-                  score_band=score_band, best_hit_per_subject=best_hit_per_subject)
+                  score_band=score_band, best_hit_per_subject=best_hit_per_subject, min_cover=min_cover)
 
 
 def build_consensus_identities_with_report(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -384,13 +419,13 @@ def build_consensus_identities_with_report(blast_output: str, taxonomies_file: s
                                            report_weight: str = "one", hit_filter: Union[None, dict, HitFilter] = None,
                                            taxon_filter: Union[None, dict, TaxonFilter] = None,
                                            score_band: Union[None, dict, ScoreBand] = None,
-                                           best_hit_per_subject: bool = False):
+                                           best_hit_per_subject: bool = False, min_cover=None):
     """build_consensus_identities plus the taxon abundance report of its results, counted on the GPU and written to
     report_path after the document (include/blu_pipeline.h: blu_consensus_request.report_path).
     report_weight: "one" (results) or "size" (dereplicated reads named in the query)."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, report_path, report_weight, hit_filter=hit_filter, taxon_filter=taxon_filter,
-                  score_band=score_band, best_hit_per_subject=best_hit_per_subject)
+                  score_band=score_band, best_hit_per_subject=best_hit_per_subject, min_cover=min_cover)
 
 
 def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -404,7 +439,7 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
                                            support_table_path: Optional[str] = None,
                                            taxon_filter: Union[None, dict, TaxonFilter] = None,
                                            score_band: Union[None, dict, ScoreBand] = None,
-                                           best_hit_per_subject: bool = False):
+                                           best_hit_per_subject: bool = False, min_cover=None):
     """build_consensus_identities plus the taxon abundance report (report_path), the per-sample table (sample_table_path,
     DESIGN.md §13), or both, counted on the GPU and written in the order document, report, table
     (include/blu_pipeline.h: blu_consensus_request).  report_weight serves both files.  A query whose name
@@ -415,13 +450,14 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, report_path, report_weight, sample_table_path, hit_filter=hit_filter,
                   support_table_path=support_table_path, taxon_filter=taxon_filter, score_band=score_band,
-                  best_hit_per_subject=best_hit_per_subject)
+                  best_hit_per_subject=best_hit_per_subject, min_cover=min_cover)
 
 
 def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device, lenient,
            parse, config, out_path, report_path, report_weight, sample_table_path=None, hit_filter=None,
-           support_table_path=None, taxon_filter=None, score_band=None, best_hit_per_subject=False):
+           support_table_path=None, taxon_filter=None, score_band=None, best_hit_per_subject=False, min_cover=None):
     L = _bind()
+    cover = min_cover_milli(min_cover) if min_cover is not None else 0
     sel = _Selection(hit_filter, taxon_filter, score_band, best_hit_per_subject)
     p = PipelineParams()
     p.cutoffs.taxon = N.TAXON[taxon]
@@ -448,12 +484,15 @@ def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_tax
         rq.run_id_text, rq.config_text = str(config.run_id).encode(), config.render(out_format).encode()
     if report_path is not None or sample_table_path is not None:
         rq.weight = REPORT_WEIGHT[report_weight]
+    rq.min_cover_milli = cover
     oc = ConsensusOutcome(selection=sel.stats())
     rc = L.blu_build_consensus(C.byref(rq), C.byref(oc))
     if rc != N.BLU_OK:
         raise N.BluError(rc, "blu_build_consensus")
     stats = {f: getattr(oc.stats, f) for f, _ in PipelineStats._fields_}
     stats.update(sel.counts(oc.selection))
+    if cover:
+        stats["min_cover"] = last_min_cover_stats()
     if out_path is not None:
         return None, stats
     try:

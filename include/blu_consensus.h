@@ -438,6 +438,56 @@ int blu_hits_subject_best(int device, int32_t* bitscore, int32_t* align_len, uin
                           uint64_t* seg_off, uint64_t n_hits, uint64_t n_queries, int on_device, const blu_subject_best* sel, void* stream,
                           uint32_t unmatched_marker, uint64_t* n_hits_out, uint64_t* n_unmatched_out, blu_subject_best_stats* stats);
 
+/* -------------------------------------------------------------------------- */
+/* Minimum cover (additive, ABI v5; not in the reference).  The consensus of a query is the strict agreement of the
+ * rows that tie on its top truncated bit-score, so one mislabelled accession among forty tied hits of one species has a veto.
+ * Under a minimum cover of P percent (min_cover_milli = 1000 P, 50001 .. 100000: 50 < P <= 100, compared in integers) the query is
+ * placed at the deepest taxon that still covers P % of its top group, and the top rows outside that taxon are dropped.  For a
+ * segment whose top group T (the rows on the segment's maximum score) has n rows:
+ *   need = the smallest integer with need * 100000 >= n * min_cover_milli                       (64-bit arithmetic)
+ *   c    = the longest sequence of lineage nodes, root first, that at least `need` rows of T start with
+ *          (need > n / 2: two such sequences are nested, so the longest is unique; the empty one always qualifies); d* = |c|
+ * and a row of T is dropped iff its lineage does not start with c.  Rows under the top score are never touched, and at least
+ * `need` >= 1 top rows stay, so the top score stays.  A query is LEFT ALONE — every row kept — when n <= 1, and (counted as
+ * n_unresolved) when T holds a row that is BLU_UNMATCHED_TAXID, a row whose lineage is `bad` or empty (length 0 in the engine row
+ * id), or a row id that names no taxonomy row (position >= n_tax, length beyond the taxonomy's deepest lineage; under a row_map
+ * also a desc row >= n_tax): the engine's verdict on such a query is not this pass's to change.  min_cover_milli = 100000
+ * drops nothing (c is the common prefix of T).  On the kept table every row of T starts with c, so a second pass finds a prefix
+ * that extends c; it is NOT in general the same one: the group has shrunk, `need` with it, and a deeper taxon may now cover it
+ * (10 rows at 60 %: four of species 1;2, two of 1;3, four elsewhere -> c = 1, six rows stay, and of those six 1;2 covers 60 %).
+ * The contract is stated for one pass.
+ * Decided on the device (csrc/cover_kernel.hip) from the engine row ids and the taxonomy's lcp8 / rmq tables alone: lineage order
+ * makes a clade a range of sorted positions, a clade with more than half of T holds T's median row m by position, the levels a
+ * row shares with m are a range minimum, and d* is the need-th largest of them. */
+typedef struct blu_min_cover_stats {
+    uint64_t n_hits;        /* rows in */
+    uint64_t n_kept;        /* rows kept */
+    uint64_t n_queries;
+    uint64_t n_narrowed;    /* queries that lost at least one row */
+    uint64_t n_unresolved;  /* queries left alone because of a top row without a usable lineage */
+} blu_min_cover_stats;
+/* The verdicts alone: keep_out[i] = 1 / 0, one 32-bit word per row, under seg_off[n_queries + 1]; depth_out[q] (may be NULL) = d*,
+ * BLU_NONE_U8 for a query left alone (an empty segment too); stats may be NULL.  tax_row[i] is the engine row id of row i, or —
+ * when row_map (blu_taxonomy_row_map's forward table, [n_tax]) is given — its desc row, mapped on the device.  The device is the
+ * handle's.  on_device = 1: device pointers (row_map too); the call waits for `stream` (a hipStream_t, NULL = default), runs on
+ * the default stream and returns when the outputs are complete.  on_device = 0: the columns, the map and the offsets are
+ * uploaded, the same kernels run, the verdicts are copied back — there is no second implementation and no CPU fallback: a
+ * host-only handle is BLU_ERR_NO_DEVICE.  Offsets beyond n_hits are clamped to it and a decreasing pair is an empty segment: a
+ * corrupt table reads nothing outside the columns and the taxonomy's tables; a row that no segment names gets 0.
+ * BLU_ERR_INVALID_ARG, before any device is asked for: min_cover_milli outside 50001 .. 100000 ("min cover: ..."), a NULL array
+ * with a non-zero count, n_hits >= 2^32 or n_queries >= 2^32. */
+int blu_hits_cover_keep(const blu_taxonomy* tax, const int32_t* bitscore, const uint32_t* tax_row, const uint32_t* row_map /* NULL: tax_row holds engine ids */,
+                        const uint64_t* seg_off, uint64_t n_hits, uint64_t n_queries, int on_device, uint32_t min_cover_milli, void* stream,
+                        uint32_t* keep_out, uint8_t* depth_out, blu_min_cover_stats* stats);
+/* The same pass, then the compaction of the five columns and seg_off IN PLACE, as blu_hits_subject_best does it (the same code):
+ * the kept rows move to the front of each column in their order, seg_off[q] becomes the number of kept rows before it.
+ * *n_hits_out: the rows left; *n_unmatched_out: how many of them have tax_row == unmatched_marker (either may be NULL).  When every
+ * row is kept the columns are not touched.  Device pointers must be 16-byte aligned.  Otherwise as above. */
+int blu_hits_cover_apply(const blu_taxonomy* tax, int32_t* bitscore, int32_t* align_len, uint32_t* tax_row, uint32_t* acc_rank, double* pident,
+                         const uint32_t* row_map, uint64_t* seg_off, uint64_t n_hits, uint64_t n_queries, int on_device,
+                         uint32_t min_cover_milli, void* stream, uint32_t unmatched_marker, uint64_t* n_hits_out, uint64_t* n_unmatched_out,
+                         blu_min_cover_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,7 +185,17 @@ typedef struct blu_consensus_request {
                                           (vsearch --relabel `<sample>.<n>`).  A query (hit or header) with neither is
                                           BLU_ERR_INVALID_ARG naming it. */
     int32_t weight;                    /* enum blu_report_weight, for both files above; read only when one of them is asked for */
-    int32_t reserved2;
+    int32_t min_cover_milli;           /* 0: not asked for.  Minimum cover (include/blu_consensus.h: blu_hits_cover_apply),
+                                          the percentage times 1000, 50001 .. 100000; any other value is BLU_ERR_INVALID_ARG ("min
+                                          cover: ...") before a file is opened.  The FOURTH step of the selection below, after the
+                                          band and on the table steps 1 - 3 leave: of the rows on a query's top score — the band's
+                                          rows included — those outside the deepest taxon that still covers that share of them are
+                                          dropped before the engine runs.  The run gives, byte for byte, what the run with the same
+                                          options before it gives on a copy of that table without the dropped lines: the document,
+                                          the report, the sample table and the support table; the stats' n_hits and n_unmatched_rows
+                                          are those of the copy.  100000 gives the bytes of the run without it.  Applied once per run
+                                          on the device (csrc/cover_kernel.hip), like steps 2 and 3; its counts: blu_last_min_cover_stats.
+                                          (The field took the place of a reserved word: neither struct here can grow.) */
     const char* support_table_path;    /* NULL: no per-query support table (not in the reference).  The counts come
                                           from the device (blu_consensus_support) — on the records and columns the run left there,
                                           or through the host-pointer route when the columns are on the host — over the lines the
@@ -268,13 +278,19 @@ int blu_ingest_columns_on(const char* blast_output_file, const char* taxonomies_
                           blu_ingest_columns* out);
 /* The same under a selection (blu_hit_selection, above; NULL = none), on either parser: the columns of the lines the filters
  * keep, thinned to the best hit per subject and with the band applied to the bitscore column, in that order.  stats may be
- * NULL.  A best-hit selection or a band with a non-empty mask needs a device (device >= 0) whichever parser ran. */
+ * NULL.  A best-hit selection or a band with a non-empty mask needs a device (device >= 0) whichever parser ran.
+ * The minimum cover (blu_consensus_request.min_cover_milli) is not part of a blu_hit_selection and this call does not learn it:
+ * it needs the taxonomy handle, which the ingest half does not build; blu_hits_cover_keep / blu_hits_cover_apply
+ * (include/blu_consensus.h) are the column-level calls. */
 int blu_ingest_columns_selected(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
                                 const blu_hit_selection* selection, blu_ingest_columns* out, blu_hit_selection_stats* stats);
 void blu_ingest_columns_free(blu_ingest_columns* cols);
 
 /* Which parser the calling thread's last ingest used: 0 = CPU, 1 = GPU. */
 int blu_last_ingest_path(void);
+/* The minimum cover's counts of the calling thread's last blu_build_consensus (the outcome has no room for them): zeros when
+ * that run had no min_cover_milli or failed.  Returns BLU_OK, BLU_ERR_INVALID_ARG for a NULL `out`. */
+int blu_last_min_cover_stats(blu_min_cover_stats* out);
 
 /* Binary cache of the taxonomies file.  The reference re-parses the `*.blutils.json` on every run
  * (mod.rs:246-327, taxonomies_map.rs:6-32) and keeps only {taxid, numericLineage | textLineage}; this writes exactly
