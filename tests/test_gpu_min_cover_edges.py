@@ -17,16 +17,29 @@ UNMATCHED = 0xFFFFFFFF
 TOP = 1000
 
 
-class Tax:
-    """lineages (lists of node ids; bad rows flagged) -> the library's handle, the independent engine row ids, and each row's
-    lineage as the reference takes it"""
+class _RowLineages:
+    """row -> its lineage as the reference takes it, read from the matrix when asked for"""
 
-    def __init__(self, lineages, bad=()):
-        self.lineages = [list(l) for l in lineages]
-        n = len(lineages)
+    def __init__(self, lin, length):
+        self.lin, self.length = lin, length
+
+    def __getitem__(self, t):
+        return tuple(int(x) for x in self.lin[t, :self.length[t]])
+
+
+class Tax:
+    """lineages (lists of node ids; bad rows flagged), or their [n, depth] matrix padded with -1 -> the library's handle, the
+    independent engine row ids, and each row's lineage as the reference takes it"""
+
+    def __init__(self, lineages=None, bad=(), matrix=None):
+        if matrix is None:
+            self.lineages = [list(l) for l in lineages]
+            raw, raw_len = se.to_matrix(self.lineages)
+        else:                                                            # (a table too large to go through lists)
+            raw, raw_len = matrix, (matrix >= 0).sum(axis=1).astype(np.int64)
+        n = len(raw)
         self.bad = np.zeros(n, np.uint8)
         self.bad[list(bad)] = 1
-        raw, raw_len = se.to_matrix(self.lineages)
         lin = raw.copy()
         lin[self.bad != 0] = -1
         length = np.where(self.bad != 0, 0, raw_len)
@@ -36,12 +49,13 @@ class Tax:
         self.order = order
         self.eng = (self.pos_of | (length << se.ROW_BITS)).astype(np.uint32)
         lin_off = np.concatenate([[0], np.cumsum(raw_len)]).astype(np.uint64)
-        node = np.array([x for l in self.lineages for x in l], np.uint32)
+        node = raw[raw >= 0].astype(np.uint32)
         rank = np.full(len(node), synth.RANK_NAMES.index("clade"), np.uint16)
         self.tax = engine.Taxonomy(lin_off, node, rank, synth.RANK_NAMES, taxon="bacteria", device=0, bad=self.bad)
         fwd = self.tax.row_map()[0]
         assert np.array_equal(fwd, self.eng), "the row map differs from the independent sort"
-        self.ref_lineage = [() if self.bad[t] else tuple(self.lineages[t]) for t in range(n)]
+        self.ref_lineage = _RowLineages(lin, length)
+        self.eng_dev = None
 
     def row_at(self, pos):
         return int(self.order[pos])
@@ -51,9 +65,11 @@ class Table:
     """segments of (desc row | -1 unmatched | ('id', raw engine id) | ('desc', raw desc row), score)"""
 
     def __init__(self, tx):
-        self.tx, self.seg, self.bs, self.desc, self.ids, self.lin = tx, [0], [], [], [], []
+        self.tx, self.seg, self.bs, self.desc, self.ids, self.lin, self.notes = tx, [0], [], [], [], [], []
 
-    def query(self, rows):
+    def query(self, rows, note=None):
+        """`note`: what a failure at this query is to say about it"""
+        self.notes.append(note)
         for r, b in rows:
             self.bs.append(int(b))
             if isinstance(r, tuple):                                     # a corrupt word: no lineage, whichever route carries it
@@ -85,7 +101,9 @@ class Table:
             t_bs, t_rows = torch.tensor(bs, device="cuda"), torch.tensor(rows.view(np.int32), device="cuda")
             t_keep = torch.full((len(bs),), 7, dtype=torch.int32, device="cuda")
             t_depth = torch.full((len(seg) - 1,), 9, dtype=torch.uint8, device="cuda")
-            t_map = torch.tensor(self.tx.eng.view(np.int32), device="cuda") if use_map else None
+            if use_map and self.tx.eng_dev is None:
+                self.tx.eng_dev = torch.tensor(self.tx.eng.view(np.int32), device="cuda")
+            t_map = self.tx.eng_dev if use_map else None
             c = engine.cover_keep_device(self.tx.tax, t_seg, t_bs, t_rows, milli, t_keep, t_depth, row_map=t_map)
             self._same(f"device/{name}", t_keep.cpu().numpy(), t_depth.cpu().numpy(), c, want_v, want_d, want_c)
         if narrowed is not None:
@@ -94,14 +112,16 @@ class Table:
             assert (want_c["n_unresolved"] > 0) == unresolved, want_c
         return want_v, want_d, want_c
 
-    @staticmethod
-    def _same(route, v, d, c, want_v, want_d, want_c):
+    def _same(self, route, v, d, c, want_v, want_d, want_c):
         v, d = [int(x) for x in v], [int(x) for x in d]
+        note = lambda q: self.notes[q] if q < len(self.notes) and self.notes[q] else f"query {q}"
         bad_q = [q for q in range(len(d)) if d[q] != want_d[q]]
-        assert not bad_q, (route, "d* differs at queries", bad_q[:5], [d[q] for q in bad_q[:5]], [want_d[q] for q in bad_q[:5]])
+        assert not bad_q, (route, "d* differs at queries", bad_q[:5], [d[q] for q in bad_q[:5]], [want_d[q] for q in bad_q[:5]],
+                           note(bad_q[0]) if bad_q else None)
         bad_i = [i for i in range(len(v)) if v[i] != want_v[i]]
-        assert not bad_i, (route, "verdicts differ at rows", bad_i[:10])
-        assert c == want_c, (route, c, want_c)
+        assert not bad_i, (route, "verdicts differ at rows", bad_i[:10],
+                           [note(q) for q in range(len(d)) if bad_i and self.seg[q] <= bad_i[0] < self.seg[q + 1]][:1])
+        assert c == want_c, (route, "counts differ", c, want_c)
 
 
 def _tree(n_phyla=3, n_fam=3, n_gen=3, n_sp=3):
