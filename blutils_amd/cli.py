@@ -121,7 +121,18 @@ writes the binary cache of a taxonomies file (not in the reference CLI; pass CAC
 
 = `blu build-db kraken2` / `blu build-db qiime2` (commands.rs:11-20): the sequences of `blastdbcmd -entry all` rewritten on
 the GPU as they stream from the pipe (blutils_amd/seqdb.py, csrc/seqdb_gpu.hip); the QIIME taxonomy TSV is rendered on the
-host from a `*.blutils.json` that `build-db blu` wrote."""
+host from a `*.blutils.json` that `build-db blu` wrote.
+
+    python -m blutils_amd.cli build-db sintax TAXONOMIES_DATABASE_PATH BLAST_DATABASE_PATH OUTPUT_SEQUENCES_FILE
+        [-u] [--listing-file FILE] [--blastdbcmd EXE] [--device N]
+    python -m blutils_amd.cli build-db dada2 TAXONOMIES_DATABASE_PATH BLAST_DATABASE_PATH OUTPUT_SEQUENCES_FILE
+        [-u] [--listing-file FILE] [--blastdbcmd EXE] [--device N]
+
+(not in the reference CLI) one FASTA whose headers carry the lineage, for `vsearch --sintax` (`>ACC;tax=d:...,p:...;`) and
+for DADA2's assignTaxonomy (`>Domain;Phylum;...;Genus;`): the kraken2 listing joined on the GPU, taxid by taxid, to the
+labels rendered from TAXONOMIES_DATABASE_PATH (a `*.blutils.json` or a `cache-db` cache).  A line whose taxid the
+taxonomies file does not hold, or whose lineage gives no label, is left out.  To stderr:
+`labelled export: wrote K of N lines, U with a taxid not in the taxonomies file, E without a label`."""
 from __future__ import annotations
 
 import argparse
@@ -259,7 +270,16 @@ def build_parser() -> argparse.ArgumentParser:
     qi.add_argument("blast_database_path")
     qi.add_argument("output_sequences_file")
     qi.add_argument("-u", "--use-taxid", action="store_true")
-    for sp, fmt in ((kr, seqdb.KRAKEN2_OUTFMT), (qi, seqdb.QIIME2_OUTFMT)):
+    sx = bd.add_parser("sintax", help="FASTA with SINTAX headers (>ACC;tax=d:...,p:...;) from a *.blutils.json and a BLAST "
+                                      "database (not in the reference CLI)")
+    da = bd.add_parser("dada2", help="FASTA with DADA2 assignTaxonomy headers (>Domain;Phylum;...;Genus;) from a "
+                                     "*.blutils.json and a BLAST database (not in the reference CLI)")
+    for sp in (sx, da):
+        sp.add_argument("taxonomies_database_path", help="a *.blutils.json or a cache-db cache of the same lineage flavour")
+        sp.add_argument("blast_database_path")
+        sp.add_argument("output_sequences_file", help="gets the extension fna; removed first if it exists")
+        sp.add_argument("-u", "--use-taxid", action="store_true", help="labels from numericLineage")
+    for sp, fmt in ((kr, seqdb.KRAKEN2_OUTFMT), (qi, seqdb.QIIME2_OUTFMT), (sx, seqdb.KRAKEN2_OUTFMT), (da, seqdb.KRAKEN2_OUTFMT)):
         sp.add_argument("--listing-file", help=f"the text `blastdbcmd -entry all -db DB -outfmt \"{fmt}\"` prints; "
                                                "no blastdbcmd run and no database check (not in the reference CLI)"
                                                .replace("%", "%%"))
@@ -392,6 +412,14 @@ def _build_db(args) -> int:
             seqdb.build_qiime_db_from_blutils_db(args.taxonomies_database_path, args.output_taxonomies_file,
                                                  args.blast_database_path, args.output_sequences_file, args.use_taxid,
                                                  args.listing_file, args.blastdbcmd, device=args.device)
+            return 0
+        if args.sub in ("sintax", "dada2"):
+            build = seqdb.build_sintax_db_from_blutils_db if args.sub == "sintax" else seqdb.build_dada2_db_from_blutils_db
+            st = build(args.taxonomies_database_path, args.blast_database_path, args.output_sequences_file, args.use_taxid,
+                       args.listing_file, args.blastdbcmd, device=args.device)
+            print(f"labelled export: wrote {st['n_lines'] - st['n_unknown_taxid'] - st['n_unlabelled']} of {st['n_lines']} lines, "
+                  f"{st['n_unknown_taxid']} with a taxid not in the taxonomies file, {st['n_unlabelled']} without a label",
+                  file=sys.stderr)
             return 0
         replace = taxdb.parse_replace_rank(args.replace_rank)
         taxdb.build_ref_db_from_ncbi_files(args.blast_database_path, args.taxdump_directory_path, args.output_file_path,

@@ -49,6 +49,7 @@
 #include "blu_internal.h"
 #include "ingest.h"
 #include "ingest_prims.h"
+#include "taxid_probe.h"
 
 namespace blu {
 namespace {
@@ -64,8 +65,6 @@ struct Slot {            // 32 bytes
     uint32_t len;
     unsigned char head[12];
 };
-
-struct DevTaxidMap { const TaxidMap::E* tab; uint64_t mask; };
 
 // ---- block-level sum and exclusive scan: 64-wide wavefronts reduce / scan in registers (DPP), the wave totals meet in LDS ----
 template <int CTRL>
@@ -301,19 +300,7 @@ __global__ __launch_bounds__(TILE_THREADS) void write_line_starts(const uint4* _
     }
 }
 
-// ---- 2. parse ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t taxid_lookup(const DevTaxidMap& t, long long k) {
-    unsigned long long x = (unsigned long long)k * 0x9E3779B97F4A7C15ull;
-    x ^= x >> 32;
-    uint64_t i = x & t.mask;
-    for (;;) {
-        const TaxidMap::E e = t.tab[i];
-        if (!e.used) return BLU_UNMATCHED_TAXID;
-        if (e.key == k) return e.val;
-        i = (i + 1) & t.mask;
-    }
-}
-
+// ---- 2. parse (the taxid join: taxid_probe.h) ------------------------------------------------------------------
 __device__ const double P10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
 
 struct NumState {

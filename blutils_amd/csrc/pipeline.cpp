@@ -39,6 +39,7 @@
 #include "blu_pipeline.h"
 #include "ingest.h"
 #include "ingest_prims.h"
+#include "seqdb_labels.h"
 
 using namespace blu;
 
@@ -2179,6 +2180,37 @@ int ingest_columns_selected(const char* blast_output_file, const char* taxonomie
 
 bool blu::parse_f64_field(const char* p, size_t n, double* out) { return parse_f64(std::string_view(p, n), out); }
 
+// the taxonomies file through load_db, then one label per row: the elements come back from the interned lineage (the raw rank
+// and the identifier of every element are kept as written; a lineage the loader marked `bad` has none and gets no label)
+int blu::load_label_set(const char* taxonomies_file, bool use_taxid, int format, LabelSet& out) {
+    Db db;
+    if (const int rc = load_db(taxonomies_file, use_taxid, db); rc != BLU_OK) return rc;
+    std::vector<uint32_t> kind(db.rank_raw.size());
+    std::string other;
+    for (size_t r = 0; r < kind.size(); ++r) {
+        const uint16_t k = parse_rank(db.rank_raw[r].c_str(), &other);
+        kind[r] = k >= K_DOMAIN && k <= K_SPECIES ? k : 0;
+    }
+    const size_t n = db.taxid.size();
+    out.taxid = std::move(db.taxid);
+    out.off.resize(n);
+    out.len.resize(n);
+    out.blob.clear();
+    std::vector<LabelElement> el;
+    for (size_t i = 0; i < n; ++i) {
+        el.clear();
+        for (uint64_t j = db.lin_off[i]; j < db.lin_off[i + 1]; ++j)
+            el.push_back(LabelElement{kind[db.lin_rank[j]], db.rank_raw[db.lin_rank[j]].empty(), db.node_ident[db.lin_node[j]]});
+        out.off[i] = out.blob.size();
+        if (!db.bad[i]) (void)render_label(el.data(), el.size(), format, &out.blob);
+        const size_t len = out.blob.size() - out.off[i];
+        if (len >= (1ull << 32)) { set_error("seqdb: the label of taxid %lld is 4 GiB or longer", (long long)out.taxid[i]); return BLU_ERR_INVALID_ARG; }
+        out.len[i] = (uint32_t)len;
+    }
+    out.row_of = std::move(db.row_of);
+    return BLU_OK;
+}
+
 extern "C" {
 
 int blu_build_consensus(const blu_consensus_request* request, blu_consensus_outcome* outcome) {
@@ -2309,6 +2341,25 @@ int blu_db_cache_build(const char* taxonomies_file, int use_taxid, const char* c
     int rc = load_db(taxonomies_file, use_taxid != 0, db);
     if (rc != BLU_OK) return rc;
     return write_db_cache(db, use_taxid != 0, cache_file);
+}
+
+int blu_seqdb_render_labels(const char* taxonomies_file, int use_taxid, int format, const char* out_path) {
+    if (!taxonomies_file || !out_path || (format != BLU_SEQDB_SINTAX && format != BLU_SEQDB_DADA2)) {
+        set_error("blu_seqdb_render_labels: null or invalid argument");
+        return BLU_ERR_INVALID_ARG;
+    }
+    LabelSet labels;
+    if (const int rc = load_label_set(taxonomies_file, use_taxid != 0, format, labels); rc != BLU_OK) return rc;
+    std::string text;
+    text.reserve(labels.blob.size() + 24 * labels.taxid.size());
+    for (size_t i = 0; i < labels.taxid.size(); ++i) {
+        text += std::to_string((long long)labels.taxid[i]);
+        text += '\t';
+        text.append(labels.blob, labels.off[i], labels.len[i]);
+        text += '\n';
+    }
+    if (!write_text_file(out_path, text)) { set_error("seqdb: cannot write %s", out_path); return BLU_ERR_IO; }
+    return BLU_OK;
 }
 
 int blu_custom_taxon_from_file(const char* path, blu_cutoff_config* cfg) {

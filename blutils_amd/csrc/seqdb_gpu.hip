@@ -20,6 +20,15 @@
 //             m == 80 is an inserted newline, otherwise it is sequence byte 80 q + m); prelim_map.txt: one thread per line
 // No thread walks a sequence: its end is the next separator from the position list and its bytes are copied, upper-cased
 // and wrapped by the output threads.  No device library is called; byte work bound by memory, no MFMA.
+//
+// `build-db sintax` / `build-db dada2` (blu_seqdb_export_labelled; neither is in the reference, DESIGN.md "Labelled FASTA
+// export") run the same three threads, byte scan, separator list and line index.  The labels of the taxonomy rows, their
+// (offset, length) and the taxid table (taxid_probe.h: the ingest's) go up once per call; per chunk
+//   label lines   one thread per line: the pieces and the taxid as for kraken2, the probe, the row's label, the record's length
+//                 (0 for a line that is skipped) and the skip word that counts it
+//   ascii         one thread per 16 listing bytes: a byte >= 0x80 inside a sequence piece is the line's error, whether or
+//                 not the line is written (the refusals do not depend on the taxonomies file)
+//   write         one thread per 16 output bytes as above; a header byte is a constant, a listing byte or a label-blob byte
 #include <hip/hip_runtime.h>
 #include <fcntl.h>
 #include <poll.h>
@@ -43,6 +52,8 @@
 #include "blu_internal.h"
 #include "blu_pipeline.h"
 #include "ingest_prims.h"
+#include "seqdb_labels.h"
+#include "taxid_probe.h"
 #include "text_dev.h"
 
 namespace blu {
@@ -166,7 +177,8 @@ __device__ __forceinline__ uint64_t lower_bound(const uint64_t* __restrict__ a, 
     return lo;
 }
 // last index i in [lo, hi] with a[i] <= x (a[lo] <= x holds)
-__device__ __forceinline__ uint64_t last_le(const unsigned long long* __restrict__ a, uint64_t lo, uint64_t hi, uint64_t x) {
+template <class T>
+__device__ __forceinline__ uint64_t last_le(const T* __restrict__ a, uint64_t lo, uint64_t hi, uint64_t x) {
     while (lo < hi) { const uint64_t mid = (lo + hi + 1) >> 1; if (a[mid] <= x) lo = mid; else hi = mid - 1; }
     return lo;
 }
@@ -345,6 +357,144 @@ __global__ __launch_bounds__(TPB) void seqdb_write_map(const unsigned char* __re
     *o = '\n';
 }
 
+// ---- the labelled formats ----------------------------------------------------------------------------------------------
+// the labels of the taxonomy rows as the kernels see them: row r's label is blob[off[r], off[r] + len[r]), len 0 = none
+struct DevLabels {
+    const unsigned char* blob;
+    const unsigned long long* off;
+    const uint32_t* len;
+    DevTaxidMap map;
+    int sintax;
+};
+
+constexpr unsigned long long SKIP_UNKNOWN = 1ull, SKIP_UNLABELLED = 1ull << 32;   // the two counts share one scanned word
+
+// one thread per line: pieces and taxid as seqdb_lines (kraken2), then the join.  What LineOut's fields hold here: tax_a /
+// tax_n the label's offset in the blob and its length, map_len the skip word; oid_* and num are not used
+__global__ __launch_bounds__(TPB) void seqdb_label_lines(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line, uint32_t n,
+                                                         const uint64_t* __restrict__ sep, uint64_t n_sep,
+                                                         const unsigned long long* __restrict__ first_bad, DevLabels lab, LineOut o) {
+    const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+    unsigned long long len = 0;
+    if (i < n) {
+        const uint64_t ls = line[i], le = line[i + 1] - 1;
+        len = le - ls;
+        const unsigned long long fb = *first_bad;
+        if (fb >= ls && fb < le) atomicMin(o.stop_line, i);
+        const uint64_t j = lower_bound(sep, n_sep, ls);
+        unsigned long long fna = 0, skip = 0;
+        uint64_t seq_a = 0, seq_n = 0;
+        if (j + 1 >= n_sep || sep[j + 1] >= le) {
+            atomicMin(o.err, ((unsigned long long)i << 3) | E_PIECES);
+        } else {
+            uint64_t a0 = ls, b0 = sep[j];
+            uint64_t a1 = sep[j] + 2, b1 = sep[j + 1];
+            uint64_t as = sep[j + 1] + 2;
+            uint64_t bs = (j + 2 < n_sep && sep[j + 2] < le) ? sep[j + 2] : le;
+            trim(text, a0, b0); trim(text, a1, b1); trim(text, as, bs);
+            o.acc_a[i] = a0; o.acc_n[i] = (uint32_t)(b0 - a0);
+            seq_a = as; seq_n = bs - as;
+            unsigned long long v = 0;
+            if (!parse_usize(text, a1, b1, &v)) {
+                atomicMin(o.err, ((unsigned long long)i << 3) | E_TAXID);
+            } else {
+                // the table's keys are i64 (a taxid of the taxonomies file above i64::MAX is stored as i64::MAX and a negative
+                // one as it is): a listing taxid of 2^63 or more equals none of them by value
+                const uint32_t row = v >> 63 ? BLU_UNMATCHED_TAXID : taxid_lookup(lab.map, (long long)v);
+                const uint32_t ln = row == BLU_UNMATCHED_TAXID ? 0 : lab.len[row];
+                if (row == BLU_UNMATCHED_TAXID) skip = SKIP_UNKNOWN;
+                else if (ln == 0) skip = SKIP_UNLABELLED;
+                else {
+                    o.tax_a[i] = lab.off[row]; o.tax_n[i] = ln;
+                    fna = lab.sintax ? 1 + (b0 - a0) + 5 + ln + 2 + seq_n + 1      // >ACC;tax=LABEL;\nSEQ\n
+                                     : 1 + (unsigned long long)ln + 1 + seq_n + 1;   // >LABEL\nSEQ\n
+                }
+            }
+        }
+        o.seq_a[i] = seq_a; o.seq_n[i] = seq_n;             // (no pieces: an empty sequence, for seqdb_label_ascii)
+        o.fna_len[i] = fna;
+        o.map_len[i] = skip;
+    }
+    for (int d = 32; d > 0; d >>= 1) len = max(len, (unsigned long long)__shfl_down(len, d));
+    if ((threadIdx.x & 63) == 0 && len) atomicMax(o.max_line, len);
+}
+
+// one thread per 16 listing bytes: a byte >= 0x80 that lies in its line's sequence piece.  All but a few threads leave after
+// one load and one test; the others find their line once by binary search over the line starts
+__global__ __launch_bounds__(TPB) void seqdb_label_ascii(const unsigned char* __restrict__ text, uint64_t size, const uint64_t* __restrict__ line,
+                                                         uint32_t n, const uint64_t* __restrict__ seq_a, const uint64_t* __restrict__ seq_n,
+                                                         unsigned long long* __restrict__ err) {
+    const uint64_t base = ((uint64_t)blockIdx.x * TPB + threadIdx.x) * 16;
+    if (base >= size || n == 0) return;
+    const uint4 v = *reinterpret_cast<const uint4*>(text + base);
+    if (((v.x | v.y | v.z | v.w) & 0x80808080u) == 0) return;
+    uint64_t i = last_le(line, 0, n - 1, base);
+    for (int k = 0; k < 16; ++k) {
+        const uint64_t p = base + k;
+        if (p >= size) break;
+        if (byte_at(v, k) < 0x80) continue;
+        while (p >= line[i + 1]) ++i;                           // (p < size <= line[n])
+        if (p >= seq_a[i] && p - seq_a[i] < seq_n[i]) { atomicMin(err, ((unsigned long long)i << 3) | E_NONASCII); break; }
+    }
+}
+
+constexpr unsigned long long SX_TAX = 0x0000003d7861743bull;   // ";tax=" as a little-endian word
+
+// one thread per 16 output bytes of the labelled .fna, as seqdb_write_fna: L.tax_a / L.tax_n are the label's place in blob
+__global__ __launch_bounds__(TPB) void seqdb_write_labelled(const unsigned char* __restrict__ text, const unsigned char* __restrict__ blob,
+                                                            uint32_t n, LineIn L, int sintax, unsigned char* __restrict__ out) {
+    __shared__ uint64_t range[2];
+    const unsigned long long total = L.off[n];
+    const uint64_t ob = (uint64_t)blockIdx.x * TILE;
+    if (threadIdx.x < 2) {
+        const uint64_t x = threadIdx.x == 0 ? ob : min(ob + TILE, (uint64_t)total) - 1;
+        range[threadIdx.x] = last_le(L.off, 0, n - 1, x);
+    }
+    __syncthreads();
+    const uint64_t o0 = ob + (uint64_t)threadIdx.x * 16;
+    if (o0 >= total) { *reinterpret_cast<uint4*>(out + o0) = make_uint4(0, 0, 0, 0); return; }
+    uint64_t i = last_le(L.off, range[0], range[1], o0);       // the last line that starts at or before o0: it is not empty
+    uint64_t start = L.off[i], next = L.off[i + 1];
+    uint64_t acc_a = L.acc_a[i], lab_a = L.tax_a[i], seq_a = L.seq_a[i];
+    uint32_t acc_n = sintax ? L.acc_n[i] : 0, lab_n = L.tax_n[i];
+    uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const uint64_t o = o0 + k;
+        uint32_t c = 0;
+        if (o < total) {
+            if (o >= next) {                                     // the next record that has bytes (skipped lines have none)
+                do { ++i; start = next; next = L.off[i + 1]; } while (o >= next);
+                acc_a = L.acc_a[i]; lab_a = L.tax_a[i]; seq_a = L.seq_a[i];
+                acc_n = sintax ? L.acc_n[i] : 0; lab_n = L.tax_n[i];
+            }
+            uint64_t r = o - start;
+            const uint64_t last = next - start - 1;              // the record's final newline
+            if (r == 0) c = '>';
+            else if (r == last) c = '\n';
+            else {
+                r -= 1;
+                bool done = false;
+                if (sintax) {                                    // ACC;tax=
+                    if (r < acc_n) { c = text[acc_a + r]; done = true; }
+                    else if ((r -= acc_n) < 5) { c = (uint32_t)((SX_TAX >> (8 * r)) & 0xFF); done = true; }
+                    else r -= 5;
+                }
+                if (!done) {
+                    if (r < lab_n) c = blob[lab_a + r];
+                    else if ((r -= lab_n) < (sintax ? 2u : 1u)) c = (sintax && r == 0) ? ';' : '\n';
+                    else {
+                        c = text[seq_a + (r - (sintax ? 2 : 1))];
+                        c = (c >= 'a' && c <= 'z') ? c - 32 : c;
+                    }
+                }
+            }
+        }
+        w[k >> 2] |= c << (8 * (k & 3));
+    }
+    *reinterpret_cast<uint4*>(out + o0) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 }  // namespace
 
 namespace {
@@ -419,6 +569,13 @@ struct Export {
     double t_read = 0, t_write = 0;
     HipPolicy pol{"seqdb", BLU_ERR_ALLOC};  // (the device stage's: the calling thread's)
 
+    // the labelled formats: the host's labels (null for kraken2 / qiime2), their device copies, the skipped lines so far
+    const LabelSet* labels = nullptr;
+    DevBuf d_blob, d_lab_off, d_lab_len, d_lab_tab;
+    DevLabels lab{};
+    uint64_t n_unknown = 0, n_unlabelled = 0;
+    double t_label_upload = 0;
+
     // device buffers (one set: the device stage is the calling thread's, chunk after chunk)
     DevBuf d_text, d_tile, d_tbase, d_stile, d_sbase, d_scan, d_line, d_sep, d_cnt, d_acc_a, d_acc_n, d_tax_a, d_tax_n, d_oid_a,
         d_oid_n, d_seq_a, d_seq_n, d_num, d_fna_len, d_fna_off, d_map_len, d_map_off, d_fna, d_map;
@@ -483,9 +640,30 @@ struct Export {
         }
     }
 
+    // ---- the labels, once per call
+    int upload_labels() {
+        const double t0 = now_s();
+        const LabelSet& H = *labels;
+        unsigned char* blob; unsigned long long* off; uint32_t* len; TaxidMap::E* tab;
+        HIP_CHECK(pol, d_blob.get(&blob, H.blob.size() + PAD, "labels", pol));
+        HIP_CHECK(pol, d_lab_off.get(&off, H.off.size() * 8 + PAD, "labels", pol));
+        HIP_CHECK(pol, d_lab_len.get(&len, H.len.size() * 4 + PAD, "labels", pol));
+        HIP_CHECK(pol, d_lab_tab.get(&tab, H.row_of.tab.size() * sizeof(TaxidMap::E), "taxid map", pol));
+        if (!H.blob.empty()) HIP_CHECK(pol, hipMemcpy(blob, H.blob.data(), H.blob.size(), hipMemcpyHostToDevice));
+        if (!H.off.empty()) {
+            HIP_CHECK(pol, hipMemcpy(off, H.off.data(), H.off.size() * 8, hipMemcpyHostToDevice));
+            HIP_CHECK(pol, hipMemcpy(len, H.len.data(), H.len.size() * 4, hipMemcpyHostToDevice));
+        }
+        HIP_CHECK(pol, hipMemcpy(tab, H.row_of.tab.data(), H.row_of.tab.size() * sizeof(TaxidMap::E), hipMemcpyHostToDevice));
+        lab = DevLabels{blob, off, len, DevTaxidMap{tab, H.row_of.tab.size() - 1}, D.format == BLU_SEQDB_SINTAX};
+        t_label_upload = 1e3 * (now_s() - t0);
+        return BLU_OK;
+    }
+
     // ---- one chunk on the device into O; *done: a stop or an error ended the listing in this chunk (set once O is filled)
     int chunk_on_device(const InSlot& I, OutSlot& O, uint64_t line_base, bool* done) {
         const int qiime = D.format == BLU_SEQDB_QIIME2;
+        const bool kraken = D.format == BLU_SEQDB_KRAKEN2;
         const uint64_t size = I.len;
         S.n_chunks += 1;
         if (size >= (1ull << 32) - TILE) { set_error("seqdb: %s: a line of 4 GiB or more near line %llu is not supported", input.c_str(),
@@ -536,23 +714,34 @@ struct Export {
         lo.err = cnt + 1; lo.max_line = cnt + 2; lo.stop_line = (uint32_t*)(cnt + 3);
         HIP_CHECK(pol, hipMemset(lo.fna_len + n, 0, 8));
         HIP_CHECK(pol, hipMemset(lo.map_len, 0, (n + 1) * 8));
-        hipLaunchKernelGGL(seqdb_lines, dim3(grid(n)), dim3(TPB), 0, 0, text, line, (uint32_t)n, sep, n_sep, qiime, cnt, lo);
+        if (labels) {
+            hipLaunchKernelGGL(seqdb_label_lines, dim3(grid(n)), dim3(TPB), 0, 0, text, line, (uint32_t)n, sep, n_sep, cnt, lab, lo);
+            HIP_CHECK(pol, hipGetLastError());
+            hipLaunchKernelGGL(seqdb_label_ascii, dim3(grid(n_tiles, 1)), dim3(TPB), 0, 0, text, size, line, (uint32_t)n, lo.seq_a, lo.seq_n,
+                               lo.err);
+        } else {
+            hipLaunchKernelGGL(seqdb_lines, dim3(grid(n)), dim3(TPB), 0, 0, text, line, (uint32_t)n, sep, n_sep, qiime, cnt, lo);
+        }
         HIP_CHECK(pol, hipGetLastError());
         HIP_CHECK(pol, d_scan.get(&tmp, std::max(scan_tmp_bytes_u32(n_tiles + 1), scan_tmp_bytes_u64(n + 1)), "scan", pol));
         HIP_CHECK(pol, exclusive_scan_u64(lo.fna_len, fna_off, n + 1, tmp));
-        if (!qiime) HIP_CHECK(pol, exclusive_scan_u64(lo.map_len, map_off, n + 1, tmp));
+        if (!qiime) HIP_CHECK(pol, exclusive_scan_u64(lo.map_len, map_off, n + 1, tmp));   // (labelled: the skip words)
         unsigned long long fna_total = 0, map_total = 0;
         HIP_CHECK(pol, hipMemcpy(&fna_total, fna_off + n, 8, hipMemcpyDeviceToHost));
-        if (!qiime) HIP_CHECK(pol, hipMemcpy(&map_total, map_off + n, 8, hipMemcpyDeviceToHost));
+        if (kraken) HIP_CHECK(pol, hipMemcpy(&map_total, map_off + n, 8, hipMemcpyDeviceToHost));
         const uint64_t fna_tiles = (fna_total + TILE - 1) / TILE;
         unsigned char *fna, *map = nullptr;
         HIP_CHECK(pol, d_fna.get(&fna, fna_tiles * TILE + PAD, "output", pol));
-        if (fna_total) {
+        if (fna_total) {                                  // (labelled: a chunk whose lines are all skipped writes nothing)
             const LineIn li{fna_off, lo.acc_a, lo.acc_n, lo.tax_a, lo.tax_n, lo.oid_a, lo.oid_n, lo.seq_a, lo.seq_n};
-            hipLaunchKernelGGL(seqdb_write_fna, dim3((unsigned)fna_tiles), dim3(TPB), 0, 0, text, (uint32_t)n, li, qiime, lo.err, fna);
+            if (labels)
+                hipLaunchKernelGGL(seqdb_write_labelled, dim3((unsigned)fna_tiles), dim3(TPB), 0, 0, text, lab.blob, (uint32_t)n, li,
+                                   lab.sintax, fna);
+            else
+                hipLaunchKernelGGL(seqdb_write_fna, dim3((unsigned)fna_tiles), dim3(TPB), 0, 0, text, (uint32_t)n, li, qiime, lo.err, fna);
             HIP_CHECK(pol, hipGetLastError());
         }
-        if (!qiime) {
+        if (kraken) {
             HIP_CHECK(pol, d_map.get(&map, map_total + PAD, "output", pol));
             hipLaunchKernelGGL(seqdb_write_map, dim3(grid(n)), dim3(TPB), 0, 0, text, (uint32_t)n, map_off, lo.map_len, lo.acc_a, lo.acc_n,
                                lo.num, map);
@@ -567,8 +756,14 @@ struct Export {
         uint64_t keep_in = size;
         if (keep < n) {
             HIP_CHECK(pol, hipMemcpy(&keep_off[0], fna_off + keep, 8, hipMemcpyDeviceToHost));
-            if (!qiime) HIP_CHECK(pol, hipMemcpy(&keep_off[1], map_off + keep, 8, hipMemcpyDeviceToHost));
+            if (kraken) HIP_CHECK(pol, hipMemcpy(&keep_off[1], map_off + keep, 8, hipMemcpyDeviceToHost));
             HIP_CHECK(pol, hipMemcpy(&keep_in, line + keep, 8, hipMemcpyDeviceToHost));
+        }
+        if (labels) {                                      // the skipped lines among those kept
+            unsigned long long skipped = 0;
+            HIP_CHECK(pol, hipMemcpy(&skipped, map_off + keep, 8, hipMemcpyDeviceToHost));
+            n_unknown += skipped & 0xFFFFFFFFull;
+            n_unlabelled += skipped >> 32;
         }
         if (!O.fna.grow(keep_off[0] + 1, 0) || !O.map.grow(keep_off[1] + 1, 0)) {
             set_error("seqdb: pinned host allocation of %llu bytes failed", keep_off[0] + keep_off[1]);
@@ -602,6 +797,7 @@ struct Export {
         if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) { (void)hipGetLastError(); set_error("seqdb: no HIP device"); return BLU_ERR_NO_DEVICE; }
         if (D.device < 0 || D.device >= n_dev) { set_error("seqdb: device %d does not exist (%d devices)", D.device, n_dev); return BLU_ERR_INVALID_ARG; }
         HIP_CHECK(pol, hipSetDevice(D.device));
+        if (labels) { if (const int rc = upload_labels(); rc != BLU_OK) return rc; }
         chunk = D.chunk_bytes ? (size_t)D.chunk_bytes : (size_t)BLU_SEQDB_DEFAULT_CHUNK;
         chunk = std::max<size_t>(chunk, 4096);
         input = D.input_path ? D.input_path : ("fd " + std::to_string(D.input_fd));
@@ -680,5 +876,41 @@ extern "C" int blu_seqdb_export(const blu_seqdb_desc* desc, blu_seqdb_stats* sta
     blu::Export e(*desc, S);
     const int rc = e.run();
     S.t_wall_ms = 1e3 * (blu::now_s() - t0);
+    return rc;
+}
+
+extern "C" int blu_seqdb_export_labelled(const blu_seqdb_label_desc* desc, blu_seqdb_label_stats* stats) {
+    if (!desc || !desc->fna_path || !desc->taxonomies_file || (desc->input_fd < 0 && !desc->input_path) ||
+        (desc->format != BLU_SEQDB_SINTAX && desc->format != BLU_SEQDB_DADA2)) {
+        blu::set_error("blu_seqdb_export_labelled: null or invalid argument");
+        return BLU_ERR_INVALID_ARG;
+    }
+    blu_seqdb_label_stats local;
+    blu_seqdb_label_stats& T = stats ? *stats : local;
+    memset(&T, 0, sizeof T);
+    const double t0 = blu::now_s();
+    blu::LabelSet labels;
+    if (const int rc = blu::load_label_set(desc->taxonomies_file, desc->use_taxid != 0, desc->format, labels); rc != BLU_OK) return rc;
+    T.n_rows = labels.taxid.size();
+    T.label_bytes = labels.blob.size();
+    T.t_labels_ms = 1e3 * (blu::now_s() - t0);
+    blu_seqdb_desc d{};
+    d.format = desc->format;
+    d.input_fd = desc->input_fd;
+    d.input_path = desc->input_path;
+    d.fna_path = desc->fna_path;
+    d.chunk_bytes = desc->chunk_bytes;
+    d.device = desc->device;
+    blu_seqdb_stats S;
+    memset(&S, 0, sizeof S);
+    blu::Export e(d, S);
+    e.labels = &labels;
+    const int rc = e.run();
+    T.n_lines = S.n_lines; T.input_bytes = S.input_bytes; T.fna_bytes = S.fna_bytes; T.n_chunks = S.n_chunks;
+    T.max_line_bytes = S.max_line_bytes; T.invalid_utf8_line = S.invalid_utf8_line;
+    T.n_unknown_taxid = e.n_unknown; T.n_unlabelled = e.n_unlabelled;
+    T.t_read_ms = S.t_read_ms; T.t_gpu_ms = S.t_gpu_ms; T.t_write_ms = S.t_write_ms;
+    T.t_labels_ms += e.t_label_upload;
+    T.t_wall_ms = 1e3 * (blu::now_s() - t0);
     return rc;
 }

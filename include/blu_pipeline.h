@@ -388,6 +388,49 @@ int blu_seqdb_export(const blu_seqdb_desc* desc, blu_seqdb_stats* stats);
  * reject is BLU_ERR_PARSE and out_path is then left absent; a binary cache (blu_db_cache_build) is refused. */
 int blu_qiime_taxonomy_tsv(const char* json_path, int use_taxid, const char* out_path);
 
+/* `build-db sintax` and `build-db dada2` (neither is in the reference): the kraken2 listing (`"%a  %T  %s"`) rewritten as one
+ * FASTA whose header carries the lineage of the line's taxid.  The labels are rendered on the host once per call from the
+ * taxonomies file (a `*.blutils.json` or a cache of the same lineage flavour, read by the loader of the consensus use-case)
+ * and joined to the lines on the device, by the taxid's value.
+ *   sintax: `>ACC;tax=d:bacteria,p:firmicutes,...,s:bacillus-subtilis;\nSEQUENCE\n`
+ *   dada2:  `>bacteria;firmicutes;...;bacillus;\nSEQUENCE\n` (domain or kingdom, then phylum to genus, cut at the first gap)
+ * The sequence is upper-cased and left on one line.  A line whose taxid has no row in the taxonomies file, or whose row has
+ * no label, gives no record and is counted; the refusals and the quiet stop are those of kraken2, and they are decided
+ * before the join.  DESIGN.md "Labelled FASTA export" has the label rules. */
+#define BLU_SEQDB_SINTAX 2
+#define BLU_SEQDB_DADA2 3
+typedef struct blu_seqdb_label_desc {
+    int32_t format;                /* BLU_SEQDB_SINTAX | BLU_SEQDB_DADA2 */
+    int32_t input_fd;              /* >= 0: read this descriptor (not closed); -1: open input_path */
+    const char* input_path;        /* the listing, or a label for input_fd in messages (may be NULL then) */
+    const char* taxonomies_file;   /* *.blutils.json or its binary cache */
+    int32_t use_taxid;             /* labels from numericLineage instead of textLineage */
+    int32_t device;                /* HIP device ordinal */
+    const char* fna_path;          /* created or truncated */
+    uint64_t chunk_bytes;          /* as in blu_seqdb_desc */
+} blu_seqdb_label_desc;
+
+typedef struct blu_seqdb_label_stats {
+    uint64_t n_lines;              /* listing lines read through (written or skipped), up to the stop or error line */
+    uint64_t input_bytes;          /* their bytes */
+    uint64_t fna_bytes;
+    uint64_t n_chunks;
+    uint64_t max_line_bytes;
+    uint64_t invalid_utf8_line;    /* 1-based line of a quiet stop, 0 = none */
+    uint64_t n_unknown_taxid;      /* of n_lines: skipped, the taxid has no row in the taxonomies file */
+    uint64_t n_unlabelled;         /* of n_lines: skipped, the row's label is empty */
+    uint64_t n_rows;               /* rows of the taxonomies file */
+    uint64_t label_bytes;          /* bytes of all labels */
+    double t_read_ms, t_gpu_ms, t_write_ms, t_wall_ms;   /* as in blu_seqdb_stats; wall includes t_labels_ms */
+    double t_labels_ms;            /* loading the taxonomies file, rendering the labels, uploading them */
+} blu_seqdb_label_stats;
+
+int blu_seqdb_export_labelled(const blu_seqdb_label_desc* desc, blu_seqdb_label_stats* stats);
+
+/* The labels alone, on the host (no device is needed): `TAXID\tLABEL\n` per row of the taxonomies file in file order, rows
+ * with an empty label included, to out_path. */
+int blu_seqdb_render_labels(const char* taxonomies_file, int use_taxid, int format, const char* out_path);
+
 /* CustomTaxon::from_file (domain/dtos/taxon.rs:28-66): .yaml or .json with the eight cutoff fields. */
 int blu_custom_taxon_from_file(const char* path, blu_cutoff_config* cfg);
 
