@@ -9,23 +9,21 @@
 // segment), tests and stores.  In place only the lanes whose value changes store; out of place every row of a segment is
 // written.  The test is 64-bit integer arithmetic throughout: t - D and b * 100000 do not fit 32 bits.
 //
-// Counts: a ballot / popcount per sweep, summed in a register over the wave's queries; lane 0 of each wave then adds them to one
-// of BAND_SPREAD 64-bit words chosen by the block (the hit filter's scheme) and the host sums the words.  No
-// LDS, no scratch, no second kernel.
+// Counts: a ballot / popcount per sweep, summed in a register over the wave's queries; lane 0 of each wave then adds them to the
+// spread counters of hit_pass.h.  No LDS, no scratch, no second kernel.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
 
-#include "blu_internal.h"
-#include "ingest_prims.h"
+#include "hit_pass.h"
 
 namespace blu {
 namespace {
 
 constexpr uint32_t BAND_BLOCK = 256;                 // threads per block: four waves
 constexpr uint32_t BAND_QPW = BLU_BAND_QUERIES_PER_WAVE;
-constexpr uint32_t BAND_SPREAD = 64;                 // counter words per count
+constexpr uint32_t CNT_RAISED = 0, CNT_WIDENED = 1, CNT_WORDS = 2 * HIT_SPREAD;   // spread counters: raised rows, widened queries
 constexpr long long MILLI_ONE = 100000ll;            // 100 % in milli-percent
 
 struct BandDev {
@@ -36,13 +34,8 @@ struct BandDev {
     uint32_t mask;                     // BLU_BAND_* bits
     long long keep_milli;              // 100000 - top_percent_milli
     long long top_bits;
-    unsigned long long* counts;        // [0 .. BAND_SPREAD) raised rows, [BAND_SPREAD .. 2 BAND_SPREAD) widened queries
+    unsigned long long* counts;        // [CNT_WORDS]
 };
-
-__device__ __forceinline__ int32_t wave_max32(int32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // b < t lies in the band under t: every criterion of the mask holds (an empty mask: none does)
 __device__ __forceinline__ bool in_band(const BandDev& d, int32_t b, int32_t t) {
@@ -61,9 +54,8 @@ __global__ __launch_bounds__(BAND_BLOCK) void score_band_kernel(BandDev d) {
     for (uint32_t k = 0; k < BAND_QPW; ++k) {
         const uint64_t q = wave * BAND_QPW + k;
         if (q >= d.n_queries) break;                 // (wave-uniform)
-        uint64_t s0 = d.seg_off[q], s1 = d.seg_off[q + 1];
-        if (s1 > d.n_hits) s1 = d.n_hits;            // (offsets that run past the column read and write nothing outside it)
-        if (s0 > s1) s0 = s1;                        // (a decreasing pair: an empty segment)
+        uint64_t s0, s1;
+        segment_of(d.seg_off, q, d.n_hits, &s0, &s1);
         if (s0 == s1) continue;
         unsigned long long raised = 0;
         if (s1 - s0 <= 64u) {
@@ -90,10 +82,7 @@ __global__ __launch_bounds__(BAND_BLOCK) void score_band_kernel(BandDev d) {
         n_raised += raised;
         n_widened += raised ? 1ull : 0ull;
     }
-    if (lane == 0 && n_raised) {
-        atomicAdd(&d.counts[blockIdx.x % BAND_SPREAD], n_raised);
-        atomicAdd(&d.counts[BAND_SPREAD + blockIdx.x % BAND_SPREAD], n_widened);
-    }
+    if (lane == 0) { spread_add(d.counts, CNT_RAISED, n_raised); spread_add(d.counts, CNT_WIDENED, n_widened); }
 }
 
 }  // namespace
@@ -119,7 +108,7 @@ int score_band_device(const int32_t* d_in, const uint64_t* d_seg_off, uint64_t n
     const uint64_t blocks = (waves + BAND_BLOCK / 64 - 1) / (BAND_BLOCK / 64);
     if (blocks > 0x7FFFFFFFull) { set_error("score band: too many queries for one launch"); return BLU_ERR_INVALID_ARG; }
     unsigned long long* d_counts = nullptr;
-    unsigned long long counts[2 * BAND_SPREAD];
+    unsigned long long counts[CNT_WORDS];
     HIP_CHECK(pol, mem.alloc(&d_counts, sizeof counts, "counts"));
     HIP_CHECK(pol, hipMemsetAsync(d_counts, 0, sizeof counts, stream));
     BandDev d{};
@@ -132,7 +121,7 @@ int score_band_device(const int32_t* d_in, const uint64_t* d_seg_off, uint64_t n
     HIP_CHECK(pol, hipGetLastError());
     HIP_CHECK(pol, hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(pol, hipStreamSynchronize(stream));    // (`out` and the counts are complete)
-    for (uint32_t k = 0; k < BAND_SPREAD; ++k) { *n_raised += counts[k]; *n_widened += counts[BAND_SPREAD + k]; }
+    *n_raised = spread_sum(counts, CNT_RAISED); *n_widened = spread_sum(counts, CNT_WIDENED);
     return BLU_OK;
 }
 
@@ -147,14 +136,14 @@ int blu_hits_score_band(int device, const int32_t* bitscore, const uint64_t* seg
     if (stats) *stats = blu_score_band_stats{n_hits, 0, n_queries, 0};
     int rc = check_score_band(band);
     if (rc != BLU_OK) return rc;
-    if ((n_hits && (!bitscore || !out)) || (n_queries && !seg_off)) { set_error("blu_hits_score_band: null array with a non-zero count"); return BLU_ERR_INVALID_ARG; }
+    if ((n_hits && (!bitscore || !out)) || (n_queries && !seg_off)) return refuse_null_array("blu_hits_score_band");
     const bool active = band && band->mask != 0;
     if (!active && !on_device) {                     // no band: the column as it is (no device needed)
         if (out != bitscore && n_hits) memmove(out, bitscore, n_hits * 4);
         return BLU_OK;
     }
     if (n_hits == 0) return BLU_OK;
-    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); set_error("blu_hits_score_band: hipSetDevice(%d) failed", device); return BLU_ERR_NO_DEVICE; }
+    if ((rc = use_device("blu_hits_score_band", device)) != BLU_OK) return rc;
     HipPolicy pol{"blu_hits_score_band", BLU_ERR_ALLOC};
     uint64_t n_raised = 0, n_widened = 0;
     if (on_device) {
@@ -174,12 +163,10 @@ int blu_hits_score_band(int device, const int32_t* bitscore, const uint64_t* seg
         DeviceArena mem(pol);
         int32_t* d_bs = nullptr;
         uint64_t* d_seg = nullptr;
-        HIP_CHECK(pol, mem.alloc(&d_bs, n_hits * 4, "bit-scores"));
-        HIP_CHECK(pol, mem.alloc(&d_seg, (n_queries + 1) * 8, "offsets"));
-        HIP_CHECK(pol, hipMemcpy(d_bs, bitscore, n_hits * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(pol, hipMemcpy(d_seg, seg_off, (n_queries + 1) * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(pol, mem.upload(&d_bs, bitscore, n_hits, "bit-scores"));
+        HIP_CHECK(pol, mem.upload(&d_seg, seg_off, n_queries + 1, "offsets"));
         rc = score_band_device(d_bs, d_seg, n_hits, n_queries, *band, nullptr, d_bs, &n_raised, &n_widened);
-        if (rc == BLU_OK) HIP_CHECK(pol, hipMemcpy(out, d_bs, n_hits * 4, hipMemcpyDeviceToHost));
+        if (rc == BLU_OK) HIP_CHECK(pol, mem.download(out, d_bs, n_hits));
     }
     if (rc != BLU_OK) return rc;
     if (stats) { stats->n_raised = n_raised; stats->n_widened = n_widened; }

@@ -155,33 +155,38 @@ int check_score_band(const blu_score_band* band);
 int score_band_device(const int32_t* d_in, const uint64_t* d_seg_off, uint64_t n_hits, uint64_t n_queries, const blu_score_band& band,
                       hipStream_t stream, int32_t* d_out, uint64_t* n_raised, uint64_t* n_widened);
 
+// hit_pass.hip: what the passes below share (hit_pass.h has the rest: device inlines, the long-query list, the staging).
+// The five columns of a table and its offsets; a column is named by the address of its pointer, which a rotation replaces.
+struct HitColumns { int32_t** bitscore; int32_t** align_len; uint32_t** tax_desc_row; uint32_t** acc_rank; double** pident; unsigned long long* seg_off; };
+// the columns the GPU ingest left on the device (ingest.h)
+struct DeviceHits;
+HitColumns columns_of(DeviceHits& dev);
+// BLU_ERR_INVALID_ARG ("<what>: n_hits must be below 2^32", or n_queries) for a count of 2^32 or more
+int check_hit_counts(const char* what, uint64_t n_hits, uint64_t n_queries);
+// hipSetDevice; BLU_ERR_NO_DEVICE and "<who>: hipSetDevice(<device>) failed" when it fails (HIP's last error is cleared)
+int use_device(const char* who, int device);
+// The compaction for any pass that gives verdicts in this form: d_keep[n_hits + 1] = 1 / 0 per row and a last word 0 -> the scan of
+// the keep words, the five gathers, seg_off rewritten, the unmatched rows (tax_desc_row == the marker; n_unmatched may be null)
+// recounted.  rotate: each column is its own hipMalloc allocation and may be replaced -- the compacted column takes the spare buffer,
+// the column's old buffer becomes the next spare and the last one is pushed to *retired (null: freed); else the kept rows are copied
+// back to the front of the same buffers.  all_kept (or n_hits == 0): nothing moves and d_keep is not read, only *n_unmatched is
+// counted.  `who` names the pass in messages.  Null stream of the current device; returns when its outputs are complete.
+int compact_kept_device(const char* who, HitColumns& c, uint64_t n_hits, uint64_t n_queries, const uint32_t* d_keep, bool all_kept, bool rotate,
+                        uint32_t unmatched_marker, uint64_t* n_hits_out, uint64_t* n_unmatched, std::vector<void*>* retired);
+
 // subject_kernel.hip: the best hit per subject on device columns (device pointers; blu_hits_subject_keep / blu_hits_subject_best stage
 // host ones).  Everything runs on the null stream of the current device and the calls return when their outputs are complete.
 #define BLU_SUBJECT_QUERIES_PER_WAVE 4u   // consecutive queries of one wave in the short kernel; four waves a block
 // BLU_ERR_INVALID_ARG (and the message) for unknown mask bits; a null selection is fine
 int check_subject_best(const blu_subject_best* sel);
-// BLU_ERR_INVALID_ARG for n_hits >= 2^32 or n_queries >= 2^32
-int check_subject_counts(uint64_t n_hits, uint64_t n_queries);
 // the verdicts: d_keep[n_hits] = 1 / 0
 int subject_keep_device(const int32_t* d_bitscore, const uint32_t* d_acc_rank, const uint64_t* d_seg_off, uint64_t n_hits, uint64_t n_queries,
                         uint32_t* d_keep, uint64_t* n_kept, uint64_t* n_thinned);
-// the verdicts and the compaction of the five columns and seg_off.  rotate: each column is its own hipMalloc allocation and may be
-// replaced -- the compacted column takes the spare buffer, the column's old buffer becomes the next spare and the last one is
-// pushed to *retired (null: freed); else the kept rows are copied back to the front of the same buffers.  count_only: no pass,
-// only *n_unmatched (rows whose tax_desc_row is the marker; may be null) is counted.
-struct SubjectColumns { int32_t** bitscore; int32_t** align_len; uint32_t** tax_desc_row; uint32_t** acc_rank; double** pident; unsigned long long* seg_off; };
-int subject_best_device(SubjectColumns& c, uint64_t n_hits, uint64_t n_queries, bool rotate, uint32_t unmatched_marker,
+// the verdicts and the compaction (compact_kept_device, above).  count_only: no pass, only *n_unmatched is counted
+int subject_best_device(HitColumns& c, uint64_t n_hits, uint64_t n_queries, bool rotate, uint32_t unmatched_marker,
                         uint64_t* n_hits_out, uint64_t* n_unmatched, uint64_t* n_thinned, std::vector<void*>* retired, bool count_only);
-
-// the compaction half of the above, for any pass that gives verdicts in that form (cover_kernel.hip too): d_keep[n_hits + 1] = 1 / 0
-// per row and a last word 0 -> the scan of the keep words, the five gathers, seg_off rewritten, the unmatched rows recounted.
-// all_kept (or n_hits == 0): nothing moves and d_keep is not read, only *n_unmatched is counted.  `who` names the pass in messages.
-int compact_kept_device(const char* who, SubjectColumns& c, uint64_t n_hits, uint64_t n_queries, const uint32_t* d_keep, bool all_kept, bool rotate,
-                        uint32_t unmatched_marker, uint64_t* n_hits_out, uint64_t* n_unmatched, std::vector<void*>* retired);
-
-// the same on the columns the GPU ingest left on the device (ingest.h: DeviceHits): compacted by rotation, the retired buffer goes
-// to its trash, n_hits shrinks and seg_off is rewritten in place; *unmatched: the kept rows with no taxonomy row
-struct DeviceHits;
+// the same on the columns the GPU ingest left on the device: compacted by rotation, the retired buffer goes to its trash, n_hits
+// shrinks and seg_off is rewritten in place; *unmatched: the kept rows with no taxonomy row
 int subject_best_hits(DeviceHits& dev, blu_subject_best_stats* stats, uint64_t* unmatched);
 
 // cover_kernel.hip: the minimum cover on device columns (device pointers; blu_hits_cover_keep / blu_hits_cover_apply stage host
@@ -190,15 +195,13 @@ int subject_best_hits(DeviceHits& dev, blu_subject_best_stats* stats, uint64_t* 
 #define BLU_COVER_QUERIES_PER_WAVE 4u     // consecutive queries of one wave in the short kernel; four waves a block
 // BLU_ERR_INVALID_ARG (and a message that says "min cover") for a value outside 50001 .. 100000
 int check_min_cover(int64_t min_cover_milli);
-// BLU_ERR_INVALID_ARG for n_hits >= 2^32 or n_queries >= 2^32
-int check_cover_counts(uint64_t n_hits, uint64_t n_queries);
 // the verdicts: d_keep[n_hits] = 1 / 0, d_depth[n_queries] (may be null) = d*, BLU_NONE_U8 for a query left alone.  d_tax_row holds
 // engine row ids, or desc rows when d_row_map[n_tax] is given
 int cover_keep_device(const blu_taxonomy* tax, const int32_t* d_bitscore, const uint32_t* d_tax_row, const uint32_t* d_row_map,
                       const uint64_t* d_seg_off, uint64_t n_hits, uint64_t n_queries, uint32_t min_cover_milli, uint32_t* d_keep,
                       uint8_t* d_depth, blu_min_cover_stats* stats);
-// the verdicts and the compaction (compact_kept_device, above)
-int cover_apply_device(const blu_taxonomy* tax, SubjectColumns& c, const uint32_t* d_row_map, uint64_t n_hits, uint64_t n_queries,
+// the verdicts and the compaction
+int cover_apply_device(const blu_taxonomy* tax, HitColumns& c, const uint32_t* d_row_map, uint64_t n_hits, uint64_t n_queries,
                        uint32_t min_cover_milli, bool rotate, uint32_t unmatched_marker, uint64_t* n_hits_out, uint64_t* n_unmatched,
                        blu_min_cover_stats* stats, std::vector<void*>* retired);
 // the same on the columns the GPU ingest left on the device, which hold desc rows: fwd[n_tax] (host; blu_taxonomy_row_map's forward

@@ -14,32 +14,29 @@
 // scalar, and so is the trip count), share is one range minimum per lane and d* a bisection over d with a ballot and a popcount
 // per step (count(d) falls as d grows).  No LDS.
 //
-// Long segments (> 64 rows): the short kernel flags them; a u32 scan (ingest_prims.h) turns the flags into the list of long
+// Long segments (> 64 rows): the short kernel flags them; long_query_list (hit_pass.h) turns the flags into the list of long
 // queries and a block takes one query of the list.  Sweeps of the segment, 256 rows at a time: the maximum; the size of T and
 // the rows that leave the query alone; four digit histograms in LDS that select the position of m among the 25 position bits
 // (7 + 6 + 6 + 6); a 65-bin histogram of share and its suffix sum for d*; the keep words.  Integer LDS atomics only: sums,
 // maxima and ors of integers, so the outcome does not depend on scheduling.
 //
-// Counts: summed per wave (short) or per block (long), then added to one of COVER_SPREAD 64-bit words chosen by the block
-// (DESIGN.md §14.3); the host sums the words.
+// Counts: summed per wave (short) or per block (long), then added to the spread counters of hit_pass.h, whose segments,
+// compaction and staging of host columns this pass uses too.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
-#include "blu_internal.h"
+#include "hit_pass.h"
 #include "ingest.h"
-#include "ingest_prims.h"
 
 namespace blu {
 namespace {
 
 constexpr uint32_t COVER_BLOCK = 256;                // threads per block: four waves
 constexpr uint32_t COVER_QPW = BLU_COVER_QUERIES_PER_WAVE;
-constexpr uint32_t COVER_SPREAD = 64;                // counter words per count
-constexpr uint32_t CNT_KEPT = 0, CNT_NARROWED = COVER_SPREAD, CNT_UNRESOLVED = 2 * COVER_SPREAD, CNT_LONG = 3 * COVER_SPREAD,
-                   CNT_WORDS = 4 * COVER_SPREAD;
+constexpr uint32_t CNT_KEPT = 0, CNT_NARROWED = 1, CNT_UNRESOLVED = 2, CNT_LONG = 3, CNT_WORDS = 4 * HIT_SPREAD;   // spread counters
 constexpr unsigned long long MILLI_ONE = 100000ull;  // 100 % in milli-percent
 constexpr uint32_t POS_MASK = (1u << BLU_ROW_BITS) - 1u;
 constexpr uint32_t SHARE_BINS = BLU_MAX_DEPTH + 1u;  // a share is 0 .. 64
@@ -61,19 +58,6 @@ struct CoverDev {
     uint32_t n_long;
     unsigned long long* __restrict__ counts;         // [CNT_WORDS]
 };
-
-__device__ __forceinline__ int32_t wave_max32(int32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// the clamped segment of query q: offsets that run past the columns read and write nothing outside them, a decreasing pair is empty
-__device__ __forceinline__ void segment_of(const unsigned long long* __restrict__ seg_off, uint64_t q, uint64_t n_hits, uint64_t* s0, uint64_t* s1) {
-    uint64_t a = seg_off[q], b = seg_off[q + 1];
-    if (b > n_hits) b = n_hits;
-    if (a > b) a = b;
-    *s0 = a; *s1 = b;
-}
 
 // the engine row id of row i; *ok false: the row leaves its query alone when it is in the top group (unmatched, a desc row the
 // map does not have, a bad or empty lineage, a position the taxonomy does not have, a length no lineage has)
@@ -178,21 +162,9 @@ __global__ __launch_bounds__(COVER_BLOCK) void cover_short_kernel(CoverDev d) {
         if (d.depth && lane == 0) d.depth[q] = (uint8_t)depth;
     }
     if (lane == 0) {
-        const uint32_t w = blockIdx.x % COVER_SPREAD;
-        if (n_kept) atomicAdd(&d.counts[CNT_KEPT + w], n_kept);
-        if (n_narrowed) atomicAdd(&d.counts[CNT_NARROWED + w], n_narrowed);
-        if (n_unresolved) atomicAdd(&d.counts[CNT_UNRESOLVED + w], n_unresolved);
-        if (n_long) atomicAdd(&d.counts[CNT_LONG + w], n_long);
+        spread_add(d.counts, CNT_KEPT, n_kept); spread_add(d.counts, CNT_NARROWED, n_narrowed);
+        spread_add(d.counts, CNT_UNRESOLVED, n_unresolved); spread_add(d.counts, CNT_LONG, n_long);
     }
-}
-
-// the long queries, in query order
-__global__ void cover_list_kernel(const uint32_t* __restrict__ long_flag, const uint32_t* __restrict__ flag_pos, uint64_t n_queries,
-                                  uint32_t n_long, uint32_t* __restrict__ list_q) {
-    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= n_queries || !long_flag[q]) return;
-    const uint32_t j = flag_pos[q];
-    if (j < n_long) list_q[j] = (uint32_t)q;
 }
 
 // digits of the radix selection over the BLU_ROW_BITS position bits, most significant first: 7 + 6 + 6 + 6
@@ -239,9 +211,8 @@ __global__ __launch_bounds__(COVER_BLOCK) void cover_long_kernel(CoverDev d) {
     if (n <= 1u || alone) {                          // (block-uniform) the query stays as it is
         for (uint64_t i = s0 + tid; i < s1; i += COVER_BLOCK) d.keep[i] = 1u;
         if (tid == 0) {
-            const uint32_t w = blockIdx.x % COVER_SPREAD;
-            atomicAdd(&d.counts[CNT_KEPT + w], (unsigned long long)n_rows);
-            if (n > 1u) atomicAdd(&d.counts[CNT_UNRESOLVED + w], 1ull);
+            spread_add(d.counts, CNT_KEPT, (unsigned long long)n_rows);
+            spread_add(d.counts, CNT_UNRESOLVED, n > 1u ? 1ull : 0ull);
             if (d.depth) d.depth[q] = (uint8_t)BLU_NONE_U8;
         }
         return;
@@ -300,9 +271,8 @@ __global__ __launch_bounds__(COVER_BLOCK) void cover_long_kernel(CoverDev d) {
     if (dropped) atomicAdd(&s_dropped, dropped);
     __syncthreads();
     if (tid == 0) {
-        const uint32_t w = blockIdx.x % COVER_SPREAD;
-        atomicAdd(&d.counts[CNT_KEPT + w], (unsigned long long)(n_rows - s_dropped));
-        if (s_dropped) atomicAdd(&d.counts[CNT_NARROWED + w], 1ull);
+        spread_add(d.counts, CNT_KEPT, (unsigned long long)(n_rows - s_dropped));
+        spread_add(d.counts, CNT_NARROWED, s_dropped ? 1ull : 0ull);
         if (d.depth) d.depth[q] = (uint8_t)depth;
     }
 }
@@ -314,12 +284,6 @@ int check_min_cover(int64_t min_cover_milli) {
         set_error("min cover: min_cover_milli must be 50001 .. 100000 (above 50 %%, at most 100 %%), not %lld", (long long)min_cover_milli);
         return BLU_ERR_INVALID_ARG;
     }
-    return BLU_OK;
-}
-
-int check_cover_counts(uint64_t n_hits, uint64_t n_queries) {
-    if (n_hits >= (1ull << 32)) { set_error("min cover: n_hits must be below 2^32"); return BLU_ERR_INVALID_ARG; }
-    if (n_queries >= (1ull << 32)) { set_error("min cover: n_queries must be below 2^32"); return BLU_ERR_INVALID_ARG; }
     return BLU_OK;
 }
 
@@ -340,7 +304,6 @@ int cover_keep_device(const blu_taxonomy* tax, const int32_t* d_bitscore, const 
     HIP_CHECK(pol, mem.alloc(&d_counts, sizeof counts, "counts"));
     HIP_CHECK(pol, mem.alloc(&d_flag, (n_queries + 1) * 4, "long flags"));
     HIP_CHECK(pol, hipMemsetAsync(d_counts, 0, sizeof counts, nullptr));
-    HIP_CHECK(pol, hipMemsetAsync(d_flag + n_queries, 0, 4, nullptr));
     CoverDev d{};
     d.bitscore = d_bitscore; d.tax_row = d_tax_row; d.row_map = d_row_map; d.seg_off = (const unsigned long long*)d_seg_off;
     d.n_hits = n_hits; d.n_queries = n_queries;
@@ -349,29 +312,22 @@ int cover_keep_device(const blu_taxonomy* tax, const int32_t* d_bitscore, const 
     hipLaunchKernelGGL(cover_short_kernel, dim3((unsigned)blocks), dim3(COVER_BLOCK), 0, nullptr, d);
     HIP_CHECK(pol, hipGetLastError());
     HIP_CHECK(pol, hipMemcpy(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost));
-    uint64_t n_long = 0;
-    for (uint32_t k = 0; k < COVER_SPREAD; ++k) n_long += counts[CNT_LONG + k];
+    const uint64_t n_long = spread_sum(counts, CNT_LONG);
     if (n_long) {
-        uint32_t *d_fpos = nullptr, *d_list_q = nullptr;
+        uint32_t* d_list_q = nullptr;
         void* d_tmp = nullptr;
-        HIP_CHECK(pol, mem.alloc(&d_fpos, (n_queries + 1) * 4, "long positions"));
         HIP_CHECK(pol, mem.alloc(&d_tmp, scan_tmp_bytes_u32(n_queries + 1), "scan work"));
-        HIP_CHECK(pol, mem.alloc(&d_list_q, n_long * 4, "long queries"));
-        HIP_CHECK(pol, exclusive_scan_u32(d_flag, d_fpos, n_queries + 1, d_tmp));
-        hipLaunchKernelGGL(cover_list_kernel, grid(n_queries), dim3(256), 0, nullptr, (const uint32_t*)d_flag, (const uint32_t*)d_fpos,
-                           n_queries, (uint32_t)n_long, d_list_q);
+        if (const int rc = long_query_list(pol, mem, d_flag, n_queries, n_long, nullptr, d_tmp, &d_list_q, nullptr)) return rc;
         d.list_q = d_list_q; d.n_long = (uint32_t)n_long;
         hipLaunchKernelGGL(cover_long_kernel, dim3((unsigned)n_long), dim3(COVER_BLOCK), 0, nullptr, d);
         HIP_CHECK(pol, hipGetLastError());
         HIP_CHECK(pol, hipMemcpy(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost));
     }
-    for (uint32_t k = 0; k < COVER_SPREAD; ++k) {
-        stats->n_kept += counts[CNT_KEPT + k]; stats->n_narrowed += counts[CNT_NARROWED + k]; stats->n_unresolved += counts[CNT_UNRESOLVED + k];
-    }
+    stats->n_kept = spread_sum(counts, CNT_KEPT); stats->n_narrowed = spread_sum(counts, CNT_NARROWED); stats->n_unresolved = spread_sum(counts, CNT_UNRESOLVED);
     return BLU_OK;
 }
 
-int cover_apply_device(const blu_taxonomy* tax, SubjectColumns& c, const uint32_t* d_row_map, uint64_t n_hits, uint64_t n_queries,
+int cover_apply_device(const blu_taxonomy* tax, HitColumns& c, const uint32_t* d_row_map, uint64_t n_hits, uint64_t n_queries,
                        uint32_t min_cover_milli, bool rotate, uint32_t unmatched_marker, uint64_t* n_hits_out, uint64_t* n_unmatched,
                        blu_min_cover_stats* stats, std::vector<void*>* retired) {
     HipPolicy pol{"min cover", BLU_ERR_ALLOC};
@@ -392,16 +348,15 @@ int cover_apply_device(const blu_taxonomy* tax, SubjectColumns& c, const uint32_
 int cover_hits(const blu_taxonomy* tax, DeviceHits& dev, const uint32_t* fwd, uint64_t n_tax, uint32_t min_cover_milli,
                blu_min_cover_stats* stats, uint64_t* unmatched) {
     *stats = blu_min_cover_stats{dev.n_hits, dev.n_hits, dev.n_queries, 0, 0};
-    if (int rc = check_cover_counts(dev.n_hits, dev.n_queries)) return rc;
+    if (int rc = check_hit_counts("min cover", dev.n_hits, dev.n_queries)) return rc;
     if (n_tax != tax->n_tax) { set_error("min cover: the row map has %llu rows, the taxonomy %llu", (unsigned long long)n_tax, (unsigned long long)tax->n_tax); return BLU_ERR_INVALID_ARG; }
-    if (hipSetDevice(dev.device) != hipSuccess) { (void)hipGetLastError(); set_error("min cover: hipSetDevice(%d) failed", dev.device); return BLU_ERR_NO_DEVICE; }
+    if (int rc = use_device("min cover", dev.device)) return rc;
     HipPolicy pol{"min cover", BLU_ERR_ALLOC};
     DeviceArena mem(pol);
     struct ToTrash { DeviceArena& mem; DeviceHits& dev; ~ToTrash() { mem.hand_over(dev.trash); } } to_trash{mem, dev};
     uint32_t* d_map = nullptr;
-    HIP_CHECK(pol, mem.alloc(&d_map, n_tax * 4, "row map"));
-    if (n_tax) HIP_CHECK(pol, hipMemcpy(d_map, fwd, n_tax * 4, hipMemcpyHostToDevice));
-    SubjectColumns c{&dev.bitscore, &dev.align_len, &dev.tax_desc_row, &dev.acc_rank, &dev.pident, dev.seg_off};
+    HIP_CHECK(pol, mem.upload(&d_map, fwd, n_tax, "row map"));
+    HitColumns c = columns_of(dev);
     uint64_t n_out = dev.n_hits;
     const int rc = cover_apply_device(tax, c, d_map, dev.n_hits, dev.n_queries, min_cover_milli, true, BLU_UNMATCHED_TAXID, &n_out, unmatched,
                                       stats, &dev.trash);
@@ -420,8 +375,8 @@ namespace {
 int cover_refusals(const char* who, const blu_taxonomy* tax, bool null_array, uint64_t n_hits, uint64_t n_queries, uint32_t min_cover_milli) {
     if (int rc = check_min_cover((int64_t)min_cover_milli)) return rc;
     if (!tax) { set_error("%s: null taxonomy handle", who); return BLU_ERR_INVALID_ARG; }
-    if (null_array) { set_error("%s: null array with a non-zero count", who); return BLU_ERR_INVALID_ARG; }
-    if (int rc = check_cover_counts(n_hits, n_queries)) return rc;
+    if (null_array) return refuse_null_array(who);
+    if (int rc = check_hit_counts("min cover", n_hits, n_queries)) return rc;
     if (tax->device < 0) { set_error("host-only taxonomy handle: %s needs a HIP device (no CPU fallback)", who); return BLU_ERR_NO_DEVICE; }
     return BLU_OK;
 }
@@ -437,7 +392,7 @@ int blu_hits_cover_keep(const blu_taxonomy* tax, const int32_t* bitscore, const 
     int rc = cover_refusals("blu_hits_cover_keep", tax, (n_hits && (!bitscore || !tax_row || !keep_out)) || (n_queries && !seg_off), n_hits, n_queries,
                             min_cover_milli);
     if (rc != BLU_OK) return rc;
-    if (hipSetDevice(tax->device) != hipSuccess) { (void)hipGetLastError(); set_error("blu_hits_cover_keep: hipSetDevice(%d) failed", tax->device); return BLU_ERR_NO_DEVICE; }
+    if ((rc = use_device("blu_hits_cover_keep", tax->device)) != BLU_OK) return rc;
     HipPolicy pol{"blu_hits_cover_keep", BLU_ERR_ALLOC};
     blu_min_cover_stats st{};
     if (on_device) {
@@ -450,21 +405,15 @@ int blu_hits_cover_keep(const blu_taxonomy* tax, const int32_t* bitscore, const 
         uint32_t *d_tax = nullptr, *d_map = nullptr, *d_keep = nullptr;
         uint64_t* d_seg = nullptr;
         uint8_t* d_depth = nullptr;
-        HIP_CHECK(pol, mem.alloc(&d_bs, n_hits * 4, "bit-scores"));
-        HIP_CHECK(pol, mem.alloc(&d_tax, n_hits * 4, "taxonomy rows"));
+        HIP_CHECK(pol, mem.upload(&d_bs, bitscore, n_hits, "bit-scores"));
+        HIP_CHECK(pol, mem.upload(&d_tax, tax_row, n_hits, "taxonomy rows"));
         HIP_CHECK(pol, mem.alloc(&d_keep, n_hits * 4, "keep words"));
-        HIP_CHECK(pol, mem.alloc(&d_seg, (n_queries + 1) * 8, "offsets"));
-        if (n_hits) HIP_CHECK(pol, hipMemcpy(d_bs, bitscore, n_hits * 4, hipMemcpyHostToDevice));
-        if (n_hits) HIP_CHECK(pol, hipMemcpy(d_tax, tax_row, n_hits * 4, hipMemcpyHostToDevice));
-        if (n_queries) HIP_CHECK(pol, hipMemcpy(d_seg, seg_off, (n_queries + 1) * 8, hipMemcpyHostToDevice));
-        if (row_map) {
-            HIP_CHECK(pol, mem.alloc(&d_map, tax->n_tax * 4, "row map"));
-            if (tax->n_tax) HIP_CHECK(pol, hipMemcpy(d_map, row_map, tax->n_tax * 4, hipMemcpyHostToDevice));
-        }
+        HIP_CHECK(pol, mem.upload(&d_seg, seg_off, n_queries ? n_queries + 1 : 0, "offsets"));
+        if (row_map) HIP_CHECK(pol, mem.upload(&d_map, row_map, tax->n_tax, "row map"));
         if (depth_out) HIP_CHECK(pol, mem.alloc(&d_depth, n_queries, "depths"));
         rc = cover_keep_device(tax, d_bs, d_tax, d_map, d_seg, n_hits, n_queries, min_cover_milli, d_keep, d_depth, &st);
-        if (rc == BLU_OK && n_hits) HIP_CHECK(pol, hipMemcpy(keep_out, d_keep, n_hits * 4, hipMemcpyDeviceToHost));
-        if (rc == BLU_OK && depth_out && n_queries) HIP_CHECK(pol, hipMemcpy(depth_out, d_depth, n_queries, hipMemcpyDeviceToHost));
+        if (rc == BLU_OK) HIP_CHECK(pol, mem.download(keep_out, d_keep, n_hits));
+        if (rc == BLU_OK && depth_out) HIP_CHECK(pol, mem.download(depth_out, d_depth, n_queries));
     }
     if (rc != BLU_OK) return rc;
     if (stats) *stats = st;
@@ -481,52 +430,19 @@ int blu_hits_cover_apply(const blu_taxonomy* tax, int32_t* bitscore, int32_t* al
                             (n_hits && (!bitscore || !align_len || !tax_row || !acc_rank || !pident)) || (n_queries && !seg_off), n_hits, n_queries,
                             min_cover_milli);
     if (rc != BLU_OK) return rc;
-    if (on_device && (((uintptr_t)bitscore | (uintptr_t)align_len | (uintptr_t)tax_row | (uintptr_t)acc_rank | (uintptr_t)pident) & 15u)) {
-        set_error("blu_hits_cover_apply: device columns must be 16-byte aligned");
-        return BLU_ERR_INVALID_ARG;
-    }
-    if (hipSetDevice(tax->device) != hipSuccess) { (void)hipGetLastError(); set_error("blu_hits_cover_apply: hipSetDevice(%d) failed", tax->device); return BLU_ERR_NO_DEVICE; }
+    HitColumns c{&bitscore, &align_len, &tax_row, &acc_rank, &pident, (unsigned long long*)seg_off};
+    if (on_device && (rc = check_aligned16("blu_hits_cover_apply", c)) != BLU_OK) return rc;
+    if ((rc = use_device("blu_hits_cover_apply", tax->device)) != BLU_OK) return rc;
     HipPolicy pol{"blu_hits_cover_apply", BLU_ERR_ALLOC};
     uint64_t n_out = n_hits, n_unmatched = 0;
     blu_min_cover_stats st{};
     if (on_device) {
         HIP_CHECK(pol, hipStreamSynchronize((hipStream_t)stream));
-        SubjectColumns c{&bitscore, &align_len, &tax_row, &acc_rank, &pident, (unsigned long long*)seg_off};
         rc = cover_apply_device(tax, c, row_map, n_hits, n_queries, min_cover_milli, false, unmatched_marker, &n_out, &n_unmatched, &st, nullptr);
     } else {
-        DeviceArena mem(pol);
-        int32_t *d_bs = nullptr, *d_aln = nullptr;
-        uint32_t *d_tax = nullptr, *d_acc = nullptr, *d_map = nullptr;
-        double* d_pid = nullptr;
-        unsigned long long* d_seg = nullptr;
-        HIP_CHECK(pol, mem.alloc(&d_bs, n_hits * 4, "bit-scores"));
-        HIP_CHECK(pol, mem.alloc(&d_aln, n_hits * 4, "alignment lengths"));
-        HIP_CHECK(pol, mem.alloc(&d_tax, n_hits * 4, "taxonomy rows"));
-        HIP_CHECK(pol, mem.alloc(&d_acc, n_hits * 4, "accession ranks"));
-        HIP_CHECK(pol, mem.alloc(&d_pid, n_hits * 8, "identities"));
-        HIP_CHECK(pol, mem.alloc(&d_seg, (n_queries + 1) * 8, "offsets"));
-        if (n_hits) {
-            HIP_CHECK(pol, hipMemcpy(d_bs, bitscore, n_hits * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(pol, hipMemcpy(d_aln, align_len, n_hits * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(pol, hipMemcpy(d_tax, tax_row, n_hits * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(pol, hipMemcpy(d_acc, acc_rank, n_hits * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(pol, hipMemcpy(d_pid, pident, n_hits * 8, hipMemcpyHostToDevice));
-        }
-        if (n_queries) HIP_CHECK(pol, hipMemcpy(d_seg, seg_off, (n_queries + 1) * 8, hipMemcpyHostToDevice));
-        if (row_map) {
-            HIP_CHECK(pol, mem.alloc(&d_map, tax->n_tax * 4, "row map"));
-            if (tax->n_tax) HIP_CHECK(pol, hipMemcpy(d_map, row_map, tax->n_tax * 4, hipMemcpyHostToDevice));
-        }
-        SubjectColumns c{&d_bs, &d_aln, &d_tax, &d_acc, &d_pid, d_seg};
-        rc = cover_apply_device(tax, c, d_map, n_hits, n_queries, min_cover_milli, false, unmatched_marker, &n_out, &n_unmatched, &st, nullptr);
-        if (rc == BLU_OK && n_out < n_hits) {
-            HIP_CHECK(pol, hipMemcpy(bitscore, d_bs, n_out * 4, hipMemcpyDeviceToHost));
-            HIP_CHECK(pol, hipMemcpy(align_len, d_aln, n_out * 4, hipMemcpyDeviceToHost));
-            HIP_CHECK(pol, hipMemcpy(tax_row, d_tax, n_out * 4, hipMemcpyDeviceToHost));
-            HIP_CHECK(pol, hipMemcpy(acc_rank, d_acc, n_out * 4, hipMemcpyDeviceToHost));
-            HIP_CHECK(pol, hipMemcpy(pident, d_pid, n_out * 8, hipMemcpyDeviceToHost));
-            if (n_queries) HIP_CHECK(pol, hipMemcpy(seg_off, d_seg, (n_queries + 1) * 8, hipMemcpyDeviceToHost));
-        }
+        rc = with_staged_columns(pol, c, n_hits, n_queries, row_map, tax->n_tax, &n_out, [&](HitColumns& d, const uint32_t* d_map, uint64_t* n) {
+            return cover_apply_device(tax, d, d_map, n_hits, n_queries, min_cover_milli, false, unmatched_marker, n, &n_unmatched, &st, nullptr);
+        });
     }
     if (rc != BLU_OK) return rc;
     if (n_hits_out) *n_hits_out = n_out;

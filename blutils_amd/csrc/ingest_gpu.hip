@@ -46,9 +46,8 @@
 #include <vector>
 
 #include "blu_consensus.h"
-#include "blu_internal.h"
+#include "hit_pass.h"
 #include "ingest.h"
-#include "ingest_prims.h"
 #include "taxid_probe.h"
 
 namespace blu {
@@ -343,9 +342,8 @@ struct DevFilter {
     int k_keep, k_drop;          // decimal magnitude tests: digits + exponent <= k_keep -> below max_e; digits - 1 + exponent >= k_drop -> above
     double e_lo, e_hi;           // max_e (1 -+ 2^-46): a computed value at or below e_lo is kept, at or above e_hi dropped
     uint32_t* keep;              // [n_rows]
-    unsigned long long* counts;  // [0 .. FCNT_SPREAD) kept lines (spread over blocks), [FCNT_SPREAD] lines left to the host
+    unsigned long long* counts;  // [0 .. HIT_SPREAD) kept lines (hit_pass.h: spread over blocks), [HIT_SPREAD] lines left to the host
 };
-constexpr uint32_t FCNT_SPREAD = 64;
 enum : uint32_t { KEEP_NO = 0, KEEP_YES = 1, KEEP_ASK_HOST = 2 };
 
 // `strtod(field) <= max_e` for a field of the plain grammar (NumState::plain), value = mant x 10^e with mant < 10^15.
@@ -385,9 +383,9 @@ __device__ __forceinline__ void filter_row(const DevFilter& f, uint32_t i, doubl
     if (pass && (f.mask & BLU_FILTER_MAX_E_VALUE)) k = e_value_verdict(e_mant, e_exp, e_neg, f);
     f.keep[i] = k;
     const uint32_t lane = threadIdx.x & 63u;
-    const unsigned long long kept = __ballot(k == KEEP_YES), ask = __ballot(k == KEEP_ASK_HOST);
-    if (k == KEEP_YES && (kept & ((1ull << lane) - 1ull)) == 0) atomicAdd(&f.counts[blockIdx.x % FCNT_SPREAD], (unsigned long long)__popcll(kept));
-    if (k == KEEP_ASK_HOST && (ask & ((1ull << lane) - 1ull)) == 0) atomicAdd(&f.counts[FCNT_SPREAD], (unsigned long long)__popcll(ask));
+    spread_add_ballot(f.counts, 0, k == KEEP_YES);
+    const unsigned long long ask = __ballot(k == KEEP_ASK_HOST);     // (rare: one word takes them all)
+    if (k == KEEP_ASK_HOST && (ask & ((1ull << lane) - 1ull)) == 0) atomicAdd(&f.counts[HIT_SPREAD], (unsigned long long)__popcll(ask));
 }
 
 // ---- taxon filter.  The host made one 16-bit code per taxonomy row from the lineages (ingest.h: TaxonCodes);
@@ -399,7 +397,7 @@ struct DevTaxa {
     uint32_t n_tax;
     uint32_t unmatched;                    // the verdict of a line whose taxid is not in the taxonomy
     unsigned long long* excluded_by;       // [n_exclude] lines whose first matching exclude element it is
-    unsigned long long* not_only;          // [FCNT_SPREAD] lines failing only the only list (spread over blocks)
+    unsigned long long* not_only;          // [HIT_SPREAD] lines failing only the only list (spread over blocks)
 };
 struct DevFilterTaxa { DevFilter f; DevTaxa t; };
 
@@ -419,8 +417,7 @@ __device__ __forceinline__ uint32_t taxon_verdict(const DevTaxa& t, uint32_t row
         if (lane == (uint32_t)first) atomicAdd(&t.excluded_by[c - 1], (unsigned long long)__popcll(same));
         left &= ~same;
     }
-    const unsigned long long no = __ballot(code == TAXON_NOT_ONLY);
-    if (code == TAXON_NOT_ONLY && (no & ((1ull << lane) - 1ull)) == 0) atomicAdd(&t.not_only[blockIdx.x % FCNT_SPREAD], (unsigned long long)__popcll(no));
+    spread_add_ballot(t.not_only, 0, code == TAXON_NOT_ONLY);
     return code;
 }
 
@@ -1188,7 +1185,7 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
     HIP_CHECK(pol, mem.alloc(&d_tile_base, (n_tiles + 1) * 4, "line index"));
     // {flags, -, -, -, counter, -, -, -, big counters}; under a hit filter the kept / undecided counts follow, and under a taxon
     // filter the not-only counts and one count per exclude element after them: all of it comes back in one copy
-    const size_t n_back = 8 + FCNT_SPREAD + 1 + (taxa ? FCNT_SPREAD + (size_t)taxa->n_exclude : 0);
+    const size_t n_back = 8 + HIT_SPREAD + 1 + (taxa ? HIT_SPREAD + (size_t)taxa->n_exclude : 0);
     const size_t flag_bytes = flt || taxa ? n_back * 8 : 64;
     HIP_CHECK(pol, mem.alloc(&d_flags, flag_bytes, "flags"));
     HIP_CHECK(pol, hipMemset(d_flags, 0, flag_bytes));
@@ -1208,8 +1205,7 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
     lap("line index");
 
     // ---- parse
-    HIP_CHECK(pol, mem.alloc(&d_taxmap, row_of.tab.size() * sizeof(TaxidMap::E), "taxid map"));
-    HIP_CHECK(pol, hipMemcpy(d_taxmap, row_of.tab.data(), row_of.tab.size() * sizeof(TaxidMap::E), hipMemcpyHostToDevice));
+    HIP_CHECK(pol, mem.upload(&d_taxmap, row_of.tab.data(), row_of.tab.size(), "taxid map"));
     HIP_CHECK(pol, mem.alloc(&d_qh, (size_t)n_rows * 8, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_ah, (size_t)n_rows * 8, "parsed rows"));
     HIP_CHECK(pol, mem.alloc(&d_qpos, (size_t)n_rows * 8, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_apos, (size_t)n_rows * 8, "parsed rows"));
     HIP_CHECK(pol, mem.alloc(&d_tax, (size_t)n_rows * 4, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_pid, (size_t)n_rows * 8, "parsed rows"));
@@ -1242,10 +1238,9 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
         } else {
             // ---- taxon filter: the row codes go up next to the taxid map; the verdict is taken in the parse
             const size_t n_tax = taxa->code.size();
-            HIP_CHECK(pol, mem.alloc(&d_code, std::max<size_t>(n_tax, 1) * 2, "taxon codes"));
-            if (n_tax) { HIP_CHECK(pol, hipMemcpy(d_code, taxa->code.data(), n_tax * 2, hipMemcpyHostToDevice)); }
+            HIP_CHECK(pol, mem.upload(&d_code, taxa->code.data(), n_tax, "taxon codes"));
             hf.t.code = d_code; hf.t.n_tax = (uint32_t)n_tax; hf.t.unmatched = taxa->unmatched;
-            hf.t.not_only = d_fcnt + FCNT_SPREAD + 1; hf.t.excluded_by = hf.t.not_only + FCNT_SPREAD;
+            hf.t.not_only = d_fcnt + HIT_SPREAD + 1; hf.t.excluded_by = hf.t.not_only + HIT_SPREAD;
             HIP_CHECK(pol, hipMemcpy(d_filter, &hf, sizeof hf, hipMemcpyHostToDevice));
             hipLaunchKernelGGL(parse_rows_taxa, grid(n_rows, PARSE_THREADS), dim3(PARSE_THREADS), 0, 0, d_text, d_line, n_rows, tm, o, d_flags,
                                (const DevFilterTaxa*)d_filter);
@@ -1253,14 +1248,13 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
         HIP_CHECK(pol, hipMemcpy(back.data(), d_flags, n_back * 8, hipMemcpyDeviceToHost));
         h_flags = (uint32_t)back[0];
         if (h_flags) return fallback(fallback_text(h_flags));
-        uint64_t n_kept = 0;
-        for (uint32_t k = 0; k < FCNT_SPREAD; ++k) n_kept += back[8 + k];
-        const uint64_t n_ask = back[8 + FCNT_SPREAD];
+        uint64_t n_kept = spread_sum(back.data() + 8, 0);
+        const uint64_t n_ask = back[8 + HIT_SPREAD];
         uint64_t n_excluded = 0, n_not_only = 0;
         if (taxa) {
-            const unsigned long long* tb = back.data() + 8 + FCNT_SPREAD + 1;
-            for (uint32_t k = 0; k < FCNT_SPREAD; ++k) n_not_only += tb[k];
-            for (uint32_t k = 0; k < taxa->n_exclude; ++k) n_excluded += tb[FCNT_SPREAD + k];
+            const unsigned long long* tb = back.data() + 8 + HIT_SPREAD + 1;
+            n_not_only = spread_sum(tb, 0);
+            for (uint32_t k = 0; k < taxa->n_exclude; ++k) n_excluded += tb[HIT_SPREAD + k];
             if (n_excluded + n_not_only + n_kept + n_ask > n_rows) return fallback("inconsistent taxon-filter counts");
         }
         lap("parse (filtered)");
@@ -1296,33 +1290,16 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
         const uint64_t n_lines = n_rows;
         if (n_kept == 0) return fallback("no rows kept by the filters");   // (the host parser returns the empty table)
         if (n_kept < n_rows) {
-            // stable compaction, one column after another through ONE spare buffer: a column is scattered into the spare, the
-            // spare becomes the column and the column's old buffer the next spare (8-byte columns first, so that every spare
-            // is large enough).  Peak: the eight arrays (52 B / line) + keep words and their scan (8 B / line) + 8 B / kept line.
+            // stable compaction, one column after another through ONE spare buffer (hit_pass.h: Compaction), 8-byte columns
+            // first.  Peak: the eight arrays (52 B / line) + keep words and their scan (8 B / line) + 8 B / kept line.
             const uint32_t n_out = (uint32_t)n_kept;
             HIP_CHECK(pol, mem.alloc(&d_kpos, (size_t)n_rows * 4, "keep positions"));
             HIP_CHECK(pol, need_tmp(scan_tmp_bytes<uint32_t>((size_t)n_rows)));
             HIP_CHECK(pol, exclusive_scan_dev<uint32_t>(d_keep, d_kpos, (size_t)n_rows, d_tmp));
-            void* spare = nullptr;
-            HIP_CHECK(pol, mem.alloc(&spare, (size_t)n_out * 8, "compaction spare"));
-            auto move8 = [&](auto*& col) {
-                using T = std::remove_reference_t<decltype(*col)>;
-                static_assert(sizeof(T) == 8, "8-byte column");
-                hipLaunchKernelGGL((compact_column<T>), grid(n_rows, COMPACT_THREADS * 2), dim3(COMPACT_THREADS), 0, 0, (const T*)col, (const uint32_t*)d_keep,
-                                   (const uint32_t*)d_kpos, n_rows, n_out, (T*)spare);
-                void* old = col; col = (T*)spare; spare = old;
-            };
-            auto move4 = [&](auto*& col) {
-                using T = std::remove_reference_t<decltype(*col)>;
-                static_assert(sizeof(T) == 4, "4-byte column");
-                hipLaunchKernelGGL((compact_column<T>), grid(n_rows, COMPACT_THREADS * 4), dim3(COMPACT_THREADS), 0, 0, (const T*)col, (const uint32_t*)d_keep,
-                                   (const uint32_t*)d_kpos, n_rows, n_out, (T*)spare);
-                void* old = col; col = (T*)spare; spare = old;
-            };
-            move8(d_qh); move8(d_ah); move8(d_qpos); move8(d_apos); move8(d_pid);
-            move4(d_tax); move4(d_aln); move4(d_bs);
-            HIP_CHECK(pol, hipGetLastError());
-            mem.free(spare); mem.free(d_kpos);
+            Compaction cp{d_keep, d_kpos, n_rows, n_out, nullptr};
+            HIP_CHECK(pol, mem.alloc(&cp.spare, (size_t)n_out * 8, "compaction spare"));
+            HIP_CHECK(pol, cp.rotate(d_qh, d_ah, d_qpos, d_apos, d_pid, d_tax, d_aln, d_bs));
+            mem.free(cp.spare); mem.free(d_kpos);
             n_rows = n_out;
             lap("  filter: compaction");
         }
@@ -1332,7 +1309,7 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
         hipLaunchKernelGGL(count_unmatched, grid(n_rows, 1024), dim3(1024), 0, 0, (const uint32_t*)d_tax, n_rows, d_big);
         ht.n_lines = n_lines; ht.n_kept = n_kept;
         if (taxa) {
-            const unsigned long long* tb = back.data() + 8 + FCNT_SPREAD + 1 + FCNT_SPREAD;
+            const unsigned long long* tb = back.data() + 8 + HIT_SPREAD + 1 + HIT_SPREAD;
             taxa->n_excluded = n_excluded; taxa->n_not_only = n_not_only;
             taxa->excluded_by.assign(tb, tb + taxa->n_exclude);
         }
@@ -1841,7 +1818,7 @@ using namespace blu;
 namespace {
 
 int dev_enter(int device, const char* who) {
-    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipSetDevice(%d) failed", who, device); return BLU_ERR_NO_DEVICE; }
+    if (const int rc = use_device(who, device)) return rc;
     const hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) { set_error("%s: hipDeviceSynchronize failed: %s", who, hipGetErrorString(e)); return BLU_ERR_HIP; }
     return BLU_OK;

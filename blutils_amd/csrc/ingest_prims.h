@@ -74,6 +74,17 @@ struct DeviceArena {
         if (e == hipSuccess) { ptrs.push_back(p); *out = (T*)p; }
         return e;
     }
+    // a device copy of host[0, n): allocated whatever n is, filled when there is something to fill it with
+    template <class T>
+    hipError_t upload(T** out, const void* host, size_t n, const char* what) {
+        const hipError_t e = alloc(out, n * sizeof(T), what);
+        return e == hipSuccess && n ? hipMemcpy(*out, host, n * sizeof(T), hipMemcpyHostToDevice) : e;
+    }
+    // n elements back to the host (the buffer may be any device memory)
+    template <class T>
+    static hipError_t download(void* host, const T* dev, size_t n) {
+        return n ? hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess;
+    }
     void free(void* p) {
         if (keep) return;
         auto it = std::find(ptrs.begin(), ptrs.end(), p);

@@ -1651,14 +1651,17 @@ struct Selection {
     // three has not been applied on the device columns.  The table's counts follow the kept rows.  tax, fwd: the taxonomy handle
     // and its forward row map, which the cover needs (the ingest-columns call has neither, and no cover).
     int on_host_columns(int device, HitTable& ht, Trace* tr = nullptr, const blu_taxonomy* tax = nullptr, const uint32_t* fwd = nullptr) {
+        auto shrink = [&ht](uint64_t n_out, uint64_t unmatched) {   // the rows a pass kept: the front of each column
+            ht.bitscore.resize(n_out); ht.align_len.resize(n_out); ht.tax_desc_row.resize(n_out); ht.acc_rank.resize(n_out); ht.pident.resize(n_out);
+            ht.n_hits = n_out; ht.unmatched = unmatched;
+        };
         if (subj && !subject_done && ht.n_hits) {
             uint64_t n_out = ht.n_hits, unmatched = ht.unmatched;
             int rc = blu_hits_subject_best(device, ht.bitscore.data(), ht.align_len.data(), ht.tax_desc_row.data(), ht.acc_rank.data(),
                                            ht.pident.data(), ht.seg_off.data(), ht.n_hits, ht.n_queries, 0, subj, nullptr, BLU_UNMATCHED_TAXID,
                                            &n_out, &unmatched, &st->subject_best);
             if (rc != BLU_OK) return rc;
-            ht.bitscore.resize(n_out); ht.align_len.resize(n_out); ht.tax_desc_row.resize(n_out); ht.acc_rank.resize(n_out); ht.pident.resize(n_out);
-            ht.n_hits = n_out; ht.unmatched = unmatched;
+            shrink(n_out, unmatched);
             subject_done = true;
             st->score_band.n_hits = n_out;
             if (tr) tr->lap("subject best hit (host columns)");
@@ -1676,8 +1679,7 @@ struct Selection {
                                           fwd, ht.seg_off.data(), ht.n_hits, ht.n_queries, 0, (uint32_t)cover_milli, nullptr, BLU_UNMATCHED_TAXID,
                                           &n_out, &unmatched, &cover_st);
             if (rc != BLU_OK) return rc;
-            ht.bitscore.resize(n_out); ht.align_len.resize(n_out); ht.tax_desc_row.resize(n_out); ht.acc_rank.resize(n_out); ht.pident.resize(n_out);
-            ht.n_hits = n_out; ht.unmatched = unmatched;
+            shrink(n_out, unmatched);
             cover_done = true;
             if (tr) tr->lap("min cover (host columns)");
         }

@@ -11,33 +11,31 @@
 // trip count: every lane takes part in every read); the low half of row k's pack is known from k.  One store per lane, counts by
 // ballot and popcount.  No LDS.
 //
-// Long segments (> 64 rows): the short kernel leaves them alone and writes their length to a word per query.  Two u32 scans
-// (ingest_prims.h) turn these words into the list of long queries and the start of each among the R long rows.  A thread per long
+// Long segments (> 64 rows): the short kernel leaves them alone and writes their length to a word per query.  A scan of the lengths
+// and long_query_list (hit_pass.h) turn these words into the list of long queries and the start of each among the R long rows.  A thread per long
 // row finds its query by a binary search in that list.  One open-addressing table of 16-byte slots {key, val}, a power-of-two
 // capacity >= 2 R, home slot = mix(key) & (capacity - 1), linear probing that wraps: kernel 1 claims the slot of
 // key = query << 32 | acc_rank with a CAS and raises val to its pack with a 64-bit atomicMax; kernel 2 looks the pair up and keeps the
 // row iff val is its own pack.  pack being unique inside a segment, the outcome does not depend on scheduling.  A probe gives up
 // after `capacity` steps (it never does on a table that holds at most R <= capacity / 2 keys) and raises the error word.
+//
+// Segments, counters, the long-query list, the compaction and the staging of host columns are hit_pass.h's.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
-#include <type_traits>
 #include <vector>
 
-#include "blu_internal.h"
+#include "hit_pass.h"
 #include "ingest.h"
-#include "ingest_prims.h"
 
 namespace blu {
 namespace {
 
 constexpr uint32_t SUBJ_BLOCK = 256;                 // threads per block: four waves
 constexpr uint32_t SUBJ_QPW = BLU_SUBJECT_QUERIES_PER_WAVE;
-constexpr uint32_t SUBJ_SPREAD = 64;                 // counter words per count
-// counter words (64-bit): SUBJ_SPREAD each of kept rows, thinned queries, long queries, long rows; then the error word
-constexpr uint32_t CNT_KEPT = 0, CNT_THINNED = SUBJ_SPREAD, CNT_LONG = 2 * SUBJ_SPREAD, CNT_LONG_ROWS = 3 * SUBJ_SPREAD,
-                   CNT_ERROR = 4 * SUBJ_SPREAD, CNT_WORDS = 4 * SUBJ_SPREAD + 1;
+// spread counters: kept rows, thinned queries, long queries, long rows; then the error word
+constexpr uint32_t CNT_KEPT = 0, CNT_THINNED = 1, CNT_LONG = 2, CNT_LONG_ROWS = 3, CNT_ERROR = 4 * HIT_SPREAD, CNT_WORDS = 4 * HIT_SPREAD + 1;
 constexpr unsigned long long EMPTY_KEY = ~0ull;
 
 struct Slot { unsigned long long key, val; };        // 16 bytes
@@ -54,14 +52,6 @@ struct SubjDev {
 };
 
 __device__ __forceinline__ uint32_t biased(int32_t bs) { return (uint32_t)bs ^ 0x80000000u; }
-
-// the clamped segment of query q: offsets that run past the columns read and write nothing outside them, a decreasing pair is empty
-__device__ __forceinline__ void segment_of(const unsigned long long* __restrict__ seg_off, uint64_t q, uint64_t n_hits, uint64_t* s0, uint64_t* s1) {
-    uint64_t a = seg_off[q], b = seg_off[q + 1];
-    if (b > n_hits) b = n_hits;
-    if (a > b) a = b;
-    *s0 = a; *s1 = b;
-}
 
 __global__ __launch_bounds__(SUBJ_BLOCK) void subject_short_kernel(SubjDev d) {
     const uint32_t lane = threadIdx.x & 63u;
@@ -95,21 +85,9 @@ __global__ __launch_bounds__(SUBJ_BLOCK) void subject_short_kernel(SubjDev d) {
         n_thinned += kept < n ? 1ull : 0ull;
     }
     if (lane == 0) {
-        const uint32_t w = blockIdx.x % SUBJ_SPREAD;
-        if (n_kept) atomicAdd(&d.counts[CNT_KEPT + w], n_kept);
-        if (n_thinned) atomicAdd(&d.counts[CNT_THINNED + w], n_thinned);
-        if (n_long) { atomicAdd(&d.counts[CNT_LONG + w], n_long); atomicAdd(&d.counts[CNT_LONG_ROWS + w], n_long_rows); }
+        spread_add(d.counts, CNT_KEPT, n_kept); spread_add(d.counts, CNT_THINNED, n_thinned);
+        spread_add(d.counts, CNT_LONG, n_long); spread_add(d.counts, CNT_LONG_ROWS, n_long_rows);
     }
-}
-
-// the long queries, in query order: list_q[j] and the start of query list_q[j] among the long rows
-__global__ void subject_list_kernel(const uint32_t* __restrict__ long_flag, const uint32_t* __restrict__ flag_pos,
-                                    const uint32_t* __restrict__ row_start, uint64_t n_queries, uint32_t n_long,
-                                    uint32_t* __restrict__ list_q, uint32_t* __restrict__ list_start) {
-    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= n_queries || !long_flag[q]) return;
-    const uint32_t j = flag_pos[q];
-    if (j < n_long) { list_q[j] = (uint32_t)q; list_start[j] = row_start[q]; }
 }
 
 __global__ void subject_table_init(Slot* __restrict__ tab, uint64_t n_slots) {
@@ -181,27 +159,9 @@ __global__ __launch_bounds__(SUBJ_BLOCK) void subject_lookup_kernel(LongDev d) {
         if (!found) atomicOr(&d.counts[CNT_ERROR], 1ull);
         d.keep[row] = keep ? 1u : 0u;
         if (found && !keep && __hip_atomic_load(&d.thinned[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u && atomicExch(&d.thinned[j], 1u) == 0u)
-            atomicAdd(&d.counts[CNT_THINNED + blockIdx.x % SUBJ_SPREAD], 1ull);
+            spread_add(d.counts, CNT_THINNED, 1ull);
     }
-    const unsigned long long kept = __ballot(keep);
-    if (kept && (threadIdx.x & 63u) == (uint32_t)__ffsll((long long)kept) - 1u)
-        atomicAdd(&d.counts[CNT_KEPT + blockIdx.x % SUBJ_SPREAD], (unsigned long long)__popcll(kept));
-}
-
-// seg_off[q] -> the kept rows before it: scan[min(seg_off[q], n_hits)], the total as the last entry
-__global__ void subject_offsets_kernel(unsigned long long* __restrict__ seg_off, uint64_t n_queries, const uint32_t* __restrict__ scan,
-                                       uint64_t n_hits) {
-    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q > n_queries) return;
-    const unsigned long long o = seg_off[q];
-    seg_off[q] = scan[q == n_queries || o > n_hits ? n_hits : o];
-}
-
-__global__ __launch_bounds__(SUBJ_BLOCK) void subject_count_marker(const uint32_t* __restrict__ tax, uint64_t n, uint32_t marker,
-                                                                    unsigned long long* __restrict__ count) {
-    const uint64_t i = (uint64_t)blockIdx.x * SUBJ_BLOCK + threadIdx.x;
-    const unsigned long long m = __ballot(i < n && tax[i] == marker);
-    if (m && (threadIdx.x & 63u) == 0) atomicAdd(&count[blockIdx.x % SUBJ_SPREAD], (unsigned long long)__popcll(m));
+    spread_add_ballot(d.counts, CNT_KEPT, keep);
 }
 
 uint64_t table_capacity(uint64_t long_rows) { uint64_t c = 2; while (c < 2 * long_rows) c <<= 1; return c; }
@@ -210,12 +170,6 @@ uint64_t table_capacity(uint64_t long_rows) { uint64_t c = 2; while (c < 2 * lon
 
 int check_subject_best(const blu_subject_best* sel) {
     if (sel && (sel->mask & ~BLU_SUBJECT_BEST_PER_QUERY)) { set_error("best hit per subject: unknown bits in the mask"); return BLU_ERR_INVALID_ARG; }
-    return BLU_OK;
-}
-
-int check_subject_counts(uint64_t n_hits, uint64_t n_queries) {
-    if (n_hits >= (1ull << 32)) { set_error("best hit per subject: n_hits must be below 2^32"); return BLU_ERR_INVALID_ARG; }
-    if (n_queries >= (1ull << 32)) { set_error("best hit per subject: n_queries must be below 2^32"); return BLU_ERR_INVALID_ARG; }
     return BLU_OK;
 }
 
@@ -230,42 +184,35 @@ int subject_keep_device(const int32_t* d_bitscore, const uint32_t* d_acc_rank, c
     const uint64_t waves = (n_queries + SUBJ_QPW - 1) / SUBJ_QPW;
     const uint64_t blocks = (waves + SUBJ_BLOCK / 64 - 1) / (SUBJ_BLOCK / 64);
     unsigned long long* d_counts = nullptr;
-    uint32_t *d_len = nullptr, *d_flag = nullptr;
+    uint32_t *d_len = nullptr, *d_flag = nullptr;             // [n_queries + 1]: a pad word for the scans
     unsigned long long counts[CNT_WORDS];
     HIP_CHECK(pol, mem.alloc(&d_counts, sizeof counts, "counts"));
     HIP_CHECK(pol, mem.alloc(&d_len, (n_queries + 1) * 4, "long lengths"));
     HIP_CHECK(pol, mem.alloc(&d_flag, (n_queries + 1) * 4, "long flags"));
     HIP_CHECK(pol, hipMemsetAsync(d_counts, 0, sizeof counts, nullptr));
     HIP_CHECK(pol, hipMemsetAsync(d_len + n_queries, 0, 4, nullptr));
-    HIP_CHECK(pol, hipMemsetAsync(d_flag + n_queries, 0, 4, nullptr));
     SubjDev d{};
     d.bitscore = d_bitscore; d.acc_rank = d_acc_rank; d.seg_off = (const unsigned long long*)d_seg_off; d.n_hits = n_hits; d.n_queries = n_queries;
     d.keep = d_keep; d.long_len = d_len; d.long_flag = d_flag; d.counts = d_counts;
     hipLaunchKernelGGL(subject_short_kernel, dim3((unsigned)blocks), dim3(SUBJ_BLOCK), 0, nullptr, d);
     HIP_CHECK(pol, hipGetLastError());
     HIP_CHECK(pol, hipMemcpy(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost));
-    uint64_t n_long = 0, long_rows = 0;
-    for (uint32_t k = 0; k < SUBJ_SPREAD; ++k) { n_long += counts[CNT_LONG + k]; long_rows += counts[CNT_LONG_ROWS + k]; }
+    const uint64_t n_long = spread_sum(counts, CNT_LONG), long_rows = spread_sum(counts, CNT_LONG_ROWS);
     if (n_long) {
         if (long_rows > n_hits) { set_error("best hit per subject: the segments overlap (their rows sum to more than n_hits)"); return BLU_ERR_INVALID_ARG; }
         const uint64_t cap = table_capacity(long_rows);
-        uint32_t *d_fpos = nullptr, *d_rstart = nullptr, *d_list_q = nullptr, *d_list_start = nullptr, *d_thinned = nullptr;
+        uint32_t *d_rstart = nullptr, *d_list_q = nullptr, *d_list_start = nullptr, *d_thinned = nullptr;
         void* d_tmp = nullptr;
         Slot* d_tab = nullptr;
-        HIP_CHECK(pol, mem.alloc(&d_fpos, (n_queries + 1) * 4, "long positions"));
         HIP_CHECK(pol, mem.alloc(&d_rstart, (n_queries + 1) * 4, "long row starts"));
         HIP_CHECK(pol, mem.alloc(&d_tmp, scan_tmp_bytes_u32(n_queries + 1), "scan work"));
-        HIP_CHECK(pol, mem.alloc(&d_list_q, n_long * 4, "long queries"));
-        HIP_CHECK(pol, mem.alloc(&d_list_start, (n_long + 1) * 4, "long starts"));
         HIP_CHECK(pol, mem.alloc(&d_thinned, n_long * 4, "thinned flags"));
         HIP_CHECK(pol, mem.alloc(&d_tab, cap * sizeof(Slot), "pair table"));
-        HIP_CHECK(pol, exclusive_scan_u32(d_flag, d_fpos, n_queries + 1, d_tmp));
         HIP_CHECK(pol, exclusive_scan_u32(d_len, d_rstart, n_queries + 1, d_tmp));
+        if (const int rc = long_query_list(pol, mem, d_flag, n_queries, n_long, d_rstart, d_tmp, &d_list_q, &d_list_start)) return rc;
         HIP_CHECK(pol, hipMemsetAsync(d_thinned, 0, n_long * 4, nullptr));
         const uint32_t rows32 = (uint32_t)long_rows;
         HIP_CHECK(pol, hipMemcpyAsync(d_list_start + n_long, &rows32, 4, hipMemcpyHostToDevice, nullptr));
-        hipLaunchKernelGGL(subject_list_kernel, grid(n_queries), dim3(256), 0, nullptr, (const uint32_t*)d_flag, (const uint32_t*)d_fpos,
-                           (const uint32_t*)d_rstart, n_queries, (uint32_t)n_long, d_list_q, d_list_start);
         hipLaunchKernelGGL(subject_table_init, grid(cap), dim3(256), 0, nullptr, d_tab, cap);
         LongDev l{};
         l.bitscore = d_bitscore; l.acc_rank = d_acc_rank; l.seg_off = (const unsigned long long*)d_seg_off; l.n_hits = n_hits;
@@ -277,70 +224,11 @@ int subject_keep_device(const int32_t* d_bitscore, const uint32_t* d_acc_rank, c
         HIP_CHECK(pol, hipMemcpy(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost));
         if (counts[CNT_ERROR]) { set_error("best hit per subject: the pair table failed (overlapping segments?)"); return BLU_ERR_INVALID_ARG; }
     }
-    for (uint32_t k = 0; k < SUBJ_SPREAD; ++k) { *n_kept += counts[CNT_KEPT + k]; *n_thinned += counts[CNT_THINNED + k]; }
+    *n_kept = spread_sum(counts, CNT_KEPT); *n_thinned = spread_sum(counts, CNT_THINNED);
     return BLU_OK;
 }
 
-int compact_kept_device(const char* who, SubjectColumns& c, uint64_t n_hits, uint64_t n_queries, const uint32_t* d_keep, bool all_kept, bool rotate,
-                        uint32_t unmatched_marker, uint64_t* n_hits_out, uint64_t* n_unmatched, std::vector<void*>* retired) {
-    HipPolicy pol{who, BLU_ERR_ALLOC};
-    DeviceArena mem(pol);
-    *n_hits_out = n_hits;
-    uint32_t* d_pos = nullptr;
-    unsigned long long* d_cnt = nullptr;
-    HIP_CHECK(pol, mem.alloc(&d_cnt, SUBJ_SPREAD * 8, "unmatched count"));
-    auto count_unmatched = [&](uint64_t n) -> int {
-        if (!n_unmatched) return BLU_OK;
-        unsigned long long cnt[SUBJ_SPREAD];
-        HIP_CHECK(pol, hipMemsetAsync(d_cnt, 0, sizeof cnt, nullptr));
-        if (n) hipLaunchKernelGGL(subject_count_marker, grid(n, SUBJ_BLOCK), dim3(SUBJ_BLOCK), 0, nullptr, (const uint32_t*)*c.tax_desc_row, n, unmatched_marker, d_cnt);
-        HIP_CHECK(pol, hipGetLastError());
-        HIP_CHECK(pol, hipMemcpy(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost));
-        *n_unmatched = 0;
-        for (uint32_t k = 0; k < SUBJ_SPREAD; ++k) *n_unmatched += cnt[k];
-        return BLU_OK;
-    };
-    if (n_hits == 0 || all_kept) return count_unmatched(n_hits);   // every row kept: the columns are not touched
-    void* d_tmp = nullptr;
-    HIP_CHECK(pol, mem.alloc(&d_pos, (n_hits + 1) * 4, "keep positions"));
-    HIP_CHECK(pol, mem.alloc(&d_tmp, scan_tmp_bytes_u32(n_hits + 1), "scan work"));
-    HIP_CHECK(pol, exclusive_scan_u32(d_keep, d_pos, n_hits + 1, d_tmp));
-    uint32_t n_out = 0;
-    HIP_CHECK(pol, hipMemcpy(&n_out, d_pos + n_hits, 4, hipMemcpyDeviceToHost));
-    mem.free(d_tmp);
-    // one column after another through ONE spare buffer.  rotate: the spare becomes the column and the column's
-    // old buffer the next spare (the 8-byte column first, so that every spare is large enough); else the kept rows are copied
-    // back to the front of the caller's buffer
-    void* spare = nullptr;
-    HIP_CHECK(pol, mem.alloc(&spare, std::max<size_t>((size_t)n_out, 1) * 8, "compaction spare"));
-    auto move = [&](auto** col) -> int {
-        using T = std::remove_reference_t<decltype(**col)>;
-        hipError_t e;
-        if constexpr (sizeof(T) == 8) e = compact_column_u64((const unsigned long long*)*col, d_keep, d_pos, (uint32_t)n_hits, n_out, (unsigned long long*)spare);
-        else e = compact_column_u32((const uint32_t*)*col, d_keep, d_pos, (uint32_t)n_hits, n_out, (uint32_t*)spare);
-        HIP_CHECK(pol, e);
-        if (rotate) { void* old = *col; *col = (T*)spare; spare = old; }
-        else HIP_CHECK(pol, hipMemcpyAsync(*col, spare, (size_t)n_out * sizeof(T), hipMemcpyDeviceToDevice, nullptr));
-        return BLU_OK;
-    };
-    if (rotate) mem.release(spare);                  // (from here the spare is one of the caller's buffers or goes to `retired`)
-    int rc = move(c.pident);
-    if (rc == BLU_OK) rc = move(c.bitscore);
-    if (rc == BLU_OK) rc = move(c.align_len);
-    if (rc == BLU_OK) rc = move(c.tax_desc_row);
-    if (rc == BLU_OK) rc = move(c.acc_rank);
-    if (rotate) { if (retired) retired->push_back(spare); else (void)hipFree(spare); }
-    if (rc != BLU_OK) return rc;
-    hipLaunchKernelGGL(subject_offsets_kernel, grid(n_queries + 1), dim3(256), 0, nullptr, c.seg_off, n_queries, (const uint32_t*)d_pos, n_hits);
-    HIP_CHECK(pol, hipGetLastError());
-    *n_hits_out = n_out;
-    rc = count_unmatched(n_out);
-    if (rc != BLU_OK) return rc;
-    HIP_CHECK(pol, hipStreamSynchronize(nullptr));
-    return BLU_OK;
-}
-
-int subject_best_device(SubjectColumns& c, uint64_t n_hits, uint64_t n_queries, bool rotate, uint32_t unmatched_marker,
+int subject_best_device(HitColumns& c, uint64_t n_hits, uint64_t n_queries, bool rotate, uint32_t unmatched_marker,
                         uint64_t* n_hits_out, uint64_t* n_unmatched, uint64_t* n_thinned, std::vector<void*>* retired, bool count_only) {
     HipPolicy pol{"best hit per subject", BLU_ERR_ALLOC};
     DeviceArena mem(pol);
@@ -358,9 +246,9 @@ int subject_best_device(SubjectColumns& c, uint64_t n_hits, uint64_t n_queries, 
 
 int subject_best_hits(DeviceHits& dev, blu_subject_best_stats* stats, uint64_t* unmatched) {
     *stats = blu_subject_best_stats{dev.n_hits, dev.n_hits, dev.n_queries, 0};
-    if (int rc = check_subject_counts(dev.n_hits, dev.n_queries)) return rc;
-    if (hipSetDevice(dev.device) != hipSuccess) { (void)hipGetLastError(); set_error("best hit per subject: hipSetDevice(%d) failed", dev.device); return BLU_ERR_NO_DEVICE; }
-    SubjectColumns c{&dev.bitscore, &dev.align_len, &dev.tax_desc_row, &dev.acc_rank, &dev.pident, dev.seg_off};
+    if (int rc = check_hit_counts("best hit per subject", dev.n_hits, dev.n_queries)) return rc;
+    if (int rc = use_device("best hit per subject", dev.device)) return rc;
+    HitColumns c = columns_of(dev);
     uint64_t n_out = dev.n_hits, n_thinned = 0;
     const int rc = subject_best_device(c, dev.n_hits, dev.n_queries, true, BLU_UNMATCHED_TAXID, &n_out, unmatched, &n_thinned, &dev.trash, false);
     if (rc != BLU_OK) return rc;
@@ -378,11 +266,11 @@ extern "C" {
 int blu_hits_subject_keep(int device, const int32_t* bitscore, const uint32_t* acc_rank, const uint64_t* seg_off, uint64_t n_hits,
                           uint64_t n_queries, int on_device, void* stream, uint32_t* keep_out, blu_subject_best_stats* stats) {
     if (stats) *stats = blu_subject_best_stats{n_hits, 0, n_queries, 0};
-    if ((n_hits && (!bitscore || !acc_rank || !keep_out)) || (n_queries && !seg_off)) { set_error("blu_hits_subject_keep: null array with a non-zero count"); return BLU_ERR_INVALID_ARG; }
-    int rc = check_subject_counts(n_hits, n_queries);
+    if ((n_hits && (!bitscore || !acc_rank || !keep_out)) || (n_queries && !seg_off)) return refuse_null_array("blu_hits_subject_keep");
+    int rc = check_hit_counts("best hit per subject", n_hits, n_queries);
     if (rc != BLU_OK) return rc;
     if (n_hits == 0) return BLU_OK;
-    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); set_error("blu_hits_subject_keep: hipSetDevice(%d) failed", device); return BLU_ERR_NO_DEVICE; }
+    if ((rc = use_device("blu_hits_subject_keep", device)) != BLU_OK) return rc;
     HipPolicy pol{"blu_hits_subject_keep", BLU_ERR_ALLOC};
     uint64_t n_kept = 0, n_thinned = 0;
     if (on_device) {
@@ -394,15 +282,12 @@ int blu_hits_subject_keep(int device, const int32_t* bitscore, const uint32_t* a
         int32_t* d_bs = nullptr;
         uint32_t *d_acc = nullptr, *d_keep = nullptr;
         uint64_t* d_seg = nullptr;
-        HIP_CHECK(pol, mem.alloc(&d_bs, n_hits * 4, "bit-scores"));
-        HIP_CHECK(pol, mem.alloc(&d_acc, n_hits * 4, "accession ranks"));
+        HIP_CHECK(pol, mem.upload(&d_bs, bitscore, n_hits, "bit-scores"));
+        HIP_CHECK(pol, mem.upload(&d_acc, acc_rank, n_hits, "accession ranks"));
         HIP_CHECK(pol, mem.alloc(&d_keep, n_hits * 4, "keep words"));
-        HIP_CHECK(pol, mem.alloc(&d_seg, (n_queries + 1) * 8, "offsets"));
-        HIP_CHECK(pol, hipMemcpy(d_bs, bitscore, n_hits * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(pol, hipMemcpy(d_acc, acc_rank, n_hits * 4, hipMemcpyHostToDevice));
-        if (n_queries) HIP_CHECK(pol, hipMemcpy(d_seg, seg_off, (n_queries + 1) * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(pol, mem.upload(&d_seg, seg_off, n_queries ? n_queries + 1 : 0, "offsets"));
         rc = subject_keep_device(d_bs, d_acc, d_seg, n_hits, n_queries, d_keep, &n_kept, &n_thinned);
-        if (rc == BLU_OK) HIP_CHECK(pol, hipMemcpy(keep_out, d_keep, n_hits * 4, hipMemcpyDeviceToHost));
+        if (rc == BLU_OK) HIP_CHECK(pol, mem.download(keep_out, d_keep, n_hits));
     }
     if (rc != BLU_OK) return rc;
     if (stats) { stats->n_kept = n_kept; stats->n_thinned = n_thinned; }
@@ -416,55 +301,25 @@ int blu_hits_subject_best(int device, int32_t* bitscore, int32_t* align_len, uin
     if (n_hits_out) *n_hits_out = n_hits;
     int rc = check_subject_best(sel);
     if (rc != BLU_OK) return rc;
-    if ((n_hits && (!bitscore || !align_len || !tax_desc_row || !acc_rank || !pident)) || (n_queries && !seg_off)) {
-        set_error("blu_hits_subject_best: null array with a non-zero count");
-        return BLU_ERR_INVALID_ARG;
-    }
-    if ((rc = check_subject_counts(n_hits, n_queries)) != BLU_OK) return rc;
+    if ((n_hits && (!bitscore || !align_len || !tax_desc_row || !acc_rank || !pident)) || (n_queries && !seg_off)) return refuse_null_array("blu_hits_subject_best");
+    if ((rc = check_hit_counts("best hit per subject", n_hits, n_queries)) != BLU_OK) return rc;
     const bool active = sel && sel->mask != 0;
     if (!active && !on_device) {                     // no selection: the table as it is (no device needed)
         if (n_unmatched_out) { *n_unmatched_out = 0; for (uint64_t i = 0; i < n_hits; ++i) *n_unmatched_out += tax_desc_row[i] == unmatched_marker; }
         return BLU_OK;
     }
-    if (on_device && (((uintptr_t)bitscore | (uintptr_t)align_len | (uintptr_t)tax_desc_row | (uintptr_t)acc_rank | (uintptr_t)pident) & 15u)) {
-        set_error("blu_hits_subject_best: device columns must be 16-byte aligned");
-        return BLU_ERR_INVALID_ARG;
-    }
-    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); set_error("blu_hits_subject_best: hipSetDevice(%d) failed", device); return BLU_ERR_NO_DEVICE; }
+    HitColumns c{&bitscore, &align_len, &tax_desc_row, &acc_rank, &pident, (unsigned long long*)seg_off};
+    if (on_device && (rc = check_aligned16("blu_hits_subject_best", c)) != BLU_OK) return rc;
+    if ((rc = use_device("blu_hits_subject_best", device)) != BLU_OK) return rc;
     HipPolicy pol{"blu_hits_subject_best", BLU_ERR_ALLOC};
     uint64_t n_out = n_hits, n_unmatched = 0, n_thinned = 0;
     if (on_device) {
         HIP_CHECK(pol, hipStreamSynchronize((hipStream_t)stream));
-        SubjectColumns c{&bitscore, &align_len, &tax_desc_row, &acc_rank, &pident, (unsigned long long*)seg_off};
         rc = subject_best_device(c, n_hits, n_queries, false, unmatched_marker, &n_out, &n_unmatched, &n_thinned, nullptr, !active);
     } else {
-        DeviceArena mem(pol);
-        int32_t *d_bs = nullptr, *d_aln = nullptr;
-        uint32_t *d_tax = nullptr, *d_acc = nullptr;
-        double* d_pid = nullptr;
-        unsigned long long* d_seg = nullptr;
-        HIP_CHECK(pol, mem.alloc(&d_bs, n_hits * 4, "bit-scores"));
-        HIP_CHECK(pol, mem.alloc(&d_aln, n_hits * 4, "alignment lengths"));
-        HIP_CHECK(pol, mem.alloc(&d_tax, n_hits * 4, "taxonomy rows"));
-        HIP_CHECK(pol, mem.alloc(&d_acc, n_hits * 4, "accession ranks"));
-        HIP_CHECK(pol, mem.alloc(&d_pid, n_hits * 8, "identities"));
-        HIP_CHECK(pol, mem.alloc(&d_seg, (n_queries + 1) * 8, "offsets"));
-        HIP_CHECK(pol, hipMemcpy(d_bs, bitscore, n_hits * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(pol, hipMemcpy(d_aln, align_len, n_hits * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(pol, hipMemcpy(d_tax, tax_desc_row, n_hits * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(pol, hipMemcpy(d_acc, acc_rank, n_hits * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(pol, hipMemcpy(d_pid, pident, n_hits * 8, hipMemcpyHostToDevice));
-        if (n_queries) HIP_CHECK(pol, hipMemcpy(d_seg, seg_off, (n_queries + 1) * 8, hipMemcpyHostToDevice));
-        SubjectColumns c{&d_bs, &d_aln, &d_tax, &d_acc, &d_pid, d_seg};
-        rc = subject_best_device(c, n_hits, n_queries, false, unmatched_marker, &n_out, &n_unmatched, &n_thinned, nullptr, false);
-        if (rc == BLU_OK && n_out < n_hits) {
-            HIP_CHECK(pol, hipMemcpy(bitscore, d_bs, n_out * 4, hipMemcpyDeviceToHost));
-            HIP_CHECK(pol, hipMemcpy(align_len, d_aln, n_out * 4, hipMemcpyDeviceToHost));
-            HIP_CHECK(pol, hipMemcpy(tax_desc_row, d_tax, n_out * 4, hipMemcpyDeviceToHost));
-            HIP_CHECK(pol, hipMemcpy(acc_rank, d_acc, n_out * 4, hipMemcpyDeviceToHost));
-            HIP_CHECK(pol, hipMemcpy(pident, d_pid, n_out * 8, hipMemcpyDeviceToHost));
-            if (n_queries) HIP_CHECK(pol, hipMemcpy(seg_off, d_seg, (n_queries + 1) * 8, hipMemcpyDeviceToHost));
-        }
+        rc = with_staged_columns(pol, c, n_hits, n_queries, nullptr, 0, &n_out, [&](HitColumns& d, const uint32_t*, uint64_t* n) {
+            return subject_best_device(d, n_hits, n_queries, false, unmatched_marker, n, &n_unmatched, &n_thinned, nullptr, false);
+        });
     }
     if (rc != BLU_OK) return rc;
     if (n_hits_out) *n_hits_out = n_out;

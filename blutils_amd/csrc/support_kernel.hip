@@ -20,8 +20,7 @@
 #include <cstring>
 #include <vector>
 
-#include "blu_internal.h"
-#include "ingest_prims.h"
+#include "hit_pass.h"
 
 namespace blu {
 namespace {
@@ -47,10 +46,6 @@ struct SupportDev {
 
 __device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int32_t wave_max32(int32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
     return v;
 }
 
@@ -102,9 +97,8 @@ __global__ __launch_bounds__(SB) void support_counts(SupportDev d) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t q = (uint64_t)blockIdx.x * (SB / 64) + (threadIdx.x >> 6);
     if (q >= d.n_queries) return;                    // (wave-uniform)
-    uint64_t s0 = d.seg_off[q], s1 = d.seg_off[q + 1];
-    if (s1 > d.n_hits) s1 = d.n_hits;                // (offsets that run past the table read nothing outside it)
-    if (s0 > s1) s0 = s1;
+    uint64_t s0, s1;
+    segment_of(d.seg_off, q, d.n_hits, &s0, &s1);
     const uint4* rp = reinterpret_cast<const uint4*>(d.recs + q);
     const uint4 ra = rp[0];
     const uint2 rb = *reinterpret_cast<const uint2*>(rp + 1);
@@ -234,21 +228,15 @@ int blu_consensus_support(const blu_taxonomy* tax, const blu_hits* hits, const b
             for (uint64_t i = 0; i < nh; ++i) gathered[i] = src[i * stride];
             src = gathered.data();
         }
-        HIP_CHECK(pol, mem.alloc(&d_recs, nq * sizeof(blu_result), "records"));
-        HIP_CHECK(pol, mem.alloc(&d_seg, (nq + 1) * 8, "offsets"));
-        HIP_CHECK(pol, mem.alloc(&d_bs, nh * 4, "bit-scores"));
-        HIP_CHECK(pol, mem.alloc(&d_rows, nh * 4, "rows"));
+        HIP_CHECK(pol, mem.upload(&d_recs, results, nq, "records"));
+        HIP_CHECK(pol, mem.upload(&d_seg, hits->seg_off, nq + 1, "offsets"));
+        HIP_CHECK(pol, mem.upload(&d_bs, hits->bitscore, nh, "bit-scores"));
+        HIP_CHECK(pol, mem.upload(&d_rows, src, nh, "rows"));
         HIP_CHECK(pol, mem.alloc(&d_out, nq * sizeof(blu_support), "counts"));
-        HIP_CHECK(pol, hipMemcpy(d_recs, results, nq * sizeof(blu_result), hipMemcpyHostToDevice));
-        HIP_CHECK(pol, hipMemcpy(d_seg, hits->seg_off, (nq + 1) * 8, hipMemcpyHostToDevice));
-        if (nh) {
-            HIP_CHECK(pol, hipMemcpy(d_bs, hits->bitscore, nh * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(pol, hipMemcpy(d_rows, src, nh * 4, hipMemcpyHostToDevice));
-        }
         SupportInput in{d_recs, nq, d_seg, d_bs, d_rows, 1u, nh};
         const int rc = support_device(tax, in, d_out);
         if (rc != BLU_OK) return rc;
-        HIP_CHECK(pol, hipMemcpy(out, d_out, nq * sizeof(blu_support), hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, mem.download(out, d_out, nq));
         return BLU_OK;
     } catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
 }

@@ -371,3 +371,14 @@ def test_apply_compacts_as_the_reference_says(tree):
     # at 100 % nothing moves
     out, n_un, c = engine.cover_apply_host(tree.tax, t.seg, t.bs, aln, np.array(t.desc, np.uint32), acc, pid, 100000, row_map=True)
     assert c["n_kept"] == n_hits and out["bitscore"].tolist() == t.bs and out["seg_off"].tolist() == t.seg
+    # no query over three rows, engine row ids and no map: no segment names a row, so both routes drop them all
+    bs3, ids3 = t.bs[:3], np.array(t.ids[:3], np.uint32)
+    want_v, _, want_c = ref.keep([0], bs3, t.lin[:3], 80000)
+    off, cols = sb.compact([0], want_v, bs3, aln[:3], ids3, acc[:3], pid[:3])
+    out, n_un, c = engine.cover_apply_host(tree.tax, [0], bs3, aln[:3], ids3, acc[:3], pid[:3], 80000)
+    dev = [torch.tensor(np.array(x), device="cuda") for x in (np.zeros(1, np.int64), np.array(bs3, np.int32), aln[:3], ids3.view(np.int32),
+                                                               acc[:3].view(np.int32), pid[:3])]
+    k, n_un_d, c_d = engine.cover_apply_device(tree.tax, *dev, 80000)
+    assert c == c_d == want_c and k == want_c["n_kept"] == 0 and n_un == n_un_d == 0
+    assert out["seg_off"].tolist() == off == dev[0].cpu().tolist() == [0]
+    assert all(out[name].tolist() == col == [] for name, col in zip(("bitscore", "align_len", "tax_row", "acc_rank", "pident"), cols))

@@ -132,6 +132,7 @@ def test_query_counts_around_wave_and_block_tails():
             lens[nq // 2] = 70                                           # one long query among them
         check(*_table(rng, lens.tolist(), n_subjects=3))
     check([0], [5, 4, 3], [1, 1, 1], tiled=False)                        # no query over rows: every verdict 0
+    check([0], [5, 4, 3], [1, 1, 1])                                     # ... and the compaction drops every row, on both routes
 
 
 def test_placement_of_duplicates():
