@@ -1,4 +1,4 @@
-// Types shared by the CPU ingest (pipeline.cpp) and the GPU ingest (ingest_gpu.hip).
+// Types shared by the CPU ingest (pipeline_ingest.cpp) and the GPU ingest (ingest_gpu.hip).
 #ifndef BLU_INGEST_H
 #define BLU_INGEST_H
 
@@ -32,7 +32,7 @@ struct NoInitAlloc : std::allocator<T> {
 template <class T> using Column = std::vector<T, NoInitAlloc<T>>;
 
 // taxid -> row of the taxonomy table; open addressing, 16-byte entries (one cache line touched per lookup: the join
-// runs once per hit row).  A duplicated taxid is refused by the loaders (pipeline.cpp).
+// runs once per hit row).  A duplicated taxid is refused by the loaders (pipeline_taxdb.cpp).
 struct TaxidMap {
     struct E { int64_t key; uint32_t val, used; };
     std::vector<E> tab = std::vector<E>(1024, E{0, 0, 0});
@@ -129,7 +129,7 @@ struct TopTable {
 
 
 // Taxon filter as the parsers read it: one code per taxonomy row, made on the host from the lineages
-// (pipeline.cpp: taxon_codes).  0 = the row passes; k = the first exclude element in list order its lineage holds is k - 1;
+// (pipeline_ingest.cpp: taxon_codes).  0 = the row passes; k = the first exclude element in list order its lineage holds is k - 1;
 // TAXON_NOT_ONLY = it holds none of the only list (exclude wins over only).  The parser that ran leaves the counts here.
 constexpr uint16_t TAXON_NOT_ONLY = 0xFFFF;
 struct TaxonCodes {
@@ -154,7 +154,7 @@ struct TaxonCodes {
 // thresholds, and the counts are left in *taxa.  Rows are dropped as under flt; either may be given without the other.
 int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, std::string* why,
                   const blu_hit_filter* flt = nullptr, TaxonCodes* taxa = nullptr);
-// an f64 field as the host parser types it (pipeline.cpp: parse_f64 — strtod's value); false: not a number.  The GPU ingest
+// an f64 field as the host parser types it (pipeline_ingest.cpp: parse_f64 — strtod's value); false: not a number.  The GPU ingest
 // decides with it the e-values its own arithmetic leaves open.
 bool parse_f64_field(const char* p, size_t n, double* out);
 int download_columns(HitTable& ht);

@@ -1,5 +1,5 @@
 // GPU ingest of BLAST outfmt-6 text ("GPU-side parser"): the whole file goes to HBM once and comes back as
-// the grouped SoA columns the engine reads.  It produces exactly what the CPU ingest in pipeline.cpp produces
+// the grouped SoA columns the engine reads.  It produces exactly what the CPU ingest in pipeline_ingest.cpp produces
 // (reference: build_consensus_identities/mod.rs:134-244,329-373 — 13 tab-separated columns, rows regrouped by query
 // in first-appearance order with file order kept inside a query, bit_score truncated toward zero, left join on the
 // taxid), for files in the plain form BLAST writes; any other file (quotes, empty lines, odd numbers) is handed back

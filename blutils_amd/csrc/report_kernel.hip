@@ -1,7 +1,7 @@
 // Taxon abundance report (include/blu_consensus.h: blu_consensus_report): the per-query records of the engine ->
 // the distinct taxonomy paths with their direct counts, on the device.
 //
-// A query's path is exactly what the renderer writes as `taxonomy` (pipeline.cpp, Renderer::lineage): the levels j of
+// A query's path is exactly what the renderer writes as `taxonomy` (pipeline_render.cpp, Renderer::lineage): the levels j of
 // the lineage row of tax_row[ref_row] whose bit is set in level_mask.  Paths are interned in one open-addressing table
 // keyed by (parent path id << 32 | node id): the slot a key lands in IS the path id, so a path's parent is named by
 // its key and nothing else has to be stored.  Every query walks its own levels; a probe that finds its key is a load
@@ -409,6 +409,7 @@ int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* ou
         paths.resize(n_paths);
         if (n_paths) HIP_CHECK(pol, hipMemcpy(paths.data(), d_paths, n_paths * sizeof(blu_report_path), hipMemcpyDeviceToHost));
         float ms = 0;
+        HIP_CHECK(pol, hipEventSynchronize(ev1));   // (no path came back: no copy has waited for the device yet)
         HIP_CHECK(pol, hipEventElapsedTime(&ms, ev0, ev1));
         out->t_device_ms = ms;
     }
@@ -545,6 +546,7 @@ int sample_table_device(const blu_taxonomy* tax, const ReportInput& in, const ui
         if (n_cells) HIP_CHECK(pol, hipMemcpy(cells.data(), d_cells, n_cells * sizeof(blu_sample_cell), hipMemcpyDeviceToHost));
         if (n_samples) HIP_CHECK(pol, hipMemcpy(fixed.data(), d_fixed, fixed.size() * 8, hipMemcpyDeviceToHost));
         float ms = 0;
+        HIP_CHECK(pol, hipEventSynchronize(ev.ev1));   // (no path, cell or sample came back: no copy has waited for the device yet)
         HIP_CHECK(pol, hipEventElapsedTime(&ms, ev.ev0, ev.ev1));
         out->t_device_ms = ms;
     }

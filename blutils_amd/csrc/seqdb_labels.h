@@ -1,6 +1,6 @@
 // The labels of `build-db sintax` / `build-db dada2` (DESIGN.md "Labelled FASTA export"): one per row of the taxonomies
 // file, rendered on the host once per call.  render_label is the rule itself (seqdb_labels.cpp: no I/O, no device);
-// load_label_set reads the taxonomies file with the consensus use-case's loader and applies it to every row (pipeline.cpp).
+// load_label_set reads the taxonomies file with the consensus use-case's loader and applies it to every row (pipeline_taxdb.cpp).
 #ifndef BLU_SEQDB_LABELS_H
 #define BLU_SEQDB_LABELS_H
 

@@ -1,4 +1,4 @@
-"""Byte-level edge cases for the BLAST table ingest (csrc/ingest_gpu.hip, csrc/pipeline.cpp): the tables, what each claims
+"""Byte-level edge cases for the BLAST table ingest (csrc/ingest_gpu.hip, csrc/pipeline_ingest.cpp): the tables, what each claims
 about itself and which parser must end up reading it.  Test infrastructure: deterministic (fixed seeds), no GPU and no product
 code; the expected columns come from tests/ingest_reference.py (str.split, float(), int()).
 

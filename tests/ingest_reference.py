@@ -1,7 +1,7 @@
 """Independent reading of an outfmt-6 table + blutils DB JSON, written with nothing but Python's own `str.split`,
 `float()` and `int()`: the expected value of every SoA column the ingest produces, and of the checksum
 `blu_ingest_only[_on]` reports over them.  Test infrastructure — shares no code with either product parser
-(csrc/pipeline.cpp, csrc/ingest_gpu.hip).
+(csrc/pipeline_ingest.cpp, csrc/ingest_gpu.hip).
 
 What the columns are (reference: core/src/use_cases/build_consensus_identities/mod.rs):
   * 13 tab-separated fields, no header; schema query:str, subject_accession:str, subject_taxid:i64, perc_identity:f64,

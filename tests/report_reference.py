@@ -1,6 +1,6 @@
 """Independent restatement of the taxon abundance report (DESIGN.md §12, §1 of its issue) from a parsed document's
 `results`, in plain dicts.  It does not import the product's report code: the product (blutils_amd/report.py on the host,
-csrc/report_kernel.hip + pipeline.cpp on the GPU path) is compared against this."""
+csrc/report_kernel.hip + pipeline.cpp, pipeline_render.cpp on the GPU path) is compared against this."""
 import re
 
 _FIELD = re.compile(r"size=([0-9]+)")

@@ -1,6 +1,6 @@
 """Independent restatement of the per-sample table (DESIGN.md §13, §1 of its issue) from a parsed document's `results`, in
 plain dicts.  It does not import the product: the product (blutils_amd/report.py on the host, csrc/report_kernel.hip +
-pipeline.cpp on the GPU path) is compared against this."""
+pipeline.cpp, pipeline_render.cpp on the GPU path) is compared against this."""
 import re
 
 _SAMPLE = re.compile(r"sample=(.+)", re.S)
