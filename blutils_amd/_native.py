@@ -17,9 +17,10 @@ EXPORTS = (
     "blu_consensus_report", "blu_report_free", "blu_dev_exclusive_scan", "blu_dev_radix_sort_pairs", "blu_dev_line_index",
     "blu_consensus_sample_table", "blu_sample_table_free", "blu_consensus_support", "blu_hits_score_band",
     "blu_hits_subject_keep", "blu_hits_subject_best", "blu_hits_cover_keep", "blu_hits_cover_apply",
+    "blu_consensus_sample_table_counts",
 )
 # include/blu_pipeline.h
-PIPELINE_EXPORTS = ("blu_build_consensus", "blu_build_consensus_identities", "blu_build_consensus_identities_cfg",
+PIPELINE_EXPORTS = ("blu_build_consensus", "blu_build_consensus_with", "blu_build_consensus_identities", "blu_build_consensus_identities_cfg",
                     "blu_build_consensus_identities_to_file", "blu_free_text", "blu_custom_taxon_from_file", "blu_ingest_only",
                     "blu_ingest_only_on", "blu_ingest_columns_on", "blu_ingest_columns_selected", "blu_ingest_columns_free",
                     "blu_last_ingest_path", "blu_last_min_cover_stats", "blu_db_cache_build", "blu_taxdb_build", "blu_seqdb_export", "blu_qiime_taxonomy_tsv",

@@ -230,7 +230,7 @@ def run_blast_and_build_consensus(input_sequences: str, input_taxonomies: str, b
                                   lenient: bool = False, report_path: Optional[str] = None, report_weight: str = "one",
                                   sample_table_path: Optional[str] = None, hit_filter=None, filter_stats: Optional[dict] = None,
                                   support_table_path: Optional[str] = None, taxon_filter=None, score_band=None,
-                                  best_hit_per_subject: bool = False, min_cover=None):
+                                  best_hit_per_subject: bool = False, min_cover=None, count_table: Optional[str] = None):
     """-> the document text (also written to blutils_out_file with the format's extension, or to stdout).  report_path:
     also the taxon abundance report of the results (pipeline.build_consensus_identities_with_report); sample_table_path:
     also the per-sample table (pipeline.build_consensus_identities_with_tables).  hit_filter (pipeline.HitFilter or a dict):
@@ -243,7 +243,8 @@ def run_blast_and_build_consensus(input_sequences: str, input_taxonomies: str, b
     takes part, selected by the consensus step after the filters and before the band — the BLAST table is still
     written in full; its counts come back in filter_stats["subject_best"].  min_cover (a decimal string above 50, at most 100):
     the top hits outside the deepest taxon that still covers that percentage of a query's top group do not take part
-    (DESIGN.md §20), dropped by the consensus step after the band; its counts come back in filter_stats["min_cover"]."""
+    (DESIGN.md §20), dropped by the consensus step after the band; its counts come back in filter_stats["min_cover"].
+    count_table: a feature x sample count table for the report and the sample table (it needs one of the two); its counts come back in filter_stats["count_table"]."""
     output_file, headers = run_parallel_blast(input_sequences, blast_out_file, blast_config, blast_execution_repo,
                                               overwrite, threads)
     to_file = blutils_out_file is not None
@@ -254,19 +255,19 @@ def run_blast_and_build_consensus(input_sequences: str, input_taxonomies: str, b
             out_format=fmt, device=device, lenient=lenient, parse=False, config=blast_config, report_path=report_path,
             sample_table_path=sample_table_path, report_weight=report_weight, hit_filter=hit_filter,
             taxon_filter=taxon_filter, support_table_path=support_table_path, score_band=score_band,
-            best_hit_per_subject=best_hit_per_subject, min_cover=min_cover)
-    elif sample_table_path is not None:
+            best_hit_per_subject=best_hit_per_subject, min_cover=min_cover, count_table=count_table)
+    elif sample_table_path is not None or (count_table is not None and report_path is None):
         text, stats = pipeline.build_consensus_identities_with_tables(
             output_file, input_taxonomies, blast_config.taxon, strategy, use_taxid, custom_taxon_values, headers=headers,
             out_format=fmt, device=device, lenient=lenient, parse=False, config=blast_config, report_path=report_path,
             sample_table_path=sample_table_path, report_weight=report_weight, hit_filter=hit_filter, taxon_filter=taxon_filter,
-            score_band=score_band, best_hit_per_subject=best_hit_per_subject, min_cover=min_cover)
+            score_band=score_band, best_hit_per_subject=best_hit_per_subject, min_cover=min_cover, count_table=count_table)
     elif report_path is not None:
         text, stats = pipeline.build_consensus_identities_with_report(
             output_file, input_taxonomies, blast_config.taxon, strategy, use_taxid, custom_taxon_values, headers=headers,
             out_format=fmt, device=device, lenient=lenient, parse=False, config=blast_config, report_path=report_path,
             report_weight=report_weight, hit_filter=hit_filter, taxon_filter=taxon_filter, score_band=score_band,
-            best_hit_per_subject=best_hit_per_subject, min_cover=min_cover)
+            best_hit_per_subject=best_hit_per_subject, min_cover=min_cover, count_table=count_table)
     else:
         text, stats = pipeline.build_consensus_identities(output_file, input_taxonomies, blast_config.taxon, strategy, use_taxid,
                                                           custom_taxon_values, headers=headers, out_format=fmt, device=device,

@@ -100,6 +100,24 @@ and --support-table; one pass over the grouped columns on the GPU (csrc/cover_ke
 nothing: the bytes of the run without the flag.  To stderr, after the band's line:
 `min cover: kept K of N lines, narrowed W of Q queries, U left alone`.
 
+    python -m blutils_amd.cli blastn build-consensus ... --count-table FILE (--report FILE | --sample-table FILE)
+    python -m blutils_amd.cli blastn run-with-consensus ... (the same)
+    python -m blutils_amd.cli blastn build-report [BLU_RESULT|-] [--by-sample] --count-table FILE [-o OUT] [-i json|jsonl|yaml]
+
+not in the reference: abundances from an OTU / ASV count table.  In the usual amplicon workflow only the
+representative sequences go through BLAST and their abundances live in a feature x sample table (`vsearch --otutabout`,
+`usearch -otutab`, a DADA2 sequence table, `biom convert --to-tsv`): tab-separated, a header whose first cell is ignored and
+whose other cells name the samples, then one row per representative with one whole-number cell per sample (`12` or `12.0`, below
+2^32); blank lines, and `#` lines without a tab before the header, are skipped.  Rows and queries are joined on their names
+up to the first `;`.  --sample-table then has one column per sample of the header (all of them, ascending bytewise) and a query
+adds its count in each sample to every taxon of its lineage; --report weighs a query by its row sum.  A row without a result —
+a representative BLAST gave no line for — counts as unclassified; a query without a row, two rows or two queries with one key,
+a malformed cell (named by line and column) or a row sum of 2^32 or more fail the run before any file is written.  The counts
+are summed on the GPU from the run's own records (csrc/report_kernel.hip: count_cells); build-report does the same on the host
+from an existing document.  The document and --support-table stay what they are without the flag.  Not together with
+`--report-weight size` / `--weight size`.  To stderr, after the selection's lines:
+`count table: R rows, S samples, J joined to results, M without a result counted as unclassified`.
+
     python -m blutils_amd.cli cache-db TAX.json CACHE [-u]
 
 writes the binary cache of a taxonomies file (not in the reference CLI; pass CACHE as -t afterwards).  
@@ -190,6 +208,10 @@ def build_parser() -> argparse.ArgumentParser:
         sp.add_argument("--support-table", help="also write the per-query support table to this file: how many of a query's "
                                                 "hits lie in the clade it was assigned to, counted on the GPU (not in the "
                                                 "reference CLI)")
+        sp.add_argument("--count-table", metavar="FILE",
+                        help="a feature x sample count table (OTU / ASV table, tab-separated): --report and --sample-table count "
+                             "its abundances, joined to the queries on their names up to the first `;`, instead of what the "
+                             "query names say; needs one of the two, not with --report-weight size (not in the reference CLI)")
         flt = sp.add_argument_group("hit filters (not in the reference CLI)",
                                     "a line of the table takes part only if it meets every threshold given; applied by "
                                     "the parser, on the GPU where it parses")
@@ -242,6 +264,9 @@ def build_parser() -> argparse.ArgumentParser:
     br.add_argument("--weight", default="one", choices=["one", "size"])
     br.add_argument("--by-sample", action="store_true",
                     help="write the taxon x sample table instead of the report (not in the reference CLI)")
+    br.add_argument("--count-table", metavar="FILE",
+                    help="a feature x sample count table: the abundances of the results, joined on their names up to the first "
+                         "`;`, instead of what the query names say; not with --weight size (not in the reference CLI)")
     bt = blastn.add_parser("build-tabular", help="blutils result document -> TSV")
     bt.add_argument("blu_result", nargs="?", default="-")
     bt.add_argument("-o", "--output-file")
@@ -399,6 +424,19 @@ def _say_kept(stats, hit_filter=True) -> None:
     if c:
         print(f"min cover: kept {c['n_kept']} of {c['n_hits']} lines, narrowed {c['n_narrowed']} of {c['n_queries']} queries, "
               f"{c['n_unresolved']} left alone", file=sys.stderr)
+    t = stats.get("count_table") if stats else None
+    if t:
+        print(report.count_table_line(t), file=sys.stderr)
+
+
+def _check_count_table(args) -> None:
+    """--count-table needs a file that uses it, and brings its own counts"""
+    if args.count_table is None:
+        return
+    if args.report is None and args.sample_table is None:
+        raise SystemExit("--count-table needs --report or --sample-table")
+    if args.report_weight == "size":
+        raise SystemExit("--count-table cannot be combined with --report-weight size: the counts are the table's")
 
 
 def _build_db(args) -> int:
@@ -452,6 +490,7 @@ def _run_with_consensus(args) -> int:
         raise SystemExit("Custom taxon values are required when the custom taxon option is selected.")
     stats = {}
     hit_filter, taxon_filter = _hit_filter(args), _taxon_filter(args)
+    _check_count_table(args)
     try:
         blast.run_blast_and_build_consensus(args.query, args.tax_file, args.blast_out_file, args.blutils_out_file, config,
                                             blast.ExecuteBlastnProcRepository(args.blastn), args.force_overwrite,
@@ -461,7 +500,8 @@ def _run_with_consensus(args) -> int:
                                             filter_stats=stats, support_table_path=args.support_table,
                                             taxon_filter=taxon_filter, score_band=_score_band(args),
                                             **({"best_hit_per_subject": True} if args.best_hit_per_subject else {}),
-                                            **({"min_cover": args.min_cover} if args.min_cover is not None else {}))
+                                            **({"min_cover": args.min_cover} if args.min_cover is not None else {}),
+                                            **({"count_table": args.count_table} if args.count_table is not None else {}))
     except blast.BlastError as e:
         raise SystemExit(str(e))
     except _native.BluError as e:
@@ -487,7 +527,13 @@ def main(argv=None) -> int:
         return 0
     if args.sub == "build-report":
         try:
-            report.build_report(args.blu_result, args.output_file, args.input_format, args.weight, by_sample=args.by_sample)
+            if args.count_table is not None and args.weight == "size":
+                raise SystemExit("--count-table cannot be combined with --weight size: the counts are the table's")
+            st = {}
+            report.build_report(args.blu_result, args.output_file, args.input_format, args.weight, by_sample=args.by_sample,
+                                **({"count_table": args.count_table, "count_stats": st} if args.count_table is not None else {}))
+            if st:
+                print(report.count_table_line(st), file=sys.stderr)
         except (tabular.TabularError, report.ReportError) as e:
             raise SystemExit(str(e))
         return 0
@@ -515,6 +561,9 @@ def main(argv=None) -> int:
         extra["best_hit_per_subject"] = True
     if args.min_cover is not None:
         extra["min_cover"] = args.min_cover
+    _check_count_table(args)
+    if args.count_table is not None:
+        extra["count_table"] = args.count_table
     if args.support_table is not None:
         build = functools.partial(pipeline.build_consensus_identities_with_tables, report_path=args.report,
                                   sample_table_path=args.sample_table, report_weight=args.report_weight,

@@ -132,6 +132,16 @@ int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* ou
 // the per-sample table of the same records: sample_of[n_queries] on the device
 int sample_table_device(const blu_taxonomy* tax, const ReportInput& in, const uint32_t* sample_of, uint32_t n_samples,
                         blu_sample_table* out);
+// the per-sample table of the same records from count rows (blu_count_rows on the device, nnz = row_ptr[n_queries] as the
+// caller read it); in.weight is not read
+struct CountRows {
+    const uint64_t* row_ptr;
+    const uint32_t* sample;
+    const uint32_t* count;
+    uint64_t nnz;
+};
+int sample_table_counts_device(const blu_taxonomy* tax, const ReportInput& in, const CountRows& rows, uint32_t n_samples,
+                               blu_sample_table* out);
 
 // support_kernel.hip: the per-query support counts of one run's records (device pointers, d_out too; blu_consensus_support
 // stages host ones).  The engine row of hit i is row_src[i * row_stride].  Returns when d_out is complete.

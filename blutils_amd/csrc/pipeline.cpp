@@ -32,6 +32,7 @@ thread_local blu_min_cover_stats g_cover_pending{}, g_last_min_cover{};
 // Under `size` weighting: w for the queries and extra_w for the headers without hits (weight one: w empty, extra_w all 1).
 int size_weights(const Run& r, std::vector<uint32_t>& w, std::vector<uint32_t>& extra_w) {
     extra_w.assign(r.extra.size(), 1);
+    if (r.counts) { w = r.joined.weight; return BLU_OK; }   // (a count table: the row sums; what is unclassified beside the records: build_report)
     if (r.rq.weight != BLU_REPORT_WEIGHT_SIZE) return BLU_OK;
     w.resize(r.recs.size());
     for (size_t k = 0; k < w.size() + extra_w.size(); ++k) {
@@ -68,14 +69,46 @@ int build_report(const Run& r, std::string& text) {
         rc = blu_consensus_report(r.tax, &h, r.recs.data(), w.empty() ? nullptr : w.data(), nullptr, &rep);
     }
     if (rc != BLU_OK) return rc;
-    for (uint32_t x : extra_w) { rep.unclassified += x; rep.total += x; }
+    if (r.counts) { rep.unclassified += r.joined.unclassified_total; rep.total += r.joined.unclassified_total; }
+    else for (uint32_t x : extra_w) { rep.unclassified += x; rep.total += x; }
     text = render_report(*r.db, rep);
+    return BLU_OK;
+}
+
+// The per-sample table with a count table: the columns are the table's samples, a query adds the counts of its
+// row, and the rows of header-only queries and of no query at all count as unclassified.
+int build_count_sample_table(const Run& r, std::string& text) {
+    const uint64_t nq = r.recs.size();
+    const CountJoin& j = r.joined;
+    const uint32_t ns = (uint32_t)r.counts->samples.size();
+    blu_sample_table tab{};
+    struct Free { blu_sample_table& t; ~Free() { blu_sample_table_free(&t); } } free_tab{tab};
+    int rc;
+    if (r.done_on_device && nq) {
+        HipPolicy pol{"count table", BLU_ERR_ALLOC};
+        DeviceArena mem(pol);
+        uint64_t* d_ptr = nullptr;
+        uint32_t *d_s = nullptr, *d_c = nullptr;
+        HIP_CHECK(pol, mem.upload(&d_ptr, j.row_ptr.data(), j.row_ptr.size(), "row offsets"));
+        HIP_CHECK(pol, mem.upload(&d_s, j.sample.data(), j.sample.size(), "sample ids"));
+        HIP_CHECK(pol, mem.upload(&d_c, j.count.data(), j.count.size(), "counts"));
+        rc = sample_table_counts_device(r.tax, device_records(r, nullptr), CountRows{d_ptr, d_s, d_c, j.sample.size()}, ns, &tab);
+    } else {
+        const blu_hits h = host_rows(r);
+        const blu_count_rows rows{j.row_ptr.data(), j.sample.data(), j.count.data()};
+        rc = blu_consensus_sample_table_counts(r.tax, &h, r.recs.data(), &rows, ns, nullptr, &tab);
+    }
+    if (rc != BLU_OK) return rc;
+    for (uint32_t s = 0; s < ns; ++s) tab.unclassified[s] += j.unclassified[s];
+    std::vector<std::string_view> names(r.counts->samples.begin(), r.counts->samples.end());
+    text = render_sample_table(*r.db, tab, names);
     return BLU_OK;
 }
 
 // The per-sample table (blu_consensus_request.sample_table_path): the samples from the query names and the header-only names
 // (ids in ascending byte order = column order); the header-only queries count as unclassified in their sample.
 int build_sample_table(const Run& r, std::string& text) {
+    if (r.counts) return build_count_sample_table(r, text);
     const std::vector<std::string>& extra = r.extra;
     const uint64_t nq = r.recs.size();
     std::vector<uint32_t> sid(nq + extra.size());
@@ -258,6 +291,10 @@ int Run::start() {
         set_error("report: a path and weight BLU_REPORT_WEIGHT_ONE or BLU_REPORT_WEIGHT_SIZE are needed");
         return BLU_ERR_INVALID_ARG;
     }
+    if (ex && ex->count_table_path) {
+        if (!rq.report_path && !rq.sample_table_path) { set_error("count table: neither a report nor a sample table is asked for"); return BLU_ERR_INVALID_ARG; }
+        if (rq.weight != BLU_REPORT_WEIGHT_ONE) { set_error("count table: the weight must be BLU_REPORT_WEIGHT_ONE (the counts are the table's)"); return BLU_ERR_INVALID_ARG; }
+    }
     g_graveyard.drain();   // (a previous call's memory — device memory too — is back before this one sizes itself against what is free)
     t0 = now_s();
     // (HIP start-up beside the reading of the taxonomy file; BLU_INGEST=cpu callers with no device never get here with one)
@@ -403,6 +440,16 @@ int Run::order() {
     return BLU_OK;
 }
 
+// the count table, when the extras name one: parsed and joined with the results' names before any table is built
+int Run::count_table() {
+    if (!ex || !ex->count_table_path) return BLU_OK;
+    counts = std::make_unique<CountTable>();
+    if (int rc = parse_count_table(ex->count_table_path, *counts)) return rc;
+    if (int rc = join_count_table(*counts, ht->query_names, extra, joined, ex->count_table_stats)) return rc;
+    tr.lap("count table");
+    return BLU_OK;
+}
+
 // the tables that were asked for, from the records while they (on the device path: and the engine rows) are still on the device
 int Run::tables(Document* d) {
     if (rq.report_path) {
@@ -492,13 +539,14 @@ void Run::bury() {
 
 namespace {
 
-int build_document(const blu_consensus_request& rq, Document* document, blu_consensus_outcome* outcome) {
-    Run r(rq, outcome);
+int build_document(const blu_consensus_request& rq, const blu_consensus_extras* ex, Document* document, blu_consensus_outcome* outcome) {
+    Run r(rq, ex, outcome);
     if (int rc = r.start()) return rc;
     if (int rc = r.taxonomy_beside_ingest()) return rc;
     if (int rc = r.select_on_device()) return rc;
     if (int rc = r.engine()) return rc;
     if (int rc = r.order()) return rc;
+    if (int rc = r.count_table()) return rc;
     if (int rc = r.tables(document)) return rc;
     if (int rc = r.render(document)) return rc;
     outcome->stats = r.st;
@@ -516,9 +564,9 @@ int put_tables(const Document& d, const blu_consensus_request& rq) {
 }
 
 // rq.out_path == NULL: the pieces joined into one malloc'd text
-int consensus_to_text(const blu_consensus_request& rq, blu_consensus_outcome* outcome) {
+int consensus_to_text(const blu_consensus_request& rq, const blu_consensus_extras* ex, blu_consensus_outcome* outcome) {
     Document d;
-    int rc = build_document(rq, &d, outcome);
+    int rc = build_document(rq, ex, &d, outcome);
     if (rc != BLU_OK) return rc;
     if ((rc = put_tables(d, rq)) != BLU_OK) return rc;
     const std::vector<size_t> at = d.offsets();
@@ -534,10 +582,10 @@ int consensus_to_text(const blu_consensus_request& rq, blu_consensus_outcome* ou
 }
 
 // (the report and table files, when asked for, are written once the document is out)
-int consensus_to_file(const blu_consensus_request& rq, blu_consensus_outcome* outcome) {
+int consensus_to_file(const blu_consensus_request& rq, const blu_consensus_extras* ex, blu_consensus_outcome* outcome) {
     const char* const out_path = rq.out_path;
     Document d;
-    int rc = build_document(rq, &d, outcome);
+    int rc = build_document(rq, ex, &d, outcome);
     if (rc != BLU_OK) return rc;
     if (getenv("BLU_INGEST_TRACE")) fprintf(stderr, "[pipeline] %-26s %.3f s\n", "tear-down (tables, strings)", now_s() - g_t_body_end);
     if (d.written) return put_tables(d, rq);
@@ -569,8 +617,20 @@ using namespace blu;
 extern "C" {
 
 int blu_build_consensus(const blu_consensus_request* request, blu_consensus_outcome* outcome) {
+    return blu_build_consensus_with(request, nullptr, outcome);
+}
+
+int blu_build_consensus_with(const blu_consensus_request* request, const blu_consensus_extras* extras, blu_consensus_outcome* outcome) {
     g_cover_pending = g_last_min_cover = blu_min_cover_stats{};
     if (!request || !outcome) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    if (extras) {
+        if (extras->struct_size != sizeof(blu_consensus_extras)) {
+            set_error("blu_build_consensus_with: struct_size %u is not a blu_consensus_extras this library knows (%zu bytes)", extras->struct_size,
+                      sizeof(blu_consensus_extras));
+            return BLU_ERR_INVALID_ARG;
+        }
+        if (extras->count_table_stats) *extras->count_table_stats = blu_count_table_stats{};
+    }
     if (request->struct_size != sizeof(blu_consensus_request)) {
         set_error("blu_build_consensus: struct_size %u is not a blu_consensus_request this library knows (%zu bytes)", request->struct_size,
                   sizeof(blu_consensus_request));
@@ -578,7 +638,7 @@ int blu_build_consensus(const blu_consensus_request* request, blu_consensus_outc
     }
     outcome->text = nullptr; outcome->text_len = 0; outcome->stats = blu_pipeline_stats{};   // (outcome->selection: by Selection)
     try {
-        const int rc = request->out_path ? consensus_to_file(*request, outcome) : consensus_to_text(*request, outcome);
+        const int rc = request->out_path ? consensus_to_file(*request, extras, outcome) : consensus_to_text(*request, extras, outcome);
         if (rc == BLU_OK) g_last_min_cover = g_cover_pending;
         return rc;
     }

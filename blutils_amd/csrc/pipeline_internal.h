@@ -2,6 +2,7 @@
 //   pipeline_taxdb.cpp    the taxonomies file: JSON reader, loader, binary cache, label set
 //   pipeline_ingest.cpp   the CPU outfmt-6 parser, the taxon-filter resolver, the ingest entry points
 //   pipeline_render.cpp   JSON / JSONL / YAML records and the text of the three tables
+//   count_table.cpp       the count table of blu_consensus_extras: its parser and its join with the queries
 //   pipeline.cpp          the use-case: one Run from the request to the document
 #ifndef BLU_PIPELINE_INTERNAL_H
 #define BLU_PIPELINE_INTERNAL_H
@@ -325,6 +326,32 @@ struct Document {
     }
 };
 
+// ---- the count table (count_table.cpp) ----------------------------------------------------------------------------
+// The file as parsed: the samples in column order of the sample table (ascending bytewise), the rows in file order as CSR over
+// those sample ids, zeros left out.
+struct CountTable {
+    std::vector<std::string> samples;
+    std::vector<std::string> row_names;
+    std::vector<uint64_t> row_ptr{0};
+    std::vector<uint32_t> sample, count;
+    std::vector<uint64_t> row_sum;
+};
+// The rows as the run's queries carry them (blu_count_rows over the queries with hits), each query's row sum (the report's
+// weight), and what counts as unclassified per sample: the rows of headers without hits and the rows no query has.
+struct CountJoin {
+    std::vector<uint64_t> row_ptr{0};
+    std::vector<uint32_t> sample, count;
+    std::vector<uint32_t> weight;
+    std::vector<uint64_t> unclassified;
+    uint64_t unclassified_total = 0;
+};
+// BLU_ERR_IO / BLU_ERR_PARSE (naming line and column)
+int parse_count_table(const char* path, CountTable& t);
+// joined on the names up to their first ';'; BLU_ERR_INVALID_ARG for a row sum of 2^32 or more, two rows or two queries with one
+// key, and a query (with hits, or `extra`: header-only) no row has
+int join_count_table(const CountTable& t, const std::vector<std::string>& query_names, const std::vector<std::string>& extra,
+                     CountJoin& j, blu_count_table_stats* st);
+
 // ---- the use-case (pipeline.cpp) -----------------------------------------------------------------------------------------------
 struct Item { const std::string* name; int64_t q; };   // one result of the document; q < 0: a header without hits
 
@@ -332,6 +359,7 @@ struct Item { const std::string* name; int64_t q; };   // one result of the docu
 // thread at the end (bury), and whatever of it is left when a step fails.
 struct Run {
     const blu_consensus_request& rq;
+    const blu_consensus_extras* const ex;          // (NULL: none)
     const blu_pipeline_params* const params;
     Selection sel;
     blu_pipeline_stats st{};
@@ -350,9 +378,11 @@ struct Run {
     std::vector<uint32_t> eng_rows;                // (the host path's engine row ids, for the tables)
     std::vector<std::string> extra;                // headers without hits (mod.rs:86-102)
     std::vector<Item> items;                       // results + extra, sorted by query (write_blutils_output.rs:111)
+    std::unique_ptr<CountTable> counts;            // (the count table, when the extras name one, and its join with the queries)
+    CountJoin joined;
 
-    Run(const blu_consensus_request& request, blu_consensus_outcome* outcome)
-        : rq(request), params(request.params), sel(&request.selection, &outcome->selection) {}
+    Run(const blu_consensus_request& request, const blu_consensus_extras* extras, blu_consensus_outcome* outcome)
+        : rq(request), ex(extras), params(request.params), sel(&request.selection, &outcome->selection) {}
     ~Run() { if (warm_up.joinable()) warm_up.join(); if (tax) blu_taxonomy_destroy(tax); }
     // the steps of build_document, in order; each returns an error code
     int start();
@@ -361,6 +391,7 @@ struct Run {
     int engine();
     int engine_on_host_columns();
     int order();
+    int count_table();
     int tables(Document* document);
     int render(Document* document);
     void bury();

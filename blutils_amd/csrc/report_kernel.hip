@@ -227,6 +227,22 @@ __device__ __forceinline__ uint32_t cell_flush(const SampleDev& d, unsigned long
     return cell_add(d, key, w) ? 0u : FLAG_OVERFLOW;
 }
 
+// adds w to a cell of the block's LDS table, or of global memory when that is crowded; the flags of a global add that failed
+__device__ __forceinline__ uint32_t block_cell_add(unsigned long long* s_key, unsigned long long* s_cnt, const SampleDev& d,
+                                                   uint32_t path, uint32_t s, unsigned long long w) {
+    const unsigned long long key = ((unsigned long long)path << 32) | s;
+    uint32_t h = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 53);   // 11 bits: CELL_LDS_SLOTS
+    for (uint32_t p = 0; p < LDS_PROBE; ++p, h = (h + 1) & (CELL_LDS_SLOTS - 1)) {
+        unsigned long long cur = s_key[h];
+        if (cur == REPORT_EMPTY) {
+            cur = atomicCAS(s_key + h, REPORT_EMPTY, key);
+            if (cur == REPORT_EMPTY) cur = key;
+        }
+        if (cur == key) { atomicAdd(s_cnt + h, w); return 0; }
+    }
+    return cell_flush(d, key, w);
+}
+
 __global__ __launch_bounds__(RB) void sample_cells(SampleDev d) {
     __shared__ unsigned long long s_key[CELL_LDS_SLOTS];
     __shared__ unsigned long long s_cnt[CELL_LDS_SLOTS];
@@ -234,19 +250,7 @@ __global__ __launch_bounds__(RB) void sample_cells(SampleDev d) {
     __syncthreads();
     uint32_t flags = 0;
     // block-local table first, global memory when it is crowded (w > 0: a zero weight leaves no cell behind)
-    auto add = [&](uint32_t path, uint32_t s, unsigned long long w) {
-        const unsigned long long key = ((unsigned long long)path << 32) | s;
-        uint32_t h = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 53);   // 11 bits: CELL_LDS_SLOTS
-        for (uint32_t p = 0; p < LDS_PROBE; ++p, h = (h + 1) & (CELL_LDS_SLOTS - 1)) {
-            unsigned long long cur = s_key[h];
-            if (cur == REPORT_EMPTY) {
-                cur = atomicCAS(s_key + h, REPORT_EMPTY, key);
-                if (cur == REPORT_EMPTY) cur = key;
-            }
-            if (cur == key) { atomicAdd(s_cnt + h, w); return; }
-        }
-        flags |= cell_flush(d, key, w);
-    };
+    auto add = [&](uint32_t path, uint32_t s, unsigned long long w) { flags |= block_cell_add(s_key, s_cnt, d, path, s, w); };
     const uint64_t base = (uint64_t)blockIdx.x * (RB * RQ) + threadIdx.x;
     for (uint32_t k = 0; k < RQ; ++k) {
         const uint64_t q = base + (uint64_t)k * RB;
@@ -314,6 +318,111 @@ __global__ void sample_cells_compact(const unsigned long long* __restrict__ keys
     out[at[i]] = c;
 }
 
+// ---- per-sample table from count rows (blu_consensus_sample_table_counts) ------------------------------
+// A query carries a CSR row of (sample, count) pairs instead of one sample and one weight: from none to thousands of them,
+// so a lane per query does not fit.  A wave takes COUNT_Q consecutive queries in turn (a block: 4 x COUNT_Q consecutive
+// queries, whose upper levels meet in the LDS cell table).  Per query the lanes load the lineage row together, lane 0 walks
+// the selected levels through `intern` (a level's key holds its parent's slot, so the walk is serial) and lane k keeps the
+// k-th path id.  The wave then goes through the row floor(64 / levels) non-zeros a step: a lane is one (non-zero, level)
+// pair and adds the count to the cell (path, sample).  The per-sample unclassified / unplaced counts are a one-level row
+// under the two reserved path ids.  All adds are u64 integer adds: exact, whatever the order.
+constexpr uint32_t COUNT_Q = 32;
+constexpr uint32_t COUNT_Q_BLOCK = COUNT_Q * (RB / 64);
+constexpr uint32_t FLAG_BAD_ROW = 8u;
+
+struct CountDev {
+    SampleDev s;                  // s.sample_of and s.r.weight are not read; s.r.ctl[5]: the query of a bad row
+    CountRows rows;
+};
+
+__global__ __launch_bounds__(RB) void count_cells(CountDev d) {
+    __shared__ unsigned long long s_key[CELL_LDS_SLOTS];
+    __shared__ unsigned long long s_cnt[CELL_LDS_SLOTS];
+    for (uint32_t i = threadIdx.x; i < CELL_LDS_SLOTS; i += RB) { s_key[i] = REPORT_EMPTY; s_cnt[i] = 0; }
+    __syncthreads();
+    const ReportDev& r = d.s.r;
+    uint32_t flags = 0;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t q0 = (uint64_t)blockIdx.x * COUNT_Q_BLOCK + (uint64_t)(threadIdx.x >> 6) * COUNT_Q;
+    for (uint32_t k = 0; k < COUNT_Q; ++k) {
+        // (everything up to the pair loop is the same in all 64 lanes)
+        const uint64_t q = q0 + k;
+        if (q >= r.n_queries) break;
+        const uint64_t lo = d.rows.row_ptr[q], hi = d.rows.row_ptr[q + 1];
+        if (lo > hi || hi > d.rows.nnz) { flags |= FLAG_BAD_ROW; if (lane == 0) r.ctl[5] = q; continue; }
+        const uint4* rp = reinterpret_cast<const uint4*>(r.recs + q);
+        const uint4 a = rp[0], b = rp[1];
+        const uint32_t status = a.x & 0xFFu;
+        const uint32_t ref_row = a.w;
+        const unsigned long long mask = (unsigned long long)b.x | ((unsigned long long)b.y << 32);
+        uint32_t mine = CELL_UNCLASSIFIED;      // lane k: the id of the query's k-th path
+        uint32_t n_levels = 1;
+        if (status < 2) {
+            const uint64_t idx = r.by_query ? q : (uint64_t)ref_row;
+            uint32_t row = REPORT_NONE;
+            if (idx < r.n_rows) row = r.row_src[idx * r.row_stride];
+            const uint32_t pos = row & ((1u << BLU_ROW_BITS) - 1u);
+            if (row == BLU_UNMATCHED_TAXID || pos >= r.n_tax) { flags |= FLAG_BAD_RECORD; if (lane == 0) r.ctl[3] = q; continue; }
+            const uint32_t* lin = r.lin + (uint64_t)pos * r.stride;
+            const uint32_t len = min(lin[0] & 0xFFu, r.max_depth);
+            const unsigned long long m = len >= 64 ? mask : mask & ((1ull << len) - 1ull);
+            mine = CELL_UNPLACED;
+            if (m != 0) {
+                const uint32_t node = lane < len ? lin[r.node_base + lane] : 0u;   // lane j: the node of level j
+                uint32_t path = REPORT_NONE;
+                n_levels = 0;
+                for (unsigned long long t = m; t; t &= t - 1ull, ++n_levels) {
+                    const uint32_t nd = __shfl(node, __ffsll(t) - 1, 64);
+                    uint32_t p = REPORT_NONE;
+                    if (lane == 0) p = intern(r, path, nd);
+                    path = __shfl(p, 0, 64);
+                    if (path == REPORT_NONE) break;
+                    if (lane == n_levels) mine = path;
+                }
+                if (path == REPORT_NONE) { flags |= FLAG_OVERFLOW; continue; }
+            }
+        }
+        // lane -> (non-zero `nz` of the step, level `lv`); the lanes past per * n_levels idle
+        const uint32_t per = 64u / n_levels;
+        const uint32_t nz = lane / n_levels, lv = lane - nz * n_levels;
+        const uint32_t path = __shfl(mine, lv, 64);
+        if (nz >= per) continue;
+        for (uint64_t i = lo + nz; i < hi; i += per) {
+            const uint32_t s = d.rows.sample[i];
+            const unsigned long long w = d.rows.count[i];
+            if (s >= d.s.n_samples) { flags |= FLAG_BAD_SAMPLE; r.ctl[4] = q; continue; }
+            if (w) flags |= block_cell_add(s_key, s_cnt, d.s, path, s, w);   // (a zero leaves no cell)
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < CELL_LDS_SLOTS; i += RB)
+        if (s_key[i] != REPORT_EMPTY && s_cnt[i]) flags |= cell_flush(d.s, s_key[i], s_cnt[i]);
+    if (flags) atomicOr(reinterpret_cast<unsigned int*>(r.ctl + 2), flags);
+}
+
+// out[0]: P, the bound on the paths (report_bound); out[1]: sum of popcount(level_mask) * non-zeros of the row over the
+// classified queries, the bound on the cells.  A row the count kernel would refuse counts as empty.
+__global__ __launch_bounds__(RB) void count_bound(const blu_result* __restrict__ recs, CountRows rows, uint64_t n_queries,
+                                                  unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long s[2];
+    if (threadIdx.x < 2) s[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned long long c = 0, cn = 0;
+    for (uint64_t q = (uint64_t)blockIdx.x * RB + threadIdx.x; q < n_queries; q += (uint64_t)gridDim.x * RB) {
+        const blu_result& r = recs[q];
+        if (r.status >= 2) continue;
+        const uint64_t lo = rows.row_ptr[q], hi = rows.row_ptr[q + 1];
+        const unsigned long long pc = (unsigned long long)__popcll(r.level_mask);
+        c += pc;
+        if (lo <= hi && hi <= rows.nnz) cn += pc * (hi - lo);
+    }
+    c = wave_sum(c);
+    cn = wave_sum(cn);
+    if ((threadIdx.x & 63) == 0 && (c | cn)) { atomicAdd(&s[0], c); atomicAdd(&s[1], cn); }
+    __syncthreads();
+    if (threadIdx.x == 0 && (s[0] | s[1])) { atomicAdd(out, s[0]); atomicAdd(out + 1, s[1]); }
+}
+
 uint64_t next_pow2(uint64_t x) { uint64_t c = 1; while (c < x) c <<= 1; return c; }
 
 // paths[] (parents named by index, in any order) -> at[i], the position of path i when parents come first: depth order,
@@ -334,6 +443,99 @@ void parents_first(const std::vector<blu_report_path>& paths, std::vector<uint32
     for (uint32_t k = 0; k < BLU_MAX_DEPTH; ++k) first[k + 1] += first[k];
     at.resize(n_paths);
     for (uint64_t i = 0; i < n_paths; ++i) at[i] = (uint32_t)first[depth[i]]++;
+}
+
+// What a count pass leaves on the device: both tables of its last attempt, the per-sample counters, the events around the
+// device work (ev0 recorded; ev1 is recorded here, after the compaction).
+struct SampleTables {
+    unsigned long long *keys = nullptr, *ckeys = nullptr, *cval = nullptr, *fixed = nullptr;
+    uint64_t cap = 0, ccap = 0;
+    uint32_t attempts = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    ~SampleTables() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
+};
+
+// The tables -> blu_sample_table: the occupied slots compacted on the device, then ordered on the host.  Shared by
+// sample_table_device and sample_table_counts_device.
+int sample_table_finish(HipPolicy& pol, DeviceArena& mem, const SampleTables& t, uint32_t n_samples, blu_sample_table* out) {
+    unsigned long long *const d_keys = t.keys, *const d_ckeys = t.ckeys, *const d_cval = t.cval, *const d_fixed = t.fixed;
+    const uint64_t cap = t.cap, ccap = t.ccap;
+    uint32_t *d_at = nullptr, *d_cat = nullptr;
+    void* d_tmp = nullptr;
+    blu_report_path* d_paths = nullptr;
+    blu_sample_cell* d_cells = nullptr;
+    uint64_t n_paths = 0, n_cells = 0;
+    std::vector<blu_report_path> paths;
+    std::vector<blu_sample_cell> cells;
+    std::vector<uint64_t> fixed(2 * (uint64_t)n_samples);
+    {
+        HIP_CHECK(pol, mem.alloc(&d_at, (cap + 1) * 4, "path ids"));
+        HIP_CHECK(pol, mem.alloc(&d_cat, (ccap + 1) * 4, "cell ids"));
+        HIP_CHECK(pol, mem.alloc(&d_tmp, scan_tmp_bytes_u32(std::max(cap, ccap) + 1), "scan scratch"));
+        hipLaunchKernelGGL(report_flags, dim3((unsigned)((cap + 1 + 255) / 256)), dim3(256), 0, 0, d_keys, cap, d_at);
+        HIP_CHECK(pol, hipGetLastError());
+        HIP_CHECK(pol, exclusive_scan_u32(d_at, d_at, cap + 1, d_tmp));
+        hipLaunchKernelGGL(report_flags, dim3((unsigned)((ccap + 1 + 255) / 256)), dim3(256), 0, 0, d_ckeys, ccap, d_cat);
+        HIP_CHECK(pol, hipGetLastError());
+        HIP_CHECK(pol, exclusive_scan_u32(d_cat, d_cat, ccap + 1, d_tmp));
+        uint32_t n32[2] = {0, 0};
+        HIP_CHECK(pol, hipMemcpy(&n32[0], d_at + cap, 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(&n32[1], d_cat + ccap, 4, hipMemcpyDeviceToHost));
+        n_paths = n32[0];
+        n_cells = n32[1];
+        HIP_CHECK(pol, mem.alloc(&d_paths, n_paths * sizeof(blu_report_path), "paths"));
+        HIP_CHECK(pol, mem.alloc(&d_cells, n_cells * sizeof(blu_sample_cell), "cells"));
+        hipLaunchKernelGGL(sample_paths_compact, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, 0, d_keys, d_at, cap, d_paths);
+        HIP_CHECK(pol, hipGetLastError());
+        hipLaunchKernelGGL(sample_cells_compact, dim3((unsigned)((ccap + 255) / 256)), dim3(256), 0, 0, d_ckeys, d_cval, d_cat, d_at, ccap, d_cells);
+        HIP_CHECK(pol, hipGetLastError());
+        HIP_CHECK(pol, hipEventRecord(t.ev1, nullptr));
+        paths.resize(n_paths);
+        cells.resize(n_cells);
+        if (n_paths) HIP_CHECK(pol, hipMemcpy(paths.data(), d_paths, n_paths * sizeof(blu_report_path), hipMemcpyDeviceToHost));
+        if (n_cells) HIP_CHECK(pol, hipMemcpy(cells.data(), d_cells, n_cells * sizeof(blu_sample_cell), hipMemcpyDeviceToHost));
+        if (n_samples) HIP_CHECK(pol, hipMemcpy(fixed.data(), d_fixed, fixed.size() * 8, hipMemcpyDeviceToHost));
+        float ms = 0;
+        HIP_CHECK(pol, hipEventSynchronize(t.ev1));   // (no path, cell or sample came back: no copy has waited for the device yet)
+        HIP_CHECK(pol, hipEventElapsedTime(&ms, t.ev0, t.ev1));
+        out->t_device_ms = ms;
+    }
+    {
+        // parents first as in the report; a path's clade = the sum of its cells, direct = clade - the children's clades;
+        // the cells ordered by path (a counting sort), then by sample inside a path
+        const uint32_t NONE = REPORT_NONE;
+        std::vector<uint32_t> at;
+        parents_first(paths, at);
+        blu_report_path* o = (blu_report_path*)malloc(std::max<uint64_t>(n_paths, 1) * sizeof(blu_report_path));
+        blu_sample_cell* c = (blu_sample_cell*)malloc(std::max<uint64_t>(n_cells, 1) * sizeof(blu_sample_cell));
+        uint64_t* un = (uint64_t*)malloc(std::max<uint64_t>(fixed.size(), 1) * 8);
+        if (!o || !c || !un) { free(o); free(c); free(un); set_error("sample table: out of memory"); return BLU_ERR_ALLOC; }
+        for (uint64_t i = 0; i < n_paths; ++i) {
+            blu_report_path p = paths[i];
+            p.parent = p.parent == NONE ? NONE : at[p.parent];
+            o[at[i]] = p;
+        }
+        std::vector<uint64_t> first(n_paths + 1, 0);
+        for (const blu_sample_cell& x : cells) { o[at[x.path]].clade += x.clade; ++first[at[x.path] + 1]; }
+        for (uint64_t i = 0; i < n_paths; ++i) first[i + 1] += first[i];
+        for (const blu_sample_cell& x : cells) { blu_sample_cell y = x; y.path = at[x.path]; c[first[y.path]++] = y; }
+        for (uint64_t i = 0, lo = 0; i < n_paths; lo = first[i++])
+            if (first[i] - lo > 1) std::sort(c + lo, c + first[i], [](const blu_sample_cell& a, const blu_sample_cell& b) { return a.sample < b.sample; });
+        for (uint64_t i = 0; i < n_paths; ++i) o[i].direct = o[i].clade;
+        for (uint64_t i = n_paths; i-- > 0;)
+            if (o[i].parent != NONE) o[o[i].parent].direct -= o[i].clade;
+        std::copy(fixed.begin(), fixed.end(), un);
+        out->paths = o;
+        out->n_paths = n_paths;
+        out->cells = c;
+        out->n_cells = n_cells;
+        out->n_samples = n_samples;
+        out->unclassified = un;
+        out->unplaced = un + n_samples;
+        out->table_slots = ccap;
+        out->attempts = t.attempts;
+    }
+    return BLU_OK;
 }
 
 }  // namespace
@@ -445,23 +647,17 @@ int sample_table_device(const blu_taxonomy* tax, const ReportInput& in, const ui
                         blu_sample_table* out) {
     const uint64_t nq = in.n_queries;
     unsigned long long *d_keys = nullptr, *d_ckeys = nullptr, *d_cval = nullptr, *d_ctl = nullptr, *d_fixed = nullptr;
-    uint32_t *d_at = nullptr, *d_cat = nullptr;
-    void* d_tmp = nullptr;
-    blu_report_path* d_paths = nullptr;
-    blu_sample_cell* d_cells = nullptr;
     unsigned long long ctl[5] = {0, 0, 0, 0, 0};
-    uint64_t cap = 0, ccap = 0, n_paths = 0, n_cells = 0;
-    uint32_t attempts = 0;
-    std::vector<blu_report_path> paths;
-    std::vector<blu_sample_cell> cells;
-    std::vector<uint64_t> fixed(2 * (uint64_t)n_samples);
+    uint64_t cap = 0, ccap = 0;
+    const uint64_t fixed_bytes = 2 * (uint64_t)n_samples * 8;
     HipPolicy pol{"sample table", BLU_ERR_ALLOC};
     DeviceArena mem(pol);
-    struct Events { hipEvent_t ev0 = nullptr, ev1 = nullptr; ~Events() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); } } ev;
-    HIP_CHECK(pol, hipEventCreate(&ev.ev0));
-    HIP_CHECK(pol, hipEventCreate(&ev.ev1));
+    SampleTables T;
+    uint32_t& attempts = T.attempts;
+    HIP_CHECK(pol, hipEventCreate(&T.ev0));
+    HIP_CHECK(pol, hipEventCreate(&T.ev1));
     HIP_CHECK(pol, mem.alloc(&d_ctl, sizeof ctl, "counters"));
-    HIP_CHECK(pol, mem.alloc(&d_fixed, fixed.size() * 8, "per-sample counters"));
+    HIP_CHECK(pol, mem.alloc(&d_fixed, fixed_bytes, "per-sample counters"));
     {
         // paths as the report sizes them; cells: the paths plus one per query (a sample's queries mostly share their upper
         // levels), at most one per level of every query
@@ -477,7 +673,7 @@ int sample_table_device(const blu_taxonomy* tax, const ReportInput& in, const ui
         d.r.recs = in.recs; d.r.n_queries = nq; d.r.row_src = in.row_src; d.r.n_rows = in.n_rows; d.r.row_stride = in.row_stride;
         d.r.by_query = in.by_query ? 1u : 0u; d.r.weight = in.weight; d.r.ctl = d_ctl;
         d.sample_of = sample_of; d.n_samples = n_samples; d.fixed = d_fixed;
-        HIP_CHECK(pol, hipEventRecord(ev.ev0, nullptr));
+        HIP_CHECK(pol, hipEventRecord(T.ev0, nullptr));
         for (;;) {
             ++attempts;
             // (path ids below 2^31: the two ids above are the fixed rows' in the cell keys)
@@ -492,7 +688,7 @@ int sample_table_device(const blu_taxonomy* tax, const ReportInput& in, const ui
             HIP_CHECK(pol, hipMemsetAsync(d_ckeys, 0xFF, ccap * 8, nullptr));
             HIP_CHECK(pol, hipMemsetAsync(d_cval, 0, ccap * 8, nullptr));
             HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, sizeof ctl, nullptr));
-            HIP_CHECK(pol, hipMemsetAsync(d_fixed, 0, fixed.size() * 8, nullptr));
+            HIP_CHECK(pol, hipMemsetAsync(d_fixed, 0, fixed_bytes, nullptr));
             d.r.keys = d_keys; d.r.cap_mask = (uint32_t)(cap - 1); d.r.max_probe = max_probe;
             d.cell_keys = d_ckeys; d.cell_val = d_cval; d.cell_mask = (uint32_t)(ccap - 1);
             if (nq) hipLaunchKernelGGL(sample_cells, dim3((unsigned)((nq + RB * RQ - 1) / (RB * RQ))), dim3(RB), 0, 0, d);
@@ -519,73 +715,87 @@ int sample_table_device(const blu_taxonomy* tax, const ReportInput& in, const ui
             cap = ccap = std::max<uint64_t>(next_pow2(2 * bound), 1024);
             max_probe = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
         }
-        HIP_CHECK(pol, mem.alloc(&d_at, (cap + 1) * 4, "path ids"));
-        HIP_CHECK(pol, mem.alloc(&d_cat, (ccap + 1) * 4, "cell ids"));
-        HIP_CHECK(pol, mem.alloc(&d_tmp, scan_tmp_bytes_u32(std::max(cap, ccap) + 1), "scan scratch"));
-        hipLaunchKernelGGL(report_flags, dim3((unsigned)((cap + 1 + 255) / 256)), dim3(256), 0, 0, d_keys, cap, d_at);
-        HIP_CHECK(pol, hipGetLastError());
-        HIP_CHECK(pol, exclusive_scan_u32(d_at, d_at, cap + 1, d_tmp));
-        hipLaunchKernelGGL(report_flags, dim3((unsigned)((ccap + 1 + 255) / 256)), dim3(256), 0, 0, d_ckeys, ccap, d_cat);
-        HIP_CHECK(pol, hipGetLastError());
-        HIP_CHECK(pol, exclusive_scan_u32(d_cat, d_cat, ccap + 1, d_tmp));
-        uint32_t n32[2] = {0, 0};
-        HIP_CHECK(pol, hipMemcpy(&n32[0], d_at + cap, 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(pol, hipMemcpy(&n32[1], d_cat + ccap, 4, hipMemcpyDeviceToHost));
-        n_paths = n32[0];
-        n_cells = n32[1];
-        HIP_CHECK(pol, mem.alloc(&d_paths, n_paths * sizeof(blu_report_path), "paths"));
-        HIP_CHECK(pol, mem.alloc(&d_cells, n_cells * sizeof(blu_sample_cell), "cells"));
-        hipLaunchKernelGGL(sample_paths_compact, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, 0, d_keys, d_at, cap, d_paths);
-        HIP_CHECK(pol, hipGetLastError());
-        hipLaunchKernelGGL(sample_cells_compact, dim3((unsigned)((ccap + 255) / 256)), dim3(256), 0, 0, d_ckeys, d_cval, d_cat, d_at, ccap, d_cells);
-        HIP_CHECK(pol, hipGetLastError());
-        HIP_CHECK(pol, hipEventRecord(ev.ev1, nullptr));
-        paths.resize(n_paths);
-        cells.resize(n_cells);
-        if (n_paths) HIP_CHECK(pol, hipMemcpy(paths.data(), d_paths, n_paths * sizeof(blu_report_path), hipMemcpyDeviceToHost));
-        if (n_cells) HIP_CHECK(pol, hipMemcpy(cells.data(), d_cells, n_cells * sizeof(blu_sample_cell), hipMemcpyDeviceToHost));
-        if (n_samples) HIP_CHECK(pol, hipMemcpy(fixed.data(), d_fixed, fixed.size() * 8, hipMemcpyDeviceToHost));
-        float ms = 0;
-        HIP_CHECK(pol, hipEventSynchronize(ev.ev1));   // (no path, cell or sample came back: no copy has waited for the device yet)
-        HIP_CHECK(pol, hipEventElapsedTime(&ms, ev.ev0, ev.ev1));
-        out->t_device_ms = ms;
     }
-    {
-        // parents first as in the report; a path's clade = the sum of its cells, direct = clade - the children's clades;
-        // the cells ordered by path (a counting sort), then by sample inside a path
-        const uint32_t NONE = REPORT_NONE;
-        std::vector<uint32_t> at;
-        parents_first(paths, at);
-        blu_report_path* o = (blu_report_path*)malloc(std::max<uint64_t>(n_paths, 1) * sizeof(blu_report_path));
-        blu_sample_cell* c = (blu_sample_cell*)malloc(std::max<uint64_t>(n_cells, 1) * sizeof(blu_sample_cell));
-        uint64_t* un = (uint64_t*)malloc(std::max<uint64_t>(fixed.size(), 1) * 8);
-        if (!o || !c || !un) { free(o); free(c); free(un); set_error("sample table: out of memory"); return BLU_ERR_ALLOC; }
-        for (uint64_t i = 0; i < n_paths; ++i) {
-            blu_report_path p = paths[i];
-            p.parent = p.parent == NONE ? NONE : at[p.parent];
-            o[at[i]] = p;
+    T.keys = d_keys; T.ckeys = d_ckeys; T.cval = d_cval; T.fixed = d_fixed; T.cap = cap; T.ccap = ccap;
+    return sample_table_finish(pol, mem, T, n_samples, out);
+}
+
+int sample_table_counts_device(const blu_taxonomy* tax, const ReportInput& in, const CountRows& rows, uint32_t n_samples,
+                               blu_sample_table* out) {
+    const uint64_t nq = in.n_queries;
+    unsigned long long *d_keys = nullptr, *d_ckeys = nullptr, *d_cval = nullptr, *d_ctl = nullptr, *d_fixed = nullptr;
+    unsigned long long ctl[6] = {0, 0, 0, 0, 0, 0};
+    const uint64_t fixed_bytes = 2 * (uint64_t)n_samples * 8;
+    HipPolicy pol{"count table", BLU_ERR_ALLOC};
+    DeviceArena mem(pol);
+    SampleTables T;
+    HIP_CHECK(pol, hipEventCreate(&T.ev0));
+    HIP_CHECK(pol, hipEventCreate(&T.ev1));
+    HIP_CHECK(pol, mem.alloc(&d_ctl, sizeof ctl, "counters"));
+    HIP_CHECK(pol, mem.alloc(&d_fixed, fixed_bytes, "per-sample counters"));
+    CountDev d{};
+    d.s.r.lin = tax->d_lin; d.s.r.n_tax = tax->n_tax; d.s.r.stride = tax->dev_stride; d.s.r.node_base = tax->node_base;
+    d.s.r.max_depth = tax->max_depth;
+    d.s.r.recs = in.recs; d.s.r.n_queries = nq; d.s.r.row_src = in.row_src; d.s.r.n_rows = in.n_rows; d.s.r.row_stride = in.row_stride;
+    d.s.r.by_query = in.by_query ? 1u : 0u; d.s.r.ctl = d_ctl;
+    d.s.n_samples = n_samples; d.s.fixed = d_fixed;
+    d.rows = rows;
+    HIP_CHECK(pol, hipEventRecord(T.ev0, nullptr));
+    // the bounds first: P on the paths, and on the cells the sum of levels x non-zeros (one pass over the records and row_ptr)
+    unsigned long long bound[2] = {0, 0};
+    HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, sizeof ctl, nullptr));
+    if (nq) hipLaunchKernelGGL(count_bound, dim3((unsigned)std::min<uint64_t>((nq + RB - 1) / RB, 4096)), dim3(RB), 0, 0, in.recs, rows, nq, d_ctl);
+    HIP_CHECK(pol, hipGetLastError());
+    HIP_CHECK(pol, hipMemcpy(bound, d_ctl, sizeof bound, hipMemcpyDeviceToHost));
+    // paths as the report sizes them; cells: no more than the bound, and no more than every path in every sample
+    const uint64_t guess = std::min<uint64_t>(nq * std::max<uint32_t>(tax->max_depth, 1), 2 * tax->n_tax + 4096);
+    uint64_t cap = std::max<uint64_t>(next_pow2(2 * guess), 1024);
+    uint64_t ccap = std::max<uint64_t>(next_pow2(2 * std::min<uint64_t>(bound[1], guess * std::max<uint32_t>(n_samples, 1))), 1024);
+    uint32_t max_probe = REPORT_PROBE_FIRST;
+    for (;;) {
+        ++T.attempts;
+        // (path ids below 2^31: the two ids above are the fixed rows' in the cell keys)
+        if (cap > (1ull << 31) || ccap > (1ull << 32)) {
+            set_error("count table: tables of %llu / %llu slots exceed 32-bit ids", (unsigned long long)cap, (unsigned long long)ccap);
+            return BLU_ERR_ALLOC;
         }
-        std::vector<uint64_t> first(n_paths + 1, 0);
-        for (const blu_sample_cell& x : cells) { o[at[x.path]].clade += x.clade; ++first[at[x.path] + 1]; }
-        for (uint64_t i = 0; i < n_paths; ++i) first[i + 1] += first[i];
-        for (const blu_sample_cell& x : cells) { blu_sample_cell y = x; y.path = at[x.path]; c[first[y.path]++] = y; }
-        for (uint64_t i = 0, lo = 0; i < n_paths; lo = first[i++])
-            if (first[i] - lo > 1) std::sort(c + lo, c + first[i], [](const blu_sample_cell& a, const blu_sample_cell& b) { return a.sample < b.sample; });
-        for (uint64_t i = 0; i < n_paths; ++i) o[i].direct = o[i].clade;
-        for (uint64_t i = n_paths; i-- > 0;)
-            if (o[i].parent != NONE) o[o[i].parent].direct -= o[i].clade;
-        std::copy(fixed.begin(), fixed.end(), un);
-        out->paths = o;
-        out->n_paths = n_paths;
-        out->cells = c;
-        out->n_cells = n_cells;
-        out->n_samples = n_samples;
-        out->unclassified = un;
-        out->unplaced = un + n_samples;
-        out->table_slots = ccap;
-        out->attempts = attempts;
+        HIP_CHECK(pol, mem.alloc(&d_keys, cap * 8, "path table"));
+        HIP_CHECK(pol, mem.alloc(&d_ckeys, ccap * 8, "cell table"));
+        HIP_CHECK(pol, mem.alloc(&d_cval, ccap * 8, "cell table"));
+        HIP_CHECK(pol, hipMemsetAsync(d_keys, 0xFF, cap * 8, nullptr));
+        HIP_CHECK(pol, hipMemsetAsync(d_ckeys, 0xFF, ccap * 8, nullptr));
+        HIP_CHECK(pol, hipMemsetAsync(d_cval, 0, ccap * 8, nullptr));
+        HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, sizeof ctl, nullptr));
+        HIP_CHECK(pol, hipMemsetAsync(d_fixed, 0, fixed_bytes, nullptr));
+        d.s.r.keys = d_keys; d.s.r.cap_mask = (uint32_t)(cap - 1); d.s.r.max_probe = max_probe;
+        d.s.cell_keys = d_ckeys; d.s.cell_val = d_cval; d.s.cell_mask = (uint32_t)(ccap - 1);
+        if (nq) hipLaunchKernelGGL(count_cells, dim3((unsigned)((nq + COUNT_Q_BLOCK - 1) / COUNT_Q_BLOCK)), dim3(RB), 0, 0, d);
+        HIP_CHECK(pol, hipGetLastError());
+        HIP_CHECK(pol, hipMemcpy(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+        if (ctl[2] & FLAG_BAD_ROW) {
+            set_error("count table: query %llu has a row_ptr that decreases or ends past the %llu non-zeros", (unsigned long long)ctl[5],
+                      (unsigned long long)rows.nnz);
+            return BLU_ERR_INVALID_ARG;
+        }
+        if (ctl[2] & FLAG_BAD_SAMPLE) {
+            set_error("count table: query %llu has a sample id that is not below n_samples = %u", (unsigned long long)ctl[4], n_samples);
+            return BLU_ERR_INVALID_ARG;
+        }
+        if (ctl[2] & FLAG_BAD_RECORD) {
+            set_error("count table: record %llu has a taxon (status 0 / 1) but its reference row names no taxonomy row",
+                      (unsigned long long)ctl[3]);
+            return BLU_ERR_INVALID_ARG;
+        }
+        if (!(ctl[2] & FLAG_OVERFLOW)) break;
+        if (max_probe != REPORT_PROBE_FIRST) { set_error("count table: table overflow"); return BLU_ERR_HIP; }   // (cannot happen at load <= 1/2)
+        // an estimate was short: both tables again from zero, at twice their bounds, where a probe always ends
+        mem.free(d_keys); mem.free(d_ckeys); mem.free(d_cval); d_keys = d_ckeys = d_cval = nullptr;
+        cap = std::max<uint64_t>(next_pow2(2 * bound[0]), 1024);
+        ccap = std::max<uint64_t>(next_pow2(2 * bound[1]), 1024);
+        max_probe = (uint32_t)std::min<uint64_t>(std::max(cap, ccap), 0xFFFFFFFFull);
     }
-    return BLU_OK;
+    T.keys = d_keys; T.ckeys = d_ckeys; T.cval = d_cval; T.fixed = d_fixed; T.cap = cap; T.ccap = ccap;
+    return sample_table_finish(pol, mem, T, n_samples, out);
 }
 
 }  // namespace blu
@@ -672,6 +882,48 @@ int blu_consensus_sample_table(const blu_taxonomy* tax, const blu_hits* hits, co
         }
         ReportInput hin{d_recs, nq, d_rows, nq, 1u, true, d_w};
         return sample_table_device(tax, hin, d_s, n_samples, out);
+    } catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
+}
+
+int blu_consensus_sample_table_counts(const blu_taxonomy* tax, const blu_hits* hits, const blu_result* results, const blu_count_rows* rows,
+                                      uint32_t n_samples, void* stream, blu_sample_table* out) {
+    if (!tax || !hits || !out || !rows || (hits->n_queries && (!results || !rows->row_ptr))) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    memset(out, 0, sizeof *out);
+    if (tax->device < 0) { set_error("host-only taxonomy handle: blu_consensus_sample_table_counts needs a HIP device (no CPU fallback)"); return BLU_ERR_NO_DEVICE; }
+    const uint32_t* src = hits->packed ? hits->packed : hits->packed64 ? hits->packed64 : hits->tax_row;
+    const uint32_t stride = hits->packed ? 4u : hits->packed64 ? 6u : 1u;
+    const uint64_t nq = hits->n_queries, nh = hits->n_hits;
+    if (nq && !src) { set_error("blu_consensus_sample_table_counts: no tax_row column"); return BLU_ERR_INVALID_ARG; }
+    if (hipSetDevice(tax->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", tax->device); return BLU_ERR_NO_DEVICE; }
+    HipPolicy pol{"blu_consensus_sample_table_counts", BLU_ERR_ALLOC};
+    uint64_t nnz = 0;   // the last offset: what the two arrays hold, and what no row may pass
+    if (hits->on_device) {
+        if (((uintptr_t)results & 15u) != 0) { set_error("blu_consensus_sample_table_counts: device records must be 16-byte aligned"); return BLU_ERR_INVALID_ARG; }
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) { set_error("blu_consensus_sample_table_counts: stream synchronise failed"); return BLU_ERR_HIP; }
+        if (nq) HIP_CHECK(pol, hipMemcpy(&nnz, rows->row_ptr + nq, 8, hipMemcpyDeviceToHost));
+        if (nnz && (!rows->sample || !rows->count)) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+        ReportInput in{results, nq, src, nh, stride, false, nullptr};
+        try { return sample_table_counts_device(tax, in, CountRows{rows->row_ptr, rows->sample, rows->count, nnz}, n_samples, out); }
+        catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
+    }
+    // host pointers: the records, each record's engine row and the three arrays of the rows go up
+    if (nq) nnz = rows->row_ptr[nq];
+    if (nnz && (!rows->sample || !rows->count)) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    DeviceArena mem(pol);
+    blu_result* d_recs = nullptr;
+    uint32_t *d_rows = nullptr, *d_s = nullptr, *d_c = nullptr;
+    uint64_t* d_ptr = nullptr;
+    try {
+        std::vector<uint32_t> erows(nq, BLU_UNMATCHED_TAXID);
+        for (uint64_t q = 0; q < nq; ++q)
+            if (results[q].status < 2 && results[q].ref_row < nh) erows[q] = src[(uint64_t)results[q].ref_row * stride];
+        HIP_CHECK(pol, mem.upload(&d_recs, results, nq, "records"));
+        HIP_CHECK(pol, mem.upload(&d_rows, erows.data(), nq, "rows"));
+        HIP_CHECK(pol, mem.upload(&d_ptr, rows->row_ptr, nq ? nq + 1 : 0, "row offsets"));
+        HIP_CHECK(pol, mem.upload(&d_s, rows->sample, nnz, "sample ids"));
+        HIP_CHECK(pol, mem.upload(&d_c, rows->count, nnz, "counts"));
+        ReportInput hin{d_recs, nq, d_rows, nq, 1u, true, nullptr};
+        return sample_table_counts_device(tax, hin, CountRows{d_ptr, d_s, d_c, nnz}, n_samples, out);
     } catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
 }
 

@@ -245,6 +245,17 @@ class ConsensusOutcome(C.Structure):
     _fields_ = [("text", C.c_void_p), ("text_len", C.c_size_t), ("stats", PipelineStats), ("selection", HitSelectionStats)]
 
 
+class CountTableStats(C.Structure):
+    """include/blu_pipeline.h: blu_count_table_stats"""
+    _fields_ = [("n_rows", C.c_uint64), ("n_samples", C.c_uint64), ("n_joined", C.c_uint64), ("n_rows_unclassified", C.c_uint64)]
+
+
+class ConsensusExtras(C.Structure):
+    """include/blu_pipeline.h: blu_consensus_extras"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("count_table_path", C.c_char_p),
+                ("count_table_stats", C.POINTER(CountTableStats))]
+
+
 class _Selection:
     """The keywords hit_filter / taxon_filter / score_band / best_hit_per_subject as the C struct, with what it points to kept
     alive, and the stats keys each of them adds."""
@@ -288,6 +299,8 @@ def _bind():
     L = N.lib()
     L.blu_build_consensus.restype = C.c_int
     L.blu_build_consensus.argtypes = [C.POINTER(ConsensusRequest), C.POINTER(ConsensusOutcome)]
+    L.blu_build_consensus_with.restype = C.c_int
+    L.blu_build_consensus_with.argtypes = [C.POINTER(ConsensusRequest), C.POINTER(ConsensusExtras), C.POINTER(ConsensusOutcome)]
     L.blu_ingest_columns_selected.restype = C.c_int
     L.blu_ingest_columns_selected.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(HitSelection),
                                               C.POINTER(IngestColumns), C.POINTER(HitSelectionStats)]
@@ -419,13 +432,16 @@ def build_consensus_identities_with_report(blast_output: str, taxonomies_file: s
                                            report_weight: str = "one", hit_filter: Union[None, dict, HitFilter] = None,
                                            taxon_filter: Union[None, dict, TaxonFilter] = None,
                                            score_band: Union[None, dict, ScoreBand] = None,
-                                           best_hit_per_subject: bool = False, min_cover=None):
+                                           best_hit_per_subject: bool = False, min_cover=None,
+                                           count_table: Optional[str] = None):
     """build_consensus_identities plus the taxon abundance report of its results, counted on the GPU and written to
     report_path after the document (include/blu_pipeline.h: blu_consensus_request.report_path).
-    report_weight: "one" (results) or "size" (dereplicated reads named in the query)."""
+    report_weight: "one" (results) or "size" (dereplicated reads named in the query).  count_table: a feature x sample count
+    table whose row sums weigh the queries instead (with report_weight "one" only); stats then also has
+    `count_table`, its counts (n_rows, n_samples, n_joined, n_rows_unclassified)."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, report_path, report_weight, hit_filter=hit_filter, taxon_filter=taxon_filter,
-                  score_band=score_band, best_hit_per_subject=best_hit_per_subject, min_cover=min_cover)
+                  score_band=score_band, best_hit_per_subject=best_hit_per_subject, min_cover=min_cover, count_table=count_table)
 
 
 def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -439,23 +455,28 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
                                            support_table_path: Optional[str] = None,
                                            taxon_filter: Union[None, dict, TaxonFilter] = None,
                                            score_band: Union[None, dict, ScoreBand] = None,
-                                           best_hit_per_subject: bool = False, min_cover=None):
+                                           best_hit_per_subject: bool = False, min_cover=None,
+                                           count_table: Optional[str] = None):
     """build_consensus_identities plus the taxon abundance report (report_path), the per-sample table (sample_table_path,
     DESIGN.md §13), or both, counted on the GPU and written in the order document, report, table
     (include/blu_pipeline.h: blu_consensus_request).  report_weight serves both files.  A query whose name
     names no sample fails the call before any file is written.  support_table_path: also the per-query support table
     (DESIGN.md §15), counted on the GPU and written last; it combines with the
     other files and with hit_filter, and may be the only one asked for.  Under a score_band its top_hits is the band's size
-    and bits / support_bits sum the raised scores."""
+    and bits / support_bits sum the raised scores.  count_table: a feature x sample count table (with
+    report_weight "one" only): the samples and counts of a query are those of the row with its key (its name up to the first
+    ';') instead of what its name says; a row no query has counts as unclassified; stats then also has `count_table`, its
+    counts (n_rows, n_samples, n_joined, n_rows_unclassified)."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, report_path, report_weight, sample_table_path, hit_filter=hit_filter,
                   support_table_path=support_table_path, taxon_filter=taxon_filter, score_band=score_band,
-                  best_hit_per_subject=best_hit_per_subject, min_cover=min_cover)
+                  best_hit_per_subject=best_hit_per_subject, min_cover=min_cover, count_table=count_table)
 
 
 def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device, lenient,
            parse, config, out_path, report_path, report_weight, sample_table_path=None, hit_filter=None,
-           support_table_path=None, taxon_filter=None, score_band=None, best_hit_per_subject=False, min_cover=None):
+           support_table_path=None, taxon_filter=None, score_band=None, best_hit_per_subject=False, min_cover=None,
+           count_table=None):
     L = _bind()
     cover = min_cover_milli(min_cover) if min_cover is not None else 0
     sel = _Selection(hit_filter, taxon_filter, score_band, best_hit_per_subject)
@@ -482,15 +503,23 @@ def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_tax
         rq.headers, rq.n_headers = (C.c_char_p * max(1, len(names)))(*names), len(names)
     if config is not None:
         rq.run_id_text, rq.config_text = str(config.run_id).encode(), config.render(out_format).encode()
-    if report_path is not None or sample_table_path is not None:
+    if report_path is not None or sample_table_path is not None or count_table is not None:
         rq.weight = REPORT_WEIGHT[report_weight]
     rq.min_cover_milli = cover
     oc = ConsensusOutcome(selection=sel.stats())
-    rc = L.blu_build_consensus(C.byref(rq), C.byref(oc))
+    if count_table is None:
+        rc = L.blu_build_consensus(C.byref(rq), C.byref(oc))
+    else:
+        # (what the request has no room for travels in the extras)
+        cst = CountTableStats()
+        ex = ConsensusExtras(struct_size=C.sizeof(ConsensusExtras), count_table_path=enc(count_table), count_table_stats=C.pointer(cst))
+        rc = L.blu_build_consensus_with(C.byref(rq), C.byref(ex), C.byref(oc))
     if rc != N.BLU_OK:
         raise N.BluError(rc, "blu_build_consensus")
     stats = {f: getattr(oc.stats, f) for f, _ in PipelineStats._fields_}
     stats.update(sel.counts(oc.selection))
+    if count_table is not None:
+        stats["count_table"] = {f: int(getattr(cst, f)) for f, _ in CountTableStats._fields_}
     if cover:
         stats["min_cover"] = last_min_cover_stats()
     if out_path is not None:

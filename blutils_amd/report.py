@@ -17,6 +17,11 @@ The per-sample table is the report split into one column per sa
 (`sample_of`): `sample_table_from_results` / `build_report(..., by_sample=True)` on the host, `build-consensus
 --sample-table` counted on the GPU (pipeline.build_consensus_identities_with_tables), `consensus_sample_table` at the engine
 level.  Both paths give the same bytes for the same results.
+
+With a count table (`--count-table`, the `count_table` keywords) the samples and counts of a result are those
+of the table's row with its key — the name up to the first ';' — instead of what its name says: `parse_count_table` and
+`join_count_table` restate the library's parser and join (csrc/count_table.cpp) for the host route, `build-consensus
+--count-table` counts on the GPU, `consensus_sample_table_counts` is the engine-level call.
 """
 from __future__ import annotations
 
@@ -95,12 +100,128 @@ def _row_order(paths):
         stack.extend(reversed(kids.get(p, [])))
 
 
-def report_from_results(results, weight: str = "one") -> str:
-    """The report of a document's `results` list (parsed QueryWithConsensus objects)."""
+# ---- the count table ---------------------------------------------------------------------------------
+
+def _bytes_key(s: str) -> bytes:
+    return s.encode("utf-8", "surrogatepass")
+
+
+def _cell(text: str):
+    """ASCII digits, optionally `.` and one or more zeros; None when it is anything else or 2^32 or more"""
+    whole, dot, frac = text.partition(".")
+    if not _digits(whole) or (dot and (not frac or frac.strip("0"))):
+        return None
+    v = int(whole)
+    return v if v < 1 << 32 else None
+
+
+def parse_count_table(text: str):
+    """-> (samples, rows): the sample names ascending bytewise, and per row of the file (name, {sample: count > 0}).  Blank
+    lines are skipped, and so are leading `#` lines without a tab; the next line is the header (first cell ignored).  Anything
+    malformed is a ReportError naming line and column (both from 1)."""
+    def fail(line, column, what):
+        raise ReportError(f"count table: line {line}, column {column}: {what}")
+
+    header, rows = None, []
+    lines = text.split("\n")
+    if lines[-1] == "":                  # (the text ends with its last line's end, or is empty)
+        lines.pop()
+    for no, line in enumerate(lines, 1):
+        if line.endswith("\r"):
+            line = line[:-1]
+        if not line:
+            continue
+        cells = line.split("\t")
+        if header is None:
+            if line.startswith("#") and len(cells) == 1:
+                continue
+            if len(cells) < 2:
+                fail(no, 2, "the header names no sample")
+            for c, name in enumerate(cells[1:], 2):
+                if not name:
+                    fail(no, c, "an empty sample name")
+                if name in cells[1:c - 1]:
+                    fail(no, c, "a sample name for the second time")
+            header = cells[1:]
+            continue
+        if len(cells) < len(header) + 1:
+            fail(no, len(cells) + 1, "the row is short of a cell")
+        if len(cells) > len(header) + 1:
+            fail(no, len(header) + 2, "the row has a cell no sample heads")
+        counts = {}
+        for c, (name, cell) in enumerate(zip(header, cells[1:]), 2):
+            v = _cell(cell)
+            if v is None:
+                fail(no, c, "a cell is not a whole number below 2^32 (digits, optionally `.0`)")
+            if v:
+                counts[name] = v
+        rows.append((cells[0], counts))
+    if header is None:
+        fail(len(lines) + 1, 1, "no header line")
+    return sorted(header, key=_bytes_key), rows
+
+
+def join_count_table(rows, queries):
+    """rows: parse_count_table's; queries: the names of the results.  -> (per query its {sample: count}, the {sample: count} of
+    the rows no query has, stats).  Joined on the names up to their first ';'."""
+    row_of = {}
+    for i, (name, counts) in enumerate(rows):
+        if sum(counts.values()) >= 1 << 32:
+            raise ReportError(f"count table: row `{name}`: its counts add up to 2^32 or more")
+        key = name.split(";", 1)[0]
+        if key in row_of:
+            raise ReportError(f"count table: rows `{rows[row_of[key]][0]}` and `{name}` have one key")
+        row_of[key] = i
+    seen, per_query, taken = {}, [], set()
+    for q in queries:
+        key = q.split(";", 1)[0]
+        if key in seen:
+            raise ReportError(f"count table: queries `{seen[key]}` and `{q}` have one key")
+        seen[key] = q
+        if key not in row_of:
+            raise ReportError(f"count table: no row for query `{q}`")
+        taken.add(row_of[key])
+        per_query.append(rows[row_of[key]][1])
+    left = {}
+    for i, (_, counts) in enumerate(rows):
+        if i not in taken:
+            for s, v in counts.items():
+                left[s] = left.get(s, 0) + v
+    return per_query, left, {"n_rows": len(rows), "n_joined": len(taken), "n_rows_unclassified": len(rows) - len(taken)}
+
+
+def count_table_line(stats: dict) -> str:
+    """the line the CLI prints to stderr"""
+    return (f"count table: {stats['n_rows']} rows, {stats['n_samples']} samples, {stats['n_joined']} joined to results, "
+            f"{stats['n_rows_unclassified']} without a result counted as unclassified")
+
+
+def _counted(results, count_table: str, count_stats):
+    """the file -> (samples, per result {sample: count}, {sample: count} of the rows without a result)"""
+    try:
+        with open(count_table, encoding="utf-8", errors="surrogateescape", newline="") as f:
+            text = f.read()
+    except OSError:
+        raise ReportError(f"cannot read the count table {count_table}") from None
+    samples, rows = parse_count_table(text)
+    per_query, left, st = join_count_table(rows, [str(r["query"]) for r in results])
+    if count_stats is not None:
+        count_stats.update(st, n_samples=len(samples))
+    return samples, per_query, left
+
+
+def report_from_results(results, weight: str = "one", count_table: Optional[str] = None, count_stats: Optional[dict] = None) -> str:
+    """The report of a document's `results` list (parsed QueryWithConsensus objects).  count_table: the path of a count table
+    whose row sums weigh the results (weight must be "one"); count_stats, a dict, receives its counts."""
     unclassified = unplaced = 0
     paths = {}
-    for r in results:
-        w = weight_of(str(r["query"]), weight)
+    if count_table is not None:
+        if weight != "one":
+            raise ReportError("count table: the weight must be `one` (the counts are the table's)")
+        _, per_query, left = _counted(results, count_table, count_stats)
+        unclassified = sum(left.values())
+    for k, r in enumerate(results):
+        w = weight_of(str(r["query"]), weight) if count_table is None else sum(per_query[k].values())
         taxon = r.get("taxon")
         if taxon is None:
             unclassified += w
@@ -135,32 +256,46 @@ def sample_of(query: str) -> str:
     raise ReportError(f"query `{query}` names no sample: neither a `sample=` field nor a `<sample>.<digits>` label")
 
 
-def sample_table_from_results(results, weight: str = "one") -> str:
+def sample_table_from_results(results, weight: str = "one", count_table: Optional[str] = None,
+                              count_stats: Optional[dict] = None) -> str:
     """The per-sample table of a document's `results` list: one column per sample, in ascending byte order of the names;
-    the report's rows in the report's order, each a clade count per sample."""
+    the report's rows in the report's order, each a clade count per sample.  count_table: the path of a count table that
+    gives the samples (all of its header) and each result's count in them (weight must be "one"); count_stats, a dict,
+    receives its counts."""
     samples = {}
     unclassified, unplaced = {}, {}
     paths, cells = {}, {}
-    for r in results:
+    if count_table is not None:
+        if weight != "one":
+            raise ReportError("count table: the weight must be `one` (the counts are the table's)")
+        names, per_query, unclassified = _counted(results, count_table, count_stats)
+        samples = dict.fromkeys(names)
+    for k, r in enumerate(results):
         q = str(r["query"])
-        s = sample_of(q)
-        w = weight_of(q, weight)
-        samples[s] = None
+        if count_table is None:
+            counts = {sample_of(q): weight_of(q, weight)}
+            samples.update(dict.fromkeys(counts))
+        else:
+            counts = per_query[k]
         taxon = r.get("taxon")
-        if taxon is None:
-            unclassified[s] = unclassified.get(s, 0) + w
-            continue
-        tax = taxon.get("taxonomy")
-        if not tax:
-            unplaced[s] = unplaced.get(s, 0) + w
-            continue
-        els = tuple(tax.split(";"))
-        for i in range(1, len(els) + 1):
-            paths.setdefault(els[:i], [0, 0])[1] += w
-            c = cells.setdefault(els[:i], {})
-            c[s] = c.get(s, 0) + w
-        paths[els][0] += w
-    cols = sorted(samples, key=lambda s: s.encode("utf-8", "surrogatepass"))
+        tax = taxon.get("taxonomy") if taxon is not None else None
+        els = tuple(tax.split(";")) if tax else ()
+        for i in range(1, len(els) + 1):                 # (a path that only zero counts reach is still listed)
+            paths.setdefault(els[:i], [0, 0])
+            cells.setdefault(els[:i], {})
+        for s, w in counts.items():
+            if taxon is None:
+                unclassified[s] = unclassified.get(s, 0) + w
+                continue
+            if not tax:
+                unplaced[s] = unplaced.get(s, 0) + w
+                continue
+            for i in range(1, len(els) + 1):
+                paths[els[:i]][1] += w
+                c = cells[els[:i]]
+                c[s] = c.get(s, 0) + w
+            paths[els][0] += w
+    cols = sorted(samples, key=_bytes_key)
 
     def line(rank, ident, taxonomy, per):
         return "\t".join([rank, ident, taxonomy, str(sum(per.values()))] + [str(per.get(s, 0)) for s in cols]) + "\n"
@@ -175,14 +310,15 @@ def sample_table_from_results(results, weight: str = "one") -> str:
 
 
 def build_report(blu_result: str = "-", output_file: Optional[str] = None, input_format: str = "json",
-                 weight: str = "one", stdout=None, by_sample: bool = False) -> str:
+                 weight: str = "one", stdout=None, by_sample: bool = False, count_table: Optional[str] = None,
+                 count_stats: Optional[dict] = None) -> str:
     """`blastn build-report`: the report of an existing document, to output_file or stdout; by_sample: the per-sample
-    table instead."""
+    table instead; count_table: the abundances from a count table, its counts into count_stats."""
     try:
         content = tabular.load_content(blu_result, input_format)
     except FileNotFoundError:
         raise ReportError(f"The file `{blu_result}` does not exist.") from None
-    text = (sample_table_from_results if by_sample else report_from_results)(content["results"], weight)
+    text = (sample_table_from_results if by_sample else report_from_results)(content["results"], weight, count_table, count_stats)
     if output_file is None:
         (stdout if stdout is not None else sys.stdout).write(text)
     else:
@@ -269,6 +405,22 @@ class SampleTable(C.Structure):
                 ("attempts", C.c_uint32), ("reserved2", C.c_uint32), ("t_device_ms", C.c_double)]
 
 
+def _sample_table_dict(tab) -> dict:
+    """a filled SampleTable as numpy arrays (copies: the caller frees the table)"""
+    import numpy as np
+    pdt = np.dtype([("node", np.uint32), ("parent", np.uint32), ("direct", np.uint64), ("clade", np.uint64)])
+    cdt = np.dtype([("path", np.uint32), ("sample", np.uint32), ("clade", np.uint64)])
+
+    def take(p, n, dt):
+        return np.frombuffer(C.string_at(p, n * dt.itemsize), dtype=dt).copy() if n else np.zeros(0, dtype=dt)
+
+    ns = int(tab.n_samples)
+    return {"paths": take(tab.paths, int(tab.n_paths), pdt), "cells": take(tab.cells, int(tab.n_cells), cdt),
+            "unclassified": take(tab.unclassified, ns, np.dtype(np.uint64)),
+            "unplaced": take(tab.unplaced, ns, np.dtype(np.uint64)), "table_slots": int(tab.table_slots),
+            "attempts": int(tab.attempts), "t_device_ms": float(tab.t_device_ms)}
+
+
 def consensus_sample_table(tax, tax_row, records, n_hits: int, sample_of, n_samples: int, weights=None,
                            on_device: Optional[bool] = None, stream=None, packed: Optional[str] = None) -> dict:
     """blu_consensus_sample_table on one run's records: the arguments of consensus_report plus sample_of (uint32 per
@@ -310,16 +462,57 @@ def consensus_sample_table(tax, tax_row, records, n_hits: int, sample_of, n_samp
     if rc != N.BLU_OK:
         raise N.BluError(rc, "blu_consensus_sample_table")
     try:
-        pdt = np.dtype([("node", np.uint32), ("parent", np.uint32), ("direct", np.uint64), ("clade", np.uint64)])
-        cdt = np.dtype([("path", np.uint32), ("sample", np.uint32), ("clade", np.uint64)])
+        return _sample_table_dict(tab)
+    finally:
+        L.blu_sample_table_free(C.byref(tab))
 
-        def take(p, n, dt):
-            return np.frombuffer(C.string_at(p, n * dt.itemsize), dtype=dt).copy() if n else np.zeros(0, dtype=dt)
 
-        ns = int(tab.n_samples)
-        return {"paths": take(tab.paths, int(tab.n_paths), pdt), "cells": take(tab.cells, int(tab.n_cells), cdt),
-                "unclassified": take(tab.unclassified, ns, np.dtype(np.uint64)),
-                "unplaced": take(tab.unplaced, ns, np.dtype(np.uint64)), "table_slots": int(tab.table_slots),
-                "attempts": int(tab.attempts), "t_device_ms": float(tab.t_device_ms)}
+# ---- engine-level binding (include/blu_consensus.h: blu_consensus_sample_table_counts) ------------------------------
+
+class CountRows(C.Structure):
+    _fields_ = [("row_ptr", C.c_void_p), ("sample", C.c_void_p), ("count", C.c_void_p)]
+
+
+def consensus_sample_table_counts(tax, tax_row, records, n_hits: int, row_ptr, sample, count, n_samples: int,
+                                  on_device: Optional[bool] = None, stream=None, packed: Optional[str] = None) -> dict:
+    """blu_consensus_sample_table_counts on one run's records: tax, tax_row, records, n_hits, stream and packed as for
+    consensus_sample_table; row_ptr (uint64 [n_queries + 1]), sample and count (uint32 [row_ptr[-1]]) the CSR rows of the
+    queries, on the records' side.  Returns the dict consensus_sample_table returns."""
+    import numpy as np
+
+    def ptr(a):
+        if a is None:
+            return None
+        return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+    if on_device is None:
+        on_device = bool(getattr(records, "is_cuda", False))
+    nbytes = records.numel() * records.element_size() if hasattr(records, "numel") else records.nbytes
+    nq = nbytes // 32
+    keep = []
+    if not on_device:
+        tax_row = np.ascontiguousarray(tax_row).view(np.uint32)
+        records = np.ascontiguousarray(records)
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint64)
+        sample = np.ascontiguousarray(sample, dtype=np.uint32)
+        count = np.ascontiguousarray(count, dtype=np.uint32)
+        keep += [tax_row, records, row_ptr, sample, count]
+    col = {"packed": (None, ptr(tax_row), None), "packed64": (None, None, ptr(tax_row))}.get(packed, (ptr(tax_row), None, None))
+    h = N.Hits(None, col[0], None, None, None, None, int(n_hits), int(nq), 1 if on_device else 0, 0, None, col[1], col[2])
+    if stream is None and on_device:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    L = N.lib()
+    L.blu_consensus_sample_table_counts.restype = C.c_int
+    L.blu_consensus_sample_table_counts.argtypes = [C.c_void_p, C.POINTER(N.Hits), C.c_void_p, C.POINTER(CountRows), C.c_uint32,
+                                                    C.c_void_p, C.POINTER(SampleTable)]
+    L.blu_sample_table_free.argtypes = [C.POINTER(SampleTable)]
+    rows = CountRows(ptr(row_ptr), ptr(sample), ptr(count))
+    tab = SampleTable()
+    rc = L.blu_consensus_sample_table_counts(tax.handle, C.byref(h), ptr(records), C.byref(rows), int(n_samples), stream, C.byref(tab))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_consensus_sample_table_counts")
+    try:
+        return _sample_table_dict(tab)
     finally:
         L.blu_sample_table_free(C.byref(tab))

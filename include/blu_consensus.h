@@ -337,6 +337,23 @@ int blu_consensus_sample_table(const blu_taxonomy* tax, const blu_hits* hits, co
                                const uint32_t* sample_of, uint32_t n_samples, void* stream, blu_sample_table* out);
 void blu_sample_table_free(blu_sample_table* table);
 
+/* The same table when a query's abundances come from a feature x sample count table instead of its name (additive, ABI v5;
+ * DESIGN.md §22): query q carries the non-zeros [row_ptr[q], row_ptr[q + 1]) of a CSR matrix, each a sample id and a count,
+ * and adds every count to the cells (path, sample) of all prefixes of its path.  The two arrays hold row_ptr[n_queries]
+ * entries.  A row may be empty (its paths are still listed), may name a sample twice (the counts add up) and may hold zeros. */
+typedef struct blu_count_rows {      /* CSR over the queries; all three on the same side as the records */
+    const uint64_t* row_ptr;         /* [n_queries + 1] */
+    const uint32_t* sample;          /* [nnz], each < n_samples */
+    const uint32_t* count;           /* [nnz]; a zero is allowed and leaves no cell */
+} blu_count_rows;
+/* hits, results and stream as for blu_consensus_sample_table; fills the same blu_sample_table, freed the same way:
+ * paths[i].direct is the summed row sum of the queries that end at the path, clade the sum of the path's cells,
+ * unclassified[s] / unplaced[s] the counts in sample s of the records without a taxon / without a selected level.  A sample id
+ * >= n_samples, or a row_ptr that decreases or passes row_ptr[n_queries], is BLU_ERR_INVALID_ARG naming the query index (decided
+ * on the device, which reads nothing out of range); a host-only taxonomy is BLU_ERR_NO_DEVICE. */
+int blu_consensus_sample_table_counts(const blu_taxonomy* tax, const blu_hits* hits, const blu_result* results, const blu_count_rows* rows,
+                                      uint32_t n_samples, void* stream, blu_sample_table* out);
+
 /* -------------------------------------------------------------------------- */
 /* Per-query assignment support (additive, ABI v5): how well the hits of a query back the taxon its record names.
  * A hit is MATCHED when its row id names a taxonomy row whose lineage parsed (not BLU_UNMATCHED_TAXID, not a `bad` or empty

@@ -230,6 +230,30 @@ typedef struct blu_consensus_outcome {
 int blu_build_consensus(const blu_consensus_request* request, blu_consensus_outcome* outcome);
 void blu_free_text(char* text);
 
+/* Options the request above has no room for (its size is pinned).  Set struct_size = sizeof(blu_consensus_extras) and zero the
+ * rest: options are added at the end; a size the library does not know is BLU_ERR_INVALID_ARG.
+ *
+ * count_table_path: a feature x sample count table (vsearch --otutabout, usearch -otutab, biom convert
+ * --to-tsv), tab-separated.  Blank lines are skipped; leading lines that start with '#' and hold no tab are comments; the first
+ * other line is the header: its first cell is ignored, every further cell a sample name (non-empty, unique, at least one).
+ * Every later line: a row name, then one cell per sample — ASCII digits, optionally '.' and only zeros, value < 2^32.  Anything
+ * else is BLU_ERR_PARSE naming line and column.  "\r\n" line ends are accepted.  Rows and queries (with hits or header-only)
+ * are joined on their names up to the first ';': two rows or two queries with one key, or a query no row has, are
+ * BLU_ERR_INVALID_ARG naming them; a row no query has counts as unclassified.  With a table the report weighs a query by its
+ * row sum (2^32 or more: BLU_ERR_INVALID_ARG naming the row) and the sample table's columns are all samples of the header
+ * (ascending bytewise), a query adding its count in sample s to column s.  It needs report_path or sample_table_path and weight
+ * BLU_REPORT_WEIGHT_ONE (else BLU_ERR_INVALID_ARG); the document and the support table are not touched by it.  All refusals
+ * come before any file is written. */
+typedef struct blu_count_table_stats { uint64_t n_rows, n_samples, n_joined, n_rows_unclassified; } blu_count_table_stats;
+typedef struct blu_consensus_extras {
+    uint32_t struct_size; uint32_t reserved;    /* options are added at the end; a size the library does not know is INVALID_ARG */
+    const char* count_table_path;               /* NULL: none */
+    blu_count_table_stats* count_table_stats;   /* caller's, or NULL; zeroed when the call begins */
+} blu_consensus_extras;
+/* blu_build_consensus(request, outcome) is blu_build_consensus_with(request, NULL, outcome). */
+int blu_build_consensus_with(const blu_consensus_request* request, const blu_consensus_extras* extras /* NULL = none */,
+                             blu_consensus_outcome* outcome);
+
 /* The reference's own three signatures, each the request above with the named fields set and the rest zero
  * (mod.rs:40-47 + write_blutils_output.rs:33-38 with config = None; the same with Some(BlastBuilder); the same to a file).
  * out_len and stats may be NULL. */
