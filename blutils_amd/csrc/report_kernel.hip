@@ -38,6 +38,8 @@ constexpr uint32_t LDS_SLOTS = 2048;            // block-local leaf table (24 KB
 constexpr uint32_t LDS_PROBE = 8;
 constexpr uint32_t REPORT_PROBE_FIRST = 128;
 constexpr uint32_t FLAG_OVERFLOW = 1u, FLAG_BAD_RECORD = 2u;
+constexpr uint32_t FLAG_BAD_NODE = 16u;              // (4 and 8 are the sample table's)
+constexpr uint32_t CTL_WORDS = 7, CTL_BAD_NODE = 6;   // ctl[]: what every entry point allocates and clears
 
 struct ReportDev {
     const uint32_t* lin;          // TaxDev rows
@@ -54,7 +56,7 @@ struct ReportDev {
     unsigned long long* direct;   // [cap]
     uint32_t cap_mask;
     uint32_t max_probe;
-    unsigned long long* ctl;      // {unclassified, unplaced, flags, bad query}
+    unsigned long long* ctl;      // [CTL_WORDS] {unclassified, unplaced, flags, bad query, .., .., the query of a bad node}
 };
 
 __device__ __forceinline__ uint32_t mix_key(unsigned long long k) {   // murmur3 fmix64
@@ -62,7 +64,9 @@ __device__ __forceinline__ uint32_t mix_key(unsigned long long k) {   // murmur3
     return (uint32_t)k;
 }
 
-// slot of (parent, node), inserted if new; REPORT_NONE when max_probe slots were all taken by other keys
+// slot of (parent, node), inserted if new; REPORT_NONE when max_probe slots were all taken by other keys.  The key of a
+// first-level node 0xFFFFFFFF would be REPORT_EMPTY itself (an empty slot would read as found): the walks refuse that
+// node before they come here (reserved_first).
 __device__ __forceinline__ uint32_t intern(const ReportDev& d, uint32_t parent, uint32_t node) {
     const unsigned long long key = ((unsigned long long)parent << 32) | node;
     uint32_t h = mix_key(key) & d.cap_mask;
@@ -76,6 +80,8 @@ __device__ __forceinline__ uint32_t intern(const ReportDev& d, uint32_t parent, 
     }
     return REPORT_NONE;
 }
+
+__device__ __forceinline__ bool reserved_first(uint32_t parent, uint32_t node) { return (parent & node) == REPORT_NONE; }
 
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -115,10 +121,12 @@ __global__ __launch_bounds__(RB) void report_paths(ReportDev d) {
         bool ok = true;
         for (uint32_t j = 0; j < len; ++j) {
             if (!((m >> j) & 1ull)) continue;
-            path = intern(d, path, lin[d.node_base + j]);
-            if (path == REPORT_NONE) { ok = false; break; }
+            const uint32_t node = lin[d.node_base + j];
+            if (reserved_first(path, node)) { flags |= FLAG_BAD_NODE; d.ctl[CTL_BAD_NODE] = q; ok = false; break; }
+            path = intern(d, path, node);
+            if (path == REPORT_NONE) { flags |= FLAG_OVERFLOW; ok = false; break; }
         }
-        if (!ok) { flags |= FLAG_OVERFLOW; continue; }
+        if (!ok) continue;
         // direct count of the leaf: block-local table first, global memory when it is crowded
         uint32_t h = (path * 2654435761u) >> 21;                        // 11 bits: LDS_SLOTS
         bool done = false;
@@ -276,7 +284,9 @@ __global__ __launch_bounds__(RB) void sample_cells(SampleDev d) {
         uint32_t path = REPORT_NONE;
         for (uint32_t j = 0; j < len; ++j) {
             if (!((m >> j) & 1ull)) continue;
-            path = intern(d.r, path, lin[d.r.node_base + j]);
+            const uint32_t node = lin[d.r.node_base + j];
+            if (reserved_first(path, node)) { flags |= FLAG_BAD_NODE; d.r.ctl[CTL_BAD_NODE] = q; break; }
+            path = intern(d.r, path, node);
             if (path == REPORT_NONE) { flags |= FLAG_OVERFLOW; break; }
             if (w) add(path, s, w);
         }
@@ -370,15 +380,18 @@ __global__ __launch_bounds__(RB) void count_cells(CountDev d) {
             if (m != 0) {
                 const uint32_t node = lane < len ? lin[r.node_base + lane] : 0u;   // lane j: the node of level j
                 uint32_t path = REPORT_NONE;
+                bool bad_node = false;
                 n_levels = 0;
                 for (unsigned long long t = m; t; t &= t - 1ull, ++n_levels) {
                     const uint32_t nd = __shfl(node, __ffsll(t) - 1, 64);
+                    if (reserved_first(path, nd)) { bad_node = true; break; }
                     uint32_t p = REPORT_NONE;
                     if (lane == 0) p = intern(r, path, nd);
                     path = __shfl(p, 0, 64);
                     if (path == REPORT_NONE) break;
                     if (lane == n_levels) mine = path;
                 }
+                if (bad_node) { flags |= FLAG_BAD_NODE; if (lane == 0) r.ctl[CTL_BAD_NODE] = q; continue; }
                 if (path == REPORT_NONE) { flags |= FLAG_OVERFLOW; continue; }
             }
         }
@@ -546,7 +559,7 @@ int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* ou
     uint32_t* d_at = nullptr;
     void* d_tmp = nullptr;
     blu_report_path* d_paths = nullptr;
-    unsigned long long ctl[4] = {0, 0, 0, 0};
+    unsigned long long ctl[CTL_WORDS] = {};
     uint64_t cap = 0, n_paths = 0;
     uint32_t attempts = 0;
     std::vector<blu_report_path> paths;
@@ -556,7 +569,7 @@ int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* ou
     hipEvent_t &ev0 = ev.ev0, &ev1 = ev.ev1;
     HIP_CHECK(pol, hipEventCreate(&ev0));
     HIP_CHECK(pol, hipEventCreate(&ev1));
-    HIP_CHECK(pol, mem.alloc(&d_ctl, 4 * 8, "counters"));
+    HIP_CHECK(pol, mem.alloc(&d_ctl, sizeof ctl, "counters"));
     {
         const uint64_t guess = std::min<uint64_t>(nq * std::max<uint32_t>(tax->max_depth, 1), 2 * tax->n_tax + 4096);
         cap = std::max<uint64_t>(next_pow2(2 * guess), 1024);
@@ -574,7 +587,7 @@ int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* ou
             HIP_CHECK(pol, mem.alloc(&d_direct, cap * 8, "path table"));
             HIP_CHECK(pol, hipMemsetAsync(d_keys, 0xFF, cap * 8, nullptr));
             HIP_CHECK(pol, hipMemsetAsync(d_direct, 0, cap * 8, nullptr));
-            HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, 4 * 8, nullptr));
+            HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, sizeof ctl, nullptr));
             d.keys = d_keys; d.direct = d_direct; d.cap_mask = (uint32_t)(cap - 1); d.max_probe = max_probe;
             if (nq) hipLaunchKernelGGL(report_paths, dim3((unsigned)((nq + RB * RQ - 1) / (RB * RQ))), dim3(RB), 0, 0, d);
             HIP_CHECK(pol, hipGetLastError());
@@ -582,6 +595,11 @@ int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* ou
             if (ctl[2] & FLAG_BAD_RECORD) {
                 set_error("report: record %llu has a taxon (status 0 / 1) but its reference row names no taxonomy row",
                           (unsigned long long)ctl[3]);
+                return BLU_ERR_INVALID_ARG;
+            }
+            if (ctl[2] & FLAG_BAD_NODE) {
+                set_error("report: record %llu has a path that begins with node id 0xFFFFFFFF, which no path may begin with",
+                          (unsigned long long)ctl[CTL_BAD_NODE]);
                 return BLU_ERR_INVALID_ARG;
             }
             if (!(ctl[2] & FLAG_OVERFLOW)) break;
@@ -647,7 +665,7 @@ int sample_table_device(const blu_taxonomy* tax, const ReportInput& in, const ui
                         blu_sample_table* out) {
     const uint64_t nq = in.n_queries;
     unsigned long long *d_keys = nullptr, *d_ckeys = nullptr, *d_cval = nullptr, *d_ctl = nullptr, *d_fixed = nullptr;
-    unsigned long long ctl[5] = {0, 0, 0, 0, 0};
+    unsigned long long ctl[CTL_WORDS] = {};
     uint64_t cap = 0, ccap = 0;
     const uint64_t fixed_bytes = 2 * (uint64_t)n_samples * 8;
     HipPolicy pol{"sample table", BLU_ERR_ALLOC};
@@ -703,6 +721,11 @@ int sample_table_device(const blu_taxonomy* tax, const ReportInput& in, const ui
                           (unsigned long long)ctl[3]);
                 return BLU_ERR_INVALID_ARG;
             }
+            if (ctl[2] & FLAG_BAD_NODE) {
+                set_error("sample table: record %llu has a path that begins with node id 0xFFFFFFFF, which no path may begin with",
+                          (unsigned long long)ctl[CTL_BAD_NODE]);
+                return BLU_ERR_INVALID_ARG;
+            }
             if (!(ctl[2] & FLAG_OVERFLOW)) break;
             if (max_probe != REPORT_PROBE_FIRST) { set_error("sample table: table overflow"); return BLU_ERR_HIP; }   // (cannot happen at load <= 1/2)
             // the estimate was short: both tables again from zero, sized from the bound on paths and on cells
@@ -724,7 +747,7 @@ int sample_table_counts_device(const blu_taxonomy* tax, const ReportInput& in, c
                                blu_sample_table* out) {
     const uint64_t nq = in.n_queries;
     unsigned long long *d_keys = nullptr, *d_ckeys = nullptr, *d_cval = nullptr, *d_ctl = nullptr, *d_fixed = nullptr;
-    unsigned long long ctl[6] = {0, 0, 0, 0, 0, 0};
+    unsigned long long ctl[CTL_WORDS] = {};
     const uint64_t fixed_bytes = 2 * (uint64_t)n_samples * 8;
     HipPolicy pol{"count table", BLU_ERR_ALLOC};
     DeviceArena mem(pol);
@@ -784,6 +807,11 @@ int sample_table_counts_device(const blu_taxonomy* tax, const ReportInput& in, c
         if (ctl[2] & FLAG_BAD_RECORD) {
             set_error("count table: record %llu has a taxon (status 0 / 1) but its reference row names no taxonomy row",
                       (unsigned long long)ctl[3]);
+            return BLU_ERR_INVALID_ARG;
+        }
+        if (ctl[2] & FLAG_BAD_NODE) {
+            set_error("count table: record %llu has a path that begins with node id 0xFFFFFFFF, which no path may begin with",
+                      (unsigned long long)ctl[CTL_BAD_NODE]);
             return BLU_ERR_INVALID_ARG;
         }
         if (!(ctl[2] & FLAG_OVERFLOW)) break;

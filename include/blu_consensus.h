@@ -274,7 +274,9 @@ int blu_consensus_last_launch(char* kernel_name, size_t len, uint32_t* grid, uin
 #define BLU_REPORT_NO_PARENT 0xFFFFFFFFu
 
 typedef struct blu_report_path {
-    uint32_t node;     /* interned node id of the last element (blu_taxonomy_desc.lin_node) */
+    uint32_t node;     /* interned node id of the last element (blu_taxonomy_desc.lin_node).  A path may not BEGIN with node id
+                          0xFFFFFFFF (elsewhere in a path it is an id like any other): the report and both sample-table calls
+                          refuse such a record with BLU_ERR_INVALID_ARG, naming it. */
     uint32_t parent;   /* index of the path one element shorter in blu_report.paths, BLU_REPORT_NO_PARENT for a first element */
     uint64_t direct;
     uint64_t clade;
