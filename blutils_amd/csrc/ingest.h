@@ -162,6 +162,8 @@ int download_columns(HitTable& ht);
 // queue another 0.04-0.17 s: whoever comes first pays); the use-case starts it on a thread of its own before it reads
 // the taxonomy file, so that part of that time passes beside host work.  Errors are left to the calls that follow.
 void warm_up_device(int device);
+// (its share for engine_dev.hip: the runtime loads that translation unit's code object; hidden, as load_dev_prims is)
+__attribute__((visibility("hidden"))) void load_engine_dev();
 
 // The engine on the columns the GPU ingest left on the device: taxonomy rows -> engine row ids (fwd = blu_taxonomy_row_map's
 // forward table), perc_identity as milli-percent when every value is exactly k/1000 (checked on the device), one

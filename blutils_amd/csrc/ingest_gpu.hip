@@ -5,14 +5,16 @@
 // taxid), for files in the plain form BLAST writes; any other file (quotes, empty lines, odd numbers) is handed back
 // to the CPU path untouched (BLU_INGEST_FALLBACK).
 //
-// Stages (all on the handle's device; the kernels on the default stream):
-//   0. upload          pread() into pinned staging slots -> HBM, three reader threads, all copies on the null stream;
-//                      the file is never mapped into the process
-//   1. line index      newline count per 4 KiB tile -> exclusive scan -> line starts
+// This file holds the parser, the hit and taxon filters, the dictionaries, the grouping, and the host code that runs them:
+// GpuIngest, whose steps are the stages below.  The upload and the threaded download are dev_io.cpp; the line index, the
+// prefix sums, the radix sort and the column compaction are dev_prims.hip (both behind ingest_prims.h); the engine on the
+// columns left here is engine_dev.hip.  All on the handle's device, the kernels on the default stream:
+//   0. upload          pread() into pinned staging slots -> HBM (dev_io.cpp: the file is never mapped into the process)
+//   1. line index      newline count per 4 KiB tile -> exclusive scan -> line starts (dev_prims.hip)
 //   2. parse           one thread per line: tab scan over aligned 16-byte loads, decimal fast path for the four numeric
 //                      columns (mantissa <= 15 digits and |exp10| <= 22: one IEEE operation, so the value is strtod's),
 //                      taxid -> taxonomy row through the uploaded open-addressing map, two 64-bit hashes of the query
-//                      and accession fields
+//                      and accession fields; under a hit or taxon filter a keep word per line, and the kept rows compacted
 //   3. dictionaries    open-addressing tables keyed by hash (insert = CAS on the hash + atomicMin of the row), finalised
 //                      with length + first 12 key bytes; every row then verifies its own text against its slot (a
 //                      mismatch = two strings with one 64-bit hash -> fallback), so ids are exact, not probabilistic
@@ -21,34 +23,27 @@
 //                      thread of its own while the device builds the query dictionary) and the ranks uploaded
 //   5. grouping        stable radix sort by query id unless the file is grouped already; gathers; segment offsets
 //   6. hand-over       the grouped columns stay on the device for the engine (host copies only on request); the distinct
-//                      query / accession strings come back packed and a background thread turns them into the host
-//                      tables; after the engine, top_rows_kernel compacts the top-score rows of the rendered queries —
-//                      all the writer reads of the table
-// Every kernel of the ingest is written here — the device-wide prefix sums, block-level sums and scans, the parsing and dictionary
-// kernels, and the stable radix sort that regroups the rows of a file whose queries are not contiguous; no device library is
-// called.  HBM-bound byte work: no MFMA.
+//                      query / accession strings come back packed and a background thread turns them into the host tables
+// HBM-bound byte work: no MFMA.
 #include <hip/hip_runtime.h>
-#include <cstring>
 #include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
-#include <cerrno>
 #include <cmath>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <string_view>
 #include <thread>
-#include <type_traits>
 #include <vector>
 
 #include "blu_consensus.h"
 #include "hit_pass.h"
 #include "ingest.h"
 #include "taxid_probe.h"
+#include "wave_scan.h"
 
 namespace blu {
 namespace {
@@ -64,241 +59,6 @@ struct Slot {            // 32 bytes
     uint32_t len;
     unsigned char head[12];
 };
-
-// ---- block-level sum and exclusive scan: 64-wide wavefronts reduce / scan in registers (DPP), the wave totals meet in LDS ----
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true); }
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {   // inclusive prefix sum over the 64 lanes
-    v += dpp_u32<0x111>(v);                                        // row_shr:1, :2, :4, :8 (zero shifted in): prefix inside each 16-lane row
-    v += dpp_u32<0x112>(v);
-    v += dpp_u32<0x114>(v);
-    v += dpp_u32<0x118>(v);
-    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)v, 15), t1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 31),
-                   t2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 47);
-    const uint32_t r = lane >> 4;
-    return v + (r == 0 ? 0u : (r == 1 ? t0 : (r == 2 ? t0 + t1 : t0 + t1 + t2)));
-}
-// sum over the block in every thread's return value; `wave_sums` = LDS, one word per wave
-template <int THREADS>
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* wave_sums) {
-    const uint32_t incl = wave_incl_scan(v);
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) wave_sums[wave] = incl;
-    __syncthreads();
-    uint32_t total = 0;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; ++w) total += wave_sums[w];
-    __syncthreads();
-    return total;
-}
-// exclusive prefix of v over the block
-template <int THREADS>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wave_sums) {
-    const uint32_t incl = wave_incl_scan(v);
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) wave_sums[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; ++w) before += (uint32_t)w < wave ? wave_sums[w] : 0u;
-    __syncthreads();
-    return before + incl - v;
-}
-
-// ---- device-wide exclusive prefix sum (u32 / u64), three launches: sums of 4096-element blocks, a one-block scan of those sums,
-// the blocks again with their offsets.  The arrays scanned here are bookkeeping (newline counts per 4 KiB tile, string lengths,
-// top-row counts: 2 M elements at most per 100 M rows), so reading them twice costs microseconds; written here rather than
-// taken from a library so that the ingest's device code is the kernels in this file plus two radix sorts.
-constexpr int SCAN_THREADS = 1024, SCAN_ITEMS = 4, SCAN_BLOCK = SCAN_THREADS * SCAN_ITEMS;
-
-template <class T>
-__device__ __forceinline__ T wave_incl_scan_t(T v) {
-    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) { const T u = __shfl_up(v, d); if (lane >= d) v += u; }
-    return v;
-}
-// exclusive prefix of v over the 1024 threads of the block, and the block's total; `wave_tot` = LDS, 16 entries
-template <class T>
-__device__ __forceinline__ T block_excl_scan_t(T v, T* wave_tot, T* total) {
-    const T incl = wave_incl_scan_t(v);
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < SCAN_THREADS / 64; ++w) { const T x = wave_tot[w]; all += x; if (w < wave) before += x; }
-    __syncthreads();
-    *total = all;
-    return before + incl - v;
-}
-template <class T>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_block_sums(const T* __restrict__ in, size_t n, T* __restrict__ block_sum) {
-    __shared__ T wave_tot[SCAN_THREADS / 64];
-    const size_t base = ((size_t)blockIdx.x * SCAN_THREADS + threadIdx.x) * SCAN_ITEMS;
-    T v = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) if (base + k < n) v += in[base + k];
-    T total;
-    (void)block_excl_scan_t(v, wave_tot, &total);
-    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
-}
-template <class T>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_block_offsets(const T* __restrict__ block_sum, size_t n_blocks, T* __restrict__ block_off) {
-    __shared__ T wave_tot[SCAN_THREADS / 64];
-    T carry = 0;
-    for (size_t b0 = 0; b0 < n_blocks; b0 += SCAN_THREADS) {        // (one block: the sums of 4096-element blocks are few)
-        const size_t b = b0 + threadIdx.x;
-        const T v = b < n_blocks ? block_sum[b] : (T)0;
-        T total;
-        const T ex = block_excl_scan_t(v, wave_tot, &total);
-        if (b < n_blocks) block_off[b] = carry + ex;
-        carry += total;
-    }
-}
-template <class T>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_apply(const T* __restrict__ in, size_t n, const T* __restrict__ block_off, T* __restrict__ out) {
-    __shared__ T wave_tot[SCAN_THREADS / 64];
-    const size_t base = ((size_t)blockIdx.x * SCAN_THREADS + threadIdx.x) * SCAN_ITEMS;
-    T x[SCAN_ITEMS], v = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) { x[k] = base + k < n ? in[base + k] : (T)0; v += x[k]; }
-    T total;
-    T run = block_off[blockIdx.x] + block_excl_scan_t(v, wave_tot, &total);
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) { if (base + k < n) out[base + k] = run; run += x[k]; }
-}
-template <class T> size_t scan_tmp_bytes(size_t n) { return 2 * ((n + SCAN_BLOCK - 1) / SCAN_BLOCK) * sizeof(T) + 16; }
-// out[i] = in[0] + ... + in[i - 1] for i < n, modulo 2^(8 sizeof(T)); in == out is allowed: scan_block_sums only reads, and
-// scan_apply reads each element into a register of the thread that writes it back (tests/test_gpu_prims.py checks both
-// ways).  tmp: scan_tmp_bytes<T>(n) bytes of device memory
-template <class T>
-hipError_t exclusive_scan_dev(const T* in, T* out, size_t n, void* tmp) {
-    if (n == 0) return hipSuccess;
-    const size_t n_blocks = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    T* const block_sum = (T*)tmp;
-    T* const block_off = block_sum + n_blocks;
-    hipLaunchKernelGGL((scan_block_sums<T>), dim3((unsigned)n_blocks), dim3(SCAN_THREADS), 0, 0, in, n, block_sum);
-    hipLaunchKernelGGL((scan_block_offsets<T>), dim3(1), dim3(SCAN_THREADS), 0, 0, (const T*)block_sum, n_blocks, block_off);
-    hipLaunchKernelGGL((scan_apply<T>), dim3((unsigned)n_blocks), dim3(SCAN_THREADS), 0, 0, in, n, (const T*)block_off, out);
-    return hipGetLastError();
-}
-
-// ---- stable radix sort of (key, value) pairs of 32-bit words, least significant digit first, 8 bits per pass: regroups the rows
-// of a file whose queries are not contiguous (key = query id, value = row: file order inside a query survives because every
-// pass is stable).  Per pass: a 256-bin histogram per 4096-element block, one prefix sum over the (digit, block) table, and a
-// scatter in which an element's place = the table's entry for (its digit, its block) + the elements of that digit before it
-// in the block — counted per round of 1024 by wave (ballot match masks: the rank inside the wave) and across waves in LDS.
-constexpr int RS_THREADS = 1024, RS_ITEMS = 4, RS_BLOCK = RS_THREADS * RS_ITEMS;
-
-__global__ __launch_bounds__(RS_THREADS) void radix_hist(const uint32_t* __restrict__ keys, uint32_t n, uint32_t shift, uint32_t n_blocks,
-                                                         uint32_t* __restrict__ hist) {
-    __shared__ uint32_t h[256];
-    if (threadIdx.x < 256) h[threadIdx.x] = 0;
-    __syncthreads();
-    const size_t base = (size_t)blockIdx.x * RS_BLOCK;
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; ++r) {
-        const size_t i = base + (size_t)r * RS_THREADS + threadIdx.x;
-        if (i < n) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < 256) hist[(size_t)threadIdx.x * n_blocks + blockIdx.x] = h[threadIdx.x];   // digit-major: the prefix sum runs over digits, then blocks
-}
-
-__global__ __launch_bounds__(RS_THREADS) void radix_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, uint32_t n,
-                                                            uint32_t shift, uint32_t n_blocks, const uint32_t* __restrict__ offs,
-                                                            uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out) {
-    __shared__ uint32_t next[256];                           // where the block's next element of each digit goes
-    __shared__ uint32_t wcount[RS_THREADS / 64][256];        // this round: elements per (wave, digit), then their first place
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    if (tid < 256) next[tid] = offs[(size_t)tid * n_blocks + blockIdx.x];
-    const size_t base = (size_t)blockIdx.x * RS_BLOCK;
-    for (int r = 0; r < RS_ITEMS; ++r) {
-        for (uint32_t k = tid; k < (RS_THREADS / 64) * 256; k += RS_THREADS) (&wcount[0][0])[k] = 0;
-        __syncthreads();
-        const size_t i = base + (size_t)r * RS_THREADS + tid;
-        const bool valid = i < n;
-        const uint32_t key = valid ? keys_in[i] : 0u, d = (key >> shift) & 255u;
-        unsigned long long same = __ballot(valid);           // lanes of this wave with a valid element of the same digit
-#pragma unroll
-        for (int b = 0; b < 8; ++b) { const unsigned long long bb = __ballot((d >> b) & 1u); same &= ((d >> b) & 1u) ? bb : ~bb; }
-        const uint32_t rank_in_wave = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
-        if (valid && rank_in_wave == 0) wcount[wave][d] = (uint32_t)__popcll(same);
-        __syncthreads();
-        if (tid < 256) {                                      // digit `tid`: the waves' first places, in wave order
-            uint32_t run = next[tid];
-#pragma unroll
-            for (uint32_t w = 0; w < RS_THREADS / 64; ++w) { const uint32_t c = wcount[w][tid]; wcount[w][tid] = run; run += c; }
-            next[tid] = run;
-        }
-        __syncthreads();
-        if (valid) { const uint32_t at = wcount[wave][d] + rank_in_wave; keys_out[at] = key; vals_out[at] = vals_in[i]; }
-        __syncthreads();
-    }
-}
-
-// sorts n pairs by the low 8 * ceil(bits / 8) bits of the key (callers pass keys < 2^bits, so: by the key); the sorted arrays are
-// (*keys, *vals) on return (the two buffers of each swap roles per pass).  table: 2 x 256 x ceil(n / 4096) words of device memory; scan_tmp: scan_tmp_bytes<uint32_t>(256 x ceil(n / 4096))
-static hipError_t radix_sort_pairs_dev(uint32_t** keys, uint32_t** keys_alt, uint32_t** vals, uint32_t** vals_alt, uint32_t n, int bits,
-                                       uint32_t* table, void* scan_tmp) {
-    if (n == 0) return hipSuccess;
-    const uint32_t n_blocks = (uint32_t)(((size_t)n + RS_BLOCK - 1) / RS_BLOCK);
-    const size_t cells = (size_t)256 * n_blocks;
-    uint32_t* const hist = table;
-    uint32_t* const offs = table + cells;
-    for (int shift = 0; shift < bits; shift += 8) {
-        hipLaunchKernelGGL(radix_hist, dim3(n_blocks), dim3(RS_THREADS), 0, 0, (const uint32_t*)*keys, n, (uint32_t)shift, n_blocks, hist);
-        const hipError_t e = exclusive_scan_dev<uint32_t>(hist, offs, cells, scan_tmp);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(radix_scatter, dim3(n_blocks), dim3(RS_THREADS), 0, 0, (const uint32_t*)*keys, (const uint32_t*)*vals, n, (uint32_t)shift, n_blocks,
-                           (const uint32_t*)offs, *keys_alt, *vals_alt);
-        std::swap(*keys, *keys_alt);
-        std::swap(*vals, *vals_alt);
-    }
-    return hipGetLastError();
-}
-
-// ---- 1. line index ---------------------------------------------------------------------------------------
-constexpr int TILE_THREADS = 256;
-constexpr uint64_t TILE_BYTES = TILE_THREADS * 16;
-
-__device__ __forceinline__ uint32_t nl_mask16(const uint4 v, uint64_t base, uint64_t size) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    uint32_t m = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const uint32_t c = (w[k >> 2] >> (8 * (k & 3))) & 0xFF;
-        if (c == '\n' && base + k < size) m |= 1u << k;
-    }
-    return m;
-}
-
-__global__ __launch_bounds__(TILE_THREADS) void count_newlines(const uint4* __restrict__ text, uint64_t size, uint32_t* __restrict__ tile_count) {
-    const uint64_t base = ((uint64_t)blockIdx.x * TILE_THREADS + threadIdx.x) * 16;
-    uint32_t c = 0;
-    if (base < size) c = __popc(nl_mask16(text[base / 16], base, size));
-    __shared__ uint32_t wave_sums[TILE_THREADS / 64];
-    const uint32_t total = block_sum<TILE_THREADS>(c, wave_sums);
-    if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(TILE_THREADS) void write_line_starts(const uint4* __restrict__ text, uint64_t size, const uint32_t* __restrict__ tile_base,
-                                                                  uint64_t* __restrict__ line_start) {
-    const uint64_t base = ((uint64_t)blockIdx.x * TILE_THREADS + threadIdx.x) * 16;
-    uint32_t m = 0;
-    if (base < size) m = nl_mask16(text[base / 16], base, size);
-    __shared__ uint32_t wave_sums[TILE_THREADS / 64];
-    const uint32_t before = block_excl_scan<TILE_THREADS>((uint32_t)__popc(m), wave_sums);
-    uint64_t k = (uint64_t)tile_base[blockIdx.x] + before;
-    while (m) {
-        const int b = __ffs(m) - 1;
-        m &= m - 1;
-        line_start[++k] = base + b + 1;     // line k+1 starts after newline k
-    }
-}
-
 // ---- 2. parse (the taxid join: taxid_probe.h) ------------------------------------------------------------------
 __device__ const double P10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
 
@@ -681,29 +441,6 @@ __global__ void apply_decisions(const uint32_t* __restrict__ rows, const uint32_
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n && rows[k] < n_rows) keep[rows[k]] = decision[k] ? KEEP_YES : KEEP_NO;
 }
-// One column of the parsed rows: element i goes to out[pos[i]] when keep[i] is set, pos = the exclusive prefix sum of the keep
-// words — so file order survives and nothing is placed by an atomic.  A thread takes 16 bytes of the column (two 8-byte or
-// four 4-byte elements) and their keep words in one load each; the kept elements of neighbouring lanes land next to each
-// other.  n_out = the kept count: no store goes beyond it whatever the keep words hold.
-constexpr int COMPACT_THREADS = 256;
-template <class T>
-__global__ __launch_bounds__(COMPACT_THREADS) void compact_column(const T* __restrict__ in, const uint32_t* __restrict__ keep,
-                                                                  const uint32_t* __restrict__ pos, uint32_t n, uint32_t n_out, T* __restrict__ out) {
-    constexpr uint32_t V = 16 / sizeof(T);
-    struct alignas(16) Elems { T v[V]; };
-    struct alignas(4 * V) Keeps { uint32_t k[V]; };
-    const uint64_t base = ((uint64_t)blockIdx.x * COMPACT_THREADS + threadIdx.x) * V;
-    if (base >= n) return;
-    uint32_t at = pos[base];
-    if (base + V <= n) {
-        const Elems x = *reinterpret_cast<const Elems*>(in + base);
-        const Keeps k = *reinterpret_cast<const Keeps*>(keep + base);
-#pragma unroll
-        for (uint32_t j = 0; j < V; ++j) if (k.k[j] == KEEP_YES && at < n_out) out[at++] = x.v[j];
-    } else {
-        for (uint64_t j = base; j < n; ++j) if (keep[j] == KEEP_YES && at < n_out) out[at++] = in[j];
-    }
-}
 __global__ __launch_bounds__(1024) void count_unmatched(const uint32_t* __restrict__ tax, uint32_t n, unsigned long long* __restrict__ count) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     __shared__ uint32_t wave_sums[1024 / 64];
@@ -930,147 +667,7 @@ struct IngestTrace {
         tp = t;
     }
 };
-
 }  // namespace
-
-// ---- the ingest's pieces for the other GPU programs (ingest_prims.h): host wrappers, the kernels stay here
-uint64_t line_tiles(uint64_t size) { return (size + TILE_BYTES - 1) / TILE_BYTES; }
-hipError_t line_count(const unsigned char* d_text, uint64_t size, uint32_t* d_tile, uint32_t* d_base, void* d_tmp, uint32_t* n_newlines) {
-    const uint64_t n_tiles = line_tiles(size);
-    if (n_tiles) hipLaunchKernelGGL(count_newlines, dim3((unsigned)n_tiles), dim3(TILE_THREADS), 0, 0, (const uint4*)d_text, size, d_tile);
-    hipError_t e = hipMemset(d_tile + n_tiles, 0, 4);
-    if (e == hipSuccess) e = exclusive_scan_dev<uint32_t>(d_tile, d_base, (size_t)n_tiles + 1, d_tmp);   // (also reports the launch above)
-    if (e == hipSuccess) e = hipMemcpy(n_newlines, d_base + n_tiles, 4, hipMemcpyDeviceToHost);
-    return e;
-}
-hipError_t line_write(const unsigned char* d_text, uint64_t size, const uint32_t* d_base, uint64_t* d_line, uint64_t n_lines, bool open_tail) {
-    const uint64_t n_tiles = line_tiles(size);
-    hipError_t e = hipMemset(d_line, 0, 8);
-    if (e != hipSuccess) return e;
-    if (n_tiles) hipLaunchKernelGGL(write_line_starts, dim3((unsigned)n_tiles), dim3(TILE_THREADS), 0, 0, (const uint4*)d_text, size, d_base, d_line);
-    e = hipGetLastError();
-    if (e != hipSuccess || !open_tail) return e;
-    const uint64_t end = size + 1;
-    return hipMemcpy(d_line + n_lines, &end, 8, hipMemcpyHostToDevice);
-}
-size_t scan_tmp_bytes_u32(size_t n) { return scan_tmp_bytes<uint32_t>(n); }
-size_t scan_tmp_bytes_u64(size_t n) { return scan_tmp_bytes<unsigned long long>(n); }
-hipError_t exclusive_scan_u32(const uint32_t* in, uint32_t* out, size_t n, void* tmp) { return exclusive_scan_dev<uint32_t>(in, out, n, tmp); }
-hipError_t exclusive_scan_u64(const unsigned long long* in, unsigned long long* out, size_t n, void* tmp) {
-    return exclusive_scan_dev<unsigned long long>(in, out, n, tmp);
-}
-hipError_t compact_column_u32(const uint32_t* in, const uint32_t* keep, const uint32_t* pos, uint32_t n, uint32_t n_out, uint32_t* out) {
-    if (n) hipLaunchKernelGGL((compact_column<uint32_t>), grid(n, COMPACT_THREADS * 4), dim3(COMPACT_THREADS), 0, 0, in, keep, pos, n, n_out, out);
-    return hipGetLastError();
-}
-hipError_t compact_column_u64(const unsigned long long* in, const uint32_t* keep, const uint32_t* pos, uint32_t n, uint32_t n_out,
-                              unsigned long long* out) {
-    if (n) hipLaunchKernelGGL((compact_column<unsigned long long>), grid(n, COMPACT_THREADS * 2), dim3(COMPACT_THREADS), 0, 0, in, keep, pos, n, n_out, out);
-    return hipGetLastError();
-}
-size_t radix_table_words(uint32_t n) { return (size_t)2 * 256 * (((size_t)n + RS_BLOCK - 1) / RS_BLOCK); }
-size_t radix_scan_tmp_bytes(uint32_t n) { return scan_tmp_bytes<uint32_t>((size_t)256 * (((size_t)n + RS_BLOCK - 1) / RS_BLOCK)); }
-hipError_t radix_sort_pairs(uint32_t** keys, uint32_t** keys_alt, uint32_t** vals, uint32_t** vals_alt, uint32_t n, int bits,
-                            uint32_t* table, void* scan_tmp) {
-    return radix_sort_pairs_dev(keys, keys_alt, vals, vals_alt, n, bits, table, scan_tmp);
-}
-
-// The text goes page cache -> pinned staging -> HBM without ever being mapped into the process: three reader threads,
-// each with two pinned slots, pread() a piece while the previous one is on the wire.  What the parts cost on a box
-// (scripts/probe/upload_probe.hip, 6.7 GB): the copies alone 0.12 s (56 GB/s, the PCIe rate; one stream carries 50 of it),
-// pread alone 30 GB/s per thread, so two or three readers keep the wire busy — and EVERY hipStreamCreate 15 ms (the first
-// one of the process 40-170 ms: an HSA queue each).  Six readers with a stream and a hipHostMalloc each, as this was
-// written first, spent more time setting up than copying.  Hence: one pinned block for all slots, and all copies on the
-// null stream, which the kernels that follow need anyway (in order on one queue: a slot's event still says when it is free).
-// Mapping the file and handing it to hipMemcpy moves the bytes as fast (the runtime pins the page-cache pages) but
-// costs 0.06 s to populate and 0.07-0.10 s to unmap 6.7 GB of page table.
-int upload_file(int fd, size_t size, unsigned char* d_text, int device, std::string* err) {
-    unsigned nt = 3;
-    if (const char* env = getenv("BLU_UPLOAD_THREADS")) nt = (unsigned)atoi(env);
-    const size_t piece = 8u << 20, n_pieces = (size + piece - 1) / piece;
-    nt = std::max(1u, std::min<unsigned>(std::min(nt, 16u), (unsigned)std::max<size_t>(n_pieces, 1)));
-    std::atomic<size_t> next{0};
-    std::atomic<int> failed{0};      // 1: the file could not be read; 2: the staging path could not be set up or used (HIP)
-    std::vector<std::string> errs(nt + 1);
-    auto fail = [&](unsigned t, const char* what, hipError_t e) {
-        errs[t] = std::string(what) + ": " + (e == hipSuccess ? strerror(errno) : hipGetErrorString(e));
-        int none = 0;
-        failed.compare_exchange_strong(none, e == hipSuccess ? 1 : 2);
-    };
-    char* block = nullptr;
-    std::vector<hipEvent_t> events((size_t)nt * 2, nullptr);
-    const bool trace = getenv("BLU_INGEST_TRACE") != nullptr;
-    const double t_in = now_s();
-    hipError_t e0 = hipHostMalloc((void**)&block, (size_t)nt * 2 * piece, hipHostMallocDefault);
-    for (size_t k = 0; k < events.size() && e0 == hipSuccess; ++k) e0 = hipEventCreateWithFlags(&events[k], hipEventDisableTiming);
-    if (e0 != hipSuccess) fail(nt, "staging set-up", e0);
-    const double t_setup = now_s();
-    auto work = [&](unsigned t) {
-        char* const slots = block + (size_t)t * 2 * piece;
-        hipEvent_t* const ev = &events[(size_t)t * 2];
-        bool busy[2] = {false, false};
-        hipError_t e = hipSetDevice(device);
-        if (e != hipSuccess) fail(t, "hipSetDevice", e);
-        unsigned turn = 0;
-        while (!failed.load(std::memory_order_relaxed)) {
-            const size_t k = next.fetch_add(1);
-            if (k >= n_pieces) break;
-            const unsigned sl = turn++ & 1;
-            if (busy[sl] && (e = hipEventSynchronize(ev[sl])) != hipSuccess) { fail(t, "hipEventSynchronize", e); break; }
-            const size_t off = k * piece, len = std::min(piece, size - off);
-            size_t got = 0;
-            while (got < len) {
-                const ssize_t r = pread(fd, slots + sl * piece + got, len - got, (off_t)(off + got));
-                if (r < 0 && errno == EINTR) continue;
-                if (r <= 0) { fail(t, "pread", hipSuccess); break; }
-                got += (size_t)r;
-            }
-            if (got < len) break;
-            if ((e = hipMemcpyAsync(d_text + off, slots + sl * piece, len, hipMemcpyHostToDevice, nullptr)) != hipSuccess) { fail(t, "hipMemcpyAsync", e); break; }
-            if ((e = hipEventRecord(ev[sl], nullptr)) != hipSuccess) { fail(t, "hipEventRecord", e); break; }
-            busy[sl] = true;
-        }
-    };
-    if (!failed) {
-        std::vector<std::thread> pool;
-        for (unsigned t = 1; t < nt; ++t) pool.emplace_back(work, t);
-        work(0);
-        for (auto& th : pool) th.join();
-    }
-    {   // the slots are free once everything queued has been sent (also on the way out of a failure: copies may be in flight)
-        const double t_queued = now_s();
-        const hipError_t e = hipStreamSynchronize(nullptr);
-        if (e != hipSuccess && !failed) fail(nt, "hipStreamSynchronize", e);
-        if (trace) fprintf(stderr, "[ingest-gpu]   upload: pinned block + events %.3f s, pieces read and queued %.3f s, last ones on the wire %.3f s\n",
-                           t_setup - t_in, t_queued - t_setup, now_s() - t_queued);
-    }
-    for (hipEvent_t ev : events) if (ev) (void)hipEventDestroy(ev);
-    if (block) (void)hipHostFree(block);
-    if (failed) {
-        for (auto& m : errs) if (!m.empty()) { *err = m; break; }
-        (void)hipGetLastError();
-        return failed == 1 ? BLU_ERR_IO : BLU_INGEST_FALLBACK;   // (no pinned memory to be had, say: the CPU parser takes the file)
-    }
-    return BLU_OK;
-}
-
-int upload_text(int fd, size_t size, int device, const char* name, DeviceArena& mem, unsigned char** d_text, bool* open_tail,
-                const std::function<void()>& allocated) {
-    HipPolicy& pol = mem.pol;
-    HIP_CHECK(pol, mem.alloc(d_text, ((size + 15) & ~(size_t)15) + 64, name));
-    HIP_CHECK(pol, hipMemset(*d_text + size, 0, 64));
-    if (allocated) allocated();
-    *open_tail = false;
-    if (size == 0) return BLU_OK;
-    std::string io;
-    const int rc = upload_file(fd, size, *d_text, device, &io);
-    if (rc == BLU_INGEST_FALLBACK && pol.why) { *pol.why = "the pinned staging path failed (" + io + ")"; return rc; }
-    if (rc != BLU_OK) { set_error("%s: reading %s failed: %s", pol.who, name, io.c_str()); return rc == BLU_ERR_IO ? BLU_ERR_IO : BLU_ERR_HIP; }
-    char last = 0;
-    if (pread(fd, &last, 1, (off_t)(size - 1)) != 1) { set_error("%s: reading %s failed", pol.who, name); return BLU_ERR_IO; }
-    *open_tail = last != '\n';
-    return BLU_OK;
-}
 
 // (defined in consensus_kernel.hip; named here only so that the warm-up can ask for its attributes, which makes the runtime load
 // the code object of that translation unit — the two dozen builds of the consensus kernels — ahead of the engine stage)
@@ -1085,6 +682,9 @@ void warm_up_device(int device) {
         hipLaunchKernelGGL(iota_u32, dim3(1), dim3(64), 0, nullptr, (uint32_t*)p, 64u);
         hipFuncAttributes attr;
         (void)hipFuncGetAttributes(&attr, (const void*)blu_classify_tasks);
+        // the two other translation units the default path runs kernels of: the line index and the engine's packing
+        load_dev_prims();
+        load_engine_dev();
         (void)hipStreamSynchronize(nullptr);
         (void)hipFree(p);
     }
@@ -1114,55 +714,103 @@ DevFilter device_filter(const blu_hit_filter& f) {
     return d;
 }
 
-// load_hits_gpu's work on the device, in the arena the caller frees; any failure returns at once
-int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, DeviceArena& mem,
-                     IngestTrace& lap, const blu_hit_filter* flt, TaxonCodes* taxa) {
-    HipPolicy& pol = mem.pol;
-    auto fallback = [&](const char* reason) { *pol.why = reason; return BLU_INGEST_FALLBACK; };
-    unsigned char* d_text = nullptr;
-    uint32_t *d_tile = nullptr, *d_tile_base = nullptr, *d_flags = nullptr, *d_counter = nullptr;
-    uint64_t* d_line = nullptr;
-    void* d_tmp = nullptr;
+#define STEP(x) do { if (const int rc_ = (x)) return rc_; } while (0)
+
+// One call of the GPU ingest on the device: the inputs, the arena the caller frees, and what the steps of run() hand from one to
+// the next.  Any other device buffer is a step's own: allocated in it, and freed in it or left to the arena.  A step that fails
+// returns at once (a HIP error through HIP_CHECK, a file for the CPU parser through fallback()).
+struct GpuIngest {
+    const int fd;
+    const size_t size;
+    const TaxidMap& row_of;
+    const int device;
+    const bool host_columns;
+    HitTable& ht;
+    DeviceArena& mem;
+    HipPolicy& pol;
+    IngestTrace& lap;
+    const blu_hit_filter* const flt;   // (null: none)
+    TaxonCodes* const taxa;            // (null: none)
+
+    unsigned char* d_text = nullptr;   // the padded text: upload_and_index -> accession_dictionary_finish, which frees it
+    uint64_t* d_line = nullptr;        // line starts: upload_and_index -> parse, drop_filtered_rows (which frees them)
+    uint32_t n_rows = 0;               // lines; from drop_filtered_rows on, the kept ones
+    // {flags, -, -, -, counter, -, -, -, big counters}: the fall-back bits, one 32-bit count, [0] unmatched rows [1] run heads;
+    // under a filter the parse's counts follow (n_back): upload_and_index -> every step
+    uint32_t *d_flags = nullptr, *d_counter = nullptr;
+    unsigned long long* d_big = nullptr;
+    void* d_tmp = nullptr;             // scan scratch, grown by need_tmp: every step
     size_t tmp_bytes = 0;
-    TaxidMap::E* d_taxmap = nullptr;
-    unsigned long long *d_qh = nullptr, *d_ah = nullptr, *d_qpos = nullptr, *d_apos = nullptr, *d_big = nullptr, *d_poslist = nullptr, *d_aposlist = nullptr;
-    uint32_t *d_tax = nullptr, *d_qid = nullptr, *d_arank = nullptr, *d_list_row = nullptr, *d_list_slot = nullptr, *d_alist_row = nullptr, *d_alist_slot = nullptr, *d_mark = nullptr,
-             *d_rank_of_row = nullptr, *d_perm = nullptr, *d_perm2 = nullptr, *d_qid2 = nullptr, *d_ranks = nullptr;
-    double *d_pid = nullptr, *d_pid2 = nullptr;
-    int32_t *d_aln = nullptr, *d_bs = nullptr, *d_aln2 = nullptr, *d_bs2 = nullptr;
-    uint32_t *d_tax2 = nullptr, *d_arank2 = nullptr;
-    Slot *d_qtab = nullptr, *d_atab = nullptr;
-    unsigned long long* d_seg = nullptr;
-    uint32_t h_flags = 0, n_rows = 0, n_queries = 0, n_acc = 0;
+    // the eight parsed-row arrays: parse -> the dictionaries (hashes, field places) and group (the four values)
+    unsigned long long *d_qh = nullptr, *d_ah = nullptr, *d_qpos = nullptr, *d_apos = nullptr;
+    uint32_t* d_tax = nullptr;
+    double* d_pid = nullptr;
+    int32_t *d_aln = nullptr, *d_bs = nullptr;
+    // a filtered parse -> drop_filtered_rows: the keep words, the filter and the row codes as the kernel read them, the counts
+    uint32_t* d_keep = nullptr;
+    DevFilterTaxa* d_filter = nullptr;                   // (its first member is the DevFilter parse_rows_filtered reads)
+    uint16_t* d_code = nullptr;
+    std::vector<unsigned long long> back;
+    // accession_dictionary_begin -> accession_dictionary_finish: the table, its slots, the slot of every distinct accession
+    Slot* d_atab = nullptr;
+    uint64_t acap = 0;
+    uint32_t* d_alist_slot = nullptr;
+    uint32_t n_acc = 0;
     // the distinct query / accession strings packed back to back (bytes + n + 1 offsets) and the accessions' byte order:
-    // what the strings thread started at the end needs
+    // the dictionaries -> hand_over's strings thread
     std::vector<char> q_bytes, a_bytes;
     std::vector<unsigned long long> q_off, a_off;
     std::vector<uint32_t> order;
     std::vector<unsigned long long> k0, k1;      // first 16 bytes of every distinct accession as two big-endian words
-    uint64_t acap = 0;                           // slots of the accession table
     std::thread acc_sort;                        // the host's sort of the distinct accessions, beside the query dictionary
     std::atomic<bool> acc_sort_failed{false};
-    struct JoinSort { std::thread& t; ~JoinSort() { if (t.joinable()) t.join(); } } join_acc_sort{acc_sort};
-    const uint64_t n_tiles = line_tiles(size);
-    auto need_tmp = [&](size_t bytes) -> hipError_t {
+    uint32_t n_queries = 0;
+    uint32_t *d_qid = nullptr, *d_arank = nullptr;   // ids of the rows: the dictionaries -> group
+    ColsOut grouped{};                               // group -> hand_over
+    unsigned long long* d_seg = nullptr;
+
+    ~GpuIngest() { if (acc_sort.joinable()) acc_sort.join(); }   // (whichever way run() is left)
+
+    int run() {
+        STEP(upload_and_index());             lap("line index");
+        STEP(parse());
+        STEP(drop_filtered_rows());           lap("parse");
+        STEP(accession_dictionary_begin());
+        STEP(query_dictionary());             lap("query dictionary");
+        STEP(accession_dictionary_finish());  lap("accession dictionary");
+        STEP(group());                        lap("grouping");
+        return hand_over();
+    }
+
+    // ---- what the steps share
+    int fallback(const char* reason) { *pol.why = reason; return BLU_INGEST_FALLBACK; }
+    int fall_back_on(uint32_t h_flags) { return h_flags ? fallback(fallback_text(h_flags)) : BLU_OK; }
+    // the flag word the kernels left: a set bit hands the file to the CPU parser
+    int check_flags() {
+        uint32_t h_flags = 0;
+        HIP_CHECK(pol, hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
+        return fall_back_on(h_flags);
+    }
+    int zero_counter() { HIP_CHECK(pol, hipMemset(d_counter, 0, 4)); return BLU_OK; }
+    size_t n_back() const { return 8 + HIT_SPREAD + 1 + (taxa ? HIT_SPREAD + (size_t)taxa->n_exclude : 0); }
+    hipError_t need_tmp(size_t bytes) {
         if (bytes <= tmp_bytes) return hipSuccess;
         if (d_tmp) mem.free(d_tmp);
         d_tmp = nullptr; tmp_bytes = 0;
         hipError_t e = mem.alloc(&d_tmp, bytes, "scan scratch");
         if (e == hipSuccess) tmp_bytes = bytes;
         return e;
-    };
+    }
     // distinct strings at d_pos[0 .. n) of the device text -> host
-    auto download_strings = [&](const unsigned long long* d_pos, uint32_t n, std::vector<char>& bytes, std::vector<unsigned long long>& off) -> int {
+    int download_strings(const unsigned long long* d_pos, uint32_t n, std::vector<char>& bytes, std::vector<unsigned long long>& off) {
         unsigned long long *d_len = nullptr, *d_off = nullptr;
         unsigned char* d_out = nullptr;
         off.assign((size_t)n + 1, 0);
         HIP_CHECK(pol, mem.alloc(&d_len, ((size_t)n + 1) * 8, "string offsets"));
         HIP_CHECK(pol, mem.alloc(&d_off, ((size_t)n + 1) * 8, "string offsets"));
         hipLaunchKernelGGL(pos_lengths, dim3((n + 256) / 256), dim3(256), 0, 0, d_pos, n, d_len);
-        HIP_CHECK(pol, need_tmp(scan_tmp_bytes<unsigned long long>((size_t)n + 1)));
-        HIP_CHECK(pol, exclusive_scan_dev<unsigned long long>(d_len, d_off, (size_t)n + 1, d_tmp));
+        HIP_CHECK(pol, need_tmp(scan_tmp_bytes_u64((size_t)n + 1)));
+        HIP_CHECK(pol, exclusive_scan_u64(d_len, d_off, (size_t)n + 1, d_tmp));
         HIP_CHECK(pol, hipMemcpy(off.data(), d_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost));
         bytes.resize(off[n]);
         HIP_CHECK(pol, mem.alloc(&d_out, off[n], "strings"));
@@ -1170,29 +818,40 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
         HIP_CHECK(pol, hipMemcpy(bytes.data(), d_out, off[n], hipMemcpyDeviceToHost));
         mem.free(d_len); mem.free(d_off); mem.free(d_out);
         return BLU_OK;
-    };
+    }
+    // an empty table of cap slots, the hashes h[0, n_rows) inserted (only_heads: dict_insert), the keys counted: their number
+    // and the flag word come back
+    int build_dictionary(Slot* tab, uint64_t cap, const unsigned long long* h, bool only_heads, bool clear_flags, uint32_t* n_keys,
+                         uint32_t* h_flags) {
+        hipLaunchKernelGGL(dict_init, grid(cap), dim3(256), 0, 0, tab, cap);   // empty slots, first_row = all ones for atomicMin
+        STEP(zero_counter());
+        if (clear_flags) HIP_CHECK(pol, hipMemset(d_flags, 0, 4));
+        hipLaunchKernelGGL(dict_insert, grid(n_rows), dim3(256), 0, 0, h, n_rows, tab, cap - 1, only_heads, d_counter, d_flags);
+        hipLaunchKernelGGL(dict_count, grid(cap, 1024), dim3(1024), 0, 0, tab, cap, d_counter);
+        HIP_CHECK(pol, hipMemcpy(n_keys, d_counter, 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(h_flags, d_flags, 4, hipMemcpyDeviceToHost));
+        return BLU_OK;
+    }
 
     // ---- upload + line index
-    lap("device start-up");
-    bool open_tail = false;
-    {
+    int upload_and_index() {
+        lap("device start-up");
+        bool open_tail = false;
         // (the device-buffer lap times the padding only: the readers' pieces end at `size`)
-        const int rc = upload_text(fd, size, device, "the table", mem, &d_text, &open_tail, [&] { lap("  upload: device buffer"); });
-        if (rc != BLU_OK) return rc;
-    }
-    lap("upload text");
-    HIP_CHECK(pol, mem.alloc(&d_tile, (n_tiles + 1) * 4, "line index"));
-    HIP_CHECK(pol, mem.alloc(&d_tile_base, (n_tiles + 1) * 4, "line index"));
-    // {flags, -, -, -, counter, -, -, -, big counters}; under a hit filter the kept / undecided counts follow, and under a taxon
-    // filter the not-only counts and one count per exclude element after them: all of it comes back in one copy
-    const size_t n_back = 8 + HIT_SPREAD + 1 + (taxa ? HIT_SPREAD + (size_t)taxa->n_exclude : 0);
-    const size_t flag_bytes = flt || taxa ? n_back * 8 : 64;
-    HIP_CHECK(pol, mem.alloc(&d_flags, flag_bytes, "flags"));
-    HIP_CHECK(pol, hipMemset(d_flags, 0, flag_bytes));
-    d_counter = d_flags + 4;                                         // {flags, -, -, -, counter, -, big counters at +8}
-    d_big = reinterpret_cast<unsigned long long*>(d_flags + 8);      // [0] unmatched rows, [1] run heads
-    HIP_CHECK(pol, need_tmp(scan_tmp_bytes<uint32_t>((size_t)n_tiles + 1)));
-    {
+        STEP(upload_text(fd, size, device, "the table", mem, &d_text, &open_tail, [&] { lap("  upload: device buffer"); }));
+        lap("upload text");
+        const uint64_t n_tiles = line_tiles(size);
+        uint32_t *d_tile = nullptr, *d_tile_base = nullptr;
+        HIP_CHECK(pol, mem.alloc(&d_tile, (n_tiles + 1) * 4, "line index"));
+        HIP_CHECK(pol, mem.alloc(&d_tile_base, (n_tiles + 1) * 4, "line index"));
+        // under a hit filter the kept / undecided counts follow the big counters, and under a taxon filter the not-only counts
+        // and one count per exclude element after them: all of it comes back in one copy
+        const size_t flag_bytes = flt || taxa ? n_back() * 8 : 64;
+        HIP_CHECK(pol, mem.alloc(&d_flags, flag_bytes, "flags"));
+        HIP_CHECK(pol, hipMemset(d_flags, 0, flag_bytes));
+        d_counter = d_flags + 4;
+        d_big = reinterpret_cast<unsigned long long*>(d_flags + 8);
+        HIP_CHECK(pol, need_tmp(scan_tmp_bytes_u32((size_t)n_tiles + 1)));
         uint32_t n_newlines = 0;
         HIP_CHECK(pol, line_count(d_text, size, d_tile, d_tile_base, d_tmp, &n_newlines));
         const uint64_t rows64 = (uint64_t)n_newlines + (open_tail ? 1 : 0);
@@ -1201,282 +860,272 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
         if (n_rows == 0) return fallback("no rows");
         HIP_CHECK(pol, mem.alloc(&d_line, ((size_t)n_rows + 2) * 8, "line index"));
         HIP_CHECK(pol, line_write(d_text, size, d_tile_base, d_line, n_rows, open_tail));
+        return BLU_OK;
     }
-    lap("line index");
 
-    // ---- parse
-    HIP_CHECK(pol, mem.upload(&d_taxmap, row_of.tab.data(), row_of.tab.size(), "taxid map"));
-    HIP_CHECK(pol, mem.alloc(&d_qh, (size_t)n_rows * 8, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_ah, (size_t)n_rows * 8, "parsed rows"));
-    HIP_CHECK(pol, mem.alloc(&d_qpos, (size_t)n_rows * 8, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_apos, (size_t)n_rows * 8, "parsed rows"));
-    HIP_CHECK(pol, mem.alloc(&d_tax, (size_t)n_rows * 4, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_pid, (size_t)n_rows * 8, "parsed rows"));
-    HIP_CHECK(pol, mem.alloc(&d_aln, (size_t)n_rows * 4, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_bs, (size_t)n_rows * 4, "parsed rows"));
-    if (!flt && !taxa) {
-        RowOut o{d_qh, d_ah, d_qpos, d_apos, d_tax, d_pid, d_aln, d_bs};
-        DevTaxidMap tm{d_taxmap, row_of.tab.size() - 1};
-        hipLaunchKernelGGL(parse_rows, grid(n_rows, PARSE_THREADS), dim3(PARSE_THREADS), 0, 0, d_text, d_line, n_rows, tm, o, d_flags, d_big);
-        HIP_CHECK(pol, hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
-        if (h_flags) return fallback(fallback_text(h_flags));
-    } else {
-        // ---- hit filter: the filtered parse leaves a keep word per line; the kept and undecided counts come
-        // back with the flags; the rows are compacted in file order before anything else sees them
-        uint32_t *d_keep = nullptr, *d_kpos = nullptr;
-        DevFilterTaxa* d_filter = nullptr;                           // (its first member is the DevFilter parse_rows_filtered reads)
-        uint16_t* d_code = nullptr;
+    // ---- parse: one of the three builds of parse_rows.  Under a filter it leaves a keep word per line, and
+    // its counts come back with the flags in `back`
+    int parse() {
+        TaxidMap::E* d_taxmap = nullptr;
+        HIP_CHECK(pol, mem.upload(&d_taxmap, row_of.tab.data(), row_of.tab.size(), "taxid map"));
+        HIP_CHECK(pol, mem.alloc(&d_qh, (size_t)n_rows * 8, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_ah, (size_t)n_rows * 8, "parsed rows"));
+        HIP_CHECK(pol, mem.alloc(&d_qpos, (size_t)n_rows * 8, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_apos, (size_t)n_rows * 8, "parsed rows"));
+        HIP_CHECK(pol, mem.alloc(&d_tax, (size_t)n_rows * 4, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_pid, (size_t)n_rows * 8, "parsed rows"));
+        HIP_CHECK(pol, mem.alloc(&d_aln, (size_t)n_rows * 4, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_bs, (size_t)n_rows * 4, "parsed rows"));
+        const RowOut o{d_qh, d_ah, d_qpos, d_apos, d_tax, d_pid, d_aln, d_bs};
+        const DevTaxidMap tm{d_taxmap, row_of.tab.size() - 1};
+        const dim3 blocks(grid(n_rows, PARSE_THREADS)), threads(PARSE_THREADS);
+        if (!flt && !taxa) {
+            hipLaunchKernelGGL(parse_rows, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, d_big);
+            return check_flags();
+        }
         HIP_CHECK(pol, mem.alloc(&d_keep, (size_t)n_rows * 4, "keep words"));
         HIP_CHECK(pol, mem.alloc(&d_filter, sizeof(DevFilterTaxa), "hit filter"));
         unsigned long long* const d_fcnt = reinterpret_cast<unsigned long long*>(d_flags + 16);
         DevFilterTaxa hf{};
         if (flt) hf.f = device_filter(*flt);                         // (no threshold beside a taxon filter: an empty mask keeps every line)
         hf.f.keep = d_keep; hf.f.counts = d_fcnt;
-        RowOut o{d_qh, d_ah, d_qpos, d_apos, d_tax, d_pid, d_aln, d_bs};
-        DevTaxidMap tm{d_taxmap, row_of.tab.size() - 1};
-        std::vector<unsigned long long> back(n_back);
         if (!taxa) {
             HIP_CHECK(pol, hipMemcpy(d_filter, &hf.f, sizeof hf.f, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(parse_rows_filtered, grid(n_rows, PARSE_THREADS), dim3(PARSE_THREADS), 0, 0, d_text, d_line, n_rows, tm, o, d_flags,
-                               (const DevFilter*)&d_filter->f);
+            hipLaunchKernelGGL(parse_rows_filtered, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilter*)&d_filter->f);
         } else {
-            // ---- taxon filter: the row codes go up next to the taxid map; the verdict is taken in the parse
+            // the row codes go up next to the taxid map; the verdict is taken in the parse
             const size_t n_tax = taxa->code.size();
             HIP_CHECK(pol, mem.upload(&d_code, taxa->code.data(), n_tax, "taxon codes"));
             hf.t.code = d_code; hf.t.n_tax = (uint32_t)n_tax; hf.t.unmatched = taxa->unmatched;
             hf.t.not_only = d_fcnt + HIT_SPREAD + 1; hf.t.excluded_by = hf.t.not_only + HIT_SPREAD;
             HIP_CHECK(pol, hipMemcpy(d_filter, &hf, sizeof hf, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(parse_rows_taxa, grid(n_rows, PARSE_THREADS), dim3(PARSE_THREADS), 0, 0, d_text, d_line, n_rows, tm, o, d_flags,
-                               (const DevFilterTaxa*)d_filter);
+            hipLaunchKernelGGL(parse_rows_taxa, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilterTaxa*)d_filter);
         }
-        HIP_CHECK(pol, hipMemcpy(back.data(), d_flags, n_back * 8, hipMemcpyDeviceToHost));
-        h_flags = (uint32_t)back[0];
-        if (h_flags) return fallback(fallback_text(h_flags));
+        back.resize(n_back());
+        HIP_CHECK(pol, hipMemcpy(back.data(), d_flags, n_back() * 8, hipMemcpyDeviceToHost));
+        return fall_back_on((uint32_t)back[0]);
+    }
+
+    // ---- after a filtered parse: the e-values the device left open are decided, the rows are compacted in file order before
+    // anything else sees them, the unmatched rows are counted over what is left
+    int drop_filtered_rows() {
+        if (!flt && !taxa) return BLU_OK;
         uint64_t n_kept = spread_sum(back.data() + 8, 0);
         const uint64_t n_ask = back[8 + HIT_SPREAD];
+        const unsigned long long* const tb = back.data() + 8 + HIT_SPREAD + 1;   // (under a taxon filter: not-only, then per element)
         uint64_t n_excluded = 0, n_not_only = 0;
         if (taxa) {
-            const unsigned long long* tb = back.data() + 8 + HIT_SPREAD + 1;
             n_not_only = spread_sum(tb, 0);
             for (uint32_t k = 0; k < taxa->n_exclude; ++k) n_excluded += tb[HIT_SPREAD + k];
             if (n_excluded + n_not_only + n_kept + n_ask > n_rows) return fallback("inconsistent taxon-filter counts");
         }
         lap("parse (filtered)");
-        if (n_ask) {
-            // e-values the device left open (as a rule: fields spelled like the threshold): the host decides them from the
-            // file's bytes with the host parser's own number reader and sends the decisions back
-            if (n_kept + n_ask > n_rows) return fallback("inconsistent hit-filter counts");
-            const uint32_t n_u = (uint32_t)n_ask;
-            uint32_t *d_urow = nullptr, *d_udec = nullptr;
-            unsigned long long* d_upos = nullptr;
-            HIP_CHECK(pol, mem.alloc(&d_urow, (size_t)n_u * 4, "undecided e-values")); HIP_CHECK(pol, mem.alloc(&d_upos, (size_t)n_u * 8, "undecided e-values"));
-            HIP_CHECK(pol, mem.alloc(&d_udec, (size_t)n_u * 4, "undecided e-values"));
-            HIP_CHECK(pol, hipMemset(d_urow, 0xFF, (size_t)n_u * 4));
-            HIP_CHECK(pol, hipMemset(d_upos, 0, (size_t)n_u * 8));
-            HIP_CHECK(pol, hipMemset(d_counter, 0, 4));
-            hipLaunchKernelGGL(list_undecided, grid(n_rows), dim3(256), 0, 0, (const uint32_t*)d_keep, n_rows, d_text, d_line, n_u, d_urow, d_upos, d_counter);
-            std::vector<char> e_bytes;
-            std::vector<unsigned long long> e_off;
-            if (const int rc = download_strings(d_upos, n_u, e_bytes, e_off); rc != BLU_OK) return rc;
-            std::vector<uint32_t> dec(n_u);
-            for (uint32_t k = 0; k < n_u; ++k) {
-                double v = 0;
-                if (!parse_f64_field(e_bytes.data() + e_off[k], (size_t)(e_off[k + 1] - e_off[k]), &v)) return fallback("an e-value the host parser reads differently");
-                dec[k] = flt && v <= flt->max_e_value ? 1u : 0u;
-                n_kept += dec[k];
-            }
-            HIP_CHECK(pol, hipMemcpy(d_udec, dec.data(), (size_t)n_u * 4, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(apply_decisions, grid(n_u), dim3(256), 0, 0, (const uint32_t*)d_urow, (const uint32_t*)d_udec, n_u, n_rows, d_keep);
-            mem.free(d_urow); mem.free(d_upos); mem.free(d_udec);
-            lap("  filter: e-values decided on the host");
-        }
+        if (n_ask) STEP(decide_e_values_on_host((uint32_t)n_ask, &n_kept));
         if (n_kept > n_rows) return fallback("inconsistent hit-filter counts");
         const uint64_t n_lines = n_rows;
         if (n_kept == 0) return fallback("no rows kept by the filters");   // (the host parser returns the empty table)
-        if (n_kept < n_rows) {
-            // stable compaction, one column after another through ONE spare buffer (hit_pass.h: Compaction), 8-byte columns
-            // first.  Peak: the eight arrays (52 B / line) + keep words and their scan (8 B / line) + 8 B / kept line.
-            const uint32_t n_out = (uint32_t)n_kept;
-            HIP_CHECK(pol, mem.alloc(&d_kpos, (size_t)n_rows * 4, "keep positions"));
-            HIP_CHECK(pol, need_tmp(scan_tmp_bytes<uint32_t>((size_t)n_rows)));
-            HIP_CHECK(pol, exclusive_scan_dev<uint32_t>(d_keep, d_kpos, (size_t)n_rows, d_tmp));
-            Compaction cp{d_keep, d_kpos, n_rows, n_out, nullptr};
-            HIP_CHECK(pol, mem.alloc(&cp.spare, (size_t)n_out * 8, "compaction spare"));
-            HIP_CHECK(pol, cp.rotate(d_qh, d_ah, d_qpos, d_apos, d_pid, d_tax, d_aln, d_bs));
-            mem.free(cp.spare); mem.free(d_kpos);
-            n_rows = n_out;
-            lap("  filter: compaction");
-        }
+        if (n_kept < n_rows) STEP(compact_rows((uint32_t)n_kept));
         mem.free(d_keep); mem.free(d_filter);
         if (d_code) mem.free(d_code);
         mem.free(d_line); d_line = nullptr;
         hipLaunchKernelGGL(count_unmatched, grid(n_rows, 1024), dim3(1024), 0, 0, (const uint32_t*)d_tax, n_rows, d_big);
         ht.n_lines = n_lines; ht.n_kept = n_kept;
         if (taxa) {
-            const unsigned long long* tb = back.data() + 8 + HIT_SPREAD + 1 + HIT_SPREAD;
             taxa->n_excluded = n_excluded; taxa->n_not_only = n_not_only;
-            taxa->excluded_by.assign(tb, tb + taxa->n_exclude);
+            taxa->excluded_by.assign(tb + HIT_SPREAD, tb + HIT_SPREAD + taxa->n_exclude);
         }
+        return BLU_OK;
     }
-    lap("parse");
+    // e-values the device left open (as a rule: fields spelled like the threshold): the host decides them from the file's bytes
+    // with the host parser's own number reader and sends the decisions back
+    int decide_e_values_on_host(uint32_t n_u, uint64_t* n_kept) {
+        if (*n_kept + n_u > n_rows) return fallback("inconsistent hit-filter counts");
+        uint32_t *d_urow = nullptr, *d_udec = nullptr;
+        unsigned long long* d_upos = nullptr;
+        HIP_CHECK(pol, mem.alloc(&d_urow, (size_t)n_u * 4, "undecided e-values")); HIP_CHECK(pol, mem.alloc(&d_upos, (size_t)n_u * 8, "undecided e-values"));
+        HIP_CHECK(pol, mem.alloc(&d_udec, (size_t)n_u * 4, "undecided e-values"));
+        HIP_CHECK(pol, hipMemset(d_urow, 0xFF, (size_t)n_u * 4));
+        HIP_CHECK(pol, hipMemset(d_upos, 0, (size_t)n_u * 8));
+        STEP(zero_counter());
+        hipLaunchKernelGGL(list_undecided, grid(n_rows), dim3(256), 0, 0, (const uint32_t*)d_keep, n_rows, d_text, d_line, n_u, d_urow, d_upos, d_counter);
+        std::vector<char> e_bytes;
+        std::vector<unsigned long long> e_off;
+        STEP(download_strings(d_upos, n_u, e_bytes, e_off));
+        std::vector<uint32_t> dec(n_u);
+        for (uint32_t k = 0; k < n_u; ++k) {
+            double v = 0;
+            if (!parse_f64_field(e_bytes.data() + e_off[k], (size_t)(e_off[k + 1] - e_off[k]), &v)) return fallback("an e-value the host parser reads differently");
+            dec[k] = flt && v <= flt->max_e_value ? 1u : 0u;
+            *n_kept += dec[k];
+        }
+        HIP_CHECK(pol, hipMemcpy(d_udec, dec.data(), (size_t)n_u * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(apply_decisions, grid(n_u), dim3(256), 0, 0, (const uint32_t*)d_urow, (const uint32_t*)d_udec, n_u, n_rows, d_keep);
+        mem.free(d_urow); mem.free(d_upos); mem.free(d_udec);
+        lap("  filter: e-values decided on the host");
+        return BLU_OK;
+    }
+    // stable compaction, one column after another through ONE spare buffer (hit_pass.h: Compaction), 8-byte columns first.
+    // Peak: the eight arrays (52 B / line) + keep words and their scan (8 B / line) + 8 B / kept line.
+    int compact_rows(uint32_t n_out) {
+        uint32_t* d_kpos = nullptr;
+        HIP_CHECK(pol, mem.alloc(&d_kpos, (size_t)n_rows * 4, "keep positions"));
+        HIP_CHECK(pol, need_tmp(scan_tmp_bytes_u32((size_t)n_rows)));
+        HIP_CHECK(pol, exclusive_scan_u32(d_keep, d_kpos, (size_t)n_rows, d_tmp));
+        Compaction cp{d_keep, d_kpos, n_rows, n_out, nullptr};
+        HIP_CHECK(pol, mem.alloc(&cp.spare, (size_t)n_out * 8, "compaction spare"));
+        HIP_CHECK(pol, cp.rotate(d_qh, d_ah, d_qpos, d_apos, d_pid, d_tax, d_aln, d_bs));
+        mem.free(cp.spare); mem.free(d_kpos);
+        n_rows = n_out;
+        lap("  filter: compaction");
+        return BLU_OK;
+    }
 
     // ---- accession dictionary, first half: distinct count unknown; the table grows until the load stays under one half.
     // (It comes before the query dictionary so that the host's sort of the distinct accessions — 12 ms for 300 k — runs on a
     // thread of its own while the device builds the query dictionary.)
-    {
+    int accession_dictionary_begin() {
         uint64_t cap = pow2_at_least(std::min<uint64_t>((uint64_t)n_rows * 2 + 16, 1ull << 20));   // (32 MB: stays in the caches while 100 M rows probe it; x4 when more than half full)
         for (;;) {
             HIP_CHECK(pol, mem.alloc(&d_atab, cap * sizeof(Slot), "accession table"));
             lap("  acc: table allocation");
-            hipLaunchKernelGGL(dict_init, grid(cap), dim3(256), 0, 0, d_atab, cap);
-            HIP_CHECK(pol, hipMemset(d_counter, 0, 4));
-            HIP_CHECK(pol, hipMemset(d_flags, 0, 4));
-            hipLaunchKernelGGL(dict_insert, grid(n_rows), dim3(256), 0, 0, d_ah, n_rows, d_atab, cap - 1, false, d_counter, d_flags);
-            hipLaunchKernelGGL(dict_count, grid(cap, 1024), dim3(1024), 0, 0, d_atab, cap, d_counter);
-            HIP_CHECK(pol, hipMemcpy(&n_acc, d_counter, 4, hipMemcpyDeviceToHost));
-            HIP_CHECK(pol, hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
+            uint32_t h_flags = 0;
+            STEP(build_dictionary(d_atab, cap, d_ah, /* only_heads */ false, /* clear_flags */ true, &n_acc, &h_flags));
             if (!(h_flags & FB_TABLE_FULL) && (uint64_t)n_acc * 2 <= cap) break;
             mem.free(d_atab); d_atab = nullptr;
             if (cap >= pow2_at_least((uint64_t)n_rows * 2 + 16)) return fallback(fallback_text(FB_TABLE_FULL));
             cap *= 4;
         }
+        acap = cap;
         lap("  acc: insert");
+        uint32_t* d_alist_row = nullptr;
+        unsigned long long* d_aposlist = nullptr;
         HIP_CHECK(pol, hipMemset(d_flags, 0, 4));
         HIP_CHECK(pol, mem.alloc(&d_alist_row, (size_t)n_acc * 4, "accession list")); HIP_CHECK(pol, mem.alloc(&d_alist_slot, (size_t)n_acc * 4, "accession list"));
-        HIP_CHECK(pol, hipMemset(d_counter, 0, 4));
+        STEP(zero_counter());
         hipLaunchKernelGGL(dict_finalize, grid(cap), dim3(256), 0, 0, d_atab, cap, d_text, d_apos, d_alist_row, d_alist_slot, d_counter);
         HIP_CHECK(pol, mem.alloc(&d_aposlist, (size_t)n_acc * 8, "accession list"));
         hipLaunchKernelGGL(gather_pos, grid(n_acc), dim3(256), 0, 0, d_apos, d_alist_row, n_acc, d_aposlist);
-        if (const int rc = download_strings(d_aposlist, n_acc, a_bytes, a_off); rc != BLU_OK) return rc;
+        STEP(download_strings(d_aposlist, n_acc, a_bytes, a_off));
         lap("  acc: distinct to host");
         // byte order of the distinct accessions (String::cmp), on the host: only the distinct strings are touched, and
         // mostly not even those — the GPU hands over their first 16 bytes as two big-endian integers; the text is read
         // only to order keys that agree on all 16
         k0.resize(n_acc); k1.resize(n_acc);
-        {
-            unsigned long long *d_k0 = nullptr, *d_k1 = nullptr;
-            HIP_CHECK(pol, mem.alloc(&d_k0, (size_t)n_acc * 8 + 8, "accession keys"));
-            HIP_CHECK(pol, mem.alloc(&d_k1, (size_t)n_acc * 8 + 8, "accession keys"));
-            hipLaunchKernelGGL(gather_key16, grid(n_acc), dim3(256), 0, 0, d_aposlist, n_acc, d_text, d_k0, d_k1);
-            HIP_CHECK(pol, hipMemcpy(k0.data(), d_k0, (size_t)n_acc * 8, hipMemcpyDeviceToHost));
-            HIP_CHECK(pol, hipMemcpy(k1.data(), d_k1, (size_t)n_acc * 8, hipMemcpyDeviceToHost));
-            mem.free(d_k0);
-            mem.free(d_k1);
-        }
-        acap = cap;
+        unsigned long long *d_k0 = nullptr, *d_k1 = nullptr;
+        HIP_CHECK(pol, mem.alloc(&d_k0, (size_t)n_acc * 8 + 8, "accession keys"));
+        HIP_CHECK(pol, mem.alloc(&d_k1, (size_t)n_acc * 8 + 8, "accession keys"));
+        hipLaunchKernelGGL(gather_key16, grid(n_acc), dim3(256), 0, 0, d_aposlist, n_acc, d_text, d_k0, d_k1);
+        HIP_CHECK(pol, hipMemcpy(k0.data(), d_k0, (size_t)n_acc * 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(pol, hipMemcpy(k1.data(), d_k1, (size_t)n_acc * 8, hipMemcpyDeviceToHost));
+        mem.free(d_k0);
+        mem.free(d_k1);
         order.resize(n_acc);
         for (uint32_t k = 0; k < n_acc; ++k) order[k] = k;
-        acc_sort = std::thread([&]() {
-            try {
-                auto view = [&](uint32_t k) { return std::string_view(a_bytes.data() + a_off[k], (size_t)(a_off[k + 1] - a_off[k])); };
-                auto less = [&](uint32_t a, uint32_t b) {
-                    if (k0[a] != k0[b]) return k0[a] < k0[b];
-                    if (k1[a] != k1[b]) return k1[a] < k1[b];
-                    const size_t la = (size_t)(a_off[a + 1] - a_off[a]), lb = (size_t)(a_off[b + 1] - a_off[b]);
-                    if (la <= 16 && lb <= 16) return la < lb;          // equal padded prefixes: the shorter string sorts first
-                    return view(a) < view(b);
-                };
-                {
-                    unsigned nt = std::thread::hardware_concurrency();
-                    if (const char* env = getenv("BLU_INGEST_THREADS")) nt = (unsigned)atoi(env);
-                    nt = std::max(1u, std::min(nt, 32u));
-                    if (n_acc < 65536) nt = 1;
-                    std::vector<std::thread> pool;
-                    for (unsigned t = 0; t < nt; ++t)
-                        pool.emplace_back([&, t]() { std::sort(order.begin() + (size_t)n_acc * t / nt, order.begin() + (size_t)n_acc * (t + 1) / nt, less); });
-                    for (auto& th : pool) th.join();
-                    for (unsigned w = 1; w < nt; w *= 2)
-                        for (unsigned t = 0; t + w < nt; t += 2 * w)
-                            std::inplace_merge(order.begin() + (size_t)n_acc * t / nt, order.begin() + (size_t)n_acc * (t + w) / nt,
-                                               order.begin() + (size_t)n_acc * std::min(t + 2 * w, nt) / nt, less);
-                }
-            } catch (...) { acc_sort_failed = true; }   // (no exception leaves a std::thread)
-        });
+        acc_sort = std::thread([this] { sort_accessions(); });
+        return BLU_OK;
+    }
+    // (the body of acc_sort) `order` into the accessions' byte order: chunk sorts by a pool of threads, then a tree of merges
+    void sort_accessions() {
+        try {
+            auto view = [&](uint32_t k) { return std::string_view(a_bytes.data() + a_off[k], (size_t)(a_off[k + 1] - a_off[k])); };
+            auto less = [&](uint32_t a, uint32_t b) {
+                if (k0[a] != k0[b]) return k0[a] < k0[b];
+                if (k1[a] != k1[b]) return k1[a] < k1[b];
+                const size_t la = (size_t)(a_off[a + 1] - a_off[a]), lb = (size_t)(a_off[b + 1] - a_off[b]);
+                if (la <= 16 && lb <= 16) return la < lb;          // equal padded prefixes: the shorter string sorts first
+                return view(a) < view(b);
+            };
+            const unsigned nt = n_acc < 65536 ? 1 : ingest_threads(32);
+            std::vector<std::thread> pool;
+            for (unsigned t = 0; t < nt; ++t)
+                pool.emplace_back([&, t]() { std::sort(order.begin() + (size_t)n_acc * t / nt, order.begin() + (size_t)n_acc * (t + 1) / nt, less); });
+            for (auto& th : pool) th.join();
+            for (unsigned w = 1; w < nt; w *= 2)
+                for (unsigned t = 0; t + w < nt; t += 2 * w)
+                    std::inplace_merge(order.begin() + (size_t)n_acc * t / nt, order.begin() + (size_t)n_acc * (t + w) / nt,
+                                       order.begin() + (size_t)n_acc * std::min(t + 2 * w, nt) / nt, less);
+        } catch (...) { acc_sort_failed = true; }   // (no exception leaves a std::thread)
     }
 
     // ---- query dictionary: sized by the number of runs of equal hashes (an upper bound of the distinct count)
-    {
+    int query_dictionary() {
+        Slot* d_qtab = nullptr;
+        uint32_t *d_list_row = nullptr, *d_list_slot = nullptr, *d_mark = nullptr, *d_rank_of_row = nullptr;
+        unsigned long long* d_poslist = nullptr;
         hipLaunchKernelGGL(count_run_heads, grid(n_rows, 1024), dim3(1024), 0, 0, d_qh, n_rows, d_big + 1);
         unsigned long long runs = 0;
         HIP_CHECK(pol, hipMemcpy(&runs, d_big + 1, 8, hipMemcpyDeviceToHost));
         const uint64_t cap = pow2_at_least(runs * 2 + 16);
         HIP_CHECK(pol, mem.alloc(&d_qtab, cap * sizeof(Slot), "query table"));
-        hipLaunchKernelGGL(dict_init, grid(cap), dim3(256), 0, 0, d_qtab, cap);   // empty slots, first_row = all ones for atomicMin
-        HIP_CHECK(pol, hipMemset(d_counter, 0, 4));
-        hipLaunchKernelGGL(dict_insert, grid(n_rows), dim3(256), 0, 0, d_qh, n_rows, d_qtab, cap - 1, true, d_counter, d_flags);
-        hipLaunchKernelGGL(dict_count, grid(cap, 1024), dim3(1024), 0, 0, d_qtab, cap, d_counter);
-        HIP_CHECK(pol, hipMemcpy(&n_queries, d_counter, 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(pol, hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
-        if (h_flags) return fallback(fallback_text(h_flags));
+        uint32_t h_flags = 0;
+        STEP(build_dictionary(d_qtab, cap, d_qh, /* only_heads */ true, /* clear_flags */ false, &n_queries, &h_flags));
+        STEP(fall_back_on(h_flags));
         lap("  query: insert");
         HIP_CHECK(pol, mem.alloc(&d_list_row, (size_t)n_queries * 4, "query list")); HIP_CHECK(pol, mem.alloc(&d_list_slot, (size_t)n_queries * 4, "query list"));
-        HIP_CHECK(pol, hipMemset(d_counter, 0, 4));
+        STEP(zero_counter());
         hipLaunchKernelGGL(dict_finalize, grid(cap), dim3(256), 0, 0, d_qtab, cap, d_text, d_qpos, d_list_row, d_list_slot, d_counter);
         // ids in first-appearance order, and the names' positions in id order
         HIP_CHECK(pol, mem.alloc(&d_mark, ((size_t)n_rows + 1) * 4, "query ids")); HIP_CHECK(pol, mem.alloc(&d_rank_of_row, ((size_t)n_rows + 1) * 4, "query ids"));
         HIP_CHECK(pol, hipMemset(d_mark, 0, ((size_t)n_rows + 1) * 4));
         hipLaunchKernelGGL(mark_first_rows, grid(n_queries), dim3(256), 0, 0, (const uint32_t*)d_list_row, n_queries, d_mark);
-        HIP_CHECK(pol, need_tmp(scan_tmp_bytes<uint32_t>((size_t)n_rows + 1)));
-        HIP_CHECK(pol, exclusive_scan_dev<uint32_t>(d_mark, d_rank_of_row, (size_t)n_rows + 1, d_tmp));
+        HIP_CHECK(pol, need_tmp(scan_tmp_bytes_u32((size_t)n_rows + 1)));
+        HIP_CHECK(pol, exclusive_scan_u32(d_mark, d_rank_of_row, (size_t)n_rows + 1, d_tmp));
         HIP_CHECK(pol, mem.alloc(&d_poslist, (size_t)n_queries * 8, "query list"));
         hipLaunchKernelGGL(number_queries, grid(n_queries), dim3(256), 0, 0, d_qtab, (const uint32_t*)d_list_row, (const uint32_t*)d_list_slot, n_queries,
                            (const uint32_t*)d_rank_of_row, (const unsigned long long*)d_qpos, d_poslist);
         HIP_CHECK(pol, mem.alloc(&d_qid, (size_t)n_rows * 4, "query ids"));
         hipLaunchKernelGGL(dict_lookup, grid(n_rows), dim3(256), 0, 0, d_qh, d_qpos, n_rows, d_qtab, cap - 1, d_text, d_qpos, d_qid, d_flags);
-        HIP_CHECK(pol, hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
-        if (h_flags) return fallback(fallback_text(h_flags));
+        STEP(check_flags());
         lap("  query: ids of the rows");
         // query names: the text of each query's first row, in id order
-        if (const int rc = download_strings(d_poslist, n_queries, q_bytes, q_off); rc != BLU_OK) return rc;
+        STEP(download_strings(d_poslist, n_queries, q_bytes, q_off));
         lap("  query: names");
-        mem.free(d_poslist); d_poslist = nullptr;
+        mem.free(d_poslist);
         mem.free(d_list_row); mem.free(d_list_slot); mem.free(d_mark); mem.free(d_rank_of_row);
-        d_list_row = d_list_slot = d_mark = d_rank_of_row = nullptr;
-        mem.free(d_qtab); d_qtab = nullptr;
+        mem.free(d_qtab);
         mem.free(d_qh); d_qh = nullptr;
         mem.free(d_qpos); d_qpos = nullptr;
+        return BLU_OK;
     }
-    lap("query dictionary");
 
     // ---- accession dictionary, second half: the ranks go up, every row gets its accession's
-    {
+    int accession_dictionary_finish() {
         acc_sort.join();
         if (acc_sort_failed) return fallback("the host could not sort the accessions");
         lap("  acc: wait for the host sort");
-        const uint64_t cap = acap;
+        uint32_t* d_ranks = nullptr;
         std::vector<uint32_t> rank_of(n_acc);
         for (uint32_t r = 0; r < n_acc; ++r) rank_of[order[r]] = r;
         HIP_CHECK(pol, mem.alloc(&d_ranks, (size_t)n_acc * 4, "accession ranks"));
         HIP_CHECK(pol, hipMemcpy(d_ranks, rank_of.data(), (size_t)n_acc * 4, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(dict_assign_ids, grid(n_acc), dim3(256), 0, 0, d_atab, d_alist_slot, (const uint32_t*)d_ranks, n_acc);
         HIP_CHECK(pol, mem.alloc(&d_arank, (size_t)n_rows * 4, "accession ranks"));
-        hipLaunchKernelGGL(dict_lookup, grid(n_rows), dim3(256), 0, 0, d_ah, d_apos, n_rows, d_atab, cap - 1, d_text, d_apos, d_arank, d_flags);
-        HIP_CHECK(pol, hipMemcpy(&h_flags, d_flags, 4, hipMemcpyDeviceToHost));
-        if (h_flags) return fallback(fallback_text(h_flags));
+        hipLaunchKernelGGL(dict_lookup, grid(n_rows), dim3(256), 0, 0, d_ah, d_apos, n_rows, d_atab, acap - 1, d_text, d_apos, d_arank, d_flags);
+        STEP(check_flags());
         lap("  acc: ranks of the rows");
         mem.free(d_atab); d_atab = nullptr;
         mem.free(d_ah); d_ah = nullptr;
         mem.free(d_apos); d_apos = nullptr;
         mem.free(d_text); d_text = nullptr;
+        return BLU_OK;
     }
-    lap("accession dictionary");
 
     // ---- grouping: queries in first-appearance order, file order inside a query (mod.rs:192-208)
-    {
-        HIP_CHECK(pol, hipMemset(d_counter, 0, 4));
+    int group() {
+        STEP(zero_counter());
         hipLaunchKernelGGL(check_grouped, grid(n_rows), dim3(256), 0, 0, d_qid, n_rows, d_counter);
         uint32_t unsorted = 0;
         HIP_CHECK(pol, hipMemcpy(&unsorted, d_counter, 4, hipMemcpyDeviceToHost));
         lap(unsorted ? "  grouping: check (unsorted)" : "  grouping: check (sorted)");
+        uint32_t *d_perm = nullptr, *d_perm2 = nullptr, *d_qid2 = nullptr;
         if (unsorted) {
             HIP_CHECK(pol, mem.alloc(&d_perm, (size_t)n_rows * 4, "regrouping")); HIP_CHECK(pol, mem.alloc(&d_perm2, (size_t)n_rows * 4, "regrouping"));
             HIP_CHECK(pol, mem.alloc(&d_qid2, (size_t)n_rows * 4, "regrouping"));
             hipLaunchKernelGGL(iota_u32, grid(n_rows), dim3(256), 0, 0, d_perm, n_rows);
             int bits = 1;
             while ((1ull << bits) < n_queries) ++bits;
-            const size_t cells = (size_t)256 * (((size_t)n_rows + RS_BLOCK - 1) / RS_BLOCK);
             uint32_t* d_table = nullptr;
-            HIP_CHECK(pol, mem.alloc(&d_table, 2 * cells * 4, "regrouping"));
-            HIP_CHECK(pol, need_tmp(scan_tmp_bytes<uint32_t>(cells)));
+            HIP_CHECK(pol, mem.alloc(&d_table, radix_table_words(n_rows) * 4, "regrouping"));
+            HIP_CHECK(pol, need_tmp(radix_scan_tmp_bytes(n_rows)));
             // (stable: file order survives inside a query; afterwards d_qid2 / d_perm2 name the sorted arrays whichever buffer they are)
             uint32_t *k0 = d_qid, *k1 = d_qid2, *v0 = d_perm, *v1 = d_perm2;
-            HIP_CHECK(pol, radix_sort_pairs_dev(&k0, &k1, &v0, &v1, n_rows, bits, d_table, d_tmp));
+            HIP_CHECK(pol, radix_sort_pairs(&k0, &k1, &v0, &v1, n_rows, bits, d_table, d_tmp));
             d_qid2 = k0; d_qid = k1; d_perm2 = v0; d_perm = v1;
             mem.free(d_table);
         }
@@ -1484,18 +1133,17 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
         HIP_CHECK(pol, hipMemset(d_seg, 0, ((size_t)n_queries + 1) * 8 * 2));
         hipLaunchKernelGGL(segment_starts, grid(n_rows), dim3(256), 0, 0, (const uint32_t*)(unsorted ? d_qid2 : d_qid), n_rows, n_queries,
                            d_seg + n_queries + 1);
-        HIP_CHECK(pol, mem.alloc(&d_bs2, (size_t)n_rows * 4, "grouped columns")); HIP_CHECK(pol, mem.alloc(&d_aln2, (size_t)n_rows * 4, "grouped columns"));
-        HIP_CHECK(pol, mem.alloc(&d_tax2, (size_t)n_rows * 4, "grouped columns")); HIP_CHECK(pol, mem.alloc(&d_arank2, (size_t)n_rows * 4, "grouped columns"));
-        HIP_CHECK(pol, mem.alloc(&d_pid2, (size_t)n_rows * 8, "grouped columns"));
+        HIP_CHECK(pol, mem.alloc(&grouped.bs, (size_t)n_rows * 4, "grouped columns")); HIP_CHECK(pol, mem.alloc(&grouped.aln, (size_t)n_rows * 4, "grouped columns"));
+        HIP_CHECK(pol, mem.alloc(&grouped.tax, (size_t)n_rows * 4, "grouped columns")); HIP_CHECK(pol, mem.alloc(&grouped.arank, (size_t)n_rows * 4, "grouped columns"));
+        HIP_CHECK(pol, mem.alloc(&grouped.pid, (size_t)n_rows * 8, "grouped columns"));
         lap("  grouping: offsets + allocations");
-        Cols in{d_bs, d_aln, d_tax, d_arank, d_pid};
-        ColsOut out{d_bs2, d_aln2, d_tax2, d_arank2, d_pid2};
-        hipLaunchKernelGGL(gather_cols, grid(n_rows), dim3(256), 0, 0, in, out, (const uint32_t*)(unsorted ? d_perm2 : nullptr), n_rows);
+        const Cols in{d_bs, d_aln, d_tax, d_arank, d_pid};
+        hipLaunchKernelGGL(gather_cols, grid(n_rows), dim3(256), 0, 0, in, grouped, (const uint32_t*)(unsorted ? d_perm2 : nullptr), n_rows);
+        return BLU_OK;
     }
-    lap("grouping");
 
     // ---- the grouped columns stay on the device for the engine; the host copies are made only on request
-    {
+    int hand_over() {
         unsigned long long unmatched = 0;
         HIP_CHECK(pol, hipMemcpy(&unmatched, d_big, 8, hipMemcpyDeviceToHost));
         ht.unmatched = unmatched;
@@ -1503,21 +1151,22 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
         ht.host_columns = false;
         ht.dev.reset(new DeviceHits());
         ht.dev->device = device; ht.dev->n_hits = n_rows; ht.dev->n_queries = n_queries;
-        ht.dev->bitscore = d_bs2; ht.dev->align_len = d_aln2; ht.dev->tax_desc_row = d_tax2; ht.dev->acc_rank = d_arank2; ht.dev->pident = d_pid2;
+        ht.dev->bitscore = grouped.bs; ht.dev->align_len = grouped.aln; ht.dev->tax_desc_row = grouped.tax; ht.dev->acc_rank = grouped.arank;
+        ht.dev->pident = grouped.pid;
         ht.dev->seg_off = d_seg + n_queries + 1; ht.dev->seg_block = d_seg;
-        for (void* q : {(void*)d_bs2, (void*)d_aln2, (void*)d_tax2, (void*)d_arank2, (void*)d_pid2, (void*)d_seg}) mem.release(q);
+        for (void* q : {(void*)grouped.bs, (void*)grouped.aln, (void*)grouped.tax, (void*)grouped.arank, (void*)grouped.pid, (void*)d_seg}) mem.release(q);
         if (host_columns) {
-            const int rc = download_columns(ht);
-            if (rc != BLU_OK) return rc;
+            STEP(download_columns(ht));
             lap("download columns");
         }
-        // the host strings (query names in id order, accessions in byte order) are built from the packed bytes by a
-        // background thread while the caller goes on to the engine: nothing on the device waits for them
         ht.n_queries = n_queries;
-        unsigned nt = std::thread::hardware_concurrency();
-        if (const char* env = getenv("BLU_INGEST_THREADS")) nt = (unsigned)atoi(env);
-        nt = std::max(1u, std::min(nt, 16u));
-        if ((uint64_t)n_queries + n_acc < 65536) nt = 1;
+        start_strings_thread();
+        return BLU_OK;
+    }
+    // the host strings (query names in id order, accessions in byte order) are built from the packed bytes by a
+    // background thread while the caller goes on to the engine: nothing on the device waits for them
+    void start_strings_thread() {
+        const unsigned nt = (uint64_t)n_queries + n_acc < 65536 ? 1 : ingest_threads(16);
         HitTable* const hp = &ht;
         ht.strings_thread = std::thread([hp, nt, q_bytes = std::move(q_bytes), q_off = std::move(q_off), a_bytes = std::move(a_bytes),
                                          a_off = std::move(a_off), order = std::move(order)]() {
@@ -1545,8 +1194,8 @@ int ingest_on_device(int fd, size_t size, const TaxidMap& row_of, int device, bo
             if (oom) hp->strings_ok = false;
         });
     }
-    return BLU_OK;
-}
+};
+#undef STEP
 
 }  // namespace
 
@@ -1570,7 +1219,9 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
         }
         mem.keep = (double)size * 4.0 + (4ull << 30) < (double)free_b;
     }
-    const int rc = ingest_on_device(fd, size, row_of, device, host_columns, ht, mem, lap, flt, taxa);
+    // (in a block of its own: the sort thread is joined and the host strings are let go before the arena's buffers are)
+    int rc;
+    { GpuIngest ingest{fd, size, row_of, device, host_columns, ht, mem, mem.pol, lap, flt, taxa}; rc = ingest.run(); }
     if (rc != BLU_OK) ht.clear();
     lap("hand-over");
     // with room on the card (mem.keep) the work buffers — the text, the hashes, the dictionaries: 10 GB for a 2 M-query table —
@@ -1579,32 +1230,6 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
     mem.free_all();
     lap("free the work buffers");
     return rc;
-}
-
-
-// Device -> pageable host memory in 8 MiB pieces by a pool of host threads: the first touch of the fresh destination pages
-// (and the runtime's pinning of them) costs more than the transfer, and it parallelises.
-void d2h_add(std::vector<D2HPiece>& v, void* dst, const void* src, size_t bytes, size_t piece) {
-    for (size_t o = 0; o < bytes; o += piece) v.push_back({(char*)dst + o, (const char*)src + o, std::min(piece, bytes - o)});
-}
-hipError_t d2h_parallel(const std::vector<D2HPiece>& pieces, int device, unsigned max_threads) {
-    if (pieces.empty()) return hipSuccess;
-    unsigned nt = std::thread::hardware_concurrency();
-    if (const char* env = getenv("BLU_INGEST_THREADS")) nt = (unsigned)atoi(env);
-    nt = std::max(1u, std::min<unsigned>(std::min(nt, max_threads), (unsigned)pieces.size()));
-    std::vector<hipError_t> errs(nt, hipSuccess);
-    std::atomic<size_t> next{0};
-    auto work = [&](unsigned t) {
-        (void)hipSetDevice(device);
-        for (size_t k = next.fetch_add(1); k < pieces.size() && errs[t] == hipSuccess; k = next.fetch_add(1))
-            errs[t] = hipMemcpy(pieces[k].dst, pieces[k].src, pieces[k].bytes, hipMemcpyDeviceToHost);
-    };
-    std::vector<std::thread> pool;
-    for (unsigned t = 1; t < nt; ++t) pool.emplace_back(work, t);
-    work(0);
-    for (auto& th : pool) th.join();
-    for (hipError_t e : errs) if (e != hipSuccess) return e;
-    return hipSuccess;
 }
 
 // The columns come back in 64 MiB pieces copied by a pool of host threads: the first touch of the fresh host pages
@@ -1628,271 +1253,4 @@ int download_columns(HitTable& ht) {
     ht.host_columns = true;
     return BLU_OK;
 }
-
-// ---- engine on the resident columns ---------------------------------------------------------------------------
-namespace {
-constexpr uint32_t ROW_NO_TAXID = BLU_UNMATCHED_TAXID;
-__device__ __forceinline__ uint32_t engine_row_of(uint32_t r, const uint32_t* __restrict__ fwd, uint64_t n_tax) {
-    return (r == ROW_NO_TAXID || r >= n_tax) ? ROW_NO_TAXID : fwd[r];
-}
-// k = round(p * 1000) is used only if fl(k / 1000.0) == p bit for bit for every row (the 20 B/hit layout is lossless then)
-__device__ __forceinline__ bool milli_of(double p, uint32_t* k_out) {
-    bool ok = p >= 0.0 && p < 4.0e6;
-    uint32_t k = 0;
-    if (ok) {
-        k = (uint32_t)(p * 1000.0 + 0.5);
-        const double back = (double)k / 1000.0;
-        ok = __double_as_longlong(back) == __double_as_longlong(p);
-    }
-    *k_out = k;
-    return ok;
-}
-// 16-byte side records of the packed layout (include/blu_consensus.h: blu_hits.packed) straight from the ingest's columns
-// (what blu_hits_pack builds from engine row ids, pack_kernel.hip, here straight from the taxonomy rows of the join: word 1 =
-// milli-percent perc_identity | shape hint of the row << 17)
-__global__ void pack_side_records(const uint32_t* __restrict__ desc_row, const double* __restrict__ pid, const int32_t* __restrict__ aln,
-                                  const uint32_t* __restrict__ acc, uint64_t n, const uint32_t* __restrict__ fwd, uint64_t n_tax,
-                                  const uint16_t* __restrict__ hint_of_pos, uint4* __restrict__ rec, uint32_t* __restrict__ inexact) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t k;
-    if (!milli_of(pid[i], &k) || k >= BLU_PACKED_PIDENT_LIMIT) *inexact = 1u;
-    const uint32_t row = engine_row_of(desc_row[i], fwd, n_tax);
-    const uint32_t pos = row & ((1u << BLU_ROW_BITS) - 1u);
-    const uint32_t hint = (row != ROW_NO_TAXID && pos < n_tax) ? (uint32_t)hint_of_pos[pos] : 0u;
-    rec[i] = make_uint4(row, (k & BLU_KTHR_NEVER) | (hint << BLU_KTHR_BITS), (uint32_t)aln[i], acc[i]);
-}
-__global__ void to_engine_rows(const uint32_t* __restrict__ desc_row, uint64_t n, const uint32_t* __restrict__ fwd, uint64_t n_tax,
-                               uint32_t* __restrict__ rows) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) rows[i] = engine_row_of(desc_row[i], fwd, n_tax);
-}
-__global__ void to_milli(const double* __restrict__ pid, uint64_t n, uint32_t* __restrict__ milli, uint32_t* __restrict__ inexact) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t k;
-    if (!milli_of(pid[i], &k)) *inexact = 1u;
-    milli[i] = k;
-}
-
-// Top-score rows of the rendered queries (status 0 / 1), one wave per TOP_QPW consecutive queries: the lanes sweep a
-// segment 64 rows at a time.  Pass 1 counts (out_rows == nullptr), pass 2 writes the rows at the scanned offsets.
-constexpr uint32_t TOP_QPW = 8;
-__global__ __launch_bounds__(256) void top_rows_kernel(const blu_result* __restrict__ recs, const unsigned long long* __restrict__ seg_off,
-                                                       const int32_t* __restrict__ bitscore, uint64_t n_queries,
-                                                       unsigned long long* __restrict__ count, const unsigned long long* __restrict__ off,
-                                                       const uint32_t* __restrict__ desc_row, const uint32_t* __restrict__ acc,
-                                                       const int32_t* __restrict__ aln, const double* __restrict__ pid,
-                                                       TopRow* __restrict__ out_rows, int32_t* __restrict__ out_score) {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    for (uint32_t k = 0; k < TOP_QPW; ++k) {
-        const uint64_t q = wave * TOP_QPW + k;
-        if (q >= n_queries) return;
-        const blu_result r = recs[q];
-        unsigned long long n_top = 0;
-        if (r.status < 2 && r.ref_row != 0xFFFFFFFFu) {
-            const int32_t top = bitscore[r.ref_row];
-            const unsigned long long b = seg_off[q], e = seg_off[q + 1];
-            const unsigned long long base = out_rows ? off[q] : 0;
-            for (unsigned long long i0 = b; i0 < e; i0 += 64) {
-                const unsigned long long i = i0 + lane;
-                const bool hit = i < e && bitscore[i] == top;
-                const unsigned long long m = __ballot(hit);
-                if (out_rows && hit) {
-                    const unsigned long long at = base + n_top + __popcll(m & ((1ull << lane) - 1));
-                    TopRow t;
-                    t.row = (uint32_t)i; t.desc_row = desc_row[i]; t.acc_rank = acc[i]; t.align_len = aln[i]; t.pident = pid[i];
-                    out_rows[at] = t;
-                }
-                n_top += __popcll(m);
-            }
-            if (out_score && lane == 0) out_score[q] = top;
-        } else if (out_score && lane == 0) out_score[q] = 0;
-        if (!out_rows && lane == 0) count[q] = n_top;
-    }
-}
-}  // namespace
-
-DeviceHits::~DeviceHits() {
-    if (device < 0) return;
-    (void)hipSetDevice(device);
-    for (void* p : {(void*)bitscore, (void*)align_len, (void*)tax_desc_row, (void*)acc_rank, (void*)pident, seg_block})
-        if (p) (void)hipFree(p);
-    for (void* p : trash) (void)hipFree(p);
-}
-
-int device_run_consensus(const blu_taxonomy* tax, DeviceHits& dev, const uint32_t* fwd, uint64_t n_tax, int strategy, blu_result* out,
-                         TopTable* top, DeviceRecords* kept) {
-    uint32_t *d_fwd = nullptr, *d_milli = nullptr, *d_rows = nullptr, *d_flag = nullptr;
-    uint4* d_rec = nullptr;
-    blu_result* d_out = nullptr;
-    unsigned long long* d_cnt = nullptr;   // [2 (Q + 1)]: counts, then their exclusive scan
-    void* d_tmp = nullptr;
-    TopRow* d_top = nullptr;
-    int32_t* d_score = nullptr;
-    uint32_t inexact = 0;
-    const uint64_t n = dev.n_hits, nq = dev.n_queries;
-    if (hipSetDevice(dev.device) != hipSuccess) { set_error("hipSetDevice(%d) failed", dev.device); return BLU_ERR_NO_DEVICE; }
-    HipPolicy pol{"GPU ingest", BLU_ERR_HIP};
-    DeviceArena mem(pol);
-    // the work buffers are freed with the columns (DeviceHits::trash), whichever way this is left: ten hipFree calls were
-    // 10-15 ms of this function
-    struct ToTrash { DeviceArena& mem; DeviceHits& dev; ~ToTrash() { mem.hand_over(dev.trash); } } to_trash{mem, dev};
-    HIP_CHECK(pol, mem.alloc(&d_fwd, n_tax * 4, "row map"));
-    HIP_CHECK(pol, hipMemcpy(d_fwd, fwd, n_tax * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(pol, mem.alloc(&d_flag, 4, "flag"));
-    HIP_CHECK(pol, hipMemset(d_flag, 0, 4));
-    HIP_CHECK(pol, mem.alloc(&d_out, nq * sizeof(blu_result), "records"));
-    {
-        blu_hits h{};
-        h.bitscore = dev.bitscore;
-        h.seg_off = (const uint64_t*)dev.seg_off;
-        // packed layout: a top row's four values in one memory line (if the records do not fit, or a perc_identity is not
-        // exactly k/1000, the columns go in)
-        bool packed = n && mem.alloc(&d_rec, n * 16, "packed records") == hipSuccess;
-        if (!packed) (void)hipGetLastError();
-        if (packed) {
-            hipLaunchKernelGGL(pack_side_records, grid(n), dim3(256), 0, 0, dev.tax_desc_row, dev.pident, dev.align_len, dev.acc_rank, n,
-                               d_fwd, n_tax, tax->d_hint_of_pos, d_rec, d_flag);
-            HIP_CHECK(pol, hipMemcpy(&inexact, d_flag, 4, hipMemcpyDeviceToHost));
-            if (inexact) { mem.free(d_rec); d_rec = nullptr; packed = false; }
-        }
-        if (packed) h.packed = (const uint32_t*)d_rec;
-        else {
-            HIP_CHECK(pol, mem.alloc(&d_rows, n * 4, "engine rows"));
-            if (n) hipLaunchKernelGGL(to_engine_rows, grid(n), dim3(256), 0, 0, dev.tax_desc_row, n, d_fwd, n_tax, d_rows);
-            h.tax_row = d_rows; h.align_len = dev.align_len; h.acc_rank = dev.acc_rank;
-            if (!inexact && n) {   // the records did not fit: milli-percent column
-                HIP_CHECK(pol, mem.alloc(&d_milli, n * 4, "milli-percent column"));
-                hipLaunchKernelGGL(to_milli, grid(n), dim3(256), 0, 0, dev.pident, n, d_milli, d_flag);
-                HIP_CHECK(pol, hipMemcpy(&inexact, d_flag, 4, hipMemcpyDeviceToHost));
-            }
-            if (inexact || !n) h.pident = dev.pident; else h.pident_milli = d_milli;
-        }
-        h.n_hits = n; h.n_queries = nq; h.on_device = 1;
-        blu_run_params rp{strategy, 0, nullptr};
-        const int rc = blu_consensus_run(tax, &h, &rp, d_out);
-        if (rc != BLU_OK) return rc;
-        if (kept) { kept->recs = d_out; kept->rows = packed ? (const uint32_t*)d_rec : d_rows; kept->row_stride = packed ? 4u : 1u; }
-    }
-    HIP_CHECK(pol, hipStreamSynchronize(nullptr));
-    {
-        std::vector<D2HPiece> pieces;
-        d2h_add(pieces, out, d_out, nq * sizeof(blu_result));
-        HIP_CHECK(pol, d2h_parallel(pieces, dev.device));
-    }
-    if (top) {
-        const uint64_t waves = (nq + TOP_QPW - 1) / TOP_QPW;
-        const dim3 g((unsigned)((waves * 64 + 255) / 256));
-        HIP_CHECK(pol, mem.alloc(&d_cnt, (nq + 1) * 8 * 2, "top-row counts"));
-        HIP_CHECK(pol, hipMemset(d_cnt, 0, (nq + 1) * 8 * 2));
-        HIP_CHECK(pol, mem.alloc(&d_score, nq * 4, "top scores"));
-        if (nq) hipLaunchKernelGGL(top_rows_kernel, g, dim3(256), 0, 0, d_out, dev.seg_off, dev.bitscore, nq, d_cnt, nullptr, nullptr, nullptr,
-                                   nullptr, nullptr, nullptr, nullptr);
-        HIP_CHECK(pol, mem.alloc(&d_tmp, scan_tmp_bytes<unsigned long long>((size_t)nq + 1), "scan scratch"));
-        HIP_CHECK(pol, exclusive_scan_dev<unsigned long long>(d_cnt, d_cnt + nq + 1, (size_t)nq + 1, d_tmp));
-        top->off.resize(nq + 1);
-        HIP_CHECK(pol, hipMemcpy(top->off.data(), d_cnt + nq + 1, (nq + 1) * 8, hipMemcpyDeviceToHost));
-        const uint64_t n_top = top->off[nq];
-        HIP_CHECK(pol, mem.alloc(&d_top, n_top * sizeof(TopRow), "top rows"));
-        if (nq) hipLaunchKernelGGL(top_rows_kernel, g, dim3(256), 0, 0, d_out, dev.seg_off, dev.bitscore, nq, nullptr, d_cnt + nq + 1,
-                                   dev.tax_desc_row, dev.acc_rank, dev.align_len, dev.pident, d_top, d_score);
-        top->rows.resize(n_top);
-        top->score.resize(nq);
-        HIP_CHECK(pol, hipStreamSynchronize(nullptr));
-        std::vector<D2HPiece> pieces;
-        d2h_add(pieces, top->rows.data(), d_top, n_top * sizeof(TopRow));
-        d2h_add(pieces, top->score.data(), d_score, nq * 4);
-        HIP_CHECK(pol, d2h_parallel(pieces, dev.device));
-    }
-    return BLU_OK;
-}
-
 }  // namespace blu
-
-// ---- (introspection) the primitives above on their own (include/blu_consensus.h: blu_dev_*), for the tests: each call
-// synchronises the device on entry and on return and allocates its own scratch.  The product paths call blu:: directly.
-using namespace blu;
-
-namespace {
-
-int dev_enter(int device, const char* who) {
-    if (const int rc = use_device(who, device)) return rc;
-    const hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) { set_error("%s: hipDeviceSynchronize failed: %s", who, hipGetErrorString(e)); return BLU_ERR_HIP; }
-    return BLU_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int blu_dev_exclusive_scan(int device, const void* in, void* out, uint64_t n, int elem_bytes) {
-    static const char WHO[] = "blu_dev_exclusive_scan";
-    if ((elem_bytes != 4 && elem_bytes != 8) || (n && (!in || !out))) { set_error("%s: invalid argument", WHO); return BLU_ERR_INVALID_ARG; }
-    if (const int rc = dev_enter(device, WHO)) return rc;
-    HipPolicy pol{WHO, BLU_ERR_ALLOC};
-    DeviceArena mem(pol);
-    void* tmp = nullptr;
-    HIP_CHECK(pol, mem.alloc(&tmp, elem_bytes == 4 ? scan_tmp_bytes_u32(n) : scan_tmp_bytes_u64(n), "scan scratch"));
-    if (elem_bytes == 4) HIP_CHECK(pol, exclusive_scan_u32((const uint32_t*)in, (uint32_t*)out, n, tmp));
-    else HIP_CHECK(pol, exclusive_scan_u64((const unsigned long long*)in, (unsigned long long*)out, n, tmp));
-    HIP_CHECK(pol, hipDeviceSynchronize());
-    return BLU_OK;
-}
-
-int blu_dev_radix_sort_pairs(int device, uint32_t* keys, uint32_t* vals, uint32_t n, int bits) {
-    static const char WHO[] = "blu_dev_radix_sort_pairs";
-    if (bits < 0 || bits > 32 || (n && (!keys || !vals))) { set_error("%s: invalid argument", WHO); return BLU_ERR_INVALID_ARG; }
-    if (const int rc = dev_enter(device, WHO)) return rc;
-    if (n == 0) return BLU_OK;
-    HipPolicy pol{WHO, BLU_ERR_ALLOC};
-    DeviceArena mem(pol);
-    uint32_t *keys_alt = nullptr, *vals_alt = nullptr, *table = nullptr;
-    void* tmp = nullptr;
-    HIP_CHECK(pol, mem.alloc(&keys_alt, (size_t)n * 4, "alternate keys"));
-    HIP_CHECK(pol, mem.alloc(&vals_alt, (size_t)n * 4, "alternate values"));
-    HIP_CHECK(pol, mem.alloc(&table, radix_table_words(n) * 4, "digit table"));
-    HIP_CHECK(pol, mem.alloc(&tmp, radix_scan_tmp_bytes(n), "scan scratch"));
-    uint32_t *k = keys, *ka = keys_alt, *v = vals, *va = vals_alt;
-    HIP_CHECK(pol, radix_sort_pairs(&k, &ka, &v, &va, n, bits, table, tmp));
-    if (k != keys) {   // an odd number of passes: the result is in the scratch pair
-        HIP_CHECK(pol, hipMemcpy(keys, k, (size_t)n * 4, hipMemcpyDeviceToDevice));
-        HIP_CHECK(pol, hipMemcpy(vals, v, (size_t)n * 4, hipMemcpyDeviceToDevice));
-    }
-    HIP_CHECK(pol, hipDeviceSynchronize());
-    return BLU_OK;
-}
-
-int blu_dev_line_index(int device, const unsigned char* text, uint64_t size, uint64_t* line, uint64_t cap, uint64_t* n_newlines) {
-    static const char WHO[] = "blu_dev_line_index";
-    if (!n_newlines || (size && !text) || ((uintptr_t)text & 15u) || (cap && !line)) { set_error("%s: invalid argument", WHO); return BLU_ERR_INVALID_ARG; }
-    *n_newlines = 0;
-    if (const int rc = dev_enter(device, WHO)) return rc;
-    const uint64_t n_tiles = line_tiles(size);
-    HipPolicy pol{WHO, BLU_ERR_ALLOC};
-    DeviceArena mem(pol);
-    uint32_t *d_tile = nullptr, *d_tile_base = nullptr, n32 = 0;
-    void* tmp = nullptr;
-    HIP_CHECK(pol, mem.alloc(&d_tile, (n_tiles + 1) * 4, "line index"));
-    HIP_CHECK(pol, mem.alloc(&d_tile_base, (n_tiles + 1) * 4, "line index"));
-    HIP_CHECK(pol, mem.alloc(&tmp, scan_tmp_bytes_u32(n_tiles + 1), "scan scratch"));
-    HIP_CHECK(pol, line_count(text, size, d_tile, d_tile_base, tmp, &n32));
-    // the total in 64 bits on the host: the device scan of the tile counts is u32 and wraps
-    std::vector<uint32_t> tiles(n_tiles);
-    if (n_tiles) HIP_CHECK(pol, hipMemcpy(tiles.data(), d_tile, n_tiles * 4, hipMemcpyDeviceToHost));
-    uint64_t total = 0;
-    for (uint32_t t : tiles) total += t;
-    *n_newlines = total;
-    if (total > 0xFFFFFFFFull || total + 1 > cap) {
-        set_error("%s: %llu newlines need %llu line entries (cap %llu, at most 2^32 newlines)", WHO, (unsigned long long)total,
-                  (unsigned long long)(total + 1), (unsigned long long)cap);
-        return BLU_ERR_INVALID_ARG;
-    }
-    HIP_CHECK(pol, line_write(text, size, d_tile_base, line, total + 1, false));
-    HIP_CHECK(pol, hipDeviceSynchronize());
-    return BLU_OK;
-}
-
-}  // extern "C"

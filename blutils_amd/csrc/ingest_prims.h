@@ -1,8 +1,8 @@
 // Host side shared by the library's GPU programs: the GPU ingest (ingest_gpu.hip), the engine on its columns, the taxon
 // report (report_kernel.hip), `build-db blu` (taxdb_gpu.hip) and the kraken2 / qiime2 export (seqdb_gpu.hip).
 //   - the error path of a HIP call (HipPolicy, hip_fail, HIP_CHECK) and the owner of one call's device memory (DeviceArena)
-//   - the ingest's device primitives (line index, prefix sums, radix sort, upload, parallel download): host wrappers around
-//     kernels that stay compiled once, in ingest_gpu.hip
+//   - the device primitives (line index, prefix sums, radix sort, column compaction): host wrappers around kernels that are
+//     compiled once, in dev_prims.hip; and the upload and the parallel download of dev_io.cpp
 //   - host one-liners: a monotonic clock, launch grids, write_all, JSON string escapes
 #ifndef BLU_INGEST_PRIMS_H
 #define BLU_INGEST_PRIMS_H
@@ -16,9 +16,11 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <functional>
 #include <string>
 #include <string_view>
+#include <thread>
 #include <vector>
 
 #include "blu_internal.h"
@@ -134,6 +136,10 @@ hipError_t compact_column_u32(const uint32_t* in, const uint32_t* keep, const ui
 hipError_t compact_column_u64(const unsigned long long* in, const uint32_t* keep, const uint32_t* pos, uint32_t n, uint32_t n_out,
                               unsigned long long* out);
 
+// makes the runtime load the code object of dev_prims.hip now (warm_up_device), not at the first use of one of the above
+// (hidden: the library exports what it exported before the primitives had a file of their own)
+__attribute__((visibility("hidden"))) void load_dev_prims();
+
 // ---- file -> HBM through pinned staging (pread, never mapped); BLU_OK, BLU_ERR_IO, or BLU_INGEST_FALLBACK (HIP staging)
 int upload_file(int fd, size_t size, unsigned char* d_text, int device, std::string* err);
 // file -> padded device text in the arena: (size rounded up to 16) + 64 bytes, the 64 after `size` zeroed, the file
@@ -149,6 +155,13 @@ void d2h_add(std::vector<D2HPiece>& v, void* dst, const void* src, size_t bytes,
 hipError_t d2h_parallel(const std::vector<D2HPiece>& pieces, int device, unsigned max_threads = 16);
 
 // ---- host one-liners
+// host threads of a parallel step: BLU_INGEST_THREADS, else the machine's; at least one, at most `cap`
+inline unsigned ingest_threads(unsigned cap) {
+    unsigned nt = std::thread::hardware_concurrency();
+    if (const char* env = getenv("BLU_INGEST_THREADS")) nt = (unsigned)atoi(env);
+    return std::max(1u, std::min(nt, cap));
+}
+
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // blocks of `block` threads over n items (at least one)

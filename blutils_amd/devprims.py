@@ -1,4 +1,4 @@
-"""The device primitives of the GPU ingest on torch tensors (include/blu_consensus.h: blu_dev_*, csrc/ingest_gpu.hip):
+"""The device primitives of the GPU ingest on torch tensors (include/blu_consensus.h: blu_dev_*, csrc/dev_prims.hip):
 device-wide exclusive prefix sums, the stable LSD radix sort of (key, value) pairs, and the newline index of a text.
 Introspection for the tests: the product paths call the primitives inside the library."""
 from __future__ import annotations

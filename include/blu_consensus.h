@@ -216,7 +216,7 @@ int blu_taxonomy_shared_levels(const blu_taxonomy* tax, uint32_t lo, uint32_t hi
 int blu_taxonomy_trim(const blu_taxonomy* tax);
 
 /* (introspection) The device primitives the GPU ingest, the database builders and the report stand on
- * (csrc/ingest_gpu.hip), callable on their own so that they can be checked against plain references.  Arrays are
+ * (csrc/dev_prims.hip), callable on their own so that they can be checked against plain references.  Arrays are
  * device pointers on `device` (n_newlines is a host pointer).  Each call synchronises the device on entry and on return, allocates its own scratch,
  * and returns a blu_error code (BLU_ERR_INVALID_ARG for a bad argument, BLU_ERR_ALLOC, BLU_ERR_HIP).
  *

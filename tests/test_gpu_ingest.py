@@ -108,6 +108,73 @@ def test_a_table_uploaded_in_many_pieces(big_table, force_gpu, threads):
     assert gs["n_hits"] == cs["n_hits"] == n_rows and gs["n_queries"] == 40000
 
 
+SAME_16 = "same_sixteen_byt"      # 16 bytes: the two key words of the accessions that start with it are equal
+
+
+@pytest.fixture(scope="module")
+def distinct_accessions_table(tmp_path_factory):
+    """524 300 rows, every one with an accession of its own: more than 2^19, so the accession table (2^20 slots at first) is
+    more than half full and grows once.  Short accessions (<= 16 bytes), long ones, 4 000 that agree on their first 16
+    bytes and differ after, chains in which one accession is a proper prefix of the next (below, at and beyond 16 bytes); the
+    rows in an order of their own, the queries scrambled."""
+    n = 524300
+    assert n * 2 > 1 << 20
+    accs = [SAME_16] + [f"{SAME_16}{k:05d}" for k in range(4000)]
+    for k in range(2000):            # PF_000123 < PF_000123.1 < PF_000123.1.beyond_sixteen (9, 11 and 26 bytes)
+        accs += [f"PF_{k:06d}", f"PF_{k:06d}.1", f"PF_{k:06d}.1.beyond_sixteen"]
+    for k in range(2000):            # 16 bytes exactly, and 17 and 18 with the same first 16
+        accs += [f"exactly16_{k:06d}", f"exactly16_{k:06d}.", f"exactly16_{k:06d}.2"]
+    k = 0
+    while len(accs) < n:
+        accs.append(f"NR_{k:07d}.1" if k % 8 else f"a_much_longer_accession_string_{k:08d}.12")
+        k += 1
+    assert len(set(accs)) == n
+    rng = np.random.default_rng(33)
+    accs = [accs[i] for i in rng.permutation(n)]
+    n_q = 40000
+    qid = rng.integers(0, n_q, n)
+    qid[:n_q] = rng.permutation(n_q)                       # every query occurs
+    tax = rng.integers(0, 3100, n)                         # some taxids are not in the DB
+    pid = rng.integers(0, 20001, n)
+    aln = rng.integers(100, 2000, n)
+    bs = rng.integers(50, 99999, n)
+    rows = [f"q{q:06d}\t{a}\t{100 + t}\t{80 + p / 1000:.3f}\t{l}\t1\t0\t1\t400\t1\t400\t1.00e-50\t{b}"
+            for q, a, t, p, l, b in zip(qid.tolist(), accs, tax.tolist(), pid.tolist(), aln.tolist(), bs.tolist())]
+    d = tmp_path_factory.mktemp("distinct")
+    bt = d / "b.tsv"
+    bt.write_bytes(("\n".join(rows) + "\n").encode())
+    cs, cck = pipeline.ingest_only(str(bt), _db(d), False, device=-1)
+    assert pipeline.last_ingest_path() == "cpu"
+    return str(bt), _db(d), n, n_q, cs, cck
+
+
+@pytest.mark.parametrize("threads", ["1", "4"])
+def test_a_table_of_distinct_accessions_grows_the_accession_table(distinct_accessions_table, force_gpu, capfd, threads):
+    """The accession table's growth loop (allocated twice: 2^20 slots, then 2^22) and the host's sort of 524 300 distinct
+    accessions, on one thread and as four chunk sorts with a two-level merge; the columns are the CPU parser's."""
+    bt, tj, n, n_q, cs, cck = distinct_accessions_table
+    old = {k: os.environ.get(k) for k in ("BLU_INGEST_THREADS", "BLU_INGEST_TRACE")}
+    os.environ["BLU_INGEST_THREADS"] = threads
+    os.environ["BLU_INGEST_TRACE"] = "1"
+    try:
+        capfd.readouterr()
+        gs, gck = pipeline.ingest_only(bt, tj, False, device=0)
+        err = capfd.readouterr().err
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    assert pipeline.last_ingest_path() == "gpu"
+    assert gck == cck
+    for k in ("n_hits", "n_queries", "n_taxids", "n_unmatched_rows"):
+        assert gs[k] == cs[k], k
+    assert gs["n_hits"] == n and gs["n_queries"] == n_q and gs["n_unmatched_rows"] > 0
+    assert err.count("acc: table allocation") == 2, err
+    assert "grouping: check (unsorted)" in err, err
+
+
 @pytest.mark.parametrize("case", ["quoted", "empty_line", "many_digits"])
 def test_files_outside_the_gpu_form_take_the_cpu_path(tmp_path, force_gpu, case):
     rng = np.random.default_rng(6)

@@ -1,4 +1,4 @@
-"""The device primitives of csrc/ingest_gpu.hip on their own (blu_dev_*: blutils_amd/devprims.py) against plain numpy:
+"""The device primitives of csrc/dev_prims.hip on their own (blu_dev_*: blutils_amd/devprims.py) against plain numpy:
 the exclusive prefix sums (u32 / u64, out of place and in place) across the block sizes of its three launches and the
 carry loop of scan_block_offsets (n > 4096 x 1024), the stable radix sort at every pass count and across the 4 M-cell
 scan of its (digit, block) table, and the line index across tile boundaries and past 4 GiB."""
