@@ -118,6 +118,19 @@ from an existing document.  The document and --support-table stay what they are 
 `--report-weight size` / `--weight size`.  To stderr, after the selection's lines:
 `count table: R rows, S samples, J joined to results, M without a result counted as unclassified`.
 
+    python -m blutils_amd.cli blastn build-consensus ... --blast-outfmt SPEC
+
+not in the reference: tables in any outfmt-6 column order.  build-consensus expects the thirteen columns of the
+reference's own blastn call, `6 qseqid saccver staxid pident length mismatch gapopen qstart qend sstart send evalue bitscore`.  A
+table written with another list — `6 std staxids`, one that carries `qcovs` or `qlen`, the output of an older pipeline — is read
+with --blast-outfmt SPEC, SPEC being the string blastn was given: specifiers separated by blanks, an optional leading `6`, `std`
+for BLAST's twelve standard columns, at most 64 columns, none named twice.  The seven fields the run reads are found by name:
+the query (`qseqid`, else `qacc`, else `qaccver`), the subject accession (`saccver`, else `sacc`, else `sseqid`), the taxid
+(`staxid`, else `staxids`, of which the id before the first `;` counts), `pident`, `length`, `bitscore` and — only needed by
+--max-e-value — `evalue`; every other column is skipped.  The run gives what it gives on a copy of the table rewritten to the
+reference's columns, under every other flag, and both parsers read the fields in place: no rewritten copy is made.  A line with
+fewer fields than SPEC names is an error naming the line.  run-with-consensus writes its own table and has no such flag.
+
     python -m blutils_amd.cli cache-db TAX.json CACHE [-u]
 
 writes the binary cache of a taxonomies file (not in the reference CLI; pass CACHE as -t afterwards).  
@@ -175,6 +188,10 @@ def build_parser() -> argparse.ArgumentParser:
     bc.add_argument("-u", "--use-taxid", action="store_true")
     bc.add_argument("--out-format", default="json", choices=["json", "jsonl", "yaml"])
     bc.add_argument("--device", type=int, default=0, help="HIP device ordinal (not in the reference CLI)")
+    bc.add_argument("--blast-outfmt", metavar="SPEC",
+                    help="the -outfmt string BLAST_OUT was written with, when it is not the reference's `6 qseqid saccver staxid pident "
+                         "length mismatch gapopen qstart qend sstart send evalue bitscore`: e.g. \"6 std staxids\"; the columns are "
+                         "found by name, in any order (not in the reference CLI)")
     rw = blastn.add_parser("run-with-consensus", help="blastn fan-out (chunks of 50 queries) + consensus")
     rw.add_argument("query", nargs="?", default="-")
     rw.add_argument("-d", "--database", required=True)
@@ -564,6 +581,14 @@ def main(argv=None) -> int:
     _check_count_table(args)
     if args.count_table is not None:
         extra["count_table"] = args.count_table
+    if args.blast_outfmt is not None:
+        try:
+            layout = pipeline.table_layout(args.blast_outfmt)
+        except _native.BluError:
+            raise SystemExit(f"--blast-outfmt: {_native.last_error()}")
+        if layout.e_value == pipeline.TABLE_LAYOUT_NO_COLUMN and args.max_e_value is not None:
+            raise SystemExit("--blast-outfmt: --max-e-value needs an `evalue` column and SPEC names none")
+        extra["blast_outfmt"] = layout
     if args.support_table is not None:
         build = functools.partial(pipeline.build_consensus_identities_with_tables, report_path=args.report,
                                   sample_table_path=args.sample_table, report_weight=args.report_weight,

@@ -152,8 +152,11 @@ struct TaxonCodes {
 // the dictionaries, so that everything after sees the kept lines only; ht.n_lines / ht.n_kept are set.
 // taxa: a taxon filter's codes, or null: the parse takes each line's verdict from its row's code before the
 // thresholds, and the counts are left in *taxa.  Rows are dropped as under flt; either may be given without the other.
+// lay: a checked column layout that is not the reference's own, or null: the parse then runs the layout builds
+// of its kernels, which read the role fields where the layout puts them; a file they decline goes to the CPU parser with the
+// same layout.
 int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, std::string* why,
-                  const blu_hit_filter* flt = nullptr, TaxonCodes* taxa = nullptr);
+                  const blu_hit_filter* flt = nullptr, TaxonCodes* taxa = nullptr, const blu_table_layout* lay = nullptr);
 // an f64 field as the host parser types it (pipeline_ingest.cpp: parse_f64 — strtod's value); false: not a number.  The GPU ingest
 // decides with it the e-values its own arithmetic leaves open.
 bool parse_f64_field(const char* p, size_t n, double* out);

@@ -419,18 +419,242 @@ __global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_taxa(const unsign
     parse_rows_body<PARSE_TAXA>(text, line_start, n_rows, taxmap, o, flags, nullptr, &flt->f);
 }
 
+// ---- 2a. the parse under a column layout.  The table was written with another `-outfmt "6 ..."` list than the
+// reference's: the seven fields the parse reads — the roles — sit where include/blu_pipeline.h's blu_table_layout says.  The
+// kernels below are the layout builds of the three above: the same stage, the same column-at-a-time walk over the same device
+// functions (hash_step / hash_finish, NumState, the range checks, taxid_lookup, taxon_verdict, filter_row), the same flags; what
+// differs is where a field begins and ends.  The layout is a kernel argument, the same for every thread: it lives in scalar
+// registers, and every test against it is a vector compare with a scalar operand.
+enum : int { ROLE_QUERY = 0, ROLE_ACC = 1, ROLE_TAX = 2, ROLE_PID = 3, ROLE_ALN = 4, ROLE_BS = 5, ROLE_E = 6, N_ROLES = 7 };
+struct DevLayout {               // 48 bytes
+    uint32_t n_cols;             // fields a line must have (1 .. 64)
+    uint32_t col[N_ROLES];       // column of each role; ROLE_E: 0xFFFFFFFF without an e-value column (the threshold is refused then)
+    uint32_t tax_list;           // the taxid field is `staxids`: the number ends at its first ';'
+    uint32_t reserved;
+    unsigned long long wanted;   // bit t: tab t — the one behind column t — bounds a role field (column t or t + 1 holds a role)
+};
+
+// The general form under a layout: parse_row_general_body with the column tests against the layout, the line walked up to the
+// end of column n_cols - 1, and a `staxids` field fed to the number reader up to its first ';' only.
+template <int MODE>
+__device__ __noinline__ void parse_row_general_layout(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
+                                                      const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
+                                                      unsigned long long* __restrict__ n_unmatched, const DevFilter* flt, const DevLayout L) {
+    constexpr bool FILTER = MODE != PARSE_PLAIN;
+    const uint64_t p = line_start[i];
+    uint64_t e = line_start[i + 1] - 1;                 // the newline (or one past the end of a last line without one)
+    if (e > p && text[e - 1] == '\r') --e;
+    if (e <= p) { atomicOr(flags, FB_EMPTY_LINE); return; }
+    const uint32_t n_cols = L.n_cols, c_q = L.col[ROLE_QUERY], c_a = L.col[ROLE_ACC], c_tax = L.col[ROLE_TAX], c_pid = L.col[ROLE_PID],
+                   c_aln = L.col[ROLE_ALN], c_bs = L.col[ROLE_BS];
+    uint32_t c_e = 0xFFFFFFFFu;                         // (the e-value column, when its threshold is on)
+    if constexpr (FILTER) if ((flt->mask & BLU_FILTER_MAX_E_VALUE) && L.col[ROLE_E] < n_cols) c_e = L.col[ROLE_E];
+    uint32_t col = 0;
+    uint64_t fstart = p;                                // start of the current field
+    unsigned long long h = 1469598103934665603ull;
+    NumState num;
+    num.reset();
+    bool cut = false;                                   // behind the first ';' of a `staxids` field
+    double v_tax = 0, v_pid = 0, v_aln = 0, v_bs = 0;
+    uint32_t fb = 0;
+    unsigned long long e_mant = 0;
+    int e_exp = 0;
+    bool e_neg = false;
+    auto end_field = [&](uint64_t fend) {
+        const uint64_t len = fend - fstart;
+        if (col == c_q) { o.qh[i] = hash_finish(h, (uint32_t)len); o.qpos[i] = fstart | (len << 44); if (len >= (1u << 20)) fb |= FB_COLUMNS; }
+        else if (col == c_a) { o.ah[i] = hash_finish(h, (uint32_t)len); o.apos[i] = fstart | (len << 44); if (len >= (1u << 20)) fb |= FB_COLUMNS; }
+        else if (col == c_tax) { if (!num.value(&v_tax) || num.seen_dot || num.seen_exp) fb |= FB_NUMBER; }   // (Int64 columns, as in the plain form)
+        else if (col == c_pid) { if (!num.value(&v_pid)) fb |= FB_NUMBER; }
+        else if (col == c_aln) { if (!num.value(&v_aln) || num.seen_dot || num.seen_exp) fb |= FB_NUMBER; }
+        else if (col == c_bs) { if (!num.value(&v_bs)) fb |= FB_NUMBER; }
+        else if (FILTER && col == c_e) { if (!num.plain()) fb |= FB_NUMBER; e_mant = num.mant; e_exp = num.exponent(); e_neg = num.neg; }
+        ++col;
+        fstart = fend + 1;
+        h = 1469598103934665603ull;
+        num.reset();
+        cut = false;
+    };
+    // aligned 16-byte loads; bytes outside [p, e) are skipped
+    for (uint64_t a = p & ~15ull; a < e && col < n_cols; a += 16) {
+        const uint4 v = *reinterpret_cast<const uint4*>(text + a);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const uint64_t q = a + k;
+            if (q < p || q >= e || col >= n_cols) continue;
+            const uint32_t c = (w[k >> 2] >> (8 * (k & 3))) & 0xFF;
+            if (c == '\t') { end_field(q); continue; }
+            if (col == c_q || col == c_a) { h = hash_step(h, c); if (c == '"') fb |= FB_QUOTE; }
+            else if (col == c_tax) { if (L.tax_list && c == ';') cut = true; if (!cut) num.feed(c, q == fstart); }
+            else if (col == c_pid || col == c_aln || col == c_bs || (FILTER && col == c_e)) num.feed(c, q == fstart);
+        }
+    }
+    if (col < n_cols) end_field(e);                     // the last field ends with the line
+    if (col < n_cols) fb |= FB_COLUMNS;
+    if (fb) { atomicOr(flags, fb); return; }
+    const double bs_t = trunc(v_bs);
+    if (!(bs_t >= -2147483648.0 && bs_t <= 2147483647.0) || !(v_aln >= -2147483648.0 && v_aln <= 2147483647.0) ||
+        !(v_tax >= -9.2e18 && v_tax <= 9.2e18)) { atomicOr(flags, FB_RANGE); return; }
+    const uint32_t row = taxid_lookup(taxmap, (long long)v_tax);   // left join (mod.rs:72-76)
+    if constexpr (MODE == PARSE_TAXA) {
+        if (taxon_verdict(reinterpret_cast<const DevFilterTaxa*>(flt)->t, row)) flt->keep[i] = KEEP_NO;
+        else filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
+    } else if constexpr (FILTER) filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
+    else if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull);
+    o.tax[i] = row; o.pid[i] = v_pid; o.aln[i] = (int32_t)v_aln; o.bs[i] = (int32_t)bs_t;
+}
+
+// The staged form under a layout: parse_rows_body with (1) a tab scan that walks the line's tabs up to the end of column
+// n_cols - 1 — a shorter line is FB_COLUMNS, as a line of fewer than 13 columns is above — and leaves in LDS only the bounds of
+// the role fields, begin and end per role and thread: 2 x 7 x 256 x 2 = 7 KB beside the 32 KB stage whatever the column count
+// (one word per column would be 64 x 256 x 2 = 32 KB more); (2) the same walk over the role fields, one role at a time.
+// A thread reads back only what it wrote itself: no barrier between (1) and (2).
+template <int MODE>
+__device__ __forceinline__ void parse_rows_layout_body(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t n_rows,
+                                                       const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
+                                                       unsigned long long* __restrict__ n_unmatched, const DevFilter* flt, const DevLayout& L) {
+    constexpr bool FILTER = MODE != PARSE_PLAIN;
+    __shared__ uint4 stage16[STAGE_BYTES / 16];
+    __shared__ uint16_t field_at[2 * N_ROLES * PARSE_THREADS];       // [role][begin, end][thread]
+    const uint32_t r0 = blockIdx.x * PARSE_THREADS, r1 = min(r0 + (uint32_t)PARSE_THREADS, n_rows), i = r0 + threadIdx.x;
+    const uint64_t ls0 = line_start[r0], s1 = line_start[r1];       // (line_start[n_rows] = one past the last newline, or size + 1)
+    const uint64_t my_p = line_start[min(i, r1 - 1)], my_e = line_start[min(i, r1 - 1) + 1];
+    const uint64_t s0 = ls0 & ~15ull;
+    if (s1 - s0 > STAGE_BYTES) {                                     // uniform over the block
+        if (i < r1) parse_row_general_layout<MODE>(text, line_start, i, taxmap, o, flags, n_unmatched, flt, L);
+        return;
+    }
+    {
+        const uint32_t n16 = (uint32_t)((s1 - s0 + 15) >> 4);        // (reads at most 15 bytes past s1 <= size + 1: inside the 64 bytes of padding)
+        const uint4* src = reinterpret_cast<const uint4*>(text + s0);
+        constexpr int PER_THREAD = STAGE_BYTES / 16 / PARSE_THREADS; // all of a thread's loads are in flight before the first is stored
+        uint4 v[PER_THREAD];
+#pragma unroll
+        for (int j = 0; j < PER_THREAD; ++j) { const uint32_t k = threadIdx.x + (uint32_t)j * PARSE_THREADS; v[j] = src[min(k, n16 - 1)]; }
+#pragma unroll
+        for (int j = 0; j < PER_THREAD; ++j) { const uint32_t k = threadIdx.x + (uint32_t)j * PARSE_THREADS; if (k < n16) stage16[k] = v[j]; }
+    }
+    __syncthreads();
+    if (i >= r1) return;
+    const unsigned char* sb = reinterpret_cast<const unsigned char*>(stage16);
+    const uint32_t* sw = reinterpret_cast<const uint32_t*>(stage16);
+    const uint32_t p = (uint32_t)(my_p - s0);
+    uint32_t e = (uint32_t)(my_e - 1 - s0);                          // the newline (or one past the end of a last line without one)
+    if (e > p && sb[e - 1] == '\r') --e;
+    if (e <= p) { atomicOr(flags, FB_EMPTY_LINE); return; }
+    uint16_t* const mine = field_at + threadIdx.x;
+    auto set_begin = [&](int r, uint32_t at) { mine[(2 * r) * PARSE_THREADS] = (uint16_t)at; };
+    auto set_end = [&](int r, uint32_t at) { mine[(2 * r + 1) * PARSE_THREADS] = (uint16_t)at; };
+    auto begin_of = [&](int r) { return (uint32_t)mine[(2 * r) * PARSE_THREADS]; };
+    auto end_of = [&](int r) { return (uint32_t)mine[(2 * r + 1) * PARSE_THREADS]; };
+    // ---- (1) the tabs, four bytes per compare as above; tab t ends column t and column t + 1 begins behind it
+    const uint32_t n_cols = L.n_cols;
+#pragma unroll
+    for (int r = 0; r < N_ROLES; ++r) if (L.col[r] == 0) set_begin(r, p);
+    uint32_t n_tabs = 0;
+    for (uint32_t a = p & ~3u; a < e && n_tabs < n_cols; a += 4) {
+        const uint32_t x = sw[a >> 2] ^ 0x09090909u;
+        uint32_t m = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);   // bit 7 of every byte that is a tab
+        if (a < p) m &= 0xFFFFFFFFu << (8 * (p - a));
+        if (e - a < 4) m &= (1u << (8 * (e - a))) - 1u;
+        while (m && n_tabs < n_cols) {
+            if ((L.wanted >> n_tabs) & 1ull) {
+                const uint32_t at = a + ((uint32_t)__builtin_ctz(m) >> 3);
+#pragma unroll
+                for (int r = 0; r < N_ROLES; ++r) {
+                    if (L.col[r] == n_tabs) set_end(r, at);
+                    if (L.col[r] == n_tabs + 1) set_begin(r, at + 1);
+                }
+            }
+            ++n_tabs;
+            m &= m - 1;
+        }
+    }
+    if (n_tabs + 1 < n_cols) { atomicOr(flags, FB_COLUMNS); return; }   // fewer columns than the layout names
+    if (n_tabs + 1 == n_cols) {                                      // the layout's last column ends with the line
+#pragma unroll
+        for (int r = 0; r < N_ROLES; ++r) if (L.col[r] == n_cols - 1) set_end(r, e);
+    }
+    uint32_t fb = 0;
+    // ---- (2) query and accession: FNV-1a over the field, as in the general form
+    auto hash_field = [&](uint32_t s, uint32_t t) {
+        unsigned long long h = 1469598103934665603ull;
+        for (uint32_t q = s; q < t; ++q) { const uint32_t c = sb[q]; h = hash_step(h, c); if (c == '"') fb |= FB_QUOTE; }
+        return hash_finish(h, t - s);
+    };
+    const uint32_t q0 = begin_of(ROLE_QUERY), q1 = end_of(ROLE_QUERY), a0 = begin_of(ROLE_ACC), a1 = end_of(ROLE_ACC);
+    const unsigned long long qh = hash_field(q0, q1), ah = hash_field(a0, a1);
+    // ---- the four numbers; list: the field is `staxids`, the number ends at its first ';'
+    auto number = [&](int r, bool integer, bool list, double* v) {
+        NumState num;
+        num.reset();
+        const uint32_t s = begin_of(r), t = end_of(r);
+        for (uint32_t q = s; q < t; ++q) { const uint32_t c = sb[q]; if (list && c == ';') break; num.feed(c, q == s); }
+        if (!num.value(v) || (integer && (num.seen_dot || num.seen_exp))) fb |= FB_NUMBER;
+    };
+    double v_tax = 0, v_pid = 0, v_aln = 0, v_bs = 0;
+    number(ROLE_TAX, true, L.tax_list != 0, &v_tax);                 // (subject_taxid and align_length are Int64 columns, mod.rs:226-244)
+    number(ROLE_PID, false, false, &v_pid);
+    number(ROLE_ALN, true, false, &v_aln);
+    number(ROLE_BS, false, false, &v_bs);
+    unsigned long long e_mant = 0;
+    int e_exp = 0;
+    bool e_neg = false;
+    if constexpr (FILTER) {
+        if ((flt->mask & BLU_FILTER_MAX_E_VALUE) && L.col[ROLE_E] < n_cols) {   // the e-value column, read only under its threshold
+            NumState num;
+            num.reset();
+            const uint32_t s = begin_of(ROLE_E), t = end_of(ROLE_E);
+            for (uint32_t q = s; q < t; ++q) num.feed(sb[q], q == s);
+            if (!num.plain()) fb |= FB_NUMBER;
+            e_mant = num.mant; e_exp = num.exponent(); e_neg = num.neg;
+        }
+    }
+    if (fb) { atomicOr(flags, fb); return; }
+    const double bs_t = trunc(v_bs);                                // mod.rs:184 AnyValue::Float64 -> try_extract::<i64> (truncation)
+    if (!(bs_t >= -2147483648.0 && bs_t <= 2147483647.0) || !(v_aln >= -2147483648.0 && v_aln <= 2147483647.0) ||
+        !(v_tax >= -9.2e18 && v_tax <= 9.2e18)) { atomicOr(flags, FB_RANGE); return; }
+    const uint32_t row = taxid_lookup(taxmap, (long long)v_tax);   // left join (mod.rs:72-76)
+    if constexpr (MODE == PARSE_TAXA) {
+        if (taxon_verdict(reinterpret_cast<const DevFilterTaxa*>(flt)->t, row)) flt->keep[i] = KEEP_NO;
+        else filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
+    } else if constexpr (FILTER) filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
+    else if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull);
+    o.qh[i] = qh; o.qpos[i] = (s0 + q0) | ((unsigned long long)(q1 - q0) << 44);
+    o.ah[i] = ah; o.apos[i] = (s0 + a0) | ((unsigned long long)(a1 - a0) << 44);
+    o.tax[i] = row; o.pid[i] = v_pid; o.aln[i] = (int32_t)v_aln; o.bs[i] = (int32_t)bs_t;
+}
+
+__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
+                                                                   uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
+                                                                   unsigned long long* __restrict__ n_unmatched, DevLayout lay) {
+    parse_rows_layout_body<PARSE_PLAIN>(text, line_start, n_rows, taxmap, o, flags, n_unmatched, nullptr, lay);
+}
+__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout_filtered(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
+                                                                            uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
+                                                                            const DevFilter* __restrict__ flt, DevLayout lay) {
+    parse_rows_layout_body<PARSE_FILTER>(text, line_start, n_rows, taxmap, o, flags, nullptr, flt, lay);
+}
+__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout_taxa(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
+                                                                        uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
+                                                                        const DevFilterTaxa* __restrict__ flt, DevLayout lay) {
+    parse_rows_layout_body<PARSE_TAXA>(text, line_start, n_rows, taxmap, o, flags, nullptr, &flt->f, lay);
+}
+
 // ---- 2b. hit filter: the e-values left to the host, and the stable compaction of the parsed rows ---------------------------
-// rows whose keep word is KEEP_ASK_HOST, in any order, each with the place of its column 11 (field offset | length << 44)
+// rows whose keep word is KEEP_ASK_HOST, in any order, each with the place of its e-value field (field offset | length << 44);
+// e_col: the 0-based column that holds it — 11 in the reference's columns, the layout's otherwise
 __global__ void list_undecided(const uint32_t* __restrict__ keep, uint32_t n, const unsigned char* __restrict__ text,
                                const uint64_t* __restrict__ line_start, uint32_t cap, uint32_t* __restrict__ rows,
-                               unsigned long long* __restrict__ pos, uint32_t* __restrict__ cursor) {
+                               unsigned long long* __restrict__ pos, uint32_t* __restrict__ cursor, uint32_t e_col) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || keep[i] != KEEP_ASK_HOST) return;
     const uint64_t p = line_start[i];
     uint64_t e = line_start[i + 1] - 1;
     if (e > p && text[e - 1] == '\r') --e;
     uint64_t q = p;
-    for (int tabs = 0; q < e && tabs < 11; ++q) if (text[q] == '\t') ++tabs;
+    for (uint32_t tabs = 0; q < e && tabs < e_col; ++q) if (text[q] == '\t') ++tabs;
     const uint64_t s = q;
     while (q < e && text[q] != '\t') ++q;
     const uint32_t at = atomicAdd(cursor, 1u);
@@ -644,7 +868,7 @@ __global__ void gather_cols(Cols in, ColsOut out, const uint32_t* __restrict__ p
 
 const char* fallback_text(uint32_t f) {
     if (f & FB_EMPTY_LINE) return "an empty line";
-    if (f & FB_COLUMNS) return "a line with fewer than 13 columns (or an oversized field)";
+    if (f & FB_COLUMNS) return "a line with fewer columns than the 13 of outfmt-6 or than the layout names (or an oversized field)";
     if (f & FB_QUOTE) return "a quoted query / accession field";
     if (f & FB_NUMBER) return "a numeric field outside the decimal fast path";
     if (f & FB_RANGE) return "a number outside the engine's 32-bit columns";
@@ -731,6 +955,7 @@ struct GpuIngest {
     IngestTrace& lap;
     const blu_hit_filter* const flt;   // (null: none)
     TaxonCodes* const taxa;            // (null: none)
+    const blu_table_layout* const lay; // (null: the reference's columns; else checked, and not the reference's own: DESIGN.md §23)
 
     unsigned char* d_text = nullptr;   // the padded text: upload_and_index -> accession_dictionary_finish, which frees it
     uint64_t* d_line = nullptr;        // line starts: upload_and_index -> parse, drop_filtered_rows (which frees them)
@@ -863,8 +1088,23 @@ struct GpuIngest {
         return BLU_OK;
     }
 
-    // ---- parse: one of the three builds of parse_rows.  Under a filter it leaves a keep word per line, and
-    // its counts come back with the flags in `back`
+    // the layout as the kernels read it
+    DevLayout device_layout() const {
+        DevLayout d{};
+        d.n_cols = lay->n_columns;
+        d.col[ROLE_QUERY] = lay->query; d.col[ROLE_ACC] = lay->accession; d.col[ROLE_TAX] = lay->taxid; d.col[ROLE_PID] = lay->perc_identity;
+        d.col[ROLE_ALN] = lay->align_length; d.col[ROLE_BS] = lay->bit_score; d.col[ROLE_E] = lay->e_value;
+        d.tax_list = lay->taxid_is_list;
+        for (int r = 0; r < N_ROLES; ++r) {
+            if (d.col[r] >= d.n_cols) continue;                      // (no e-value column)
+            d.wanted |= 1ull << d.col[r];
+            if (d.col[r] > 0) d.wanted |= 1ull << (d.col[r] - 1);
+        }
+        return d;
+    }
+
+    // ---- parse: one of the three builds of parse_rows, or under a column layout of parse_rows_layout.  Under a
+    // filter it leaves a keep word per line, and its counts come back with the flags in `back`
     int parse() {
         TaxidMap::E* d_taxmap = nullptr;
         HIP_CHECK(pol, mem.upload(&d_taxmap, row_of.tab.data(), row_of.tab.size(), "taxid map"));
@@ -875,8 +1115,11 @@ struct GpuIngest {
         const RowOut o{d_qh, d_ah, d_qpos, d_apos, d_tax, d_pid, d_aln, d_bs};
         const DevTaxidMap tm{d_taxmap, row_of.tab.size() - 1};
         const dim3 blocks(grid(n_rows, PARSE_THREADS)), threads(PARSE_THREADS);
+        if (lay && flt && (flt->mask & BLU_FILTER_MAX_E_VALUE) && lay->e_value >= lay->n_columns) return fallback("an e-value threshold without an e-value column");
+        const DevLayout dl = lay ? device_layout() : DevLayout{};
         if (!flt && !taxa) {
-            hipLaunchKernelGGL(parse_rows, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, d_big);
+            if (lay) hipLaunchKernelGGL(parse_rows_layout, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, d_big, dl);
+            else hipLaunchKernelGGL(parse_rows, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, d_big);
             return check_flags();
         }
         HIP_CHECK(pol, mem.alloc(&d_keep, (size_t)n_rows * 4, "keep words"));
@@ -887,7 +1130,8 @@ struct GpuIngest {
         hf.f.keep = d_keep; hf.f.counts = d_fcnt;
         if (!taxa) {
             HIP_CHECK(pol, hipMemcpy(d_filter, &hf.f, sizeof hf.f, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(parse_rows_filtered, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilter*)&d_filter->f);
+            if (lay) hipLaunchKernelGGL(parse_rows_layout_filtered, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilter*)&d_filter->f, dl);
+            else hipLaunchKernelGGL(parse_rows_filtered, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilter*)&d_filter->f);
         } else {
             // the row codes go up next to the taxid map; the verdict is taken in the parse
             const size_t n_tax = taxa->code.size();
@@ -895,7 +1139,8 @@ struct GpuIngest {
             hf.t.code = d_code; hf.t.n_tax = (uint32_t)n_tax; hf.t.unmatched = taxa->unmatched;
             hf.t.not_only = d_fcnt + HIT_SPREAD + 1; hf.t.excluded_by = hf.t.not_only + HIT_SPREAD;
             HIP_CHECK(pol, hipMemcpy(d_filter, &hf, sizeof hf, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(parse_rows_taxa, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilterTaxa*)d_filter);
+            if (lay) hipLaunchKernelGGL(parse_rows_layout_taxa, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilterTaxa*)d_filter, dl);
+            else hipLaunchKernelGGL(parse_rows_taxa, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilterTaxa*)d_filter);
         }
         back.resize(n_back());
         HIP_CHECK(pol, hipMemcpy(back.data(), d_flags, n_back() * 8, hipMemcpyDeviceToHost));
@@ -943,7 +1188,8 @@ struct GpuIngest {
         HIP_CHECK(pol, hipMemset(d_urow, 0xFF, (size_t)n_u * 4));
         HIP_CHECK(pol, hipMemset(d_upos, 0, (size_t)n_u * 8));
         STEP(zero_counter());
-        hipLaunchKernelGGL(list_undecided, grid(n_rows), dim3(256), 0, 0, (const uint32_t*)d_keep, n_rows, d_text, d_line, n_u, d_urow, d_upos, d_counter);
+        hipLaunchKernelGGL(list_undecided, grid(n_rows), dim3(256), 0, 0, (const uint32_t*)d_keep, n_rows, d_text, d_line, n_u, d_urow, d_upos, d_counter,
+                           lay ? lay->e_value : 11u);
         std::vector<char> e_bytes;
         std::vector<unsigned long long> e_off;
         STEP(download_strings(d_upos, n_u, e_bytes, e_off));
@@ -1200,7 +1446,7 @@ struct GpuIngest {
 }  // namespace
 
 int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, std::string* why,
-                  const blu_hit_filter* flt, TaxonCodes* taxa) {
+                  const blu_hit_filter* flt, TaxonCodes* taxa, const blu_table_layout* lay) {
     if (flt && !(flt->mask & 15u)) flt = nullptr;
     IngestTrace lap;
     std::string why_unread;
@@ -1221,7 +1467,7 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
     }
     // (in a block of its own: the sort thread is joined and the host strings are let go before the arena's buffers are)
     int rc;
-    { GpuIngest ingest{fd, size, row_of, device, host_columns, ht, mem, mem.pol, lap, flt, taxa}; rc = ingest.run(); }
+    { GpuIngest ingest{fd, size, row_of, device, host_columns, ht, mem, mem.pol, lap, flt, taxa, lay}; rc = ingest.run(); }
     if (rc != BLU_OK) ht.clear();
     lap("hand-over");
     // with room on the card (mem.keep) the work buffers — the text, the hashes, the dictionaries: 10 GB for a 2 M-query table —

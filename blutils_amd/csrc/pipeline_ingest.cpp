@@ -170,7 +170,16 @@ inline bool filter_keeps(const blu_hit_filter& f, double pid, int64_t aln, doubl
     return true;
 }
 
-void parse_chunk(Chunk& c, const Db& db, const char* path, const blu_hit_filter* flt = nullptr, const TaxonCodes* taxa = nullptr) {
+// LAID_OUT: the seven role fields are read through `lay` (blu_table_layout: a checked layout that is not the
+// reference's own); otherwise the positions are the reference's literals and lay is not looked at.
+template <bool LAID_OUT>
+void parse_chunk_as(Chunk& c, const Db& db, const char* path, const blu_hit_filter* flt, const TaxonCodes* taxa, const blu_table_layout* lay) {
+    constexpr int MAX_COLS = LAID_OUT ? (int)BLU_TABLE_LAYOUT_MAX_COLUMNS : 13;
+    const int n_cols = LAID_OUT ? (int)lay->n_columns : 13;
+    const int c_q = LAID_OUT ? (int)lay->query : 0, c_a = LAID_OUT ? (int)lay->accession : 1, c_tax = LAID_OUT ? (int)lay->taxid : 2;
+    const int c_pid = LAID_OUT ? (int)lay->perc_identity : 3, c_aln = LAID_OUT ? (int)lay->align_length : 4;
+    const int c_e = LAID_OUT ? (int)lay->e_value : 11, c_bs = LAID_OUT ? (int)lay->bit_score : 12;   // (no e-value column: refused before the parse)
+    const bool tax_list = LAID_OUT && lay->taxid_is_list != 0;
     if (taxa) c.excluded_by.assign(taxa->n_exclude, 0);
     const char* p = c.begin;
     uint64_t line_no = 0;
@@ -185,10 +194,10 @@ void parse_chunk(Chunk& c, const Db& db, const char* path, const blu_hit_filter*
         if (lend > p && lend[-1] == '\r') --lend;
         ++line_no;
         if (lend > p) {
-            std::string_view col[13];
+            std::string_view col[MAX_COLS];
             int nc = 0;
             const char* s = p;
-            while (nc < 13) {
+            while (nc < n_cols) {
                 const char* tab = (const char*)memchr(s, '\t', (size_t)(lend - s));
                 const char* ce = tab ? tab : lend;
                 col[nc++] = std::string_view(s, (size_t)(ce - s));
@@ -196,14 +205,16 @@ void parse_chunk(Chunk& c, const Db& db, const char* path, const blu_hit_filter*
                 s = tab + 1;
             }
             char msg[512];
-            if (nc < 13) {
-                snprintf(msg, sizeof msg, "line %llu(+%llu) of %s has %d columns, outfmt-6 with 13 expected (mod.rs:226-244)",
-                         (unsigned long long)line_no, (unsigned long long)c.first_line, path, nc);
+            if (nc < n_cols) {
+                snprintf(msg, sizeof msg, "line %llu(+%llu) of %s has %d columns, outfmt-6 with %d expected (%s)",
+                         (unsigned long long)line_no, (unsigned long long)c.first_line, path, nc, n_cols, LAID_OUT ? "the table layout" : "mod.rs:226-244");
                 c.rc = BLU_ERR_PARSE; c.err = msg; return;
             }
             double pid, bs;
             int64_t taxid_i, aln;
-            if (!parse_i64(col[2], &taxid_i) || !parse_f64(col[3], &pid) || !parse_i64(col[4], &aln) || !parse_f64(col[12], &bs)) {
+            std::string_view tax_field = col[c_tax];
+            if (tax_list) tax_field = tax_field.substr(0, tax_field.find(';'));   // `staxids`: the id before the first ';'
+            if (!parse_i64(tax_field, &taxid_i) || !parse_f64(col[c_pid], &pid) || !parse_i64(col[c_aln], &aln) || !parse_f64(col[c_bs], &bs)) {
                 snprintf(msg, sizeof msg, "line %llu(+%llu) of %s: numeric column does not parse", (unsigned long long)line_no,
                          (unsigned long long)c.first_line, path);
                 c.rc = BLU_ERR_PARSE; c.err = msg; return;
@@ -216,7 +227,7 @@ void parse_chunk(Chunk& c, const Db& db, const char* path, const blu_hit_filter*
             }
             if (flt || taxa) {                                // (validated like every line; dropped before it reaches a dictionary)
                 double ev = 0;
-                if (flt && (flt->mask & BLU_FILTER_MAX_E_VALUE) && !parse_f64(col[11], &ev)) {
+                if (flt && (flt->mask & BLU_FILTER_MAX_E_VALUE) && !parse_f64(col[c_e], &ev)) {
                     snprintf(msg, sizeof msg, "line %llu(+%llu) of %s: numeric column does not parse (e_value)", (unsigned long long)line_no,
                              (unsigned long long)c.first_line, path);
                     c.rc = BLU_ERR_PARSE; c.err = msg; return;
@@ -236,13 +247,13 @@ void parse_chunk(Chunk& c, const Db& db, const char* path, const blu_hit_filter*
             }
             RawRow r;
             // rows of one query usually sit next to each other: the previous row's ids are tried before the dictionaries
-            if (!have_last || col[0] != last_q_raw) {
+            if (!have_last || col[c_q] != last_q_raw) {
                 bool is_new = false;
-                last_q = c.queries.intern(c.clean(col[0]), &is_new);
+                last_q = c.queries.intern(c.clean(col[c_q]), &is_new);
                 if (is_new) c.q_count.push_back(0);
-                last_q_raw = col[0];
+                last_q_raw = col[c_q];
             }
-            if (!have_last || col[1] != last_a_raw) { last_a = c.accs.intern(c.clean(col[1])); last_a_raw = col[1]; }
+            if (!have_last || col[c_a] != last_a_raw) { last_a = c.accs.intern(c.clean(col[c_a])); last_a_raw = col[c_a]; }
             have_last = true;
             ++c.q_count[last_q];
             r.lq = last_q; r.la = last_a;
@@ -262,6 +273,11 @@ void parse_chunk(Chunk& c, const Db& db, const char* path, const blu_hit_filter*
     // this chunk's accessions in byte order (String::cmp), for the merge below
     c.acc_sorted = c.accs.keys;
     std::sort(c.acc_sorted.begin(), c.acc_sorted.end());
+}
+void parse_chunk(Chunk& c, const Db& db, const char* path, const blu_hit_filter* flt = nullptr, const TaxonCodes* taxa = nullptr,
+                 const blu_table_layout* lay = nullptr) {
+    if (lay) parse_chunk_as<true>(c, db, path, flt, taxa, lay);
+    else parse_chunk_as<false>(c, db, path, flt, taxa, nullptr);
 }
 
 // ---- taxon filter (include/blu_pipeline.h: blu_taxon_filter): the two lists -> one code per taxonomy row.
@@ -360,6 +376,96 @@ int taxon_codes(const Db& db, const blu_taxon_filter& f, unsigned nthreads, Taxo
     return BLU_OK;
 }
 
+// ---- the table's column layout (include/blu_pipeline.h: blu_table_layout) ----------------------------------------
+int check_table_layout(const blu_table_layout* lay, const blu_hit_filter* flt, const blu_table_layout** use) {
+    *use = nullptr;
+    if (!lay) return BLU_OK;
+    if (lay->struct_size != sizeof(blu_table_layout)) {
+        set_error("table layout: struct_size %u is not a blu_table_layout this library knows (%zu bytes)", lay->struct_size, sizeof(blu_table_layout));
+        return BLU_ERR_INVALID_ARG;
+    }
+    if (lay->n_columns < 1 || lay->n_columns > BLU_TABLE_LAYOUT_MAX_COLUMNS) {
+        set_error("table layout: %u columns, 1 to %u are taken", lay->n_columns, BLU_TABLE_LAYOUT_MAX_COLUMNS);
+        return BLU_ERR_INVALID_ARG;
+    }
+    const uint32_t role[7] = {lay->query, lay->accession, lay->taxid, lay->perc_identity, lay->align_length, lay->bit_score, lay->e_value};
+    static const char* const name[7] = {"query", "accession", "taxid", "perc_identity", "align_length", "bit_score", "e_value"};
+    for (int a = 0; a < 7; ++a) {
+        if (a == 6 && role[a] == BLU_TABLE_LAYOUT_NO_COLUMN) continue;
+        if (role[a] >= lay->n_columns) { set_error("table layout: the %s column %u is not one of the %u columns", name[a], role[a], lay->n_columns); return BLU_ERR_INVALID_ARG; }
+        for (int b = 0; b < a; ++b)
+            if (role[a] == role[b]) { set_error("table layout: %s and %s are both column %u", name[b], name[a], role[a]); return BLU_ERR_INVALID_ARG; }
+    }
+    if (lay->taxid_is_list > 1) { set_error("table layout: taxid_is_list is %u, 0 or 1 is taken", lay->taxid_is_list); return BLU_ERR_INVALID_ARG; }
+    if (lay->e_value == BLU_TABLE_LAYOUT_NO_COLUMN && flt && (flt->mask & BLU_FILTER_MAX_E_VALUE)) {
+        set_error("table layout: the e-value threshold (max_e_value) needs an `evalue` column and the layout names none");
+        return BLU_ERR_INVALID_ARG;
+    }
+    const bool reference = lay->n_columns == 13 && lay->query == 0 && lay->accession == 1 && lay->taxid == 2 && lay->perc_identity == 3 &&
+                           lay->align_length == 4 && lay->e_value == 11 && lay->bit_score == 12 && !lay->taxid_is_list;
+    if (!reference) *use = lay;
+    return BLU_OK;
+}
+
+namespace {
+// BLAST's format string -> layout (blu_table_layout_parse).  Roles by priority, not by position: the first name of each list
+// that the string holds.
+int parse_layout_spec(const char* spec, blu_table_layout* out) {
+    static const char* const STD[12] = {"qseqid", "sseqid", "pident", "length", "mismatch", "gapopen", "qstart", "qend", "sstart", "send", "evalue", "bitscore"};
+    std::vector<std::string> cols;
+    const char* p = spec;
+    bool first = true;
+    while (*p) {
+        if (*p == ' ' || *p == '\t') { ++p; continue; }
+        const char* b = p;
+        while (*p && *p != ' ' && *p != '\t') ++p;
+        const std::string tok(b, (size_t)(p - b));
+        bool digits = true, word = true;
+        for (unsigned char ch : tok) {
+            if (ch - '0' >= 10u) digits = false;
+            if (!(ch - '0' < 10u || (ch | 32) - 'a' < 26u || ch == '_')) word = false;
+        }
+        if (!word) { set_error("blast outfmt: `%s` is not a format specifier (letters, digits and `_`)", tok.c_str()); return BLU_ERR_INVALID_ARG; }
+        const bool lead = first;
+        first = false;
+        if (lead && digits) {
+            if (tok != "6") { set_error("blast outfmt: format `%s` is not read, only the tabular format 6", tok.c_str()); return BLU_ERR_INVALID_ARG; }
+            continue;
+        }
+        if (tok == "std") cols.insert(cols.end(), STD, STD + 12);
+        else cols.push_back(tok);
+    }
+    if (cols.size() > BLU_TABLE_LAYOUT_MAX_COLUMNS) {
+        set_error("blast outfmt: %zu columns, at most %u are taken (the first beyond them: `%s`)", cols.size(), BLU_TABLE_LAYOUT_MAX_COLUMNS,
+                  cols[BLU_TABLE_LAYOUT_MAX_COLUMNS].c_str());
+        return BLU_ERR_INVALID_ARG;
+    }
+    for (size_t a = 0; a < cols.size(); ++a)
+        for (size_t b = 0; b < a; ++b)
+            if (cols[a] == cols[b]) { set_error("blast outfmt: `%s` is named twice (columns %zu and %zu)", cols[a].c_str(), b + 1, a + 1); return BLU_ERR_INVALID_ARG; }
+    auto find = [&](std::initializer_list<const char*> names, uint32_t* at, const char** which) {
+        for (const char* n : names)
+            for (size_t k = 0; k < cols.size(); ++k)
+                if (cols[k] == n) { *at = (uint32_t)k; if (which) *which = n; return true; }
+        return false;
+    };
+    blu_table_layout l{};
+    l.struct_size = sizeof l;
+    l.n_columns = (uint32_t)cols.size();
+    const char* tax_name = nullptr;
+    if (!find({"qseqid", "qacc", "qaccver"}, &l.query, nullptr)) { set_error("blast outfmt: no query column: one of `qseqid`, `qacc`, `qaccver` is needed"); return BLU_ERR_INVALID_ARG; }
+    if (!find({"saccver", "sacc", "sseqid"}, &l.accession, nullptr)) { set_error("blast outfmt: no subject column: one of `saccver`, `sacc`, `sseqid` is needed"); return BLU_ERR_INVALID_ARG; }
+    if (!find({"staxid", "staxids"}, &l.taxid, &tax_name)) { set_error("blast outfmt: no taxid column: `staxid` or `staxids` is needed"); return BLU_ERR_INVALID_ARG; }
+    if (!find({"pident"}, &l.perc_identity, nullptr)) { set_error("blast outfmt: no `pident` column"); return BLU_ERR_INVALID_ARG; }
+    if (!find({"length"}, &l.align_length, nullptr)) { set_error("blast outfmt: no `length` column"); return BLU_ERR_INVALID_ARG; }
+    if (!find({"bitscore"}, &l.bit_score, nullptr)) { set_error("blast outfmt: no `bitscore` column"); return BLU_ERR_INVALID_ARG; }
+    if (!find({"evalue"}, &l.e_value, nullptr)) l.e_value = BLU_TABLE_LAYOUT_NO_COLUMN;
+    l.taxid_is_list = strcmp(tax_name, "staxids") == 0 ? 1u : 0u;
+    *out = l;
+    return BLU_OK;
+}
+}  // namespace
+
 static thread_local int g_last_ingest_path = 0;   // 0 = CPU parser, 1 = GPU parser (blu_last_ingest_path)
 
 // a2 + a4 + a5: outfmt-6 text -> SoA columns.  The file is cut into line-aligned chunks; each worker parses its
@@ -367,9 +473,11 @@ static thread_local int g_last_ingest_path = 0;   // 0 = CPU parser, 1 = GPU par
 // Afterwards only the DISTINCT strings are merged — queries in file order (first appearance decides a query's
 // position, mod.rs:192-208), accessions by a tree of sorted-list merges (their id is their rank in byte order) —
 // and the workers scatter their rows into the grouped table.  The result does not depend on the thread count.
-int load_hits(const char* path, const Db& db, HitTable& ht, int device, bool host_columns, const blu_hit_filter* flt, TaxonCodes* taxa) {
+int load_hits(const char* path, const Db& db, HitTable& ht, int device, bool host_columns, const blu_hit_filter* flt, TaxonCodes* taxa,
+              const blu_table_layout* lay) {
     g_last_ingest_path = 0;
     if (flt && !(flt->mask & 15u)) flt = nullptr;   // no threshold given: today's path
+    if (int rc = check_table_layout(lay, flt, &lay)) return rc;   // (the reference's own columns: today's path)
     // GPU parser first (ingest_gpu.hip) when a device is given: same columns bit for bit; files it does not handle
     // (quotes, empty lines, unusual numbers), small files and BLU_INGEST=cpu take the CPU path below.  The GPU path
     // reads the file through its descriptor and never maps it.
@@ -383,7 +491,7 @@ int load_hits(const char* path, const Db& db, HitTable& ht, int device, bool hos
         const bool want_gpu = device >= 0 && db.dup_rows.empty() && !(mode && strcmp(mode, "cpu") == 0) && (fsize >= (1u << 20) || (mode && strcmp(mode, "gpu") == 0));
         int rc = BLU_INGEST_FALLBACK;
         std::string why;
-        if (want_gpu) rc = load_hits_gpu(fd, fsize, db.row_of, device, host_columns, ht, &why, flt, taxa);
+        if (want_gpu) rc = load_hits_gpu(fd, fsize, db.row_of, device, host_columns, ht, &why, flt, taxa, lay);
         ::close(fd);
         if (want_gpu) {
             if (rc == BLU_OK) { g_last_ingest_path = 1; return BLU_OK; }
@@ -410,7 +518,7 @@ int load_hits(const char* path, const Db& db, HitTable& ht, int device, bool hos
         cur = target;
     }
     Trace tr{"[ingest]", 22};
-    parallel_for(nthreads, nthreads, [&](unsigned t) { parse_chunk(chunks[t], db, path, flt, taxa); });
+    parallel_for(nthreads, nthreads, [&](unsigned t) { parse_chunk(chunks[t], db, path, flt, taxa, lay); });
     tr.lap("parse (parallel)");
     uint64_t lines_before = 0;
     size_t nh = 0;
@@ -496,15 +604,17 @@ int load_hits(const char* path, const Db& db, HitTable& ht, int device, bool hos
 
 // The ingest half under a selection, into malloc'd copies of the host columns.
 static int ingest_columns_selected(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
-                            const blu_hit_selection* selection, blu_ingest_columns* out, blu_hit_selection_stats* stats) {
+                            const blu_table_layout* lay, const blu_hit_selection* selection, blu_ingest_columns* out,
+                            blu_hit_selection_stats* stats) {
     Selection sel(selection, stats);
     if (int rc = sel.check()) return rc;
+    if (int rc = check_table_layout(lay, sel.flt, &lay)) return rc;   // (before any file is opened)
     Db db;
     int rc = load_db(taxonomies_file, use_taxid != 0, db);
     if (rc != BLU_OK) return rc;
     if ((rc = sel.resolve(db, worker_threads())) != BLU_OK) return rc;
     HitTable ht;
-    rc = load_hits(blast_output_file, db, ht, device, true, sel.flt, sel.taxa.get());
+    rc = load_hits(blast_output_file, db, ht, device, true, sel.flt, sel.taxa.get(), lay);
     if (rc != BLU_OK) return rc;
     ht.wait_strings();
     if (!ht.strings_ok) { set_error("out of memory while building the query / accession strings"); return BLU_ERR_ALLOC; }
@@ -590,9 +700,15 @@ int blu_ingest_columns_on(const char* blast_output_file, const char* taxonomies_
 
 int blu_ingest_columns_selected(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
                                 const blu_hit_selection* selection, blu_ingest_columns* out, blu_hit_selection_stats* stats) {
+    return blu_ingest_columns_laid_out(blast_output_file, taxonomies_file, use_taxid, device, nullptr, selection, out, stats);
+}
+
+int blu_ingest_columns_laid_out(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                                const blu_table_layout* layout, const blu_hit_selection* selection, blu_ingest_columns* out,
+                                blu_hit_selection_stats* stats) {
     if (!blast_output_file || !taxonomies_file || !out) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     memset(out, 0, sizeof *out);
-    try { return ingest_columns_selected(blast_output_file, taxonomies_file, use_taxid, device, selection, out, stats); }
+    try { return ingest_columns_selected(blast_output_file, taxonomies_file, use_taxid, device, layout, selection, out, stats); }
     catch (const std::bad_alloc&) { blu_ingest_columns_free(out); set_error("out of memory"); return BLU_ERR_ALLOC; }
 }
 
@@ -604,5 +720,15 @@ void blu_ingest_columns_free(blu_ingest_columns* c) {
 }
 
 int blu_last_ingest_path(void) { return g_last_ingest_path; }
+
+int blu_table_layout_parse(const char* spec, blu_table_layout* out) {
+    if (!spec || !out) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    if (out->struct_size != sizeof(blu_table_layout)) {
+        set_error("blu_table_layout_parse: struct_size %u is not a blu_table_layout this library knows (%zu bytes)", out->struct_size, sizeof(blu_table_layout));
+        return BLU_ERR_INVALID_ARG;
+    }
+    try { return parse_layout_spec(spec, out); }
+    catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
+}
 
 }  // extern "C"

@@ -151,8 +151,13 @@ struct Trace {
 
 // ---- CPU ingest (pipeline_ingest.cpp) --------------------------------------------------------------------------------------
 int taxon_codes(const Db& db, const blu_taxon_filter& f, unsigned nthreads, TaxonCodes& tc);
+// lay: the table's column layout, checked by check_table_layout on the way in; null = the reference's columns
 int load_hits(const char* path, const Db& db, HitTable& ht, int device = -1, bool host_columns = true, const blu_hit_filter* flt = nullptr,
-              TaxonCodes* taxa = nullptr);
+              TaxonCodes* taxa = nullptr, const blu_table_layout* lay = nullptr);
+// A caller's layout before any file is opened: BLU_ERR_INVALID_ARG for a size, a count or role columns the library does not
+// take, and for an e-value threshold (flt: the active hit filter, or null) over a layout without an e-value column.  *use: the
+// layout the parsers are to read through, null when lay is null or names the reference's thirteen columns in their order.
+int check_table_layout(const blu_table_layout* lay, const blu_hit_filter* flt, const blu_table_layout** use);
 
 // One run's hit selection (include/blu_pipeline.h: blu_hit_selection) as the use-case and the
 // ingest-columns call both take it: an option with an empty mask or two empty lists is absent, the taxon lists are resolved
@@ -360,6 +365,7 @@ struct Item { const std::string* name; int64_t q; };   // one result of the docu
 struct Run {
     const blu_consensus_request& rq;
     const blu_consensus_extras* const ex;          // (NULL: none)
+    const blu_table_layout* lay;                   // (the table's column layout; NULL once start() has checked it: the reference's columns)
     const blu_pipeline_params* const params;
     Selection sel;
     blu_pipeline_stats st{};
@@ -381,8 +387,8 @@ struct Run {
     std::unique_ptr<CountTable> counts;            // (the count table, when the extras name one, and its join with the queries)
     CountJoin joined;
 
-    Run(const blu_consensus_request& request, const blu_consensus_extras* extras, blu_consensus_outcome* outcome)
-        : rq(request), ex(extras), params(request.params), sel(&request.selection, &outcome->selection) {}
+    Run(const blu_consensus_request& request, const blu_consensus_extras* extras, const blu_table_layout* layout, blu_consensus_outcome* outcome)
+        : rq(request), ex(extras), lay(layout), params(request.params), sel(&request.selection, &outcome->selection) {}
     ~Run() { if (warm_up.joinable()) warm_up.join(); if (tax) blu_taxonomy_destroy(tax); }
     // the steps of build_document, in order; each returns an error code
     int start();

@@ -256,6 +256,49 @@ class ConsensusExtras(C.Structure):
                 ("count_table_stats", C.POINTER(CountTableStats))]
 
 
+TABLE_LAYOUT_NO_COLUMN = 0xFFFFFFFF
+TABLE_LAYOUT_MAX_COLUMNS = 64
+REFERENCE_OUTFMT = "6 qseqid saccver staxid pident length mismatch gapopen qstart qend sstart send evalue bitscore"
+
+
+class TableLayoutC(C.Structure):
+    """include/blu_pipeline.h: blu_table_layout"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_columns", C.c_uint32), ("query", C.c_uint32), ("accession", C.c_uint32),
+                ("taxid", C.c_uint32), ("perc_identity", C.c_uint32), ("align_length", C.c_uint32), ("bit_score", C.c_uint32),
+                ("e_value", C.c_uint32), ("taxid_is_list", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        d = {f: int(getattr(self, f)) for f, _ in self._fields_ if f != "struct_size"}
+        d["e_value"] = None if d["e_value"] == TABLE_LAYOUT_NO_COLUMN else d["e_value"]
+        d["taxid_is_list"] = bool(d["taxid_is_list"])
+        return d
+
+    def is_reference(self) -> bool:
+        """the reference's thirteen columns in the reference's order: the call without a layout"""
+        return self.as_dict() == {"n_columns": 13, "query": 0, "accession": 1, "taxid": 2, "perc_identity": 3, "align_length": 4,
+                                  "bit_score": 12, "e_value": 11, "taxid_is_list": False}
+
+
+def table_layout(blast_outfmt: str) -> TableLayoutC:
+    """BLAST's own format string (`6 std staxids`, `qseqid sacc staxid pident length bitscore qcovs`, ...) -> the column layout
+    (include/blu_pipeline.h: blu_table_layout_parse).  A string the library refuses is a BluError whose message
+    names the offending token."""
+    L = _bind()
+    lay = TableLayoutC(struct_size=C.sizeof(TableLayoutC))
+    rc = L.blu_table_layout_parse(str(blast_outfmt).encode(), C.byref(lay))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_table_layout_parse")
+    return lay
+
+
+def _layout(blast_outfmt) -> Optional[TableLayoutC]:
+    """None, or a string that names the reference's own columns -> None (today's calls); else the C struct."""
+    if blast_outfmt is None:
+        return None
+    lay = blast_outfmt if isinstance(blast_outfmt, TableLayoutC) else table_layout(blast_outfmt)
+    return None if lay.is_reference() else lay
+
+
 class _Selection:
     """The keywords hit_filter / taxon_filter / score_band / best_hit_per_subject as the C struct, with what it points to kept
     alive, and the stats keys each of them adds."""
@@ -305,6 +348,15 @@ def _bind():
     L.blu_ingest_columns_selected.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(HitSelection),
                                               C.POINTER(IngestColumns), C.POINTER(HitSelectionStats)]
     L.blu_ingest_columns_free.argtypes = [C.POINTER(IngestColumns)]
+    if hasattr(L, "blu_table_layout_parse"):     # (an A/B library of an older build: BLU_CONSENSUS_LIB)
+        L.blu_table_layout_parse.restype = C.c_int
+        L.blu_table_layout_parse.argtypes = [C.c_char_p, C.POINTER(TableLayoutC)]
+        L.blu_build_consensus_laid_out.restype = C.c_int
+        L.blu_build_consensus_laid_out.argtypes = [C.POINTER(ConsensusRequest), C.POINTER(ConsensusExtras), C.POINTER(TableLayoutC),
+                                                   C.POINTER(ConsensusOutcome)]
+        L.blu_ingest_columns_laid_out.restype = C.c_int
+        L.blu_ingest_columns_laid_out.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(TableLayoutC), C.POINTER(HitSelection),
+                                                  C.POINTER(IngestColumns), C.POINTER(HitSelectionStats)]
     L.blu_free_text.argtypes = [C.c_void_p]
     L.blu_custom_taxon_from_file.restype = C.c_int
     L.blu_custom_taxon_from_file.argtypes = [C.c_char_p, C.POINTER(N.CutoffConfig)]
@@ -334,23 +386,31 @@ class IngestColumns(C.Structure):
 def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = False, device: int = -1,
                    hit_filter: Union[None, dict, HitFilter] = None,
                    taxon_filter: Union[None, dict, TaxonFilter] = None,
-                   score_band: Union[None, dict, ScoreBand] = None, best_hit_per_subject: bool = False) -> dict:
+                   score_band: Union[None, dict, ScoreBand] = None, best_hit_per_subject: bool = False,
+                   blast_outfmt: Optional[str] = None) -> dict:
     """The SoA columns of the ingest (include/blu_pipeline.h: blu_ingest_columns_selected) as numpy arrays + the two string
     tables.  hit_filter (a dict or HitFilter): the columns of the lines it keeps, plus `n_lines` and `n_kept`.  taxon_filter (a
     dict or TaxonFilter): the same under a taxon filter, alone or beside hit_filter, plus `taxon_filter`: its counts (n_lines,
     n_excluded, n_not_only, exclude, excluded_by).  score_band (a dict or ScoreBand): the bitscore column with the band applied
     (needs device >= 0), plus `score_band`: its counts (n_hits, n_raised, n_queries, n_widened).  best_hit_per_subject: the
     columns with only the best row of every (query, subject accession) pair, selected before the band (needs
-    device >= 0), plus `subject_best`: its counts (n_hits, n_kept, n_queries, n_thinned)."""
+    device >= 0), plus `subject_best`: its counts (n_hits, n_kept, n_queries, n_thinned).  blast_outfmt: the format string the table
+    was written with, when it is not the reference's (blu_ingest_columns_laid_out): the columns are those of the
+    table rewritten to the reference's columns."""
     import numpy as np
     L = _bind()
     c = IngestColumns()
     sel = _Selection(hit_filter, taxon_filter, score_band, best_hit_per_subject)
     st = sel.stats()
-    rc = L.blu_ingest_columns_selected(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
-                                       C.byref(sel.c), C.byref(c), C.byref(st))
+    lay = _layout(blast_outfmt)
+    if lay is None:
+        rc = L.blu_ingest_columns_selected(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
+                                           C.byref(sel.c), C.byref(c), C.byref(st))
+    else:
+        rc = L.blu_ingest_columns_laid_out(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
+                                           C.byref(lay), C.byref(sel.c), C.byref(c), C.byref(st))
     if rc != N.BLU_OK:
-        raise N.BluError(rc, "blu_ingest_columns_selected")
+        raise N.BluError(rc, "blu_ingest_columns_selected" if lay is None else "blu_ingest_columns_laid_out")
     try:
         nh, nq = int(c.n_hits), int(c.n_queries)
         arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(max(n, 1),))[:n].astype(dt, copy=True)
@@ -401,7 +461,7 @@ def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: s
                                config=None, out_path: Optional[str] = None, hit_filter: Union[None, dict, HitFilter] = None,
                                taxon_filter: Union[None, dict, TaxonFilter] = None,
                                score_band: Union[None, dict, ScoreBand] = None, best_hit_per_subject: bool = False,
-                               min_cover=None):
+                               min_cover=None, blast_outfmt: Optional[str] = None):
     """Returns (results, stats).  With out_path the document is written there by the library (no copy through Python) and
     (None, stats) is returned.  results: the parsed `results` list (json) / list of records (jsonl), sorted by
     query, or the raw text when parse=False.  config: Some(BlastBuilder) of the run-with-consensus path
@@ -417,10 +477,12 @@ def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: s
     string or Decimal above 50 and at most 100, at most three decimals; None = strict agreement): of the lines on a query's top
     bit-score, the band's included, those outside the deepest taxon that still covers that percentage of them do not take part
     (DESIGN.md §20), after everything above; stats then also has `min_cover`, its counts (n_hits, n_kept, n_queries,
-    n_narrowed, n_unresolved), and n_hits / n_unmatched_rows count the kept lines."""
+    n_narrowed, n_unresolved), and n_hits / n_unmatched_rows count the kept lines.  blast_outfmt (BLAST's own format string, e.g.
+    `6 std staxids`; None = the reference's thirteen columns): the column list the table was written with; the
+    run gives what it gives on a copy of the table rewritten to the reference's columns."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, None, "one", hit_filter=hit_filter, taxon_filter=taxon_filter,
-                  score_band=score_band, best_hit_per_subject=best_hit_per_subject, min_cover=min_cover)
+                  score_band=score_band, best_hit_per_subject=best_hit_per_subject, min_cover=min_cover, blast_outfmt=blast_outfmt)
 
 
 def build_consensus_identities_with_report(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -433,7 +495,7 @@ def build_consensus_identities_with_report(blast_output: str, taxonomies_file: s
                                            taxon_filter: Union[None, dict, TaxonFilter] = None,
                                            score_band: Union[None, dict, ScoreBand] = None,
                                            best_hit_per_subject: bool = False, min_cover=None,
-                                           count_table: Optional[str] = None):
+                                           count_table: Optional[str] = None, blast_outfmt: Optional[str] = None):
     """build_consensus_identities plus the taxon abundance report of its results, counted on the GPU and written to
     report_path after the document (include/blu_pipeline.h: blu_consensus_request.report_path).
     report_weight: "one" (results) or "size" (dereplicated reads named in the query).  count_table: a feature x sample count
@@ -441,7 +503,8 @@ def build_consensus_identities_with_report(blast_output: str, taxonomies_file: s
     `count_table`, its counts (n_rows, n_samples, n_joined, n_rows_unclassified)."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, report_path, report_weight, hit_filter=hit_filter, taxon_filter=taxon_filter,
-                  score_band=score_band, best_hit_per_subject=best_hit_per_subject, min_cover=min_cover, count_table=count_table)
+                  score_band=score_band, best_hit_per_subject=best_hit_per_subject, min_cover=min_cover, count_table=count_table,
+                  blast_outfmt=blast_outfmt)
 
 
 def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -456,7 +519,7 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
                                            taxon_filter: Union[None, dict, TaxonFilter] = None,
                                            score_band: Union[None, dict, ScoreBand] = None,
                                            best_hit_per_subject: bool = False, min_cover=None,
-                                           count_table: Optional[str] = None):
+                                           count_table: Optional[str] = None, blast_outfmt: Optional[str] = None):
     """build_consensus_identities plus the taxon abundance report (report_path), the per-sample table (sample_table_path,
     DESIGN.md §13), or both, counted on the GPU and written in the order document, report, table
     (include/blu_pipeline.h: blu_consensus_request).  report_weight serves both files.  A query whose name
@@ -470,14 +533,16 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, report_path, report_weight, sample_table_path, hit_filter=hit_filter,
                   support_table_path=support_table_path, taxon_filter=taxon_filter, score_band=score_band,
-                  best_hit_per_subject=best_hit_per_subject, min_cover=min_cover, count_table=count_table)
+                  best_hit_per_subject=best_hit_per_subject, min_cover=min_cover, count_table=count_table,
+                  blast_outfmt=blast_outfmt)
 
 
 def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device, lenient,
            parse, config, out_path, report_path, report_weight, sample_table_path=None, hit_filter=None,
            support_table_path=None, taxon_filter=None, score_band=None, best_hit_per_subject=False, min_cover=None,
-           count_table=None):
+           count_table=None, blast_outfmt=None):
     L = _bind()
+    lay = _layout(blast_outfmt)
     cover = min_cover_milli(min_cover) if min_cover is not None else 0
     sel = _Selection(hit_filter, taxon_filter, score_band, best_hit_per_subject)
     p = PipelineParams()
@@ -507,12 +572,17 @@ def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_tax
         rq.weight = REPORT_WEIGHT[report_weight]
     rq.min_cover_milli = cover
     oc = ConsensusOutcome(selection=sel.stats())
-    if count_table is None:
-        rc = L.blu_build_consensus(C.byref(rq), C.byref(oc))
-    else:
+    ex = None
+    if count_table is not None:
         # (what the request has no room for travels in the extras)
         cst = CountTableStats()
         ex = ConsensusExtras(struct_size=C.sizeof(ConsensusExtras), count_table_path=enc(count_table), count_table_stats=C.pointer(cst))
+    if lay is not None:
+        # (the sibling entry point: only under a layout that is not the reference's own)
+        rc = L.blu_build_consensus_laid_out(C.byref(rq), C.byref(ex) if ex is not None else None, C.byref(lay), C.byref(oc))
+    elif ex is None:
+        rc = L.blu_build_consensus(C.byref(rq), C.byref(oc))
+    else:
         rc = L.blu_build_consensus_with(C.byref(rq), C.byref(ex), C.byref(oc))
     if rc != N.BLU_OK:
         raise N.BluError(rc, "blu_build_consensus")

@@ -254,6 +254,41 @@ typedef struct blu_consensus_extras {
 int blu_build_consensus_with(const blu_consensus_request* request, const blu_consensus_extras* extras /* NULL = none */,
                              blu_consensus_outcome* outcome);
 
+/* The column layout of the table (not in the reference), for tables written with another `-outfmt "6 ..."` list
+ * than the reference's `6 qseqid saccver staxid pident length mismatch gapopen qstart qend sstart send evalue bitscore`.  Both
+ * parsers read the seven role fields through it; the typing rules (Int64 / f64), quote stripping, CR LF, the open last line,
+ * blank lines and the left join are those of the reference's columns and apply to whichever field holds the role.  A line with
+ * fewer than n_columns fields is BLU_ERR_PARSE naming the line and n_columns; further fields are ignored.  The run gives, byte
+ * for byte, what it gives on a copy of the table rewritten to the reference's thirteen columns (the role fields copied as their
+ * bytes, a `staxids` field cut at its first ';').  Set struct_size = sizeof(blu_table_layout); a size the library does not know
+ * is BLU_ERR_INVALID_ARG, and so are a column count outside 1 .. BLU_TABLE_LAYOUT_MAX_COLUMNS, a role column at or beyond
+ * n_columns and two roles in one column. */
+#define BLU_TABLE_LAYOUT_MAX_COLUMNS 64u
+#define BLU_TABLE_LAYOUT_NO_COLUMN 0xFFFFFFFFu
+typedef struct blu_table_layout {
+    uint32_t struct_size;
+    uint32_t n_columns;            /* fields a line must have, 1 .. BLU_TABLE_LAYOUT_MAX_COLUMNS */
+    uint32_t query;                /* 0-based column of each role: qseqid, else qacc, else qaccver */
+    uint32_t accession;            /*   saccver, else sacc, else sseqid */
+    uint32_t taxid;                /*   staxid, else staxids */
+    uint32_t perc_identity;        /*   pident */
+    uint32_t align_length;         /*   length */
+    uint32_t bit_score;            /*   bitscore */
+    uint32_t e_value;              /*   evalue, or BLU_TABLE_LAYOUT_NO_COLUMN: BLU_FILTER_MAX_E_VALUE is then BLU_ERR_INVALID_ARG */
+    uint32_t taxid_is_list;        /* 1: the taxid column is `staxids`: the digits before its first ';' are the taxid (read by the
+                                      Int64 rules: an empty prefix or `N/A` is BLU_ERR_PARSE); the bytes behind it are not read */
+} blu_table_layout;
+/* BLAST's own format string -> the layout.  Specifiers are separated by blanks; an optional leading `6` is ignored and any
+ * other leading number refused; `std` stands for `qseqid sseqid pident length mismatch gapopen qstart qend sstart send evalue
+ * bitscore`; at most BLU_TABLE_LAYOUT_MAX_COLUMNS columns after that expansion; a specifier named twice is refused; any other
+ * token of [A-Za-z0-9_]+ is a column nobody reads.  Every role but e_value must be present.  Set out->struct_size before the
+ * call.  Each refusal is BLU_ERR_INVALID_ARG with a message that names the offending token. */
+int blu_table_layout_parse(const char* spec, blu_table_layout* out);
+/* blu_build_consensus_with under a layout (NULL, or the reference's thirteen columns in the reference's order: the call without
+ * one — the same parser builds, the same bytes). */
+int blu_build_consensus_laid_out(const blu_consensus_request* request, const blu_consensus_extras* extras /* NULL = none */,
+                                 const blu_table_layout* layout /* NULL = the reference's columns */, blu_consensus_outcome* outcome);
+
 /* The reference's own three signatures, each the request above with the named fields set and the rest zero
  * (mod.rs:40-47 + write_blutils_output.rs:33-38 with config = None; the same with Some(BlastBuilder); the same to a file).
  * out_len and stats may be NULL. */
@@ -308,6 +343,10 @@ int blu_ingest_columns_on(const char* blast_output_file, const char* taxonomies_
  * (include/blu_consensus.h) are the column-level calls. */
 int blu_ingest_columns_selected(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
                                 const blu_hit_selection* selection, blu_ingest_columns* out, blu_hit_selection_stats* stats);
+/* The same under a column layout (blu_table_layout, above; NULL = the reference's columns: blu_ingest_columns_selected). */
+int blu_ingest_columns_laid_out(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                                const blu_table_layout* layout, const blu_hit_selection* selection, blu_ingest_columns* out,
+                                blu_hit_selection_stats* stats);
 void blu_ingest_columns_free(blu_ingest_columns* cols);
 
 /* Which parser the calling thread's last ingest used: 0 = CPU, 1 = GPU. */
