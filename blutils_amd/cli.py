@@ -131,6 +131,22 @@ the query (`qseqid`, else `qacc`, else `qaccver`), the subject accession (`saccv
 reference's columns, under every other flag, and both parsers read the fields in place: no rewritten copy is made.  A line with
 fewer fields than SPEC names is an error naming the line.  run-with-consensus writes its own table and has no such flag.
 
+    python -m blutils_amd.cli blastn build-consensus ... --blast-outfmt SPEC --min-query-cover P
+        [--query-cover-from auto|qcovhsp|qlen|qcovs]
+
+not in the reference CLI: query coverage, the third threshold of the reference's own blastn call (`-q`, there
+`-qcov_hsp_perc`), on a table that already exists.  P is a decimal with at most three decimals, 0 .. 100, read exactly.  A line
+takes part only if its coverage is at least P, taken from the columns SPEC names: `qcovhsp` (BLAST's per-HSP integer percent c:
+kept when c >= P), else `qstart qend qlen` (kept when (|qend - qstart| + 1) * 100 >= P * qlen, in integers: the exact ratio, not
+BLAST's rounded percent, so 79.6 % is below 80 where `qcovhsp` prints 80), else `qcovs` (per subject over all HSPs of the pair:
+the coarser figure); --query-cover-from names one of the three instead.  A source whose columns SPEC lacks is an error naming
+them, and without --blast-outfmt the flag is refused: the reference's thirteen columns hold no query length.  The coverage
+fields are read only under the flag, as integers 0 .. 2^31 - 1 (qlen above 0); one that is not is an error naming the line,
+kept or not.  The GPU parser decides it with the other filters — after the taxon verdict, before the e-value — and the run gives
+what it gives on a copy of the table without the failing lines.  `--min-query-cover 0` keeps every line.  To stderr, before the
+hit filter's line: `query cover: B of N lines under P percent (from SOURCE)`.  run-with-consensus has `-q` for blastn itself
+and no such flag.
+
     python -m blutils_amd.cli cache-db TAX.json CACHE [-u]
 
 writes the binary cache of a taxonomies file (not in the reference CLI; pass CACHE as -t afterwards).  
@@ -174,10 +190,18 @@ import sys
 from . import _native, blast, pipeline, report, seqdb, tabular, taxdb
 
 
+class _BlastnParser(argparse.ArgumentParser):
+    """argparse's prefix matching for every flag but the query-cover pair, which is taken only when spelled out: `--min-query-cov`
+    stays the unknown flag it was (run-with-consensus calls blastn's own threshold `--query-cov`)."""
+
+    def _get_option_tuples(self, option_string):
+        return [t for t in super()._get_option_tuples(option_string) if t[0].dest not in ("min_query_cover", "query_cover_from")]
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="blu", description="MI355X-native consensus step of blutils")
     sub = ap.add_subparsers(dest="cmd", required=True)
-    blastn = sub.add_parser("blastn").add_subparsers(dest="sub", required=True)
+    blastn = sub.add_parser("blastn").add_subparsers(dest="sub", required=True, parser_class=_BlastnParser)
     bc = blastn.add_parser("build-consensus", help="consensus identities from a BLAST outfmt-6 table")
     bc.add_argument("blast_out")
     bc.add_argument("-t", "--tax-file", required=True)
@@ -192,6 +216,15 @@ def build_parser() -> argparse.ArgumentParser:
                     help="the -outfmt string BLAST_OUT was written with, when it is not the reference's `6 qseqid saccver staxid pident "
                          "length mismatch gapopen qstart qend sstart send evalue bitscore`: e.g. \"6 std staxids\"; the columns are "
                          "found by name, in any order (not in the reference CLI)")
+    qcv = bc.add_argument_group("query coverage (not in the reference CLI)",
+                                "a line of the table takes part only if its query coverage is at least P; needs --blast-outfmt, "
+                                "which names the columns; applied by the parser, on the GPU where it parses")
+    qcv.add_argument("--min-query-cover", type=_min_query_cover, metavar="P",
+                     help="keep lines whose query coverage is at least P percent; a decimal with at most three decimals, 0 .. 100 "
+                          "(not in the reference CLI)")
+    qcv.add_argument("--query-cover-from", default="auto", choices=["auto", "qcovhsp", "qlen", "qcovs"],
+                     help="where the coverage comes from: the `qcovhsp` column, the exact ratio of `qstart qend qlen`, the `qcovs` "
+                          "column, or (auto) the first of these that --blast-outfmt names")
     rw = blastn.add_parser("run-with-consensus", help="blastn fan-out (chunks of 50 queries) + consensus")
     rw.add_argument("query", nargs="?", default="-")
     rw.add_argument("-d", "--database", required=True)
@@ -378,6 +411,16 @@ def _min_cover(text: str):
     return decimal.Decimal(text.strip())
 
 
+def _min_query_cover(text: str):
+    """--min-query-cover: a decimal with at most three decimals in 0 .. 100, kept exact (decimal.Decimal)"""
+    import decimal
+    try:
+        pipeline.min_query_cover_milli(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return decimal.Decimal(text.strip())
+
+
 def _top_bits(text: str) -> int:
     """--top-bits: an integer in 0 .. 2^32 - 1"""
     try:
@@ -427,7 +470,10 @@ def _say_kept(stats, hit_filter=True) -> None:
         for el, count in zip(t["exclude"], t["excluded_by"]):
             if count:
                 print(f"  {el}: {count}", file=sys.stderr)
-    if hit_filter and stats and "n_kept" in stats:
+    q = stats.get("query_cover") if stats else None
+    if q:
+        print(f"query cover: {q['n_below']} of {q['n_lines']} lines under {q['percent']} percent (from {q['source']})", file=sys.stderr)
+    if (hit_filter or q) and stats and "n_kept" in stats:
         print(f"hit filter: kept {stats['n_kept']} of {stats['n_lines']} lines", file=sys.stderr)
     s = stats.get("subject_best") if stats else None
     if s:
@@ -589,6 +635,18 @@ def main(argv=None) -> int:
         if layout.e_value == pipeline.TABLE_LAYOUT_NO_COLUMN and args.max_e_value is not None:
             raise SystemExit("--blast-outfmt: --max-e-value needs an `evalue` column and SPEC names none")
         extra["blast_outfmt"] = layout
+    if args.min_query_cover is not None:
+        if args.blast_outfmt is None:
+            raise SystemExit("--min-query-cover needs --blast-outfmt: the reference's thirteen columns hold no query length, so the "
+                             "table's columns have to be named (e.g. --blast-outfmt \"6 std staxids qlen\")")
+        try:
+            pipeline.query_cover_columns(args.blast_outfmt, args.query_cover_from)
+        except _native.BluError:
+            raise SystemExit(f"--min-query-cover: {_native.last_error()}")
+        extra["blast_outfmt"] = args.blast_outfmt
+        extra["query_cover"] = pipeline.QueryCover(args.min_query_cover, args.query_cover_from)
+    elif args.query_cover_from != "auto":
+        raise SystemExit("--query-cover-from needs --min-query-cover")
     if args.support_table is not None:
         build = functools.partial(pipeline.build_consensus_identities_with_tables, report_path=args.report,
                                   sample_table_path=args.sample_table, report_weight=args.report_weight,

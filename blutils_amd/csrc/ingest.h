@@ -95,7 +95,8 @@ struct HitTable {
     uint64_t unmatched = 0;
     uint64_t n_hits = 0;                         // rows of the table (the host columns may be absent, see below)
     uint64_t n_queries = 0;                      // = query_names.size() once the strings are there (wait_strings())
-    uint64_t n_lines = 0, n_kept = 0;            // under a hit or taxon filter: non-empty lines read, lines kept
+    uint64_t n_lines = 0, n_kept = 0;            // under a hit or taxon filter or a query cover: non-empty lines read, lines kept
+    uint64_t n_below = 0;                        // under a query cover: lines below it, whatever else says about them
     bool host_columns = true;                    // false: the GPU ingest was asked to leave the columns on the device only
     std::unique_ptr<DeviceHits> dev;             // set by the GPU ingest
     // The GPU ingest returns as soon as the device columns are complete; query_names and accessions are still being
@@ -108,7 +109,7 @@ struct HitTable {
         wait_strings();
         query_names.clear(); accessions.clear();
         seg_off = {}; bitscore = {}; align_len = {}; tax_desc_row = {}; acc_rank = {}; pident = {};
-        unmatched = n_hits = n_queries = n_lines = n_kept = 0; host_columns = true; strings_ok = true;
+        unmatched = n_hits = n_queries = n_lines = n_kept = n_below = 0; host_columns = true; strings_ok = true;
         dev.reset();
     }
     HitTable() = default;
@@ -155,8 +156,11 @@ struct TaxonCodes {
 // lay: a checked column layout that is not the reference's own, or null: the parse then runs the layout builds
 // of its kernels, which read the role fields where the layout puts them; a file they decline goes to the CPU parser with the
 // same layout.
+// cov: a checked query cover, or null (needs lay): the parse runs the cover builds of the layout kernels, which fold
+// the line's coverage into its keep word; ht.n_below is set beside ht.n_lines / ht.n_kept.
 int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, std::string* why,
-                  const blu_hit_filter* flt = nullptr, TaxonCodes* taxa = nullptr, const blu_table_layout* lay = nullptr);
+                  const blu_hit_filter* flt = nullptr, TaxonCodes* taxa = nullptr, const blu_table_layout* lay = nullptr,
+                  const blu_query_cover* cov = nullptr);
 // an f64 field as the host parser types it (pipeline_ingest.cpp: parse_f64 — strtod's value); false: not a number.  The GPU ingest
 // decides with it the e-values its own arithmetic leaves open.
 bool parse_f64_field(const char* p, size_t n, double* out);

@@ -434,13 +434,48 @@ struct DevLayout {               // 48 bytes
     unsigned long long wanted;   // bit t: tab t — the one behind column t — bounds a role field (column t or t + 1 holds a role)
 };
 
+// ---- 2a'. the query cover: a fifth threshold of the keep word, on fields the seven roles do not include — one
+// column (`qcovhsp` or `qcovs`: BLAST's integer percent) or three (`qstart`, `qend`, `qlen`: the exact ratio).  The cover builds
+// of the layout kernels (PARSE_QCOV, PARSE_QCOV_TAXA) take the layout with the cover behind it, DevLayoutCover; the six builds
+// above take DevLayout and compile to what they were.  `wanted` also names the tab in front of every cover field.
+enum : int { PARSE_QCOV = 3, PARSE_QCOV_TAXA = 4 };
+enum : int { COVER_FIELDS = 3 };
+struct DevCover {
+    uint32_t by_len;             // 0: col[0] holds the percent c, kept iff c * 1000 >= p_milli; 1: col = {qstart, qend, qlen},
+    uint32_t n_fields;           //    kept iff (|qend - qstart| + 1) * 100000 >= p_milli * qlen.  n_fields: 1 or 3
+    uint32_t col[COVER_FIELDS];  // (unused: 0xFFFFFFFF, which no tab count reaches)
+    uint32_t reserved;
+    double p_milli;              // the threshold times 1000: an integer 0 .. 100000
+    unsigned long long* below;   // [HIT_SPREAD] lines below the cover, whatever the other filters say (spread over blocks)
+};
+struct DevLayoutCover : DevLayout { DevCover cov; };
+
+// One cover field, already read: an Int64 field (no fraction, no exponent — else FB_NUMBER and the host parser's error) in
+// 0 .. 2^31 - 1 (else FB_RANGE, likewise).  NumState::value has the integer exactly: at most 15 digits.
+__device__ __forceinline__ uint32_t cover_field(const NumState& num, double* v) {
+    if (!num.value(v) || num.seen_dot || num.seen_exp) return FB_NUMBER;
+    return *v >= 0.0 && *v <= 2147483647.0 ? 0u : FB_RANGE;
+}
+// The line's verdict on its three values (v[1], v[2] unused for a percent column) and the count.  Every operand is an integer
+// below 2^31 and every product below 2^48: the doubles compare as the host's 64-bit integers do.  Every lane that validated
+// its line calls it, before the taxon verdict: the count does not depend on the other filters.  false: qlen = 0 (FB_RANGE).
+__device__ __forceinline__ bool cover_verdict(const DevCover& c, const double v[COVER_FIELDS], bool* below) {
+    if (c.by_len) {
+        if (v[2] == 0.0) return false;
+        *below = !((fabs(v[1] - v[0]) + 1.0) * 100000.0 >= c.p_milli * v[2]);
+    } else *below = !(v[0] * 1000.0 >= c.p_milli);
+    spread_add_ballot(c.below, 0, *below);
+    return true;
+}
+
 // The general form under a layout: parse_row_general_body with the column tests against the layout, the line walked up to the
 // end of column n_cols - 1, and a `staxids` field fed to the number reader up to its first ';' only.
-template <int MODE>
+template <int MODE, class LAY>
 __device__ __noinline__ void parse_row_general_layout(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
                                                       const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
-                                                      unsigned long long* __restrict__ n_unmatched, const DevFilter* flt, const DevLayout L) {
+                                                      unsigned long long* __restrict__ n_unmatched, const DevFilter* flt, const LAY L) {
     constexpr bool FILTER = MODE != PARSE_PLAIN;
+    constexpr bool TAXA = MODE == PARSE_TAXA || MODE == PARSE_QCOV_TAXA, COVER = MODE == PARSE_QCOV || MODE == PARSE_QCOV_TAXA;
     const uint64_t p = line_start[i];
     uint64_t e = line_start[i + 1] - 1;                 // the newline (or one past the end of a last line without one)
     if (e > p && text[e - 1] == '\r') --e;
@@ -460,6 +495,14 @@ __device__ __noinline__ void parse_row_general_layout(const unsigned char* __res
     unsigned long long e_mant = 0;
     int e_exp = 0;
     bool e_neg = false;
+    double v_cov[COVER_FIELDS] = {0, 0, 0};
+    auto cover_col = [&](uint32_t c) {                  // which cover field column c holds, or -1
+        if constexpr (COVER) {
+#pragma unroll
+            for (int k = 0; k < COVER_FIELDS; ++k) if (c == L.cov.col[k]) return k;
+        }
+        return -1;
+    };
     auto end_field = [&](uint64_t fend) {
         const uint64_t len = fend - fstart;
         if (col == c_q) { o.qh[i] = hash_finish(h, (uint32_t)len); o.qpos[i] = fstart | (len << 44); if (len >= (1u << 20)) fb |= FB_COLUMNS; }
@@ -469,6 +512,10 @@ __device__ __noinline__ void parse_row_general_layout(const unsigned char* __res
         else if (col == c_aln) { if (!num.value(&v_aln) || num.seen_dot || num.seen_exp) fb |= FB_NUMBER; }
         else if (col == c_bs) { if (!num.value(&v_bs)) fb |= FB_NUMBER; }
         else if (FILTER && col == c_e) { if (!num.plain()) fb |= FB_NUMBER; e_mant = num.mant; e_exp = num.exponent(); e_neg = num.neg; }
+        else if (COVER) {
+            const int k = cover_col(col);
+            if (k >= 0) { double v = 0; fb |= cover_field(num, &v); v_cov[0] = k == 0 ? v : v_cov[0]; v_cov[1] = k == 1 ? v : v_cov[1]; v_cov[2] = k == 2 ? v : v_cov[2]; }
+        }
         ++col;
         fstart = fend + 1;
         h = 1469598103934665603ull;
@@ -487,7 +534,7 @@ __device__ __noinline__ void parse_row_general_layout(const unsigned char* __res
             if (c == '\t') { end_field(q); continue; }
             if (col == c_q || col == c_a) { h = hash_step(h, c); if (c == '"') fb |= FB_QUOTE; }
             else if (col == c_tax) { if (L.tax_list && c == ';') cut = true; if (!cut) num.feed(c, q == fstart); }
-            else if (col == c_pid || col == c_aln || col == c_bs || (FILTER && col == c_e)) num.feed(c, q == fstart);
+            else if (col == c_pid || col == c_aln || col == c_bs || (FILTER && col == c_e) || (COVER && cover_col(col) >= 0)) num.feed(c, q == fstart);
         }
     }
     if (col < n_cols) end_field(e);                     // the last field ends with the line
@@ -496,9 +543,14 @@ __device__ __noinline__ void parse_row_general_layout(const unsigned char* __res
     const double bs_t = trunc(v_bs);
     if (!(bs_t >= -2147483648.0 && bs_t <= 2147483647.0) || !(v_aln >= -2147483648.0 && v_aln <= 2147483647.0) ||
         !(v_tax >= -9.2e18 && v_tax <= 9.2e18)) { atomicOr(flags, FB_RANGE); return; }
+    bool below = false;                                 // (the cover's verdict and count: ahead of the taxon verdict's early-out)
+    if constexpr (COVER) if (!cover_verdict(L.cov, v_cov, &below)) { atomicOr(flags, FB_RANGE); return; }
     const uint32_t row = taxid_lookup(taxmap, (long long)v_tax);   // left join (mod.rs:72-76)
-    if constexpr (MODE == PARSE_TAXA) {
-        if (taxon_verdict(reinterpret_cast<const DevFilterTaxa*>(flt)->t, row)) flt->keep[i] = KEEP_NO;
+    if constexpr (TAXA) {
+        if (taxon_verdict(reinterpret_cast<const DevFilterTaxa*>(flt)->t, row) || below) flt->keep[i] = KEEP_NO;
+        else filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
+    } else if constexpr (COVER) {
+        if (below) flt->keep[i] = KEEP_NO;              // (its e-value is never looked at)
         else filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
     } else if constexpr (FILTER) filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
     else if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull);
@@ -510,11 +562,15 @@ __device__ __noinline__ void parse_row_general_layout(const unsigned char* __res
 // the role fields, begin and end per role and thread: 2 x 7 x 256 x 2 = 7 KB beside the 32 KB stage whatever the column count
 // (one word per column would be 64 x 256 x 2 = 32 KB more); (2) the same walk over the role fields, one role at a time.
 // A thread reads back only what it wrote itself: no barrier between (1) and (2).
-template <int MODE>
+// The cover builds keep of a cover field only its begin, and in a register, not in LDS: the three 16-bit
+// positions share one 64-bit word, set at the tab `wanted` names in front of the field; the field ends at the next tab or with
+// the line, which the short walk over its digits finds for itself.  LDS stays at the 39 936 B of the other layout builds.
+template <int MODE, class LAY>
 __device__ __forceinline__ void parse_rows_layout_body(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t n_rows,
                                                        const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
-                                                       unsigned long long* __restrict__ n_unmatched, const DevFilter* flt, const DevLayout& L) {
+                                                       unsigned long long* __restrict__ n_unmatched, const DevFilter* flt, const LAY& L) {
     constexpr bool FILTER = MODE != PARSE_PLAIN;
+    constexpr bool TAXA = MODE == PARSE_TAXA || MODE == PARSE_QCOV_TAXA, COVER = MODE == PARSE_QCOV || MODE == PARSE_QCOV_TAXA;
     __shared__ uint4 stage16[STAGE_BYTES / 16];
     __shared__ uint16_t field_at[2 * N_ROLES * PARSE_THREADS];       // [role][begin, end][thread]
     const uint32_t r0 = blockIdx.x * PARSE_THREADS, r1 = min(r0 + (uint32_t)PARSE_THREADS, n_rows), i = r0 + threadIdx.x;
@@ -552,6 +608,11 @@ __device__ __forceinline__ void parse_rows_layout_body(const unsigned char* __re
     const uint32_t n_cols = L.n_cols;
 #pragma unroll
     for (int r = 0; r < N_ROLES; ++r) if (L.col[r] == 0) set_begin(r, p);
+    unsigned long long cov_at = 0;                                   // begin of cover field k: bits 16 k .. 16 k + 15
+    if constexpr (COVER) {
+#pragma unroll
+        for (int k = 0; k < COVER_FIELDS; ++k) if (L.cov.col[k] == 0) cov_at |= (unsigned long long)p << (16 * k);
+    }
     uint32_t n_tabs = 0;
     for (uint32_t a = p & ~3u; a < e && n_tabs < n_cols; a += 4) {
         const uint32_t x = sw[a >> 2] ^ 0x09090909u;
@@ -565,6 +626,10 @@ __device__ __forceinline__ void parse_rows_layout_body(const unsigned char* __re
                 for (int r = 0; r < N_ROLES; ++r) {
                     if (L.col[r] == n_tabs) set_end(r, at);
                     if (L.col[r] == n_tabs + 1) set_begin(r, at + 1);
+                }
+                if constexpr (COVER) {
+#pragma unroll
+                    for (int k = 0; k < COVER_FIELDS; ++k) if (L.cov.col[k] == n_tabs + 1) cov_at |= (unsigned long long)(at + 1) << (16 * k);
                 }
             }
             ++n_tabs;
@@ -611,13 +676,30 @@ __device__ __forceinline__ void parse_rows_layout_body(const unsigned char* __re
             e_mant = num.mant; e_exp = num.exponent(); e_neg = num.neg;
         }
     }
+    double v_cov[COVER_FIELDS] = {0, 0, 0};
+    if constexpr (COVER) {                                           // the cover fields: from their begin to the next tab or the line's end
+#pragma unroll
+        for (int k = 0; k < COVER_FIELDS; ++k) {
+            if (k >= (int)L.cov.n_fields) continue;
+            NumState num;
+            num.reset();
+            const uint32_t s = (uint32_t)(cov_at >> (16 * k)) & 0xFFFFu;
+            for (uint32_t q = s; q < e; ++q) { const uint32_t c = sb[q]; if (c == '\t') break; num.feed(c, q == s); }
+            fb |= cover_field(num, &v_cov[k]);
+        }
+    }
     if (fb) { atomicOr(flags, fb); return; }
     const double bs_t = trunc(v_bs);                                // mod.rs:184 AnyValue::Float64 -> try_extract::<i64> (truncation)
     if (!(bs_t >= -2147483648.0 && bs_t <= 2147483647.0) || !(v_aln >= -2147483648.0 && v_aln <= 2147483647.0) ||
         !(v_tax >= -9.2e18 && v_tax <= 9.2e18)) { atomicOr(flags, FB_RANGE); return; }
+    bool below = false;                                             // (the cover's verdict and count: ahead of the taxon verdict's early-out)
+    if constexpr (COVER) if (!cover_verdict(L.cov, v_cov, &below)) { atomicOr(flags, FB_RANGE); return; }
     const uint32_t row = taxid_lookup(taxmap, (long long)v_tax);   // left join (mod.rs:72-76)
-    if constexpr (MODE == PARSE_TAXA) {
-        if (taxon_verdict(reinterpret_cast<const DevFilterTaxa*>(flt)->t, row)) flt->keep[i] = KEEP_NO;
+    if constexpr (TAXA) {
+        if (taxon_verdict(reinterpret_cast<const DevFilterTaxa*>(flt)->t, row) || below) flt->keep[i] = KEEP_NO;
+        else filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
+    } else if constexpr (COVER) {
+        if (below) flt->keep[i] = KEEP_NO;                          // (its e-value is never looked at)
         else filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
     } else if constexpr (FILTER) filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
     else if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull);
@@ -640,6 +722,18 @@ __global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout_taxa(const
                                                                         uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
                                                                         const DevFilterTaxa* __restrict__ flt, DevLayout lay) {
     parse_rows_layout_body<PARSE_TAXA>(text, line_start, n_rows, taxmap, o, flags, nullptr, &flt->f, lay);
+}
+
+// the cover builds: the thresholds of the filter may all be off (a cover alone), as under a taxon filter alone
+__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout_qcov(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
+                                                                        uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
+                                                                        const DevFilter* __restrict__ flt, DevLayoutCover lay) {
+    parse_rows_layout_body<PARSE_QCOV>(text, line_start, n_rows, taxmap, o, flags, nullptr, flt, lay);
+}
+__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout_qcov_taxa(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
+                                                                             uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
+                                                                             const DevFilterTaxa* __restrict__ flt, DevLayoutCover lay) {
+    parse_rows_layout_body<PARSE_QCOV_TAXA>(text, line_start, n_rows, taxmap, o, flags, nullptr, &flt->f, lay);
 }
 
 // ---- 2b. hit filter: the e-values left to the host, and the stable compaction of the parsed rows ---------------------------
@@ -956,6 +1050,7 @@ struct GpuIngest {
     const blu_hit_filter* const flt;   // (null: none)
     TaxonCodes* const taxa;            // (null: none)
     const blu_table_layout* const lay; // (null: the reference's columns; else checked, and not the reference's own: DESIGN.md §23)
+    const blu_query_cover* const cov;  // (null: none; else checked against lay, which is then not null: DESIGN.md §24)
 
     unsigned char* d_text = nullptr;   // the padded text: upload_and_index -> accession_dictionary_finish, which frees it
     uint64_t* d_line = nullptr;        // line starts: upload_and_index -> parse, drop_filtered_rows (which frees them)
@@ -1017,7 +1112,8 @@ struct GpuIngest {
         return fall_back_on(h_flags);
     }
     int zero_counter() { HIP_CHECK(pol, hipMemset(d_counter, 0, 4)); return BLU_OK; }
-    size_t n_back() const { return 8 + HIT_SPREAD + 1 + (taxa ? HIT_SPREAD + (size_t)taxa->n_exclude : 0); }
+    size_t n_taxa_back() const { return taxa ? HIT_SPREAD + (size_t)taxa->n_exclude : 0; }
+    size_t n_back() const { return 8 + HIT_SPREAD + 1 + n_taxa_back() + (cov ? HIT_SPREAD : 0); }   // (the cover's count comes last)
     hipError_t need_tmp(size_t bytes) {
         if (bytes <= tmp_bytes) return hipSuccess;
         if (d_tmp) mem.free(d_tmp);
@@ -1071,7 +1167,7 @@ struct GpuIngest {
         HIP_CHECK(pol, mem.alloc(&d_tile_base, (n_tiles + 1) * 4, "line index"));
         // under a hit filter the kept / undecided counts follow the big counters, and under a taxon filter the not-only counts
         // and one count per exclude element after them: all of it comes back in one copy
-        const size_t flag_bytes = flt || taxa ? n_back() * 8 : 64;
+        const size_t flag_bytes = flt || taxa || cov ? n_back() * 8 : 64;
         HIP_CHECK(pol, mem.alloc(&d_flags, flag_bytes, "flags"));
         HIP_CHECK(pol, hipMemset(d_flags, 0, flag_bytes));
         d_counter = d_flags + 4;
@@ -1102,6 +1198,22 @@ struct GpuIngest {
         }
         return d;
     }
+    // the layout with the cover behind it: the cover's columns, the threshold, where its count goes; the tab in front of each
+    // cover field joins `wanted`
+    DevLayoutCover device_layout_cover(unsigned long long* d_below) const {
+        DevLayoutCover d{};
+        static_cast<DevLayout&>(d) = device_layout();
+        const bool by_len = cov->source == BLU_QUERY_COVER_QLEN;
+        d.cov.by_len = by_len ? 1u : 0u;
+        d.cov.n_fields = by_len ? 3u : 1u;
+        d.cov.col[0] = by_len ? cov->qstart : cov->cover_column;
+        d.cov.col[1] = by_len ? cov->qend : 0xFFFFFFFFu;
+        d.cov.col[2] = by_len ? cov->qlen : 0xFFFFFFFFu;
+        d.cov.p_milli = (double)cov->min_cover_milli;
+        d.cov.below = d_below;
+        for (uint32_t k = 0; k < d.cov.n_fields; ++k) if (d.cov.col[k] > 0) d.wanted |= 1ull << (d.cov.col[k] - 1);
+        return d;
+    }
 
     // ---- parse: one of the three builds of parse_rows, or under a column layout of parse_rows_layout.  Under a
     // filter it leaves a keep word per line, and its counts come back with the flags in `back`
@@ -1117,7 +1229,8 @@ struct GpuIngest {
         const dim3 blocks(grid(n_rows, PARSE_THREADS)), threads(PARSE_THREADS);
         if (lay && flt && (flt->mask & BLU_FILTER_MAX_E_VALUE) && lay->e_value >= lay->n_columns) return fallback("an e-value threshold without an e-value column");
         const DevLayout dl = lay ? device_layout() : DevLayout{};
-        if (!flt && !taxa) {
+        if (cov && !lay) return fallback("a query cover without a column layout");
+        if (!flt && !taxa && !cov) {
             if (lay) hipLaunchKernelGGL(parse_rows_layout, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, d_big, dl);
             else hipLaunchKernelGGL(parse_rows, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, d_big);
             return check_flags();
@@ -1128,9 +1241,12 @@ struct GpuIngest {
         DevFilterTaxa hf{};
         if (flt) hf.f = device_filter(*flt);                         // (no threshold beside a taxon filter: an empty mask keeps every line)
         hf.f.keep = d_keep; hf.f.counts = d_fcnt;
+        // under a cover: the cover builds of the layout kernels, whose layout argument carries it
+        const DevLayoutCover dlc = cov ? device_layout_cover(d_fcnt + HIT_SPREAD + 1 + n_taxa_back()) : DevLayoutCover{};
         if (!taxa) {
             HIP_CHECK(pol, hipMemcpy(d_filter, &hf.f, sizeof hf.f, hipMemcpyHostToDevice));
-            if (lay) hipLaunchKernelGGL(parse_rows_layout_filtered, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilter*)&d_filter->f, dl);
+            if (cov) hipLaunchKernelGGL(parse_rows_layout_qcov, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilter*)&d_filter->f, dlc);
+            else if (lay) hipLaunchKernelGGL(parse_rows_layout_filtered, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilter*)&d_filter->f, dl);
             else hipLaunchKernelGGL(parse_rows_filtered, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilter*)&d_filter->f);
         } else {
             // the row codes go up next to the taxid map; the verdict is taken in the parse
@@ -1139,7 +1255,8 @@ struct GpuIngest {
             hf.t.code = d_code; hf.t.n_tax = (uint32_t)n_tax; hf.t.unmatched = taxa->unmatched;
             hf.t.not_only = d_fcnt + HIT_SPREAD + 1; hf.t.excluded_by = hf.t.not_only + HIT_SPREAD;
             HIP_CHECK(pol, hipMemcpy(d_filter, &hf, sizeof hf, hipMemcpyHostToDevice));
-            if (lay) hipLaunchKernelGGL(parse_rows_layout_taxa, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilterTaxa*)d_filter, dl);
+            if (cov) hipLaunchKernelGGL(parse_rows_layout_qcov_taxa, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilterTaxa*)d_filter, dlc);
+            else if (lay) hipLaunchKernelGGL(parse_rows_layout_taxa, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilterTaxa*)d_filter, dl);
             else hipLaunchKernelGGL(parse_rows_taxa, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilterTaxa*)d_filter);
         }
         back.resize(n_back());
@@ -1150,7 +1267,7 @@ struct GpuIngest {
     // ---- after a filtered parse: the e-values the device left open are decided, the rows are compacted in file order before
     // anything else sees them, the unmatched rows are counted over what is left
     int drop_filtered_rows() {
-        if (!flt && !taxa) return BLU_OK;
+        if (!flt && !taxa && !cov) return BLU_OK;
         uint64_t n_kept = spread_sum(back.data() + 8, 0);
         const uint64_t n_ask = back[8 + HIT_SPREAD];
         const unsigned long long* const tb = back.data() + 8 + HIT_SPREAD + 1;   // (under a taxon filter: not-only, then per element)
@@ -1160,6 +1277,8 @@ struct GpuIngest {
             for (uint32_t k = 0; k < taxa->n_exclude; ++k) n_excluded += tb[HIT_SPREAD + k];
             if (n_excluded + n_not_only + n_kept + n_ask > n_rows) return fallback("inconsistent taxon-filter counts");
         }
+        const uint64_t n_below = cov ? spread_sum(tb + n_taxa_back(), 0) : 0;
+        if (n_below > n_rows) return fallback("inconsistent query-cover counts");
         lap("parse (filtered)");
         if (n_ask) STEP(decide_e_values_on_host((uint32_t)n_ask, &n_kept));
         if (n_kept > n_rows) return fallback("inconsistent hit-filter counts");
@@ -1170,7 +1289,7 @@ struct GpuIngest {
         if (d_code) mem.free(d_code);
         mem.free(d_line); d_line = nullptr;
         hipLaunchKernelGGL(count_unmatched, grid(n_rows, 1024), dim3(1024), 0, 0, (const uint32_t*)d_tax, n_rows, d_big);
-        ht.n_lines = n_lines; ht.n_kept = n_kept;
+        ht.n_lines = n_lines; ht.n_kept = n_kept; ht.n_below = n_below;
         if (taxa) {
             taxa->n_excluded = n_excluded; taxa->n_not_only = n_not_only;
             taxa->excluded_by.assign(tb + HIT_SPREAD, tb + HIT_SPREAD + taxa->n_exclude);
@@ -1446,7 +1565,7 @@ struct GpuIngest {
 }  // namespace
 
 int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool host_columns, HitTable& ht, std::string* why,
-                  const blu_hit_filter* flt, TaxonCodes* taxa, const blu_table_layout* lay) {
+                  const blu_hit_filter* flt, TaxonCodes* taxa, const blu_table_layout* lay, const blu_query_cover* cov) {
     if (flt && !(flt->mask & 15u)) flt = nullptr;
     IngestTrace lap;
     std::string why_unread;
@@ -1467,7 +1586,7 @@ int load_hits_gpu(int fd, size_t size, const TaxidMap& row_of, int device, bool 
     }
     // (in a block of its own: the sort thread is joined and the host strings are let go before the arena's buffers are)
     int rc;
-    { GpuIngest ingest{fd, size, row_of, device, host_columns, ht, mem, mem.pol, lap, flt, taxa, lay}; rc = ingest.run(); }
+    { GpuIngest ingest{fd, size, row_of, device, host_columns, ht, mem, mem.pol, lap, flt, taxa, lay, cov}; rc = ingest.run(); }
     if (rc != BLU_OK) ht.clear();
     lap("hand-over");
     // with room on the card (mem.keep) the work buffers — the text, the hashes, the dictionaries: 10 GB for a 2 M-query table —

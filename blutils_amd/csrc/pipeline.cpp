@@ -287,7 +287,9 @@ int Run::start() {
     if (!rq.blast_output_file || !rq.taxonomies_file || !params) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     sel.cover_milli = rq.min_cover_milli;
     if (int rc = sel.check()) return rc;
-    if (int rc = check_table_layout(lay, sel.flt, &lay)) return rc;
+    if (int rc = check_query_cover(cov, lay)) return rc;
+    if (int rc = check_table_layout(lay, sel.flt, &lay, cov != nullptr)) return rc;
+    sel.cov = cov;
     if ((rq.report_path || rq.sample_table_path) && rq.weight != BLU_REPORT_WEIGHT_ONE && rq.weight != BLU_REPORT_WEIGHT_SIZE) {
         set_error("report: a path and weight BLU_REPORT_WEIGHT_ONE or BLU_REPORT_WEIGHT_SIZE are needed");
         return BLU_ERR_INVALID_ARG;
@@ -327,7 +329,7 @@ int Run::taxonomy_beside_ingest() {
     std::thread tax_thread([&]() { const double ts = now_s(); create(); t_tax = now_s() - ts; });
     struct Join { std::thread& t; ~Join() { if (t.joinable()) t.join(); } } join_tax{tax_thread};
     t0 = now_s();
-    if (int rc = load_hits(rq.blast_output_file, *db, *ht, params->device, /*host_columns=*/false, sel.flt, sel.taxa.get(), lay)) return rc;   // mod.rs:54, 72-82
+    if (int rc = load_hits(rq.blast_output_file, *db, *ht, params->device, /*host_columns=*/false, sel.flt, sel.taxa.get(), lay, cov)) return rc;   // mod.rs:54, 72-82
     sel.loaded(*ht);
     st.t_load_hits_s = now_s() - t0;
     tr.lap("load hits");
@@ -540,9 +542,9 @@ void Run::bury() {
 
 namespace {
 
-int build_document(const blu_consensus_request& rq, const blu_consensus_extras* ex, const blu_table_layout* lay, Document* document,
-                   blu_consensus_outcome* outcome) {
-    Run r(rq, ex, lay, outcome);
+int build_document(const blu_consensus_request& rq, const blu_consensus_extras* ex, const blu_table_layout* lay, const blu_query_cover* cov,
+                   Document* document, blu_consensus_outcome* outcome) {
+    Run r(rq, ex, lay, cov, outcome);
     if (int rc = r.start()) return rc;
     if (int rc = r.taxonomy_beside_ingest()) return rc;
     if (int rc = r.select_on_device()) return rc;
@@ -566,9 +568,10 @@ int put_tables(const Document& d, const blu_consensus_request& rq) {
 }
 
 // rq.out_path == NULL: the pieces joined into one malloc'd text
-int consensus_to_text(const blu_consensus_request& rq, const blu_consensus_extras* ex, const blu_table_layout* lay, blu_consensus_outcome* outcome) {
+int consensus_to_text(const blu_consensus_request& rq, const blu_consensus_extras* ex, const blu_table_layout* lay, const blu_query_cover* cov,
+                      blu_consensus_outcome* outcome) {
     Document d;
-    int rc = build_document(rq, ex, lay, &d, outcome);
+    int rc = build_document(rq, ex, lay, cov, &d, outcome);
     if (rc != BLU_OK) return rc;
     if ((rc = put_tables(d, rq)) != BLU_OK) return rc;
     const std::vector<size_t> at = d.offsets();
@@ -584,10 +587,11 @@ int consensus_to_text(const blu_consensus_request& rq, const blu_consensus_extra
 }
 
 // (the report and table files, when asked for, are written once the document is out)
-int consensus_to_file(const blu_consensus_request& rq, const blu_consensus_extras* ex, const blu_table_layout* lay, blu_consensus_outcome* outcome) {
+int consensus_to_file(const blu_consensus_request& rq, const blu_consensus_extras* ex, const blu_table_layout* lay, const blu_query_cover* cov,
+                      blu_consensus_outcome* outcome) {
     const char* const out_path = rq.out_path;
     Document d;
-    int rc = build_document(rq, ex, lay, &d, outcome);
+    int rc = build_document(rq, ex, lay, cov, &d, outcome);
     if (rc != BLU_OK) return rc;
     if (getenv("BLU_INGEST_TRACE")) fprintf(stderr, "[pipeline] %-26s %.3f s\n", "tear-down (tables, strings)", now_s() - g_t_body_end);
     if (d.written) return put_tables(d, rq);
@@ -628,6 +632,11 @@ int blu_build_consensus_with(const blu_consensus_request* request, const blu_con
 
 int blu_build_consensus_laid_out(const blu_consensus_request* request, const blu_consensus_extras* extras, const blu_table_layout* layout,
                                  blu_consensus_outcome* outcome) {
+    return blu_build_consensus_covered(request, extras, layout, nullptr, outcome);
+}
+
+int blu_build_consensus_covered(const blu_consensus_request* request, const blu_consensus_extras* extras, const blu_table_layout* layout,
+                                const blu_query_cover* cover, blu_consensus_outcome* outcome) {
     g_cover_pending = g_last_min_cover = blu_min_cover_stats{};
     if (!request || !outcome) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     if (extras) {
@@ -645,7 +654,7 @@ int blu_build_consensus_laid_out(const blu_consensus_request* request, const blu
     }
     outcome->text = nullptr; outcome->text_len = 0; outcome->stats = blu_pipeline_stats{};   // (outcome->selection: by Selection)
     try {
-        const int rc = request->out_path ? consensus_to_file(*request, extras, layout, outcome) : consensus_to_text(*request, extras, layout, outcome);
+        const int rc = request->out_path ? consensus_to_file(*request, extras, layout, cover, outcome) : consensus_to_text(*request, extras, layout, cover, outcome);
         if (rc == BLU_OK) g_last_min_cover = g_cover_pending;
         return rc;
     }

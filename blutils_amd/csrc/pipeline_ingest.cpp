@@ -149,6 +149,7 @@ struct Chunk {
     std::vector<std::string_view> acc_sorted;
     uint64_t unmatched = 0, first_line = 0, n_lines = 0;
     uint64_t n_data_lines = 0, n_kept = 0;   // under a hit or taxon filter: non-empty lines, lines kept
+    uint64_t n_below = 0;                    // under a query cover: lines below it, whatever the other filters say
     uint64_t n_not_only = 0;                 // under a taxon filter: lines failing only the only list, and per exclude element
     std::vector<uint64_t> excluded_by;       // the lines whose first matching element it is
     int rc = BLU_OK;
@@ -170,10 +171,21 @@ inline bool filter_keeps(const blu_hit_filter& f, double pid, int64_t aln, doubl
     return true;
 }
 
+// The query cover's predicate (include/blu_pipeline.h: blu_query_cover) on the values parse_i64 gave, each in
+// 0 .. 2^31 - 1 and qlen > 0: 64-bit integers, both sides below 2^48.  a: the percent column, or qstart; b: qend.  This is the
+// definition the GPU parser's decisions are held to.
+inline bool cover_keeps(const blu_query_cover& c, int64_t a, int64_t b, int64_t qlen) {
+    if (c.source != BLU_QUERY_COVER_QLEN) return a * 1000 >= (int64_t)c.min_cover_milli;
+    const int64_t span = (a > b ? a - b : b - a) + 1;
+    return span * 100000 >= (int64_t)c.min_cover_milli * qlen;
+}
+
 // LAID_OUT: the seven role fields are read through `lay` (blu_table_layout: a checked layout that is not the
-// reference's own); otherwise the positions are the reference's literals and lay is not looked at.
+// reference's own); otherwise the positions are the reference's literals and lay is not looked at.  cov (LAID_OUT only): the
+// query cover, whose fields are read through their own columns.
 template <bool LAID_OUT>
-void parse_chunk_as(Chunk& c, const Db& db, const char* path, const blu_hit_filter* flt, const TaxonCodes* taxa, const blu_table_layout* lay) {
+void parse_chunk_as(Chunk& c, const Db& db, const char* path, const blu_hit_filter* flt, const TaxonCodes* taxa, const blu_table_layout* lay,
+                    const blu_query_cover* cov) {
     constexpr int MAX_COLS = LAID_OUT ? (int)BLU_TABLE_LAYOUT_MAX_COLUMNS : 13;
     const int n_cols = LAID_OUT ? (int)lay->n_columns : 13;
     const int c_q = LAID_OUT ? (int)lay->query : 0, c_a = LAID_OUT ? (int)lay->accession : 1, c_tax = LAID_OUT ? (int)lay->taxid : 2;
@@ -225,12 +237,34 @@ void parse_chunk_as(Chunk& c, const Db& db, const char* path, const blu_hit_filt
                          (unsigned long long)line_no, (unsigned long long)c.first_line, path);
                 c.rc = BLU_ERR_PARSE; c.err = msg; return;
             }
-            if (flt || taxa) {                                // (validated like every line; dropped before it reaches a dictionary)
+            if (flt || taxa || (LAID_OUT && cov)) {           // (validated like every line; dropped before it reaches a dictionary)
                 double ev = 0;
                 if (flt && (flt->mask & BLU_FILTER_MAX_E_VALUE) && !parse_f64(col[c_e], &ev)) {
                     snprintf(msg, sizeof msg, "line %llu(+%llu) of %s: numeric column does not parse (e_value)", (unsigned long long)line_no,
                              (unsigned long long)c.first_line, path);
                     c.rc = BLU_ERR_PARSE; c.err = msg; return;
+                }
+                bool covered = true;
+                if constexpr (LAID_OUT) if (cov) {            // the coverage fields: Int64 like `length`, 0 .. 2^31 - 1, qlen > 0 — on every line
+                    const bool by_len = cov->source == BLU_QUERY_COVER_QLEN;
+                    const uint32_t at[3] = {by_len ? cov->qstart : cov->cover_column, cov->qend, cov->qlen};
+                    static const char* const what[3] = {"qstart", "qend", "qlen"};
+                    int64_t v[3] = {0, 0, 1};
+                    for (int k = 0; k < (by_len ? 3 : 1); ++k) {
+                        const char* const name = by_len ? what[k] : cov->source == BLU_QUERY_COVER_QCOVS ? "qcovs" : "qcovhsp";
+                        if (!parse_i64(col[at[k]], &v[k])) {
+                            snprintf(msg, sizeof msg, "line %llu(+%llu) of %s: query cover column does not parse (%s)", (unsigned long long)line_no,
+                                     (unsigned long long)c.first_line, path, name);
+                            c.rc = BLU_ERR_PARSE; c.err = msg; return;
+                        }
+                        if (v[k] < 0 || v[k] > INT32_MAX || (k == 2 && v[k] == 0)) {
+                            snprintf(msg, sizeof msg, "line %llu(+%llu) of %s: query cover column outside its range (%s: 0 to 2^31 - 1, qlen above 0)",
+                                     (unsigned long long)line_no, (unsigned long long)c.first_line, path, name);
+                            c.rc = BLU_ERR_PARSE; c.err = msg; return;
+                        }
+                    }
+                    covered = cover_keeps(*cov, v[0], v[1], v[2]);
+                    if (!covered) ++c.n_below;                // (whatever the other filters say)
                 }
                 ++c.n_data_lines;
                 // the taxon verdict: the code of the row the line joins to, first and whatever the thresholds say.
@@ -242,7 +276,7 @@ void parse_chunk_as(Chunk& c, const Db& db, const char* path, const blu_hit_filt
                     if (code == TAXON_NOT_ONLY) ++c.n_not_only;
                     else if (code) ++c.excluded_by[code - 1];
                 }
-                if (code || (flt && !filter_keeps(*flt, pid, aln, ev, bs))) { p = nl ? nl + 1 : c.end; continue; }
+                if (code || !covered || (flt && !filter_keeps(*flt, pid, aln, ev, bs))) { p = nl ? nl + 1 : c.end; continue; }
                 ++c.n_kept;
             }
             RawRow r;
@@ -275,9 +309,9 @@ void parse_chunk_as(Chunk& c, const Db& db, const char* path, const blu_hit_filt
     std::sort(c.acc_sorted.begin(), c.acc_sorted.end());
 }
 void parse_chunk(Chunk& c, const Db& db, const char* path, const blu_hit_filter* flt = nullptr, const TaxonCodes* taxa = nullptr,
-                 const blu_table_layout* lay = nullptr) {
-    if (lay) parse_chunk_as<true>(c, db, path, flt, taxa, lay);
-    else parse_chunk_as<false>(c, db, path, flt, taxa, nullptr);
+                 const blu_table_layout* lay = nullptr, const blu_query_cover* cov = nullptr) {
+    if (lay) parse_chunk_as<true>(c, db, path, flt, taxa, lay, cov);
+    else parse_chunk_as<false>(c, db, path, flt, taxa, nullptr, nullptr);
 }
 
 // ---- taxon filter (include/blu_pipeline.h: blu_taxon_filter): the two lists -> one code per taxonomy row.
@@ -377,7 +411,7 @@ int taxon_codes(const Db& db, const blu_taxon_filter& f, unsigned nthreads, Taxo
 }
 
 // ---- the table's column layout (include/blu_pipeline.h: blu_table_layout) ----------------------------------------
-int check_table_layout(const blu_table_layout* lay, const blu_hit_filter* flt, const blu_table_layout** use) {
+int check_table_layout(const blu_table_layout* lay, const blu_hit_filter* flt, const blu_table_layout** use, bool keep_reference) {
     *use = nullptr;
     if (!lay) return BLU_OK;
     if (lay->struct_size != sizeof(blu_table_layout)) {
@@ -403,16 +437,52 @@ int check_table_layout(const blu_table_layout* lay, const blu_hit_filter* flt, c
     }
     const bool reference = lay->n_columns == 13 && lay->query == 0 && lay->accession == 1 && lay->taxid == 2 && lay->perc_identity == 3 &&
                            lay->align_length == 4 && lay->e_value == 11 && lay->bit_score == 12 && !lay->taxid_is_list;
-    if (!reference) *use = lay;
+    if (!reference || keep_reference) *use = lay;
+    return BLU_OK;
+}
+
+// ---- the query cover (include/blu_pipeline.h: blu_query_cover) ------------------------------------------------------
+int check_query_cover(const blu_query_cover* cov, const blu_table_layout* lay) {
+    if (!cov) return BLU_OK;
+    if (cov->struct_size != sizeof(blu_query_cover)) {
+        set_error("query cover: struct_size %u is not a blu_query_cover this library knows (%zu bytes)", cov->struct_size, sizeof(blu_query_cover));
+        return BLU_ERR_INVALID_ARG;
+    }
+    if (cov->stats) *cov->stats = blu_query_cover_stats{};
+    if (cov->source != BLU_QUERY_COVER_QCOVHSP && cov->source != BLU_QUERY_COVER_QLEN && cov->source != BLU_QUERY_COVER_QCOVS) {
+        set_error("query cover: source %u is not qcovhsp (1), qlen (2) or qcovs (3); blu_query_cover_parse resolves `auto`", cov->source);
+        return BLU_ERR_INVALID_ARG;
+    }
+    if (cov->min_cover_milli > BLU_QUERY_COVER_MAX_MILLI) {
+        set_error("query cover: %u thousandths of a percent, 0 to %u are taken", cov->min_cover_milli, BLU_QUERY_COVER_MAX_MILLI);
+        return BLU_ERR_INVALID_ARG;
+    }
+    if (!lay) {
+        set_error("query cover: the reference's columns hold no query length; the table's columns have to be named (a blu_table_layout)");
+        return BLU_ERR_INVALID_ARG;
+    }
+    if (lay->struct_size != sizeof(blu_table_layout)) return BLU_OK;   // (check_table_layout refuses it, with its own message)
+    const bool by_len = cov->source == BLU_QUERY_COVER_QLEN;
+    const uint32_t at[3] = {by_len ? cov->qstart : cov->cover_column, cov->qend, cov->qlen};
+    static const char* const len_name[3] = {"qstart", "qend", "qlen"};
+    const uint32_t role[7] = {lay->query, lay->accession, lay->taxid, lay->perc_identity, lay->align_length, lay->bit_score, lay->e_value};
+    static const char* const role_name[7] = {"query", "accession", "taxid", "perc_identity", "align_length", "bit_score", "e_value"};
+    for (int k = 0; k < (by_len ? 3 : 1); ++k) {
+        const char* const name = by_len ? len_name[k] : "cover";
+        if (at[k] >= lay->n_columns) { set_error("query cover: the %s column %u is not one of the %u columns", name, at[k], lay->n_columns); return BLU_ERR_INVALID_ARG; }
+        for (int r = 0; r < 7; ++r)
+            if (at[k] == role[r]) { set_error("query cover: the %s column %u is the layout's %s column", name, at[k], role_name[r]); return BLU_ERR_INVALID_ARG; }
+        for (int j = 0; j < k; ++j)
+            if (at[k] == at[j]) { set_error("query cover: %s and %s are both column %u", len_name[j], name, at[k]); return BLU_ERR_INVALID_ARG; }
+    }
     return BLU_OK;
 }
 
 namespace {
 // BLAST's format string -> layout (blu_table_layout_parse).  Roles by priority, not by position: the first name of each list
 // that the string holds.
-int parse_layout_spec(const char* spec, blu_table_layout* out) {
+int spec_columns(const char* spec, std::vector<std::string>& cols) {
     static const char* const STD[12] = {"qseqid", "sseqid", "pident", "length", "mismatch", "gapopen", "qstart", "qend", "sstart", "send", "evalue", "bitscore"};
-    std::vector<std::string> cols;
     const char* p = spec;
     bool first = true;
     while (*p) {
@@ -443,6 +513,11 @@ int parse_layout_spec(const char* spec, blu_table_layout* out) {
     for (size_t a = 0; a < cols.size(); ++a)
         for (size_t b = 0; b < a; ++b)
             if (cols[a] == cols[b]) { set_error("blast outfmt: `%s` is named twice (columns %zu and %zu)", cols[a].c_str(), b + 1, a + 1); return BLU_ERR_INVALID_ARG; }
+    return BLU_OK;
+}
+int parse_layout_spec(const char* spec, blu_table_layout* out, std::vector<std::string>* names = nullptr) {
+    std::vector<std::string> cols;
+    if (int rc = spec_columns(spec, cols)) return rc;
     auto find = [&](std::initializer_list<const char*> names, uint32_t* at, const char** which) {
         for (const char* n : names)
             for (size_t k = 0; k < cols.size(); ++k)
@@ -462,6 +537,43 @@ int parse_layout_spec(const char* spec, blu_table_layout* out) {
     if (!find({"evalue"}, &l.e_value, nullptr)) l.e_value = BLU_TABLE_LAYOUT_NO_COLUMN;
     l.taxid_is_list = strcmp(tax_name, "staxids") == 0 ? 1u : 0u;
     *out = l;
+    if (names) names->swap(cols);
+    return BLU_OK;
+}
+
+// The format string and a source -> the cover's columns (blu_query_cover_parse): the string goes through parse_layout_spec first,
+// so every refusal of the layout is a refusal here.
+int parse_cover_spec(const char* spec, uint32_t source, blu_query_cover* out) {
+    blu_table_layout lay{};
+    std::vector<std::string> cols;
+    if (int rc = parse_layout_spec(spec, &lay, &cols)) return rc;
+    if (source > BLU_QUERY_COVER_QCOVS) { set_error("query cover: source %u is not auto (0), qcovhsp (1), qlen (2) or qcovs (3)", source); return BLU_ERR_INVALID_ARG; }
+    auto at = [&](const char* n) { for (size_t k = 0; k < cols.size(); ++k) if (cols[k] == n) return (uint32_t)k; return BLU_TABLE_LAYOUT_NO_COLUMN; };
+    const uint32_t c_hsp = at("qcovhsp"), c_s = at("qstart"), c_e = at("qend"), c_l = at("qlen"), c_subj = at("qcovs");
+    const bool has_len = c_s != BLU_TABLE_LAYOUT_NO_COLUMN && c_e != BLU_TABLE_LAYOUT_NO_COLUMN && c_l != BLU_TABLE_LAYOUT_NO_COLUMN;
+    std::string missing;                            // of what the asked source reads
+    auto lacks = [&](uint32_t c, const char* n) { if (c == BLU_TABLE_LAYOUT_NO_COLUMN) { missing += missing.empty() ? "`" : ", `"; missing += n; missing += '`'; } };
+    if (source == BLU_QUERY_COVER_AUTO) {
+        source = c_hsp != BLU_TABLE_LAYOUT_NO_COLUMN ? BLU_QUERY_COVER_QCOVHSP : has_len ? BLU_QUERY_COVER_QLEN : c_subj != BLU_TABLE_LAYOUT_NO_COLUMN ? BLU_QUERY_COVER_QCOVS : BLU_QUERY_COVER_AUTO;
+        if (source == BLU_QUERY_COVER_AUTO) {
+            lacks(c_hsp, "qcovhsp"); lacks(c_s, "qstart"); lacks(c_e, "qend"); lacks(c_l, "qlen"); lacks(c_subj, "qcovs");
+            set_error("query cover: the format string names no coverage column: `qcovhsp`, or `qstart` `qend` `qlen`, or `qcovs` is needed; it lacks %s", missing.c_str());
+            return BLU_ERR_INVALID_ARG;
+        }
+    }
+    if (source == BLU_QUERY_COVER_QCOVHSP) lacks(c_hsp, "qcovhsp");
+    else if (source == BLU_QUERY_COVER_QCOVS) lacks(c_subj, "qcovs");
+    else { lacks(c_s, "qstart"); lacks(c_e, "qend"); lacks(c_l, "qlen"); }
+    if (!missing.empty()) {
+        set_error("query cover: source %s needs %s, and the format string lacks %s", source == BLU_QUERY_COVER_QCOVHSP ? "qcovhsp" : source == BLU_QUERY_COVER_QCOVS ? "qcovs" : "qlen",
+                  source == BLU_QUERY_COVER_QLEN ? "`qstart`, `qend` and `qlen`" : "that column", missing.c_str());
+        return BLU_ERR_INVALID_ARG;
+    }
+    const bool by_len = source == BLU_QUERY_COVER_QLEN;
+    out->source = source;
+    out->cover_column = by_len ? BLU_TABLE_LAYOUT_NO_COLUMN : source == BLU_QUERY_COVER_QCOVHSP ? c_hsp : c_subj;
+    out->qstart = by_len ? c_s : BLU_TABLE_LAYOUT_NO_COLUMN; out->qend = by_len ? c_e : BLU_TABLE_LAYOUT_NO_COLUMN; out->qlen = by_len ? c_l : BLU_TABLE_LAYOUT_NO_COLUMN;
+    out->reserved = 0;
     return BLU_OK;
 }
 }  // namespace
@@ -474,10 +586,11 @@ static thread_local int g_last_ingest_path = 0;   // 0 = CPU parser, 1 = GPU par
 // position, mod.rs:192-208), accessions by a tree of sorted-list merges (their id is their rank in byte order) —
 // and the workers scatter their rows into the grouped table.  The result does not depend on the thread count.
 int load_hits(const char* path, const Db& db, HitTable& ht, int device, bool host_columns, const blu_hit_filter* flt, TaxonCodes* taxa,
-              const blu_table_layout* lay) {
+              const blu_table_layout* lay, const blu_query_cover* cov) {
     g_last_ingest_path = 0;
     if (flt && !(flt->mask & 15u)) flt = nullptr;   // no threshold given: today's path
-    if (int rc = check_table_layout(lay, flt, &lay)) return rc;   // (the reference's own columns: today's path)
+    if (int rc = check_query_cover(cov, lay)) return rc;
+    if (int rc = check_table_layout(lay, flt, &lay, cov != nullptr)) return rc;   // (the reference's own columns: today's path)
     // GPU parser first (ingest_gpu.hip) when a device is given: same columns bit for bit; files it does not handle
     // (quotes, empty lines, unusual numbers), small files and BLU_INGEST=cpu take the CPU path below.  The GPU path
     // reads the file through its descriptor and never maps it.
@@ -491,7 +604,7 @@ int load_hits(const char* path, const Db& db, HitTable& ht, int device, bool hos
         const bool want_gpu = device >= 0 && db.dup_rows.empty() && !(mode && strcmp(mode, "cpu") == 0) && (fsize >= (1u << 20) || (mode && strcmp(mode, "gpu") == 0));
         int rc = BLU_INGEST_FALLBACK;
         std::string why;
-        if (want_gpu) rc = load_hits_gpu(fd, fsize, db.row_of, device, host_columns, ht, &why, flt, taxa, lay);
+        if (want_gpu) rc = load_hits_gpu(fd, fsize, db.row_of, device, host_columns, ht, &why, flt, taxa, lay, cov);
         ::close(fd);
         if (want_gpu) {
             if (rc == BLU_OK) { g_last_ingest_path = 1; return BLU_OK; }
@@ -518,7 +631,7 @@ int load_hits(const char* path, const Db& db, HitTable& ht, int device, bool hos
         cur = target;
     }
     Trace tr{"[ingest]", 22};
-    parallel_for(nthreads, nthreads, [&](unsigned t) { parse_chunk(chunks[t], db, path, flt, taxa, lay); });
+    parallel_for(nthreads, nthreads, [&](unsigned t) { parse_chunk(chunks[t], db, path, flt, taxa, lay, cov); });
     tr.lap("parse (parallel)");
     uint64_t lines_before = 0;
     size_t nh = 0;
@@ -528,7 +641,7 @@ int load_hits(const char* path, const Db& db, HitTable& ht, int device, bool hos
         lines_before += c.n_lines;
         nh += c.rows.size();
         ht.unmatched += c.unmatched;
-        ht.n_lines += c.n_data_lines; ht.n_kept += c.n_kept;
+        ht.n_lines += c.n_data_lines; ht.n_kept += c.n_kept; ht.n_below += c.n_below;
         if (taxa) {
             taxa->n_not_only += c.n_not_only;
             for (uint32_t k = 0; k < taxa->n_exclude; ++k) { taxa->excluded_by[k] += c.excluded_by[k]; taxa->n_excluded += c.excluded_by[k]; }
@@ -604,17 +717,19 @@ int load_hits(const char* path, const Db& db, HitTable& ht, int device, bool hos
 
 // The ingest half under a selection, into malloc'd copies of the host columns.
 static int ingest_columns_selected(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
-                            const blu_table_layout* lay, const blu_hit_selection* selection, blu_ingest_columns* out,
+                            const blu_table_layout* lay, const blu_query_cover* cov, const blu_hit_selection* selection, blu_ingest_columns* out,
                             blu_hit_selection_stats* stats) {
     Selection sel(selection, stats);
     if (int rc = sel.check()) return rc;
-    if (int rc = check_table_layout(lay, sel.flt, &lay)) return rc;   // (before any file is opened)
+    if (int rc = check_query_cover(cov, lay)) return rc;              // (before any file is opened)
+    if (int rc = check_table_layout(lay, sel.flt, &lay, cov != nullptr)) return rc;
+    sel.cov = cov;
     Db db;
     int rc = load_db(taxonomies_file, use_taxid != 0, db);
     if (rc != BLU_OK) return rc;
     if ((rc = sel.resolve(db, worker_threads())) != BLU_OK) return rc;
     HitTable ht;
-    rc = load_hits(blast_output_file, db, ht, device, true, sel.flt, sel.taxa.get(), lay);
+    rc = load_hits(blast_output_file, db, ht, device, true, sel.flt, sel.taxa.get(), lay, cov);
     if (rc != BLU_OK) return rc;
     ht.wait_strings();
     if (!ht.strings_ok) { set_error("out of memory while building the query / accession strings"); return BLU_ERR_ALLOC; }
@@ -706,9 +821,15 @@ int blu_ingest_columns_selected(const char* blast_output_file, const char* taxon
 int blu_ingest_columns_laid_out(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
                                 const blu_table_layout* layout, const blu_hit_selection* selection, blu_ingest_columns* out,
                                 blu_hit_selection_stats* stats) {
+    return blu_ingest_columns_covered(blast_output_file, taxonomies_file, use_taxid, device, layout, nullptr, selection, out, stats);
+}
+
+int blu_ingest_columns_covered(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                               const blu_table_layout* layout, const blu_query_cover* cover, const blu_hit_selection* selection,
+                               blu_ingest_columns* out, blu_hit_selection_stats* stats) {
     if (!blast_output_file || !taxonomies_file || !out) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     memset(out, 0, sizeof *out);
-    try { return ingest_columns_selected(blast_output_file, taxonomies_file, use_taxid, device, layout, selection, out, stats); }
+    try { return ingest_columns_selected(blast_output_file, taxonomies_file, use_taxid, device, layout, cover, selection, out, stats); }
     catch (const std::bad_alloc&) { blu_ingest_columns_free(out); set_error("out of memory"); return BLU_ERR_ALLOC; }
 }
 
@@ -728,6 +849,16 @@ int blu_table_layout_parse(const char* spec, blu_table_layout* out) {
         return BLU_ERR_INVALID_ARG;
     }
     try { return parse_layout_spec(spec, out); }
+    catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
+}
+
+int blu_query_cover_parse(const char* spec, uint32_t source, blu_query_cover* out) {
+    if (!spec || !out) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    if (out->struct_size != sizeof(blu_query_cover)) {
+        set_error("blu_query_cover_parse: struct_size %u is not a blu_query_cover this library knows (%zu bytes)", out->struct_size, sizeof(blu_query_cover));
+        return BLU_ERR_INVALID_ARG;
+    }
+    try { return parse_cover_spec(spec, source, out); }
     catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
 }
 

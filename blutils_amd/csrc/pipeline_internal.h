@@ -152,12 +152,17 @@ struct Trace {
 // ---- CPU ingest (pipeline_ingest.cpp) --------------------------------------------------------------------------------------
 int taxon_codes(const Db& db, const blu_taxon_filter& f, unsigned nthreads, TaxonCodes& tc);
 // lay: the table's column layout, checked by check_table_layout on the way in; null = the reference's columns
+// cov: the query cover, checked by check_query_cover on the way in; null = none
 int load_hits(const char* path, const Db& db, HitTable& ht, int device = -1, bool host_columns = true, const blu_hit_filter* flt = nullptr,
-              TaxonCodes* taxa = nullptr, const blu_table_layout* lay = nullptr);
+              TaxonCodes* taxa = nullptr, const blu_table_layout* lay = nullptr, const blu_query_cover* cov = nullptr);
 // A caller's layout before any file is opened: BLU_ERR_INVALID_ARG for a size, a count or role columns the library does not
 // take, and for an e-value threshold (flt: the active hit filter, or null) over a layout without an e-value column.  *use: the
-// layout the parsers are to read through, null when lay is null or names the reference's thirteen columns in their order.
-int check_table_layout(const blu_table_layout* lay, const blu_hit_filter* flt, const blu_table_layout** use);
+// layout the parsers are to read through, null when lay is null or names the reference's thirteen columns in their order —
+// unless keep_reference: under a query cover the parsers read through the layout whatever it names.
+int check_table_layout(const blu_table_layout* lay, const blu_hit_filter* flt, const blu_table_layout** use, bool keep_reference = false);
+// A caller's query cover against the caller's layout, before any file is opened: BLU_ERR_INVALID_ARG for a size, a
+// source, a threshold or columns the library does not take, and for a cover without a layout.  The caller's stats are zeroed.
+int check_query_cover(const blu_query_cover* cov, const blu_table_layout* lay);
 
 // One run's hit selection (include/blu_pipeline.h: blu_hit_selection) as the use-case and the
 // ingest-columns call both take it: an option with an empty mask or two empty lists is absent, the taxon lists are resolved
@@ -171,6 +176,7 @@ struct Selection {
     std::unique_ptr<TaxonCodes> taxa;             // (the taxon filter as the parsers read it)
     blu_hit_selection_stats own{};                // (a caller that wants no counts)
     blu_hit_selection_stats* const st;
+    const blu_query_cover* cov = nullptr;         // (the query cover beside the request, checked; null = none: DESIGN.md §24)
     int64_t cover_milli = 0;                      // (blu_consensus_request.min_cover_milli; 0 = not asked for: DESIGN.md §20)
     blu_min_cover_stats cover_st{};               // (its counts: blu_last_min_cover_stats)
     bool subject_done = false, band_done = false, cover_done = false;   // (once per run, on the device columns or on the host columns)
@@ -203,8 +209,9 @@ struct Selection {
     }
     // the parser's counts, and the table as it stands before options 2 and 3
     void loaded(const HitTable& ht) {
-        const bool on = flt || taxa;
+        const bool on = flt || taxa || cov;
         st->hit_filter = blu_hit_filter_stats{on ? ht.n_lines : ht.n_hits, on ? ht.n_kept : ht.n_hits};
+        if (cov && cov->stats) *cov->stats = blu_query_cover_stats{ht.n_lines, ht.n_below};
         if (taxa) {
             st->taxon_filter.n_lines = ht.n_lines; st->taxon_filter.n_excluded = taxa->n_excluded; st->taxon_filter.n_not_only = taxa->n_not_only;
             if (st->taxon_filter.excluded_by) for (uint32_t k = 0; k < taxa->n_exclude; ++k) st->taxon_filter.excluded_by[k] = taxa->excluded_by[k];
@@ -366,6 +373,7 @@ struct Run {
     const blu_consensus_request& rq;
     const blu_consensus_extras* const ex;          // (NULL: none)
     const blu_table_layout* lay;                   // (the table's column layout; NULL once start() has checked it: the reference's columns)
+    const blu_query_cover* const cov;              // (the query cover; NULL: none)
     const blu_pipeline_params* const params;
     Selection sel;
     blu_pipeline_stats st{};
@@ -387,8 +395,9 @@ struct Run {
     std::unique_ptr<CountTable> counts;            // (the count table, when the extras name one, and its join with the queries)
     CountJoin joined;
 
-    Run(const blu_consensus_request& request, const blu_consensus_extras* extras, const blu_table_layout* layout, blu_consensus_outcome* outcome)
-        : rq(request), ex(extras), lay(layout), params(request.params), sel(&request.selection, &outcome->selection) {}
+    Run(const blu_consensus_request& request, const blu_consensus_extras* extras, const blu_table_layout* layout, const blu_query_cover* cover,
+        blu_consensus_outcome* outcome)
+        : rq(request), ex(extras), lay(layout), cov(cover), params(request.params), sel(&request.selection, &outcome->selection) {}
     ~Run() { if (warm_up.joinable()) warm_up.join(); if (tax) blu_taxonomy_destroy(tax); }
     // the steps of build_document, in order; each returns an error code
     int start();

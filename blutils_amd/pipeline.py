@@ -299,6 +299,82 @@ def _layout(blast_outfmt) -> Optional[TableLayoutC]:
     return None if lay.is_reference() else lay
 
 
+QUERY_COVER_SOURCE = {"auto": 0, "qcovhsp": 1, "qlen": 2, "qcovs": 3}
+QUERY_COVER_SOURCE_NAME = {v: k for k, v in QUERY_COVER_SOURCE.items()}
+
+
+def min_query_cover_milli(value) -> int:
+    """A --min-query-cover value -> thousandths of a percent (0 .. 100000), exactly: a decimal with at most three decimals in
+    0 .. 100, read as top_percent_milli reads --top-percent (never through a float)."""
+    try:
+        return top_percent_milli(value)
+    except ValueError as e:
+        raise ValueError(str(e).replace("top_percent", "min_query_cover", 1))
+
+
+@dataclasses.dataclass(frozen=True)
+class QueryCover:
+    """Lines dropped by their query coverage, in the parser (include/blu_pipeline.h: blu_query_cover; the
+    reference has it only as `-q` of its own blastn call).  percent: a decimal string or Decimal with at most three decimals,
+    0 .. 100, read exactly.  source: `qcovhsp` (that column, BLAST's per-HSP integer percent c: kept iff c * 1000 >= 1000 *
+    percent), `qlen` (the columns qstart, qend, qlen: kept iff (|qend - qstart| + 1) * 100000 >= 1000 * percent * qlen — the
+    exact ratio, not BLAST's rounded percent), `qcovs` (that column, the coarser per-subject figure) or `auto`: the first of the
+    three the format string has.  Needs blast_outfmt, which names the columns."""
+    percent: Union[str, decimal.Decimal] = "0"
+    source: str = "auto"
+
+
+class QueryCoverStats(C.Structure):
+    """include/blu_pipeline.h: blu_query_cover_stats"""
+    _fields_ = [("n_lines", C.c_uint64), ("n_below", C.c_uint64)]
+
+
+class QueryCoverC(C.Structure):
+    """include/blu_pipeline.h: blu_query_cover"""
+    _fields_ = [("struct_size", C.c_uint32), ("source", C.c_uint32), ("min_cover_milli", C.c_uint32), ("cover_column", C.c_uint32),
+                ("qstart", C.c_uint32), ("qend", C.c_uint32), ("qlen", C.c_uint32), ("reserved", C.c_uint32),
+                ("stats", C.POINTER(QueryCoverStats))]
+
+
+class _Cover:
+    """The C cover of one call, resolved against the format string, and the stats it points to."""
+
+    def __init__(self, query_cover, blast_outfmt):
+        if isinstance(query_cover, dict):
+            unknown = set(query_cover) - {"percent", "source"}
+            if unknown:
+                raise ValueError(f"query_cover: unknown keys {sorted(unknown)}")
+            query_cover = QueryCover(**query_cover)
+        elif not isinstance(query_cover, QueryCover):
+            query_cover = QueryCover(query_cover)
+        if query_cover.source not in QUERY_COVER_SOURCE:
+            raise ValueError(f"query_cover: source must be one of {sorted(QUERY_COVER_SOURCE)}, got {query_cover.source!r}")
+        if not isinstance(blast_outfmt, str):
+            raise ValueError("query_cover: the reference's columns hold no query length; blast_outfmt has to name the table's "
+                             "columns, as the format string itself")
+        self.milli = min_query_cover_milli(query_cover.percent)
+        self.percent = str(query_cover.percent).strip()
+        self.st = QueryCoverStats()
+        self.c = QueryCoverC(struct_size=C.sizeof(QueryCoverC), min_cover_milli=self.milli, stats=C.pointer(self.st))
+        self.layout = table_layout(blast_outfmt)          # (never turned into None: the cover reads through it)
+        rc = _bind().blu_query_cover_parse(blast_outfmt.encode(), QUERY_COVER_SOURCE[query_cover.source], C.byref(self.c))
+        if rc != N.BLU_OK:
+            raise N.BluError(rc, "blu_query_cover_parse")
+
+    def counts(self) -> dict:
+        return {"n_lines": int(self.st.n_lines), "n_below": int(self.st.n_below), "percent": self.percent,
+                "source": QUERY_COVER_SOURCE_NAME[int(self.c.source)]}
+
+
+def query_cover_columns(blast_outfmt: str, source: str = "auto", percent="0") -> dict:
+    """The cover a format string and a source resolve to (blu_query_cover_parse): source, cover_column, qstart, qend, qlen
+    (None for the columns the source does not read) and min_cover_milli.  A refusal is a BluError naming the missing specifiers."""
+    c = _Cover(QueryCover(percent, source), blast_outfmt).c
+    col = lambda v: None if v == TABLE_LAYOUT_NO_COLUMN else int(v)
+    return {"source": QUERY_COVER_SOURCE_NAME[int(c.source)], "cover_column": col(c.cover_column), "qstart": col(c.qstart),
+            "qend": col(c.qend), "qlen": col(c.qlen), "min_cover_milli": int(c.min_cover_milli)}
+
+
 class _Selection:
     """The keywords hit_filter / taxon_filter / score_band / best_hit_per_subject as the C struct, with what it points to kept
     alive, and the stats keys each of them adds."""
@@ -357,6 +433,15 @@ def _bind():
         L.blu_ingest_columns_laid_out.restype = C.c_int
         L.blu_ingest_columns_laid_out.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(TableLayoutC), C.POINTER(HitSelection),
                                                   C.POINTER(IngestColumns), C.POINTER(HitSelectionStats)]
+    if hasattr(L, "blu_query_cover_parse"):      # (an A/B library of an older build: BLU_CONSENSUS_LIB)
+        L.blu_query_cover_parse.restype = C.c_int
+        L.blu_query_cover_parse.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(QueryCoverC)]
+        L.blu_build_consensus_covered.restype = C.c_int
+        L.blu_build_consensus_covered.argtypes = [C.POINTER(ConsensusRequest), C.POINTER(ConsensusExtras), C.POINTER(TableLayoutC),
+                                                  C.POINTER(QueryCoverC), C.POINTER(ConsensusOutcome)]
+        L.blu_ingest_columns_covered.restype = C.c_int
+        L.blu_ingest_columns_covered.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(TableLayoutC), C.POINTER(QueryCoverC),
+                                                 C.POINTER(HitSelection), C.POINTER(IngestColumns), C.POINTER(HitSelectionStats)]
     L.blu_free_text.argtypes = [C.c_void_p]
     L.blu_custom_taxon_from_file.restype = C.c_int
     L.blu_custom_taxon_from_file.argtypes = [C.c_char_p, C.POINTER(N.CutoffConfig)]
@@ -387,7 +472,7 @@ def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = Fa
                    hit_filter: Union[None, dict, HitFilter] = None,
                    taxon_filter: Union[None, dict, TaxonFilter] = None,
                    score_band: Union[None, dict, ScoreBand] = None, best_hit_per_subject: bool = False,
-                   blast_outfmt: Optional[str] = None) -> dict:
+                   blast_outfmt: Optional[str] = None, query_cover=None) -> dict:
     """The SoA columns of the ingest (include/blu_pipeline.h: blu_ingest_columns_selected) as numpy arrays + the two string
     tables.  hit_filter (a dict or HitFilter): the columns of the lines it keeps, plus `n_lines` and `n_kept`.  taxon_filter (a
     dict or TaxonFilter): the same under a taxon filter, alone or beside hit_filter, plus `taxon_filter`: its counts (n_lines,
@@ -396,21 +481,29 @@ def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = Fa
     columns with only the best row of every (query, subject accession) pair, selected before the band (needs
     device >= 0), plus `subject_best`: its counts (n_hits, n_kept, n_queries, n_thinned).  blast_outfmt: the format string the table
     was written with, when it is not the reference's (blu_ingest_columns_laid_out): the columns are those of the
-    table rewritten to the reference's columns."""
+    table rewritten to the reference's columns.  query_cover (a QueryCover, a dict of its fields, or the percent alone; needs
+    blast_outfmt as the format string; blu_ingest_columns_covered): the columns of the lines at or above the cover,
+    plus `n_lines`, `n_kept` and `query_cover`: its counts (n_lines, n_below, percent, source)."""
     import numpy as np
     L = _bind()
     c = IngestColumns()
     sel = _Selection(hit_filter, taxon_filter, score_band, best_hit_per_subject)
     st = sel.stats()
-    lay = _layout(blast_outfmt)
-    if lay is None:
+    cover = _Cover(query_cover, blast_outfmt) if query_cover is not None else None
+    lay = _layout(blast_outfmt) if cover is None else cover.layout
+    if cover is not None:
+        # (the sibling entry point: only under a cover)
+        rc = L.blu_ingest_columns_covered(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
+                                          C.byref(lay), C.byref(cover.c), C.byref(sel.c), C.byref(c), C.byref(st))
+    elif lay is None:
         rc = L.blu_ingest_columns_selected(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
                                            C.byref(sel.c), C.byref(c), C.byref(st))
     else:
         rc = L.blu_ingest_columns_laid_out(blast_output.encode(), taxonomies_file.encode(), 1 if use_taxid else 0, device,
                                            C.byref(lay), C.byref(sel.c), C.byref(c), C.byref(st))
     if rc != N.BLU_OK:
-        raise N.BluError(rc, "blu_ingest_columns_selected" if lay is None else "blu_ingest_columns_laid_out")
+        raise N.BluError(rc, "blu_ingest_columns_covered" if cover is not None else
+                         "blu_ingest_columns_selected" if lay is None else "blu_ingest_columns_laid_out")
     try:
         nh, nq = int(c.n_hits), int(c.n_queries)
         arr = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(max(n, 1),))[:n].astype(dt, copy=True)
@@ -421,6 +514,9 @@ def ingest_columns(blast_output: str, taxonomies_file: str, use_taxid: bool = Fa
         out["query_names"] = split(c.query_names, int(c.query_names_bytes))
         out["accessions"] = split(c.accessions, int(c.accessions_bytes))
         out.update(sel.counts(st))
+        if cover is not None:
+            out["n_lines"], out["n_kept"] = int(st.hit_filter.n_lines), int(st.hit_filter.n_kept)
+            out["query_cover"] = cover.counts()
         return out
     finally:
         L.blu_ingest_columns_free(C.byref(c))
@@ -461,7 +557,7 @@ def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: s
                                config=None, out_path: Optional[str] = None, hit_filter: Union[None, dict, HitFilter] = None,
                                taxon_filter: Union[None, dict, TaxonFilter] = None,
                                score_band: Union[None, dict, ScoreBand] = None, best_hit_per_subject: bool = False,
-                               min_cover=None, blast_outfmt: Optional[str] = None):
+                               min_cover=None, blast_outfmt: Optional[str] = None, query_cover=None):
     """Returns (results, stats).  With out_path the document is written there by the library (no copy through Python) and
     (None, stats) is returned.  results: the parsed `results` list (json) / list of records (jsonl), sorted by
     query, or the raw text when parse=False.  config: Some(BlastBuilder) of the run-with-consensus path
@@ -479,10 +575,14 @@ def build_consensus_identities(blast_output: str, taxonomies_file: str, taxon: s
     (DESIGN.md §20), after everything above; stats then also has `min_cover`, its counts (n_hits, n_kept, n_queries,
     n_narrowed, n_unresolved), and n_hits / n_unmatched_rows count the kept lines.  blast_outfmt (BLAST's own format string, e.g.
     `6 std staxids`; None = the reference's thirteen columns): the column list the table was written with; the
-    run gives what it gives on a copy of the table rewritten to the reference's columns."""
+    run gives what it gives on a copy of the table rewritten to the reference's columns.  query_cover (a QueryCover, a dict of
+    its fields, or the percent alone; None = no cover; needs blast_outfmt as the format string): only the lines whose query
+    coverage is at least the percent take part, decided by the parser with the filters; stats then also has
+    `n_lines`, `n_kept` and `query_cover`, its counts (n_lines, n_below, percent, source)."""
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, None, "one", hit_filter=hit_filter, taxon_filter=taxon_filter,
-                  score_band=score_band, best_hit_per_subject=best_hit_per_subject, min_cover=min_cover, blast_outfmt=blast_outfmt)
+                  score_band=score_band, best_hit_per_subject=best_hit_per_subject, min_cover=min_cover, blast_outfmt=blast_outfmt,
+                  query_cover=query_cover)
 
 
 def build_consensus_identities_with_report(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -495,7 +595,8 @@ def build_consensus_identities_with_report(blast_output: str, taxonomies_file: s
                                            taxon_filter: Union[None, dict, TaxonFilter] = None,
                                            score_band: Union[None, dict, ScoreBand] = None,
                                            best_hit_per_subject: bool = False, min_cover=None,
-                                           count_table: Optional[str] = None, blast_outfmt: Optional[str] = None):
+                                           count_table: Optional[str] = None, blast_outfmt: Optional[str] = None,
+                                           query_cover=None):
     """build_consensus_identities plus the taxon abundance report of its results, counted on the GPU and written to
     report_path after the document (include/blu_pipeline.h: blu_consensus_request.report_path).
     report_weight: "one" (results) or "size" (dereplicated reads named in the query).  count_table: a feature x sample count
@@ -504,7 +605,7 @@ def build_consensus_identities_with_report(blast_output: str, taxonomies_file: s
     return _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device,
                   lenient, parse, config, out_path, report_path, report_weight, hit_filter=hit_filter, taxon_filter=taxon_filter,
                   score_band=score_band, best_hit_per_subject=best_hit_per_subject, min_cover=min_cover, count_table=count_table,
-                  blast_outfmt=blast_outfmt)
+                  blast_outfmt=blast_outfmt, query_cover=query_cover)
 
 
 def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: str, taxon: str = "bacteria",
@@ -519,7 +620,8 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
                                            taxon_filter: Union[None, dict, TaxonFilter] = None,
                                            score_band: Union[None, dict, ScoreBand] = None,
                                            best_hit_per_subject: bool = False, min_cover=None,
-                                           count_table: Optional[str] = None, blast_outfmt: Optional[str] = None):
+                                           count_table: Optional[str] = None, blast_outfmt: Optional[str] = None,
+                                           query_cover=None):
     """build_consensus_identities plus the taxon abundance report (report_path), the per-sample table (sample_table_path,
     DESIGN.md §13), or both, counted on the GPU and written in the order document, report, table
     (include/blu_pipeline.h: blu_consensus_request).  report_weight serves both files.  A query whose name
@@ -534,15 +636,16 @@ def build_consensus_identities_with_tables(blast_output: str, taxonomies_file: s
                   lenient, parse, config, out_path, report_path, report_weight, sample_table_path, hit_filter=hit_filter,
                   support_table_path=support_table_path, taxon_filter=taxon_filter, score_band=score_band,
                   best_hit_per_subject=best_hit_per_subject, min_cover=min_cover, count_table=count_table,
-                  blast_outfmt=blast_outfmt)
+                  blast_outfmt=blast_outfmt, query_cover=query_cover)
 
 
 def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_taxon_values, headers, out_format, device, lenient,
            parse, config, out_path, report_path, report_weight, sample_table_path=None, hit_filter=None,
            support_table_path=None, taxon_filter=None, score_band=None, best_hit_per_subject=False, min_cover=None,
-           count_table=None, blast_outfmt=None):
+           count_table=None, blast_outfmt=None, query_cover=None):
     L = _bind()
-    lay = _layout(blast_outfmt)
+    qcov = _Cover(query_cover, blast_outfmt) if query_cover is not None else None
+    lay = _layout(blast_outfmt) if qcov is None else qcov.layout
     cover = min_cover_milli(min_cover) if min_cover is not None else 0
     sel = _Selection(hit_filter, taxon_filter, score_band, best_hit_per_subject)
     p = PipelineParams()
@@ -577,7 +680,10 @@ def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_tax
         # (what the request has no room for travels in the extras)
         cst = CountTableStats()
         ex = ConsensusExtras(struct_size=C.sizeof(ConsensusExtras), count_table_path=enc(count_table), count_table_stats=C.pointer(cst))
-    if lay is not None:
+    if qcov is not None:
+        # (the sibling entry point: only under a cover)
+        rc = L.blu_build_consensus_covered(C.byref(rq), C.byref(ex) if ex is not None else None, C.byref(lay), C.byref(qcov.c), C.byref(oc))
+    elif lay is not None:
         # (the sibling entry point: only under a layout that is not the reference's own)
         rc = L.blu_build_consensus_laid_out(C.byref(rq), C.byref(ex) if ex is not None else None, C.byref(lay), C.byref(oc))
     elif ex is None:
@@ -592,6 +698,9 @@ def _build(blast_output, taxonomies_file, taxon, strategy, use_taxid, custom_tax
         stats["count_table"] = {f: int(getattr(cst, f)) for f, _ in CountTableStats._fields_}
     if cover:
         stats["min_cover"] = last_min_cover_stats()
+    if qcov is not None:
+        stats["n_lines"], stats["n_kept"] = int(oc.selection.hit_filter.n_lines), int(oc.selection.hit_filter.n_kept)
+        stats["query_cover"] = qcov.counts()
     if out_path is not None:
         return None, stats
     try:

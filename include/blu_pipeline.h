@@ -289,6 +289,46 @@ int blu_table_layout_parse(const char* spec, blu_table_layout* out);
 int blu_build_consensus_laid_out(const blu_consensus_request* request, const blu_consensus_extras* extras /* NULL = none */,
                                  const blu_table_layout* layout /* NULL = the reference's columns */, blu_consensus_outcome* outcome);
 
+/* Query coverage (not in the reference, whose `-q` goes to blastn itself): a fifth threshold of the parser's
+ * keep word, on columns the thirteen of the reference do not hold, so it needs a layout that names them.  A line is kept iff
+ *   BLU_QUERY_COVER_QCOVHSP / _QCOVS  c * 1000 >= min_cover_milli, c the integer of `cover_column` (BLAST's rounded percent: per
+ *                                     HSP, or — the coarser figure — per subject over all HSPs of the pair)
+ *   BLU_QUERY_COVER_QLEN              (|qend - qstart| + 1) * 100000 >= min_cover_milli * qlen: the exact ratio, not BLAST's
+ *                                     rounded percent; a span longer than qlen passes
+ * in 64-bit integers (both sides stay below 2^48).  The fields are read only under a cover, by the Int64 rules of `length`; one
+ * that does not parse, a value outside 0 .. 2^31 - 1 and qlen = 0 are BLU_ERR_PARSE naming the line, on every line, kept or not.
+ * The taxon verdict comes first and is counted as without a cover; a line that fails the cover never has its e-value decided.
+ * The run gives, byte for byte, what it gives without the cover on a copy of the table (same layout) from which the failing lines
+ * were deleted; min_cover_milli = 0 keeps every line (the fields are still validated).  hit_filter.n_lines / n_kept of the
+ * selection's stats then count lines as under a hit filter.  Refused with BLU_ERR_INVALID_ARG before any file is opened: a
+ * struct_size the library does not know, a source that is not one of the three resolved ones, min_cover_milli > 100000, a cover
+ * without a layout, a column the source reads at or beyond the layout's n_columns, on one of the seven roles, or named twice. */
+enum blu_query_cover_source { BLU_QUERY_COVER_AUTO = 0,      /* blu_query_cover_parse only: qcovhsp, else the qlen form, else qcovs */
+                              BLU_QUERY_COVER_QCOVHSP = 1, BLU_QUERY_COVER_QLEN = 2, BLU_QUERY_COVER_QCOVS = 3 };
+#define BLU_QUERY_COVER_MAX_MILLI 100000u
+typedef struct blu_query_cover_stats {
+    uint64_t n_lines;              /* non-empty lines of the table */
+    uint64_t n_below;              /* of them: coverage below the threshold, whatever the other filters say about the line */
+} blu_query_cover_stats;
+typedef struct blu_query_cover {
+    uint32_t struct_size;
+    uint32_t source;               /* enum blu_query_cover_source, resolved */
+    uint32_t min_cover_milli;      /* the percentage times 1000, 0 .. BLU_QUERY_COVER_MAX_MILLI */
+    uint32_t cover_column;         /* QCOVHSP / QCOVS: the 0-based column; else BLU_TABLE_LAYOUT_NO_COLUMN */
+    uint32_t qstart, qend, qlen;   /* QLEN: the three columns; else BLU_TABLE_LAYOUT_NO_COLUMN */
+    uint32_t reserved;
+    blu_query_cover_stats* stats;  /* caller's, or NULL; zeroed when the call begins */
+} blu_query_cover;
+/* The format string (blu_table_layout_parse's tokenising and refusals) and a source -> the columns.  BLU_QUERY_COVER_AUTO takes
+ * `qcovhsp`, else `qstart qend qlen`, else `qcovs`; an explicit source — or AUTO — whose specifiers the string lacks is
+ * BLU_ERR_INVALID_ARG with a message that names the missing ones.  Set out->struct_size before the call; min_cover_milli and
+ * stats are left as the caller set them. */
+int blu_query_cover_parse(const char* spec, uint32_t source, blu_query_cover* out);
+/* blu_build_consensus_laid_out under a cover (NULL: that call). */
+int blu_build_consensus_covered(const blu_consensus_request* request, const blu_consensus_extras* extras /* NULL = none */,
+                                const blu_table_layout* layout, const blu_query_cover* cover /* NULL = none */,
+                                blu_consensus_outcome* outcome);
+
 /* The reference's own three signatures, each the request above with the named fields set and the rest zero
  * (mod.rs:40-47 + write_blutils_output.rs:33-38 with config = None; the same with Some(BlastBuilder); the same to a file).
  * out_len and stats may be NULL. */
@@ -347,6 +387,10 @@ int blu_ingest_columns_selected(const char* blast_output_file, const char* taxon
 int blu_ingest_columns_laid_out(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
                                 const blu_table_layout* layout, const blu_hit_selection* selection, blu_ingest_columns* out,
                                 blu_hit_selection_stats* stats);
+/* The same under a query cover (blu_query_cover, above; NULL = none: blu_ingest_columns_laid_out). */
+int blu_ingest_columns_covered(const char* blast_output_file, const char* taxonomies_file, int use_taxid, int device,
+                               const blu_table_layout* layout, const blu_query_cover* cover, const blu_hit_selection* selection,
+                               blu_ingest_columns* out, blu_hit_selection_stats* stats);
 void blu_ingest_columns_free(blu_ingest_columns* cols);
 
 /* Which parser the calling thread's last ingest used: 0 = CPU, 1 = GPU. */
