@@ -14,7 +14,11 @@
 //   2. parse           one thread per line: tab scan over aligned 16-byte loads, decimal fast path for the four numeric
 //                      columns (mantissa <= 15 digits and |exp10| <= 22: one IEEE operation, so the value is strtod's),
 //                      taxid -> taxonomy row through the uploaded open-addressing map, two 64-bit hashes of the query
-//                      and accession fields; under a hit or taxon filter a keep word per line, and the kept rows compacted
+//                      and accession fields; under a hit or taxon filter a keep word per line, and the kept rows compacted.
+//                      One staged form (parse_rows_body), one general form (parse_row_general) and one tail (finish_row)
+//                      serve all eight kernels: a build is a MODE (no filter, thresholds, taxon filter) and a layout type
+//                      (the reference's columns, a column layout, a layout with a query cover).  Only how a thread of
+//                      the staged form learns where a field begins and ends differs by layout: RefFields, LayoutFields
 //   3. dictionaries    open-addressing tables keyed by hash (insert = CAS on the hash + atomicMin of the row), finalised
 //                      with length + first 12 key bytes; every row then verifies its own text against its slot (a
 //                      mismatch = two strings with one 64-bit hash -> fallback), so ids are exact, not probabilistic
@@ -37,6 +41,7 @@
 #include <string>
 #include <string_view>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "blu_consensus.h"
@@ -149,7 +154,7 @@ __device__ __forceinline__ void filter_row(const DevFilter& f, uint32_t i, doubl
 }
 
 // ---- taxon filter.  The host made one 16-bit code per taxonomy row from the lineages (ingest.h: TaxonCodes);
-// the third build of the parse kernels reads the code of the row a line joined to — 2 bytes beside the 16-byte map entry the
+// the PARSE_TAXA builds of the parse kernels read the code of the row a line joined to — 2 bytes beside the 16-byte map entry the
 // join just read — and takes the line's verdict from it before the thresholds: a failing line's keep word is 0 at once and
 // its e-value is never looked at.
 struct DevTaxa {
@@ -194,237 +199,11 @@ struct RowOut {
     uint32_t* tax; double* pid; int32_t* aln; int32_t* bs;
 };
 
-// One line, read from global memory a byte at a time through one state machine for all thirteen columns: the form that
-// takes any line length.  parse_rows uses it for the blocks whose 256 lines do not fit its LDS stage.
-// FILTER: also reads column 11 when the e-value threshold is on, leaves the line's keep word (filter_row) and does not count
-// unmatched rows (they are counted over the kept rows, after the compaction).
-// Built three times behind functions of their own: parse_row_general (MODE = PARSE_PLAIN: the function of every unfiltered
-// call, its signature as it was), parse_row_general_filtered (PARSE_FILTER) and parse_row_general_taxa (PARSE_TAXA: flt is the
-// DevFilter of a DevFilterTaxa; the taxon verdict first, then the thresholds if any).
-enum : int { PARSE_PLAIN = 0, PARSE_FILTER = 1, PARSE_TAXA = 2 };
-template <int MODE>
-__device__ __forceinline__ void parse_row_general_body(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
-                                                       const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
-                                                       unsigned long long* __restrict__ n_unmatched, const DevFilter* flt) {
-    constexpr bool FILTER = MODE != PARSE_PLAIN;
-    const uint64_t p = line_start[i];
-    uint64_t e = line_start[i + 1] - 1;                 // the newline (or one past the end of a last line without one)
-    if (e > p && text[e - 1] == '\r') --e;
-    if (e <= p) { atomicOr(flags, FB_EMPTY_LINE); return; }
-    int col = 0;
-    uint64_t fstart = p;                                // start of the current field
-    unsigned long long h = 1469598103934665603ull;
-    NumState num;
-    num.reset();
-    double v_tax = 0, v_pid = 0, v_aln = 0, v_bs = 0;
-    uint32_t fb = 0;
-    bool want_e = false;
-    if constexpr (FILTER) want_e = (flt->mask & BLU_FILTER_MAX_E_VALUE) != 0;
-    unsigned long long e_mant = 0;
-    int e_exp = 0;
-    bool e_neg = false;
-    auto end_field = [&](uint64_t fend) {
-        const uint64_t len = fend - fstart;
-        if (col == 0) { o.qh[i] = hash_finish(h, (uint32_t)len); o.qpos[i] = fstart | (len << 44); if (len >= (1u << 20)) fb |= FB_COLUMNS; }
-        else if (col == 1) { o.ah[i] = hash_finish(h, (uint32_t)len); o.apos[i] = fstart | (len << 44); if (len >= (1u << 20)) fb |= FB_COLUMNS; }
-        // (subject_taxid and align_length are Int64 columns, mod.rs:226-244: a fraction or an exponent is left to the CPU
-        // parser, which refuses the file as the reference would)
-        else if (col == 2) { if (!num.value(&v_tax) || num.seen_dot || num.seen_exp) fb |= FB_NUMBER; }
-        else if (col == 3) { if (!num.value(&v_pid)) fb |= FB_NUMBER; }
-        else if (col == 4) { if (!num.value(&v_aln) || num.seen_dot || num.seen_exp) fb |= FB_NUMBER; }
-        else if (col == 12) { if (!num.value(&v_bs)) fb |= FB_NUMBER; }
-        else if (FILTER && col == 11 && want_e) { if (!num.plain()) fb |= FB_NUMBER; e_mant = num.mant; e_exp = num.exponent(); e_neg = num.neg; }
-        ++col;
-        fstart = fend + 1;
-        h = 1469598103934665603ull;
-        num.reset();
-    };
-    // aligned 16-byte loads; bytes outside [p, e) are skipped
-    for (uint64_t a = p & ~15ull; a < e && col < 13; a += 16) {
-        const uint4 v = *reinterpret_cast<const uint4*>(text + a);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const uint64_t q = a + k;
-            if (q < p || q >= e || col >= 13) continue;
-            const uint32_t c = (w[k >> 2] >> (8 * (k & 3))) & 0xFF;
-            if (c == '\t') { end_field(q); continue; }
-            if (col <= 1) { h = hash_step(h, c); if (c == '"') fb |= FB_QUOTE; }
-            else if (col <= 4 || col == 12 || (FILTER && col == 11 && want_e)) num.feed(c, q == fstart);
-        }
-    }
-    if (col < 13) end_field(e);                         // the last field ends with the line
-    if (col < 13) fb |= FB_COLUMNS;
-    if (fb) { atomicOr(flags, fb); return; }
-    // mod.rs:184 AnyValue::Float64 -> try_extract::<i64> (truncation); the engine columns are 32-bit
-    const double bs_t = trunc(v_bs);
-    if (!(bs_t >= -2147483648.0 && bs_t <= 2147483647.0) || !(v_aln >= -2147483648.0 && v_aln <= 2147483647.0) ||
-        !(v_tax >= -9.2e18 && v_tax <= 9.2e18)) { atomicOr(flags, FB_RANGE); return; }
-    const uint32_t row = taxid_lookup(taxmap, (long long)v_tax);   // left join (mod.rs:72-76)
-    if constexpr (MODE == PARSE_TAXA) {
-        if (taxon_verdict(reinterpret_cast<const DevFilterTaxa*>(flt)->t, row)) flt->keep[i] = KEEP_NO;
-        else filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
-    } else if constexpr (FILTER) filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
-    else if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull);
-    o.tax[i] = row; o.pid[i] = v_pid; o.aln[i] = (int32_t)v_aln; o.bs[i] = (int32_t)bs_t;
-}
-__device__ __noinline__ void parse_row_general(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
-                                               const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
-                                               unsigned long long* __restrict__ n_unmatched) {
-    parse_row_general_body<PARSE_PLAIN>(text, line_start, i, taxmap, o, flags, n_unmatched, nullptr);
-}
-__device__ __noinline__ void parse_row_general_filtered(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
-                                                        const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
-                                                        const DevFilter* __restrict__ flt) {
-    parse_row_general_body<PARSE_FILTER>(text, line_start, i, taxmap, o, flags, nullptr, flt);
-}
-__device__ __noinline__ void parse_row_general_taxa(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
-                                                    const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
-                                                    const DevFilter* __restrict__ flt) {
-    parse_row_general_body<PARSE_TAXA>(text, line_start, i, taxmap, o, flags, nullptr, flt);
-}
-
-// The parse kernel proper: a block takes 256 consecutive lines, whose text is one contiguous span of the file (17 KB for
-// BLAST's usual 67-byte lines).  The span is staged in LDS with coalesced 16-byte loads; every lane then (1) finds the
-// tabs of its line with word-wide compares and leaves their positions in LDS, (2) walks the six columns the engine
-// reads ONE COLUMN AT A TIME, so that the 64 lanes of a wave are in the same column and the same branch of the same
-// small loop: the one-state-machine-per-line form above spends its time in divergence (a wave has lanes in every
-// column at once and runs the end-of-field code of all of them at nearly every byte) and in instruction fetch (the
-// 16-byte unrolled body does not fit the instruction cache).  Same grammar, same hashes, same flags as the general form;
-// a block whose span exceeds the stage (lines of 128 bytes and more on average) is parsed by the general form.
-constexpr uint32_t STAGE_BYTES = 32768;
-constexpr int PARSE_THREADS = 256;
-
-//
-// The body is built three times: parse_rows (PARSE_PLAIN: the kernel of every unfiltered call, flt unused),
-// parse_rows_filtered (PARSE_FILTER: column 11 read when its threshold is on, the predicate evaluated on the parsed values,
-// one keep word per line — filter_row; unmatched rows are counted after the compaction instead) and parse_rows_taxa
-// (PARSE_TAXA: as filtered, with the taxon verdict — taxon_verdict — taken first; the thresholds may all be off).
-template <int MODE>
-__device__ __forceinline__ void parse_rows_body(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t n_rows,
-                                                const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
-                                                unsigned long long* __restrict__ n_unmatched, const DevFilter* flt) {
-    constexpr bool FILTER = MODE != PARSE_PLAIN;
-    __shared__ uint4 stage16[STAGE_BYTES / 16];
-    __shared__ uint16_t tab_at[13 * PARSE_THREADS];                  // [column][thread]: position of the tab that ends the column
-    const uint32_t r0 = blockIdx.x * PARSE_THREADS, r1 = min(r0 + (uint32_t)PARSE_THREADS, n_rows), i = r0 + threadIdx.x;
-    // (the four line starts travel together: two round trips to memory per block — these, then the text — and no more)
-    const uint64_t ls0 = line_start[r0], s1 = line_start[r1];       // (line_start[n_rows] = one past the last newline, or size + 1)
-    const uint64_t my_p = line_start[min(i, r1 - 1)], my_e = line_start[min(i, r1 - 1) + 1];
-    const uint64_t s0 = ls0 & ~15ull;
-    if (s1 - s0 > STAGE_BYTES) {                                     // uniform over the block
-        if (i < r1) {
-            if constexpr (MODE == PARSE_TAXA) parse_row_general_taxa(text, line_start, i, taxmap, o, flags, flt);
-            else if constexpr (FILTER) parse_row_general_filtered(text, line_start, i, taxmap, o, flags, flt);
-            else parse_row_general(text, line_start, i, taxmap, o, flags, n_unmatched);
-        }
-        return;
-    }
-    {
-        const uint32_t n16 = (uint32_t)((s1 - s0 + 15) >> 4);        // (reads at most 15 bytes past s1 <= size + 1: inside the 64 bytes of padding)
-        const uint4* src = reinterpret_cast<const uint4*>(text + s0);
-        constexpr int PER_THREAD = STAGE_BYTES / 16 / PARSE_THREADS; // all of a thread's loads are in flight before the first is stored
-        uint4 v[PER_THREAD];
-#pragma unroll
-        for (int j = 0; j < PER_THREAD; ++j) { const uint32_t k = threadIdx.x + (uint32_t)j * PARSE_THREADS; v[j] = src[min(k, n16 - 1)]; }
-#pragma unroll
-        for (int j = 0; j < PER_THREAD; ++j) { const uint32_t k = threadIdx.x + (uint32_t)j * PARSE_THREADS; if (k < n16) stage16[k] = v[j]; }
-    }
-    __syncthreads();
-    if (i >= r1) return;
-    const unsigned char* sb = reinterpret_cast<const unsigned char*>(stage16);
-    const uint32_t* sw = reinterpret_cast<const uint32_t*>(stage16);
-    const uint32_t p = (uint32_t)(my_p - s0);
-    uint32_t e = (uint32_t)(my_e - 1 - s0);                          // the newline (or one past the end of a last line without one)
-    if (e > p && sb[e - 1] == '\r') --e;
-    if (e <= p) { atomicOr(flags, FB_EMPTY_LINE); return; }
-    // ---- (1) the tabs: four bytes per compare (exact zero-byte test on word ^ 0x09090909), bytes outside [p, e) masked off
-    uint32_t n_tabs = 0;
-    for (uint32_t a = p & ~3u; a < e && n_tabs < 13; a += 4) {
-        const uint32_t x = sw[a >> 2] ^ 0x09090909u;
-        uint32_t m = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);   // bit 7 of every byte that is a tab
-        if (a < p) m &= 0xFFFFFFFFu << (8 * (p - a));
-        if (e - a < 4) m &= (1u << (8 * (e - a))) - 1u;
-        while (m && n_tabs < 13) {
-            tab_at[n_tabs * PARSE_THREADS + threadIdx.x] = (uint16_t)(a + ((uint32_t)__builtin_ctz(m) >> 3));
-            ++n_tabs;
-            m &= m - 1;
-        }
-    }
-    if (n_tabs < 12) { atomicOr(flags, FB_COLUMNS); return; }       // fewer than 13 columns
-    auto tab = [&](int c) { return (uint32_t)tab_at[c * PARSE_THREADS + threadIdx.x]; };
-    uint32_t fb = 0;
-    // ---- (2) query and accession: FNV-1a over the field, as in the general form
-    auto hash_field = [&](uint32_t s, uint32_t t) {
-        unsigned long long h = 1469598103934665603ull;
-        for (uint32_t q = s; q < t; ++q) { const uint32_t c = sb[q]; h = hash_step(h, c); if (c == '"') fb |= FB_QUOTE; }
-        return hash_finish(h, t - s);
-    };
-    const uint32_t t0 = tab(0), t1 = tab(1);
-    const unsigned long long qh = hash_field(p, t0), ah = hash_field(t0 + 1, t1);
-    // ---- the four numbers
-    auto number = [&](uint32_t s, uint32_t t, bool integer, double* v) {
-        NumState num;
-        num.reset();
-        for (uint32_t q = s; q < t; ++q) num.feed(sb[q], q == s);
-        if (!num.value(v) || (integer && (num.seen_dot || num.seen_exp))) fb |= FB_NUMBER;
-    };
-    double v_tax = 0, v_pid = 0, v_aln = 0, v_bs = 0;
-    const uint32_t t2 = tab(2), t3 = tab(3);
-    number(t1 + 1, t2, true, &v_tax);                               // (subject_taxid and align_length are Int64 columns, mod.rs:226-244)
-    number(t2 + 1, t3, false, &v_pid);
-    number(t3 + 1, tab(4), true, &v_aln);
-    number(tab(11) + 1, n_tabs == 13 ? tab(12) : e, false, &v_bs);
-    unsigned long long e_mant = 0;
-    int e_exp = 0;
-    bool e_neg = false;
-    if constexpr (FILTER) {
-        if (flt->mask & BLU_FILTER_MAX_E_VALUE) {                   // column 11, read only under its threshold
-            NumState num;
-            num.reset();
-            const uint32_t s = tab(10) + 1, t = tab(11);
-            for (uint32_t q = s; q < t; ++q) num.feed(sb[q], q == s);
-            if (!num.plain()) fb |= FB_NUMBER;
-            e_mant = num.mant; e_exp = num.exponent(); e_neg = num.neg;
-        }
-    }
-    if (fb) { atomicOr(flags, fb); return; }
-    const double bs_t = trunc(v_bs);                                // mod.rs:184 AnyValue::Float64 -> try_extract::<i64> (truncation)
-    if (!(bs_t >= -2147483648.0 && bs_t <= 2147483647.0) || !(v_aln >= -2147483648.0 && v_aln <= 2147483647.0) ||
-        !(v_tax >= -9.2e18 && v_tax <= 9.2e18)) { atomicOr(flags, FB_RANGE); return; }
-    const uint32_t row = taxid_lookup(taxmap, (long long)v_tax);   // left join (mod.rs:72-76)
-    if constexpr (MODE == PARSE_TAXA) {
-        if (taxon_verdict(reinterpret_cast<const DevFilterTaxa*>(flt)->t, row)) flt->keep[i] = KEEP_NO;
-        else filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
-    } else if constexpr (FILTER) filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
-    else if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull);
-    o.qh[i] = qh; o.qpos[i] = (s0 + p) | ((unsigned long long)(t0 - p) << 44);
-    o.ah[i] = ah; o.apos[i] = (s0 + t0 + 1) | ((unsigned long long)(t1 - t0 - 1) << 44);
-    o.tax[i] = row; o.pid[i] = v_pid; o.aln[i] = (int32_t)v_aln; o.bs[i] = (int32_t)bs_t;
-}
-
-__global__ __launch_bounds__(PARSE_THREADS) void parse_rows(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t n_rows,
-                                                            DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
-                                                            unsigned long long* __restrict__ n_unmatched) {
-    parse_rows_body<PARSE_PLAIN>(text, line_start, n_rows, taxmap, o, flags, n_unmatched, nullptr);
-}
-__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_filtered(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
-                                                                     uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
-                                                                     const DevFilter* __restrict__ flt) {   // (in device memory: read with scalar loads)
-    parse_rows_body<PARSE_FILTER>(text, line_start, n_rows, taxmap, o, flags, nullptr, flt);
-}
-__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_taxa(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
-                                                                 uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
-                                                                 const DevFilterTaxa* __restrict__ flt) {   // (in device memory, as the filter alone is)
-    parse_rows_body<PARSE_TAXA>(text, line_start, n_rows, taxmap, o, flags, nullptr, &flt->f);
-}
-
-// ---- 2a. the parse under a column layout.  The table was written with another `-outfmt "6 ..."` list than the
-// reference's: the seven fields the parse reads — the roles — sit where include/blu_pipeline.h's blu_table_layout says.  The
-// kernels below are the layout builds of the three above: the same stage, the same column-at-a-time walk over the same device
-// functions (hash_step / hash_finish, NumState, the range checks, taxid_lookup, taxon_verdict, filter_row), the same flags; what
-// differs is where a field begins and ends.  The layout is a kernel argument, the same for every thread: it lives in scalar
-// registers, and every test against it is a vector compare with a scalar operand.
+// ---- where a line's fields are.  The parse reads seven fields of a line, the roles.  In the reference's thirteen columns their
+// places are constants: RefLayout, an empty type, so every test against it folds at compile time.  In a table written with another
+// `-outfmt "6 ..."` list they sit where include/blu_pipeline.h's blu_table_layout says: DevLayout, a kernel
+// argument, the same for every thread — it lives in scalar registers, and every test against it is a vector compare with a
+// scalar operand.  The parser below reads either through lay_n_cols / lay_col / lay_tax_list and is otherwise one text.
 enum : int { ROLE_QUERY = 0, ROLE_ACC = 1, ROLE_TAX = 2, ROLE_PID = 3, ROLE_ALN = 4, ROLE_BS = 5, ROLE_E = 6, N_ROLES = 7 };
 struct DevLayout {               // 48 bytes
     uint32_t n_cols;             // fields a line must have (1 .. 64)
@@ -433,12 +212,18 @@ struct DevLayout {               // 48 bytes
     uint32_t reserved;
     unsigned long long wanted;   // bit t: tab t — the one behind column t — bounds a role field (column t or t + 1 holds a role)
 };
+struct RefLayout {};             // mod.rs:134-244: 13 columns, the roles in columns 0 .. 4, the e-value in 11, the bit score in 12
+__device__ constexpr uint32_t lay_n_cols(const RefLayout&) { return 13; }
+__device__ constexpr uint32_t lay_n_cols(const DevLayout& L) { return L.n_cols; }
+__device__ constexpr uint32_t lay_col(const RefLayout&, int r) { return r == ROLE_BS ? 12u : r == ROLE_E ? 11u : (uint32_t)r; }
+__device__ constexpr uint32_t lay_col(const DevLayout& L, int r) { return L.col[r]; }
+__device__ constexpr bool lay_tax_list(const RefLayout&) { return false; }
+__device__ constexpr bool lay_tax_list(const DevLayout& L) { return L.tax_list != 0; }
 
-// ---- 2a'. the query cover: a fifth threshold of the keep word, on fields the seven roles do not include — one
-// column (`qcovhsp` or `qcovs`: BLAST's integer percent) or three (`qstart`, `qend`, `qlen`: the exact ratio).  The cover builds
-// of the layout kernels (PARSE_QCOV, PARSE_QCOV_TAXA) take the layout with the cover behind it, DevLayoutCover; the six builds
-// above take DevLayout and compile to what they were.  `wanted` also names the tab in front of every cover field.
-enum : int { PARSE_QCOV = 3, PARSE_QCOV_TAXA = 4 };
+// ---- the query cover: a fifth threshold of the keep word, on fields the seven roles do not include — one
+// column (`qcovhsp` or `qcovs`: BLAST's integer percent) or three (`qstart`, `qend`, `qlen`: the exact ratio).  A cover build
+// takes the layout with the cover behind it, DevLayoutCover: the layout's type says whether a build has a cover (HAS_COVER).
+// `wanted` also names the tab in front of every cover field.
 enum : int { COVER_FIELDS = 3 };
 struct DevCover {
     uint32_t by_len;             // 0: col[0] holds the percent c, kept iff c * 1000 >= p_milli; 1: col = {qstart, qend, qlen},
@@ -449,6 +234,7 @@ struct DevCover {
     unsigned long long* below;   // [HIT_SPREAD] lines below the cover, whatever the other filters say (spread over blocks)
 };
 struct DevLayoutCover : DevLayout { DevCover cov; };
+template <class LAY> constexpr bool HAS_COVER = std::is_same<LAY, DevLayoutCover>::value;
 
 // One cover field, already read: an Int64 field (no fraction, no exponent — else FB_NUMBER and the host parser's error) in
 // 0 .. 2^31 - 1 (else FB_RANGE, likewise).  NumState::value has the integer exactly: at most 15 digits.
@@ -468,34 +254,70 @@ __device__ __forceinline__ bool cover_verdict(const DevCover& c, const double v[
     return true;
 }
 
-// The general form under a layout: parse_row_general_body with the column tests against the layout, the line walked up to the
-// end of column n_cols - 1, and a `staxids` field fed to the number reader up to its first ';' only.
+// ---- the parser: two forms (general, staged) over one tail, each a template on MODE and on the layout's type.
+// PARSE_PLAIN: every unfiltered call; flt is null and unmatched rows are counted here.  PARSE_FILTER: the e-value field is read
+// when its threshold is on, the thresholds are evaluated on the parsed values and every line gets a keep word (filter_row);
+// unmatched rows are counted over the kept rows, after the compaction.  PARSE_TAXA: as PARSE_FILTER with the taxon verdict
+// (taxon_verdict) taken first; the thresholds may all be off, as they may under a cover alone.
+enum : int { PARSE_PLAIN = 0, PARSE_FILTER = 1, PARSE_TAXA = 2 };
+
+struct RowValues {               // what a line's fields read as, before finish_row's checks
+    double tax = 0, pid = 0, aln = 0, bs = 0, cov[COVER_FIELDS] = {0, 0, 0};
+    unsigned long long e_mant = 0;   // the e-value field, read only under its threshold: e_value_verdict's operands
+    int e_exp = 0;
+    bool e_neg = false;
+};
+
+// The tail of both forms, on a line whose fields all read well: the 32-bit range checks, the truncation of the bit score, the
+// cover's verdict and count (ahead of the taxon verdict's early-out: it is counted whatever the other filters say), the taxid
+// join, the line's keep word — a line the taxon filter or the cover removes never has its e-value looked at — or, in the
+// unfiltered builds, the unmatched count; then the four value columns.  false: the line set FB_RANGE and nothing was stored.
 template <int MODE, class LAY>
-__device__ __noinline__ void parse_row_general_layout(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
-                                                      const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
-                                                      unsigned long long* __restrict__ n_unmatched, const DevFilter* flt, const LAY L) {
-    constexpr bool FILTER = MODE != PARSE_PLAIN;
-    constexpr bool TAXA = MODE == PARSE_TAXA || MODE == PARSE_QCOV_TAXA, COVER = MODE == PARSE_QCOV || MODE == PARSE_QCOV_TAXA;
+__device__ __forceinline__ bool finish_row(const LAY& L, uint32_t i, const RowValues& v, const DevTaxidMap& taxmap, const RowOut& o,
+                                           uint32_t* __restrict__ flags, unsigned long long* __restrict__ n_unmatched, const DevFilterTaxa* flt) {
+    static_assert(MODE != PARSE_PLAIN || !HAS_COVER<LAY>, "a cover leaves a keep word: it needs a filtered build");
+    // mod.rs:184 AnyValue::Float64 -> try_extract::<i64> (truncation); the engine columns are 32-bit
+    const double bs_t = trunc(v.bs);
+    if (!(bs_t >= -2147483648.0 && bs_t <= 2147483647.0) || !(v.aln >= -2147483648.0 && v.aln <= 2147483647.0) ||
+        !(v.tax >= -9.2e18 && v.tax <= 9.2e18)) { atomicOr(flags, FB_RANGE); return false; }
+    bool below = false;
+    if constexpr (HAS_COVER<LAY>) if (!cover_verdict(L.cov, v.cov, &below)) { atomicOr(flags, FB_RANGE); return false; }
+    const uint32_t row = taxid_lookup(taxmap, (long long)v.tax);   // left join (mod.rs:72-76)
+    if constexpr (MODE == PARSE_PLAIN) { if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull); }
+    else {
+        bool drop = below;
+        if constexpr (MODE == PARSE_TAXA) drop = taxon_verdict(flt->t, row) || below;
+        if (drop) flt->f.keep[i] = KEEP_NO;
+        else filter_row(flt->f, i, v.pid, v.aln, v.bs, v.e_mant, v.e_exp, v.e_neg);
+    }
+    o.tax[i] = row; o.pid[i] = v.pid; o.aln[i] = (int32_t)v.aln; o.bs[i] = (int32_t)bs_t;
+    return true;
+}
+
+// The general form: one line, read from global memory a byte at a time through one state machine for all its columns, up to the
+// end of column n_cols - 1.  It takes any line length: the staged form below hands it the blocks whose 256 lines do not fit the
+// LDS stage.  A `staxids` field is fed to the number reader up to its first ';' only.
+template <int MODE, class LAY>
+__device__ __noinline__ void parse_row_general(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t i,
+                                               const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
+                                               unsigned long long* __restrict__ n_unmatched, const DevFilterTaxa* flt, const LAY L) {
+    constexpr bool FILTER = MODE != PARSE_PLAIN, COVER = HAS_COVER<LAY>;
     const uint64_t p = line_start[i];
     uint64_t e = line_start[i + 1] - 1;                 // the newline (or one past the end of a last line without one)
     if (e > p && text[e - 1] == '\r') --e;
     if (e <= p) { atomicOr(flags, FB_EMPTY_LINE); return; }
-    const uint32_t n_cols = L.n_cols, c_q = L.col[ROLE_QUERY], c_a = L.col[ROLE_ACC], c_tax = L.col[ROLE_TAX], c_pid = L.col[ROLE_PID],
-                   c_aln = L.col[ROLE_ALN], c_bs = L.col[ROLE_BS];
+    const uint32_t n_cols = lay_n_cols(L), c_q = lay_col(L, ROLE_QUERY), c_a = lay_col(L, ROLE_ACC), c_tax = lay_col(L, ROLE_TAX),
+                   c_pid = lay_col(L, ROLE_PID), c_aln = lay_col(L, ROLE_ALN), c_bs = lay_col(L, ROLE_BS);
     uint32_t c_e = 0xFFFFFFFFu;                         // (the e-value column, when its threshold is on)
-    if constexpr (FILTER) if ((flt->mask & BLU_FILTER_MAX_E_VALUE) && L.col[ROLE_E] < n_cols) c_e = L.col[ROLE_E];
+    if constexpr (FILTER) if ((flt->f.mask & BLU_FILTER_MAX_E_VALUE) && lay_col(L, ROLE_E) < n_cols) c_e = lay_col(L, ROLE_E);
     uint32_t col = 0;
     uint64_t fstart = p;                                // start of the current field
     unsigned long long h = 1469598103934665603ull;
     NumState num;
     num.reset();
     bool cut = false;                                   // behind the first ';' of a `staxids` field
-    double v_tax = 0, v_pid = 0, v_aln = 0, v_bs = 0;
+    RowValues v;
     uint32_t fb = 0;
-    unsigned long long e_mant = 0;
-    int e_exp = 0;
-    bool e_neg = false;
-    double v_cov[COVER_FIELDS] = {0, 0, 0};
     auto cover_col = [&](uint32_t c) {                  // which cover field column c holds, or -1
         if constexpr (COVER) {
 #pragma unroll
@@ -507,14 +329,16 @@ __device__ __noinline__ void parse_row_general_layout(const unsigned char* __res
         const uint64_t len = fend - fstart;
         if (col == c_q) { o.qh[i] = hash_finish(h, (uint32_t)len); o.qpos[i] = fstart | (len << 44); if (len >= (1u << 20)) fb |= FB_COLUMNS; }
         else if (col == c_a) { o.ah[i] = hash_finish(h, (uint32_t)len); o.apos[i] = fstart | (len << 44); if (len >= (1u << 20)) fb |= FB_COLUMNS; }
-        else if (col == c_tax) { if (!num.value(&v_tax) || num.seen_dot || num.seen_exp) fb |= FB_NUMBER; }   // (Int64 columns, as in the plain form)
-        else if (col == c_pid) { if (!num.value(&v_pid)) fb |= FB_NUMBER; }
-        else if (col == c_aln) { if (!num.value(&v_aln) || num.seen_dot || num.seen_exp) fb |= FB_NUMBER; }
-        else if (col == c_bs) { if (!num.value(&v_bs)) fb |= FB_NUMBER; }
-        else if (FILTER && col == c_e) { if (!num.plain()) fb |= FB_NUMBER; e_mant = num.mant; e_exp = num.exponent(); e_neg = num.neg; }
+        // (subject_taxid and align_length are Int64 columns, mod.rs:226-244: a fraction or an exponent is left to the CPU
+        // parser, which refuses the file as the reference would)
+        else if (col == c_tax) { if (!num.value(&v.tax) || num.seen_dot || num.seen_exp) fb |= FB_NUMBER; }
+        else if (col == c_pid) { if (!num.value(&v.pid)) fb |= FB_NUMBER; }
+        else if (col == c_aln) { if (!num.value(&v.aln) || num.seen_dot || num.seen_exp) fb |= FB_NUMBER; }
+        else if (col == c_bs) { if (!num.value(&v.bs)) fb |= FB_NUMBER; }
+        else if (FILTER && col == c_e) { if (!num.plain()) fb |= FB_NUMBER; v.e_mant = num.mant; v.e_exp = num.exponent(); v.e_neg = num.neg; }
         else if (COVER) {
             const int k = cover_col(col);
-            if (k >= 0) { double v = 0; fb |= cover_field(num, &v); v_cov[0] = k == 0 ? v : v_cov[0]; v_cov[1] = k == 1 ? v : v_cov[1]; v_cov[2] = k == 2 ? v : v_cov[2]; }
+            if (k >= 0) { double x = 0; fb |= cover_field(num, &x); v.cov[0] = k == 0 ? x : v.cov[0]; v.cov[1] = k == 1 ? x : v.cov[1]; v.cov[2] = k == 2 ? x : v.cov[2]; }
         }
         ++col;
         fstart = fend + 1;
@@ -524,8 +348,8 @@ __device__ __noinline__ void parse_row_general_layout(const unsigned char* __res
     };
     // aligned 16-byte loads; bytes outside [p, e) are skipped
     for (uint64_t a = p & ~15ull; a < e && col < n_cols; a += 16) {
-        const uint4 v = *reinterpret_cast<const uint4*>(text + a);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        const uint4 w16 = *reinterpret_cast<const uint4*>(text + a);
+        const uint32_t w[4] = {w16.x, w16.y, w16.z, w16.w};
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             const uint64_t q = a + k;
@@ -533,114 +357,158 @@ __device__ __noinline__ void parse_row_general_layout(const unsigned char* __res
             const uint32_t c = (w[k >> 2] >> (8 * (k & 3))) & 0xFF;
             if (c == '\t') { end_field(q); continue; }
             if (col == c_q || col == c_a) { h = hash_step(h, c); if (c == '"') fb |= FB_QUOTE; }
-            else if (col == c_tax) { if (L.tax_list && c == ';') cut = true; if (!cut) num.feed(c, q == fstart); }
-            else if (col == c_pid || col == c_aln || col == c_bs || (FILTER && col == c_e) || (COVER && cover_col(col) >= 0)) num.feed(c, q == fstart);
+            else if (col == c_tax || col == c_pid || col == c_aln || col == c_bs || (FILTER && col == c_e) || (COVER && cover_col(col) >= 0)) {
+                if (lay_tax_list(L) && col == c_tax && c == ';') cut = true;
+                if (!cut) num.feed(c, q == fstart);     // (one feed for every numeric column: the 16 unrolled copies of this body are the form's size)
+            }
         }
     }
     if (col < n_cols) end_field(e);                     // the last field ends with the line
     if (col < n_cols) fb |= FB_COLUMNS;
     if (fb) { atomicOr(flags, fb); return; }
-    const double bs_t = trunc(v_bs);
-    if (!(bs_t >= -2147483648.0 && bs_t <= 2147483647.0) || !(v_aln >= -2147483648.0 && v_aln <= 2147483647.0) ||
-        !(v_tax >= -9.2e18 && v_tax <= 9.2e18)) { atomicOr(flags, FB_RANGE); return; }
-    bool below = false;                                 // (the cover's verdict and count: ahead of the taxon verdict's early-out)
-    if constexpr (COVER) if (!cover_verdict(L.cov, v_cov, &below)) { atomicOr(flags, FB_RANGE); return; }
-    const uint32_t row = taxid_lookup(taxmap, (long long)v_tax);   // left join (mod.rs:72-76)
-    if constexpr (TAXA) {
-        if (taxon_verdict(reinterpret_cast<const DevFilterTaxa*>(flt)->t, row) || below) flt->keep[i] = KEEP_NO;
-        else filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
-    } else if constexpr (COVER) {
-        if (below) flt->keep[i] = KEEP_NO;              // (its e-value is never looked at)
-        else filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
-    } else if constexpr (FILTER) filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
-    else if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull);
-    o.tax[i] = row; o.pid[i] = v_pid; o.aln[i] = (int32_t)v_aln; o.bs[i] = (int32_t)bs_t;
+    finish_row<MODE>(L, i, v, taxmap, o, flags, n_unmatched, flt);
 }
 
-// The staged form under a layout: parse_rows_body with (1) a tab scan that walks the line's tabs up to the end of column
-// n_cols - 1 — a shorter line is FB_COLUMNS, as a line of fewer than 13 columns is above — and leaves in LDS only the bounds of
-// the role fields, begin and end per role and thread: 2 x 7 x 256 x 2 = 7 KB beside the 32 KB stage whatever the column count
-// (one word per column would be 64 x 256 x 2 = 32 KB more); (2) the same walk over the role fields, one role at a time.
-// A thread reads back only what it wrote itself: no barrier between (1) and (2).
-// The cover builds keep of a cover field only its begin, and in a register, not in LDS: the three 16-bit
-// positions share one 64-bit word, set at the tab `wanted` names in front of the field; the field ends at the next tab or with
-// the line, which the short walk over its digits finds for itself.  LDS stays at the 39 936 B of the other layout builds.
+// ---- the staged form's field providers.  After the stage a thread finds the tabs of its line and leaves in LDS what tells it
+// where a role's field begins and ends; this is the one part that differs between the reference's columns and a layout, and
+// everything behind it is written against begin(role) / end(role).  A thread reads back only what it wrote: no barrier.
+constexpr uint32_t STAGE_BYTES = 32768;
+constexpr int PARSE_THREADS = 256;
+
+// bit 7 of every byte of the staged word at a (a multiple of 4) that is a tab inside [p, e): four bytes per compare, the exact
+// zero-byte test on word ^ 0x09090909, bytes outside the line masked off
+__device__ __forceinline__ uint32_t tab_mask(const uint32_t* sw, uint32_t a, uint32_t p, uint32_t e) {
+    const uint32_t x = sw[a >> 2] ^ 0x09090909u;
+    uint32_t m = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
+    if (a < p) m &= 0xFFFFFFFFu << (8 * (p - a));
+    if (e - a < 4) m &= (1u << (8 * (e - a))) - 1u;
+    return m;
+}
+
+// The reference's columns: the positions of the line's first 13 tabs, [column][thread], 13 x 256 x 2 = 6.5 KB; a role's bounds
+// are the tabs around its constant column.  It keeps a scan of its own because this one has no test inside its loop — every tab
+// is stored where its count says — while the layout's asks `wanted` and seven columns at every tab: 11 ms against 12 ms on the
+// same 100 M lines (profiles/outfmt_bench.json), and this is the kernel of every call without --blast-outfmt.
+struct RefFields {
+    static constexpr int LDS_WORDS = 13 * PARSE_THREADS;
+    const uint16_t* mine;
+    uint32_t p, e, n_tabs;
+    __device__ __forceinline__ bool scan(const RefLayout&, const uint32_t* sw, uint32_t p_, uint32_t e_, uint16_t* lds) {
+        mine = lds; p = p_; e = e_; n_tabs = 0;
+        for (uint32_t a = p & ~3u; a < e && n_tabs < 13; a += 4) {
+            uint32_t m = tab_mask(sw, a, p, e);
+            while (m && n_tabs < 13) {
+                lds[n_tabs * PARSE_THREADS] = (uint16_t)(a + ((uint32_t)__builtin_ctz(m) >> 3));
+                ++n_tabs;
+                m &= m - 1;
+            }
+        }
+        return n_tabs >= 12;                                         // (false: fewer than 13 columns)
+    }
+    __device__ __forceinline__ uint32_t tab(uint32_t c) const { return (uint32_t)mine[c * PARSE_THREADS]; }
+    __device__ __forceinline__ uint32_t begin(int r) const { const uint32_t c = lay_col(RefLayout{}, r); return c == 0 ? p : tab(c - 1) + 1; }
+    // (the bit score ends at the 13th tab, or with the line when there is none)
+    __device__ __forceinline__ uint32_t end(int r) const { const uint32_t c = lay_col(RefLayout{}, r); return c == 12 && n_tabs < 13 ? e : tab(c); }
+};
+
+// A layout: the scan walks the line's tabs up to the end of column n_cols - 1 — the field count has to be checked — but acts only
+// at a tab `wanted` names, and leaves in LDS only the bounds of the role fields, begin and end per role and thread: 2 x 7 x 256 x
+// 2 = 7 KB beside the 32 KB stage whatever the column count (one word per column would be 64 x 256 x 2 = 32 KB more).
+// Of a cover field it keeps only the begin, and in a register, not in LDS: the three 16-bit positions share one
+// 64-bit word; the field ends at the next tab or with the line, which the short walk over its digits finds for itself.  LDS
+// stays at 39 936 B with or without a cover.
+template <class LAY>
+struct LayoutFields {
+    static constexpr int LDS_WORDS = 2 * N_ROLES * PARSE_THREADS;    // [role][begin, end][thread]
+    uint16_t* mine;
+    unsigned long long cov_at;                                       // begin of cover field k: bits 16 k .. 16 k + 15
+    __device__ __forceinline__ void set_begin(int r, uint32_t at) { mine[(2 * r) * PARSE_THREADS] = (uint16_t)at; }
+    __device__ __forceinline__ void set_end(int r, uint32_t at) { mine[(2 * r + 1) * PARSE_THREADS] = (uint16_t)at; }
+    __device__ __forceinline__ uint32_t begin(int r) const { return (uint32_t)mine[(2 * r) * PARSE_THREADS]; }
+    __device__ __forceinline__ uint32_t end(int r) const { return (uint32_t)mine[(2 * r + 1) * PARSE_THREADS]; }
+    __device__ __forceinline__ uint32_t cover_begin(int k) const { return (uint32_t)(cov_at >> (16 * k)) & 0xFFFFu; }
+    // tab t ends column t and column t + 1 begins behind it
+    __device__ __forceinline__ bool scan(const LAY& L, const uint32_t* sw, uint32_t p, uint32_t e, uint16_t* lds) {
+        mine = lds; cov_at = 0;
+        const uint32_t n_cols = L.n_cols;
+#pragma unroll
+        for (int r = 0; r < N_ROLES; ++r) if (L.col[r] == 0) set_begin(r, p);
+        if constexpr (HAS_COVER<LAY>) {
+#pragma unroll
+            for (int k = 0; k < COVER_FIELDS; ++k) if (L.cov.col[k] == 0) cov_at |= (unsigned long long)p << (16 * k);
+        }
+        uint32_t n_tabs = 0;
+        for (uint32_t a = p & ~3u; a < e && n_tabs < n_cols; a += 4) {
+            uint32_t m = tab_mask(sw, a, p, e);
+            while (m && n_tabs < n_cols) {
+                if ((L.wanted >> n_tabs) & 1ull) {
+                    const uint32_t at = a + ((uint32_t)__builtin_ctz(m) >> 3);
+#pragma unroll
+                    for (int r = 0; r < N_ROLES; ++r) {
+                        if (L.col[r] == n_tabs) set_end(r, at);
+                        if (L.col[r] == n_tabs + 1) set_begin(r, at + 1);
+                    }
+                    if constexpr (HAS_COVER<LAY>) {
+#pragma unroll
+                        for (int k = 0; k < COVER_FIELDS; ++k) if (L.cov.col[k] == n_tabs + 1) cov_at |= (unsigned long long)(at + 1) << (16 * k);
+                    }
+                }
+                ++n_tabs;
+                m &= m - 1;
+            }
+        }
+        if (n_tabs + 1 < n_cols) return false;                       // fewer columns than the layout names
+        if (n_tabs + 1 == n_cols) {                                  // the layout's last column ends with the line
+#pragma unroll
+            for (int r = 0; r < N_ROLES; ++r) if (L.col[r] == n_cols - 1) set_end(r, e);
+        }
+        return true;
+    }
+};
+
+// The staged form, the parse kernel proper: a block takes 256 consecutive lines, whose text is one contiguous span of the file
+// (17 KB for BLAST's usual 67-byte lines).  The span is staged in LDS with coalesced 16-byte loads; every lane then (1) finds the
+// tabs of its line with word-wide compares (the field provider), (2) walks the fields the engine reads ONE FIELD AT A TIME, so
+// that the 64 lanes of a wave are in the same field and the same branch of the same small loop: the general form spends its
+// time in divergence (a wave has lanes in every column at once and runs the end-of-field code of all of them at nearly every
+// byte) and in instruction fetch (its 16-byte unrolled body does not fit the instruction cache).  Same grammar, same hashes,
+// same flags as the general form; a block whose span exceeds the stage (lines of 128 bytes and more on average) is parsed by it.
 template <int MODE, class LAY>
-__device__ __forceinline__ void parse_rows_layout_body(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t n_rows,
-                                                       const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
-                                                       unsigned long long* __restrict__ n_unmatched, const DevFilter* flt, const LAY& L) {
-    constexpr bool FILTER = MODE != PARSE_PLAIN;
-    constexpr bool TAXA = MODE == PARSE_TAXA || MODE == PARSE_QCOV_TAXA, COVER = MODE == PARSE_QCOV || MODE == PARSE_QCOV_TAXA;
+__device__ __forceinline__ void parse_rows_body(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t n_rows,
+                                                const DevTaxidMap& taxmap, const RowOut& o, uint32_t* __restrict__ flags,
+                                                unsigned long long* __restrict__ n_unmatched, const DevFilterTaxa* flt, const LAY& L) {
+    using Fields = std::conditional_t<std::is_same<LAY, RefLayout>::value, RefFields, LayoutFields<LAY>>;
     __shared__ uint4 stage16[STAGE_BYTES / 16];
-    __shared__ uint16_t field_at[2 * N_ROLES * PARSE_THREADS];       // [role][begin, end][thread]
+    __shared__ uint16_t field_at[Fields::LDS_WORDS];
     const uint32_t r0 = blockIdx.x * PARSE_THREADS, r1 = min(r0 + (uint32_t)PARSE_THREADS, n_rows), i = r0 + threadIdx.x;
+    // (the four line starts travel together: two round trips to memory per block — these, then the text — and no more)
     const uint64_t ls0 = line_start[r0], s1 = line_start[r1];       // (line_start[n_rows] = one past the last newline, or size + 1)
     const uint64_t my_p = line_start[min(i, r1 - 1)], my_e = line_start[min(i, r1 - 1) + 1];
     const uint64_t s0 = ls0 & ~15ull;
     if (s1 - s0 > STAGE_BYTES) {                                     // uniform over the block
-        if (i < r1) parse_row_general_layout<MODE>(text, line_start, i, taxmap, o, flags, n_unmatched, flt, L);
+        if (i < r1) parse_row_general<MODE>(text, line_start, i, taxmap, o, flags, n_unmatched, flt, L);
         return;
     }
     {
         const uint32_t n16 = (uint32_t)((s1 - s0 + 15) >> 4);        // (reads at most 15 bytes past s1 <= size + 1: inside the 64 bytes of padding)
         const uint4* src = reinterpret_cast<const uint4*>(text + s0);
         constexpr int PER_THREAD = STAGE_BYTES / 16 / PARSE_THREADS; // all of a thread's loads are in flight before the first is stored
-        uint4 v[PER_THREAD];
+        uint4 w[PER_THREAD];
 #pragma unroll
-        for (int j = 0; j < PER_THREAD; ++j) { const uint32_t k = threadIdx.x + (uint32_t)j * PARSE_THREADS; v[j] = src[min(k, n16 - 1)]; }
+        for (int j = 0; j < PER_THREAD; ++j) { const uint32_t k = threadIdx.x + (uint32_t)j * PARSE_THREADS; w[j] = src[min(k, n16 - 1)]; }
 #pragma unroll
-        for (int j = 0; j < PER_THREAD; ++j) { const uint32_t k = threadIdx.x + (uint32_t)j * PARSE_THREADS; if (k < n16) stage16[k] = v[j]; }
+        for (int j = 0; j < PER_THREAD; ++j) { const uint32_t k = threadIdx.x + (uint32_t)j * PARSE_THREADS; if (k < n16) stage16[k] = w[j]; }
     }
     __syncthreads();
     if (i >= r1) return;
     const unsigned char* sb = reinterpret_cast<const unsigned char*>(stage16);
-    const uint32_t* sw = reinterpret_cast<const uint32_t*>(stage16);
     const uint32_t p = (uint32_t)(my_p - s0);
     uint32_t e = (uint32_t)(my_e - 1 - s0);                          // the newline (or one past the end of a last line without one)
     if (e > p && sb[e - 1] == '\r') --e;
     if (e <= p) { atomicOr(flags, FB_EMPTY_LINE); return; }
-    uint16_t* const mine = field_at + threadIdx.x;
-    auto set_begin = [&](int r, uint32_t at) { mine[(2 * r) * PARSE_THREADS] = (uint16_t)at; };
-    auto set_end = [&](int r, uint32_t at) { mine[(2 * r + 1) * PARSE_THREADS] = (uint16_t)at; };
-    auto begin_of = [&](int r) { return (uint32_t)mine[(2 * r) * PARSE_THREADS]; };
-    auto end_of = [&](int r) { return (uint32_t)mine[(2 * r + 1) * PARSE_THREADS]; };
-    // ---- (1) the tabs, four bytes per compare as above; tab t ends column t and column t + 1 begins behind it
-    const uint32_t n_cols = L.n_cols;
-#pragma unroll
-    for (int r = 0; r < N_ROLES; ++r) if (L.col[r] == 0) set_begin(r, p);
-    unsigned long long cov_at = 0;                                   // begin of cover field k: bits 16 k .. 16 k + 15
-    if constexpr (COVER) {
-#pragma unroll
-        for (int k = 0; k < COVER_FIELDS; ++k) if (L.cov.col[k] == 0) cov_at |= (unsigned long long)p << (16 * k);
-    }
-    uint32_t n_tabs = 0;
-    for (uint32_t a = p & ~3u; a < e && n_tabs < n_cols; a += 4) {
-        const uint32_t x = sw[a >> 2] ^ 0x09090909u;
-        uint32_t m = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);   // bit 7 of every byte that is a tab
-        if (a < p) m &= 0xFFFFFFFFu << (8 * (p - a));
-        if (e - a < 4) m &= (1u << (8 * (e - a))) - 1u;
-        while (m && n_tabs < n_cols) {
-            if ((L.wanted >> n_tabs) & 1ull) {
-                const uint32_t at = a + ((uint32_t)__builtin_ctz(m) >> 3);
-#pragma unroll
-                for (int r = 0; r < N_ROLES; ++r) {
-                    if (L.col[r] == n_tabs) set_end(r, at);
-                    if (L.col[r] == n_tabs + 1) set_begin(r, at + 1);
-                }
-                if constexpr (COVER) {
-#pragma unroll
-                    for (int k = 0; k < COVER_FIELDS; ++k) if (L.cov.col[k] == n_tabs + 1) cov_at |= (unsigned long long)(at + 1) << (16 * k);
-                }
-            }
-            ++n_tabs;
-            m &= m - 1;
-        }
-    }
-    if (n_tabs + 1 < n_cols) { atomicOr(flags, FB_COLUMNS); return; }   // fewer columns than the layout names
-    if (n_tabs + 1 == n_cols) {                                      // the layout's last column ends with the line
-#pragma unroll
-        for (int r = 0; r < N_ROLES; ++r) if (L.col[r] == n_cols - 1) set_end(r, e);
-    }
+    // ---- (1) the tabs
+    Fields f;
+    if (!f.scan(L, reinterpret_cast<const uint32_t*>(stage16), p, e, field_at + threadIdx.x)) { atomicOr(flags, FB_COLUMNS); return; }
     uint32_t fb = 0;
     // ---- (2) query and accession: FNV-1a over the field, as in the general form
     auto hash_field = [&](uint32_t s, uint32_t t) {
@@ -648,93 +516,77 @@ __device__ __forceinline__ void parse_rows_layout_body(const unsigned char* __re
         for (uint32_t q = s; q < t; ++q) { const uint32_t c = sb[q]; h = hash_step(h, c); if (c == '"') fb |= FB_QUOTE; }
         return hash_finish(h, t - s);
     };
-    const uint32_t q0 = begin_of(ROLE_QUERY), q1 = end_of(ROLE_QUERY), a0 = begin_of(ROLE_ACC), a1 = end_of(ROLE_ACC);
+    const uint32_t q0 = f.begin(ROLE_QUERY), q1 = f.end(ROLE_QUERY), a0 = f.begin(ROLE_ACC), a1 = f.end(ROLE_ACC);
     const unsigned long long qh = hash_field(q0, q1), ah = hash_field(a0, a1);
     // ---- the four numbers; list: the field is `staxids`, the number ends at its first ';'
-    auto number = [&](int r, bool integer, bool list, double* v) {
+    auto number = [&](int r, bool integer, bool list, double* x) {
         NumState num;
         num.reset();
-        const uint32_t s = begin_of(r), t = end_of(r);
+        const uint32_t s = f.begin(r), t = f.end(r);
         for (uint32_t q = s; q < t; ++q) { const uint32_t c = sb[q]; if (list && c == ';') break; num.feed(c, q == s); }
-        if (!num.value(v) || (integer && (num.seen_dot || num.seen_exp))) fb |= FB_NUMBER;
+        if (!num.value(x) || (integer && (num.seen_dot || num.seen_exp))) fb |= FB_NUMBER;
     };
-    double v_tax = 0, v_pid = 0, v_aln = 0, v_bs = 0;
-    number(ROLE_TAX, true, L.tax_list != 0, &v_tax);                 // (subject_taxid and align_length are Int64 columns, mod.rs:226-244)
-    number(ROLE_PID, false, false, &v_pid);
-    number(ROLE_ALN, true, false, &v_aln);
-    number(ROLE_BS, false, false, &v_bs);
-    unsigned long long e_mant = 0;
-    int e_exp = 0;
-    bool e_neg = false;
-    if constexpr (FILTER) {
-        if ((flt->mask & BLU_FILTER_MAX_E_VALUE) && L.col[ROLE_E] < n_cols) {   // the e-value column, read only under its threshold
+    RowValues v;
+    number(ROLE_TAX, true, lay_tax_list(L), &v.tax);                 // (subject_taxid and align_length are Int64 columns, mod.rs:226-244)
+    number(ROLE_PID, false, false, &v.pid);
+    number(ROLE_ALN, true, false, &v.aln);
+    number(ROLE_BS, false, false, &v.bs);
+    if constexpr (MODE != PARSE_PLAIN) {
+        if ((flt->f.mask & BLU_FILTER_MAX_E_VALUE) && lay_col(L, ROLE_E) < lay_n_cols(L)) {   // the e-value column, read only under its threshold
             NumState num;
             num.reset();
-            const uint32_t s = begin_of(ROLE_E), t = end_of(ROLE_E);
+            const uint32_t s = f.begin(ROLE_E), t = f.end(ROLE_E);
             for (uint32_t q = s; q < t; ++q) num.feed(sb[q], q == s);
             if (!num.plain()) fb |= FB_NUMBER;
-            e_mant = num.mant; e_exp = num.exponent(); e_neg = num.neg;
+            v.e_mant = num.mant; v.e_exp = num.exponent(); v.e_neg = num.neg;
         }
     }
-    double v_cov[COVER_FIELDS] = {0, 0, 0};
-    if constexpr (COVER) {                                           // the cover fields: from their begin to the next tab or the line's end
+    if constexpr (HAS_COVER<LAY>) {                                  // the cover fields: from their begin to the next tab or the line's end
 #pragma unroll
         for (int k = 0; k < COVER_FIELDS; ++k) {
             if (k >= (int)L.cov.n_fields) continue;
             NumState num;
             num.reset();
-            const uint32_t s = (uint32_t)(cov_at >> (16 * k)) & 0xFFFFu;
+            const uint32_t s = f.cover_begin(k);
             for (uint32_t q = s; q < e; ++q) { const uint32_t c = sb[q]; if (c == '\t') break; num.feed(c, q == s); }
-            fb |= cover_field(num, &v_cov[k]);
+            fb |= cover_field(num, &v.cov[k]);
         }
     }
     if (fb) { atomicOr(flags, fb); return; }
-    const double bs_t = trunc(v_bs);                                // mod.rs:184 AnyValue::Float64 -> try_extract::<i64> (truncation)
-    if (!(bs_t >= -2147483648.0 && bs_t <= 2147483647.0) || !(v_aln >= -2147483648.0 && v_aln <= 2147483647.0) ||
-        !(v_tax >= -9.2e18 && v_tax <= 9.2e18)) { atomicOr(flags, FB_RANGE); return; }
-    bool below = false;                                             // (the cover's verdict and count: ahead of the taxon verdict's early-out)
-    if constexpr (COVER) if (!cover_verdict(L.cov, v_cov, &below)) { atomicOr(flags, FB_RANGE); return; }
-    const uint32_t row = taxid_lookup(taxmap, (long long)v_tax);   // left join (mod.rs:72-76)
-    if constexpr (TAXA) {
-        if (taxon_verdict(reinterpret_cast<const DevFilterTaxa*>(flt)->t, row) || below) flt->keep[i] = KEEP_NO;
-        else filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
-    } else if constexpr (COVER) {
-        if (below) flt->keep[i] = KEEP_NO;                          // (its e-value is never looked at)
-        else filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
-    } else if constexpr (FILTER) filter_row(*flt, i, v_pid, v_aln, v_bs, e_mant, e_exp, e_neg);
-    else if (row == BLU_UNMATCHED_TAXID) atomicAdd(n_unmatched, 1ull);
+    if (!finish_row<MODE>(L, i, v, taxmap, o, flags, n_unmatched, flt)) return;
     o.qh[i] = qh; o.qpos[i] = (s0 + q0) | ((unsigned long long)(q1 - q0) << 44);
     o.ah[i] = ah; o.apos[i] = (s0 + a0) | ((unsigned long long)(a1 - a0) << 44);
-    o.tax[i] = row; o.pid[i] = v_pid; o.aln[i] = (int32_t)v_aln; o.bs[i] = (int32_t)bs_t;
 }
 
-__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
-                                                                   uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
-                                                                   unsigned long long* __restrict__ n_unmatched, DevLayout lay) {
-    parse_rows_layout_body<PARSE_PLAIN>(text, line_start, n_rows, taxmap, o, flags, n_unmatched, nullptr, lay);
+// The eight builds.  Every one takes the same arguments, then its layout if it has one: n_unmatched is read by the unfiltered
+// builds only, and flt (in device memory: read with scalar loads) is null in them.
+#define PARSE_ARGS const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start, uint32_t n_rows, DevTaxidMap taxmap, RowOut o, \
+                   uint32_t* __restrict__ flags, unsigned long long* __restrict__ n_unmatched, const DevFilterTaxa* __restrict__ flt
+__global__ __launch_bounds__(PARSE_THREADS) void parse_rows(PARSE_ARGS) {
+    parse_rows_body<PARSE_PLAIN>(text, line_start, n_rows, taxmap, o, flags, n_unmatched, flt, RefLayout{});
 }
-__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout_filtered(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
-                                                                            uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
-                                                                            const DevFilter* __restrict__ flt, DevLayout lay) {
-    parse_rows_layout_body<PARSE_FILTER>(text, line_start, n_rows, taxmap, o, flags, nullptr, flt, lay);
+__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_filtered(PARSE_ARGS) {
+    parse_rows_body<PARSE_FILTER>(text, line_start, n_rows, taxmap, o, flags, n_unmatched, flt, RefLayout{});
 }
-__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout_taxa(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
-                                                                        uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
-                                                                        const DevFilterTaxa* __restrict__ flt, DevLayout lay) {
-    parse_rows_layout_body<PARSE_TAXA>(text, line_start, n_rows, taxmap, o, flags, nullptr, &flt->f, lay);
+__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_taxa(PARSE_ARGS) {
+    parse_rows_body<PARSE_TAXA>(text, line_start, n_rows, taxmap, o, flags, n_unmatched, flt, RefLayout{});
 }
-
-// the cover builds: the thresholds of the filter may all be off (a cover alone), as under a taxon filter alone
-__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout_qcov(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
-                                                                        uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
-                                                                        const DevFilter* __restrict__ flt, DevLayoutCover lay) {
-    parse_rows_layout_body<PARSE_QCOV>(text, line_start, n_rows, taxmap, o, flags, nullptr, flt, lay);
+__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout(PARSE_ARGS, DevLayout lay) {
+    parse_rows_body<PARSE_PLAIN>(text, line_start, n_rows, taxmap, o, flags, n_unmatched, flt, lay);
 }
-__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout_qcov_taxa(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
-                                                                             uint32_t n_rows, DevTaxidMap taxmap, RowOut o, uint32_t* __restrict__ flags,
-                                                                             const DevFilterTaxa* __restrict__ flt, DevLayoutCover lay) {
-    parse_rows_layout_body<PARSE_QCOV_TAXA>(text, line_start, n_rows, taxmap, o, flags, nullptr, &flt->f, lay);
+__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout_filtered(PARSE_ARGS, DevLayout lay) {
+    parse_rows_body<PARSE_FILTER>(text, line_start, n_rows, taxmap, o, flags, n_unmatched, flt, lay);
 }
+__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout_taxa(PARSE_ARGS, DevLayout lay) {
+    parse_rows_body<PARSE_TAXA>(text, line_start, n_rows, taxmap, o, flags, n_unmatched, flt, lay);
+}
+__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout_qcov(PARSE_ARGS, DevLayoutCover lay) {
+    parse_rows_body<PARSE_FILTER>(text, line_start, n_rows, taxmap, o, flags, n_unmatched, flt, lay);
+}
+__global__ __launch_bounds__(PARSE_THREADS, 4) void parse_rows_layout_qcov_taxa(PARSE_ARGS, DevLayoutCover lay) {
+    parse_rows_body<PARSE_TAXA>(text, line_start, n_rows, taxmap, o, flags, n_unmatched, flt, lay);
+}
+#undef PARSE_ARGS
 
 // ---- 2b. hit filter: the e-values left to the host, and the stable compaction of the parsed rows ---------------------------
 // rows whose keep word is KEEP_ASK_HOST, in any order, each with the place of its e-value field (field offset | length << 44);
@@ -1068,7 +920,7 @@ struct GpuIngest {
     int32_t *d_aln = nullptr, *d_bs = nullptr;
     // a filtered parse -> drop_filtered_rows: the keep words, the filter and the row codes as the kernel read them, the counts
     uint32_t* d_keep = nullptr;
-    DevFilterTaxa* d_filter = nullptr;                   // (its first member is the DevFilter parse_rows_filtered reads)
+    DevFilterTaxa* d_filter = nullptr;                   // (null without a filter; .t unused without a taxon filter)
     uint16_t* d_code = nullptr;
     std::vector<unsigned long long> back;
     // accession_dictionary_begin -> accession_dictionary_finish: the table, its slots, the slot of every distinct accession
@@ -1215,8 +1067,9 @@ struct GpuIngest {
         return d;
     }
 
-    // ---- parse: one of the three builds of parse_rows, or under a column layout of parse_rows_layout.  Under a
-    // filter it leaves a keep word per line, and its counts come back with the flags in `back`
+    // ---- parse: one of the eight builds of the parse kernel, by the table's layout (none, one, one with a cover: DESIGN.md §23,
+    // §24) and by the filter (none, thresholds, a taxon filter: DESIGN.md §14, §16).  Under a filter it leaves a keep word per
+    // line, and its counts come back with the flags in `back`
     int parse() {
         TaxidMap::E* d_taxmap = nullptr;
         HIP_CHECK(pol, mem.upload(&d_taxmap, row_of.tab.data(), row_of.tab.size(), "taxid map"));
@@ -1226,39 +1079,32 @@ struct GpuIngest {
         HIP_CHECK(pol, mem.alloc(&d_aln, (size_t)n_rows * 4, "parsed rows")); HIP_CHECK(pol, mem.alloc(&d_bs, (size_t)n_rows * 4, "parsed rows"));
         const RowOut o{d_qh, d_ah, d_qpos, d_apos, d_tax, d_pid, d_aln, d_bs};
         const DevTaxidMap tm{d_taxmap, row_of.tab.size() - 1};
-        const dim3 blocks(grid(n_rows, PARSE_THREADS)), threads(PARSE_THREADS);
         if (lay && flt && (flt->mask & BLU_FILTER_MAX_E_VALUE) && lay->e_value >= lay->n_columns) return fallback("an e-value threshold without an e-value column");
-        const DevLayout dl = lay ? device_layout() : DevLayout{};
         if (cov && !lay) return fallback("a query cover without a column layout");
-        if (!flt && !taxa && !cov) {
-            if (lay) hipLaunchKernelGGL(parse_rows_layout, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, d_big, dl);
-            else hipLaunchKernelGGL(parse_rows, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, d_big);
-            return check_flags();
-        }
-        HIP_CHECK(pol, mem.alloc(&d_keep, (size_t)n_rows * 4, "keep words"));
-        HIP_CHECK(pol, mem.alloc(&d_filter, sizeof(DevFilterTaxa), "hit filter"));
-        unsigned long long* const d_fcnt = reinterpret_cast<unsigned long long*>(d_flags + 16);
-        DevFilterTaxa hf{};
-        if (flt) hf.f = device_filter(*flt);                         // (no threshold beside a taxon filter: an empty mask keeps every line)
-        hf.f.keep = d_keep; hf.f.counts = d_fcnt;
-        // under a cover: the cover builds of the layout kernels, whose layout argument carries it
-        const DevLayoutCover dlc = cov ? device_layout_cover(d_fcnt + HIT_SPREAD + 1 + n_taxa_back()) : DevLayoutCover{};
-        if (!taxa) {
-            HIP_CHECK(pol, hipMemcpy(d_filter, &hf.f, sizeof hf.f, hipMemcpyHostToDevice));
-            if (cov) hipLaunchKernelGGL(parse_rows_layout_qcov, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilter*)&d_filter->f, dlc);
-            else if (lay) hipLaunchKernelGGL(parse_rows_layout_filtered, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilter*)&d_filter->f, dl);
-            else hipLaunchKernelGGL(parse_rows_filtered, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilter*)&d_filter->f);
-        } else {
-            // the row codes go up next to the taxid map; the verdict is taken in the parse
-            const size_t n_tax = taxa->code.size();
-            HIP_CHECK(pol, mem.upload(&d_code, taxa->code.data(), n_tax, "taxon codes"));
-            hf.t.code = d_code; hf.t.n_tax = (uint32_t)n_tax; hf.t.unmatched = taxa->unmatched;
-            hf.t.not_only = d_fcnt + HIT_SPREAD + 1; hf.t.excluded_by = hf.t.not_only + HIT_SPREAD;
+        const bool filtered = flt || taxa || cov;
+        unsigned long long* const d_fcnt = reinterpret_cast<unsigned long long*>(d_flags + 16);   // (the filters' counts, behind the big counters)
+        if (filtered) {
+            HIP_CHECK(pol, mem.alloc(&d_keep, (size_t)n_rows * 4, "keep words"));
+            HIP_CHECK(pol, mem.alloc(&d_filter, sizeof(DevFilterTaxa), "hit filter"));
+            DevFilterTaxa hf{};
+            if (flt) hf.f = device_filter(*flt);                     // (no threshold beside a taxon filter or a cover: an empty mask keeps every line)
+            hf.f.keep = d_keep; hf.f.counts = d_fcnt;
+            if (taxa) {                                              // the row codes go up next to the taxid map; the verdict is taken in the parse
+                const size_t n_tax = taxa->code.size();
+                HIP_CHECK(pol, mem.upload(&d_code, taxa->code.data(), n_tax, "taxon codes"));
+                hf.t.code = d_code; hf.t.n_tax = (uint32_t)n_tax; hf.t.unmatched = taxa->unmatched;
+                hf.t.not_only = d_fcnt + HIT_SPREAD + 1; hf.t.excluded_by = hf.t.not_only + HIT_SPREAD;
+            }
             HIP_CHECK(pol, hipMemcpy(d_filter, &hf, sizeof hf, hipMemcpyHostToDevice));
-            if (cov) hipLaunchKernelGGL(parse_rows_layout_qcov_taxa, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilterTaxa*)d_filter, dlc);
-            else if (lay) hipLaunchKernelGGL(parse_rows_layout_taxa, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilterTaxa*)d_filter, dl);
-            else hipLaunchKernelGGL(parse_rows_taxa, blocks, threads, 0, 0, d_text, d_line, n_rows, tm, o, d_flags, (const DevFilterTaxa*)d_filter);
         }
+        // every build takes the same arguments (d_filter is null without a filter), then its layout if it has one
+        auto launch = [&](auto kernel, auto... layout) {
+            hipLaunchKernelGGL(kernel, dim3(grid(n_rows, PARSE_THREADS)), dim3(PARSE_THREADS), 0, 0, d_text, d_line, n_rows, tm, o, d_flags, d_big, d_filter, layout...);
+        };
+        if (cov) launch(taxa ? parse_rows_layout_qcov_taxa : parse_rows_layout_qcov, device_layout_cover(d_fcnt + HIT_SPREAD + 1 + n_taxa_back()));
+        else if (lay) launch(taxa ? parse_rows_layout_taxa : filtered ? parse_rows_layout_filtered : parse_rows_layout, device_layout());
+        else launch(taxa ? parse_rows_taxa : filtered ? parse_rows_filtered : parse_rows);
+        if (!filtered) return check_flags();
         back.resize(n_back());
         HIP_CHECK(pol, hipMemcpy(back.data(), d_flags, n_back() * 8, hipMemcpyDeviceToHost));
         return fall_back_on((uint32_t)back[0]);

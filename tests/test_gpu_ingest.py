@@ -315,6 +315,47 @@ def test_gpu_parser_columns_of_blast_shaped_tables(tmp_path, force_gpu, layout):
     _assert_columns_equal(got, ref.read_table(str(bt), tj))
 
 
+@pytest.mark.parametrize("hit_filter", [None, {"max_e_value": 1e-50, "min_perc_identity": 85.0}], ids=["unfiltered", "hit_filter"])
+def test_the_default_kernel_and_the_layout_kernel_read_the_same_fields(tmp_path, force_gpu, hit_filter):
+    """The parse kernels share one body behind two field providers (csrc/ingest_gpu.hip: RefFields, LayoutFields); the one thing
+    that rests on is that both hand the body the same bounds.  A table in the reference's columns — 300 lines of 70 bytes, then
+    300 of 200, so that the first 256-line block is staged and the second takes the general form — is parsed by the default
+    kernel, and its copy with one dead trailing column by the layout kernel under the matching format string: the grouped
+    columns, the names, the unmatched rows and the kept counts must be identical."""
+    from tests import outfmt_reference as R
+    rng = np.random.default_rng(23)
+    rows = []
+    for i in range(600):
+        t = int(rng.integers(0, 3100))                               # (some taxids are not in the DB)
+        e_txt = "1.00e-50" if i % 11 == 0 else f"{10.0 ** -int(rng.integers(3, 180)):.2e}"   # (the threshold's own spelling: left to the host)
+        rest = (f"\tNR_{t:06d}.1\t{100 + t}\t{80 + int(rng.integers(0, 20001)) / 1000:.3f}\t{int(rng.integers(100, 2000))}"
+                f"\t1\t0\t1\t400\t1\t400\t{e_txt}\t{int(rng.integers(50, 5000))}")
+        name = f"q{i // 3:05d}_"
+        rows.append(name + "x" * ((70 if i < 300 else 200) - 1 - len(name) - len(rest)) + rest)
+    assert {len(r) + 1 for r in rows[:300]} == {70} and {len(r) + 1 for r in rows[300:]} == {200}
+    assert 256 * 70 + 15 <= 32768 < 44 * 70 + 212 * 200               # block 0 fits the 32 KiB stage, block 1 does not
+    bt, wide = tmp_path / "b.tsv", tmp_path / "wide.tsv"
+    bt.write_text("\n".join(rows) + "\n")
+    wide.write_text("\n".join(r + "\t7" for r in rows) + "\n")
+    tj, spec = _db(tmp_path), R.REFERENCE_SPEC + " qlen"
+    kw = {} if hit_filter is None else {"hit_filter": hit_filter}
+    exp = pipeline.ingest_columns(str(bt), tj, device=0, **kw)
+    assert pipeline.last_ingest_path() == "gpu"
+    got = pipeline.ingest_columns(str(wide), tj, device=0, blast_outfmt=spec, **kw)
+    assert pipeline.last_ingest_path() == "gpu"
+    _assert_columns_equal(got, exp)
+    assert len(exp["bitscore"]) == (600 if hit_filter is None else exp["n_kept"])
+    if hit_filter is not None:
+        assert (got["n_lines"], got["n_kept"]) == (exp["n_lines"], exp["n_kept"]) and 0 < exp["n_kept"] < exp["n_lines"] == 600
+    _, exp_st = pipeline.build_consensus_identities(str(bt), tj, device=0, lenient=True, parse=False, **kw)
+    assert pipeline.last_ingest_path() == "gpu"
+    _, got_st = pipeline.build_consensus_identities(str(wide), tj, device=0, lenient=True, parse=False, blast_outfmt=spec, **kw)
+    assert pipeline.last_ingest_path() == "gpu"
+    for k in ("n_hits", "n_queries", "n_unmatched_rows"):
+        assert got_st[k] == exp_st[k], k
+    assert exp_st["n_unmatched_rows"] > 0 and exp_st["n_hits"] == len(exp["bitscore"])
+
+
 @pytest.mark.parametrize("strategy,use_taxid", [("relaxed", False), ("cautious", True)])
 def test_gpu_parsed_c1_files_give_the_faithful_oracles_document(tmp_path, golden_dir, force_gpu, strategy, use_taxid):
     """BASELINE config 1 as files, the table parsed by the GPU (forced: it is under 1 MiB), every rendered field compared
