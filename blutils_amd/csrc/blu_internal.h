@@ -107,6 +107,43 @@ struct HitsDev {
     const uint32_t* packed64 = nullptr;   // 6 words per hit {tax_row, shape hint << 17, align_len, acc_rank, pident f64 lo, hi}, or nullptr
 };
 
+// How the stream kernel deals its wave tasks (consensus_kernel.hip, the head of the task loop).  Tasks are 64
+// consecutive queries while there is a whole round of them (one task per wave of the grid: n_blocks x W); the queries left after
+// the last whole round are cut into one piece per wave, tail_q queries each (a multiple of 8, at least 16, at most 64).  Block b
+// owns the tasks b W + i + k n_waves (i < W, k < rounds) and the pieces of its W waves, and its waves CLAIM them from a queue
+// of the block's own in the order n = k W + i, pieces last: the block sweeps the table in step with the others, as a strided
+// loop would, but a wave that gets cheap tasks takes more of them.
+struct TaskDeal {
+    uint32_t own;      // entries of a block's queue that are whole-round tasks: rounds x W
+    uint32_t tail_q;   // queries per tail piece
+};
+__host__ __device__ inline TaskDeal task_deal(uint32_t n_q, uint32_t n_blocks, uint32_t W) {
+    const uint32_t n_waves = n_blocks * W;
+    const uint32_t n_tasks64 = n_q / 64u + ((n_q % 64u) != 0u ? 1u : 0u);
+    const uint32_t rounds = n_tasks64 / n_waves;
+    const uint32_t t_full = rounds * n_waves;                            // tasks of the whole rounds
+    const uint32_t q_full = t_full == n_tasks64 ? n_q : t_full * 64u;
+    uint32_t tail_q = (((n_q - q_full) + n_waves - 1u) / n_waves + 7u) / 8u * 8u;   // (at most 64: the tail is less than a round)
+    tail_q = tail_q < 16u ? 16u : (tail_q > 64u ? 64u : tail_q);
+    return TaskDeal{rounds * W, tail_q};
+}
+// Entry n of block b's queue -> queries [q0, q0 + nq).  nq = 0: nothing there, and nothing at any later n either (the pieces
+// ascend with n) — the claiming wave is done.  (The last whole-round task is cut at n_q: when the 64-query tasks fill the
+// rounds exactly, the last of them may be a partial one.)
+__host__ __device__ inline void task_of_claim(uint32_t n, uint32_t b, uint32_t n_blocks, uint32_t W, uint32_t n_q, TaskDeal d,
+                                              uint32_t& q0, uint32_t& nq) {
+    if (n < d.own) {
+        q0 = ((n / W) * (n_blocks * W) + b * W + n % W) * 64u;
+        nq = n_q - q0 < 64u ? n_q - q0 : 64u;
+        return;
+    }
+    const uint32_t p = n - d.own;                                        // the piece wave b W + p of a strided deal would take
+    const uint64_t q_full = (uint64_t)d.own * n_blocks * 64u < n_q ? (uint64_t)d.own * n_blocks * 64u : n_q;
+    const uint64_t p0 = q_full + (uint64_t)(b * W + p) * d.tail_q;
+    q0 = p < W && p0 < n_q ? (uint32_t)p0 : n_q;
+    nq = n_q - q0 < d.tail_q ? n_q - q0 : d.tail_q;
+}
+
 // launch wrapper implemented in consensus_kernel.hip
 // worklist: n_queries uint32 slots; work_count: {queue length, blocks done}, zero between runs (the worklist kernel
 // leaves them so)

@@ -5,8 +5,9 @@
 // build_blast_consensus_identity.rs:9-105 (restated in SURVEY §3.3).
 //
 // Kernel A  blu_consensus_stream_kernel — segments of up to 512 hits.
-//   A wave task is 64 consecutive queries; the waves stride over the tasks on their own (no block-level barrier in the
-//   loop); the offsets of a task are requested one task ahead.
+//   A wave task is 64 consecutive queries; a block owns a stride of the tasks and its waves claim them from a queue of the
+//   block's own, one task ahead (an LDS counter; no block-level barrier in the loop); the offsets of a task are requested
+//   one task ahead.
 //   phase 1, ring tasks (queries back to back, none over 128 rows): the bit-score column streams through a per-wave
 //     LDS ring filled by LDS-DMA (256-row chunks, requested as far ahead as the ring has room — across task boundaries —
 //     and waited for with counted s_waitcnt vmcnt); a lane scans 16 or 32 consecutive rows of its query out of the ring,
@@ -508,26 +509,23 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
     // (task arithmetic in 32 bits: the ABI keeps n_queries below 2^32 — worklist entries are 32-bit query ids — and every
     // kernel-lifetime scalar of this kernel costs a register it does not have)
     const uint32_t n_q32 = (uint32_t)h.n_queries;
-    const uint32_t wave = blockIdx.x * WAVES_T + (uint32_t)wib;
-    const uint32_t n_waves = gridDim.x * WAVES_T;
     // Tasks: 64 consecutive queries each while there is a whole round of them (one task per wave of the grid); the queries left
-    // after the last whole round — up to a round's worth — are dealt to ALL waves in equal pieces of `tail_q` queries (a
-    // multiple of 8, at least 16) instead of 64-query tasks for some waves and nothing for the others: the kernel ends when
-    // the slowest wave does, and a piece costs less than a task.  (C4 slice, 1.25 M queries: 6 whole rounds + 1099 tasks
-    // became 6 rounds + 3072 pieces of 24 queries; C2, 100 k queries, less than one round: 1563 tasks on 131 CUs became 2500
-    // pieces of 40 on all CUs.)
-    // (kept to three kernel-lifetime scalars — the whole rounds' task count and this wave's own piece: every further one costs
-    // a register the ring build does not have)
-    uint32_t t_full, tail_q0, tail_nq;
-    {
-        const uint32_t n_tasks64 = n_q32 / WAVE + ((n_q32 % WAVE) != 0u ? 1u : 0u);
-        t_full = n_tasks64 / n_waves * n_waves;                         // tasks of the whole rounds
-        const uint32_t q_full = t_full == n_tasks64 ? n_q32 : t_full * WAVE;
-        uint32_t tail_q = (((n_q32 - q_full) + n_waves - 1u) / n_waves + 7u) / 8u * 8u;   // (at most 64: the tail is less than a round)
-        tail_q = tail_q < 16u ? 16u : (tail_q > WAVE ? WAVE : tail_q);
-        const uint64_t p0 = (uint64_t)q_full + (uint64_t)wave * tail_q;   // this wave's piece of the tail
-        tail_q0 = p0 < n_q32 ? (uint32_t)p0 : n_q32;
-        tail_nq = n_q32 - tail_q0 < tail_q ? n_q32 - tail_q0 : tail_q;
+    // after the last whole round — up to a round's worth — are cut into one piece of `tail_q` queries per wave (a multiple of
+    // 8, at least 16) instead of 64-query tasks for some waves and nothing for the others: the kernel ends when the slowest
+    // wave does, and a piece costs less than a task.  (C4 slice, 1.25 M queries: 6 whole rounds + 1099 tasks became 6 rounds
+    // + 3072 pieces of 24 queries; C2, 100 k queries, less than one round: 1563 tasks on 131 CUs became 2500 pieces of 40 on
+    // all CUs.)
+    // The block owns the tasks and pieces a strided deal gives its waves (task_deal / task_of_claim in blu_internal.h), in a
+    // queue of its own: s_queue is the next entry nobody has claimed.  The waves start on entries 0 .. W - 1.  A table of less
+    // than one round (deal.own = 0: C2) is those entries — one piece per wave — and nothing is claimed: no barrier, no atomic.
+    // (two kernel-lifetime scalars — the queue's whole-round entries and the piece size: every further one costs a register
+    // the ring build does not have)
+    const TaskDeal deal = task_deal(n_q32, gridDim.x, WAVES_T);
+    // (s_queue: that entry during the task loop; after it, the queued queries the last block drains — one word for both)
+    __shared__ uint32_t s_queue, s_last;
+    if (deal.own != 0u) {
+        if (threadIdx.x == 0) s_queue = WAVES_T;
+        __syncthreads();   // (the only block barrier before the end of the task loop)
     }
 
     // ---- the bit-score ring of this wave (see WaveLds).  The table's rows are numbered v = row + mis, where mis (0..3)
@@ -589,12 +587,17 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
         }
     };
     uint32_t nx_off, nx_end;
-    // the wave's tasks: wave, wave + n_waves, .. below t_full (64 queries each), then its piece of the tail
-    uint32_t task = wave;
-    bool in_tail = task >= t_full, tail_done = false;
-    load_seg(in_tail ? tail_q0 : task * WAVE, in_tail ? tail_nq : (uint32_t)WAVE, nx_off, nx_end);
+    // The wave's tasks are the queue entries it claims, ONE TASK AHEAD: (nx_q0, nx_nq) is the task after the one being worked
+    // on — its offsets are already requested — and nx_nq = 0 says the queue is empty.  Which wave computes a task enters no
+    // record.  A strided deal (wave w: tasks w, w + n_waves, ..) gave every wave the same count, and the launch ended with the
+    // wave whose ~50 task times added up to the most while the others had stopped.  Now a wave whose tasks were cheap takes
+    // another, and a block's waves end within a task of each other.  (The spread of the finish times as measured, and why the
+    // end of the launch is not handed out across blocks as well: DESIGN section 8.)
+    uint32_t nx_q0, nx_nq;
+    task_of_claim((uint32_t)wib, blockIdx.x, gridDim.x, WAVES_T, n_q32, deal, nx_q0, nx_nq);
+    load_seg(nx_q0, nx_nq, nx_off, nx_end);
 
-    for (; !in_tail || (tail_nq != 0u && !tail_done); tail_done = in_tail, task += n_waves, in_tail = task >= t_full) {
+    while (nx_nq != 0u) {
         // Wave priority by phase (s_setprio): 0 for the scan; 3 from the request of a task's side records to the request of its
         // reference rows — the stretch in which the wave is about to start its next memory round trip, and must not queue
         // behind other waves' scan arithmetic, whose data is prefetched anyway — then 1 for the finalisation.  One box, medians
@@ -606,9 +609,9 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
         // compiler: it had hoisted fifty-odd lane-derived addresses and masks (one instruction each to recompute) out of this loop
         // into registers of their own for the whole kernel — a third of the register file of a kernel that spills for lack of them.
         asm volatile("" : "+v"(lane));
-        const uint32_t q0_32 = in_tail ? tail_q0 : task * WAVE;
+        const uint32_t q0_32 = nx_q0;
         const uint64_t q0 = q0_32;
-        const uint32_t nq = in_tail ? tail_nq : (uint32_t)WAVE;
+        const uint32_t nq = nx_nq;
         // the worklist queue this task appends to: by the 64-query block its first query lies in, so that a queue receives what
         // wl_capacity() sized it for whether the tail was cut into pieces or not
         const uint32_t wl_sel = (uint32_t)(q0 / WAVE) & (WL_QUEUES - 1u);
@@ -618,10 +621,13 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
         uint32_t my_off = nx_off, my_end = nx_end;
         if (my_end > n_hits32) my_end = n_hits32;   // defend the column reads against a corrupt offset table
         if (my_off > my_end) my_off = my_end;
-        // the task after this one: the next whole-round task, else this wave's tail piece, else none (nx_nq = 0)
-        const bool nx_tail = task + n_waves >= t_full;
-        const uint32_t nx_q0 = nx_tail ? tail_q0 : (task + n_waves) * WAVE;
-        const uint32_t nx_nq = in_tail ? 0u : (nx_tail ? tail_nq : (uint32_t)WAVE);
+        // the task after this one: the next entry of the block's queue (one lane's LDS atomic, relaxed: the entry is a number,
+        // no data hangs on it; its latency lies behind this whole task), or none (nx_nq = 0)
+        {
+            uint32_t n = 0xFFFFFFFFu;   // (no such entry: what a table of less than one round gets without asking)
+            if (lane == 0 && deal.own != 0u) n = __hip_atomic_fetch_add(&s_queue, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            task_of_claim((uint32_t)__builtin_amdgcn_readfirstlane((int)n), blockIdx.x, gridDim.x, WAVES_T, n_q32, deal, nx_q0, nx_nq);
+        }
         load_seg(nx_q0, nx_nq, nx_off, nx_end);     // consumed after this task's phase 1 (prefetch decision) and by the next iteration
         asm volatile("" ::: "memory");              // (keeps these loads in front of the ring requests below: the counted waits rely on it)
         uint32_t fill = 0;   // wave-uniform: entries used in the LDS list
@@ -2069,7 +2075,6 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
     // also goes to a pinned host word: the next call on this table launches no worklist kernel when it was (next to) nothing
     // — a kernel boundary costs more than a C4 slice can afford — and if the queue is not empty after all, this block, the
     // last one running, works it off itself (every other block has finished and published its entries).
-    __shared__ uint32_t s_drain, s_last;
     uint32_t* const s_cnt = s_lds[0].meta;   // (the queues' lengths, for the drain below: the first wave's task table is dead by now)
     // The entries this wave queued (write-through stores, wl_push) may be read by the last block of THIS kernel: every wave
     // waits for its own stores before the block's ticket — the barrier below is a workgroup-scope release and does not wait
@@ -2081,7 +2086,7 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
         __threadfence();
         const uint32_t ticket = atomicAdd(work_count + 1, 1u);
         s_last = ticket == gridDim.x - 1 ? 1u : 0u;
-        s_drain = 0u;
+        s_queue = 0u;
     }
     __syncthreads();
     if (s_last && wib == 0) {   // (one wave: lane = queue)
@@ -2096,12 +2101,12 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
             if (host_len) __hip_atomic_store(host_len, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             __hip_atomic_store(work_count + 2, no_long ? 0u : n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(work_count + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_drain = no_long ? n : 0u;
+            s_queue = no_long ? n : 0u;
         }
     }
     if (no_long) {
         __syncthreads();
-        const uint32_t n = s_drain;
+        const uint32_t n = s_queue;
         if (n) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // the entries other blocks queued
             uint32_t* const slot = reinterpret_cast<uint32_t*>(&L.rec[0]);
