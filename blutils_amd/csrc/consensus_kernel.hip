@@ -1207,8 +1207,15 @@ void blu_consensus_stream_kernel(HitsDev h, TaxDev t, blu_result* __restrict__ o
                 if (LPQ >= 8) M = imax(M, dpp<0x141>(M));             // row_half_mirror
                 if (LPQ >= 16) M = imax(M, dpp<0x140>(M));            // row_mirror
                 uint32_t mask = tie_mask<RPL>(b, M);                  // bit RPL - 1 - i = row i ties on the query's top score
-                mask = left > 0 ? mask : 0u;
-                if constexpr (FULL) mask &= 0xFFFFFFFFu >> (32u - RPL + over);   // rows 0 .. over - 1 are the previous lane's
+                if constexpr (FULL) {
+                    mask = left > 0 ? mask : 0u;
+                    mask &= 0xFFFFFFFFu >> (32u - RPL + over);        // rows 0 .. over - 1 are the previous lane's
+                } else {
+                    // the rows behind the lane's last one were set to INT_MIN above: under a top score of INT_MIN itself they
+                    // would tie with it (a two-row query of -2147483648 took the next queries' rows into its top group)
+                    const uint32_t held = (uint32_t)imin(imax(left, 0), (int)RPL);
+                    mask = held ? mask & (0xFFFFFFFFu << (RPL - held)) : 0u;
+                }
                 const uint32_t c = (uint32_t)__builtin_popcount(mask);
                 uint32_t incl = c;                                    // inclusive prefix of the top-row counts inside the 16-lane row
                 incl += (uint32_t)dpp<0x111>((int)incl);

@@ -133,6 +133,11 @@ struct Renderer {
         const uint32_t lvl = (r.flags & BLU_FLAG_AGREE) ? r.bean_index : (uint32_t)r.bean_index + 1;   // level the scan stopped at
         for (uint32_t i : sc.S) {   // consensus_result.rs:65-88 fold, first-seen order
             const uint32_t d = rows[i].desc_row;
+            // Every top row has level `lvl`: the reference's scan takes, per level, the rows of the length-ascending sort
+            // while they still have that level (find_multi_taxa_consensus.rs:142-145), so from the shortest lineage's length
+            // on it takes none and sets nothing; the level it stopped at — and the engine's bean_index, which follows it —
+            // lies inside the shortest lineage of the group.  tests/document_edges.py, family "ragged": two- and three-level
+            // lineages among four-level ones, the short one the last row of lin_off included.
             const uint32_t node = db.lin_node[db.lin_off[d] + lvl];
             uint32_t bi = 0;
             while (bi < sc.beans.size() && sc.beans[bi].node != node) ++bi;

@@ -11,6 +11,7 @@ from blutils_amd import _native as N
 from blutils_amd import pipeline, synth
 from oracle import oracle as orc
 from tests import helpers as H
+from tests.document_edges import oracle_from_files as _oracle_from_files
 
 pytestmark = pytest.mark.gpu
 
@@ -45,33 +46,6 @@ def _write_inputs(tmp_path, tax, hits, use_taxid=False, scramble=True, half_scor
     bt = tmp_path / "blast.out.tsv"
     bt.write_text("\n".join(r[1] for r in rows) + "\n")
     return str(bt), str(tj), [r[0] for r in rows]
-
-
-def _oracle_from_files(bt, tj, use_taxid, taxon, strategy, custom):
-    """Independent reading of the two files -> faithful oracle."""
-    db = json.load(open(tj))
-    lin = {}                                           # taxid -> its lineages, one per listing (the left join of mod.rs:72-76
-    for t in db["taxonomies"]:                         # gives one joined row per matching taxonomy row, in the DB's order)
-        lin.setdefault(int(t["taxid"]), []).append(t["numericLineage"] if use_taxid else t["textLineage"])
-    lineages = list(dict.fromkeys(s for v in lin.values() for s in v))
-    lin_idx = {s: i for i, s in enumerate(lineages)}
-    per_q = {}
-    for line in open(bt):
-        c = line.rstrip("\n").split("\t")
-        per_q.setdefault(c[0], []).append(c)
-    names = list(per_q)
-    seg, acc_idx, accs, tax_row, pid, aln, bsc = [0], [], {}, [], [], [], []
-    for qn in names:
-        for c in per_q[qn]:
-            for lineage in lin.get(int(c[2]), [None]):
-                acc_idx.append(accs.setdefault(c[1], len(accs)))
-                tax_row.append(lin_idx[lineage] if lineage is not None else -1)
-                pid.append(float(c[3])); aln.append(int(c[4])); bsc.append(int(float(c[12])))
-        seg.append(len(acc_idx))
-    tab = orc.HitTable(np.array(seg, np.uint64), np.array(acc_idx, np.uint32), list(accs), np.array(tax_row, np.int64),
-                       lineages, np.array(pid), np.array(aln, np.int64), np.array(bsc, np.int64))
-    res = orc.run(tab, taxon=taxon, strategy=strategy, custom=custom, threads=4).results()
-    return dict(zip(names, res))
 
 
 @pytest.mark.parametrize("strategy,use_taxid,fmt", [("relaxed", False, "json"), ("cautious", True, "jsonl")])
