@@ -25,7 +25,8 @@ PIPELINE_EXPORTS = ("blu_build_consensus", "blu_build_consensus_with", "blu_buil
                     "blu_ingest_only_on", "blu_ingest_columns_on", "blu_ingest_columns_selected", "blu_ingest_columns_free",
                     "blu_last_ingest_path", "blu_last_min_cover_stats", "blu_db_cache_build", "blu_taxdb_build", "blu_seqdb_export", "blu_qiime_taxonomy_tsv",
                     "blu_seqdb_export_labelled", "blu_seqdb_render_labels", "blu_table_layout_parse", "blu_build_consensus_laid_out",
-                    "blu_ingest_columns_laid_out", "blu_query_cover_parse", "blu_build_consensus_covered", "blu_ingest_columns_covered")
+                    "blu_ingest_columns_laid_out", "blu_query_cover_parse", "blu_build_consensus_covered", "blu_ingest_columns_covered",
+                    "blu_lineage_db_build")
 
 BLU_UNMATCHED_TAXID = 0xFFFFFFFF
 BLU_NONE_U8, BLU_NONE_U16, BLU_MAR_NEVER_EQUAL = 0xFF, 0xFFFF, 0xFFFE

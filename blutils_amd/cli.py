@@ -161,6 +161,14 @@ writes the binary cache of a taxonomies file (not in the reference CLI; pass CAC
 = `blu build-db blu` (ports/cli/src/cmds/db_builder/commands.rs:22-77): the taxonomies database built on the GPU
 (blutils_amd/taxdb.py, csrc/taxdb_gpu.hip); `blastdbcmd` stays an external process.
 
+    python -m blutils_amd.cli build-db lineages TABLE OUTPUT_FILE_PATH [--taxid-map FILE] [-r RANK=NEW]... [--device N]
+
+(not in the reference CLI) the taxonomies database from a lineage table `ID<TAB>d__Bacteria; p__Proteobacteria; ...` (SILVA,
+GTDB, UNITE, Greengenes, any QIIME 2 reference), interned and rendered on the GPU (blutils_amd/lineagedb.py,
+csrc/lineage_db_gpu.hip).  Every distinct path gets a taxid, from 1 in order of first appearance; `--taxid-map FILE` writes
+the `ID taxid` lines that `makeblastdb -parse_seqids -taxid_map FILE` takes, so that BLAST prints those ids in `staxid`.  To
+stderr: `lineage table: N lines, U taxonomies, T taxa, E without a lineage, C truncated, deepest D levels`.
+
     python -m blutils_amd.cli build-db kraken2 BLAST_DATABASE_PATH -o OUTPUT_DIRECTORY
         [--listing-file FILE] [--blastdbcmd EXE] [--device N]
     python -m blutils_amd.cli build-db qiime2 TAXONOMIES_DATABASE_PATH OUTPUT_TAXONOMIES_FILE BLAST_DATABASE_PATH
@@ -187,7 +195,7 @@ import functools
 import os
 import sys
 
-from . import _native, blast, pipeline, report, seqdb, tabular, taxdb
+from . import _native, blast, lineagedb, pipeline, report, seqdb, tabular, taxdb
 
 
 class _BlastnParser(argparse.ArgumentParser):
@@ -333,6 +341,14 @@ def build_parser() -> argparse.ArgumentParser:
                                               "no blastdbcmd run and no database check (not in the reference CLI)")
     db.add_argument("--blastdbcmd", default="blastdbcmd", help="blastdbcmd executable (not in the reference CLI)")
     db.add_argument("--device", type=int, default=0, help="HIP device ordinal (not in the reference CLI)")
+    ln = bd.add_parser("lineages", help="the taxonomies database (*.blutils.json) from a lineage table ID<TAB>d__...; p__...; "
+                                        "(SILVA, GTDB, UNITE, Greengenes, QIIME 2; not in the reference CLI)")
+    ln.add_argument("table", help="two tab-separated columns: ID and lineage; a `Feature ID` header, blank lines and # comments "
+                                  "are skipped, a third column is ignored")
+    ln.add_argument("output_file_path")
+    ln.add_argument("--taxid-map", help="also write `ID taxid` per line, for makeblastdb -parse_seqids -taxid_map")
+    ln.add_argument("-r", "--replace-rank", action="append", help="RANK=NEW: levels of rank RANK (lower-cased) get rank NEW")
+    ln.add_argument("--device", type=int, default=0, help="HIP device ordinal")
     kr = bd.add_parser("kraken2", help="library.fna and prelim_map.txt for Kraken 2 from a BLAST database",
                        description="OUTPUT_DIRECTORY is removed first, whether it is a directory or a file, and created "
                                    "again, before the database is checked (as the reference does).")
@@ -522,11 +538,16 @@ def _build_db(args) -> int:
                   f"{st['n_unknown_taxid']} with a taxid not in the taxonomies file, {st['n_unlabelled']} without a label",
                   file=sys.stderr)
             return 0
+        if args.sub == "lineages":
+            st = lineagedb.build_ref_db_from_lineage_table(args.table, args.output_file_path, args.taxid_map,
+                                                           lineagedb.parse_replace_rank(args.replace_rank), args.device)
+            print(lineagedb.summary(st), file=sys.stderr)
+            return 0
         replace = taxdb.parse_replace_rank(args.replace_rank)
         taxdb.build_ref_db_from_ncbi_files(args.blast_database_path, args.taxdump_directory_path, args.output_file_path,
                                            args.skip_taxid, replace, args.drop_non_linnaean_taxonomies,
                                            args.accessions_file, args.blastdbcmd, args.device)
-    except (taxdb.TaxdbError, blast.BlastError, seqdb.SeqdbError) as e:
+    except (taxdb.TaxdbError, blast.BlastError, seqdb.SeqdbError, lineagedb.LineageDbError) as e:
         raise SystemExit(str(e))
     return 0
 

@@ -2,12 +2,15 @@
 // report (report_kernel.hip), `build-db blu` (taxdb_gpu.hip) and the kraken2 / qiime2 export (seqdb_gpu.hip).
 //   - the error path of a HIP call (HipPolicy, hip_fail, HIP_CHECK) and the owner of one call's device memory (DeviceArena)
 //   - the device primitives (line index, prefix sums, radix sort, column compaction): host wrappers around kernels that are
-//     compiled once, in dev_prims.hip; and the upload and the parallel download of dev_io.cpp
+//     compiled once, in dev_prims.hip; the upload and the parallel download of dev_io.cpp; a whole text file with its line
+//     index (load_text), for the two `build-db` builders that read theirs at once
 //   - host one-liners: a monotonic clock, launch grids, write_all, JSON string escapes
 #ifndef BLU_INGEST_PRIMS_H
 #define BLU_INGEST_PRIMS_H
 
 #include <hip/hip_runtime.h>
+#include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -17,6 +20,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <string>
 #include <string_view>
@@ -148,6 +152,42 @@ int upload_file(int fd, size_t size, unsigned char* d_text, int device, std::str
 // the padded buffer is there (a trace lap)
 int upload_text(int fd, size_t size, int device, const char* name, DeviceArena& mem, unsigned char** d_text, bool* open_tail,
                 const std::function<void()>& allocated = nullptr);
+
+// ---- a whole text file in HBM with its line index (the `build-db` builders): line k is [line[k], line[k + 1] - 1).  Errors
+// name the path; at most 2^31 - 17 lines
+struct DeviceText {
+    std::string path;
+    size_t size = 0;
+    unsigned char* d = nullptr;
+    uint64_t* line = nullptr;
+    uint32_t n_lines = 0;
+};
+inline int load_text(const char* path, int device, DeviceArena& mem, DeviceText& t) {
+    HipPolicy& pol = mem.pol;
+    t.path = path;
+    const int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) { set_error("build-db: cannot open %s: %s", path, strerror(errno)); return BLU_ERR_IO; }
+    struct FdCloser { int fd; ~FdCloser() { close(fd); } } closer{fd};
+    struct stat sb;
+    if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { set_error("build-db: %s is not a regular file", path); return BLU_ERR_IO; }
+    t.size = (size_t)sb.st_size;
+    if (t.size >= (1ull << 40)) { set_error("build-db: %s is too large (%zu bytes)", path, t.size); return BLU_ERR_INVALID_ARG; }
+    bool open_tail = false;
+    if (const int rc = upload_text(fd, t.size, device, path, mem, &t.d, &open_tail); rc != BLU_OK) return rc;
+    const uint64_t n_tiles = line_tiles(t.size);
+    uint32_t *tile = nullptr, *base = nullptr, n_nl = 0;
+    void* tmp = nullptr;
+    HIP_CHECK(pol, mem.alloc(&tile, (n_tiles + 1) * 4, "line index"));
+    HIP_CHECK(pol, mem.alloc(&base, (n_tiles + 1) * 4, "line index"));
+    HIP_CHECK(pol, mem.alloc(&tmp, scan_tmp_bytes_u32(n_tiles + 1), "line index"));
+    HIP_CHECK(pol, line_count(t.d, t.size, tile, base, tmp, &n_nl));
+    const uint64_t n = (uint64_t)n_nl + (open_tail ? 1 : 0);
+    if (n >= 0x7FFFFFF0ull) { set_error("build-db: %s has 2^31 lines or more", path); return BLU_ERR_INVALID_ARG; }
+    t.n_lines = (uint32_t)n;
+    HIP_CHECK(pol, mem.alloc(&t.line, (n + 2) * 8, "line index"));
+    HIP_CHECK(pol, line_write(t.d, t.size, base, t.line, n, open_tail));
+    return BLU_OK;
+}
 
 // ---- device -> pageable host memory by a pool of host threads
 struct D2HPiece { char* dst; const char* src; size_t bytes; };

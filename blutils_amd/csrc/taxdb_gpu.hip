@@ -36,6 +36,7 @@
 #include "blu_pipeline.h"
 #include "ingest.h"
 #include "ingest_prims.h"
+#include "taxmap_entry_dev.h"
 #include "text_dev.h"
 
 namespace blu {
@@ -312,16 +313,6 @@ struct AccOut {
     unsigned long long* err;
     uint32_t* first_bad;   // first line that is not UTF-8: read_line fails there and the reference's loop ends
 };
-// bytes of a string once serde_json has escaped it
-__device__ __forceinline__ uint32_t esc_bytes(uint32_t c) {
-    if (c == '"' || c == '\\' || c == '\b' || c == '\f' || c == '\n' || c == '\r' || c == '\t') return 2;
-    return c < 0x20 ? 6 : 1;
-}
-__device__ __forceinline__ uint32_t esc_len(const unsigned char* __restrict__ text, uint64_t a, uint64_t b) {
-    uint32_t n = 0;
-    for_bytes(text, a, b, [&](uint32_t c, uint64_t) { n += esc_bytes(c); return true; });
-    return n;
-}
 
 __global__ __launch_bounds__(TPB) void taxdb_parse_acc(const unsigned char* __restrict__ text, const uint64_t* __restrict__ line_start,
                                                        uint32_t n, uint32_t n_ids, AccOut o) {
@@ -557,20 +548,7 @@ __global__ __launch_bounds__(TPB) void taxdb_lineages(const uint32_t* __restrict
 }
 
 // ---- render ----------------------------------------------------------------------------------------------------------
-// Pieces of one entry (serde_json::to_string_pretty of TaxonomyMapUnit at depth 2); every entry starts with ",\n" and the
-// host drops the first two bytes of the array
-#define H0 ",\n    {\n      \"taxid\": "
-#define H1 ",\n      \"rank\": \""
-#define H2 "\",\n      \"numericLineage\": \""
-#define H3 "\",\n      \"textLineage\": \""
-#define H4 "\",\n      \"accessions\": [\n"
-#define A0 "        {\n          \"accession\": \""
-#define A1 "\",\n          \"oid\": \""
-#define A2 "\"\n        }"
-#define A_NEXT ",\n"
-#define A_LAST "\n      ]\n    }"
-constexpr uint32_t cl(const char* s) { return *s ? 1 + cl(s + 1) : 0; }
-
+// (the pieces of one entry, the escapes and the byte writers: taxmap_entry_dev.h)
 struct RowIn {
     const uint32_t* seg_of; const uint32_t* seg_start; const uint32_t* seg_key; const uint8_t* status; const uint32_t* node;
     const unsigned long long* num_off; const unsigned long long* num_len; const unsigned long long* txt_off;
@@ -597,31 +575,6 @@ __global__ __launch_bounds__(TPB) void taxdb_row_len(RowIn R, uint32_t n, unsign
              R.txt_len[s] + cl(H4);
     }
     len[i] = l;
-}
-
-__device__ __forceinline__ unsigned char* put(unsigned char* o, const char* s) { while (*s) *o++ = (unsigned char)*s++; return o; }
-__device__ __forceinline__ unsigned char* put_bytes(unsigned char* o, const unsigned char* s, unsigned long long n) {
-    for (unsigned long long k = 0; k < n; ++k) o[k] = s[k];
-    return o + n;
-}
-__device__ __forceinline__ unsigned char* put_escaped(unsigned char* o, const unsigned char* text, uint64_t a, uint32_t n) {
-    const char* hex = "0123456789abcdef";
-    for_bytes(text, a, a + n, [&](uint32_t c, uint64_t) {
-        switch (c) {
-            case '"': *o++ = '\\'; *o++ = '"'; break;
-            case '\\': *o++ = '\\'; *o++ = '\\'; break;
-            case '\b': *o++ = '\\'; *o++ = 'b'; break;
-            case '\f': *o++ = '\\'; *o++ = 'f'; break;
-            case '\n': *o++ = '\\'; *o++ = 'n'; break;
-            case '\r': *o++ = '\\'; *o++ = 'r'; break;
-            case '\t': *o++ = '\\'; *o++ = 't'; break;
-            default:
-                if (c < 0x20) { o = put(o, "\\u00"); *o++ = (unsigned char)hex[c >> 4]; *o++ = (unsigned char)hex[c & 15]; }
-                else *o++ = (unsigned char)c;
-        }
-        return true;
-    });
-    return o;
 }
 
 __global__ __launch_bounds__(TPB) void taxdb_row_write(RowIn R, uint32_t n, const unsigned long long* __restrict__ off, unsigned char* __restrict__ doc) {
@@ -663,42 +616,6 @@ __global__ __launch_bounds__(TPB) void taxdb_gather_u64(const unsigned long long
 
 namespace {
 
-// a text file in HBM and its line index: line k is [line[k], line[k + 1] - 1)
-struct Text {
-    std::string path;
-    size_t size = 0;
-    unsigned char* d = nullptr;
-    uint64_t* line = nullptr;
-    uint32_t n_lines = 0;
-};
-
-int load_text(const char* path, int device, DeviceArena& mem, Text& t) {
-    HipPolicy& pol = mem.pol;
-    t.path = path;
-    const int fd = open(path, O_RDONLY | O_CLOEXEC);
-    if (fd < 0) { set_error("build-db: cannot open %s: %s", path, strerror(errno)); return BLU_ERR_IO; }
-    struct FdCloser { int fd; ~FdCloser() { close(fd); } } closer{fd};
-    struct stat sb;
-    if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { set_error("build-db: %s is not a regular file", path); return BLU_ERR_IO; }
-    t.size = (size_t)sb.st_size;
-    if (t.size >= (1ull << 40)) { set_error("build-db: %s is too large (%zu bytes)", path, t.size); return BLU_ERR_INVALID_ARG; }
-    bool open_tail = false;
-    if (const int rc = upload_text(fd, t.size, device, path, mem, &t.d, &open_tail); rc != BLU_OK) return rc;
-    const uint64_t n_tiles = line_tiles(t.size);
-    uint32_t *tile = nullptr, *base = nullptr, n_nl = 0;
-    void* tmp = nullptr;
-    HIP_CHECK(pol, mem.alloc(&tile, (n_tiles + 1) * 4, "line index"));
-    HIP_CHECK(pol, mem.alloc(&base, (n_tiles + 1) * 4, "line index"));
-    HIP_CHECK(pol, mem.alloc(&tmp, scan_tmp_bytes_u32(n_tiles + 1), "line index"));
-    HIP_CHECK(pol, line_count(t.d, t.size, tile, base, tmp, &n_nl));
-    const uint64_t n = (uint64_t)n_nl + (open_tail ? 1 : 0);
-    if (n >= 0x7FFFFFF0ull) { set_error("build-db: %s has 2^31 lines or more", path); return BLU_ERR_INVALID_ARG; }
-    t.n_lines = (uint32_t)n;
-    HIP_CHECK(pol, mem.alloc(&t.line, (n + 2) * 8, "line index"));
-    HIP_CHECK(pol, line_write(t.d, t.size, base, t.line, n, open_tail));
-    return BLU_OK;
-}
-
 struct Parsed {
     uint32_t* id = nullptr; uint64_t* span_a = nullptr; uint32_t* span_len = nullptr; uint32_t* aux = nullptr;
     unsigned long long counters[4] = {0, 0, 0, 0};
@@ -731,7 +648,7 @@ int build(const blu_taxdb_desc& D, blu_taxdb_stats& S) {
 
     // ---- upload + line index of every input (the line index is part of the parse stage's time)
     const char* paths[N_DUMPS] = {D.nodes_path, D.lineage_path, D.names_path, D.merged_path, D.delnodes_path};
-    Text txt[N_DUMPS], acc;
+    DeviceText txt[N_DUMPS], acc;
     for (int m = 0; m < N_DUMPS; ++m)
         if (const int rc = load_text(paths[m], D.device, mem, txt[m]); rc != BLU_OK) return rc;
     if (const int rc = load_text(D.accessions_path, D.device, mem, acc); rc != BLU_OK) return rc;

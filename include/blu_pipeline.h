@@ -452,6 +452,48 @@ typedef struct blu_taxdb_stats {
 
 int blu_taxdb_build(const blu_taxdb_desc* desc, blu_taxdb_stats* stats);
 
+/* `build-db lineages` (not in the reference) on the GPU: a two-column lineage table
+ * `ID<TAB>d__Bacteria; p__Proteobacteria; ...` (SILVA, GTDB, UNITE, Greengenes, any QIIME 2 reference; what `build-db qiime2`
+ * writes) -> <output_stem>.blutils.json, <output_stem>.non-mapped.tsv (`ID<TAB>LINE<TAB>empty-lineage` per data line no level of
+ * which survives, in file order; removed and created again on every call) and, with taxid_map_path, the `ID taxid` lines that
+ * `makeblastdb -parse_seqids -taxid_map` takes (written as <taxid_map_path>.partial and renamed at the end).  Every distinct
+ * normalised path `rank__identifier;...` is one taxon; taxa are numbered from 1 in the order of their first appearance, file
+ * top to bottom and levels left to right; the document has one entry per path that a line ends on, in ascending taxid.  Paths
+ * are interned exactly: two of them are one taxon only when their bytes are equal, whatever their hashes.  Errors name the
+ * table and the 1-based line (blu_last_error) and come before any file is written; there is no CPU path. */
+typedef struct blu_lineage_db_desc {
+    const char* table_path;        /* the lineage table */
+    const char* output_stem;       /* as in blu_taxdb_desc */
+    const char* taxid_map_path;    /* NULL: no taxid map */
+    const char* const* replace_from;   /* -r FROM=TO pairs in command-line order, FROM lower-cased (a repeated FROM keeps its */
+    const char* const* replace_to;     /*   last TO): an exact match on the lower-cased rank token of a level */
+    uint64_t n_replace;
+    int32_t has_replace;           /* 0: replaceRank is null */
+    int32_t device;                /* HIP device ordinal */
+    const char* source_database;   /* sourceDatabase, as given */
+    const char* blutils_version;   /* NULL = BLU_TAXDB_DEFAULT_VERSION */
+    /* two test aids; the files do not depend on either */
+    uint32_t hash_bits;            /* 0 = all 64: the path hash is cut to its low hash_bits bits (1 .. 63), so that paths collide */
+    uint32_t initial_slots;        /* 0 = sized for the table: slots of the first path dictionary, rounded up to a power of two
+                                      (at least 16); a dictionary more than half full is doubled and built again */
+} blu_lineage_db_desc;
+
+typedef struct blu_lineage_db_stats {
+    uint64_t n_lines;              /* lines of the file */
+    uint64_t n_data_lines;         /* of them: not blank, not a comment, not the header */
+    uint64_t n_taxonomies;         /* entries of the document */
+    uint64_t n_taxa;               /* distinct paths (the largest taxid) */
+    uint64_t n_empty;              /* data lines without a surviving level (TSV lines) */
+    uint64_t n_truncated;          /* data lines cut at a level whose identifier is empty */
+    uint64_t max_depth;            /* levels of the deepest line */
+    uint64_t n_levels;             /* surviving levels of all lines (the items interned) */
+    uint64_t n_dictionary_builds;  /* 1 + the times the dictionary was doubled */
+    uint64_t input_bytes, doc_bytes, tsv_bytes, map_bytes;
+    double t_upload_ms, t_parse_ms, t_intern_ms, t_group_ms, t_render_ms, t_write_ms;
+} blu_lineage_db_stats;
+
+int blu_lineage_db_build(const blu_lineage_db_desc* desc, blu_lineage_db_stats* stats);
+
 /* `blu build-db kraken2` and the sequence half of `blu build-db qiime2` on the GPU
  * (core/src/use_cases/build_kraken_db_from_ncbi_files/, build_qiime_db_from_blutils_db/mod.rs:90-150): the text
  * `blastdbcmd -entry all -db DB -outfmt "%a  %T  %s"` (kraken2) or `"%a  %T  %o  %s"` (qiime2) prints, streamed in chunks
