@@ -17,7 +17,7 @@ EXPORTS = (
     "blu_consensus_report", "blu_report_free", "blu_dev_exclusive_scan", "blu_dev_radix_sort_pairs", "blu_dev_line_index",
     "blu_consensus_sample_table", "blu_sample_table_free", "blu_consensus_support", "blu_hits_score_band",
     "blu_hits_subject_keep", "blu_hits_subject_best", "blu_hits_cover_keep", "blu_hits_cover_apply",
-    "blu_consensus_sample_table_counts",
+    "blu_consensus_sample_table_counts", "blu_sample_distances", "blu_sample_distance_free",
 )
 # include/blu_pipeline.h
 PIPELINE_EXPORTS = ("blu_build_consensus", "blu_build_consensus_with", "blu_build_consensus_identities", "blu_build_consensus_identities_cfg",
@@ -26,7 +26,8 @@ PIPELINE_EXPORTS = ("blu_build_consensus", "blu_build_consensus_with", "blu_buil
                     "blu_last_ingest_path", "blu_last_min_cover_stats", "blu_db_cache_build", "blu_taxdb_build", "blu_seqdb_export", "blu_qiime_taxonomy_tsv",
                     "blu_seqdb_export_labelled", "blu_seqdb_render_labels", "blu_table_layout_parse", "blu_build_consensus_laid_out",
                     "blu_ingest_columns_laid_out", "blu_query_cover_parse", "blu_build_consensus_covered", "blu_ingest_columns_covered",
-                    "blu_lineage_db_build")
+                    "blu_lineage_db_build", "blu_distance_features_from_table", "blu_distance_features_free", "blu_distance_render",
+                    "blu_distance_matrix_file")
 
 BLU_UNMATCHED_TAXID = 0xFFFFFFFF
 BLU_NONE_U8, BLU_NONE_U16, BLU_MAR_NEVER_EQUAL = 0xFF, 0xFFFF, 0xFFFE
@@ -107,6 +108,22 @@ def cover_counts(st: MinCoverStats) -> dict:
     return {f: int(getattr(st, f)) for f, _ in MinCoverStats._fields_}
 
 
+DISTANCE_MAX_SAMPLES, DISTANCE_CHUNK, DISTANCE_PARTNERS = 4096, 8192, 64
+
+
+class DistanceDesc(C.Structure):
+    """include/blu_consensus.h: blu_distance_desc"""
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_features", C.c_uint64), ("n_samples", C.c_uint32),
+                ("reserved", C.c_uint32), ("row_ptr", C.c_void_p), ("sample", C.c_void_p), ("count", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class SampleDistance(C.Structure):
+    """include/blu_consensus.h: blu_sample_distance"""
+    _fields_ = [("n_samples", C.c_uint32), ("reserved", C.c_uint32), ("total", C.POINTER(C.c_uint64)),
+                ("richness", C.POINTER(C.c_uint32)), ("min_sum", C.POINTER(C.c_uint64)), ("shared", C.POINTER(C.c_uint32)),
+                ("t_device_ms", C.c_double)]
+
+
 class NativeLibraryMissing(RuntimeError):
     pass
 
@@ -184,6 +201,10 @@ def lib() -> C.CDLL:
                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(MinCoverStats)]
         L.blu_last_min_cover_stats.restype = C.c_int
         L.blu_last_min_cover_stats.argtypes = [C.POINTER(MinCoverStats)]
+    if hasattr(L, "blu_sample_distances"):       # (an A/B library of an older build: BLU_CONSENSUS_LIB)
+        L.blu_sample_distances.restype = C.c_int
+        L.blu_sample_distances.argtypes = [C.POINTER(DistanceDesc), C.POINTER(SampleDistance)]
+        L.blu_sample_distance_free.argtypes = [C.POINTER(SampleDistance)]
     L.blu_consensus_last_launch.restype = C.c_int
     L.blu_consensus_last_launch.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     _lib = L

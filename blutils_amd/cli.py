@@ -147,6 +147,25 @@ what it gives on a copy of the table without the failing lines.  `--min-query-co
 hit filter's line: `query cover: B of N lines under P percent (from SOURCE)`.  run-with-consensus has `-q` for blastn itself
 and no such flag.
 
+    python -m blutils_amd.cli blastn build-distances TABLE -o OUT [--rank R] [--metric bray-curtis|jaccard]
+        [--drop-unclassified] [--device N]
+    python -m blutils_amd.cli blastn build-consensus ... --sample-table FILE --distance-matrix OUT [--distance-rank R]
+        [--distance-metric M]
+    python -m blutils_amd.cli blastn run-with-consensus ... (the same three)
+    python -m blutils_amd.cli blastn build-report [BLU_RESULT|-] --by-sample -o FILE --distance-matrix OUT (the same two)
+
+not in the reference: distances between the samples of a sample table.  TABLE is what --sample-table or
+build-report --by-sample wrote.  Its rows are collapsed at rank R (the table's rank column: `g`, or `genus`): every row of rank
+R not under another one is a feature with its clade counts, every row that neither is nor lies under a row of rank R is a feature
+with its direct counts (queries that ended above R, branches that skip R), and unclassified and unplaced are one feature each
+unless --drop-unclassified leaves them out; without --rank every row is a feature with its direct counts.  OUT is a square
+tab-separated matrix with the sample names on both sides, in the table's column order: Bray-Curtis (the default) or Jaccard
+distances with six decimals, `nan` between two empty samples.  The sums behind them are integers counted on the GPU
+(csrc/distance_kernel.hip) and the rounding is done in integers, half up, so the bytes do not depend on the machine.  A table
+whose lines do not add up — a total that is not its cells' sum, children that pass their parent, a missing parent — is an
+error naming the line.  The --distance-matrix form runs the same call on the file --sample-table (build-report: -o) just wrote,
+after every other output.  To stderr: `distances: F features at R, S samples, Z non-zeros`.
+
     python -m blutils_amd.cli cache-db TAX.json CACHE [-u]
 
 writes the binary cache of a taxonomies file (not in the reference CLI; pass CACHE as -t afterwards).  
@@ -195,7 +214,7 @@ import functools
 import os
 import sys
 
-from . import _native, blast, lineagedb, pipeline, report, seqdb, tabular, taxdb
+from . import _native, blast, distance, lineagedb, pipeline, report, seqdb, tabular, taxdb
 
 
 class _BlastnParser(argparse.ArgumentParser):
@@ -325,6 +344,23 @@ def build_parser() -> argparse.ArgumentParser:
     br.add_argument("--count-table", metavar="FILE",
                     help="a feature x sample count table: the abundances of the results, joined on their names up to the first "
                          "`;`, instead of what the query names say; not with --weight size (not in the reference CLI)")
+    bdi = blastn.add_parser("build-distances", help="sample table -> Bray-Curtis or Jaccard distance matrix between its samples, "
+                                                    "counted on the GPU (not in the reference)")
+    bdi.add_argument("table", help="a file written by --sample-table or build-report --by-sample")
+    bdi.add_argument("-o", "--output-file", required=True)
+    bdi.add_argument("--rank", metavar="R", help="collapse the rows at this rank, as the table's rank column spells it (`g`, or "
+                                                 "`genus`); default: every row by its direct counts")
+    bdi.add_argument("--metric", default="bray-curtis", choices=list(distance.METRICS))
+    bdi.add_argument("--drop-unclassified", action="store_true", help="leave the unclassified and unplaced rows out")
+    bdi.add_argument("--device", type=int, default=0, help="HIP device ordinal")
+    for sp in (bc, rw, br):
+        dst = sp.add_argument_group("sample distances (not in the reference CLI)",
+                                    "the distance matrix of the sample table just written, as build-distances makes it")
+        dst.add_argument("--distance-matrix", metavar="FILE",
+                         help="also write the distance matrix between the samples to FILE; needs "
+                              + ("--by-sample and -o" if sp is br else "--sample-table"))
+        dst.add_argument("--distance-rank", metavar="R", help="build-distances --rank")
+        dst.add_argument("--distance-metric", choices=list(distance.METRICS), help="build-distances --metric (default bray-curtis)")
     bt = blastn.add_parser("build-tabular", help="blutils result document -> TSV")
     bt.add_argument("blu_result", nargs="?", default="-")
     bt.add_argument("-o", "--output-file")
@@ -518,6 +554,29 @@ def _check_count_table(args) -> None:
         raise SystemExit("--count-table cannot be combined with --report-weight size: the counts are the table's")
 
 
+def _check_distance_flags(ap, args, table) -> None:
+    """--distance-matrix needs the table it reads; its two companions need it"""
+    needs = "--by-sample and -o" if args.sub == "build-report" else "--sample-table"
+    if args.distance_matrix is None:
+        if args.distance_rank is not None or args.distance_metric is not None:
+            ap.error("--distance-rank and --distance-metric need --distance-matrix")
+        return
+    if table is None:
+        ap.error(f"--distance-matrix needs {needs}: it reads the table that flag writes")
+
+
+def _distance_matrix(args, table, device=0) -> None:
+    """the matrix of the table just written (after every other output)"""
+    if args.distance_matrix is None:
+        return
+    try:
+        st = distance.build_distances(table, args.distance_matrix, args.distance_rank, args.distance_metric or "bray-curtis",
+                                      device=device)
+    except _native.BluError as e:
+        raise SystemExit(str(e))
+    print(distance.summary(st), file=sys.stderr)
+
+
 def _build_db(args) -> int:
     """ports/cli/src/cmds/db_builder/mod.rs:12-44"""
     try:
@@ -552,7 +611,7 @@ def _build_db(args) -> int:
     return 0
 
 
-def _run_with_consensus(args) -> int:
+def _run_with_consensus(ap, args) -> int:
     """ports/cli/src/cmds/blast/mod.rs:24-102"""
     config = blast.BlastBuilder.default(args.database, args.taxon)
     if args.max_target_seqs is not None:
@@ -575,6 +634,7 @@ def _run_with_consensus(args) -> int:
     stats = {}
     hit_filter, taxon_filter = _hit_filter(args), _taxon_filter(args)
     _check_count_table(args)
+    _check_distance_flags(ap, args, args.sample_table)
     try:
         blast.run_blast_and_build_consensus(args.query, args.tax_file, args.blast_out_file, args.blutils_out_file, config,
                                             blast.ExecuteBlastnProcRepository(args.blastn), args.force_overwrite,
@@ -593,11 +653,13 @@ def _run_with_consensus(args) -> int:
             raise
         raise SystemExit(str(e))                                                       # (an unknown element: the library's message)
     _say_kept(stats, hit_filter is not None)
+    _distance_matrix(args, args.sample_table, args.device)
     return 0
 
 
 def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
     if args.cmd == "build-db":
         return _build_db(args)
     if args.cmd == "cache-db":
@@ -609,7 +671,15 @@ def main(argv=None) -> int:
         except tabular.TabularError as e:
             raise SystemExit(str(e))
         return 0
+    if args.sub == "build-distances":
+        try:
+            st = distance.build_distances(args.table, args.output_file, args.rank, args.metric, args.drop_unclassified, args.device)
+        except _native.BluError as e:
+            raise SystemExit(str(e))
+        print(distance.summary(st), file=sys.stderr)
+        return 0
     if args.sub == "build-report":
+        _check_distance_flags(ap, args, args.output_file if args.by_sample else None)
         try:
             if args.count_table is not None and args.weight == "size":
                 raise SystemExit("--count-table cannot be combined with --weight size: the counts are the table's")
@@ -620,9 +690,10 @@ def main(argv=None) -> int:
                 print(report.count_table_line(st), file=sys.stderr)
         except (tabular.TabularError, report.ReportError) as e:
             raise SystemExit(str(e))
+        _distance_matrix(args, args.output_file)
         return 0
     if args.sub == "run-with-consensus":
-        return _run_with_consensus(args)
+        return _run_with_consensus(ap, args)
     custom = None
     if args.custom_taxon_cutoff_file:
         custom = pipeline.custom_taxon_from_file(args.custom_taxon_cutoff_file)        # CustomTaxon::from_file
@@ -646,6 +717,7 @@ def main(argv=None) -> int:
     if args.min_cover is not None:
         extra["min_cover"] = args.min_cover
     _check_count_table(args)
+    _check_distance_flags(ap, args, args.sample_table)
     if args.count_table is not None:
         extra["count_table"] = args.count_table
     if args.blast_outfmt is not None:
@@ -695,6 +767,7 @@ def main(argv=None) -> int:
             raise
         raise SystemExit(str(e))                                                       # (an unknown element: the library's message)
     _say_kept(stats, hit_filter is not None)
+    _distance_matrix(args, args.sample_table, args.device)
     return 0
 
 

@@ -414,8 +414,32 @@ def last_min_cover_stats() -> dict:
     return N.cover_counts(st)
 
 
+DISTANCE_DROP_UNCLASSIFIED = 1
+DISTANCE_METRIC = {"bray-curtis": 0, "jaccard": 1}
+
+
+class DistanceFeatures(C.Structure):
+    """include/blu_pipeline.h: blu_distance_features"""
+    _fields_ = [("n_features", C.c_uint64), ("n_samples", C.c_uint32), ("reserved", C.c_uint32), ("row_ptr", C.POINTER(C.c_uint64)),
+                ("sample", C.POINTER(C.c_uint32)), ("count", C.POINTER(C.c_uint64)), ("sample_names", C.POINTER(C.c_char_p)),
+                ("feature_text", C.POINTER(C.c_char_p)), ("n_dropped", C.c_uint64)]
+
+
+class DistanceStats(C.Structure):
+    """include/blu_pipeline.h: blu_distance_stats"""
+    _fields_ = [("n_features", C.c_uint64), ("n_samples", C.c_uint64), ("n_nonzeros", C.c_uint64), ("n_dropped", C.c_uint64)]
+
+
 def _bind():
     L = N.lib()
+    if hasattr(L, "blu_distance_matrix_file"):   # (an A/B library of an older build: BLU_CONSENSUS_LIB)
+        L.blu_distance_features_from_table.restype = C.c_int
+        L.blu_distance_features_from_table.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(DistanceFeatures)]
+        L.blu_distance_features_free.argtypes = [C.POINTER(DistanceFeatures)]
+        L.blu_distance_render.restype = C.c_int
+        L.blu_distance_render.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(N.SampleDistance), C.c_char_p]
+        L.blu_distance_matrix_file.restype = C.c_int
+        L.blu_distance_matrix_file.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_int, C.c_char_p, C.POINTER(DistanceStats)]
     L.blu_build_consensus.restype = C.c_int
     L.blu_build_consensus.argtypes = [C.POINTER(ConsensusRequest), C.POINTER(ConsensusOutcome)]
     L.blu_build_consensus_with.restype = C.c_int
@@ -446,6 +470,21 @@ def _bind():
     L.blu_custom_taxon_from_file.restype = C.c_int
     L.blu_custom_taxon_from_file.argtypes = [C.c_char_p, C.POINTER(N.CutoffConfig)]
     return L
+
+
+def distance_matrix_file(table_path: str, out_path: str, rank: Optional[str] = None, metric: str = "bray-curtis",
+                         drop_unclassified: bool = False, device: int = 0) -> dict:
+    """blu_distance_matrix_file: the features of a sample-table file at `rank` (None: every row by its direct counts), the pair
+    integers counted on the GPU, the matrix of `metric` written to out_path.  Returns the counts of blu_distance_stats."""
+    if metric not in DISTANCE_METRIC:
+        raise ValueError(f"unknown metric `{metric}`: bray-curtis or jaccard")
+    st = DistanceStats()
+    rc = _bind().blu_distance_matrix_file(table_path.encode(), None if rank is None else rank.encode(), DISTANCE_METRIC[metric],
+                                          DISTANCE_DROP_UNCLASSIFIED if drop_unclassified else 0, int(device), out_path.encode(),
+                                          C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_distance_matrix_file")
+    return {f: int(getattr(st, f)) for f, _ in DistanceStats._fields_}
 
 
 def ingest_only(blast_output: str, taxonomies_file: str, use_taxid: bool = False, device: int = -1):

@@ -507,6 +507,50 @@ int blu_hits_cover_apply(const blu_taxonomy* tax, int32_t* bitscore, int32_t* al
                          uint32_t min_cover_milli, void* stream, uint32_t unmatched_marker, uint64_t* n_hits_out, uint64_t* n_unmatched_out,
                          blu_min_cover_stats* stats);
 
+/* -------------------------------------------------------------------------- */
+/* Pairwise sample distances (additive, ABI v5; not in the reference).  A feature x sample matrix of u64 counts,
+ * given as CSR over the features, and for every pair of samples a, b the integers that Bray-Curtis and Jaccard are ratios of:
+ *   total[a]      = sum over features f of x[f][a]                      (u64)
+ *   richness[a]   = number of features with x[f][a] > 0                 (u32)
+ *   min_sum[a][b] = sum over f of min(x[f][a], x[f][b])                 (u64)
+ *   shared[a][b]  = number of f with x[f][a] > 0 and x[f][b] > 0        (u32)
+ * The matrices are full, row-major [n_samples][n_samples] and symmetric; min_sum[a][a] = total[a], shared[a][a] = richness[a].
+ * No floating point takes part: the values are exact and do not depend on the launch geometry.  Counted on the device
+ * (csrc/distance_kernel.hip): the CSR is transposed by sample there, and a block that owns sample a stages BLU_DISTANCE_CHUNK
+ * features of it in LDS at a time while each of its waves walks the non-zeros of one partner b after the other. */
+#define BLU_DISTANCE_MAX_SAMPLES 4096u   /* n_samples above this is refused */
+#define BLU_DISTANCE_CHUNK 8192u         /* features staged in LDS at a time (8 bytes each) */
+#define BLU_DISTANCE_PARTNERS 64u        /* partners b of one block: 8 waves, 8 partners each */
+typedef struct blu_distance_desc {
+    uint32_t struct_size;      /* sizeof(blu_distance_desc) */
+    int32_t device;            /* HIP device ordinal */
+    uint64_t n_features;       /* below 2^31 */
+    uint32_t n_samples;        /* 1 .. BLU_DISTANCE_MAX_SAMPLES */
+    uint32_t reserved;
+    const uint64_t* row_ptr;   /* [n_features + 1] host; non-decreasing, row_ptr[0] = 0, row_ptr[n_features] <= 2^32 - 1024 */
+    const uint32_t* sample;    /* [nnz] host; ascending within a feature, each < n_samples */
+    const uint64_t* count;     /* [nnz] host; each > 0 */
+    void* stream;              /* a hipStream_t the call waits for before it starts (NULL = default); it runs on the default stream */
+} blu_distance_desc;           /* 56 bytes */
+
+typedef struct blu_sample_distance {
+    uint32_t n_samples;
+    uint32_t reserved;
+    uint64_t* total;           /* [n_samples] */
+    uint32_t* richness;        /* [n_samples] */
+    uint64_t* min_sum;         /* [n_samples * n_samples] */
+    uint32_t* shared;          /* [n_samples * n_samples] */
+    double t_device_ms;        /* transpose + pair kernel on the device, by events */
+} blu_sample_distance;         /* every array malloc'd by the library: blu_sample_distance_free */
+
+/* Host arrays in, host arrays out; synchronous.  BLU_ERR_INVALID_ARG, naming the feature, before anything is uploaded or
+ * launched: a sample id >= n_samples, a sample that does not ascend within its feature (unsorted or repeated), a zero count, a
+ * row_ptr that decreases; and: n_samples of 0 or above BLU_DISTANCE_MAX_SAMPLES, a struct_size the library does not know,
+ * n_features >= 2^31, more than 2^32 - 1024 non-zeros, a sample whose counts add up to 2^63 or more (naming the sample).  A device that
+ * cannot be used is BLU_ERR_NO_DEVICE: there is no CPU fallback. */
+int blu_sample_distances(const blu_distance_desc* desc, blu_sample_distance* out);
+void blu_sample_distance_free(blu_sample_distance* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -580,6 +580,57 @@ int blu_seqdb_export_labelled(const blu_seqdb_label_desc* desc, blu_seqdb_label_
  * with an empty label included, to out_path. */
 int blu_seqdb_render_labels(const char* taxonomies_file, int use_taxid, int format, const char* out_path);
 
+/* `blastn build-distances` (not in the reference): Bray-Curtis and Jaccard distances between the samples of a
+ * sample-table file (`--sample-table`, `build-report --by-sample`), collapsed at one rank.
+ *
+ * The table: `#rank identifier taxonomy total <sample>...`, then `- unclassified`, optionally `- unplaced`, then one line per path;
+ * every cell a u64 clade count.  A row's parent is the row whose taxonomy is its own minus the last `;element`; a row without `;`
+ * is top-level.  direct_s(p) = clade_s(p) - the sum of clade_s over p's children.  BLU_ERR_PARSE, naming the 1-based line: a
+ * negative direct count (the parent's line), a row whose parent is missing, a line whose cells do not number the header's samples,
+ * a cell that is not a u64, a `total` that is not the sum of the line's cells, a taxonomy for the second time.
+ * Features at rank R (the spelling of the table's rank column; `genus` is `g`, as for the taxon filters):
+ *   (a) every row of rank R without a proper ancestor of rank R, with its clade cells;
+ *   (b) every row that neither is nor has an ancestor of rank R, with its direct counts;
+ *   (c) unclassified and unplaced, one feature each, unless BLU_DISTANCE_DROP_UNCLASSIFIED is set.
+ * rank NULL: (b) for every row.  A feature that is zero in every sample is dropped (counted in n_dropped).  A rank no row
+ * carries is BLU_ERR_INVALID_ARG naming it.  Per sample the features add up to unclassified + unplaced + the top-level clade
+ * counts (the top-level sum alone under the flag); the call checks it. */
+#define BLU_DISTANCE_DROP_UNCLASSIFIED 1u
+#define BLU_DISTANCE_BRAY_CURTIS 0
+#define BLU_DISTANCE_JACCARD 1
+typedef struct blu_distance_features {
+    uint64_t n_features;
+    uint32_t n_samples;
+    uint32_t reserved;
+    uint64_t* row_ptr;        /* [n_features + 1] CSR over the features: what blu_distance_desc takes */
+    uint32_t* sample;         /* [nnz] column of the table, ascending within a feature */
+    uint64_t* count;          /* [nnz] > 0 */
+    char** sample_names;      /* [n_samples] in the table's column order */
+    char** feature_text;      /* [n_features] the row's taxonomy; `unclassified`, `unplaced`.  Fixed rows first, then file order */
+    uint64_t n_dropped;       /* all-zero features left out */
+} blu_distance_features;      /* every array malloc'd by the library: blu_distance_features_free */
+int blu_distance_features_from_table(const char* table_path, const char* rank /* or NULL */, uint32_t flags, blu_distance_features* out);
+void blu_distance_features_free(blu_distance_features* features);
+
+/* The square matrix of one metric as text: a header line with an empty first cell and the names, then per sample its name and
+ * one value per sample, tab-separated.
+ *   bray-curtis: (N - 2 C) / N, N = total[a] + total[b], C = min_sum[a][b]
+ *   jaccard:     (U - I) / U,   I = shared[a][b], U = richness[a] + richness[b] - I
+ * with six decimals, rounded half up in integers: (num * 10^6 + den / 2) / den in 128 bits; `nan` where den = 0.
+ * `integers` as blu_sample_distances filled it (include/blu_consensus.h); names[integers->n_samples]. */
+int blu_distance_render(int metric, const char* const* names, const blu_sample_distance* integers, const char* out_path);
+
+typedef struct blu_distance_stats {
+    uint64_t n_features;      /* features kept */
+    uint64_t n_samples;
+    uint64_t n_nonzeros;
+    uint64_t n_dropped;       /* all-zero features left out */
+} blu_distance_stats;
+/* The three steps chained: the features of table_path at `rank` (NULL: none), blu_sample_distances on `device`, the matrix of
+ * `metric` to out_path.  stats may be NULL.  Nothing is written unless every step succeeds. */
+int blu_distance_matrix_file(const char* table_path, const char* rank, int metric, uint32_t flags, int device, const char* out_path,
+                             blu_distance_stats* stats);
+
 /* CustomTaxon::from_file (domain/dtos/taxon.rs:28-66): .yaml or .json with the eight cutoff fields. */
 int blu_custom_taxon_from_file(const char* path, blu_cutoff_config* cfg);
 
