@@ -18,6 +18,7 @@ EXPORTS = (
     "blu_consensus_sample_table", "blu_sample_table_free", "blu_consensus_support", "blu_hits_score_band",
     "blu_hits_subject_keep", "blu_hits_subject_best", "blu_hits_cover_keep", "blu_hits_cover_apply",
     "blu_consensus_sample_table_counts", "blu_sample_distances", "blu_sample_distance_free",
+    "blu_rarefy_stream", "blu_sample_rarefy", "blu_rarefied_free",
 )
 # include/blu_pipeline.h
 PIPELINE_EXPORTS = ("blu_build_consensus", "blu_build_consensus_with", "blu_build_consensus_identities", "blu_build_consensus_identities_cfg",
@@ -27,11 +28,12 @@ PIPELINE_EXPORTS = ("blu_build_consensus", "blu_build_consensus_with", "blu_buil
                     "blu_seqdb_export_labelled", "blu_seqdb_render_labels", "blu_table_layout_parse", "blu_build_consensus_laid_out",
                     "blu_ingest_columns_laid_out", "blu_query_cover_parse", "blu_build_consensus_covered", "blu_ingest_columns_covered",
                     "blu_lineage_db_build", "blu_distance_features_from_table", "blu_distance_features_free", "blu_distance_render",
-                    "blu_distance_matrix_file")
+                    "blu_distance_matrix_file", "blu_distance_matrix_file_with")
 
 BLU_UNMATCHED_TAXID = 0xFFFFFFFF
 BLU_NONE_U8, BLU_NONE_U16, BLU_MAR_NEVER_EQUAL = 0xFF, 0xFFFF, 0xFFFE
 BLU_OK, BLU_ERR_INVALID_ARG, BLU_ERR_NO_DEVICE, BLU_ERR_HIP, BLU_ERR_DEPTH, BLU_ERR_CUSTOM_MISSING = 0, 1, 2, 3, 4, 5
+BLU_ERR_INTERNAL = 10
 ST_MULTI, ST_SINGLE, ST_NO_HITS = 0, 1, 2
 ST_ERR_UNMATCHED, ST_ERR_BAD_LINEAGE, ST_ERR_ROOT, ST_ERR_SINGLE_BELOW, ST_ERR_BAD_PIDENT = 16, 17, 18, 19, 20
 FLAG_MUTATED, FLAG_AGREE = 1, 2
@@ -124,6 +126,23 @@ class SampleDistance(C.Structure):
                 ("t_device_ms", C.c_double)]
 
 
+RAREFY_TILE, RAREFY_MAX_READS = 65536, 1 << 36
+
+
+class RarefyDesc(C.Structure):
+    """include/blu_consensus.h: blu_rarefy_desc"""
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_features", C.c_uint64), ("n_samples", C.c_uint32),
+                ("reserved", C.c_uint32), ("row_ptr", C.c_void_p), ("sample", C.c_void_p), ("count", C.c_void_p),
+                ("sample_stream", C.c_void_p), ("depth", C.c_uint64), ("stream", C.c_void_p)]
+
+
+class Rarefied(C.Structure):
+    """include/blu_consensus.h: blu_rarefied"""
+    _fields_ = [("n_features", C.c_uint64), ("n_kept", C.c_uint32), ("reserved", C.c_uint32), ("kept_sample", C.POINTER(C.c_uint32)),
+                ("row_ptr", C.POINTER(C.c_uint64)), ("sample", C.POINTER(C.c_uint32)), ("count", C.POINTER(C.c_uint64)),
+                ("t_device_ms", C.c_double)]
+
+
 class NativeLibraryMissing(RuntimeError):
     pass
 
@@ -205,6 +224,12 @@ def lib() -> C.CDLL:
         L.blu_sample_distances.restype = C.c_int
         L.blu_sample_distances.argtypes = [C.POINTER(DistanceDesc), C.POINTER(SampleDistance)]
         L.blu_sample_distance_free.argtypes = [C.POINTER(SampleDistance)]
+    if hasattr(L, "blu_sample_rarefy"):          # (an A/B library of an older build: BLU_CONSENSUS_LIB)
+        L.blu_rarefy_stream.restype = C.c_uint64
+        L.blu_rarefy_stream.argtypes = [C.c_uint64, C.c_char_p, C.c_uint64]
+        L.blu_sample_rarefy.restype = C.c_int
+        L.blu_sample_rarefy.argtypes = [C.POINTER(RarefyDesc), C.POINTER(Rarefied)]
+        L.blu_rarefied_free.argtypes = [C.POINTER(Rarefied)]
     L.blu_consensus_last_launch.restype = C.c_int
     L.blu_consensus_last_launch.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     _lib = L

@@ -148,9 +148,9 @@ hit filter's line: `query cover: B of N lines under P percent (from SOURCE)`.  r
 and no such flag.
 
     python -m blutils_amd.cli blastn build-distances TABLE -o OUT [--rank R] [--metric bray-curtis|jaccard]
-        [--drop-unclassified] [--device N]
+        [--drop-unclassified] [--device N] [--rarefy D [--seed N] [--rarefied-table FILE]]
     python -m blutils_amd.cli blastn build-consensus ... --sample-table FILE --distance-matrix OUT [--distance-rank R]
-        [--distance-metric M]
+        [--distance-metric M] [--distance-rarefy D [--distance-seed N] [--distance-rarefied-table FILE]]
     python -m blutils_amd.cli blastn run-with-consensus ... (the same three)
     python -m blutils_amd.cli blastn build-report [BLU_RESULT|-] --by-sample -o FILE --distance-matrix OUT (the same two)
 
@@ -165,6 +165,16 @@ distances with six decimals, `nan` between two empty samples.  The sums behind t
 whose lines do not add up — a total that is not its cells' sum, children that pass their parent, a missing parent — is an
 error naming the line.  The --distance-matrix form runs the same call on the file --sample-table (build-report: -o) just wrote,
 after every other output.  To stderr: `distances: F features at R, S samples, Z non-zeros`.
+
+--rarefy D subsamples every sample to D reads first, without replacement: raw counts mostly measure sequencing
+depth.  Samples with fewer than D reads are dropped from the matrix, a sample of exactly D reads is kept whole.  The draw is a
+rule in integers — read i of a sample is kept when its 64-bit hash, keyed by --seed (default 0) and the sample's NAME, is among
+the sample's D smallest — selected on the GPU (csrc/rarefy_kernel.hip), so the same table, depth and seed give the same bytes
+on any machine, and re-ordering or leaving out columns does not change the draw of the others.  --rarefied-table FILE also
+writes the rarefied features: `#feature total <kept samples>`, one line per feature that is still non-zero.  Two columns of one
+name, a D no sample reaches (the message says the largest total) and a sample of 2^32 reads or more are errors.  To stderr,
+after the `distances:` line, which then counts the kept samples and the rarefied non-zeros:
+`rarefy: depth D, seed N, kept K of S samples, E features emptied`, and `rarefy: dropped SAMPLE (TOTAL reads)` per dropped sample.
 
     python -m blutils_amd.cli cache-db TAX.json CACHE [-u]
 
@@ -353,6 +363,10 @@ def build_parser() -> argparse.ArgumentParser:
     bdi.add_argument("--metric", default="bray-curtis", choices=list(distance.METRICS))
     bdi.add_argument("--drop-unclassified", action="store_true", help="leave the unclassified and unplaced rows out")
     bdi.add_argument("--device", type=int, default=0, help="HIP device ordinal")
+    bdi.add_argument("--rarefy", metavar="D", type=_depth, help="subsample every sample to D reads first, without replacement, on "
+                                                               "the GPU; samples with fewer are dropped")
+    bdi.add_argument("--seed", metavar="N", type=_seed, help="the seed of the draw, 0 .. 2^64 - 1 (default 0); needs --rarefy")
+    bdi.add_argument("--rarefied-table", metavar="FILE", help="also write the rarefied features to FILE; needs --rarefy")
     for sp in (bc, rw, br):
         dst = sp.add_argument_group("sample distances (not in the reference CLI)",
                                     "the distance matrix of the sample table just written, as build-distances makes it")
@@ -361,6 +375,9 @@ def build_parser() -> argparse.ArgumentParser:
                               + ("--by-sample and -o" if sp is br else "--sample-table"))
         dst.add_argument("--distance-rank", metavar="R", help="build-distances --rank")
         dst.add_argument("--distance-metric", choices=list(distance.METRICS), help="build-distances --metric (default bray-curtis)")
+        dst.add_argument("--distance-rarefy", metavar="D", type=_depth, help="build-distances --rarefy")
+        dst.add_argument("--distance-seed", metavar="N", type=_seed, help="build-distances --seed; needs --distance-rarefy")
+        dst.add_argument("--distance-rarefied-table", metavar="FILE", help="build-distances --rarefied-table; needs --distance-rarefy")
     bt = blastn.add_parser("build-tabular", help="blutils result document -> TSV")
     bt.add_argument("blu_result", nargs="?", default="-")
     bt.add_argument("-o", "--output-file")
@@ -554,15 +571,41 @@ def _check_count_table(args) -> None:
         raise SystemExit("--count-table cannot be combined with --report-weight size: the counts are the table's")
 
 
+def _depth(text: str) -> int:
+    """argparse type of --rarefy: a whole number of reads, 1 .. 2^64 - 1"""
+    v = int(text)
+    if not 1 <= v < 2 ** 64:
+        raise argparse.ArgumentTypeError("the depth is a whole number of reads, 1 or more")
+    return v
+
+
+def _seed(text: str) -> int:
+    """argparse type of --seed: 0 .. 2^64 - 1"""
+    v = int(text)
+    if not 0 <= v < 2 ** 64:
+        raise argparse.ArgumentTypeError("the seed is a whole number, 0 .. 2^64 - 1")
+    return v
+
+
+def _rarefy_kwargs(depth, seed, table) -> dict:
+    """build_distances' keyword arguments of a rarefaction; none without a depth, so that the call is the one it was"""
+    return {} if depth is None else {"rarefy": depth, "seed": seed or 0, "rarefied_table": table}
+
+
 def _check_distance_flags(ap, args, table) -> None:
-    """--distance-matrix needs the table it reads; its two companions need it"""
+    """--distance-matrix needs the table it reads; its companions need it, and the rarefaction's need --distance-rarefy"""
     needs = "--by-sample and -o" if args.sub == "build-report" else "--sample-table"
+    rarefy = (args.distance_rarefy, args.distance_seed, args.distance_rarefied_table)
     if args.distance_matrix is None:
         if args.distance_rank is not None or args.distance_metric is not None:
             ap.error("--distance-rank and --distance-metric need --distance-matrix")
+        if any(v is not None for v in rarefy):
+            ap.error("--distance-rarefy, --distance-seed and --distance-rarefied-table need --distance-matrix")
         return
     if table is None:
         ap.error(f"--distance-matrix needs {needs}: it reads the table that flag writes")
+    if args.distance_rarefy is None and any(v is not None for v in rarefy):
+        ap.error("--distance-seed and --distance-rarefied-table need --distance-rarefy")
 
 
 def _distance_matrix(args, table, device=0) -> None:
@@ -571,10 +614,10 @@ def _distance_matrix(args, table, device=0) -> None:
         return
     try:
         st = distance.build_distances(table, args.distance_matrix, args.distance_rank, args.distance_metric or "bray-curtis",
-                                      device=device)
+                                      device=device, **_rarefy_kwargs(args.distance_rarefy, args.distance_seed, args.distance_rarefied_table))
     except _native.BluError as e:
         raise SystemExit(str(e))
-    print(distance.summary(st), file=sys.stderr)
+    print("\n".join([distance.summary(st)] + distance.rarefy_summary(st)), file=sys.stderr)
 
 
 def _build_db(args) -> int:
@@ -672,11 +715,14 @@ def main(argv=None) -> int:
             raise SystemExit(str(e))
         return 0
     if args.sub == "build-distances":
+        if args.rarefy is None and (args.seed is not None or args.rarefied_table is not None):
+            ap.error("--seed and --rarefied-table need --rarefy")
         try:
-            st = distance.build_distances(args.table, args.output_file, args.rank, args.metric, args.drop_unclassified, args.device)
+            st = distance.build_distances(args.table, args.output_file, args.rank, args.metric, args.drop_unclassified, args.device,
+                                          **_rarefy_kwargs(args.rarefy, args.seed, args.rarefied_table))
         except _native.BluError as e:
             raise SystemExit(str(e))
-        print(distance.summary(st), file=sys.stderr)
+        print("\n".join([distance.summary(st)] + distance.rarefy_summary(st)), file=sys.stderr)
         return 0
     if args.sub == "build-report":
         _check_distance_flags(ap, args, args.output_file if args.by_sample else None)

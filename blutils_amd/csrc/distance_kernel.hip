@@ -24,6 +24,7 @@
 #include <cstring>
 #include <vector>
 
+#include "csr_check.h"
 #include "ingest_prims.h"
 
 namespace blu {
@@ -178,39 +179,15 @@ __global__ __launch_bounds__(PB) void distance_pairs(PairDev d) {
     }
 }
 
-int refuse(const char* fmt, unsigned long long a, unsigned long long b = 0) {
-    set_error(fmt, a, b);
-    return BLU_ERR_INVALID_ARG;
-}
-
 // the desc's refusals; *nnz_out = row_ptr[n_features]
 int check_desc(const blu_distance_desc& d, uint64_t* nnz_out) {
-    if (d.struct_size != sizeof(blu_distance_desc))
-        return refuse("blu_sample_distances: struct_size %llu is not one this library knows (%llu)", d.struct_size, sizeof(blu_distance_desc));
-    if (d.n_samples == 0 || d.n_samples > BLU_DISTANCE_MAX_SAMPLES)
-        return refuse("blu_sample_distances: n_samples %llu is outside 1 .. %llu", d.n_samples, BLU_DISTANCE_MAX_SAMPLES);
-    if (d.n_features >= (1ull << 31)) return refuse("blu_sample_distances: n_features %llu is 2^31 or more", d.n_features);
-    if (!d.row_ptr) { set_error("blu_sample_distances: row_ptr is NULL"); return BLU_ERR_INVALID_ARG; }
-    if (d.row_ptr[0] != 0) return refuse("blu_sample_distances: feature 0: row_ptr[0] is %llu, not 0", d.row_ptr[0]);
-    for (uint64_t f = 0; f < d.n_features; ++f)
-        if (d.row_ptr[f + 1] < d.row_ptr[f]) return refuse("blu_sample_distances: feature %llu: row_ptr decreases", f);
-    const uint64_t nnz = d.row_ptr[d.n_features];
-    if (nnz > 0xFFFFFC00ull) return refuse("blu_sample_distances: %llu non-zeros: more than 2^32 - 1024", nnz);   // (a position + a block's stride fits 32 bits)
-    if (nnz && (!d.sample || !d.count)) { set_error("blu_sample_distances: sample or count is NULL"); return BLU_ERR_INVALID_ARG; }
-    std::vector<uint64_t> total(d.n_samples, 0);
-    for (uint64_t f = 0; f < d.n_features; ++f) {
-        for (uint64_t e = d.row_ptr[f]; e < d.row_ptr[f + 1]; ++e) {
-            const uint32_t s = d.sample[e];
-            if (s >= d.n_samples) return refuse("blu_sample_distances: feature %llu: sample id %llu is not below n_samples", f, s);
-            if (e > d.row_ptr[f] && s <= d.sample[e - 1])
-                return refuse("blu_sample_distances: feature %llu: sample %llu does not ascend (unsorted or repeated)", f, s);
-            if (d.count[e] == 0) return refuse("blu_sample_distances: feature %llu: a zero count (sample %llu)", f, s);
-            if (d.count[e] >> 63 || (total[s] += d.count[e]) >> 63)
-                return refuse("blu_sample_distances: sample %llu: its counts add up to 2^63 or more (at feature %llu)", s, f);
-        }
+    if (d.struct_size != sizeof(blu_distance_desc)) {
+        set_error("blu_sample_distances: struct_size %llu is not one this library knows (%llu)", (unsigned long long)d.struct_size,
+                  (unsigned long long)sizeof(blu_distance_desc));
+        return BLU_ERR_INVALID_ARG;
     }
-    *nnz_out = nnz;
-    return BLU_OK;
+    std::vector<uint64_t> total;
+    return check_csr("blu_sample_distances", d.n_features, d.n_samples, d.row_ptr, d.sample, d.count, nnz_out, total);
 }
 
 template <class T>

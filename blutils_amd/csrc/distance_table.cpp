@@ -1,6 +1,8 @@
 // `build-distances` on the host (include/blu_pipeline.h): the features of a sample-table file at one rank as
 // CSR, the rendering of a distance matrix from the pair integers, and the chain of the two around blu_sample_distances.  The
 // file is small next to what precedes it in a run (one line per path); the pairwise pass is the device's (distance_kernel.hip).
+// With a depth the chain has a step more: the features are rarefied on the device first (rarefy_kernel.hip) and
+// the rarefied table is rendered here too.
 #include "pipeline_internal.h"
 
 namespace blu {
@@ -239,6 +241,80 @@ int render_text(int metric, const char* const* names, const blu_sample_distance&
     return BLU_OK;
 }
 
+// features -> rarefied features -> pair integers of the kept samples -> both texts, then both files
+int rarefied_matrix(const blu_distance_features& ft, const blu_distance_desc& desc, int metric, uint64_t depth, uint64_t seed, const char* out_path,
+                    const char* table_out, blu_rarefied& rf, blu_sample_distance& d, blu_distance_stats2* stats2) {
+    const uint32_t S = ft.n_samples;
+    {
+        std::unordered_map<std::string_view, uint32_t> column_of;
+        for (uint32_t a = 0; a < S; ++a) {
+            const auto at = column_of.emplace(ft.sample_names[a], a);
+            if (!at.second) {
+                set_error("build-distances: sample columns %u and %u are both named `%s`: a sample's draw goes by its name", at.first->second + 1, a + 1,
+                          ft.sample_names[a]);
+                return BLU_ERR_INVALID_ARG;
+            }
+        }
+    }
+    std::vector<uint64_t> stream(S), total(S, 0);
+    for (uint32_t a = 0; a < S; ++a) stream[a] = blu_rarefy_stream(seed, ft.sample_names[a], strlen(ft.sample_names[a]));
+    blu_rarefy_desc rd{};
+    rd.struct_size = sizeof rd;
+    rd.device = desc.device;
+    rd.n_features = ft.n_features;
+    rd.n_samples = S;
+    rd.row_ptr = ft.row_ptr; rd.sample = ft.sample; rd.count = ft.count;
+    rd.sample_stream = stream.data();
+    rd.depth = depth;
+    if (const int rc = blu_sample_rarefy(&rd, &rf)) return rc;
+    for (uint64_t e = 0; e < ft.row_ptr[ft.n_features]; ++e) total[ft.sample[e]] += ft.count[e];   // (no wrap: the call above checked)
+    if (rf.n_kept == 0) {
+        uint32_t top = 0;
+        for (uint32_t a = 1; a < S; ++a) if (total[a] > total[top]) top = a;
+        set_error("build-distances: no sample reaches the depth %llu: the largest, `%s`, has %llu reads", (unsigned long long)depth,
+                  ft.sample_names[top], (unsigned long long)total[top]);
+        return BLU_ERR_INVALID_ARG;
+    }
+    const uint32_t K = rf.n_kept;
+    std::vector<const char*> names(K);
+    uint64_t reads = 0;
+    for (uint32_t k = 0; k < K; ++k) { names[k] = ft.sample_names[rf.kept_sample[k]]; reads += total[rf.kept_sample[k]]; }
+    blu_distance_desc kd = desc;
+    kd.n_samples = K;
+    kd.row_ptr = rf.row_ptr; kd.sample = rf.sample; kd.count = rf.count;
+    if (const int rc = blu_sample_distances(&kd, &d)) return rc;
+    std::string matrix, table;
+    if (const int rc = render_text(metric, names.data(), d, matrix)) return rc;
+    uint64_t n_left = 0;
+    for (uint64_t f = 0; f < ft.n_features; ++f) n_left += rf.row_ptr[f + 1] != rf.row_ptr[f];
+    if (table_out) {
+        table = "#feature\ttotal";
+        for (uint32_t k = 0; k < K; ++k) { table.push_back('\t'); table += names[k]; }
+        table.push_back('\n');
+        std::vector<uint64_t> cells(K);
+        for (uint64_t f = 0; f < ft.n_features; ++f) {
+            if (rf.row_ptr[f + 1] == rf.row_ptr[f]) continue;
+            std::fill(cells.begin(), cells.end(), 0);
+            uint64_t sum = 0;
+            for (uint64_t e = rf.row_ptr[f]; e < rf.row_ptr[f + 1]; ++e) { cells[rf.sample[e]] = rf.count[e]; sum += rf.count[e]; }
+            table += ft.feature_text[f];
+            table.push_back('\t');
+            table += std::to_string(sum);
+            for (uint32_t k = 0; k < K; ++k) { table.push_back('\t'); table += std::to_string(cells[k]); }
+            table.push_back('\n');
+        }
+    }
+    if (!write_text_file(out_path, matrix)) { set_error("cannot write %s", out_path); return BLU_ERR_IO; }
+    if (table_out && !write_text_file(table_out, table)) {
+        unlink(out_path);                           // nothing is left behind unless every step succeeded
+        set_error("cannot write %s", table_out);
+        return BLU_ERR_IO;
+    }
+    if (stats2)
+        *stats2 = blu_distance_stats2{n_left, K, rf.row_ptr[ft.n_features], ft.n_dropped, depth, K, (uint64_t)S - K, ft.n_features - n_left, reads};
+    return BLU_OK;
+}
+
 }  // namespace
 }  // namespace blu
 
@@ -280,11 +356,31 @@ int blu_distance_render(int metric, const char* const* names, const blu_sample_d
 
 int blu_distance_matrix_file(const char* table_path, const char* rank, int metric, uint32_t flags, int device, const char* out_path,
                              blu_distance_stats* stats) {
+    blu_distance_stats2 st{};
+    const int rc = blu_distance_matrix_file_with(table_path, rank, metric, flags, device, out_path, nullptr, &st);
+    if (rc == BLU_OK && stats) *stats = blu_distance_stats{st.n_features, st.n_samples, st.n_nonzeros, st.n_dropped};
+    return rc;
+}
+
+int blu_distance_matrix_file_with(const char* table_path, const char* rank, int metric, uint32_t flags, int device, const char* out_path,
+                                  const blu_distance_options* options, blu_distance_stats2* stats2) {
     if (!table_path || !out_path) { set_error("build-distances: null argument"); return BLU_ERR_INVALID_ARG; }
     if (metric != BLU_DISTANCE_BRAY_CURTIS && metric != BLU_DISTANCE_JACCARD) { set_error("build-distances: unknown metric %d", metric); return BLU_ERR_INVALID_ARG; }
+    if (options && options->struct_size != sizeof(blu_distance_options)) {
+        set_error("build-distances: options struct_size %llu is not one this library knows (%llu)", (unsigned long long)options->struct_size,
+                  (unsigned long long)sizeof(blu_distance_options));
+        return BLU_ERR_INVALID_ARG;
+    }
+    const uint64_t depth = options ? options->depth : 0;
+    const char* table_out = options ? options->rarefied_table_path : nullptr;
+    if (!depth && table_out) { set_error("build-distances: a rarefied table needs a depth"); return BLU_ERR_INVALID_ARG; }
     blu_distance_features ft{};
+    blu_rarefied rf{};
     blu_sample_distance d{};
-    struct Free { blu_distance_features& f; blu_sample_distance& d; ~Free() { blu_distance_features_free(&f); blu_sample_distance_free(&d); } } guard{ft, d};
+    struct Free {
+        blu_distance_features& f; blu_rarefied& r; blu_sample_distance& d;
+        ~Free() { blu_distance_features_free(&f); blu_rarefied_free(&r); blu_sample_distance_free(&d); }
+    } guard{ft, rf, d};
     if (const int rc = blu_distance_features_from_table(table_path, rank, flags, &ft)) return rc;
     blu_distance_desc desc{};
     desc.struct_size = sizeof desc;
@@ -292,10 +388,15 @@ int blu_distance_matrix_file(const char* table_path, const char* rank, int metri
     desc.n_features = ft.n_features;
     desc.n_samples = ft.n_samples;
     desc.row_ptr = ft.row_ptr; desc.sample = ft.sample; desc.count = ft.count;
-    if (const int rc = blu_sample_distances(&desc, &d)) return rc;
-    if (const int rc = blu_distance_render(metric, ft.sample_names, &d, out_path)) return rc;
-    if (stats) *stats = blu_distance_stats{ft.n_features, ft.n_samples, ft.row_ptr[ft.n_features], ft.n_dropped};
-    return BLU_OK;
+    if (!depth) {
+        if (const int rc = blu_sample_distances(&desc, &d)) return rc;
+        if (const int rc = blu_distance_render(metric, ft.sample_names, &d, out_path)) return rc;
+        if (stats2) *stats2 = blu_distance_stats2{ft.n_features, ft.n_samples, ft.row_ptr[ft.n_features], ft.n_dropped, 0, ft.n_samples, 0, 0, 0};
+        return BLU_OK;
+    }
+    try {
+        return rarefied_matrix(ft, desc, metric, depth, options->seed, out_path, table_out, rf, d, stats2);
+    } catch (const std::bad_alloc&) { set_error("build-distances: out of memory"); return BLU_ERR_ALLOC; }
 }
 
 }  // extern "C"

@@ -430,8 +430,24 @@ class DistanceStats(C.Structure):
     _fields_ = [("n_features", C.c_uint64), ("n_samples", C.c_uint64), ("n_nonzeros", C.c_uint64), ("n_dropped", C.c_uint64)]
 
 
+class DistanceOptions(C.Structure):
+    """include/blu_pipeline.h: blu_distance_options"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("depth", C.c_uint64), ("seed", C.c_uint64),
+                ("rarefied_table_path", C.c_char_p)]
+
+
+class DistanceStats2(C.Structure):
+    """include/blu_pipeline.h: blu_distance_stats2"""
+    _fields_ = [(f, C.c_uint64) for f in ("n_features", "n_samples", "n_nonzeros", "n_dropped", "depth", "n_samples_kept",
+                                          "n_samples_dropped", "n_features_emptied", "n_reads_hashed")]
+
+
 def _bind():
     L = N.lib()
+    if hasattr(L, "blu_distance_matrix_file_with"):   # (an A/B library of an older build: BLU_CONSENSUS_LIB)
+        L.blu_distance_matrix_file_with.restype = C.c_int
+        L.blu_distance_matrix_file_with.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_int, C.c_char_p,
+                                                    C.POINTER(DistanceOptions), C.POINTER(DistanceStats2)]
     if hasattr(L, "blu_distance_matrix_file"):   # (an A/B library of an older build: BLU_CONSENSUS_LIB)
         L.blu_distance_features_from_table.restype = C.c_int
         L.blu_distance_features_from_table.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(DistanceFeatures)]
@@ -485,6 +501,24 @@ def distance_matrix_file(table_path: str, out_path: str, rank: Optional[str] = N
     if rc != N.BLU_OK:
         raise N.BluError(rc, "blu_distance_matrix_file")
     return {f: int(getattr(st, f)) for f, _ in DistanceStats._fields_}
+
+
+def distance_matrix_file_with(table_path: str, out_path: str, rank: Optional[str] = None, metric: str = "bray-curtis",
+                              drop_unclassified: bool = False, device: int = 0, depth: int = 0, seed: int = 0,
+                              rarefied_table: Optional[str] = None, struct_size: Optional[int] = None) -> dict:
+    """blu_distance_matrix_file_with: the same with every sample rarefied to `depth` reads first (0: not at all), the rarefied
+    features written to rarefied_table.  Returns the counts of blu_distance_stats2."""
+    if metric not in DISTANCE_METRIC:
+        raise ValueError(f"unknown metric `{metric}`: bray-curtis or jaccard")
+    opt = DistanceOptions(struct_size=C.sizeof(DistanceOptions) if struct_size is None else struct_size, depth=int(depth), seed=int(seed),
+                          rarefied_table_path=None if rarefied_table is None else rarefied_table.encode())
+    st = DistanceStats2()
+    rc = _bind().blu_distance_matrix_file_with(table_path.encode(), None if rank is None else rank.encode(), DISTANCE_METRIC[metric],
+                                               DISTANCE_DROP_UNCLASSIFIED if drop_unclassified else 0, int(device), out_path.encode(),
+                                               C.byref(opt), C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_distance_matrix_file_with")
+    return {f: int(getattr(st, f)) for f, _ in DistanceStats2._fields_}
 
 
 def ingest_only(blast_output: str, taxonomies_file: str, use_taxid: bool = False, device: int = -1):

@@ -45,7 +45,8 @@ enum blu_error {
     BLU_ERR_CUSTOM_MISSING = 5, /* Taxon::Custom without values (domain/dtos/taxon.rs:117) */
     BLU_ERR_ALLOC = 6,
     BLU_ERR_IO = 7,
-    BLU_ERR_PARSE = 8
+    BLU_ERR_PARSE = 8,
+    BLU_ERR_INTERNAL = 10       /* a result failed the library's own check (9 is BLU_ERR_REFERENCE_PANIC of blu_pipeline.h) */
 };
 
 /* domain/dtos/taxon.rs:68-87 */
@@ -550,6 +551,60 @@ typedef struct blu_sample_distance {
  * cannot be used is BLU_ERR_NO_DEVICE: there is no CPU fallback. */
 int blu_sample_distances(const blu_distance_desc* desc, blu_sample_distance* out);
 void blu_sample_distance_free(blu_sample_distance* out);
+
+/* -------------------------------------------------------------------------- */
+/* Rarefaction: every sample subsampled to one depth, without replacement (additive, ABI v5; not in the
+ * reference).  The feature CSR of blu_distance_desc in, a CSR over the same features and the kept samples out.  The rule, all in
+ * u64 with wrap-around:
+ *   mix64(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *             z ^ (z >> 31)                                    (the splitmix64 step: a bijection)
+ *   the reads of sample a are numbered 0 .. N_a - 1 along its non-zeros in feature order: feature f owns
+ *   [start_af, start_af + x_fa), start_af = the sum of x_ga over g < f
+ *   key(a, i) = mix64(i + sample_stream[a])                    (distinct for distinct i)
+ *   N_a < depth: the sample is dropped; else the `depth` reads with the smallest keys are kept, x'_fa = the kept reads among
+ *   feature f's ordinals.
+ * Kept samples are renumbered 0 .. n_kept - 1 in their order (kept_sample gives the ids they had), zero counts are removed, a
+ * feature that lost every count stays as an empty row, and every kept column sums to `depth`: the call checks that on the host
+ * and returns BLU_ERR_INTERNAL naming the sample rather than a wrong table.  No sample reaching `depth` is not an error here:
+ * n_kept = 0, and no device is asked for.  Selected on the device (csrc/rarefy_kernel.hip): a radix select of the depth-th smallest key over tiles of
+ * BLU_RAREFY_TILE reads, then a count per non-zero; integers only, nothing depends on launch geometry or atomic order. */
+#define BLU_RAREFY_TILE 65536u                /* reads of one block */
+#define BLU_RAREFY_MAX_READS (1ull << 36)     /* the reads of the samples that reach `depth`, together: above is refused */
+typedef struct blu_rarefy_desc {
+    uint32_t struct_size;          /* sizeof(blu_rarefy_desc) */
+    int32_t device;                /* HIP device ordinal */
+    uint64_t n_features;           /* as in blu_distance_desc, and so are the next five */
+    uint32_t n_samples;
+    uint32_t reserved;
+    const uint64_t* row_ptr;
+    const uint32_t* sample;
+    const uint64_t* count;
+    const uint64_t* sample_stream; /* [n_samples] host: blu_rarefy_stream(seed, name) of each sample; no two equal */
+    uint64_t depth;                /* >= 1 */
+    void* stream;                  /* a hipStream_t the call waits for before it starts (NULL = default) */
+} blu_rarefy_desc;                 /* 72 bytes */
+
+typedef struct blu_rarefied {
+    uint64_t n_features;
+    uint32_t n_kept;
+    uint32_t reserved;
+    uint32_t* kept_sample;         /* [n_kept] ids in the input, ascending */
+    uint64_t* row_ptr;             /* [n_features + 1] */
+    uint32_t* sample;              /* [row_ptr[n_features]] 0 .. n_kept - 1, ascending within a feature */
+    uint64_t* count;               /* [row_ptr[n_features]] > 0 */
+    double t_device_ms;            /* transpose, select and count on the device, by events; 0 when nothing was launched */
+} blu_rarefied;                    /* every array malloc'd by the library: blu_rarefied_free */
+
+/* mix64(mix64(seed) ^ fnv1a64(name[0, len))): FNV-1a with offset 0xcbf29ce484222325 and prime 0x100000001b3.  The name is hashed,
+ * not the column index: re-ordering or subsetting the columns does not change a sample's draw. */
+uint64_t blu_rarefy_stream(uint64_t seed, const char* name, uint64_t len);
+
+/* Host arrays in, host arrays out; synchronous.  BLU_ERR_INVALID_ARG before any device is asked for: whatever
+ * blu_sample_distances refuses about the CSR, a struct_size the library does not know, depth = 0, a NULL sample_stream, two
+ * samples with the same stream (naming both), a sample of 2^32 reads or more (naming it), more than BLU_RAREFY_MAX_READS reads
+ * in the samples that reach `depth`.  A device that cannot be used is BLU_ERR_NO_DEVICE: there is no CPU fallback. */
+int blu_sample_rarefy(const blu_rarefy_desc* desc, blu_rarefied* out);
+void blu_rarefied_free(blu_rarefied* out);
 
 #ifdef __cplusplus
 }

@@ -631,6 +631,35 @@ typedef struct blu_distance_stats {
 int blu_distance_matrix_file(const char* table_path, const char* rank, int metric, uint32_t flags, int device, const char* out_path,
                              blu_distance_stats* stats);
 
+/* The same with every sample rarefied to one depth first (`build-distances --rarefy`): features ->
+ * blu_sample_rarefy with sample_stream[a] = blu_rarefy_stream of the seed and column a's name -> blu_sample_distances on the kept
+ * samples -> the matrix with the kept names.  options NULL, or depth = 0 without a table path: exactly blu_distance_matrix_file.
+ * rarefied_table_path: the rarefied features as text, `#feature<TAB>total<TAB><kept sample names...>`, then one line per feature
+ * that is still non-zero, in feature order: its text, the line's sum, one u64 cell per kept sample; lines end in `\n`.
+ * BLU_ERR_INVALID_ARG on top of what the steps refuse: a struct_size the library does not know, a table path with depth = 0, two
+ * columns of one name (naming both), no sample that reaches `depth` (the message says the largest total).  Nothing is written
+ * unless every step succeeds. */
+typedef struct blu_distance_options {
+    uint32_t struct_size;             /* sizeof(blu_distance_options) */
+    uint32_t reserved;
+    uint64_t depth;                   /* 0 = no rarefaction */
+    uint64_t seed;
+    const char* rarefied_table_path;  /* or NULL */
+} blu_distance_options;               /* 32 bytes */
+typedef struct blu_distance_stats2 {
+    uint64_t n_features;              /* features kept; with a depth: those still non-zero after rarefaction */
+    uint64_t n_samples;               /* with a depth: the kept samples */
+    uint64_t n_nonzeros;              /* with a depth: of the rarefied features */
+    uint64_t n_dropped;               /* all-zero features of the table left out */
+    uint64_t depth;
+    uint64_t n_samples_kept;
+    uint64_t n_samples_dropped;
+    uint64_t n_features_emptied;      /* features that lost every count */
+    uint64_t n_reads_hashed;          /* the reads of the kept samples before rarefaction: what the device pass walks */
+} blu_distance_stats2;
+int blu_distance_matrix_file_with(const char* table_path, const char* rank, int metric, uint32_t flags, int device, const char* out_path,
+                                  const blu_distance_options* options, blu_distance_stats2* stats2);
+
 /* CustomTaxon::from_file (domain/dtos/taxon.rs:28-66): .yaml or .json with the eight cutoff fields. */
 int blu_custom_taxon_from_file(const char* path, blu_cutoff_config* cfg);
 
