@@ -16,6 +16,12 @@
 // read off the handle, no pass over the records) at load <= 1/2 and
 // gives up (flag) on a probe longer than REPORT_PROBE_FIRST; the table is then rebuilt from zero at 2 P slots, where a
 // probe always ends (load <= 1/2).  No count is ever dropped: a table that cannot be allocated is BLU_ERR_ALLOC.
+//
+// The per-sample table (sample_cells) and the table from count rows (count_cells) are counted here too, and the three share
+// what is not their own counting: the two cell kernels decode_record (what a record is) and their LDS cell table; all
+// three report_compact, TableRun (the tables, the attempt loop, flag_error), compact_table and parents_first on the way
+// back, and entry_begin / stage_records in front of the three C entries.  report_paths spells the decode and the walk out
+// (see there).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,8 +43,9 @@ constexpr uint32_t RQ = 4;                      // queries per thread
 constexpr uint32_t LDS_SLOTS = 2048;            // block-local leaf table (24 KB)
 constexpr uint32_t LDS_PROBE = 8;
 constexpr uint32_t REPORT_PROBE_FIRST = 128;
-constexpr uint32_t FLAG_OVERFLOW = 1u, FLAG_BAD_RECORD = 2u;
-constexpr uint32_t FLAG_BAD_NODE = 16u;              // (4 and 8 are the sample table's)
+// ctl[2]: OVERFLOW starts the next attempt, the others refuse the call (flag_error).  BAD_SAMPLE is the two cell kernels',
+// BAD_ROW count_cells'.
+constexpr uint32_t FLAG_OVERFLOW = 1u, FLAG_BAD_RECORD = 2u, FLAG_BAD_SAMPLE = 4u, FLAG_BAD_ROW = 8u, FLAG_BAD_NODE = 16u;
 constexpr uint32_t CTL_WORDS = 7, CTL_BAD_NODE = 6;   // ctl[]: what every entry point allocates and clears
 
 struct ReportDev {
@@ -56,7 +63,8 @@ struct ReportDev {
     unsigned long long* direct;   // [cap]
     uint32_t cap_mask;
     uint32_t max_probe;
-    unsigned long long* ctl;      // [CTL_WORDS] {unclassified, unplaced, flags, bad query, .., .., the query of a bad node}
+    // [CTL_WORDS] {unclassified, unplaced, flags, the query of a bad record, of a bad sample, of a bad row, of a bad node}
+    unsigned long long* ctl;
 };
 
 __device__ __forceinline__ uint32_t mix_key(unsigned long long k) {   // murmur3 fmix64
@@ -88,6 +96,57 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
     return v;
 }
 
+// What record q is.  REC_NO_TAXON: taxon null (status >= 2); REC_BAD: a taxon, but its reference row names no taxonomy row;
+// REC_NO_LEVEL: taxonomy "" (no selected level inside the lineage); REC_PATH: lin is the lineage row, len its length cut to
+// max_depth, m the level mask cut to len (not 0).  The flag and ctl[] of a bad record are the caller's to write.
+enum RecordKind : uint32_t { REC_NO_TAXON, REC_BAD, REC_NO_LEVEL, REC_PATH };
+struct Record {
+    RecordKind kind;
+    const uint32_t* lin;
+    uint32_t len;
+    unsigned long long m;
+};
+
+__device__ __forceinline__ Record decode_record(const ReportDev& d, uint64_t q) {
+    const uint4* rp = reinterpret_cast<const uint4*>(d.recs + q);
+    const uint4 a = rp[0], b = rp[1];
+    const uint32_t status = a.x & 0xFFu;
+    const uint32_t ref_row = a.w;
+    const unsigned long long mask = (unsigned long long)b.x | ((unsigned long long)b.y << 32);
+    if (status >= 2) return {REC_NO_TAXON, nullptr, 0, 0};
+    const uint64_t idx = d.by_query ? q : (uint64_t)ref_row;
+    uint32_t row = REPORT_NONE;
+    if (idx < d.n_rows) row = d.row_src[idx * d.row_stride];
+    const uint32_t pos = row & ((1u << BLU_ROW_BITS) - 1u);
+    if (row == BLU_UNMATCHED_TAXID || pos >= d.n_tax) return {REC_BAD, nullptr, 0, 0};
+    const uint32_t* lin = d.lin + (uint64_t)pos * d.stride;
+    const uint32_t len = min(lin[0] & 0xFFu, d.max_depth);
+    const unsigned long long m = len >= 64 ? mask : mask & ((1ull << len) - 1ull);
+    return {m ? REC_PATH : REC_NO_LEVEL, lin, len, m};
+}
+
+// One lane's walk (sample_cells): the selected levels of a REC_PATH record interned in turn, each(path id) called for every
+// one reached.
+// stopped: 0 and `leaf` is the id of the last level, or the flag that ended the walk (FLAG_BAD_NODE, FLAG_OVERFLOW).
+struct Walk { uint32_t leaf, stopped; };
+
+template <class Each>
+__device__ __forceinline__ Walk walk_levels(const ReportDev& d, const Record& r, Each&& each) {
+    uint32_t path = REPORT_NONE;
+    for (uint32_t j = 0; j < r.len; ++j) {
+        if (!((r.m >> j) & 1ull)) continue;
+        const uint32_t node = r.lin[d.node_base + j];
+        if (reserved_first(path, node)) return {REPORT_NONE, FLAG_BAD_NODE};
+        path = intern(d, path, node);
+        if (path == REPORT_NONE) return {REPORT_NONE, FLAG_OVERFLOW};
+        each(path);
+    }
+    return {path, 0u};
+}
+
+// The decode and the walk are written out here, not taken from decode_record / walk_levels: around the helpers the
+// compiler lays the four-query loop out with more branches and waits (or does not unroll it), and this kernel, the hottest
+// of the file, measured 1 to 9 % slower.  A change to the record layout or the refusal rules is made here and in decode_record.
 __global__ __launch_bounds__(RB) void report_paths(ReportDev d) {
     __shared__ uint32_t s_key[LDS_SLOTS];
     __shared__ unsigned long long s_cnt[LDS_SLOTS];
@@ -176,7 +235,8 @@ __global__ void report_flags(const unsigned long long* __restrict__ keys, uint64
     else if (i == cap) used[i] = 0;
 }
 
-// the occupied slots in slot order, parents renamed to their index in that order
+// the occupied path slots in slot order, parents renamed to their index in that order; direct null (the per-sample tables
+// count in cells): 0
 __global__ void report_compact(const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ direct,
                                const uint32_t* __restrict__ at, uint64_t cap, blu_report_path* __restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -187,7 +247,7 @@ __global__ void report_compact(const unsigned long long* __restrict__ keys, cons
     blu_report_path p;
     p.node = (uint32_t)k;
     p.parent = parent == REPORT_NONE ? REPORT_NONE : at[parent];
-    p.direct = direct[i];
+    p.direct = direct ? direct[i] : 0;
     p.clade = 0;
     out[at[i]] = p;
 }
@@ -201,10 +261,9 @@ __global__ void report_compact(const unsigned long long* __restrict__ keys, cons
 // no path table reaches (the tables are limited to 2^31 slots).
 constexpr uint32_t CELL_UNCLASSIFIED = 0xFFFFFFFEu, CELL_UNPLACED = 0xFFFFFFFDu;
 constexpr uint32_t CELL_LDS_SLOTS = 2048;       // block-local cell table (32 KB)
-constexpr uint32_t FLAG_BAD_SAMPLE = 4u;
 
 struct SampleDev {
-    ReportDev r;                    // the report's walk and path table (r.direct is not used); r.ctl[4]: a bad sample's query
+    ReportDev r;                    // the report's walk and path table (r.direct is not used)
     const uint32_t* sample_of;      // [n_queries]
     uint32_t n_samples;
     uint32_t cell_mask;
@@ -251,66 +310,44 @@ __device__ __forceinline__ uint32_t block_cell_add(unsigned long long* s_key, un
     return cell_flush(d, key, w);
 }
 
-__global__ __launch_bounds__(RB) void sample_cells(SampleDev d) {
-    __shared__ unsigned long long s_key[CELL_LDS_SLOTS];
-    __shared__ unsigned long long s_cnt[CELL_LDS_SLOTS];
+// a cell kernel begins: the block's LDS table empty
+__device__ __forceinline__ void block_cells_clear(unsigned long long* s_key, unsigned long long* s_cnt) {
     for (uint32_t i = threadIdx.x; i < CELL_LDS_SLOTS; i += RB) { s_key[i] = REPORT_EMPTY; s_cnt[i] = 0; }
     __syncthreads();
-    uint32_t flags = 0;
-    // block-local table first, global memory when it is crowded (w > 0: a zero weight leaves no cell behind)
-    auto add = [&](uint32_t path, uint32_t s, unsigned long long w) { flags |= block_cell_add(s_key, s_cnt, d, path, s, w); };
-    const uint64_t base = (uint64_t)blockIdx.x * (RB * RQ) + threadIdx.x;
-    for (uint32_t k = 0; k < RQ; ++k) {
-        const uint64_t q = base + (uint64_t)k * RB;
-        if (q >= d.r.n_queries) break;
-        const uint4* rp = reinterpret_cast<const uint4*>(d.r.recs + q);
-        const uint4 a = rp[0], b = rp[1];
-        const uint32_t s = d.sample_of[q];
-        if (s >= d.n_samples) { flags |= FLAG_BAD_SAMPLE; d.r.ctl[4] = q; continue; }
-        const uint32_t status = a.x & 0xFFu;
-        const uint32_t ref_row = a.w;
-        const unsigned long long mask = (unsigned long long)b.x | ((unsigned long long)b.y << 32);
-        const unsigned long long w = d.r.weight ? (unsigned long long)d.r.weight[q] : 1ull;
-        if (status >= 2) { if (w) add(CELL_UNCLASSIFIED, s, w); continue; }   // taxon: null
-        const uint64_t idx = d.r.by_query ? q : (uint64_t)ref_row;
-        uint32_t row = REPORT_NONE;
-        if (idx < d.r.n_rows) row = d.r.row_src[idx * d.r.row_stride];
-        const uint32_t pos = row & ((1u << BLU_ROW_BITS) - 1u);
-        if (row == BLU_UNMATCHED_TAXID || pos >= d.r.n_tax) { flags |= FLAG_BAD_RECORD; d.r.ctl[3] = q; continue; }
-        const uint32_t* lin = d.r.lin + (uint64_t)pos * d.r.stride;
-        const uint32_t len = min(lin[0] & 0xFFu, d.r.max_depth);
-        const unsigned long long m = len >= 64 ? mask : mask & ((1ull << len) - 1ull);
-        if (m == 0) { if (w) add(CELL_UNPLACED, s, w); continue; }           // taxonomy: ""
-        uint32_t path = REPORT_NONE;
-        for (uint32_t j = 0; j < len; ++j) {
-            if (!((m >> j) & 1ull)) continue;
-            const uint32_t node = lin[d.r.node_base + j];
-            if (reserved_first(path, node)) { flags |= FLAG_BAD_NODE; d.r.ctl[CTL_BAD_NODE] = q; break; }
-            path = intern(d.r, path, node);
-            if (path == REPORT_NONE) { flags |= FLAG_OVERFLOW; break; }
-            if (w) add(path, s, w);
-        }
-    }
+}
+
+// ... and ends: the block's sums reach global memory, the thread's flags ctl[2]
+__device__ __forceinline__ void block_cells_flush(const unsigned long long* s_key, const unsigned long long* s_cnt, const SampleDev& d,
+                                                  uint32_t flags) {
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < CELL_LDS_SLOTS; i += RB)
         if (s_key[i] != REPORT_EMPTY && s_cnt[i]) flags |= cell_flush(d, s_key[i], s_cnt[i]);
     if (flags) atomicOr(reinterpret_cast<unsigned int*>(d.r.ctl + 2), flags);
 }
 
-// the occupied path slots in slot order, parents renamed to their index in that order (report_compact without counts)
-__global__ void sample_paths_compact(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ at, uint64_t cap,
-                                     blu_report_path* __restrict__ out) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= cap) return;
-    const unsigned long long k = keys[i];
-    if (k == REPORT_EMPTY) return;
-    const uint32_t parent = (uint32_t)(k >> 32);
-    blu_report_path p;
-    p.node = (uint32_t)k;
-    p.parent = parent == REPORT_NONE ? REPORT_NONE : at[parent];
-    p.direct = 0;
-    p.clade = 0;
-    out[at[i]] = p;
+__global__ __launch_bounds__(RB) void sample_cells(SampleDev d) {
+    __shared__ unsigned long long s_key[CELL_LDS_SLOTS];
+    __shared__ unsigned long long s_cnt[CELL_LDS_SLOTS];
+    block_cells_clear(s_key, s_cnt);
+    uint32_t flags = 0;
+    // block-local table first, global memory when it is crowded (w > 0: a zero weight leaves no cell behind)
+    auto add = [&](uint32_t path, uint32_t s, unsigned long long w) { if (w) flags |= block_cell_add(s_key, s_cnt, d, path, s, w); };
+    const uint64_t base = (uint64_t)blockIdx.x * (RB * RQ) + threadIdx.x;
+    for (uint32_t k = 0; k < RQ; ++k) {
+        const uint64_t q = base + (uint64_t)k * RB;
+        if (q >= d.r.n_queries) break;
+        const uint32_t s = d.sample_of[q];
+        const Record rec = decode_record(d.r, q);   // (ahead of the sample's check: its loads go out beside the sample's)
+        if (s >= d.n_samples) { flags |= FLAG_BAD_SAMPLE; d.r.ctl[4] = q; continue; }
+        const unsigned long long w = d.r.weight ? (unsigned long long)d.r.weight[q] : 1ull;
+        if (rec.kind == REC_NO_TAXON) { add(CELL_UNCLASSIFIED, s, w); continue; }
+        if (rec.kind == REC_BAD) { flags |= FLAG_BAD_RECORD; d.r.ctl[3] = q; continue; }
+        if (rec.kind == REC_NO_LEVEL) { add(CELL_UNPLACED, s, w); continue; }
+        const Walk end = walk_levels(d.r, rec, [&](uint32_t path) { add(path, s, w); });
+        flags |= end.stopped;
+        if (end.stopped == FLAG_BAD_NODE) d.r.ctl[CTL_BAD_NODE] = q;
+    }
+    block_cells_flush(s_key, s_cnt, d, flags);
 }
 
 // the occupied cells in slot order, their path slots renamed to the compacted path index
@@ -338,18 +375,16 @@ __global__ void sample_cells_compact(const unsigned long long* __restrict__ keys
 // under the two reserved path ids.  All adds are u64 integer adds: exact, whatever the order.
 constexpr uint32_t COUNT_Q = 32;
 constexpr uint32_t COUNT_Q_BLOCK = COUNT_Q * (RB / 64);
-constexpr uint32_t FLAG_BAD_ROW = 8u;
 
 struct CountDev {
-    SampleDev s;                  // s.sample_of and s.r.weight are not read; s.r.ctl[5]: the query of a bad row
+    SampleDev s;                  // s.sample_of and s.r.weight are not read
     CountRows rows;
 };
 
 __global__ __launch_bounds__(RB) void count_cells(CountDev d) {
     __shared__ unsigned long long s_key[CELL_LDS_SLOTS];
     __shared__ unsigned long long s_cnt[CELL_LDS_SLOTS];
-    for (uint32_t i = threadIdx.x; i < CELL_LDS_SLOTS; i += RB) { s_key[i] = REPORT_EMPTY; s_cnt[i] = 0; }
-    __syncthreads();
+    block_cells_clear(s_key, s_cnt);
     const ReportDev& r = d.s.r;
     uint32_t flags = 0;
     const uint32_t lane = threadIdx.x & 63u;
@@ -360,40 +395,26 @@ __global__ __launch_bounds__(RB) void count_cells(CountDev d) {
         if (q >= r.n_queries) break;
         const uint64_t lo = d.rows.row_ptr[q], hi = d.rows.row_ptr[q + 1];
         if (lo > hi || hi > d.rows.nnz) { flags |= FLAG_BAD_ROW; if (lane == 0) r.ctl[5] = q; continue; }
-        const uint4* rp = reinterpret_cast<const uint4*>(r.recs + q);
-        const uint4 a = rp[0], b = rp[1];
-        const uint32_t status = a.x & 0xFFu;
-        const uint32_t ref_row = a.w;
-        const unsigned long long mask = (unsigned long long)b.x | ((unsigned long long)b.y << 32);
-        uint32_t mine = CELL_UNCLASSIFIED;      // lane k: the id of the query's k-th path
+        const Record rec = decode_record(r, q);
+        if (rec.kind == REC_BAD) { flags |= FLAG_BAD_RECORD; if (lane == 0) r.ctl[3] = q; continue; }
+        uint32_t mine = rec.kind == REC_NO_TAXON ? CELL_UNCLASSIFIED : CELL_UNPLACED;   // lane k: the id of the query's k-th path
         uint32_t n_levels = 1;
-        if (status < 2) {
-            const uint64_t idx = r.by_query ? q : (uint64_t)ref_row;
-            uint32_t row = REPORT_NONE;
-            if (idx < r.n_rows) row = r.row_src[idx * r.row_stride];
-            const uint32_t pos = row & ((1u << BLU_ROW_BITS) - 1u);
-            if (row == BLU_UNMATCHED_TAXID || pos >= r.n_tax) { flags |= FLAG_BAD_RECORD; if (lane == 0) r.ctl[3] = q; continue; }
-            const uint32_t* lin = r.lin + (uint64_t)pos * r.stride;
-            const uint32_t len = min(lin[0] & 0xFFu, r.max_depth);
-            const unsigned long long m = len >= 64 ? mask : mask & ((1ull << len) - 1ull);
-            mine = CELL_UNPLACED;
-            if (m != 0) {
-                const uint32_t node = lane < len ? lin[r.node_base + lane] : 0u;   // lane j: the node of level j
-                uint32_t path = REPORT_NONE;
-                bool bad_node = false;
-                n_levels = 0;
-                for (unsigned long long t = m; t; t &= t - 1ull, ++n_levels) {
-                    const uint32_t nd = __shfl(node, __ffsll(t) - 1, 64);
-                    if (reserved_first(path, nd)) { bad_node = true; break; }
-                    uint32_t p = REPORT_NONE;
-                    if (lane == 0) p = intern(r, path, nd);
-                    path = __shfl(p, 0, 64);
-                    if (path == REPORT_NONE) break;
-                    if (lane == n_levels) mine = path;
-                }
-                if (bad_node) { flags |= FLAG_BAD_NODE; if (lane == 0) r.ctl[CTL_BAD_NODE] = q; continue; }
-                if (path == REPORT_NONE) { flags |= FLAG_OVERFLOW; continue; }
+        if (rec.kind == REC_PATH) {
+            const uint32_t node = lane < rec.len ? rec.lin[r.node_base + lane] : 0u;   // lane j: the node of level j
+            uint32_t path = REPORT_NONE;
+            bool bad_node = false;
+            n_levels = 0;
+            for (unsigned long long t = rec.m; t; t &= t - 1ull, ++n_levels) {
+                const uint32_t nd = __shfl(node, __ffsll(t) - 1, 64);
+                if (reserved_first(path, nd)) { bad_node = true; break; }
+                uint32_t p = REPORT_NONE;
+                if (lane == 0) p = intern(r, path, nd);
+                path = __shfl(p, 0, 64);
+                if (path == REPORT_NONE) break;
+                if (lane == n_levels) mine = path;
             }
+            if (bad_node) { flags |= FLAG_BAD_NODE; if (lane == 0) r.ctl[CTL_BAD_NODE] = q; continue; }
+            if (path == REPORT_NONE) { flags |= FLAG_OVERFLOW; continue; }
         }
         // lane -> (non-zero `nz` of the step, level `lv`); the lanes past per * n_levels idle
         const uint32_t per = 64u / n_levels;
@@ -407,10 +428,7 @@ __global__ __launch_bounds__(RB) void count_cells(CountDev d) {
             if (w) flags |= block_cell_add(s_key, s_cnt, d.s, path, s, w);   // (a zero leaves no cell)
         }
     }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < CELL_LDS_SLOTS; i += RB)
-        if (s_key[i] != REPORT_EMPTY && s_cnt[i]) flags |= cell_flush(d.s, s_key[i], s_cnt[i]);
-    if (flags) atomicOr(reinterpret_cast<unsigned int*>(r.ctl + 2), flags);
+    block_cells_flush(s_key, s_cnt, d.s, flags);
 }
 
 // out[0]: P, the bound on the paths (report_bound); out[1]: sum of popcount(level_mask) * non-zeros of the row over the
@@ -436,11 +454,182 @@ __global__ __launch_bounds__(RB) void count_bound(const blu_result* __restrict__
     if (threadIdx.x == 0 && (s[0] | s[1])) { atomicAdd(out, s[0]); atomicAdd(out + 1, s[1]); }
 }
 
+// ---- host side: the three entries share their tables, their attempts and the way back ------------------------------------
+
 uint64_t next_pow2(uint64_t x) { uint64_t c = 1; while (c < x) c <<= 1; return c; }
 
-// paths[] (parents named by index, in any order) -> at[i], the position of path i when parents come first: depth order,
-// input order inside a depth
-void parents_first(const std::vector<blu_report_path>& paths, std::vector<uint32_t>& at) {
+// the slots of a table that holds up to n keys at load <= 1/2
+uint64_t table_slots(uint64_t n) { return std::max<uint64_t>(next_pow2(2 * n), 1024); }
+
+// the first attempt's guess at the distinct paths: read off the handle, no pass over the records
+uint64_t path_guess(const blu_taxonomy* tax, uint64_t nq) {
+    return std::min<uint64_t>(nq * std::max<uint32_t>(tax->max_depth, 1), 2 * tax->n_tax + 4096);
+}
+
+dim3 bound_grid(uint64_t nq) { return dim3((unsigned)std::min<uint64_t>((nq + RB - 1) / RB, 4096)); }
+
+// everything of ReportDev but the tables of an attempt (TableRun::point)
+ReportDev report_dev(const blu_taxonomy* tax, const ReportInput& in, unsigned long long* d_ctl) {
+    ReportDev d{};
+    d.lin = tax->d_lin; d.n_tax = tax->n_tax; d.stride = tax->dev_stride; d.node_base = tax->node_base;
+    d.max_depth = tax->max_depth;
+    d.recs = in.recs; d.n_queries = in.n_queries; d.row_src = in.row_src; d.n_rows = in.n_rows; d.row_stride = in.row_stride;
+    d.by_query = in.by_query ? 1u : 0u; d.weight = in.weight; d.ctl = d_ctl;
+    return d;
+}
+
+// ctl[2] -> the refusal, in the one order that is every entry's (an entry never raises a flag it does not have)
+int flag_error(const char* who, const unsigned long long* ctl, uint32_t n_samples, uint64_t nnz) {
+    const uint32_t flags = (uint32_t)ctl[2];
+    if (flags & FLAG_BAD_ROW)
+        set_error("%s: query %llu has a row_ptr that decreases or ends past the %llu non-zeros", who, ctl[5], (unsigned long long)nnz);
+    else if (flags & FLAG_BAD_SAMPLE)
+        set_error("%s: query %llu has a sample id that is not below n_samples = %u", who, ctl[4], n_samples);
+    else if (flags & FLAG_BAD_RECORD)
+        set_error("%s: record %llu has a taxon (status 0 / 1) but its reference row names no taxonomy row", who, ctl[3]);
+    else if (flags & FLAG_BAD_NODE)
+        set_error("%s: record %llu has a path that begins with node id 0xFFFFFFFF, which no path may begin with", who, ctl[CTL_BAD_NODE]);
+    else return BLU_OK;
+    return BLU_ERR_INVALID_ARG;
+}
+
+// One entry's device state and the cycle all three run: allocate the tables, clear them, launch, read ctl back, refuse
+// (flag_error) or start again from zero at the sizes `resize` sets.  cells: a cell table and per-sample counters beside the
+// path table (the two per-sample entries); else the path table carries direct counts (the report).  The first sizes are
+// the caller's to set (cap, ccap) between begin() and run().
+struct TableRun {
+    HipPolicy pol;                // pol.who is the prefix of every message: "report", "sample table", "count table"
+    DeviceArena mem{pol};
+    const bool cells;
+    const uint32_t n_samples;
+    const uint64_t nnz;           // (for count_cells' refusal of a row)
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the device work: begin() ... stop()
+    unsigned long long *d_ctl = nullptr, *keys = nullptr, *direct = nullptr, *ckeys = nullptr, *cval = nullptr, *fixed = nullptr;
+    uint64_t cap = 0, ccap = 0;
+    uint32_t max_probe = REPORT_PROBE_FIRST, attempts = 0;
+    unsigned long long ctl[CTL_WORDS] = {};    // of the last attempt
+
+    TableRun(const char* who, bool cells, uint32_t n_samples = 0, uint64_t nnz = 0)
+        : pol{who, BLU_ERR_ALLOC}, cells(cells), n_samples(n_samples), nnz(nnz) {}
+    ~TableRun() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
+
+    uint64_t fixed_bytes() const { return 2 * (uint64_t)n_samples * 8; }
+
+    int begin() {
+        HIP_CHECK(pol, hipEventCreate(&ev0));
+        HIP_CHECK(pol, hipEventCreate(&ev1));
+        HIP_CHECK(pol, mem.alloc(&d_ctl, sizeof ctl, "counters"));
+        if (cells) HIP_CHECK(pol, mem.alloc(&fixed, fixed_bytes(), "per-sample counters"));
+        HIP_CHECK(pol, hipEventRecord(ev0, nullptr));
+        return BLU_OK;
+    }
+
+    // the tables of the attempt at hand
+    void point(ReportDev& r) const { r.keys = keys; r.direct = direct; r.cap_mask = (uint32_t)(cap - 1); r.max_probe = max_probe; }
+    void point(SampleDev& s) const {
+        point(s.r);
+        s.cell_keys = ckeys; s.cell_val = cval; s.cell_mask = (uint32_t)(ccap - 1); s.n_samples = n_samples; s.fixed = fixed;
+    }
+
+    // launch(): the entry's kernel on the tables of this attempt; resize(): cap and ccap from the bounds, after an overflow
+    template <class Launch, class Resize>
+    int run(Launch&& launch, Resize&& resize) {
+        for (;;) {
+            ++attempts;
+            // (with cells, path ids below 2^31: the two ids above are the fixed rows' in the cell keys)
+            if (!cells && cap > (1ull << 32)) {
+                set_error("%s: a table of %llu slots exceeds 32-bit path ids", pol.who, (unsigned long long)cap);
+                return BLU_ERR_ALLOC;
+            }
+            if (cells && (cap > (1ull << 31) || ccap > (1ull << 32))) {
+                set_error("%s: tables of %llu / %llu slots exceed 32-bit ids", pol.who, (unsigned long long)cap, (unsigned long long)ccap);
+                return BLU_ERR_ALLOC;
+            }
+            HIP_CHECK(pol, mem.alloc(&keys, cap * 8, "path table"));
+            if (cells) {
+                HIP_CHECK(pol, mem.alloc(&ckeys, ccap * 8, "cell table"));
+                HIP_CHECK(pol, mem.alloc(&cval, ccap * 8, "cell table"));
+            } else {
+                HIP_CHECK(pol, mem.alloc(&direct, cap * 8, "path table"));
+            }
+            HIP_CHECK(pol, hipMemsetAsync(keys, 0xFF, cap * 8, nullptr));
+            if (cells) {
+                HIP_CHECK(pol, hipMemsetAsync(ckeys, 0xFF, ccap * 8, nullptr));
+                HIP_CHECK(pol, hipMemsetAsync(cval, 0, ccap * 8, nullptr));
+                HIP_CHECK(pol, hipMemsetAsync(fixed, 0, fixed_bytes(), nullptr));
+            } else {
+                HIP_CHECK(pol, hipMemsetAsync(direct, 0, cap * 8, nullptr));
+            }
+            HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, sizeof ctl, nullptr));
+            launch();
+            HIP_CHECK(pol, hipGetLastError());
+            HIP_CHECK(pol, hipMemcpy(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+            if (const int rc = flag_error(pol.who, ctl, n_samples, nnz); rc != BLU_OK) return rc;
+            if (!(ctl[2] & FLAG_OVERFLOW)) return BLU_OK;
+            if (max_probe != REPORT_PROBE_FIRST) {   // (cannot happen at load <= 1/2)
+                set_error(cells ? "%s: table overflow" : "%s: path table overflow", pol.who);
+                return BLU_ERR_HIP;
+            }
+            // an estimate was short: every table again from zero, sized from the bounds, where a probe always ends
+            mem.free(keys); mem.free(direct); mem.free(ckeys); mem.free(cval);
+            keys = direct = ckeys = cval = nullptr;
+            if (const int rc = resize(); rc != BLU_OK) return rc;
+            max_probe = (uint32_t)std::min<uint64_t>(std::max(cap, ccap), 0xFFFFFFFFull);
+        }
+    }
+
+    // P of report_bound, through ctl[0]: what the report and the sample table size their retry from
+    int path_bound(const ReportInput& in, unsigned long long* bound) {
+        HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, 8, nullptr));
+        hipLaunchKernelGGL(report_bound, bound_grid(in.n_queries), dim3(RB), 0, 0, in.recs, in.n_queries, d_ctl);
+        HIP_CHECK(pol, hipGetLastError());
+        HIP_CHECK(pol, hipMemcpy(bound, d_ctl, 8, hipMemcpyDeviceToHost));
+        return BLU_OK;
+    }
+
+    // the device work ends here: its time by the events
+    int stop(double* ms) {
+        float f = 0;
+        HIP_CHECK(pol, hipEventRecord(ev1, nullptr));
+        HIP_CHECK(pol, hipEventSynchronize(ev1));
+        HIP_CHECK(pol, hipEventElapsedTime(&f, ev0, ev1));
+        *ms = f;
+        return BLU_OK;
+    }
+};
+
+dim3 walk_grid(uint64_t nq) { return dim3((unsigned)((nq + RB * RQ - 1) / (RB * RQ))); }   // report_paths, sample_cells
+
+// A table's occupied slots, compacted on the device: at[i] = the index of slot i among them (report_flags and a scan;
+// at[cap] = their number = n), then launch(grid, block) starts the kernel that writes rows[at[i]] for every such slot.
+template <class Row>
+struct Compacted {
+    uint32_t* at = nullptr;
+    Row* rows = nullptr;
+    uint64_t n = 0;
+};
+
+template <class Row, class Launch>
+int compact_table(TableRun& T, const unsigned long long* keys, uint64_t cap, const char* ids, const char* what, Compacted<Row>* c,
+                  Launch&& launch) {
+    void* d_tmp = nullptr;
+    HIP_CHECK(T.pol, T.mem.alloc(&c->at, (cap + 1) * 4, ids));
+    hipLaunchKernelGGL(report_flags, dim3((unsigned)((cap + 1 + 255) / 256)), dim3(256), 0, 0, keys, cap, c->at);
+    HIP_CHECK(T.pol, hipGetLastError());
+    HIP_CHECK(T.pol, T.mem.alloc(&d_tmp, scan_tmp_bytes_u32(cap + 1), "scan scratch"));   // (while the flags are written)
+    HIP_CHECK(T.pol, exclusive_scan_u32(c->at, c->at, cap + 1, d_tmp));
+    uint32_t n32 = 0;
+    HIP_CHECK(T.pol, hipMemcpy(&n32, c->at + cap, 4, hipMemcpyDeviceToHost));
+    c->n = n32;
+    HIP_CHECK(T.pol, T.mem.alloc(&c->rows, c->n * sizeof(Row), what));
+    launch(dim3((unsigned)((cap + 255) / 256)), dim3(256));
+    HIP_CHECK(T.pol, hipGetLastError());
+    return BLU_OK;
+}
+
+// paths[] (parents named by index, in any order) -> o[], parents first (depth order, input order inside a depth) and
+// renamed to their place in o; at[i]: the place of path i
+void parents_first(const std::vector<blu_report_path>& paths, std::vector<uint32_t>& at, blu_report_path* o) {
     const uint64_t n_paths = paths.size();
     const uint32_t NONE = REPORT_NONE;
     std::vector<uint8_t> depth(n_paths, 0xFF);
@@ -456,98 +645,62 @@ void parents_first(const std::vector<blu_report_path>& paths, std::vector<uint32
     for (uint32_t k = 0; k < BLU_MAX_DEPTH; ++k) first[k + 1] += first[k];
     at.resize(n_paths);
     for (uint64_t i = 0; i < n_paths; ++i) at[i] = (uint32_t)first[depth[i]]++;
+    for (uint64_t i = 0; i < n_paths; ++i) {
+        blu_report_path p = paths[i];
+        p.parent = p.parent == NONE ? NONE : at[p.parent];
+        o[at[i]] = p;
+    }
 }
 
-// What a count pass leaves on the device: both tables of its last attempt, the per-sample counters, the events around the
-// device work (ev0 recorded; ev1 is recorded here, after the compaction).
-struct SampleTables {
-    unsigned long long *keys = nullptr, *ckeys = nullptr, *cval = nullptr, *fixed = nullptr;
-    uint64_t cap = 0, ccap = 0;
-    uint32_t attempts = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~SampleTables() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
-};
-
-// The tables -> blu_sample_table: the occupied slots compacted on the device, then ordered on the host.  Shared by
-// sample_table_device and sample_table_counts_device.
-int sample_table_finish(HipPolicy& pol, DeviceArena& mem, const SampleTables& t, uint32_t n_samples, blu_sample_table* out) {
-    unsigned long long *const d_keys = t.keys, *const d_ckeys = t.ckeys, *const d_cval = t.cval, *const d_fixed = t.fixed;
-    const uint64_t cap = t.cap, ccap = t.ccap;
-    uint32_t *d_at = nullptr, *d_cat = nullptr;
-    void* d_tmp = nullptr;
-    blu_report_path* d_paths = nullptr;
-    blu_sample_cell* d_cells = nullptr;
-    uint64_t n_paths = 0, n_cells = 0;
-    std::vector<blu_report_path> paths;
-    std::vector<blu_sample_cell> cells;
+// The tables of a per-sample run -> blu_sample_table: the occupied slots compacted on the device, then ordered on the host.
+// Shared by sample_table_device and sample_table_counts_device.
+int sample_table_finish(TableRun& T, blu_sample_table* out) {
+    HipPolicy& pol = T.pol;
+    const uint32_t n_samples = T.n_samples;
+    Compacted<blu_report_path> P;
+    Compacted<blu_sample_cell> C;
+    if (const int rc = compact_table(T, T.keys, T.cap, "path ids", "paths", &P, [&](dim3 g, dim3 b) {
+            hipLaunchKernelGGL(report_compact, g, b, 0, 0, T.keys, (const unsigned long long*)nullptr, P.at, T.cap, P.rows);
+        }); rc != BLU_OK) return rc;
+    if (const int rc = compact_table(T, T.ckeys, T.ccap, "cell ids", "cells", &C, [&](dim3 g, dim3 b) {
+            hipLaunchKernelGGL(sample_cells_compact, g, b, 0, 0, T.ckeys, T.cval, C.at, P.at, T.ccap, C.rows);
+        }); rc != BLU_OK) return rc;
+    if (const int rc = T.stop(&out->t_device_ms); rc != BLU_OK) return rc;
+    const uint64_t n_paths = P.n, n_cells = C.n;
+    std::vector<blu_report_path> paths(n_paths);
+    std::vector<blu_sample_cell> cells(n_cells);
     std::vector<uint64_t> fixed(2 * (uint64_t)n_samples);
-    {
-        HIP_CHECK(pol, mem.alloc(&d_at, (cap + 1) * 4, "path ids"));
-        HIP_CHECK(pol, mem.alloc(&d_cat, (ccap + 1) * 4, "cell ids"));
-        HIP_CHECK(pol, mem.alloc(&d_tmp, scan_tmp_bytes_u32(std::max(cap, ccap) + 1), "scan scratch"));
-        hipLaunchKernelGGL(report_flags, dim3((unsigned)((cap + 1 + 255) / 256)), dim3(256), 0, 0, d_keys, cap, d_at);
-        HIP_CHECK(pol, hipGetLastError());
-        HIP_CHECK(pol, exclusive_scan_u32(d_at, d_at, cap + 1, d_tmp));
-        hipLaunchKernelGGL(report_flags, dim3((unsigned)((ccap + 1 + 255) / 256)), dim3(256), 0, 0, d_ckeys, ccap, d_cat);
-        HIP_CHECK(pol, hipGetLastError());
-        HIP_CHECK(pol, exclusive_scan_u32(d_cat, d_cat, ccap + 1, d_tmp));
-        uint32_t n32[2] = {0, 0};
-        HIP_CHECK(pol, hipMemcpy(&n32[0], d_at + cap, 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(pol, hipMemcpy(&n32[1], d_cat + ccap, 4, hipMemcpyDeviceToHost));
-        n_paths = n32[0];
-        n_cells = n32[1];
-        HIP_CHECK(pol, mem.alloc(&d_paths, n_paths * sizeof(blu_report_path), "paths"));
-        HIP_CHECK(pol, mem.alloc(&d_cells, n_cells * sizeof(blu_sample_cell), "cells"));
-        hipLaunchKernelGGL(sample_paths_compact, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, 0, d_keys, d_at, cap, d_paths);
-        HIP_CHECK(pol, hipGetLastError());
-        hipLaunchKernelGGL(sample_cells_compact, dim3((unsigned)((ccap + 255) / 256)), dim3(256), 0, 0, d_ckeys, d_cval, d_cat, d_at, ccap, d_cells);
-        HIP_CHECK(pol, hipGetLastError());
-        HIP_CHECK(pol, hipEventRecord(t.ev1, nullptr));
-        paths.resize(n_paths);
-        cells.resize(n_cells);
-        if (n_paths) HIP_CHECK(pol, hipMemcpy(paths.data(), d_paths, n_paths * sizeof(blu_report_path), hipMemcpyDeviceToHost));
-        if (n_cells) HIP_CHECK(pol, hipMemcpy(cells.data(), d_cells, n_cells * sizeof(blu_sample_cell), hipMemcpyDeviceToHost));
-        if (n_samples) HIP_CHECK(pol, hipMemcpy(fixed.data(), d_fixed, fixed.size() * 8, hipMemcpyDeviceToHost));
-        float ms = 0;
-        HIP_CHECK(pol, hipEventSynchronize(t.ev1));   // (no path, cell or sample came back: no copy has waited for the device yet)
-        HIP_CHECK(pol, hipEventElapsedTime(&ms, t.ev0, t.ev1));
-        out->t_device_ms = ms;
-    }
-    {
-        // parents first as in the report; a path's clade = the sum of its cells, direct = clade - the children's clades;
-        // the cells ordered by path (a counting sort), then by sample inside a path
-        const uint32_t NONE = REPORT_NONE;
-        std::vector<uint32_t> at;
-        parents_first(paths, at);
-        blu_report_path* o = (blu_report_path*)malloc(std::max<uint64_t>(n_paths, 1) * sizeof(blu_report_path));
-        blu_sample_cell* c = (blu_sample_cell*)malloc(std::max<uint64_t>(n_cells, 1) * sizeof(blu_sample_cell));
-        uint64_t* un = (uint64_t*)malloc(std::max<uint64_t>(fixed.size(), 1) * 8);
-        if (!o || !c || !un) { free(o); free(c); free(un); set_error("sample table: out of memory"); return BLU_ERR_ALLOC; }
-        for (uint64_t i = 0; i < n_paths; ++i) {
-            blu_report_path p = paths[i];
-            p.parent = p.parent == NONE ? NONE : at[p.parent];
-            o[at[i]] = p;
-        }
-        std::vector<uint64_t> first(n_paths + 1, 0);
-        for (const blu_sample_cell& x : cells) { o[at[x.path]].clade += x.clade; ++first[at[x.path] + 1]; }
-        for (uint64_t i = 0; i < n_paths; ++i) first[i + 1] += first[i];
-        for (const blu_sample_cell& x : cells) { blu_sample_cell y = x; y.path = at[x.path]; c[first[y.path]++] = y; }
-        for (uint64_t i = 0, lo = 0; i < n_paths; lo = first[i++])
-            if (first[i] - lo > 1) std::sort(c + lo, c + first[i], [](const blu_sample_cell& a, const blu_sample_cell& b) { return a.sample < b.sample; });
-        for (uint64_t i = 0; i < n_paths; ++i) o[i].direct = o[i].clade;
-        for (uint64_t i = n_paths; i-- > 0;)
-            if (o[i].parent != NONE) o[o[i].parent].direct -= o[i].clade;
-        std::copy(fixed.begin(), fixed.end(), un);
-        out->paths = o;
-        out->n_paths = n_paths;
-        out->cells = c;
-        out->n_cells = n_cells;
-        out->n_samples = n_samples;
-        out->unclassified = un;
-        out->unplaced = un + n_samples;
-        out->table_slots = ccap;
-        out->attempts = t.attempts;
-    }
+    HIP_CHECK(pol, DeviceArena::download(paths.data(), P.rows, n_paths));
+    HIP_CHECK(pol, DeviceArena::download(cells.data(), C.rows, n_cells));
+    HIP_CHECK(pol, DeviceArena::download(fixed.data(), T.fixed, fixed.size()));
+    // parents first as in the report; a path's clade = the sum of its cells, direct = clade - the children's clades;
+    // the cells ordered by path (a counting sort), then by sample inside a path
+    const uint32_t NONE = REPORT_NONE;
+    blu_report_path* o = (blu_report_path*)malloc(std::max<uint64_t>(n_paths, 1) * sizeof(blu_report_path));
+    blu_sample_cell* c = (blu_sample_cell*)malloc(std::max<uint64_t>(n_cells, 1) * sizeof(blu_sample_cell));
+    uint64_t* un = (uint64_t*)malloc(std::max<uint64_t>(fixed.size(), 1) * 8);
+    if (!o || !c || !un) { free(o); free(c); free(un); set_error("sample table: out of memory"); return BLU_ERR_ALLOC; }
+    std::vector<uint32_t> at;
+    parents_first(paths, at, o);
+    std::vector<uint64_t> first(n_paths + 1, 0);
+    for (const blu_sample_cell& x : cells) { o[at[x.path]].clade += x.clade; ++first[at[x.path] + 1]; }
+    for (uint64_t i = 0; i < n_paths; ++i) first[i + 1] += first[i];
+    for (const blu_sample_cell& x : cells) { blu_sample_cell y = x; y.path = at[x.path]; c[first[y.path]++] = y; }
+    for (uint64_t i = 0, lo = 0; i < n_paths; lo = first[i++])
+        if (first[i] - lo > 1) std::sort(c + lo, c + first[i], [](const blu_sample_cell& a, const blu_sample_cell& b) { return a.sample < b.sample; });
+    for (uint64_t i = 0; i < n_paths; ++i) o[i].direct = o[i].clade;
+    for (uint64_t i = n_paths; i-- > 0;)
+        if (o[i].parent != NONE) o[o[i].parent].direct -= o[i].clade;
+    std::copy(fixed.begin(), fixed.end(), un);
+    out->paths = o;
+    out->n_paths = n_paths;
+    out->cells = c;
+    out->n_cells = n_cells;
+    out->n_samples = n_samples;
+    out->unclassified = un;
+    out->unplaced = un + n_samples;
+    out->table_slots = T.ccap;
+    out->attempts = T.attempts;
     return BLU_OK;
 }
 
@@ -555,403 +708,205 @@ int sample_table_finish(HipPolicy& pol, DeviceArena& mem, const SampleTables& t,
 
 int report_device(const blu_taxonomy* tax, const ReportInput& in, blu_report* out) {
     const uint64_t nq = in.n_queries;
-    unsigned long long *d_keys = nullptr, *d_direct = nullptr, *d_ctl = nullptr;
-    uint32_t* d_at = nullptr;
-    void* d_tmp = nullptr;
-    blu_report_path* d_paths = nullptr;
-    unsigned long long ctl[CTL_WORDS] = {};
-    uint64_t cap = 0, n_paths = 0;
-    uint32_t attempts = 0;
-    std::vector<blu_report_path> paths;
-    HipPolicy pol{"report", BLU_ERR_ALLOC};
-    DeviceArena mem(pol);
-    struct Events { hipEvent_t ev0 = nullptr, ev1 = nullptr; ~Events() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); } } ev;
-    hipEvent_t &ev0 = ev.ev0, &ev1 = ev.ev1;
-    HIP_CHECK(pol, hipEventCreate(&ev0));
-    HIP_CHECK(pol, hipEventCreate(&ev1));
-    HIP_CHECK(pol, mem.alloc(&d_ctl, sizeof ctl, "counters"));
-    {
-        const uint64_t guess = std::min<uint64_t>(nq * std::max<uint32_t>(tax->max_depth, 1), 2 * tax->n_tax + 4096);
-        cap = std::max<uint64_t>(next_pow2(2 * guess), 1024);
-        uint32_t max_probe = REPORT_PROBE_FIRST;
-        ReportDev d{};
-        d.lin = tax->d_lin; d.n_tax = tax->n_tax; d.stride = tax->dev_stride; d.node_base = tax->node_base;
-        d.max_depth = tax->max_depth;
-        d.recs = in.recs; d.n_queries = nq; d.row_src = in.row_src; d.n_rows = in.n_rows; d.row_stride = in.row_stride;
-        d.by_query = in.by_query ? 1u : 0u; d.weight = in.weight; d.ctl = d_ctl;
-        HIP_CHECK(pol, hipEventRecord(ev0, nullptr));
-        for (;;) {
-            ++attempts;
-            if (cap > (1ull << 32)) { set_error("report: a table of %llu slots exceeds 32-bit path ids", (unsigned long long)cap); return BLU_ERR_ALLOC; }
-            HIP_CHECK(pol, mem.alloc(&d_keys, cap * 8, "path table"));
-            HIP_CHECK(pol, mem.alloc(&d_direct, cap * 8, "path table"));
-            HIP_CHECK(pol, hipMemsetAsync(d_keys, 0xFF, cap * 8, nullptr));
-            HIP_CHECK(pol, hipMemsetAsync(d_direct, 0, cap * 8, nullptr));
-            HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, sizeof ctl, nullptr));
-            d.keys = d_keys; d.direct = d_direct; d.cap_mask = (uint32_t)(cap - 1); d.max_probe = max_probe;
-            if (nq) hipLaunchKernelGGL(report_paths, dim3((unsigned)((nq + RB * RQ - 1) / (RB * RQ))), dim3(RB), 0, 0, d);
-            HIP_CHECK(pol, hipGetLastError());
-            HIP_CHECK(pol, hipMemcpy(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost));
-            if (ctl[2] & FLAG_BAD_RECORD) {
-                set_error("report: record %llu has a taxon (status 0 / 1) but its reference row names no taxonomy row",
-                          (unsigned long long)ctl[3]);
-                return BLU_ERR_INVALID_ARG;
-            }
-            if (ctl[2] & FLAG_BAD_NODE) {
-                set_error("report: record %llu has a path that begins with node id 0xFFFFFFFF, which no path may begin with",
-                          (unsigned long long)ctl[CTL_BAD_NODE]);
-                return BLU_ERR_INVALID_ARG;
-            }
-            if (!(ctl[2] & FLAG_OVERFLOW)) break;
-            if (max_probe != REPORT_PROBE_FIRST) { set_error("report: path table overflow"); return BLU_ERR_HIP; }   // (cannot happen at load <= 1/2)
-            // the estimate was short: again from zero, sized from the bound
-            mem.free(d_keys); mem.free(d_direct); d_keys = d_direct = nullptr;
-            HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, 8, nullptr));
-            hipLaunchKernelGGL(report_bound, dim3((unsigned)std::min<uint64_t>((nq + RB - 1) / RB, 4096)), dim3(RB), 0, 0, in.recs, nq, d_ctl);
-            HIP_CHECK(pol, hipGetLastError());
-            unsigned long long bound = 0;
-            HIP_CHECK(pol, hipMemcpy(&bound, d_ctl, 8, hipMemcpyDeviceToHost));
-            cap = std::max<uint64_t>(next_pow2(2 * bound), 1024);
-            max_probe = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
-        }
-        HIP_CHECK(pol, mem.alloc(&d_at, (cap + 1) * 4, "path ids"));
-        hipLaunchKernelGGL(report_flags, dim3((unsigned)((cap + 1 + 255) / 256)), dim3(256), 0, 0, d_keys, cap, d_at);
-        HIP_CHECK(pol, hipGetLastError());
-        HIP_CHECK(pol, mem.alloc(&d_tmp, scan_tmp_bytes_u32(cap + 1), "scan scratch"));
-        HIP_CHECK(pol, exclusive_scan_u32(d_at, d_at, cap + 1, d_tmp));
-        uint32_t np32 = 0;
-        HIP_CHECK(pol, hipMemcpy(&np32, d_at + cap, 4, hipMemcpyDeviceToHost));
-        n_paths = np32;
-        HIP_CHECK(pol, mem.alloc(&d_paths, n_paths * sizeof(blu_report_path), "paths"));
-        hipLaunchKernelGGL(report_compact, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, 0, d_keys, d_direct, d_at, cap, d_paths);
-        HIP_CHECK(pol, hipGetLastError());
-        HIP_CHECK(pol, hipEventRecord(ev1, nullptr));
-        paths.resize(n_paths);
-        if (n_paths) HIP_CHECK(pol, hipMemcpy(paths.data(), d_paths, n_paths * sizeof(blu_report_path), hipMemcpyDeviceToHost));
-        float ms = 0;
-        HIP_CHECK(pol, hipEventSynchronize(ev1));   // (no path came back: no copy has waited for the device yet)
-        HIP_CHECK(pol, hipEventElapsedTime(&ms, ev0, ev1));
-        out->t_device_ms = ms;
-    }
-    {
-        // parents first (depth order, slot order inside a depth), then clade = direct + the children's clades
-        const uint32_t NONE = REPORT_NONE;
-        std::vector<uint32_t> at;
-        parents_first(paths, at);
-        blu_report_path* o = n_paths ? (blu_report_path*)malloc(n_paths * sizeof(blu_report_path)) : nullptr;
-        if (n_paths && !o) { set_error("report: out of memory"); return BLU_ERR_ALLOC; }
-        for (uint64_t i = 0; i < n_paths; ++i) {
-            blu_report_path p = paths[i];
-            p.parent = p.parent == NONE ? NONE : at[p.parent];
-            p.clade = p.direct;
-            o[at[i]] = p;
-        }
-        for (uint64_t i = n_paths; i-- > 0;)
-            if (o[i].parent != NONE) o[o[i].parent].clade += o[i].clade;
-        out->paths = o;
-        out->n_paths = n_paths;
-        out->unclassified = ctl[0];
-        out->unplaced = ctl[1];
-        uint64_t classified = 0;
-        for (uint64_t i = 0; i < n_paths; ++i) if (o[i].parent == NONE) classified += o[i].clade;
-        out->total = ctl[0] + ctl[1] + classified;
-        out->table_slots = cap;
-        out->attempts = attempts;
-    }
+    TableRun T("report", false);
+    if (const int rc = T.begin(); rc != BLU_OK) return rc;
+    ReportDev d = report_dev(tax, in, T.d_ctl);
+    T.cap = table_slots(path_guess(tax, nq));
+    if (const int rc = T.run(
+            [&] { T.point(d); if (nq) hipLaunchKernelGGL(report_paths, walk_grid(nq), dim3(RB), 0, 0, d); },
+            [&] {
+                unsigned long long bound = 0;
+                const int rc = T.path_bound(in, &bound);
+                T.cap = table_slots(bound);
+                return rc;
+            }); rc != BLU_OK) return rc;
+    HipPolicy& pol = T.pol;
+    Compacted<blu_report_path> P;
+    if (const int rc = compact_table(T, T.keys, T.cap, "path ids", "paths", &P, [&](dim3 g, dim3 b) {
+            hipLaunchKernelGGL(report_compact, g, b, 0, 0, T.keys, T.direct, P.at, T.cap, P.rows);
+        }); rc != BLU_OK) return rc;
+    if (const int rc = T.stop(&out->t_device_ms); rc != BLU_OK) return rc;
+    const uint64_t n_paths = P.n;
+    std::vector<blu_report_path> paths(n_paths);
+    HIP_CHECK(pol, DeviceArena::download(paths.data(), P.rows, n_paths));
+    // parents first (depth order, slot order inside a depth), then clade = direct + the children's clades
+    const uint32_t NONE = REPORT_NONE;
+    blu_report_path* o = n_paths ? (blu_report_path*)malloc(n_paths * sizeof(blu_report_path)) : nullptr;
+    if (n_paths && !o) { set_error("report: out of memory"); return BLU_ERR_ALLOC; }
+    std::vector<uint32_t> at;
+    parents_first(paths, at, o);
+    for (uint64_t i = 0; i < n_paths; ++i) o[i].clade = o[i].direct;
+    for (uint64_t i = n_paths; i-- > 0;)
+        if (o[i].parent != NONE) o[o[i].parent].clade += o[i].clade;
+    out->paths = o;
+    out->n_paths = n_paths;
+    out->unclassified = T.ctl[0];
+    out->unplaced = T.ctl[1];
+    uint64_t classified = 0;
+    for (uint64_t i = 0; i < n_paths; ++i) if (o[i].parent == NONE) classified += o[i].clade;
+    out->total = T.ctl[0] + T.ctl[1] + classified;
+    out->table_slots = T.cap;
+    out->attempts = T.attempts;
     return BLU_OK;
 }
 
 int sample_table_device(const blu_taxonomy* tax, const ReportInput& in, const uint32_t* sample_of, uint32_t n_samples,
                         blu_sample_table* out) {
     const uint64_t nq = in.n_queries;
-    unsigned long long *d_keys = nullptr, *d_ckeys = nullptr, *d_cval = nullptr, *d_ctl = nullptr, *d_fixed = nullptr;
-    unsigned long long ctl[CTL_WORDS] = {};
-    uint64_t cap = 0, ccap = 0;
-    const uint64_t fixed_bytes = 2 * (uint64_t)n_samples * 8;
-    HipPolicy pol{"sample table", BLU_ERR_ALLOC};
-    DeviceArena mem(pol);
-    SampleTables T;
-    uint32_t& attempts = T.attempts;
-    HIP_CHECK(pol, hipEventCreate(&T.ev0));
-    HIP_CHECK(pol, hipEventCreate(&T.ev1));
-    HIP_CHECK(pol, mem.alloc(&d_ctl, sizeof ctl, "counters"));
-    HIP_CHECK(pol, mem.alloc(&d_fixed, fixed_bytes, "per-sample counters"));
-    {
-        // paths as the report sizes them; cells: the paths plus one per query (a sample's queries mostly share their upper
-        // levels), at most one per level of every query
-        const uint64_t depth = std::max<uint32_t>(tax->max_depth, 1);
-        const uint64_t guess = std::min<uint64_t>(nq * depth, 2 * tax->n_tax + 4096);
-        const uint64_t cguess = std::min<uint64_t>(nq * depth, guess + nq);
-        cap = std::max<uint64_t>(next_pow2(2 * guess), 1024);
-        ccap = std::max<uint64_t>(next_pow2(2 * cguess), 1024);
-        uint32_t max_probe = REPORT_PROBE_FIRST;
-        SampleDev d{};
-        d.r.lin = tax->d_lin; d.r.n_tax = tax->n_tax; d.r.stride = tax->dev_stride; d.r.node_base = tax->node_base;
-        d.r.max_depth = tax->max_depth;
-        d.r.recs = in.recs; d.r.n_queries = nq; d.r.row_src = in.row_src; d.r.n_rows = in.n_rows; d.r.row_stride = in.row_stride;
-        d.r.by_query = in.by_query ? 1u : 0u; d.r.weight = in.weight; d.r.ctl = d_ctl;
-        d.sample_of = sample_of; d.n_samples = n_samples; d.fixed = d_fixed;
-        HIP_CHECK(pol, hipEventRecord(T.ev0, nullptr));
-        for (;;) {
-            ++attempts;
-            // (path ids below 2^31: the two ids above are the fixed rows' in the cell keys)
-            if (cap > (1ull << 31) || ccap > (1ull << 32)) {
-                set_error("sample table: tables of %llu / %llu slots exceed 32-bit ids", (unsigned long long)cap, (unsigned long long)ccap);
-                return BLU_ERR_ALLOC;
-            }
-            HIP_CHECK(pol, mem.alloc(&d_keys, cap * 8, "path table"));
-            HIP_CHECK(pol, mem.alloc(&d_ckeys, ccap * 8, "cell table"));
-            HIP_CHECK(pol, mem.alloc(&d_cval, ccap * 8, "cell table"));
-            HIP_CHECK(pol, hipMemsetAsync(d_keys, 0xFF, cap * 8, nullptr));
-            HIP_CHECK(pol, hipMemsetAsync(d_ckeys, 0xFF, ccap * 8, nullptr));
-            HIP_CHECK(pol, hipMemsetAsync(d_cval, 0, ccap * 8, nullptr));
-            HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, sizeof ctl, nullptr));
-            HIP_CHECK(pol, hipMemsetAsync(d_fixed, 0, fixed_bytes, nullptr));
-            d.r.keys = d_keys; d.r.cap_mask = (uint32_t)(cap - 1); d.r.max_probe = max_probe;
-            d.cell_keys = d_ckeys; d.cell_val = d_cval; d.cell_mask = (uint32_t)(ccap - 1);
-            if (nq) hipLaunchKernelGGL(sample_cells, dim3((unsigned)((nq + RB * RQ - 1) / (RB * RQ))), dim3(RB), 0, 0, d);
-            HIP_CHECK(pol, hipGetLastError());
-            HIP_CHECK(pol, hipMemcpy(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost));
-            if (ctl[2] & FLAG_BAD_SAMPLE) {
-                set_error("sample table: query %llu has a sample id that is not below n_samples = %u", (unsigned long long)ctl[4], n_samples);
-                return BLU_ERR_INVALID_ARG;
-            }
-            if (ctl[2] & FLAG_BAD_RECORD) {
-                set_error("sample table: record %llu has a taxon (status 0 / 1) but its reference row names no taxonomy row",
-                          (unsigned long long)ctl[3]);
-                return BLU_ERR_INVALID_ARG;
-            }
-            if (ctl[2] & FLAG_BAD_NODE) {
-                set_error("sample table: record %llu has a path that begins with node id 0xFFFFFFFF, which no path may begin with",
-                          (unsigned long long)ctl[CTL_BAD_NODE]);
-                return BLU_ERR_INVALID_ARG;
-            }
-            if (!(ctl[2] & FLAG_OVERFLOW)) break;
-            if (max_probe != REPORT_PROBE_FIRST) { set_error("sample table: table overflow"); return BLU_ERR_HIP; }   // (cannot happen at load <= 1/2)
-            // the estimate was short: both tables again from zero, sized from the bound on paths and on cells
-            mem.free(d_keys); mem.free(d_ckeys); mem.free(d_cval); d_keys = d_ckeys = d_cval = nullptr;
-            HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, 8, nullptr));
-            hipLaunchKernelGGL(report_bound, dim3((unsigned)std::min<uint64_t>((nq + RB - 1) / RB, 4096)), dim3(RB), 0, 0, in.recs, nq, d_ctl);
-            HIP_CHECK(pol, hipGetLastError());
-            unsigned long long bound = 0;
-            HIP_CHECK(pol, hipMemcpy(&bound, d_ctl, 8, hipMemcpyDeviceToHost));
-            cap = ccap = std::max<uint64_t>(next_pow2(2 * bound), 1024);
-            max_probe = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
-        }
-    }
-    T.keys = d_keys; T.ckeys = d_ckeys; T.cval = d_cval; T.fixed = d_fixed; T.cap = cap; T.ccap = ccap;
-    return sample_table_finish(pol, mem, T, n_samples, out);
+    TableRun T("sample table", true, n_samples);
+    if (const int rc = T.begin(); rc != BLU_OK) return rc;
+    SampleDev d{};
+    d.r = report_dev(tax, in, T.d_ctl);
+    d.sample_of = sample_of;
+    // paths as the report sizes them; cells: the paths plus one per query (a sample's queries mostly share their upper
+    // levels), at most one per level of every query
+    const uint64_t guess = path_guess(tax, nq);
+    T.cap = table_slots(guess);
+    T.ccap = table_slots(std::min<uint64_t>(nq * std::max<uint32_t>(tax->max_depth, 1), guess + nq));
+    if (const int rc = T.run(
+            [&] { T.point(d); if (nq) hipLaunchKernelGGL(sample_cells, walk_grid(nq), dim3(RB), 0, 0, d); },
+            [&] {   // both tables from the bound on the paths: a query reaches no more cells than paths
+                unsigned long long bound = 0;
+                const int rc = T.path_bound(in, &bound);
+                T.cap = T.ccap = table_slots(bound);
+                return rc;
+            }); rc != BLU_OK) return rc;
+    return sample_table_finish(T, out);
 }
 
 int sample_table_counts_device(const blu_taxonomy* tax, const ReportInput& in, const CountRows& rows, uint32_t n_samples,
                                blu_sample_table* out) {
     const uint64_t nq = in.n_queries;
-    unsigned long long *d_keys = nullptr, *d_ckeys = nullptr, *d_cval = nullptr, *d_ctl = nullptr, *d_fixed = nullptr;
-    unsigned long long ctl[CTL_WORDS] = {};
-    const uint64_t fixed_bytes = 2 * (uint64_t)n_samples * 8;
-    HipPolicy pol{"count table", BLU_ERR_ALLOC};
-    DeviceArena mem(pol);
-    SampleTables T;
-    HIP_CHECK(pol, hipEventCreate(&T.ev0));
-    HIP_CHECK(pol, hipEventCreate(&T.ev1));
-    HIP_CHECK(pol, mem.alloc(&d_ctl, sizeof ctl, "counters"));
-    HIP_CHECK(pol, mem.alloc(&d_fixed, fixed_bytes, "per-sample counters"));
+    TableRun T("count table", true, n_samples, rows.nnz);
+    if (const int rc = T.begin(); rc != BLU_OK) return rc;
+    HipPolicy& pol = T.pol;
     CountDev d{};
-    d.s.r.lin = tax->d_lin; d.s.r.n_tax = tax->n_tax; d.s.r.stride = tax->dev_stride; d.s.r.node_base = tax->node_base;
-    d.s.r.max_depth = tax->max_depth;
-    d.s.r.recs = in.recs; d.s.r.n_queries = nq; d.s.r.row_src = in.row_src; d.s.r.n_rows = in.n_rows; d.s.r.row_stride = in.row_stride;
-    d.s.r.by_query = in.by_query ? 1u : 0u; d.s.r.ctl = d_ctl;
-    d.s.n_samples = n_samples; d.s.fixed = d_fixed;
+    d.s.r = report_dev(tax, in, T.d_ctl);
     d.rows = rows;
-    HIP_CHECK(pol, hipEventRecord(T.ev0, nullptr));
     // the bounds first: P on the paths, and on the cells the sum of levels x non-zeros (one pass over the records and row_ptr)
     unsigned long long bound[2] = {0, 0};
-    HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, sizeof ctl, nullptr));
-    if (nq) hipLaunchKernelGGL(count_bound, dim3((unsigned)std::min<uint64_t>((nq + RB - 1) / RB, 4096)), dim3(RB), 0, 0, in.recs, rows, nq, d_ctl);
+    HIP_CHECK(pol, hipMemsetAsync(T.d_ctl, 0, sizeof T.ctl, nullptr));
+    if (nq) hipLaunchKernelGGL(count_bound, bound_grid(nq), dim3(RB), 0, 0, in.recs, rows, nq, T.d_ctl);
     HIP_CHECK(pol, hipGetLastError());
-    HIP_CHECK(pol, hipMemcpy(bound, d_ctl, sizeof bound, hipMemcpyDeviceToHost));
+    HIP_CHECK(pol, hipMemcpy(bound, T.d_ctl, sizeof bound, hipMemcpyDeviceToHost));
     // paths as the report sizes them; cells: no more than the bound, and no more than every path in every sample
-    const uint64_t guess = std::min<uint64_t>(nq * std::max<uint32_t>(tax->max_depth, 1), 2 * tax->n_tax + 4096);
-    uint64_t cap = std::max<uint64_t>(next_pow2(2 * guess), 1024);
-    uint64_t ccap = std::max<uint64_t>(next_pow2(2 * std::min<uint64_t>(bound[1], guess * std::max<uint32_t>(n_samples, 1))), 1024);
-    uint32_t max_probe = REPORT_PROBE_FIRST;
-    for (;;) {
-        ++T.attempts;
-        // (path ids below 2^31: the two ids above are the fixed rows' in the cell keys)
-        if (cap > (1ull << 31) || ccap > (1ull << 32)) {
-            set_error("count table: tables of %llu / %llu slots exceed 32-bit ids", (unsigned long long)cap, (unsigned long long)ccap);
-            return BLU_ERR_ALLOC;
-        }
-        HIP_CHECK(pol, mem.alloc(&d_keys, cap * 8, "path table"));
-        HIP_CHECK(pol, mem.alloc(&d_ckeys, ccap * 8, "cell table"));
-        HIP_CHECK(pol, mem.alloc(&d_cval, ccap * 8, "cell table"));
-        HIP_CHECK(pol, hipMemsetAsync(d_keys, 0xFF, cap * 8, nullptr));
-        HIP_CHECK(pol, hipMemsetAsync(d_ckeys, 0xFF, ccap * 8, nullptr));
-        HIP_CHECK(pol, hipMemsetAsync(d_cval, 0, ccap * 8, nullptr));
-        HIP_CHECK(pol, hipMemsetAsync(d_ctl, 0, sizeof ctl, nullptr));
-        HIP_CHECK(pol, hipMemsetAsync(d_fixed, 0, fixed_bytes, nullptr));
-        d.s.r.keys = d_keys; d.s.r.cap_mask = (uint32_t)(cap - 1); d.s.r.max_probe = max_probe;
-        d.s.cell_keys = d_ckeys; d.s.cell_val = d_cval; d.s.cell_mask = (uint32_t)(ccap - 1);
-        if (nq) hipLaunchKernelGGL(count_cells, dim3((unsigned)((nq + COUNT_Q_BLOCK - 1) / COUNT_Q_BLOCK)), dim3(RB), 0, 0, d);
-        HIP_CHECK(pol, hipGetLastError());
-        HIP_CHECK(pol, hipMemcpy(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost));
-        if (ctl[2] & FLAG_BAD_ROW) {
-            set_error("count table: query %llu has a row_ptr that decreases or ends past the %llu non-zeros", (unsigned long long)ctl[5],
-                      (unsigned long long)rows.nnz);
-            return BLU_ERR_INVALID_ARG;
-        }
-        if (ctl[2] & FLAG_BAD_SAMPLE) {
-            set_error("count table: query %llu has a sample id that is not below n_samples = %u", (unsigned long long)ctl[4], n_samples);
-            return BLU_ERR_INVALID_ARG;
-        }
-        if (ctl[2] & FLAG_BAD_RECORD) {
-            set_error("count table: record %llu has a taxon (status 0 / 1) but its reference row names no taxonomy row",
-                      (unsigned long long)ctl[3]);
-            return BLU_ERR_INVALID_ARG;
-        }
-        if (ctl[2] & FLAG_BAD_NODE) {
-            set_error("count table: record %llu has a path that begins with node id 0xFFFFFFFF, which no path may begin with",
-                      (unsigned long long)ctl[CTL_BAD_NODE]);
-            return BLU_ERR_INVALID_ARG;
-        }
-        if (!(ctl[2] & FLAG_OVERFLOW)) break;
-        if (max_probe != REPORT_PROBE_FIRST) { set_error("count table: table overflow"); return BLU_ERR_HIP; }   // (cannot happen at load <= 1/2)
-        // an estimate was short: both tables again from zero, at twice their bounds, where a probe always ends
-        mem.free(d_keys); mem.free(d_ckeys); mem.free(d_cval); d_keys = d_ckeys = d_cval = nullptr;
-        cap = std::max<uint64_t>(next_pow2(2 * bound[0]), 1024);
-        ccap = std::max<uint64_t>(next_pow2(2 * bound[1]), 1024);
-        max_probe = (uint32_t)std::min<uint64_t>(std::max(cap, ccap), 0xFFFFFFFFull);
-    }
-    T.keys = d_keys; T.ckeys = d_ckeys; T.cval = d_cval; T.fixed = d_fixed; T.cap = cap; T.ccap = ccap;
-    return sample_table_finish(pol, mem, T, n_samples, out);
+    const uint64_t guess = path_guess(tax, nq);
+    T.cap = table_slots(guess);
+    T.ccap = table_slots(std::min<uint64_t>(bound[1], guess * std::max<uint32_t>(n_samples, 1)));
+    if (const int rc = T.run(
+            [&] { T.point(d.s); if (nq) hipLaunchKernelGGL(count_cells, dim3((unsigned)((nq + COUNT_Q_BLOCK - 1) / COUNT_Q_BLOCK)), dim3(RB), 0, 0, d); },
+            [&] { T.cap = table_slots(bound[0]); T.ccap = table_slots(bound[1]); return BLU_OK; }); rc != BLU_OK) return rc;
+    return sample_table_finish(T, out);
 }
 
 }  // namespace blu
 
 using namespace blu;
 
+namespace {
+
+// What the three entries begin with: the argument checks (`needed`: the entry's own array, which may be null only when there
+// are no queries), *out cleared, the column the engine rows come from and its stride, the device and, for device pointers,
+// the records' alignment and the stream.  fn names the entry in the messages.  *in: the device-pointer view of the call
+// (no weights); host pointers go through stage_records.
+int entry_begin(const char* fn, const blu_taxonomy* tax, const blu_hits* hits, const blu_result* results, const void* needed,
+                void* stream, void* out, size_t out_bytes, ReportInput* in) {
+    if (!tax || !hits || !out || (hits->n_queries && (!results || !needed))) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    memset(out, 0, out_bytes);
+    if (tax->device < 0) { set_error("host-only taxonomy handle: %s needs a HIP device (no CPU fallback)", fn); return BLU_ERR_NO_DEVICE; }
+    const uint32_t* src = hits->packed ? hits->packed : hits->packed64 ? hits->packed64 : hits->tax_row;
+    const uint32_t stride = hits->packed ? 4u : hits->packed64 ? 6u : 1u;
+    if (hits->n_queries && !src) { set_error("%s: no tax_row column", fn); return BLU_ERR_INVALID_ARG; }
+    if (hipSetDevice(tax->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", tax->device); return BLU_ERR_NO_DEVICE; }
+    if (hits->on_device) {
+        if (((uintptr_t)results & 15u) != 0) { set_error("%s: device records must be 16-byte aligned", fn); return BLU_ERR_INVALID_ARG; }
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) { set_error("%s: stream synchronise failed", fn); return BLU_ERR_HIP; }
+    }
+    *in = ReportInput{results, hits->n_queries, src, hits->n_hits, stride, false, nullptr};
+    return BLU_OK;
+}
+
+// Host pointers: the records go up, and each record's engine row, gathered here (4 bytes a query instead of the whole
+// column).  *in: the host view on entry, the staged one (rows by query) on return.
+int stage_records(HipPolicy& pol, DeviceArena& mem, ReportInput* in) {
+    const uint64_t nq = in->n_queries;
+    std::vector<uint32_t> rows(nq, BLU_UNMATCHED_TAXID);
+    for (uint64_t q = 0; q < nq; ++q)
+        if (in->recs[q].status < 2 && in->recs[q].ref_row < in->n_rows) rows[q] = in->row_src[(uint64_t)in->recs[q].ref_row * in->row_stride];
+    blu_result* d_recs = nullptr;
+    uint32_t* d_rows = nullptr;
+    HIP_CHECK(pol, mem.upload(&d_recs, in->recs, nq, "records"));
+    HIP_CHECK(pol, mem.upload(&d_rows, rows.data(), nq, "rows"));
+    *in = ReportInput{d_recs, nq, d_rows, nq, 1u, true, nullptr};
+    return BLU_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int blu_consensus_report(const blu_taxonomy* tax, const blu_hits* hits, const blu_result* results, const uint32_t* weights,
                          void* stream, blu_report* out) {
-    if (!tax || !hits || !out || (hits->n_queries && !results)) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
-    memset(out, 0, sizeof *out);
-    if (tax->device < 0) { set_error("host-only taxonomy handle: blu_consensus_report needs a HIP device (no CPU fallback)"); return BLU_ERR_NO_DEVICE; }
-    const uint32_t* src = hits->packed ? hits->packed : hits->packed64 ? hits->packed64 : hits->tax_row;
-    const uint32_t stride = hits->packed ? 4u : hits->packed64 ? 6u : 1u;
-    const uint64_t nq = hits->n_queries, nh = hits->n_hits;
-    if (nq && !src) { set_error("blu_consensus_report: no tax_row column"); return BLU_ERR_INVALID_ARG; }
-    if (hipSetDevice(tax->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", tax->device); return BLU_ERR_NO_DEVICE; }
-    ReportInput in{results, nq, src, nh, stride, false, weights};
-    if (hits->on_device) {
-        if (((uintptr_t)results & 15u) != 0) { set_error("blu_consensus_report: device records must be 16-byte aligned"); return BLU_ERR_INVALID_ARG; }
-        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) { set_error("blu_consensus_report: stream synchronise failed"); return BLU_ERR_HIP; }
-        try { return report_device(tax, in, out); }
-        catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
-    }
-    // host pointers: the records, each record's engine row (gathered here: 4 bytes a query instead of the whole column)
-    // and the weights go up
+    ReportInput in{};
+    if (const int rc = entry_begin("blu_consensus_report", tax, hits, results, results, stream, out, sizeof *out, &in); rc != BLU_OK) return rc;
     HipPolicy pol{"blu_consensus_report", BLU_ERR_ALLOC};
     DeviceArena mem(pol);
-    blu_result* d_recs = nullptr;
-    uint32_t *d_rows = nullptr, *d_w = nullptr;
     try {
-        std::vector<uint32_t> rows(nq, BLU_UNMATCHED_TAXID);
-        for (uint64_t q = 0; q < nq; ++q)
-            if (results[q].status < 2 && results[q].ref_row < nh) rows[q] = src[(uint64_t)results[q].ref_row * stride];
-        HIP_CHECK(pol, mem.alloc(&d_recs, nq * sizeof(blu_result), "records"));
-        HIP_CHECK(pol, mem.alloc(&d_rows, nq * 4, "rows"));
-        if (weights) HIP_CHECK(pol, mem.alloc(&d_w, nq * 4, "weights"));
-        if (nq) {
-            HIP_CHECK(pol, hipMemcpy(d_recs, results, nq * sizeof(blu_result), hipMemcpyHostToDevice));
-            HIP_CHECK(pol, hipMemcpy(d_rows, rows.data(), nq * 4, hipMemcpyHostToDevice));
-            if (weights) HIP_CHECK(pol, hipMemcpy(d_w, weights, nq * 4, hipMemcpyHostToDevice));
+        in.weight = weights;
+        if (!hits->on_device) {   // the weights go up beside the records
+            uint32_t* d_w = nullptr;
+            if (const int rc = stage_records(pol, mem, &in); rc != BLU_OK) return rc;
+            if (weights) HIP_CHECK(pol, mem.upload(&d_w, weights, in.n_queries, "weights"));
+            in.weight = d_w;
         }
-        ReportInput hin{d_recs, nq, d_rows, nq, 1u, true, d_w};
-        return report_device(tax, hin, out);
+        return report_device(tax, in, out);
     } catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
 }
 
 int blu_consensus_sample_table(const blu_taxonomy* tax, const blu_hits* hits, const blu_result* results, const uint32_t* weights,
                                const uint32_t* sample_of, uint32_t n_samples, void* stream, blu_sample_table* out) {
-    if (!tax || !hits || !out || (hits->n_queries && (!results || !sample_of))) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
-    memset(out, 0, sizeof *out);
-    if (tax->device < 0) { set_error("host-only taxonomy handle: blu_consensus_sample_table needs a HIP device (no CPU fallback)"); return BLU_ERR_NO_DEVICE; }
-    const uint32_t* src = hits->packed ? hits->packed : hits->packed64 ? hits->packed64 : hits->tax_row;
-    const uint32_t stride = hits->packed ? 4u : hits->packed64 ? 6u : 1u;
-    const uint64_t nq = hits->n_queries, nh = hits->n_hits;
-    if (nq && !src) { set_error("blu_consensus_sample_table: no tax_row column"); return BLU_ERR_INVALID_ARG; }
-    if (hipSetDevice(tax->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", tax->device); return BLU_ERR_NO_DEVICE; }
-    ReportInput in{results, nq, src, nh, stride, false, weights};
-    if (hits->on_device) {
-        if (((uintptr_t)results & 15u) != 0) { set_error("blu_consensus_sample_table: device records must be 16-byte aligned"); return BLU_ERR_INVALID_ARG; }
-        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) { set_error("blu_consensus_sample_table: stream synchronise failed"); return BLU_ERR_HIP; }
-        try { return sample_table_device(tax, in, sample_of, n_samples, out); }
-        catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
-    }
-    // host pointers: the records, each record's engine row, the weights and the sample ids go up
+    ReportInput in{};
+    if (const int rc = entry_begin("blu_consensus_sample_table", tax, hits, results, sample_of, stream, out, sizeof *out, &in); rc != BLU_OK) return rc;
     HipPolicy pol{"blu_consensus_sample_table", BLU_ERR_ALLOC};
     DeviceArena mem(pol);
-    blu_result* d_recs = nullptr;
-    uint32_t *d_rows = nullptr, *d_w = nullptr, *d_s = nullptr;
     try {
-        std::vector<uint32_t> rows(nq, BLU_UNMATCHED_TAXID);
-        for (uint64_t q = 0; q < nq; ++q)
-            if (results[q].status < 2 && results[q].ref_row < nh) rows[q] = src[(uint64_t)results[q].ref_row * stride];
-        HIP_CHECK(pol, mem.alloc(&d_recs, nq * sizeof(blu_result), "records"));
-        HIP_CHECK(pol, mem.alloc(&d_rows, nq * 4, "rows"));
-        HIP_CHECK(pol, mem.alloc(&d_s, nq * 4, "sample ids"));
-        if (weights) HIP_CHECK(pol, mem.alloc(&d_w, nq * 4, "weights"));
-        if (nq) {
-            HIP_CHECK(pol, hipMemcpy(d_recs, results, nq * sizeof(blu_result), hipMemcpyHostToDevice));
-            HIP_CHECK(pol, hipMemcpy(d_rows, rows.data(), nq * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(pol, hipMemcpy(d_s, sample_of, nq * 4, hipMemcpyHostToDevice));
-            if (weights) HIP_CHECK(pol, hipMemcpy(d_w, weights, nq * 4, hipMemcpyHostToDevice));
+        in.weight = weights;
+        if (!hits->on_device) {   // the sample ids and the weights go up beside the records
+            uint32_t *d_s = nullptr, *d_w = nullptr;
+            if (const int rc = stage_records(pol, mem, &in); rc != BLU_OK) return rc;
+            HIP_CHECK(pol, mem.upload(&d_s, sample_of, in.n_queries, "sample ids"));
+            if (weights) HIP_CHECK(pol, mem.upload(&d_w, weights, in.n_queries, "weights"));
+            in.weight = d_w;
+            sample_of = d_s;
         }
-        ReportInput hin{d_recs, nq, d_rows, nq, 1u, true, d_w};
-        return sample_table_device(tax, hin, d_s, n_samples, out);
+        return sample_table_device(tax, in, sample_of, n_samples, out);
     } catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
 }
 
 int blu_consensus_sample_table_counts(const blu_taxonomy* tax, const blu_hits* hits, const blu_result* results, const blu_count_rows* rows,
                                       uint32_t n_samples, void* stream, blu_sample_table* out) {
-    if (!tax || !hits || !out || !rows || (hits->n_queries && (!results || !rows->row_ptr))) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
-    memset(out, 0, sizeof *out);
-    if (tax->device < 0) { set_error("host-only taxonomy handle: blu_consensus_sample_table_counts needs a HIP device (no CPU fallback)"); return BLU_ERR_NO_DEVICE; }
-    const uint32_t* src = hits->packed ? hits->packed : hits->packed64 ? hits->packed64 : hits->tax_row;
-    const uint32_t stride = hits->packed ? 4u : hits->packed64 ? 6u : 1u;
-    const uint64_t nq = hits->n_queries, nh = hits->n_hits;
-    if (nq && !src) { set_error("blu_consensus_sample_table_counts: no tax_row column"); return BLU_ERR_INVALID_ARG; }
-    if (hipSetDevice(tax->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", tax->device); return BLU_ERR_NO_DEVICE; }
+    if (!rows) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
+    ReportInput in{};
+    if (const int rc = entry_begin("blu_consensus_sample_table_counts", tax, hits, results, rows->row_ptr, stream, out, sizeof *out, &in); rc != BLU_OK) return rc;
     HipPolicy pol{"blu_consensus_sample_table_counts", BLU_ERR_ALLOC};
-    uint64_t nnz = 0;   // the last offset: what the two arrays hold, and what no row may pass
-    if (hits->on_device) {
-        if (((uintptr_t)results & 15u) != 0) { set_error("blu_consensus_sample_table_counts: device records must be 16-byte aligned"); return BLU_ERR_INVALID_ARG; }
-        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) { set_error("blu_consensus_sample_table_counts: stream synchronise failed"); return BLU_ERR_HIP; }
-        if (nq) HIP_CHECK(pol, hipMemcpy(&nnz, rows->row_ptr + nq, 8, hipMemcpyDeviceToHost));
-        if (nnz && (!rows->sample || !rows->count)) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
-        ReportInput in{results, nq, src, nh, stride, false, nullptr};
-        try { return sample_table_counts_device(tax, in, CountRows{rows->row_ptr, rows->sample, rows->count, nnz}, n_samples, out); }
-        catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
-    }
-    // host pointers: the records, each record's engine row and the three arrays of the rows go up
-    if (nq) nnz = rows->row_ptr[nq];
-    if (nnz && (!rows->sample || !rows->count)) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     DeviceArena mem(pol);
-    blu_result* d_recs = nullptr;
-    uint32_t *d_rows = nullptr, *d_s = nullptr, *d_c = nullptr;
-    uint64_t* d_ptr = nullptr;
+    const uint64_t nq = in.n_queries;
+    uint64_t nnz = 0;   // the last offset: what the two arrays hold, and what no row may pass
+    if (nq && hits->on_device) HIP_CHECK(pol, hipMemcpy(&nnz, rows->row_ptr + nq, 8, hipMemcpyDeviceToHost));
+    else if (nq) nnz = rows->row_ptr[nq];
+    if (nnz && (!rows->sample || !rows->count)) { set_error("null argument"); return BLU_ERR_INVALID_ARG; }
     try {
-        std::vector<uint32_t> erows(nq, BLU_UNMATCHED_TAXID);
-        for (uint64_t q = 0; q < nq; ++q)
-            if (results[q].status < 2 && results[q].ref_row < nh) erows[q] = src[(uint64_t)results[q].ref_row * stride];
-        HIP_CHECK(pol, mem.upload(&d_recs, results, nq, "records"));
-        HIP_CHECK(pol, mem.upload(&d_rows, erows.data(), nq, "rows"));
-        HIP_CHECK(pol, mem.upload(&d_ptr, rows->row_ptr, nq ? nq + 1 : 0, "row offsets"));
-        HIP_CHECK(pol, mem.upload(&d_s, rows->sample, nnz, "sample ids"));
-        HIP_CHECK(pol, mem.upload(&d_c, rows->count, nnz, "counts"));
-        ReportInput hin{d_recs, nq, d_rows, nq, 1u, true, nullptr};
-        return sample_table_counts_device(tax, hin, CountRows{d_ptr, d_s, d_c, nnz}, n_samples, out);
+        CountRows cr{rows->row_ptr, rows->sample, rows->count, nnz};
+        if (!hits->on_device) {   // the three arrays of the rows go up beside the records
+            uint64_t* d_ptr = nullptr;
+            uint32_t *d_s = nullptr, *d_c = nullptr;
+            if (const int rc = stage_records(pol, mem, &in); rc != BLU_OK) return rc;
+            HIP_CHECK(pol, mem.upload(&d_ptr, rows->row_ptr, nq ? nq + 1 : 0, "row offsets"));
+            HIP_CHECK(pol, mem.upload(&d_s, rows->sample, nnz, "sample ids"));
+            HIP_CHECK(pol, mem.upload(&d_c, rows->count, nnz, "counts"));
+            cr = CountRows{d_ptr, d_s, d_c, nnz};
+        }
+        return sample_table_counts_device(tax, in, cr, n_samples, out);
     } catch (const std::bad_alloc&) { set_error("out of memory"); return BLU_ERR_ALLOC; }
 }
 
