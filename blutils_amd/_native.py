@@ -18,7 +18,7 @@ EXPORTS = (
     "blu_consensus_sample_table", "blu_sample_table_free", "blu_consensus_support", "blu_hits_score_band",
     "blu_hits_subject_keep", "blu_hits_subject_best", "blu_hits_cover_keep", "blu_hits_cover_apply",
     "blu_consensus_sample_table_counts", "blu_sample_distances", "blu_sample_distance_free",
-    "blu_rarefy_stream", "blu_sample_rarefy", "blu_rarefied_free",
+    "blu_rarefy_stream", "blu_sample_rarefy", "blu_rarefied_free", "blu_alpha_log2", "blu_sample_alpha", "blu_alpha_free",
 )
 # include/blu_pipeline.h
 PIPELINE_EXPORTS = ("blu_build_consensus", "blu_build_consensus_with", "blu_build_consensus_identities", "blu_build_consensus_identities_cfg",
@@ -28,7 +28,7 @@ PIPELINE_EXPORTS = ("blu_build_consensus", "blu_build_consensus_with", "blu_buil
                     "blu_seqdb_export_labelled", "blu_seqdb_render_labels", "blu_table_layout_parse", "blu_build_consensus_laid_out",
                     "blu_ingest_columns_laid_out", "blu_query_cover_parse", "blu_build_consensus_covered", "blu_ingest_columns_covered",
                     "blu_lineage_db_build", "blu_distance_features_from_table", "blu_distance_features_free", "blu_distance_render",
-                    "blu_distance_matrix_file", "blu_distance_matrix_file_with")
+                    "blu_distance_matrix_file", "blu_distance_matrix_file_with", "blu_alpha_render", "blu_alpha_table_file")
 
 BLU_UNMATCHED_TAXID = 0xFFFFFFFF
 BLU_NONE_U8, BLU_NONE_U16, BLU_MAR_NEVER_EQUAL = 0xFF, 0xFFFF, 0xFFFE
@@ -143,6 +143,23 @@ class Rarefied(C.Structure):
                 ("t_device_ms", C.c_double)]
 
 
+ALPHA_MAX_DEPTHS, ALPHA_TILE = 32, 8192
+
+
+class AlphaDesc(C.Structure):
+    """include/blu_consensus.h: blu_alpha_desc"""
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_features", C.c_uint64), ("n_samples", C.c_uint32),
+                ("n_depths", C.c_uint32), ("row_ptr", C.c_void_p), ("sample", C.c_void_p), ("count", C.c_void_p),
+                ("sample_stream", C.c_void_p), ("depths", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class Alpha(C.Structure):
+    """include/blu_consensus.h: blu_alpha"""
+    _fields_ = [("n_samples", C.c_uint32), ("n_slots", C.c_uint32), ("present", C.POINTER(C.c_uint8)), ("n", C.POINTER(C.c_uint64)),
+                ("observed", C.POINTER(C.c_uint32)), ("singletons", C.POINTER(C.c_uint32)), ("doubletons", C.POINTER(C.c_uint32)),
+                ("sum_sq", C.POINTER(C.c_uint64)), ("sum_xlog", C.POINTER(C.c_uint64)), ("t_device_ms", C.c_double)]
+
+
 class NativeLibraryMissing(RuntimeError):
     pass
 
@@ -230,6 +247,12 @@ def lib() -> C.CDLL:
         L.blu_sample_rarefy.restype = C.c_int
         L.blu_sample_rarefy.argtypes = [C.POINTER(RarefyDesc), C.POINTER(Rarefied)]
         L.blu_rarefied_free.argtypes = [C.POINTER(Rarefied)]
+    if hasattr(L, "blu_sample_alpha"):           # (an A/B library of an older build: BLU_CONSENSUS_LIB)
+        L.blu_alpha_log2.restype = C.c_uint64
+        L.blu_alpha_log2.argtypes = [C.c_uint64]
+        L.blu_sample_alpha.restype = C.c_int
+        L.blu_sample_alpha.argtypes = [C.POINTER(AlphaDesc), C.POINTER(Alpha)]
+        L.blu_alpha_free.argtypes = [C.POINTER(Alpha)]
     L.blu_consensus_last_launch.restype = C.c_int
     L.blu_consensus_last_launch.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     _lib = L

@@ -176,6 +176,23 @@ name, a D no sample reaches (the message says the largest total) and a sample of
 after the `distances:` line, which then counts the kept samples and the rarefied non-zeros:
 `rarefy: depth D, seed N, kept K of S samples, E features emptied`, and `rarefy: dropped SAMPLE (TOTAL reads)` per dropped sample.
 
+    python -m blutils_amd.cli blastn build-diversity TABLE -o OUT [--rank R] [--drop-unclassified]
+        [--depths D1,D2,... | --steps K [--max-depth M]] [--seed N] [--device N]
+    python -m blutils_amd.cli blastn build-consensus ... --sample-table FILE --alpha-table OUT [--alpha-rank R]
+        [--alpha-depths D1,D2,... | --alpha-steps K] [--alpha-seed N]
+    python -m blutils_amd.cli blastn run-with-consensus ... (the same five)
+    python -m blutils_amd.cli blastn build-report [BLU_RESULT|-] --by-sample -o FILE --alpha-table OUT (the same four)
+
+not in the reference: alpha diversity and rarefaction curves.  OUT is
+`#sample depth reads observed singletons doubletons chao1 simpson shannon goods_coverage`, one line per sample; with a ladder
+(at most 32 depths: --depths, or --steps K for D_k = max(1, floor(k M / K)), M the largest sample total unless --max-depth says
+it), one line per sample and depth the sample reaches, over exactly the reads `build-distances --rarefy D --seed N` keeps at
+that depth — the curve is what D is picked from.  The sums are integers counted on the GPU (csrc/alpha_kernel.hip), Shannon's
+logarithm included (a fixed-point log2 with 24 fractional bits), and rendered with six decimals half up in integers, so the
+bytes do not depend on the machine.  The --alpha-table form runs the same call on the file --sample-table (build-report: -o)
+just wrote, after every other output.  To stderr: `diversity: F features at R, S samples, K depths, P rows`, and with a ladder
+`diversity: SAMPLE (TOTAL reads) reaches J of K depths` per sample that misses some.
+
     python -m blutils_amd.cli cache-db TAX.json CACHE [-u]
 
 writes the binary cache of a taxonomies file (not in the reference CLI; pass CACHE as -t afterwards).  
@@ -224,7 +241,7 @@ import functools
 import os
 import sys
 
-from . import _native, blast, distance, lineagedb, pipeline, report, seqdb, tabular, taxdb
+from . import _native, blast, distance, diversity, lineagedb, pipeline, report, seqdb, tabular, taxdb
 
 
 class _BlastnParser(argparse.ArgumentParser):
@@ -378,6 +395,27 @@ def build_parser() -> argparse.ArgumentParser:
         dst.add_argument("--distance-rarefy", metavar="D", type=_depth, help="build-distances --rarefy")
         dst.add_argument("--distance-seed", metavar="N", type=_seed, help="build-distances --seed; needs --distance-rarefy")
         dst.add_argument("--distance-rarefied-table", metavar="FILE", help="build-distances --rarefied-table; needs --distance-rarefy")
+    bdv = blastn.add_parser("build-diversity", help="sample table -> alpha diversity of its samples, raw or along a ladder of "
+                                                    "rarefaction depths, counted on the GPU (not in the reference)")
+    bdv.add_argument("table", help="a file written by --sample-table or build-report --by-sample")
+    bdv.add_argument("-o", "--output-file", required=True)
+    bdv.add_argument("--rank", metavar="R", help="collapse the rows at this rank, as build-distances --rank")
+    bdv.add_argument("--drop-unclassified", action="store_true", help="leave the unclassified and unplaced rows out")
+    bdv.add_argument("--depths", metavar="D1,D2,...", type=_depths, help="the ladder: at most 32 depths, strictly ascending")
+    bdv.add_argument("--steps", metavar="K", type=_steps, help="the ladder D_k = max(1, floor(k M / K)), k = 1 .. K, duplicates removed")
+    bdv.add_argument("--max-depth", metavar="M", type=_depth, help="the top of --steps' ladder (default: the largest sample total)")
+    bdv.add_argument("--seed", metavar="N", type=_seed, help="the seed of the draw, as build-distances --seed; needs a ladder")
+    bdv.add_argument("--device", type=int, default=0, help="HIP device ordinal")
+    for sp in (bc, rw, br):
+        alp = sp.add_argument_group("alpha diversity (not in the reference CLI)",
+                                    "the alpha diversity of the sample table just written, as build-diversity makes it")
+        alp.add_argument("--alpha-table", metavar="FILE",
+                         help="also write the alpha diversity of the samples to FILE; needs "
+                              + ("--by-sample and -o" if sp is br else "--sample-table"))
+        alp.add_argument("--alpha-rank", metavar="R", help="build-diversity --rank")
+        alp.add_argument("--alpha-depths", metavar="D1,D2,...", type=_depths, help="build-diversity --depths")
+        alp.add_argument("--alpha-steps", metavar="K", type=_steps, help="build-diversity --steps")
+        alp.add_argument("--alpha-seed", metavar="N", type=_seed, help="build-diversity --seed; needs --alpha-depths or --alpha-steps")
     bt = blastn.add_parser("build-tabular", help="blutils result document -> TSV")
     bt.add_argument("blu_result", nargs="?", default="-")
     bt.add_argument("-o", "--output-file")
@@ -587,6 +625,57 @@ def _seed(text: str) -> int:
     return v
 
 
+def _depths(text: str) -> list:
+    """argparse type of --depths: D1,D2,... strictly ascending, 1 .. 32 of them"""
+    try:
+        v = [_depth(t) for t in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError("the depths are whole numbers of reads separated by commas")
+    if len(v) > _native.ALPHA_MAX_DEPTHS:
+        raise argparse.ArgumentTypeError(f"at most {_native.ALPHA_MAX_DEPTHS} depths")
+    if any(a >= b for a, b in zip(v, v[1:])):
+        raise argparse.ArgumentTypeError("the depths ascend strictly")
+    return v
+
+
+def _steps(text: str) -> int:
+    """argparse type of --steps: 1 .. 32"""
+    v = int(text)
+    if not 1 <= v <= _native.ALPHA_MAX_DEPTHS:
+        raise argparse.ArgumentTypeError(f"the steps are a whole number, 1 .. {_native.ALPHA_MAX_DEPTHS}")
+    return v
+
+
+def _check_alpha_flags(ap, args, table) -> None:
+    """--alpha-table needs the table it reads; its companions need it, and the seed needs a ladder"""
+    needs = "--by-sample and -o" if args.sub == "build-report" else "--sample-table"
+    others = (args.alpha_rank, args.alpha_depths, args.alpha_steps, args.alpha_seed)
+    if args.alpha_table is None:
+        if any(v is not None for v in others):
+            ap.error("--alpha-rank, --alpha-depths, --alpha-steps and --alpha-seed need --alpha-table")
+        return
+    if table is None:
+        ap.error(f"--alpha-table needs {needs}: it reads the table that flag writes")
+    if args.alpha_depths is not None and args.alpha_steps is not None:
+        ap.error("--alpha-depths and --alpha-steps: one or the other")
+    if args.alpha_seed is not None and args.alpha_depths is None and args.alpha_steps is None:
+        ap.error("--alpha-seed needs --alpha-depths or --alpha-steps")
+
+
+def _diversity(table, out, rank, drop, device, depths, steps, max_depth, seed) -> None:
+    try:
+        st = diversity.build_diversity(table, out, rank, drop, device, depths, steps, max_depth, seed)
+    except _native.BluError as e:
+        raise SystemExit(str(e))
+    print("\n".join(diversity.summary(st)), file=sys.stderr)
+
+
+def _alpha_table(args, table, device=0) -> None:
+    """the alpha diversity of the table just written (after every other output)"""
+    if args.alpha_table is not None:
+        _diversity(table, args.alpha_table, args.alpha_rank, False, device, args.alpha_depths, args.alpha_steps, None, args.alpha_seed)
+
+
 def _rarefy_kwargs(depth, seed, table) -> dict:
     """build_distances' keyword arguments of a rarefaction; none without a depth, so that the call is the one it was"""
     return {} if depth is None else {"rarefy": depth, "seed": seed or 0, "rarefied_table": table}
@@ -678,6 +767,7 @@ def _run_with_consensus(ap, args) -> int:
     hit_filter, taxon_filter = _hit_filter(args), _taxon_filter(args)
     _check_count_table(args)
     _check_distance_flags(ap, args, args.sample_table)
+    _check_alpha_flags(ap, args, args.sample_table)
     try:
         blast.run_blast_and_build_consensus(args.query, args.tax_file, args.blast_out_file, args.blutils_out_file, config,
                                             blast.ExecuteBlastnProcRepository(args.blastn), args.force_overwrite,
@@ -697,6 +787,7 @@ def _run_with_consensus(ap, args) -> int:
         raise SystemExit(str(e))                                                       # (an unknown element: the library's message)
     _say_kept(stats, hit_filter is not None)
     _distance_matrix(args, args.sample_table, args.device)
+    _alpha_table(args, args.sample_table, args.device)
     return 0
 
 
@@ -724,8 +815,19 @@ def main(argv=None) -> int:
             raise SystemExit(str(e))
         print("\n".join([distance.summary(st)] + distance.rarefy_summary(st)), file=sys.stderr)
         return 0
+    if args.sub == "build-diversity":
+        if args.depths is not None and args.steps is not None:
+            ap.error("--depths and --steps: one or the other")
+        if args.max_depth is not None and args.steps is None:
+            ap.error("--max-depth needs --steps")
+        if args.seed is not None and args.depths is None and args.steps is None:
+            ap.error("--seed needs a ladder: --depths or --steps")
+        _diversity(args.table, args.output_file, args.rank, args.drop_unclassified, args.device, args.depths, args.steps, args.max_depth,
+                   args.seed)
+        return 0
     if args.sub == "build-report":
         _check_distance_flags(ap, args, args.output_file if args.by_sample else None)
+        _check_alpha_flags(ap, args, args.output_file if args.by_sample else None)
         try:
             if args.count_table is not None and args.weight == "size":
                 raise SystemExit("--count-table cannot be combined with --weight size: the counts are the table's")
@@ -737,6 +839,7 @@ def main(argv=None) -> int:
         except (tabular.TabularError, report.ReportError) as e:
             raise SystemExit(str(e))
         _distance_matrix(args, args.output_file)
+        _alpha_table(args, args.output_file)
         return 0
     if args.sub == "run-with-consensus":
         return _run_with_consensus(ap, args)
@@ -764,6 +867,7 @@ def main(argv=None) -> int:
         extra["min_cover"] = args.min_cover
     _check_count_table(args)
     _check_distance_flags(ap, args, args.sample_table)
+    _check_alpha_flags(ap, args, args.sample_table)
     if args.count_table is not None:
         extra["count_table"] = args.count_table
     if args.blast_outfmt is not None:
@@ -814,6 +918,7 @@ def main(argv=None) -> int:
         raise SystemExit(str(e))                                                       # (an unknown element: the library's message)
     _say_kept(stats, hit_filter is not None)
     _distance_matrix(args, args.sample_table, args.device)
+    _alpha_table(args, args.sample_table, args.device)
     return 0
 
 

@@ -2,7 +2,8 @@
 // CSR, the rendering of a distance matrix from the pair integers, and the chain of the two around blu_sample_distances.  The
 // file is small next to what precedes it in a run (one line per path); the pairwise pass is the device's (distance_kernel.hip).
 // With a depth the chain has a step more: the features are rarefied on the device first (rarefy_kernel.hip) and
-// the rarefied table is rendered here too.
+// the rarefied table is rendered here too.  `build-diversity` takes the same features to blu_sample_alpha
+// (alpha_kernel.hip) and renders its integers here.
 #include "pipeline_internal.h"
 
 namespace blu {
@@ -315,12 +316,147 @@ int rarefied_matrix(const blu_distance_features& ft, const blu_distance_desc& de
     return BLU_OK;
 }
 
+// num / den with six decimals, half up, in 128 bits; den > 0 (the quotient may pass 1: chao1)
+void six_decimals_wide(std::string& o, unsigned __int128 num, unsigned __int128 den) {
+    const unsigned __int128 q = (num * 1000000u + den / 2) / den;
+    char b[48];
+    const int n = snprintf(b, sizeof b, "%llu.%06llu", (unsigned long long)(q / 1000000u), (unsigned long long)(q % 1000000u));
+    o.append(b, (size_t)n);
+}
+
+int impossible(const char* name, uint64_t depth, const char* what) {
+    set_error("build-diversity: sample `%s` at depth %llu: %s: integers that cannot occur", name, (unsigned long long)depth, what);
+    return BLU_ERR_INVALID_ARG;
+}
+
+// the alpha file (include/blu_pipeline.h: blu_alpha_render); *rows = its lines after the header
+int alpha_text(const char* const* names, const uint64_t* reads, const uint64_t* depths, uint32_t n_depths, const blu_alpha& al, std::string& o,
+               uint64_t* rows) {
+    const uint64_t S = al.n_samples, NS = al.n_slots;
+    if (NS != (n_depths ? n_depths : 1u)) { set_error("build-diversity: %u slots do not go with %u depths", al.n_slots, n_depths); return BLU_ERR_INVALID_ARG; }
+    if (S && (!names || !reads || (n_depths && !depths) || !al.present || !al.n || !al.observed || !al.singletons || !al.doubletons || !al.sum_sq ||
+              !al.sum_xlog)) {
+        set_error("build-diversity: null argument");
+        return BLU_ERR_INVALID_ARG;
+    }
+    o = "#sample\tdepth\treads\tobserved\tsingletons\tdoubletons\tchao1\tsimpson\tshannon\tgoods_coverage\n";
+    *rows = 0;
+    for (uint64_t a = 0; a < S; ++a) {
+        for (uint64_t j = 0; j < NS; ++j) {
+            const uint64_t at = a * NS + j;
+            if (!al.present[at]) continue;
+            const uint64_t depth = n_depths ? depths[j] : reads[a];
+            const uint64_t n = al.n[at], obs = al.observed[at], f1 = al.singletons[at], f2 = al.doubletons[at];
+            const unsigned __int128 n2 = (unsigned __int128)n * n;
+            if (n >> 32) return impossible(names[a], depth, "n is 2^32 or more");
+            if (al.sum_sq[at] > n2) return impossible(names[a], depth, "sum_sq passes n^2");
+            if (f1 > n) return impossible(names[a], depth, "singletons pass n");
+            if (f1 + f2 > obs) return impossible(names[a], depth, "singletons and doubletons pass observed");
+            if (obs > n) return impossible(names[a], depth, "observed passes n");
+            o += names[a];
+            for (uint64_t v : {depth, reads[a], obs, f1, f2}) { o.push_back('\t'); o += std::to_string(v); }
+            o.push_back('\t');
+            const unsigned __int128 twice = 2 * ((unsigned __int128)f2 + 1);
+            six_decimals_wide(o, (unsigned __int128)obs * twice + (f1 ? (unsigned __int128)f1 * (f1 - 1) : 0), twice);
+            if (n == 0) { o += "\tnan\tnan\tnan\n"; ++*rows; continue; }
+            o.push_back('\t');
+            six_decimals_wide(o, n2 - al.sum_sq[at], n2);
+            o.push_back('\t');
+            const uint64_t whole = n * blu_alpha_log2(n);                 // (below 2^61)
+            six_decimals_wide(o, whole > al.sum_xlog[at] ? whole - al.sum_xlog[at] : 0, (unsigned __int128)n << 24);
+            o.push_back('\t');
+            six_decimals_wide(o, n - f1, n);
+            o.push_back('\n');
+            ++*rows;
+        }
+    }
+    return BLU_OK;
+}
+
+// features -> alpha integers -> the text, then the file
+int alpha_table(const char* table_path, const char* rank, uint32_t flags, int device, const char* out_path, const blu_alpha_options* opt,
+                blu_distance_features& ft, blu_alpha& al, blu_alpha_stats* stats) {
+    if (const int rc = blu_distance_features_from_table(table_path, rank, flags, &ft)) return rc;
+    const uint32_t S = ft.n_samples, K = opt ? opt->n_depths : 0u;
+    if (K) {
+        std::unordered_map<std::string_view, uint32_t> column_of;
+        for (uint32_t a = 0; a < S; ++a) {
+            const auto at = column_of.emplace(ft.sample_names[a], a);
+            if (!at.second) {
+                set_error("build-diversity: sample columns %u and %u are both named `%s`: a sample's draw goes by its name", at.first->second + 1, a + 1,
+                          ft.sample_names[a]);
+                return BLU_ERR_INVALID_ARG;
+            }
+        }
+    }
+    std::vector<uint64_t> stream(S), total(S, 0);
+    for (uint32_t a = 0; a < S; ++a) stream[a] = blu_rarefy_stream(opt ? opt->seed : 0, ft.sample_names[a], strlen(ft.sample_names[a]));
+    blu_alpha_desc ad{};
+    ad.struct_size = sizeof ad;
+    ad.device = device;
+    ad.n_features = ft.n_features;
+    ad.n_samples = S;
+    ad.n_depths = K;
+    ad.row_ptr = ft.row_ptr; ad.sample = ft.sample; ad.count = ft.count;
+    ad.sample_stream = stream.data();
+    ad.depths = K ? opt->depths : nullptr;
+    if (const int rc = blu_sample_alpha(&ad, &al)) return rc;
+    for (uint64_t e = 0; e < ft.row_ptr[ft.n_features]; ++e) total[ft.sample[e]] += ft.count[e];   // (no wrap: the call above checked)
+    if (K) {
+        uint32_t top = 0;
+        for (uint32_t a = 1; a < S; ++a) if (total[a] > total[top]) top = a;
+        if (total[top] < opt->depths[0]) {
+            set_error("build-diversity: no sample reaches the first depth %llu: the largest, `%s`, has %llu reads", (unsigned long long)opt->depths[0],
+                      ft.sample_names[top], (unsigned long long)total[top]);
+            return BLU_ERR_INVALID_ARG;
+        }
+    }
+    std::string text;
+    uint64_t rows = 0;
+    if (const int rc = alpha_text(ft.sample_names, total.data(), ad.depths, K, al, text, &rows)) return rc;
+    if (!write_text_file(out_path, text)) { set_error("cannot write %s", out_path); return BLU_ERR_IO; }
+    if (stats) *stats = blu_alpha_stats{ft.n_features, S, ft.row_ptr[ft.n_features], ft.n_dropped, K, rows, al.t_device_ms};
+    return BLU_OK;
+}
+
 }  // namespace
 }  // namespace blu
 
 using namespace blu;
 
 extern "C" {
+
+int blu_alpha_render(const char* const* names, const uint64_t* reads, const uint64_t* depths, uint32_t n_depths, const blu_alpha* integers,
+                     const char* out_path) {
+    if (!integers || !out_path) { set_error("build-diversity: null argument"); return BLU_ERR_INVALID_ARG; }
+    try {
+        std::string text;
+        uint64_t rows = 0;
+        if (const int rc = alpha_text(names, reads, depths, n_depths, *integers, text, &rows)) return rc;
+        if (!write_text_file(out_path, text)) { set_error("cannot write %s", out_path); return BLU_ERR_IO; }
+        return BLU_OK;
+    } catch (const std::bad_alloc&) { set_error("build-diversity: out of memory"); return BLU_ERR_ALLOC; }
+}
+
+int blu_alpha_table_file(const char* table_path, const char* rank, uint32_t flags, int device, const char* out_path,
+                         const blu_alpha_options* options, blu_alpha_stats* stats) {
+    if (!table_path || !out_path) { set_error("build-diversity: null argument"); return BLU_ERR_INVALID_ARG; }
+    if (options && options->struct_size != sizeof(blu_alpha_options)) {
+        set_error("build-diversity: options struct_size %llu is not one this library knows (%llu)", (unsigned long long)options->struct_size,
+                  (unsigned long long)sizeof(blu_alpha_options));
+        return BLU_ERR_INVALID_ARG;
+    }
+    if (options && options->n_depths && !options->depths) { set_error("build-diversity: depths is NULL"); return BLU_ERR_INVALID_ARG; }
+    blu_distance_features ft{};
+    blu_alpha al{};
+    struct Free {
+        blu_distance_features& f; blu_alpha& a;
+        ~Free() { blu_distance_features_free(&f); blu_alpha_free(&a); }
+    } guard{ft, al};
+    try {
+        return alpha_table(table_path, rank, flags, device, out_path, options, ft, al, stats);
+    } catch (const std::bad_alloc&) { set_error("build-diversity: out of memory"); return BLU_ERR_ALLOC; }
+}
 
 void blu_distance_features_free(blu_distance_features* ft) {
     if (!ft) return;

@@ -442,8 +442,25 @@ class DistanceStats2(C.Structure):
                                           "n_samples_dropped", "n_features_emptied", "n_reads_hashed")]
 
 
+class AlphaOptions(C.Structure):
+    """include/blu_pipeline.h: blu_alpha_options"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_depths", C.c_uint32), ("depths", C.POINTER(C.c_uint64)), ("seed", C.c_uint64)]
+
+
+class AlphaStats(C.Structure):
+    """include/blu_pipeline.h: blu_alpha_stats"""
+    _fields_ = [(f, C.c_uint64) for f in ("n_features", "n_samples", "n_nonzeros", "n_dropped", "n_depths", "n_rows")] + [("t_device_ms", C.c_double)]
+
+
 def _bind():
     L = N.lib()
+    if hasattr(L, "blu_alpha_table_file"):       # (an A/B library of an older build: BLU_CONSENSUS_LIB)
+        L.blu_alpha_render.restype = C.c_int
+        L.blu_alpha_render.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(N.Alpha),
+                                       C.c_char_p]
+        L.blu_alpha_table_file.restype = C.c_int
+        L.blu_alpha_table_file.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.c_int, C.c_char_p, C.POINTER(AlphaOptions),
+                                           C.POINTER(AlphaStats)]
     if hasattr(L, "blu_distance_matrix_file_with"):   # (an A/B library of an older build: BLU_CONSENSUS_LIB)
         L.blu_distance_matrix_file_with.restype = C.c_int
         L.blu_distance_matrix_file_with.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_int, C.c_char_p,
@@ -519,6 +536,24 @@ def distance_matrix_file_with(table_path: str, out_path: str, rank: Optional[str
     if rc != N.BLU_OK:
         raise N.BluError(rc, "blu_distance_matrix_file_with")
     return {f: int(getattr(st, f)) for f, _ in DistanceStats2._fields_}
+
+
+def alpha_table_file(table_path: str, out_path: str, rank: Optional[str] = None, drop_unclassified: bool = False, device: int = 0,
+                     depths=(), seed: int = 0, struct_size: Optional[int] = None) -> dict:
+    """blu_alpha_table_file: the features of a sample-table file at `rank`, the alpha integers of every sample counted on the GPU
+    (raw without depths, else at every depth of the ladder a sample reaches), the text written to out_path.  Returns
+    blu_alpha_stats."""
+    depths = [int(d) for d in depths]
+    arr = (C.c_uint64 * max(len(depths), 1))(*depths)
+    opt = AlphaOptions(struct_size=C.sizeof(AlphaOptions) if struct_size is None else struct_size, n_depths=len(depths), depths=arr,
+                       seed=int(seed))
+    st = AlphaStats()
+    rc = _bind().blu_alpha_table_file(table_path.encode(), None if rank is None else rank.encode(),
+                                      DISTANCE_DROP_UNCLASSIFIED if drop_unclassified else 0, int(device), out_path.encode(),
+                                      C.byref(opt), C.byref(st))
+    if rc != N.BLU_OK:
+        raise N.BluError(rc, "blu_alpha_table_file")
+    return {f: getattr(st, f) for f, _ in AlphaStats._fields_}
 
 
 def ingest_only(blast_output: str, taxonomies_file: str, use_taxid: bool = False, device: int = -1):

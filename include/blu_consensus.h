@@ -606,6 +606,63 @@ uint64_t blu_rarefy_stream(uint64_t seed, const char* name, uint64_t len);
 int blu_sample_rarefy(const blu_rarefy_desc* desc, blu_rarefied* out);
 void blu_rarefied_free(blu_rarefied* out);
 
+/* -------------------------------------------------------------------------- */
+/* Alpha diversity and rarefaction curves (additive, ABI v5; not in the reference).  The feature CSR of
+ * blu_distance_desc in; for every sample a and every depth D_j of a strictly ascending ladder (slot j) the integers that
+ * observed features, Chao1, Simpson, Shannon and Good's coverage are ratios of, taken over x'_fa(j) = exactly the kept count
+ * of blu_sample_rarefy at depth D_j with the same sample_stream: the subsamples of one sample at increasing depths are nested,
+ * so one pass over the reads serves every depth.  A slot with D_j > N_a is absent for that sample (present = 0, the integers 0).
+ * n_depths = 0 is the raw mode: one slot per sample, x' = x, every read kept.
+ *   blu_alpha_log2(x), 1 <= x: log2 x with 24 fractional bits, by squaring, all in u64 with a 128-bit product:
+ *     e = bit_length(x) - 1; m = x << (63 - e); frac = 0
+ *     for i = 1 .. 24: p = m * m; hi = p >> 64; if hi >= 2^63: m = hi, bit 24 - i of frac is set; else m = (p >> 63) mod 2^64
+ *     L = (e << 24) | frac                                   (never above log2 x * 2^24, less than 1 unit below it; L(0) = 0)
+ *   n = sum x'  (u64)   observed = #{x' > 0}   singletons = #{x' = 1}   doubletons = #{x' = 2}  (u32)
+ *   sum_sq = sum x'^2  (u64)   sum_xlog = sum x' * L(x')  (u64)          (a sample has below 2^32 reads: both fit)
+ * Counted on the device (csrc/alpha_kernel.hip): a radix select of all the ladder's thresholds at once, the level at which
+ * every read enters over tiles of BLU_ALPHA_TILE reads, then the six sums per (sample, slot); integers only, nothing depends on
+ * launch geometry or atomic order.  Before it returns the call checks that every present slot's n is D_j (raw: N_a):
+ * BLU_ERR_INTERNAL naming the sample and the depth otherwise. */
+#define BLU_ALPHA_MAX_DEPTHS 32u              /* n_depths above this is refused */
+#define BLU_ALPHA_TILE 8192u                  /* reads of one block of the level pass: 32 bit maps of it are 32 KB of LDS */
+typedef struct blu_alpha_desc {
+    uint32_t struct_size;          /* sizeof(blu_alpha_desc) */
+    int32_t device;                /* HIP device ordinal */
+    uint64_t n_features;           /* as in blu_distance_desc, and so are n_samples, row_ptr, sample and count */
+    uint32_t n_samples;
+    uint32_t n_depths;             /* 0 (raw) .. BLU_ALPHA_MAX_DEPTHS */
+    const uint64_t* row_ptr;
+    const uint32_t* sample;
+    const uint64_t* count;
+    const uint64_t* sample_stream; /* [n_samples] as in blu_rarefy_desc; not read in raw mode */
+    const uint64_t* depths;        /* [n_depths] each >= 1, strictly ascending */
+    void* stream;                  /* a hipStream_t the call waits for before it starts (NULL = default) */
+} blu_alpha_desc;                  /* 72 bytes */
+
+typedef struct blu_alpha {
+    uint32_t n_samples;
+    uint32_t n_slots;              /* n_depths, or 1 in raw mode */
+    uint8_t* present;              /* [n_samples * n_slots], sample-major as the next six: 1 where D_j <= N_a (raw: always) */
+    uint64_t* n;
+    uint32_t* observed;
+    uint32_t* singletons;
+    uint32_t* doubletons;
+    uint64_t* sum_sq;
+    uint64_t* sum_xlog;
+    double t_device_ms;            /* transpose, select, levels and sums on the device, by events; 0 when nothing was launched */
+} blu_alpha;                       /* every array malloc'd by the library: blu_alpha_free */
+
+uint64_t blu_alpha_log2(uint64_t x);
+
+/* Host arrays in, host arrays out; synchronous.  BLU_ERR_INVALID_ARG before any device is asked for: a struct_size the library
+ * does not know, whatever blu_sample_distances refuses about the CSR, n_depths above BLU_ALPHA_MAX_DEPTHS, a depth of 0, depths
+ * that do not strictly ascend (naming the position), with a ladder a NULL sample_stream or two samples with the same stream, a
+ * sample of 2^32 reads or more (naming it), more than BLU_RAREFY_MAX_READS reads in the samples that reach depths[0].  No sample
+ * reaching depths[0] is not an error here: every slot is absent and no device is asked for.  A device that cannot be used is
+ * BLU_ERR_NO_DEVICE: there is no CPU fallback. */
+int blu_sample_alpha(const blu_alpha_desc* desc, blu_alpha* out);
+void blu_alpha_free(blu_alpha* out);
+
 #ifdef __cplusplus
 }
 #endif

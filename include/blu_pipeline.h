@@ -660,6 +660,46 @@ typedef struct blu_distance_stats2 {
 int blu_distance_matrix_file_with(const char* table_path, const char* rank, int metric, uint32_t flags, int device, const char* out_path,
                                   const blu_distance_options* options, blu_distance_stats2* stats2);
 
+/* `blastn build-diversity` (not in the reference): alpha diversity of the samples of a sample-table file, raw or
+ * along a ladder of rarefaction depths.
+ *
+ * blu_alpha_render: the integers that include/blu_consensus.h's blu_sample_alpha counts, as text, on the host:
+ *   `#sample depth reads observed singletons doubletons chao1 simpson shannon goods_coverage` (tab-separated), then one line per
+ *   present (sample, slot), samples in their order, depths ascending.  depth = depths[j] (raw, n_depths = 0: reads[a]); reads =
+ *   reads[a] = N_a.  With F1 = singletons, F2 = doubletons and L = blu_alpha_log2:
+ *     chao1          = (observed * 2 (F2 + 1) + F1 (F1 - 1)) / (2 (F2 + 1))
+ *     simpson        = (n^2 - sum_sq) / n^2
+ *     shannon        = max(0, n L(n) - sum_xlog) / (n 2^24)          (bits; the clamp is part of the rule: L is truncated)
+ *     goods_coverage = (n - F1) / n
+ *   with six decimals, rounded half up in 128-bit integers as blu_distance_render does; `nan` where the denominator is 0.
+ *   BLU_ERR_INVALID_ARG for integers that cannot occur: n_slots that is not max(n_depths, 1), n of 2^32 or more, sum_sq > n^2,
+ *   F1 > n, F1 + F2 > observed, observed > n. */
+int blu_alpha_render(const char* const* names, const uint64_t* reads, const uint64_t* depths, uint32_t n_depths, const blu_alpha* integers,
+                     const char* out_path);
+
+typedef struct blu_alpha_options {
+    uint32_t struct_size;             /* sizeof(blu_alpha_options) */
+    uint32_t n_depths;                /* 0 = raw */
+    const uint64_t* depths;           /* [n_depths] */
+    uint64_t seed;                    /* not read in raw mode */
+} blu_alpha_options;                  /* 24 bytes */
+typedef struct blu_alpha_stats {
+    uint64_t n_features;              /* features kept */
+    uint64_t n_samples;
+    uint64_t n_nonzeros;
+    uint64_t n_dropped;               /* all-zero features of the table left out */
+    uint64_t n_depths;
+    uint64_t n_rows;                  /* lines of the file after the header */
+    double t_device_ms;
+} blu_alpha_stats;
+/* The three steps chained: the features of table_path at `rank` (as blu_distance_matrix_file takes them), blu_sample_alpha with
+ * sample_stream[a] = blu_rarefy_stream of the seed and column a's name, the text to out_path.  options NULL: raw.
+ * BLU_ERR_INVALID_ARG on top of what the steps refuse: a struct_size the library does not know, with a ladder two columns of
+ * one name (naming both) and no sample that reaches depths[0] (the message says the largest total).  Nothing is written unless
+ * every step succeeds. */
+int blu_alpha_table_file(const char* table_path, const char* rank, uint32_t flags, int device, const char* out_path,
+                         const blu_alpha_options* options, blu_alpha_stats* stats);
+
 /* CustomTaxon::from_file (domain/dtos/taxon.rs:28-66): .yaml or .json with the eight cutoff fields. */
 int blu_custom_taxon_from_file(const char* path, blu_cutoff_config* cfg);
 
